@@ -4,10 +4,12 @@
 Default line = "96 concurrent streams as 3 pipeline groups, inputs resident in HBM": a compute rate.  The same 16 frames per
 stream are re-processed every step from a reset pipeline (identical work per step, no upload in the timed region);
 `--workload kitti_stream` is the streaming figure (BASELINE configs[2]: 4541 frames through the host-pointer entry,
-upload included, 10-keyframe window, nothing reset).  The default line also carries `streaming` (the same lanes fed from host
+upload included, 10-keyframe window, nothing reset).  A plain run sets up, warms up, times `--steps` steps and prints the headline;
+with `--full` the default line also carries `streaming` (the same lanes fed from host
 memory through svo_pipeline_group_staging / _upload / _process_uploaded, upload timed), `single_stream`, `parity_self` (every
 lane of every timed step against the first step) and `parity_vs_cpu` (4 lanes of every group against the CPU oracle), and `other_workloads`
 (kitti_stream, ba50k sparse and dense, hd_1280x720_10k), each with its own roofline / cpu_baseline / parity record.
+`--dump-outputs DIR` writes the per-frame results of the last timed step (every stream, seeded inputs) as DIR/<name>.npy.
 
 A "step" = one pass of the whole hot path on every one of `--streams` (default 96) independent stereo streams that share the
 GPU — as `--groups` (default 3) pipeline groups (svo_pipeline_group_*: one host thread per group, one kernel launch per stage
@@ -22,7 +24,7 @@ N GPUs: the frame stream shards across ranks (rank r processes its own sequence 
 data-path collective — SURVEY §8e "front end / frames").  value = frames all ranks processed / max-over-
 ranks time.  The BA all-reduce path (config 4) is benchmarked with --workload ba50k.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (the front end's contract figure; the dominant
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, config); with `--full` it holds `roofline` (the front end's contract figure; the dominant
 kernel = ba_lm_kernel with live HIP-event duration and live algorithmic flops / bytes; the tracker on VALU issue) and `cpu_baseline` (oracle pipeline on the host cores, rank 0, N=1 only).
 """
 import argparse
@@ -63,13 +65,20 @@ def parse():
     ap.add_argument("--stagger-ms", type=float, default=0.0, help="group i starts its steps i x this many milliseconds after group 0 (inside the timed region)")
     ap.add_argument("--workload", default="kitti_cfg1", choices=["kitti_cfg1", "kitti_stream", "ba50k", "hd10k"])
     ap.add_argument("--frames", type=int, default=4541, help="kitti_stream: length of the stream (KITTI 00 has 4541 frames)")
-    ap.add_argument("--profile-kernel", default="lk_fb", help="kernel timed with HIP events for the roofline object")
+    ap.add_argument("--profile-kernel", default="lk_fb", help="kernel timed with HIP events for the roofline object (--full)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline as well: single-stream and host-fed figures, CPU "
+                    "baselines, parity legs, rooflines, the other BASELINE workloads (the --no-* options below leave parts out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-single", action="store_true", help="skip the single-stream measurement (profiling runs)")
     ap.add_argument("--no-streaming", action="store_true", help="default line only: skip the host-fed (PCIe upload timed) variant of the same lanes")
     ap.add_argument("--no-other-workloads", action="store_true", help="default line only: skip the driver-timed figures of BASELINE configs[2..4]")
     ap.add_argument("--cpu-frames", type=int, default=16)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed path returned in its last step as "
+                    "DIR/<name>.npy (float32 / float64; rank 0; bench_outputs/ is git-ignored)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def dist_setup(n):
@@ -145,6 +154,28 @@ def cpu_baseline(p, L, R, frames):
 
 
 RES_KEY = lambda r: (r.n_detected, r.n_tracked, r.n_inliers, r.n_new, r.is_keyframe, r.ba_iterations, list(r.pose7))
+FRAME_FIELDS = ("n_detected", "n_tracked", "n_inliers", "n_new", "is_keyframe", "av_parallax", "percent_lost", "ba_iterations")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def frame_outputs(lanes):
+    """What a caller receives per frame (svo_frame_result) as arrays over (lane, frame): the counters in float64 (exact), av_parallax and
+    percent_lost in float32 (as the library stores them), pose7 (qw qx qy qz tx ty tz) in float64."""
+    out = {f: np.array([[getattr(r, f) for r in lane] for lane in lanes], np.float32 if f in ("av_parallax", "percent_lost") else np.float64)
+           for f in FRAME_FIELDS}
+    out["pose7"] = np.array([[list(r.pose7) for r in lane] for lane in lanes], np.float64).reshape(len(lanes), -1, 7)
+    return out
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than the {DUMP_LIMIT_BYTES} allowed")
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def run_threads(fns):
@@ -331,9 +362,10 @@ def run_kitti(args):
     NG = max(0, min(args.groups, NS))
     group_lines(NG)
     single_pipe = None
+    want_single = args.full and NS > 1 and not args.no_single
     if NG > 0:  # pipeline groups: NG host threads, the streams dealt round-robin
         streams = [_Group(S, torch, local, seeds[gi::NG], B) for gi in range(NG)]
-        if NS > 1 and not args.no_single:
+        if want_single:
             single_pipe = _Stream(S, torch, local, seeds[0], B)
     else:
         streams = [_Stream(S, torch, local, sd, B) for sd in seeds]
@@ -357,7 +389,7 @@ def run_kitti(args):
     run_steps(args.warmup)
     # single-stream rate (latency-bound: one sequential VO chain) measured first, in the same run
     single = None
-    if NS > 1 and not args.no_single:
+    if want_single:
         one = single_pipe if single_pipe is not None else streams[0]
         for _ in range(max(1, args.warmup)):
             one.step()
@@ -370,13 +402,14 @@ def run_kitti(args):
         dts = time.perf_counter() - t0
         single = {"value": B * n_single / dts, "unit": "frames/s", "ms_per_step": 1e3 * dts / n_single, "steps": n_single,
                   "note": "one stream alone on the GPU (per rank)"}
-    ctx.profile_select(args.profile_kernel)
-    if NG > 1:
-        streams[1].ctx.profile_select("ba_step")  # the solve launches of the second group, timed live as well (HIP events on its solve lines)
+    if args.full:  # HIP events around the profiled launches, inside the timed region
+        ctx.profile_select(args.profile_kernel)
+        if NG > 1:
+            streams[1].ctx.profile_select("ba_step")  # the solve launches of the second group, timed live as well (HIP events on its solve lines)
     for st in streams:
         if hasattr(st, "clear_counters"):
             st.clear_counters()
-    if NG > 1:
+    if args.full and NG > 1:
         streams[1].pipe.solve_work(reset=True)
     barrier_sync(torch, dist, ctx)
     cpu0 = time.process_time()
@@ -387,13 +420,18 @@ def run_kitti(args):
     barrier_sync(torch, dist, ctx)
     dt = time.perf_counter() - t0
     host_cores = (time.process_time() - cpu0) / dt  # CPU time of all threads of this rank over the timed region
-    k_ms, k_n = ctx.profile_read()
-    ctx.profile_select(None)
-    ba_ms, ba_n, ba_work = 0.0, 0, None
-    if NG > 1:
-        ba_ms, ba_n = streams[1].ctx.profile_read()
-        streams[1].ctx.profile_select(None)
-        ba_work = streams[1].pipe.solve_work()
+    if args.dump_outputs and rank == 0:
+        # every stream's results of the last timed step, in stream (seed) order: stream i is lane i // NG of group i % NG
+        lanes = [streams[i % NG].all_res[i // NG] for i in range(NS)] if NG else [st.res for st in streams]
+        dump_outputs(args.dump_outputs, frame_outputs(lanes))
+    k_ms, k_n, ba_ms, ba_n, ba_work = 0.0, 0, 0.0, 0, None
+    if args.full:
+        k_ms, k_n = ctx.profile_read()
+        ctx.profile_select(None)
+        if NG > 1:
+            ba_ms, ba_n = streams[1].ctx.profile_read()
+            streams[1].ctx.profile_select(None)
+            ba_work = streams[1].pipe.solve_work()
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -419,38 +457,39 @@ def run_kitti(args):
         out["single_stream"] = single
     out["config"]["label"] = (f"{NS} concurrent stream(s) per GPU" + (f" as {NG} pipeline group(s), one host thread each" if NG else ", one host thread each") +
                               f", inputs resident in HBM (same {B} frames per step from a reset pipeline)")
-    # roofline: (a) the SURVEY 8(d) contract figure of the whole front end, (b) the dominant kernel on the resource
-    # that binds it (HIP events on the library's stream over the timed region + the committed SQ counter pass)
-    avg_us = 1e3 * k_ms / k_n if k_n > 0 else None
-    lanes_per_launch = 1.0
-    g0_stats = streams[0].stats_sum if NG else None  # summed over the timed region
-    if g0_stats and g0_stats.get("track", [0, 0])[0]:
-        lanes_per_launch = g0_stats["track"][1] / g0_stats["track"][0]
-    out["roofline"] = front_end_roofline(frames / dt / world, args.profile_kernel, avg_us, res, k_n, lanes_per_launch, bool(NG))
-    share = profile_summary()
-    if share and share.get("valu_wave_instructions_per_frame"):
-        # the resource the whole path comes closest to: wave-level VALU instructions of every kernel per stereo frame (committed
-        # SQ_INSTS_VALU pass of this workload, profiles/r05_sq_counters.txt) x this run's frames/s against the chip's VALU issue rate
-        vpf = float(share["valu_wave_instructions_per_frame"])
-        g = vpf * (frames / dt / world) / 1e9
-        byk = share.get("valu_wave_instructions_per_frame_by_kernel") or {}
-        lk = float(sum(v for k, v in byk.items() if k.startswith("lk_fb")))
-        # SIMD cycles: the tracker's iteration is 81 half-rate (4.3 cycles) + 51 full-rate (2.5) instructions = 3.6 cycles per instruction
-        # (tools/exp/issue_rate.hip on this GPU, profiles/r05_exp_issue_rate.txt, and the kernel's ISA); the other kernels at the mid-point 3.4
-        simd_cycles_per_frame = lk * VALU_CYCLES_TRACKER_MIX + (vpf - lk) * VALU_CYCLES_OTHER_KERNELS
-        ceiling = 256 * 4 * 2.4e9 / simd_cycles_per_frame
-        out["roofline"]["chip_valu_issue"] = {
-            "bound": "valu_issue", "valu_wave_instructions_per_frame": vpf, "by_kernel_per_frame": byk,
-            "achieved_ginstr_s": g, "peak_ginstr_s": VALU_ISSUE_PEAK_GINSTR, "frac_of_full_rate_issue": g / VALU_ISSUE_PEAK_GINSTR,
-            "simd_cycles_per_frame": simd_cycles_per_frame, "frames_per_s_if_every_simd_computed_all_the_time": ceiling,
-            "frac": (frames / dt / world) / ceiling,
-            "note": "per GPU; every kernel of the path together (the tracker ~70 %); full-rate peak = 256 CUs x 4 SIMDs x 2.4 GHz / 2 cycles per wave64 "
-                    "instruction, but 60 % of the tracker's instructions are half-rate on gfx950: frac prices them at their measured cost"}
-    if share:
-        out["kernel_time_share"] = {"source": "profiles/r05_kernel_stats_*.csv (rocprofv3 --kernel-trace --stats of this command)",
-                                    "default_percent": share.get("kernel_time_share_default"),
-                                    "1_stream_percent": share.get("kernel_time_share_1_stream")}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        # roofline: (a) the SURVEY 8(d) contract figure of the whole front end, (b) the dominant kernel on the resource
+        # that binds it (HIP events on the library's stream over the timed region + the committed SQ counter pass)
+        avg_us = 1e3 * k_ms / k_n if k_n > 0 else None
+        lanes_per_launch = 1.0
+        g0_stats = streams[0].stats_sum if NG else None  # summed over the timed region
+        if g0_stats and g0_stats.get("track", [0, 0])[0]:
+            lanes_per_launch = g0_stats["track"][1] / g0_stats["track"][0]
+        out["roofline"] = front_end_roofline(frames / dt / world, args.profile_kernel, avg_us, res, k_n, lanes_per_launch, bool(NG))
+        share = profile_summary()
+        if share and share.get("valu_wave_instructions_per_frame"):
+            # the resource the whole path comes closest to: wave-level VALU instructions of every kernel per stereo frame (committed
+            # SQ_INSTS_VALU pass of this workload, profiles/r05_sq_counters.txt) x this run's frames/s against the chip's VALU issue rate
+            vpf = float(share["valu_wave_instructions_per_frame"])
+            g = vpf * (frames / dt / world) / 1e9
+            byk = share.get("valu_wave_instructions_per_frame_by_kernel") or {}
+            lk = float(sum(v for k, v in byk.items() if k.startswith("lk_fb")))
+            # SIMD cycles: the tracker's iteration is 81 half-rate (4.3 cycles) + 51 full-rate (2.5) instructions = 3.6 cycles per instruction
+            # (tools/exp/issue_rate.hip on this GPU, profiles/r05_exp_issue_rate.txt, and the kernel's ISA); the other kernels at the mid-point 3.4
+            simd_cycles_per_frame = lk * VALU_CYCLES_TRACKER_MIX + (vpf - lk) * VALU_CYCLES_OTHER_KERNELS
+            ceiling = 256 * 4 * 2.4e9 / simd_cycles_per_frame
+            out["roofline"]["chip_valu_issue"] = {
+                "bound": "valu_issue", "valu_wave_instructions_per_frame": vpf, "by_kernel_per_frame": byk,
+                "achieved_ginstr_s": g, "peak_ginstr_s": VALU_ISSUE_PEAK_GINSTR, "frac_of_full_rate_issue": g / VALU_ISSUE_PEAK_GINSTR,
+                "simd_cycles_per_frame": simd_cycles_per_frame, "frames_per_s_if_every_simd_computed_all_the_time": ceiling,
+                "frac": (frames / dt / world) / ceiling,
+                "note": "per GPU; every kernel of the path together (the tracker ~70 %); full-rate peak = 256 CUs x 4 SIMDs x 2.4 GHz / 2 cycles per wave64 "
+                        "instruction, but 60 % of the tracker's instructions are half-rate on gfx950: frac prices them at their measured cost"}
+        if share:
+            out["kernel_time_share"] = {"source": "profiles/r05_kernel_stats_*.csv (rocprofv3 --kernel-trace --stats of this command)",
+                                        "default_percent": share.get("kernel_time_share_default"),
+                                        "1_stream_percent": share.get("kernel_time_share_1_stream")}
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cb, ores = cpu_baseline(streams[0].p, streams[0].L, streams[0].R, args.cpu_frames)
         out["cpu_baseline"] = cb
         m = min(len(ores), len(res))
@@ -473,9 +512,10 @@ def run_kitti(args):
         if NG > 0:
             out["parity_vs_cpu"].update(group_parity_vs_cpu(streams, B, ores))
     if NG > 0:
-        out["parity_self"] = group_self_parity(streams, B)
         launches_sum = {k: list(v) for k, v in streams[0].stats_sum.items()}
-    if NG > 0 and not args.no_streaming:
+    if args.full and NG > 0:
+        out["parity_self"] = group_self_parity(streams, B)
+    if args.full and NG > 0 and not args.no_streaming:
         # the same lanes fed from host memory: every step uploads its batch over PCIe (pinned staging slots of the groups,
         # the upload of step s+1 overlapped with the processing of step s); results must equal the resident ones bit for bit
         resident_raw = [g.raws[0] if g.raws else None for g in streams]
@@ -639,10 +679,13 @@ def run_kitti_stream(args):
                       "ba_lm_iterations": int(sum(r.ba_iterations for r in res_all)),
                       "ate_rmse_m_at_keyframes_vs_generator": ate, "path_length_m": path,
                       "pcie_bytes_per_step": 2 * B * W * H}}
-    out["roofline"] = front_end_roofline(frames / dt / world, args.profile_kernel, None, res_all, 0)
-    if (SMAXC, SQUAL, SMIND, SMAXF, window) == (2800, 0.004, 7.0, 3300, 10):  # = tests/stream_configs.py "kitti_bench"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, frame_outputs([res_all[(steps - 1) * B:]]))
+    if args.full:
+        out["roofline"] = front_end_roofline(frames / dt / world, args.profile_kernel, None, res_all, 0)
+    if args.full and (SMAXC, SQUAL, SMIND, SMAXF, window) == (2800, 0.004, 7.0, 3300, 10):  # = tests/stream_configs.py "kitti_bench"
         out["parity_vs_oracle_fixture"] = fixture_parity("kitti_bench", res_all, rank)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as O
         cores = min(os.cpu_count() or 1, 16)
@@ -719,11 +762,14 @@ def run_hd10k(args):
                       "mean_tracked": float(np.mean([r.n_tracked for r in res if r.n_tracked] or [0])),
                       "mean_detected": float(np.mean([r.n_detected for r in res])),
                       **{k: v for k, v in window_load([r for r in res if r.is_keyframe], 10).items() if k != "mean_detected"},
-                      "ba_lm_iterations": int(sum(r.ba_iterations for r in res)), "fps_vs_60": n_frames / dt / 60.0},
-           "roofline": {"bound": "hbm", "kernel": "whole front end per stereo pair (6.33 A bytes, SURVEY 8d)", "achieved": gbs, "peak": HBM_PEAK_GBS,
-                        "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS, "algorithmic_bytes_per_pair": 6.33 * A, "traffic": None}}
-    out["parity_vs_oracle_fixture"] = fixture_parity("hd10k", res, rank)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+                      "ba_lm_iterations": int(sum(r.ba_iterations for r in res)), "fps_vs_60": n_frames / dt / 60.0}}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, frame_outputs([res[-B:]]))
+    if args.full:
+        out["roofline"] = {"bound": "hbm", "kernel": "whole front end per stereo pair (6.33 A bytes, SURVEY 8d)", "achieved": gbs, "peak": HBM_PEAK_GBS,
+                           "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS, "algorithmic_bytes_per_pair": 6.33 * A, "traffic": None}
+        out["parity_vs_oracle_fixture"] = fixture_parity("hd10k", res, rank)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as O
         cores = min(os.cpu_count() or 1, 16)
@@ -764,6 +810,8 @@ def other_workloads(args):
         except Exception as e:  # a sub-workload must never take the headline down with it
             out[name] = {"error": f"{type(e).__name__}: {e}", "wall_s": round(time.perf_counter() - t0, 1)}
 
+    args = copy.copy(args)
+    args.dump_outputs = None  # --dump-outputs holds the headline's outputs
     a = copy.copy(args)
     a.batch, a.cpu_frames = 16, 12
     sub("kitti_stream_4541_frames", lambda: run_kitti_stream(a))
@@ -907,7 +955,7 @@ def main():
         sys.exit(2)
     if args.workload == "kitti_cfg1":
         out = run_kitti(args)
-        if out is not None and world == 1 and not args.no_other_workloads:
+        if out is not None and world == 1 and args.full and not args.no_other_workloads:
             out["other_workloads"] = other_workloads(args)
     elif args.workload == "hd10k":
         out = run_hd10k(args)

@@ -34,11 +34,11 @@ def test_bench_refuses_a_world_size_that_is_not_gpus():
 def test_bench_spawner_counts_gpus_without_hip_and_starts_the_ranks():
     """`bench.py --gpus N` without a launcher: the parent counts GPUs WITHOUT the HIP runtime (here: the stub
     SVO_BENCH_GPU_COUNT, on a box: *_VISIBLE_DEVICES / the KFD topology in sysfs), refuses to fork + exec from a process that
-    has libamdhip64 mapped, and starts the ranks with torch.distributed.run.  In this GPU-less container the two ranks come
-    up, rendezvous over gloo and then fail at svo_create (no device): what is checked is that the spawner got that far and
-    relayed the failure, never a line measured on fewer ranks."""
+    has libamdhip64 mapped, and starts the ranks with torch.distributed.run.  The two ranks come up, rendezvous over gloo and
+    then fail at svo_create: they are forced onto device 64, which no machine has (with device 0 they would run on a GPU box):
+    what is checked is that the spawner got that far and relayed the failure, never a line measured on fewer ranks."""
     r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--workload", "ba50k"],
-             env={"SVO_BENCH_GPU_COUNT": "2", "SVO_BENCH_BACKEND": "gloo", "SVO_BENCH_FORCE_DEVICE": "0"})
+             env={"SVO_BENCH_GPU_COUNT": "2", "SVO_BENCH_BACKEND": "gloo", "SVO_BENCH_FORCE_DEVICE": "64"})
     assert r.returncode != 0
     assert "2-rank run failed" in r.stderr and '"metric"' not in r.stdout
     assert "HIP runtime mapped" not in r.stderr

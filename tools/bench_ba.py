@@ -171,14 +171,18 @@ def run(args, cpu_seconds=12.0):
     ws = wb.solve_problem()
     wb.close()
     ba.load_problem(p["poses0"], pts, op, oj, uv)
-    ctx.profile_select("ba_linearize")
+    if args.full:
+        ctx.profile_select("ba_linearize")
     bench.barrier_sync(torch, dist, ctx)
     t0 = time.perf_counter()
     s = ba.solve_problem()
     bench.barrier_sync(torch, dist, ctx)
     dt = time.perf_counter() - t0
-    k_ms, k_n = ctx.profile_read()
+    k_ms, k_n = ctx.profile_read() if args.full else (0.0, 0)
     st = ba.last_stats()
+    if args.dump_outputs and rank == 0:
+        poses, points = ba.read_problem()  # this rank's landmarks
+        bench.dump_outputs(args.dump_outputs, {"poses": poses, "points": points, "final_cost": np.array([s.final_cost])})
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -225,7 +229,7 @@ def run(args, cpu_seconds=12.0):
                                    "launch time; peaks measured on this card by svo_measure_peak; the kernel's parity-exact "
                                    "residual/Jacobian part issues separate f64 multiply and add (f64_muladd row), only the "
                                    "Schur products run on the matrix pipe"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not emu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not emu:
         out["cpu_baseline"], sub = cpu_baseline(p, K, cpu_seconds)
         out["parity_vs_cpu"] = parity_vs_cpu(S, ctx, p, K, sub, acc_mode)
     ba.close()

@@ -13,13 +13,13 @@ cd "$GRAFT_REPO_ROOT"
 # caller passes the commit, tools/prof_round.sh <tag> <commit>), together with the library's own build stamp
 echo "commit ${2:-unknown}; libsvo_hip.so sha256 $(sha256sum stereo_vo_amd/libsvo_hip.so | cut -c1-16); $(date -u +%Y-%m-%dT%H:%MZ)" > "$OUT/STAMP.txt"
 echo "[1/5] kernel trace, default bench"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/s8" -o p -- python3 bench.py --no-cpu-baseline --no-other-workloads --no-single --no-streaming > "$OUT/bench_s8.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/s8" -o p -- python3 bench.py --full --no-cpu-baseline --no-other-workloads --no-single --no-streaming > "$OUT/bench_s8.log" 2>&1
 grep '^{"metric"' "$OUT/bench_s8.log" | tail -1 > "$OUT/bench_s8.json"
 python3 tools/gpu_busy.py "$OUT/s8/p_kernel_trace.csv" 100 > "$OUT/gpu_busy_s8.txt" || true
 python3 tools/trace_by_grid.py "$OUT/s8/p_kernel_trace.csv" > "$OUT/by_grid_s8.txt" || true
 rm -f "$OUT/s8/p_kernel_trace.csv"
 echo "[2/5] kernel trace, single stream"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/s1" -o p -- python3 bench.py --no-cpu-baseline --no-other-workloads --streams 1 --groups 0 > "$OUT/bench_s1.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/s1" -o p -- python3 bench.py --full --no-cpu-baseline --no-other-workloads --streams 1 --groups 0 > "$OUT/bench_s1.log" 2>&1
 grep '^{"metric"' "$OUT/bench_s1.log" | tail -1 > "$OUT/bench_s1.json"
 python3 tools/trace_by_grid.py "$OUT/s1/p_kernel_trace.csv" > "$OUT/by_grid_s1.txt" || true
 rm -f "$OUT/s1/p_kernel_trace.csv"
@@ -33,7 +33,7 @@ for C in FETCH_SIZE WRITE_SIZE; do
   rm -f "$OUT/$C/p_kernel_trace.csv"
 done
 echo "[5/5] kernel trace, ba50k"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/ba" -o p -- python3 bench.py --workload ba50k --steps 30 --warmup 5 --no-cpu-baseline > "$OUT/bench_ba.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/ba" -o p -- python3 bench.py --full --workload ba50k --steps 30 --warmup 5 --no-cpu-baseline > "$OUT/bench_ba.log" 2>&1
 grep '^{"metric"' "$OUT/bench_ba.log" | tail -1 > "$OUT/bench_ba.json"
 rm -f "$OUT/ba/p_kernel_trace.csv"
 echo "[6/6] f64 MFMA counters, ba50k"

@@ -6,7 +6,7 @@ OUT=gpurun_out/r5_sweep_a.txt
 run() {  # label, env..., -- bench args
   label="$1"; shift
   envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  env "${envs[@]}" timeout -k 10 240 python bench.py --no-cpu-baseline --no-other-workloads --no-single --no-streaming "$@" > gpurun_out/r5_sweep_tmp.log 2>&1
+  env "${envs[@]}" timeout -k 10 240 python bench.py --full --no-cpu-baseline --no-other-workloads --no-single --no-streaming "$@" > "$(dirname "$OUT")"/r5_sweep_tmp.log 2>&1
   rc=$?
   v=$(grep -o '"value": [0-9.]*' gpurun_out/r5_sweep_tmp.log | head -1)
   p=$(grep -o '"lane_steps_that_differ_from_step_0": [0-9]*' gpurun_out/r5_sweep_tmp.log | head -1)

@@ -6,7 +6,7 @@ OUT=gpurun_out/r5_sweep_l.txt
 full() {
   label="$1"; shift
   envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  env "${envs[@]}" timeout -k 10 420 python bench.py --no-cpu-baseline "$@" > gpurun_out/r5_full_tmp.log 2>&1
+  env "${envs[@]}" timeout -k 10 420 python bench.py --full --no-cpu-baseline "$@" > "$(dirname "$OUT")"/r5_full_tmp.log 2>&1
   rc=$?
   python3 - "$label" $rc >> $OUT <<'PY'
 import json, sys

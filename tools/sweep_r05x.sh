@@ -11,7 +11,7 @@ if [ $rc -ne 0 ]; then echo "tests failed: no bench" | tee -a $OUT; exit 1; fi
 run() {
   label="$1"; shift
   envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  env "${envs[@]}" timeout -k 10 280 python bench.py --no-other-workloads --no-single --no-cpu-baseline "$@" > gpurun_out/r5_sweep_tmp.log 2>&1
+  env "${envs[@]}" timeout -k 10 280 python bench.py --full --no-other-workloads --no-single --no-cpu-baseline "$@" > "$(dirname "$OUT")"/r5_sweep_tmp.log 2>&1
   rc=$?
   v=$(grep -o '"value": [0-9.]*' gpurun_out/r5_sweep_tmp.log | head -1)
   sv=$(grep -o '"streaming": {"value": [0-9.]*' gpurun_out/r5_sweep_tmp.log | head -1)
