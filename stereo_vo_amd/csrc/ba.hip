@@ -1784,6 +1784,8 @@ struct LmDevArgs {
   LmDevOpt opt;
   unsigned* dbg;            // per workgroup 16 words: its last command (diagnostics of a solve that gave up; null: none)
   int test_giveup;          // test hook (SVO_BA_TEST_GIVEUP): the wide launch reports "gave up" at once, as if a bounded wait had run out
+  int wave_chunks;          // chunks every wavefront takes in turn (1: ba_lm_kernel / ba_lm_grouped_kernel; 2-4: ba_lm_multi_kernel)
+  int wave_contig;          // ba_lm_multi_kernel: a wavefront's chunks are neighbours (1) or one per stride of 2 x workgroups (0)
 };
 enum { LMC_ARRIVE = 0, LMC_WORDS = 16 };
 enum { LMR_ITERATIONS = 0, LMR_SUCCESSFUL, LMR_TERMINATION, LMR_INITIAL_COST, LMR_FINAL_COST, LMR_LINEARIZE_CALLS, LMR_STEP_CALLS, LMR_SEL,
@@ -1811,14 +1813,17 @@ constexpr double LM_MIN_RADIUS = 1e-32, LM_MAX_RADIUS = 1e16;
 __host__ __device__ static inline size_t ba_lm_ctl_doubles(int n, int K) { return (size_t)n * n + 3 * (size_t)n + 2 + 4 * (size_t)(n > 0 ? n : 1) + (size_t)(n > 0 ? n : 1) + 14 * (size_t)K + 21 * (size_t)(K > 1 ? K - 1 : 1) + 8; }
 // dynamic LDS of ba_lm_kernel (doubles): [staging rows + landmark scalars of CPW wavefronts | controller workspace] (union) |
 // chunk tables | Jacobi scales of the pose columns | step block [dc | candidate poses | current poses]
+// A workgroup is LM_CPW wavefronts; each takes `kw` chunks in turn (ba_lm_multi_kernel; kw = 1: ba_lm_kernel, one chunk per wavefront).
 constexpr int LM_CPW = 2;
+constexpr int LM_MAX_WAVE_CHUNKS = 4;
+__host__ __device__ static inline int ba_lm_blocks(int C, int kw) { return (C + LM_CPW * kw - 1) / (LM_CPW * kw); }  // workgroups of a wide solve
 __host__ __device__ static inline int ba_wire_elements(int K) { const int F = K - 1; return 18 * F * (F + 1) + 33 * F + 2; }
 __host__ __device__ static inline size_t ba_lm_union_doubles(int n, int K) { const size_t a = (size_t)LM_CPW * (size_t)wg_lds_doubles(ba_wire_elements(K)), b = ba_lm_ctl_doubles(n, K); return a > b ? a : b; }
-__host__ __device__ static inline size_t ba_lm_lds_doubles(int n, int K, int tab_words /* per wavefront, a multiple of 4, <= TAB_LDS_WORDS */) {
-  // behind the union and the tables: Jacobi scales (nn) | spare (nn) | step block [dc (nn) | candidate poses (7 K) | current poses (7 K)] — the kernel's
+__host__ __device__ static inline size_t ba_lm_lds_doubles(int n, int K, int tab_words /* per chunk, a multiple of 4, <= TAB_LDS_WORDS */, int kw = 1) {
+  // behind the union and the kw tables of every wavefront: Jacobi scales (nn) | spare (nn) | step block [dc (nn) | candidate poses (7 K) | current poses (7 K)] — the kernel's
   // carve-up (cSc, sStep).  (Until the end of round 4 this said 2 nn: the current poses' tail lay nn doubles beyond the allocation, inside the
   // allocation granule for the 5-keyframe window and outside it from n = 36 on — NaN poses, found when larger windows first took this kernel.)
-  return ba_lm_union_doubles(n, K) + (size_t)LM_CPW * (size_t)tab_words / 4 + 3 * (size_t)(n > 0 ? n : 1) + 14 * (size_t)K;
+  return ba_lm_union_doubles(n, K) + (size_t)LM_CPW * (size_t)kw * (size_t)tab_words / 4 + 3 * (size_t)(n > 0 ? n : 1) + 14 * (size_t)K;
 }
 
 // wire total e -> its place in the payload image (cP) or the U triangles (cU)
@@ -1908,11 +1913,12 @@ __device__ __forceinline__ bool lm_fetch_totals(double* cP, double* cU, const do
 // [dc | candidate poses | current poses] in sStep and its parameters in cs; returns an LMOP_* code.
 // LOCAL (ba_lm_compact_kernel: ONE workgroup runs the whole solve): the summed payloads are not collected from granules, they sit in
 // the workgroup's LDS — `tot` (E wire totals) and `tot2` (pass B's four sums); cs.elapsed is set by the caller from its own clock.
-template <bool LOCAL, bool GROUPED = false>
+// MULTI: ba_lm_multi_kernel (a.wave_chunks chunks per wavefront: fewer workgroups per solve).
+template <bool LOCAL, bool GROUPED = false, bool MULTI = false>
 __device__ __attribute__((noinline)) int lm_controller(const BaDev& P, const LmDevArgs& a, LmDevState& cs, double* cl, double* cSc, double* sStep, double* sOut4,
                                                         const double* tot = nullptr, const double* tot2 = nullptr) {
   const int tid = threadIdx.x, nt = blockDim.x, n = P.n, K = P.K, nn = n > 0 ? n : 1;
-  const int grid = LOCAL ? 1 : (P.C + LM_CPW - 1) / LM_CPW;  // workgroups of THIS solve (the launch may hold several solves)
+  const int grid = LOCAL ? 1 : ba_lm_blocks(P.C, MULTI ? a.wave_chunks : 1);  // workgroups of THIS solve (the launch may hold several solves)
   const int pay1 = n * n + 3 * n + 2;
   double* cP = cl;             // payload image [S | g_red | g_c | diag U | cost | sum g_p^2]; S becomes the scaled system, then L
   double* cDf = cP + pay1;
@@ -2306,13 +2312,111 @@ __device__ __forceinline__ bool lm_iterate(const BaDev& P, const LmDevArgs& a, L
   return ok;
 }
 
+// The chunks a wavefront of ba_lm_multi_kernel takes in turn: first, first + stride, ... (`count` of them lie below C).  Strided
+// (default): slot s = 2 x workgroup + wavefront takes s, s + S, s + 2 S, ... with S = 2 x workgroups, so neighbouring chunks — the
+// slow ones (a chunk of brand-new landmarks of the newest pose) come in runs — land on different wavefronts; contiguous: the
+// workgroup's own 2 kw chunks, alternating between its two wavefronts.
+struct LmTurns {
+  int first, stride, count;
+  __device__ __forceinline__ int chunk(int t) const { return first + t * stride; }
+};
+__device__ __forceinline__ LmTurns lm_turns(int C, int kw, int n_blocks, bool contig) {
+  const int wave = threadIdx.x >> 6;
+  LmTurns T;
+  if (contig) { T.first = (int)blockIdx.x * LM_CPW * kw + wave; T.stride = LM_CPW; }
+  else { T.first = (int)blockIdx.x * LM_CPW + wave; T.stride = LM_CPW * n_blocks; }
+  T.count = T.first < C ? min(kw, (C - 1 - T.first) / T.stride + 1) : 0;
+  return T;
+}
+
+// One command of ba_lm_multi_kernel: lm_iterate with every wavefront taking its Tn.count chunks in turn through its ONE staging area.
+// Every chunk still publishes its own partials in its own slot (make_sink(P, chunk, ...)): level 2 sums the same values in the same
+// order as ba_lm_kernel.  Nothing of a chunk stays in registers between turns — its observations come from the device arena (the
+// kernel copied them there once), its landmarks from the current / candidate buffer, its Jacobi scales from P.sp, its table sits in
+// LDS — so the wavefront's registers are those of ONE chunk.  Pass B runs for all of a wavefront's chunks before a chained decision
+// (which waits for every chunk's payload2); pass A then runs at the point and with the radius the decision chose.
+__device__ __forceinline__ bool lm_iterate_multi(const BaDev& P, const LmDevArgs& a, const LmTurns& Tn, const uint16_t* tabs, const WgLds& L,
+                                                 double* union_lds, int union_doubles, LmDevState& cs, double* sStep, LmShared& sh, int n_blocks,
+                                                 long long t_first, long long* tp, bool linearize_only) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  long long tmark = tp && tid == 0 ? (long long)wall_clock64() : 0;
+  auto stamp = [&](int slot) { if (tp && tid == 0) { const long long tn = (long long)wall_clock64(); tp[slot] += tn - tmark; tmark = tn; } };
+  const double* dc_ = sStep;
+  const double* cand_poses_ = sStep + (P.n > 0 ? P.n : 1);
+  const double* cur_poses_ = cand_poses_ + 7 * P.K;
+  const double radius = cs.radius, spec_radius = linearize_only ? 0.0 : cs.spec;
+  const int chain = linearize_only ? 0 : cs.chain;
+  const int with_pay1 = linearize_only || chain || spec_radius > 0;
+  double unused0 = 0, unused1 = 0, unused2 = 0, unused3 = 0;
+  if (!linearize_only) {
+#pragma nounroll
+    for (int t = 0; t < Tn.count; ++t) {
+      const int chunk = Tn.chunk(t);
+      const ObsRec R = load_obs(P, chunk, lane, P.points);
+      const PartSink sink = make_sink(P, chunk, 1, L.pst);
+      D3 cand;
+      backsub_chunk(P, R, cur_poses_, cand_poses_, dc_, P.cand_points, radius, cand, unused0, unused1, unused2, unused3, nullptr, L.rec, &sink);
+    }
+    stores_acknowledged();  // the candidate landmarks are in place before pass A reads them back
+  }
+  stamp(0);
+  if (with_pay1) {
+    // what pass A linearises: the current point (a linearisation alone, or a chained step the decision rejected), or the candidate
+    // pass B just formed (same sweep: with the predicted radius; chained and accepted: with the radius of the decision)
+    bool at_cand = !linearize_only;
+    double radius_a = linearize_only ? radius : spec_radius;
+    const int first_a = linearize_only ? cs.first : 0;
+    if (chain) {
+      stamp(1);
+      if (!sum_pay2<false>(P, P.pay_parity, P.pay_tag, union_lds, sh.sOut, &sh.sGo)) return false;
+      if (tid == 0) {
+        const SvoLmDecision dec = svo_lm_decide(cs.cost, cs.mcc, radius, cs.df, sh.sOut[0], sh.sOut[1]);
+        sh.sDec[0] = (double)dec.accept; sh.sDec[1] = dec.next_radius;
+        cs.pay2[0] = sh.sOut[0]; cs.pay2[1] = sh.sOut[1]; cs.pay2[2] = sh.sOut[2]; cs.pay2[3] = sh.sOut[3];
+        cs.pay2[4] = (double)dec.accept; cs.pay2[5] = dec.next_radius;
+      }
+      __syncthreads();
+      stamp(2);
+      radius_a = sh.sDec[1];
+      at_cand = sh.sDec[0] != 0.0;
+    }
+    const double* pts_a = at_cand ? P.cand_points : P.points;
+    const double* poses_a = at_cand ? cand_poses_ : cur_poses_;
+#pragma nounroll
+    for (int t = 0; t < Tn.count; ++t) {
+      const int chunk = Tn.chunk(t);
+      const ObsRec R = load_obs(P, chunk, lane, pts_a);
+      LinPre pre;
+      SufRegs o;
+      o.freep = false;
+      linearize_prefix(P, R, poses_a, pre, unused0);
+      suffix_math(P, R, pre, radius_a, first_a, L.rec, nullptr, o);
+      const ChunkTab T{tabs + t * a.tab_words, (P.K - 1) * P.K / 2, P.K - 1};
+      chunk_owner_phases<false>(R, T, o, L.rec, make_sink(P, chunk, 1, L.pst), L.s_ne);
+    }
+  }
+  stamp(3);
+  if (!with_pay1) return true;
+  __syncthreads();  // both wavefronts are through their passes: their LDS becomes the scratch of level 2
+  const int per = (P.E + n_blocks - 1) / n_blocks;  // (see lm_iterate: a workgroup without a slice waits for nobody)
+  const int e0 = min(P.E, (int)blockIdx.x * per), e1 = min(P.E, e0 + per);
+  double* res = a.dev_res;
+  const unsigned long long tag = P.pay_tag;
+  bool ok = true;
+  if (e0 < e1) ok = reduce_elements<false>(P, e0, e1, tag, union_lds, union_doubles, &sh.sGo, [res, tag](int e, double v) { granule_store(&res[2 * e], v, tag); }, tp ? tp + 5 : nullptr);
+  if (blockIdx.x == 0 && tid == 0) granule_store(&res[2 * P.E], 1e-8 * (double)((long long)wall_clock64() - t_first), tag);
+  stamp(4);
+  return ok;
+}
+
 #ifndef SVO_LM_WAVES_PER_EU  // developer experiments only (SVO_EXTRA_HIPFLAGS): the register budget of the solve kernel's wavefronts
 #define SVO_LM_WAVES_PER_EU 2
 #endif
 // GROUPED: windows of 129..LM_MAX_CHUNKS_GROUPED chunks (the 10-keyframe windows of configs[2]): levels 1-2 of the declared order sum
 // groups of G = ceil(C / 128) consecutive chunks first (reduce_elements<true>, sum_pay2<true>: the forms the host-driven kernels use).
 // A kernel of its own (ba_lm_grouped_kernel) so that the plain one — every pipeline group's solve — keeps its code size.
-template <bool GROUPED>
+// MULTI (ba_lm_multi_kernel): every wavefront takes a.wave_chunks chunks in turn (lm_iterate_multi) — 1 / kw of the workgroups per solve.
+template <bool GROUPED, bool MULTI = false>
 __device__ __forceinline__ void ba_lm_body(const LmLanePtrs& lanes) {
   extern __shared__ double lds[];  // ba_lm_lds_doubles(n, K)
   __shared__ LmShared sh;
@@ -2329,7 +2433,8 @@ __device__ __forceinline__ void ba_lm_body(const LmLanePtrs& lanes) {
     for (int i = tid; i < (int)(sizeof(LmLane) / 4); i += blockDim.x) dst[i] = __hip_atomic_load(&src[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   __syncthreads();
-  const int n_blocks = (sLane.P.C + LM_CPW - 1) / LM_CPW;  // workgroups of THIS solve; the launch is as wide as its largest solve
+  const int kw = MULTI ? sLane.a.wave_chunks : 1;
+  const int n_blocks = ba_lm_blocks(sLane.P.C, kw);  // workgroups of THIS solve; the launch is as wide as its largest solve
   if ((int)blockIdx.x >= n_blocks) return;
   BaDev P = sLane.P;
   const LmDevArgs& a = sLane.a;
@@ -2337,11 +2442,12 @@ __device__ __forceinline__ void ba_lm_body(const LmLanePtrs& lanes) {
   const int union_doubles = (int)ba_lm_union_doubles(n, K);
   double* union_lds = lds;                                         // staging rows + landmark scalars | controller workspace
   const WgLds L = wg_lds(lds + wave * wg_lds_doubles(P.E), P.E);  // this wavefront's own staging rows and outgoing partials
-  uint16_t* tabs = reinterpret_cast<uint16_t*>(lds + union_doubles) + wave * a.tab_words;
-  double* cSc = lds + union_doubles + LM_CPW * a.tab_words / 4;  // persistent: Jacobi scales of the pose columns
+  uint16_t* tabs = reinterpret_cast<uint16_t*>(lds + union_doubles) + wave * kw * a.tab_words;  // this wavefront's kw chunk tables
+  double* cSc = lds + union_doubles + LM_CPW * kw * a.tab_words / 4;  // persistent: Jacobi scales of the pose columns
   double* sStep = cSc + 2 * nn;                                    // [dc | candidate poses | current poses] (the second nn: spare)
   const int my_chunk = (int)blockIdx.x * LM_CPW + wave;
-  const bool my_wave_works = my_chunk < P.C;
+  const bool my_wave_works = !MULTI && my_chunk < P.C;
+  const LmTurns turns = lm_turns(P.C, kw, n_blocks, MULTI && a.wave_contig);
   if (a.test_giveup) {  // (test hook: the host must re-run this solve and lose nothing)
     if (blockIdx.x == 0 && tid == 0) __hip_atomic_store(a.host_flag, -a.host_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     return;
@@ -2362,11 +2468,28 @@ __device__ __forceinline__ void ba_lm_body(const LmLanePtrs& lanes) {
     if (shift && W.R.active && lane == W.R.first) { a.points_a[3 * W.R.j] = W.R.p.x; a.points_a[3 * W.R.j + 1] = W.R.p.y; a.points_a[3 * W.R.j + 2] = W.R.p.z; }
     load_chunk_table(P, my_chunk, tabs, shift);
   }
+  if (MULTI) {
+    // every chunk of the wavefront: table -> LDS; observations and landmarks -> the device arena / the current landmark buffer, where
+    // every later turn reads them (plain loads: written by this wavefront)
+    for (int t = 0; t < turns.count; ++t) {
+      const int chunk = turns.chunk(t);
+      const ObsRec R = load_obs_image(P, chunk, lane, a.points_a, shift);
+      if (shift) {
+        const int4 rc = R.active ? make_int4(R.k, R.j, R.first, R.len) : make_int4(-1, 0, 0, 0);
+        const_cast<int4*>(P.rec)[R.o] = rc;
+        double* uv = const_cast<double*>(P.obs_uv) + 2 * R.o;
+        uv[0] = R.u; uv[1] = R.v;
+        if (R.active && lane == R.first) { a.points_a[3 * R.j] = R.p.x; a.points_a[3 * R.j + 1] = R.p.y; a.points_a[3 * R.j + 2] = R.p.z; }
+      }
+      load_chunk_table(P, chunk, tabs + t * a.tab_words, shift);
+    }
+    stores_acknowledged();
+  }
   long long t_first = 0;
   __syncthreads();
   for (;;) {
     const int st_before = cs.state;
-    const int op = lm_controller<false, GROUPED>(P, a, cs, union_lds, cSc, sStep, sh.sOut);
+    const int op = lm_controller<false, GROUPED, MULTI>(P, a, cs, union_lds, cSc, sStep, sh.sOut);
     if (a.dbg && tid == 0) {
       unsigned* g = a.dbg + 16 * blockIdx.x;
       g[0] = (unsigned)op; g[1] = (unsigned)cs.state; g[2] = (unsigned)cs.iterations; g[3] = (unsigned)cs.need_linearize;
@@ -2378,7 +2501,7 @@ __device__ __forceinline__ void ba_lm_body(const LmLanePtrs& lanes) {
       return;
     }
     if (op == LMOP_EXIT) break;
-    if (st_before == LMS_STEP && cs.accepted) W.R.p = W.cand;  // the step control took the step: the candidate is the current point
+    if (!MULTI && st_before == LMS_STEP && cs.accepted) W.R.p = W.cand;  // the step control took the step: the candidate is the current point
     if (!t_first) t_first = (long long)wall_clock64();
     const bool sel = cs.sel != 0;
     P.points = sel ? a.points_b : a.points_a;
@@ -2390,6 +2513,23 @@ __device__ __forceinline__ void ba_lm_body(const LmLanePtrs& lanes) {
         ObsRec R = W.R;  // the landmarks of the buffer the step control selected (a chained pass A may have run ahead of a step that was not taken)
         if (R.active) R.p = D3{P.points[3 * R.j], P.points[3 * R.j + 1], P.points[3 * R.j + 2]};
         deliver_chunk_points(R, a.export_points, union_lds + wave * ((64 * REC_STRIDE) / LM_CPW), (64 * REC_STRIDE) / LM_CPW);  // the staging rows are idle
+      }
+      if (MULTI) {
+        double* stage = union_lds + wave * ((64 * REC_STRIDE) / LM_CPW);  // the staging rows are idle
+        // last turn first: a landmark store too small for the window's ids (two landmarks of one slot) must keep the entry of the
+        // OLDER landmark as often as ba_lm_kernel's concurrent delivery does, so that the next PnP meets the foreign id and reports
+        // it (tests/test_group.py) — in turn order the newest landmarks always won and tracking went on unaware of the overwrite
+        for (int t = turns.count - 1; t >= 0; --t) {
+          const ObsRec R = load_obs(P, turns.chunk(t), lane, P.points);
+          if (a.export_points) deliver_chunk_points(R, a.export_points, stage, (64 * REC_STRIDE) / LM_CPW);
+          if (a.store && R.active && lane == R.first) {
+            const unsigned key = sys_load(&P.lm_key[R.j], shift);
+            const unsigned long long lo = ((unsigned long long)__float_as_uint((float)R.p.y) << 32) | __float_as_uint((float)R.p.x);
+            const unsigned long long hi = ((unsigned long long)key << 32) | __float_as_uint((float)R.p.z);
+            slot_store2<true>(reinterpret_cast<double*>(a.store + (key & a.store_mask)), __longlong_as_double((long long)lo), __longlong_as_double((long long)hi));
+          }
+          wave_lds_fence();
+        }
       }
       if (a.store && my_wave_works && W.R.active && lane == W.R.first) {
         // get_world_points (src/bundle_adjuster.cpp:159-163: double -> float) for the next keyframe's PnP, served from the device:
@@ -2417,7 +2557,10 @@ __device__ __forceinline__ void ba_lm_body(const LmLanePtrs& lanes) {
       continue;  // the next controller turn answers "delivered": everybody leaves
     }
     long long* tp = a.dbg ? cs.tp : nullptr;
-    if (!lm_iterate<GROUPED>(P, a, W, my_wave_works, tabs, L, union_lds, union_doubles, cs, sStep, sh, n_blocks, t_first, op == LMOP_ITERATE ? tp : nullptr, op != LMOP_ITERATE)) {
+    bool good;
+    if constexpr (MULTI) good = lm_iterate_multi(P, a, turns, tabs, L, union_lds, union_doubles, cs, sStep, sh, n_blocks, t_first, op == LMOP_ITERATE ? tp : nullptr, op != LMOP_ITERATE);
+    else good = lm_iterate<GROUPED>(P, a, W, my_wave_works, tabs, L, union_lds, union_doubles, cs, sStep, sh, n_blocks, t_first, op == LMOP_ITERATE ? tp : nullptr, op != LMOP_ITERATE);
+    if (!good) {
       if (tid == 0) __hip_atomic_store(a.host_flag, -a.host_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       return;
     }
@@ -2426,6 +2569,7 @@ __device__ __forceinline__ void ba_lm_body(const LmLanePtrs& lanes) {
 }
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(SVO_LM_WAVES_PER_EU, SVO_LM_WAVES_PER_EU))) void ba_lm_kernel(LmLanePtrs lanes) { ba_lm_body<false>(lanes); }
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(SVO_LM_WAVES_PER_EU, SVO_LM_WAVES_PER_EU))) void ba_lm_grouped_kernel(LmLanePtrs lanes) { ba_lm_body<true>(lanes); }
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(SVO_LM_WAVES_PER_EU, SVO_LM_WAVES_PER_EU))) void ba_lm_multi_kernel(LmLanePtrs lanes) { ba_lm_body<false, true>(lanes); }
 
 // ---------------------------------------------------------------------------------------------------
 // The THROUGHPUT form of the device-resident solve: ba_lm_compact_kernel — ONE workgroup runs a whole solve (round 5).
@@ -3724,18 +3868,20 @@ int ba_fused_budget(int device) {
 
 // What `grid` workgroups of ba_lm_kernel with `lds` bytes of dynamic LDS cost in the units of that budget: a
 // larger reduced camera system (10-keyframe windows) lowers the kernel's occupancy, its workgroups then count for more.
-int ba_lm_admission_cost(int grid, size_t lds, int device) {
+// (multi: ba_lm_multi_kernel's workgroups — the same 128 threads at 256 VGPRs; its kw chunk tables per wavefront make the LDS larger)
+int ba_lm_admission_cost(int grid, size_t lds, int device, bool multi = false) {
   (void)ba_fused_budget(device);
   static std::mutex mu;
   static size_t cached_lds[8];
   static int cached_per_cu[8], n_cached = 0;
   int per_cu = 0;
+  const size_t key = lds | (multi ? (size_t)1 << 62 : 0);
   {
     std::lock_guard<std::mutex> g(mu);
-    for (int i = 0; i < n_cached; ++i) if (cached_lds[i] == lds) per_cu = cached_per_cu[i];
+    for (int i = 0; i < n_cached; ++i) if (cached_lds[i] == key) per_cu = cached_per_cu[i];
     if (!per_cu) {
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ba_lm_kernel, 128, lds) != hipSuccess || per_cu <= 0) return 1 << 30;
-      if (n_cached < 8) { cached_lds[n_cached] = lds; cached_per_cu[n_cached++] = per_cu; }
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, multi ? ba_lm_multi_kernel : ba_lm_kernel, 128, lds) != hipSuccess || per_cu <= 0) return 1 << 30;
+      if (n_cached < 8) { cached_lds[n_cached] = key; cached_per_cu[n_cached++] = per_cu; }
     }
   }
   if (per_cu >= g_fused_per_cu) return grid;
@@ -3760,7 +3906,25 @@ bool ba_device_lm_wanted() {
 }
 
 int ba_lm_tab_words(const svo_ba* ba) { return std::max(64, (ba->tab_max_words + 63) & ~63); }
-size_t ba_lm_lds_bytes(const svo_ba* ba) { return sizeof(double) * ba_lm_lds_doubles(ba->d.n, ba->d.K, ba_lm_tab_words(ba)); }
+size_t ba_lm_lds_bytes(const svo_ba* ba, int kw) { return sizeof(double) * ba_lm_lds_doubles(ba->d.n, ba->d.K, ba_lm_tab_words(ba), kw); }
+
+// Chunks per wavefront of a wide solve (ba_lm_multi_kernel for more than one).  SVO_BA_WAVE_CHUNKS=1..4 (developer knob);
+// SVO_BA_WAVE_ORDER=contiguous gives a wavefront neighbouring chunks instead of one per stride (see lm_turns).  Windows of more
+// than 128 chunks (ba_lm_grouped_kernel) keep one chunk per wavefront; so do solves of no more than two chunks (one workgroup either way).
+constexpr int LM_WAVE_CHUNKS_DEFAULT = 3;
+int ba_lm_wave_chunks(const svo_ba* ba) {
+  static const int env = [] {
+    const char* e = getenv("SVO_BA_WAVE_CHUNKS");
+    const int v = e && *e ? atoi(e) : LM_WAVE_CHUNKS_DEFAULT;
+    return v < 1 ? 1 : (v > LM_MAX_WAVE_CHUNKS ? LM_MAX_WAVE_CHUNKS : v);
+  }();
+  if (ba->d.G > 1 || ba->d.C <= LM_CPW) return 1;
+  return env;
+}
+bool ba_lm_wave_contig() {
+  static const bool contig = [] { const char* e = getenv("SVO_BA_WAVE_ORDER"); return e && e[0] == 'c'; }();
+  return contig;
+}
 
 // Fills the adjuster's launch record for the loaded problem; false: not eligible (use the host-driven path).
 // compact form: the waves per workgroup that fit 156 KB of dynamic LDS (the kernel keeps ~1.5 KB of static LDS), at most
@@ -3788,7 +3952,7 @@ bool ba_device_lm_fill(svo_ba* ba, int* cost, size_t* lds_out, bool forced, bool
   BaDev& d = ba->d;
   if (!d.det || d.C <= 0 || !ba_zero_copy(ba) || !(forced || ba->device_lm == 1 || (ba->device_lm < 0 && ba_device_lm_wanted())) || !ba->h_lane) return false;
   size_t lds = 0;
-  int nw = 0;
+  int nw = 0, kw = 1;
   if (compact) {
     if (d.C > LMC_MAX_CHUNKS || ba->tab_max_words > 4096) return false;
     nw = ba_lmc_waves(ba);
@@ -3801,7 +3965,8 @@ bool ba_device_lm_fill(svo_ba* ba, int* cost, size_t* lds_out, bool forced, bool
   // beyond 128 chunks (ba_lm_grouped_kernel) only on request: measured on configs[2]'s 10-keyframe windows (~210 chunks, E = 2,312 wire
   // elements) the host-driven loop is faster — 780 against 590 frames/s (profiles/r05_exp_single_stream_paths.txt)
   if (d.G > 1 && ba->device_lm != 1) return false;
-  lds = ba_lm_lds_bytes(ba);
+  kw = ba_lm_wave_chunks(ba);
+  lds = ba_lm_lds_bytes(ba, kw);
   if (lds > 120 * 1024) return false;  // n <= 100 or so; window problems are n <= 60
   }
   d.points = ba->cur_points; d.cand_points = ba->cand_points; d.poses = ba->cur_poses; d.cand_poses = ba->cand_poses;
@@ -3824,6 +3989,8 @@ bool ba_device_lm_fill(svo_ba* ba, int* cost, size_t* lds_out, bool forced, bool
   const bool fresh = ba->lm_counters_dirty || !ba->lm_have_base;
   a.base_arrive = fresh ? 0 : ba->lm_base;
   a.tab_words = compact ? ba_lmc_tab_words(ba) : ba_lm_tab_words(ba);
+  a.wave_chunks = kw;
+  a.wave_contig = ba_lm_wave_contig() ? 1 : 0;
   a.opt.max_iterations = ba->opt.max_iterations;
   a.opt.function_tolerance = ba->opt.function_tolerance; a.opt.gradient_tolerance = ba->opt.gradient_tolerance;
   a.opt.parameter_tolerance = ba->opt.parameter_tolerance; a.opt.initial_radius = ba->opt.initial_radius;
@@ -3834,7 +4001,7 @@ bool ba_device_lm_fill(svo_ba* ba, int* cost, size_t* lds_out, bool forced, bool
     static const int every = [] { const char* e = getenv("SVO_BA_TEST_GIVEUP"); return e && *e ? atoi(e) : 0; }();
     a.test_giveup = (!compact && every > 0 && (++ba->wide_launches % every) == 0) ? 1 : 0;
   }
-  *cost = compact ? 0 : ba_lm_admission_cost((d.C + LM_CPW - 1) / LM_CPW, lds, ba->ctx->device);
+  *cost = compact ? 0 : ba_lm_admission_cost(ba_lm_blocks(d.C, kw), lds, ba->ctx->device, kw > 1);
   *lds_out = lds;
   if (waves_out) *waves_out = nw;
   return true;
@@ -3856,7 +4023,8 @@ int ba_device_lm_launch(svo_ba** bas, int n, hipStream_t st, bool forced, unsign
   // ---- the wide form (ba_lm_kernel): admitted against the budget of co-resident waiting workgroups
   int launched_total = 0;
   for (int i = 0; i < n && i < SVO_MAX_LANES; ++i) bas[i]->lm_inflight = false;
-  for (int grouped = 0; grouped < 2; ++grouped) {  // windows of up to 128 chunks: ba_lm_kernel; beyond: ba_lm_grouped_kernel
+  for (int form = 0; form < 3; ++form) {  // windows of up to 128 chunks: ba_lm_kernel, or ba_lm_multi_kernel (form 2, several chunks per wavefront); beyond: ba_lm_grouped_kernel (form 1)
+  const void* kernel = form == 0 ? (const void*)ba_lm_kernel : (form == 1 ? (const void*)ba_lm_grouped_kernel : (const void*)ba_lm_multi_kernel);
   LmLanePtrs ptrs;
   int launched = 0, max_c = 0;
   size_t max_lds = 0;
@@ -3866,10 +4034,10 @@ int ba_device_lm_launch(svo_ba** bas, int n, hipStream_t st, bool forced, unsign
     svo_ba* ba = bas[i];
     int cost = 0;
     size_t lds = 0;
-    if ((ba->d.G > 1) != (grouped != 0)) continue;
+    if ((ba->d.G > 1 ? 1 : (ba_lm_wave_chunks(ba) > 1 ? 2 : 0)) != form) continue;
     if (ba_wants_compact(ba)) { to_compact[i] = true; continue; }
     if (!ba_device_lm_fill(ba, &cost, &lds, forced)) continue;
-    if (lds > 32 * 1024 && hipFuncSetAttribute(grouped ? (const void*)ba_lm_grouped_kernel : (const void*)ba_lm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) != hipSuccess) continue;
+    if (lds > 32 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) != hipSuccess) continue;
     if (!ba_resident_admission(ba)->admit(cost, ba->ctx->device)) { to_compact[i] = overflow; continue; }
     // the counter starts from zero: cleared in front of the launch (the adjuster's previous solve no longer touches it
     // once its completion word is out)
@@ -3880,7 +4048,7 @@ int ba_device_lm_launch(svo_ba** bas, int n, hipStream_t st, bool forced, unsign
     ptrs.p[launched] = ba->h_lane;
     took[launched] = ba;
     tidx[launched] = i;
-    max_c = std::max(max_c, (ba->d.C + LM_CPW - 1) / LM_CPW);
+    max_c = std::max(max_c, ba_lm_blocks(ba->d.C, ba->h_lane->a.wave_chunks));
     max_lds = std::max(max_lds, lds);
     ++launched;
   }
@@ -3888,7 +4056,8 @@ int ba_device_lm_launch(svo_ba** bas, int n, hipStream_t st, bool forced, unsign
     const auto t0 = now();
     {
       SvoProfScope prof(took[0]->ctx, SVO_PROF_BA_STEP, st);
-      if (grouped) hipLaunchKernelGGL(ba_lm_grouped_kernel, dim3(max_c, launched), dim3(128), max_lds, st, ptrs);
+      if (form == 1) hipLaunchKernelGGL(ba_lm_grouped_kernel, dim3(max_c, launched), dim3(128), max_lds, st, ptrs);
+      else if (form == 2) hipLaunchKernelGGL(ba_lm_multi_kernel, dim3(max_c, launched), dim3(128), max_lds, st, ptrs);
       else hipLaunchKernelGGL(ba_lm_kernel, dim3(max_c, launched), dim3(128), max_lds, st, ptrs);
     }
     if (hipGetLastError() != hipSuccess) {
@@ -3978,7 +4147,7 @@ int ba_device_lm_end(svo_ba* ba, svo_ba_summary* sum) {
       if (ba->d_lmdbg && d.C <= 4096) {
         std::vector<unsigned> g(16 * (size_t)d.C);
         (void)hipMemcpy(g.data(), ba->d_lmdbg, sizeof(unsigned) * g.size(), hipMemcpyDeviceToHost);
-        for (int b = 0; b < (d.C + LM_CPW - 1) / LM_CPW; ++b) {
+        for (int b = 0; b < ba_lm_blocks(d.C, ba->h_lane->a.wave_chunks); ++b) {
           const unsigned* q = &g[16 * (size_t)b];
           if (b == 0 || memcmp(q, &g[0], 20) != 0)
             fprintf(stderr, "[svo ba]   workgroup %d: op %u state %u iterations %u need_linearize %u chain/bad %x arrive_total %u commands %u lin_calls %u\n", b, q[0], q[1],
@@ -4004,7 +4173,7 @@ int ba_device_lm_end(svo_ba* ba, svo_ba_summary* sum) {
   ba->lm_same += (long)r[LMR_SAME_SWEEP]; ba->lm_used += (long)r[LMR_NEXT_USED]; ba->lm_steps += (long)r[LMR_STEP_CALLS]; ba->lm_lins += (long)r[LMR_LINEARIZE_CALLS];
   for (int i = 0; i < 14; ++i) ba->lm_tp[i] += r[LMR_TP0 + i];
   if (ba->d_lmdbg && getenv("SVO_TIMING")) {
-    const int nb = (d.C + LM_CPW - 1) / LM_CPW;
+    const int kw = ba->h_lane->a.wave_chunks, nb = ba_lm_blocks(d.C, kw);
     std::vector<unsigned> g(16 * (size_t)nb);
     if (hipMemcpy(g.data(), ba->d_lmdbg, sizeof(unsigned) * g.size(), hipMemcpyDeviceToHost) == hipSuccess) {
       for (int sl = 0; sl < 7; ++sl) {
@@ -4017,7 +4186,7 @@ int ba_device_lm_end(svo_ba* ba, svo_ba_summary* sum) {
         ++traced;
         const int nU = (d.K - 1) * d.K / 2, F = d.K - 1;
         for (int b = 0; b < nb; ++b) {
-          const int c = b * LM_CPW;
+          const int c = b * LM_CPW * (ba->h_lane->a.wave_contig ? kw : 1);  // the first chunk of the workgroup's first wavefront
           const uint16_t* w = ba->u_tab.data() + ba->u_tab_off[(size_t)c];
           int ne = 0, longest = 0, plong = 0;
           for (int q = 0; q < nU; ++q) { const int len = w[q + 1] - w[q]; ne += len > 0; longest = std::max(longest, len); }
