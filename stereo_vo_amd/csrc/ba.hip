@@ -457,12 +457,35 @@ __device__ __forceinline__ ObsRec load_obs(const BaDev& P, int chunk, int lane, 
   return R;
 }
 
+// The same load in two halves, for the forms that walk several chunks per wavefront in turn (ba_lm_multi_kernel, lmc_sweep):
+// obs_request issues the next turn's record and measurement while the current turn computes; obs_complete, once the record is
+// in, issues its landmark and — for passes that read them (sp != null) — its Jacobi scales, which the turn then takes from `c`.
+struct ObsNext { int4 rc; double u, v; };
+__device__ __forceinline__ ObsNext obs_request(const BaDev& P, int chunk, int lane) {
+  const int o = chunk * 64 + lane;
+  return ObsNext{P.rec[o], P.obs_uv[2 * o], P.obs_uv[2 * o + 1]};
+}
+
 // What pass A computes before the trust-region radius enters (residual, Jacobians, the landmark's sums in observation order):
 // inside ba_lm_kernel this part runs while the accept / radius decision of the step is still on its way.
 struct LinPre { double r[2], Jc[12], Jp[6], V[9], gp[3], cost_l; int maxlen; };
 // Per-lane constants of a solve that ba_lm_kernel keeps in registers from pass to pass: the landmark's Jacobi scales
 // (fixed by the first pass A).
 struct ChunkRegs { double s[3]; };
+
+__device__ __forceinline__ ObsRec obs_complete(const ObsNext& x, int chunk, int lane, const double* __restrict__ points, const double* sp, ChunkRegs& c) {
+  ObsRec R{false, 0, 0, 0, lane, 0, D3{0, 0, 1}, 0.0, 0.0};
+  R.o = chunk * 64 + lane;
+  R.u = x.u; R.v = x.v;
+  R.active = x.rc.x >= 0;
+  c.s[0] = c.s[1] = c.s[2] = 1.0;
+  if (R.active) {
+    R.k = x.rc.x; R.j = x.rc.y; R.first = x.rc.z; R.len = x.rc.w;
+    R.p = D3{points[3 * R.j], points[3 * R.j + 1], points[3 * R.j + 2]};
+    if (sp) { c.s[0] = sp[3 * R.j]; c.s[1] = sp[3 * R.j + 1]; c.s[2] = sp[3 * R.j + 2]; }
+  }
+  return R;
+}
 
 __device__ __forceinline__ void linearize_prefix(const BaDev& P, const ObsRec& R, const double* __restrict__ poses_, LinPre& q, double& lcost) {
   const bool active = R.active;
@@ -2348,17 +2371,27 @@ __device__ __forceinline__ bool lm_iterate_multi(const BaDev& P, const LmDevArgs
   const int chain = linearize_only ? 0 : cs.chain;
   const int with_pay1 = linearize_only || chain || spec_radius > 0;
   double unused0 = 0, unused1 = 0, unused2 = 0, unused3 = 0;
-  if (!linearize_only) {
+  // The turns are pipelined: a turn's record is requested while the previous turn computes, and its landmark (with its Jacobi
+  // scales, where the pass reads them) as soon as the record is in — in pass A before the previous turn's owner phases, which
+  // wait on LDS.  Only loads move: every turn computes from the same values in the same order.
+  ObsNext nx{};
+  ChunkRegs cr;
+  if (!linearize_only && Tn.count > 0) {
+    nx = obs_request(P, Tn.chunk(0), lane);
+    ObsRec R = obs_complete(nx, Tn.chunk(0), lane, P.points, P.sp, cr);
 #pragma nounroll
     for (int t = 0; t < Tn.count; ++t) {
       const int chunk = Tn.chunk(t);
-      const ObsRec R = load_obs(P, chunk, lane, P.points);
+      const bool more = t + 1 < Tn.count;
+      if (more) nx = obs_request(P, Tn.chunk(t + 1), lane);
       const PartSink sink = make_sink(P, chunk, 1, L.pst);
       D3 cand;
-      backsub_chunk(P, R, cur_poses_, cand_poses_, dc_, P.cand_points, radius, cand, unused0, unused1, unused2, unused3, nullptr, L.rec, &sink);
+      backsub_chunk(P, R, cur_poses_, cand_poses_, dc_, P.cand_points, radius, cand, unused0, unused1, unused2, unused3, &cr, L.rec, &sink);
+      if (more) R = obs_complete(nx, Tn.chunk(t + 1), lane, P.points, P.sp, cr);
     }
-    stores_acknowledged();  // the candidate landmarks are in place before pass A reads them back
   }
+  if (with_pay1 && Tn.count > 0) nx = obs_request(P, Tn.chunk(0), lane);  // pass A's first record: whatever the decision below
+  if (!linearize_only) stores_acknowledged();  // the candidate landmarks are in place before pass A reads them back
   stamp(0);
   if (with_pay1) {
     // what pass A linearises: the current point (a linearisation alone, or a chained step the decision rejected), or the candidate
@@ -2382,17 +2415,24 @@ __device__ __forceinline__ bool lm_iterate_multi(const BaDev& P, const LmDevArgs
     }
     const double* pts_a = at_cand ? P.cand_points : P.points;
     const double* poses_a = at_cand ? cand_poses_ : cur_poses_;
+    const double* sp_a = first_a ? nullptr : P.sp;  // (the first pass writes the scales)
+    ObsRec R = Tn.count > 0 ? obs_complete(nx, Tn.chunk(0), lane, pts_a, sp_a, cr) : ObsRec{};
 #pragma nounroll
     for (int t = 0; t < Tn.count; ++t) {
       const int chunk = Tn.chunk(t);
-      const ObsRec R = load_obs(P, chunk, lane, pts_a);
+      const bool more = t + 1 < Tn.count;
+      if (more) nx = obs_request(P, Tn.chunk(t + 1), lane);
       LinPre pre;
       SufRegs o;
       o.freep = false;
       linearize_prefix(P, R, poses_a, pre, unused0);
-      suffix_math(P, R, pre, radius_a, first_a, L.rec, nullptr, o);
+      suffix_math(P, R, pre, radius_a, first_a, L.rec, &cr, o);
+      ChunkRegs crn;
+      const ObsRec Rn = more ? obs_complete(nx, Tn.chunk(t + 1), lane, pts_a, sp_a, crn) : R;
       const ChunkTab T{tabs + t * a.tab_words, (P.K - 1) * P.K / 2, P.K - 1};
       chunk_owner_phases<false>(R, T, o, L.rec, make_sink(P, chunk, 1, L.pst), L.s_ne);
+      R = Rn;
+      cr = crn;
     }
   }
   stamp(3);
@@ -2616,9 +2656,13 @@ struct LmcLds { double* wave_area; uint16_t* tab; double *tot, *q, *tot2, *q2; i
 // One sweep over all chunks of the solve.  do_b: pass B (step dc_ from the current point, candidate landmarks -> P.cand_points);
 // do_a: pass A — at the candidate pass B just formed (a_from_b: same sweep), at the stored candidate (a_at_cand: behind an accepted
 // chained decision) or at the current point.  Leaves the totals in L.tot2 / L.tot.  Block-uniform arguments.
+// tp (SVO_BA_TRACE, thread 0 = wavefront 0's view, ticks): slot 0 turns of sweeps with pass B, 3 turns of pass-A-only sweeps,
+// 1 waiting at a round's first barrier for the slowest wavefront, 2 the in-order accumulation and the second barrier, 13 rounds.
 __device__ __forceinline__ void lmc_sweep(const BaDev& P, const LmcLds& L, const double* sStep, bool do_b, bool do_a, bool a_from_b, bool a_at_cand,
-                                          double radius_b, double radius_a, int first_a) {
+                                          double radius_b, double radius_a, int first_a, long long* tp = nullptr) {
   const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, NW = nt >> 6;
+  long long tmark = tp && tid == 0 ? (long long)wall_clock64() : 0;
+  auto stamp = [&](int slot) { if (tp && tid == 0) { const long long tn = (long long)wall_clock64(); tp[slot] += tn - tmark; tmark = tn; } };
   const int C = P.C, G = P.G, E = P.E;
   const double* dc_ = sStep;
   const double* cand_poses_ = sStep + (P.n > 0 ? P.n : 1);
@@ -2629,10 +2673,24 @@ __device__ __forceinline__ void lmc_sweep(const BaDev& P, const LmcLds& L, const
   int* s_ne = reinterpret_cast<int*>(pst + ((E + 1) & ~1));
   double* pst2 = pst + ((E + 1) & ~1) + 2;
   const PartSink sink{nullptr, nullptr, pst, P.Epad, E, P.NG, 0, 1, 0, 0ull, pst2};
+  // Pipelined as in lm_iterate_multi: the next round's record is requested while this round computes, its landmark (from the buffer
+  // the sweep reads: the stored candidate behind an accepted chained decision) and Jacobi scales as soon as the record is in.
+  const double* pts_l = !do_b && a_at_cand ? P.cand_points : P.points;
+  const double* sp_l = do_b || !first_a ? P.sp : nullptr;  // (a first pass A writes the scales)
+  ObsNext nx{};
+  ChunkRegs cr;
+  ObsRec R{};
+  if (wave < C) {
+    nx = obs_request(P, wave, lane);
+    R = obs_complete(nx, wave, lane, pts_l, sp_l, cr);
+  }
   for (int c0 = 0; c0 < C; c0 += NW) {
-    const int chunk = c0 + wave;
+    const int chunk = c0 + wave, next = chunk + NW;
     if (chunk < C) {
-      const ObsRec R = load_obs(P, chunk, lane, P.points);
+      const bool more = next < C;
+      if (more) nx = obs_request(P, next, lane);
+      ChunkRegs crn;
+      ObsRec Rn = R;
       D3 cand = R.p;
       double u0 = 0, u1 = 0, u2 = 0, u3 = 0;
       if (do_a) {  // the chunk's table on its way to LDS while pass B / the prefix compute (plain loads: the arena was written by this workgroup)
@@ -2642,29 +2700,29 @@ __device__ __forceinline__ void lmc_sweep(const BaDev& P, const LmcLds& L, const
         uint32_t* d32 = reinterpret_cast<uint32_t*>(L.tab);
         for (int i = lane; i < words32; i += 64) d32[i] = src[i];
       }
-      if (do_b) backsub_chunk(P, R, cur_poses_, cand_poses_, dc_, P.cand_points, radius_b, cand, u0, u1, u2, u3, nullptr, rec, &sink);
+      if (do_b) backsub_chunk(P, R, cur_poses_, cand_poses_, dc_, P.cand_points, radius_b, cand, u0, u1, u2, u3, &cr, rec, &sink);
+      if (!do_a && more) Rn = obs_complete(nx, next, lane, pts_l, sp_l, crn);
       if (do_a) {
         ObsRec Ra = R;
         const double* poses_a = cur_poses_;
         if (a_from_b) { Ra.p = cand; poses_a = cand_poses_; }
-        else if (a_at_cand) {
-          if (R.active) Ra.p = D3{P.cand_points[3 * R.j], P.cand_points[3 * R.j + 1], P.cand_points[3 * R.j + 2]};
-          poses_a = cand_poses_;
-        }
+        else if (a_at_cand) poses_a = cand_poses_;  // (R.p came from the candidate buffer)
         LinPre pre;
         linearize_prefix(P, Ra, poses_a, pre, u0);
-        ChunkRegs cr;
-        cr.s[0] = cr.s[1] = cr.s[2] = 1.0;
-        if (!first_a && R.active) { cr.s[0] = P.sp[3 * R.j]; cr.s[1] = P.sp[3 * R.j + 1]; cr.s[2] = P.sp[3 * R.j + 2]; }
         SufRegs o;
         o.freep = false;
         suffix_math(P, Ra, pre, radius_a, first_a, rec, &cr, o);
+        if (more) Rn = obs_complete(nx, next, lane, pts_l, sp_l, crn);
         wave_lds_fence();  // the table's LDS copy is complete
         const ChunkTab T{L.tab, (P.K - 1) * P.K / 2, P.K - 1};
         chunk_owner_phases<false>(Ra, T, o, rec, sink, s_ne);
       }
+      R = Rn;
+      cr = crn;
     }
+    stamp(do_b ? 0 : 3);
     __syncthreads();
+    stamp(1);
     // the round's partials join the running sums in chunk order
     const int nw = min(NW, C - c0);
     if (do_b && tid < 4)
@@ -2673,6 +2731,8 @@ __device__ __forceinline__ void lmc_sweep(const BaDev& P, const LmcLds& L, const
       for (int e = tid; e < E; e += nt)
         for (int w = 0; w < nw; ++w) lmc_acc(L.tot, L.q, e, c0 + w, C, G, (L.wave_area + (size_t)w * L.wave_doubles)[64 * REC_STRIDE + e]);
     __syncthreads();
+    stamp(2);
+    if (tp && tid == 0) ++tp[13];
   }
 }
 
@@ -2765,12 +2825,13 @@ __global__ __launch_bounds__(64 * LMC_MAX_WAVES) void ba_lm_compact_kernel(LmLan
     const bool linearize_only = op != LMOP_ITERATE;
     const double radius = cs.radius, spec = linearize_only ? 0.0 : cs.spec;
     const int chain = linearize_only ? 0 : cs.chain;
+    long long* tp = a.dbg ? cs.tp : nullptr;
     if (linearize_only) {
-      lmc_sweep(P, L, sStep, false, true, false, false, 0.0, radius, cs.first);
+      lmc_sweep(P, L, sStep, false, true, false, false, 0.0, radius, cs.first, tp);
     } else if (spec > 0) {
-      lmc_sweep(P, L, sStep, true, true, true, false, radius, spec, 0);
+      lmc_sweep(P, L, sStep, true, true, true, false, radius, spec, 0, tp);
     } else {
-      lmc_sweep(P, L, sStep, true, false, false, false, radius, 0.0, 0);
+      lmc_sweep(P, L, sStep, true, false, false, false, radius, 0.0, 0, tp);
       if (chain) {
         if (tid == 0) {  // Ceres' decision on the summed payload2 (the same function as everywhere)
           const SvoLmDecision dec = svo_lm_decide(cs.cost, cs.mcc, radius, cs.df, L.tot2[0], L.tot2[1]);
@@ -2779,7 +2840,7 @@ __global__ __launch_bounds__(64 * LMC_MAX_WAVES) void ba_lm_compact_kernel(LmLan
           cs.pay2[4] = (double)dec.accept; cs.pay2[5] = dec.next_radius;
         }
         __syncthreads();
-        lmc_sweep(P, L, sStep, false, true, false, sh.sDec[0] != 0.0, 0.0, sh.sDec[1], 0);
+        lmc_sweep(P, L, sStep, false, true, false, sh.sDec[0] != 0.0, 0.0, sh.sDec[1], 0, tp);
       }
     }
     __syncthreads();
@@ -3163,6 +3224,7 @@ struct svo_ba {
   svo_lm_stats stats{};
   // SVO_TIMING accumulators
   double lm_tp[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  double lmc_tp[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; long lmc_n = 0, lmc_iters = 0, lm_iters_wide = 0;  // SVO_BA_TRACE: the compact form's split; LM iterations of wide solves
   double lm_wg_min[7] = {0, 0, 0, 0, 0, 0, 0}, lm_wg_mean[7] = {0, 0, 0, 0, 0, 0, 0}, lm_wg_max[7] = {0, 0, 0, 0, 0, 0, 0};  // SVO_BA_TRACE: spread of the per-workgroup split
   double lm_t_wait = 0, lm_t_ctl = 0, lm_t_body = 0, lm_t_total = 0; long lm_n = 0, lm_iters = 0, lm_same = 0, lm_used = 0, lm_steps = 0, lm_lins = 0;
   double t_lin = 0, t_step = 0, t_upload = 0, t_total = 0, t_prep = 0, t_read = 0; long n_lin = 0, n_step = 0, n_solves = 0, n_spec = 0, n_hit = 0;
@@ -3301,20 +3363,27 @@ extern "C" void svo_ba_destroy(svo_ba* ba) {
     fprintf(stderr, "[svo ba] device-resident solves: %ld, %.1f LM iterations each; per solve (workgroup 0, us): total %.1f = waiting for the passes %.1f + step control %.1f "
                     "+ own share of the passes %.1f; steps %ld (same sweep %ld, next linearisation used %ld), stand-alone linearisations %ld\n", ba->lm_n, (double)ba->lm_iters / ba->lm_n, 1e-2 * ba->lm_t_total / ba->lm_n, 1e-2 * ba->lm_t_wait / ba->lm_n,
             1e-2 * ba->lm_t_ctl / ba->lm_n, 1e-2 * ba->lm_t_body / ba->lm_n, ba->lm_steps, ba->lm_same, ba->lm_used, ba->lm_lins);
-  if (getenv("SVO_TIMING") && ba->lm_n && ba->d_lmdbg)
+  const bool wide_traced = ba->lm_iters_wide > 0 && ba->d_lmdbg != nullptr;  // (the split of the wide solves: per LM iteration of theirs)
+  const double wi = (double)std::max(ba->lm_iters_wide, 1l), ci = (double)std::max(ba->lmc_iters, 1l);
+  if (getenv("SVO_TIMING") && wide_traced)
     fprintf(stderr, "[svo ba]   per LM iteration (workgroup 0, us): pass B %.2f, radius-free part of pass A %.2f, collecting payload2 + decision %.2f, rest of pass A %.2f, "
-                    "own slice of level 2 %.2f (of which waiting for everybody's partials %.2f) | collecting the totals + assembly %.2f, system build %.2f, Cholesky %.2f, step tail %.2f\n", 1e-2 * ba->lm_tp[0] / ba->lm_iters, 1e-2 * ba->lm_tp[1] / ba->lm_iters,
-            1e-2 * ba->lm_tp[2] / ba->lm_iters, 1e-2 * (ba->lm_tp[3] + ba->lm_tp[10]) / ba->lm_iters, 1e-2 * ba->lm_tp[4] / ba->lm_iters, 1e-2 * ba->lm_tp[5] / ba->lm_iters,
-            1e-2 * ba->lm_tp[6] / ba->lm_iters, 1e-2 * ba->lm_tp[7] / ba->lm_iters, 1e-2 * ba->lm_tp[8] / ba->lm_iters, 1e-2 * ba->lm_tp[9] / ba->lm_iters);
-  if (getenv("SVO_TIMING") && ba->lm_n && ba->d_lmdbg)
+                    "own slice of level 2 %.2f (of which waiting for everybody's partials %.2f) | collecting the totals + assembly %.2f, system build %.2f, Cholesky %.2f, step tail %.2f\n", 1e-2 * ba->lm_tp[0] / wi, 1e-2 * ba->lm_tp[1] / wi,
+            1e-2 * ba->lm_tp[2] / wi, 1e-2 * (ba->lm_tp[3] + ba->lm_tp[10]) / wi, 1e-2 * ba->lm_tp[4] / wi, 1e-2 * ba->lm_tp[5] / wi,
+            1e-2 * ba->lm_tp[6] / wi, 1e-2 * ba->lm_tp[7] / wi, 1e-2 * ba->lm_tp[8] / wi, 1e-2 * ba->lm_tp[9] / wi);
+  if (getenv("SVO_TIMING") && wide_traced)
     fprintf(stderr, "[svo ba]   rest of pass A, chained steps (workgroup 0's first wavefront, us per LM iteration): lanes' arithmetic behind the decision %.2f, Schur owners %.2f, "
-                    "per-pose owners + posting the partials %.2f\n", 1e-2 * ba->lm_tp[10] / ba->lm_iters, 1e-2 * ba->lm_tp[12] / ba->lm_iters, 1e-2 * (ba->lm_tp[3] - ba->lm_tp[12]) / ba->lm_iters);
-  if (getenv("SVO_TIMING") && ba->lm_n && ba->d_lmdbg) {
+                    "per-pose owners + posting the partials %.2f\n", 1e-2 * ba->lm_tp[10] / wi, 1e-2 * ba->lm_tp[12] / wi, 1e-2 * (ba->lm_tp[3] - ba->lm_tp[12]) / wi);
+  if (getenv("SVO_TIMING") && wide_traced) {
     static const char* nm[7] = {"pass B", "radius-free part of pass A", "collecting payload2", "rest of pass A", "own slice of level 2", "waiting for the partials", "collecting the totals"};
     for (int sl = 0; sl < 7; ++sl)
-      fprintf(stderr, "[svo ba]   over the workgroups of a solve, per LM iteration (us): %-28s min %.2f mean %.2f max %.2f\n", nm[sl], 1e-2 * ba->lm_wg_min[sl] / ba->lm_iters,
-              1e-2 * ba->lm_wg_mean[sl] / ba->lm_iters, 1e-2 * ba->lm_wg_max[sl] / ba->lm_iters);
+      fprintf(stderr, "[svo ba]   over the workgroups of a solve, per LM iteration (us): %-28s min %.2f mean %.2f max %.2f\n", nm[sl], 1e-2 * ba->lm_wg_min[sl] / wi,
+              1e-2 * ba->lm_wg_mean[sl] / wi, 1e-2 * ba->lm_wg_max[sl] / wi);
   }
+  if (getenv("SVO_TIMING") && ba->lmc_iters && ba->d_lmdbg)
+    fprintf(stderr, "[svo ba] compact solves: %ld, %.1f LM iterations each, %.1f rounds of turns per LM iteration; per LM iteration (wavefront 0, us): turns of sweeps with pass B %.2f, "
+                    "turns of pass-A-only sweeps %.2f, waiting at a round's first barrier %.2f, in-order accumulation + second barrier %.2f | collecting the totals + assembly %.2f, "
+                    "system build %.2f, Cholesky %.2f, step tail %.2f\n", ba->lmc_n, (double)ba->lmc_iters / std::max(ba->lmc_n, 1l), ba->lmc_tp[13] / ci, 1e-2 * ba->lmc_tp[0] / ci,
+            1e-2 * ba->lmc_tp[3] / ci, 1e-2 * ba->lmc_tp[1] / ci, 1e-2 * ba->lmc_tp[2] / ci, 1e-2 * ba->lmc_tp[6] / ci, 1e-2 * ba->lmc_tp[7] / ci, 1e-2 * ba->lmc_tp[8] / ci, 1e-2 * ba->lmc_tp[9] / ci);
   if (ba->stream) (void)hipStreamSynchronize(ba->stream);
   void* ptrs[] = {ba->d_res, ba->d_lmdbg, ba->d_lmc, ba->d_arrive, ba->d_pay, ba->d_step, ba->d_bctl, d.sp, d.part1, d.part2, ba->d_arena};
   if (ba->h_bstat) (void)hipHostFree(ba->h_bstat);
@@ -4171,7 +4240,13 @@ int ba_device_lm_end(svo_ba* ba, svo_ba_summary* sum) {
   ba->stats.speculation_hits = (int)r[LMR_NEXT_USED];
   ba->stats.single_exchange = (int)r[LMR_SAME_SWEEP];
   ba->lm_same += (long)r[LMR_SAME_SWEEP]; ba->lm_used += (long)r[LMR_NEXT_USED]; ba->lm_steps += (long)r[LMR_STEP_CALLS]; ba->lm_lins += (long)r[LMR_LINEARIZE_CALLS];
-  for (int i = 0; i < 14; ++i) ba->lm_tp[i] += r[LMR_TP0 + i];
+  if (was_compact) {  // (the compact form's own split: lmc_sweep's slots)
+    for (int i = 0; i < 14; ++i) ba->lmc_tp[i] += r[LMR_TP0 + i];
+    ba->lmc_n++; ba->lmc_iters += (long)r[LMR_ITERATIONS];
+  } else {
+    for (int i = 0; i < 14; ++i) ba->lm_tp[i] += r[LMR_TP0 + i];
+    ba->lm_iters_wide += (long)r[LMR_ITERATIONS];
+  }
   if (ba->d_lmdbg && getenv("SVO_TIMING")) {
     const int kw = ba->h_lane->a.wave_chunks, nb = ba_lm_blocks(d.C, kw);
     std::vector<unsigned> g(16 * (size_t)nb);
