@@ -352,7 +352,22 @@ int svo_ba_set_solve_form(svo_ba* ba, int form);
 int svo_ba_set_bulk_control(svo_ba* ba, int mode);
 /* counters of the last svo_ba_solve / svo_ba_solve_problem */
 int svo_ba_last_stats(svo_ba* ba, svo_lm_stats* stats);
+/* Chunks of 64 observation slots that every wavefront of this adjuster's WIDE device-resident solves takes in turn: k = 1 ..
+ * svo_ba_wave_chunks_limit() (fewer workgroups per solve, a longer LM chain; the bits do not depend on k), 0 (default): the
+ * process default (3, SVO_BA_WAVE_CHUNKS), which the admission raises for a solve that its budget of co-resident workgroups
+ * refuses at the default. */
+int svo_ba_wave_chunks_limit(void);
+int svo_ba_set_wave_chunks(svo_ba* ba, int k);
+/* Device-resident solves this adjuster has launched since it was created: counts[0] in the compact form (one workgroup),
+ * counts[k] in the wide form at k chunks per wavefront; entries beyond the limit are 0.  gave_up (may be null): how many of
+ * them gave up within their bounded waits and were run again (compact form, else host-driven) — such a solve counts in both
+ * forms. */
+int svo_ba_solve_forms(svo_ba* ba, long* counts, int n, long* gave_up);
 int svo_ba_solve_problem(svo_ba* ba, svo_ba_summary* summary);
+/* svo_ba_solve_problem for the loaded problems of n adjusters (of one context, n <= 64) at once: those that are eligible for the
+ * wide device-resident form and admitted leave as ONE launch — as the lanes of a pipeline group do —, the others are solved one
+ * by one.  summaries: n entries or null.  Returns how many shared the launch, or a negative error code. */
+int svo_ba_solve_problems(svo_ba** bas, int n, svo_ba_summary* summaries);
 int svo_ba_read_problem(svo_ba* ba, double* poses7, double* points3);
 
 /* ---------------------------------------------------------------- pipeline --
@@ -439,6 +454,8 @@ int svo_pipeline_group_last_stats(const svo_pipeline_group* g, long* launches6, 
  * 24 B per observation + 48 B per landmark + 56 B per pose) of the bundle adjustments all lanes have finished since the last
  * reset: out4 = [f64 flops, bytes, solves, LM iterations].  Measurement aid (bench.py's roofline of the solve kernel). */
 int svo_pipeline_group_solve_work(svo_pipeline_group* g, double* out4, int reset);
+/* svo_ba_solve_forms summed over the lanes' adjusters: "compact solves" and "wide solves at k" of a profile. */
+int svo_pipeline_group_solve_forms(svo_pipeline_group* g, long* counts, int n, long* gave_up);
 
 /* FeatureTracker::draw_track + get_drawing (src/feature_tracker.cpp:74-91; used by src/vo_node.cpp:137,188):
  * the keyframe image as RGB (3 bytes per pixel, width*height*3 output) with one green arrow of thickness 4 per feature

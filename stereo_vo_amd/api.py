@@ -160,13 +160,13 @@ SYMBOLS = [
     "svo_pnp_ransac",
     "svo_ba_default_options", "svo_ba_create", "svo_ba_destroy", "svo_ba_reset", "svo_ba_add_keyframe", "svo_ba_solve",
     "svo_ba_get_pose", "svo_ba_window_count", "svo_ba_get_points", "svo_ba_load_problem",
-    "svo_ba_set_allreduce", "svo_ba_set_device_lm", "svo_ba_set_bulk_control", "svo_ba_set_solve_form", "svo_ba_solve_problem", "svo_ba_read_problem", "svo_ba_set_comm", "svo_ba_last_stats", "svo_lm_solve", "svo_lm_decide_step",
+    "svo_ba_set_allreduce", "svo_ba_set_device_lm", "svo_ba_set_bulk_control", "svo_ba_set_solve_form", "svo_ba_wave_chunks_limit", "svo_ba_set_wave_chunks", "svo_ba_solve_forms", "svo_ba_solve_problem", "svo_ba_solve_problems", "svo_ba_read_problem", "svo_ba_set_comm", "svo_ba_last_stats", "svo_lm_solve", "svo_lm_decide_step",
     "svo_rccl_unique_id", "svo_rccl_comm_create", "svo_rccl_comm_destroy",
     "svo_pipeline_default_params", "svo_pipeline_create", "svo_pipeline_destroy", "svo_pipeline_reset",
     "svo_pipeline_process_batch_dev", "svo_pipeline_process_batch", "svo_pipeline_get_tracked",
     "svo_pipeline_group_create", "svo_pipeline_group_destroy", "svo_pipeline_group_reset", "svo_pipeline_group_lanes",
     "svo_pipeline_group_process_batch_dev", "svo_pipeline_group_get_tracked", "svo_pipeline_group_last_stats",
-    "svo_pipeline_group_solve_work", "svo_pipeline_group_staging", "svo_pipeline_group_upload", "svo_pipeline_group_process_uploaded", "svo_pipeline_group_process_batch",
+    "svo_pipeline_group_solve_work", "svo_pipeline_group_solve_forms", "svo_pipeline_group_staging", "svo_pipeline_group_upload", "svo_pipeline_group_process_uploaded", "svo_pipeline_group_process_batch",
     "svo_synth_default_params", "svo_synth_render", "svo_synth_pose",
     "svo_image_read_gray", "svo_kitti_read_poses", "svo_ate_rmse", "svo_kitti_run", "svo_cholesky_solve", "svo_cholesky_solve_dev", "svo_draw_track", "svo_pipeline_draw_track",
 ]
@@ -474,6 +474,30 @@ class BA:
         self.ctx._chk(self.L.svo_ba_solve_problem(self.h, C.byref(s)), "svo_ba_solve_problem")
         return s
 
+    def set_wave_chunks(self, k):
+        """Chunks per wavefront of this adjuster's wide device-resident solves (1 .. svo_ba_wave_chunks_limit(); 0: the process default,
+        raised by the admission where its budget asks for it)."""
+        self.ctx._chk(self.L.svo_ba_set_wave_chunks(self.h, int(k)), "svo_ba_set_wave_chunks")
+
+    def solve_forms(self):
+        """([compact solves, wide solves at k = 1, 2, ... chunks per wavefront], solves that gave up and were run again) of this adjuster so far."""
+        n = self.L.svo_ba_wave_chunks_limit() + 1
+        out, gu = (C.c_long * n)(), C.c_long(0)
+        self.ctx._chk(self.L.svo_ba_solve_forms(self.h, out, n, C.byref(gu)), "svo_ba_solve_forms")
+        return list(out), gu.value
+
+    @staticmethod
+    def solve_problems(bas):
+        """solve_problem for the loaded problems of several adjusters of one context at once: the admitted wide solves share ONE launch
+        (as the lanes of a pipeline group do).  Returns (solves in the shared launch, [BASummary])."""
+        n = len(bas)
+        hs = (C.c_void_p * n)(*[b.h for b in bas])
+        sums = (BASummary * n)()
+        rc = bas[0].L.svo_ba_solve_problems(hs, n, sums)
+        if rc < 0:
+            bas[0].ctx._chk(rc, "svo_ba_solve_problems")
+        return rc, list(sums)
+
     def last_stats(self):
         st = LmStats()
         self.ctx._chk(self.L.svo_ba_last_stats(self.h, C.byref(st)), "svo_ba_last_stats")
@@ -683,6 +707,14 @@ class PipelineGroup:
         out = (C.c_double * 4)()
         self.ctx._chk(self.L.svo_pipeline_group_solve_work(self.h, out, int(reset)), "svo_pipeline_group_solve_work")
         return list(out)
+
+    def solve_forms(self):
+        """([compact solves, wide solves at k = 1, 2, ... chunks per wavefront], solves that gave up and were run again), summed over the
+        lanes' adjusters since the group was created."""
+        n = self.L.svo_ba_wave_chunks_limit() + 1
+        out, gu = (C.c_long * n)(), C.c_long(0)
+        self.ctx._chk(self.L.svo_pipeline_group_solve_forms(self.h, out, n, C.byref(gu)), "svo_pipeline_group_solve_forms")
+        return list(out), gu.value
 
     def last_stats(self):
         """{stage: (launches, lane-stages carried)} of the last process_batch_dev call; "host_thread_busy_us_of_call_us": (microseconds of the

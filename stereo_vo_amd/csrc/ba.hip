@@ -63,6 +63,7 @@
 #include "group_kernels.h"
 #include "lm_decide.h"
 #include "lm_device.h"
+#include "lm_turns.h"
 #include "ref_constants.h"
 #include "reproj_device.h"
 
@@ -1807,7 +1808,7 @@ struct LmDevArgs {
   LmDevOpt opt;
   unsigned* dbg;            // per workgroup 16 words: its last command (diagnostics of a solve that gave up; null: none)
   int test_giveup;          // test hook (SVO_BA_TEST_GIVEUP): the wide launch reports "gave up" at once, as if a bounded wait had run out
-  int wave_chunks;          // chunks every wavefront takes in turn (1: ba_lm_kernel / ba_lm_grouped_kernel; 2-4: ba_lm_multi_kernel)
+  int wave_chunks;          // chunks every wavefront takes in turn (1: ba_lm_kernel / ba_lm_grouped_kernel; 2..LM_MAX_WAVE_CHUNKS: ba_lm_multi_kernel), chosen per solve where it is admitted
   int wave_contig;          // ba_lm_multi_kernel: a wavefront's chunks are neighbours (1) or one per stride of 2 x workgroups (0)
 };
 enum { LMC_ARRIVE = 0, LMC_WORDS = 16 };
@@ -1837,9 +1838,7 @@ __host__ __device__ static inline size_t ba_lm_ctl_doubles(int n, int K) { retur
 // dynamic LDS of ba_lm_kernel (doubles): [staging rows + landmark scalars of CPW wavefronts | controller workspace] (union) |
 // chunk tables | Jacobi scales of the pose columns | step block [dc | candidate poses | current poses]
 // A workgroup is LM_CPW wavefronts; each takes `kw` chunks in turn (ba_lm_multi_kernel; kw = 1: ba_lm_kernel, one chunk per wavefront).
-constexpr int LM_CPW = 2;
-constexpr int LM_MAX_WAVE_CHUNKS = 4;
-__host__ __device__ static inline int ba_lm_blocks(int C, int kw) { return (C + LM_CPW * kw - 1) / (LM_CPW * kw); }  // workgroups of a wide solve
+// (LM_CPW, LM_MAX_WAVE_CHUNKS, ba_lm_blocks: lm_turns.h)
 __host__ __device__ static inline int ba_wire_elements(int K) { const int F = K - 1; return 18 * F * (F + 1) + 33 * F + 2; }
 __host__ __device__ static inline size_t ba_lm_union_doubles(int n, int K) { const size_t a = (size_t)LM_CPW * (size_t)wg_lds_doubles(ba_wire_elements(K)), b = ba_lm_ctl_doubles(n, K); return a > b ? a : b; }
 __host__ __device__ static inline size_t ba_lm_lds_doubles(int n, int K, int tab_words /* per chunk, a multiple of 4, <= TAB_LDS_WORDS */, int kw = 1) {
@@ -2335,21 +2334,9 @@ __device__ __forceinline__ bool lm_iterate(const BaDev& P, const LmDevArgs& a, L
   return ok;
 }
 
-// The chunks a wavefront of ba_lm_multi_kernel takes in turn: first, first + stride, ... (`count` of them lie below C).  Strided
-// (default): slot s = 2 x workgroup + wavefront takes s, s + S, s + 2 S, ... with S = 2 x workgroups, so neighbouring chunks — the
-// slow ones (a chunk of brand-new landmarks of the newest pose) come in runs — land on different wavefronts; contiguous: the
-// workgroup's own 2 kw chunks, alternating between its two wavefronts.
-struct LmTurns {
-  int first, stride, count;
-  __device__ __forceinline__ int chunk(int t) const { return first + t * stride; }
-};
+// The chunks this wavefront of ba_lm_multi_kernel takes in turn (lm_turns.h: the arithmetic, as a pure function that the host tests walk).
 __device__ __forceinline__ LmTurns lm_turns(int C, int kw, int n_blocks, bool contig) {
-  const int wave = threadIdx.x >> 6;
-  LmTurns T;
-  if (contig) { T.first = (int)blockIdx.x * LM_CPW * kw + wave; T.stride = LM_CPW; }
-  else { T.first = (int)blockIdx.x * LM_CPW + wave; T.stride = LM_CPW * n_blocks; }
-  T.count = T.first < C ? min(kw, (C - 1 - T.first) / T.stride + 1) : 0;
-  return T;
+  return lm_turns_of(C, kw, n_blocks, (int)blockIdx.x, (int)(threadIdx.x >> 6), contig);
 }
 
 // One command of ba_lm_multi_kernel: lm_iterate with every wavefront taking its Tn.count chunks in turn through its ONE staging area.
@@ -3187,6 +3174,8 @@ struct svo_ba {
   int device_lm = -1;            // svo_ba_set_device_lm: -1 automatic, 0 never, 1 whenever eligible
   int lm_form = -1;              // svo_ba_set_solve_form: which device-resident form — 0 wide (ba_lm_kernel: many workgroups, lowest latency), 1 compact (ba_lm_compact_kernel: one workgroup, smallest footprint), -1 automatic (SVO_BA_FORM, else wide)
   bool lm_compact_inflight = false;  // the launch in flight is the compact form (nothing admitted, no counter)
+  int lm_wave_chunks = 0;        // svo_ba_set_wave_chunks: chunks per wavefront of this adjuster's wide solves (0: the process default, raised where the admission budget asks for it)
+  long lm_k_solves[LM_MAX_WAVE_CHUNKS + 1] = {};  // svo_ba_solve_forms: device-resident solves launched in the compact form [0] and in the wide form at k chunks per wavefront [k]
   int lm_penalty = 0;            // solves left that avoid the wide form after one of its launches gave up
   long wide_launches = 0;        // (test hook SVO_BA_TEST_GIVEUP counts them)
   long fallbacks = 0;            // device-resident solves that gave up and were re-run (svo_lm_stats.fallbacks of the last solve: 0 / 1)
@@ -3363,6 +3352,11 @@ extern "C" void svo_ba_destroy(svo_ba* ba) {
     fprintf(stderr, "[svo ba] device-resident solves: %ld, %.1f LM iterations each; per solve (workgroup 0, us): total %.1f = waiting for the passes %.1f + step control %.1f "
                     "+ own share of the passes %.1f; steps %ld (same sweep %ld, next linearisation used %ld), stand-alone linearisations %ld\n", ba->lm_n, (double)ba->lm_iters / ba->lm_n, 1e-2 * ba->lm_t_total / ba->lm_n, 1e-2 * ba->lm_t_wait / ba->lm_n,
             1e-2 * ba->lm_t_ctl / ba->lm_n, 1e-2 * ba->lm_t_body / ba->lm_n, ba->lm_steps, ba->lm_same, ba->lm_used, ba->lm_lins);
+  if (getenv("SVO_TIMING") && ba->lm_n) {  // (svo_ba_solve_forms)
+    fprintf(stderr, "[svo ba] solve forms: compact %ld, wide at k = 1..%d:", ba->lm_k_solves[0], LM_MAX_WAVE_CHUNKS);
+    for (int k = 1; k <= LM_MAX_WAVE_CHUNKS; ++k) fprintf(stderr, " %ld", ba->lm_k_solves[k]);
+    fprintf(stderr, "; gave up %ld\n", ba->fallbacks);
+  }
   const bool wide_traced = ba->lm_iters_wide > 0 && ba->d_lmdbg != nullptr;  // (the split of the wide solves: per LM iteration of theirs)
   const double wi = (double)std::max(ba->lm_iters_wide, 1l), ci = (double)std::max(ba->lmc_iters, 1l);
   if (getenv("SVO_TIMING") && wide_traced)
@@ -3437,6 +3431,21 @@ void svo_ba_note_group_lanes(int delta) { g_group_lanes.fetch_add(delta, std::me
 extern "C" int svo_ba_set_solve_form(svo_ba* ba, int form) {
   if (!ba || form < -1 || form > 1) return SVO_ERR_INVALID;
   ba->lm_form = form;
+  return SVO_OK;
+}
+
+extern "C" int svo_ba_wave_chunks_limit(void) { return LM_MAX_WAVE_CHUNKS; }
+
+extern "C" int svo_ba_set_wave_chunks(svo_ba* ba, int k) {
+  if (!ba || k < 0 || k > LM_MAX_WAVE_CHUNKS) return SVO_ERR_INVALID;
+  ba->lm_wave_chunks = k;
+  return SVO_OK;
+}
+
+extern "C" int svo_ba_solve_forms(svo_ba* ba, long* counts, int n, long* gave_up) {
+  if (!ba || !counts || n < 1) return SVO_ERR_INVALID;
+  for (int i = 0; i < n; ++i) counts[i] = i <= LM_MAX_WAVE_CHUNKS ? ba->lm_k_solves[i] : 0;
+  if (gave_up) *gave_up = ba->fallbacks;
   return SVO_OK;
 }
 
@@ -3938,21 +3947,26 @@ int ba_fused_budget(int device) {
 // What `grid` workgroups of ba_lm_kernel with `lds` bytes of dynamic LDS cost in the units of that budget: a
 // larger reduced camera system (10-keyframe windows) lowers the kernel's occupancy, its workgroups then count for more.
 // (multi: ba_lm_multi_kernel's workgroups — the same 128 threads at 256 VGPRs; its kw chunk tables per wavefront make the LDS larger)
-int ba_lm_admission_cost(int grid, size_t lds, int device, bool multi = false) {
-  (void)ba_fused_budget(device);
+// workgroups per CU of the wide solve's kernel at `lds` bytes of dynamic LDS (0: the query failed)
+int ba_lm_per_cu(size_t lds, bool multi) {
   static std::mutex mu;
-  static size_t cached_lds[8];
-  static int cached_per_cu[8], n_cached = 0;
+  constexpr int N_CACHED = 32;  // (lds grows with k and with the chunk tables' size: a few dozen values per process)
+  static size_t cached_lds[N_CACHED];
+  static int cached_per_cu[N_CACHED], n_cached = 0;
   int per_cu = 0;
   const size_t key = lds | (multi ? (size_t)1 << 62 : 0);
-  {
-    std::lock_guard<std::mutex> g(mu);
-    for (int i = 0; i < n_cached; ++i) if (cached_lds[i] == key) per_cu = cached_per_cu[i];
-    if (!per_cu) {
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, multi ? ba_lm_multi_kernel : ba_lm_kernel, 128, lds) != hipSuccess || per_cu <= 0) return 1 << 30;
-      if (n_cached < 8) { cached_lds[n_cached] = key; cached_per_cu[n_cached++] = per_cu; }
-    }
+  std::lock_guard<std::mutex> g(mu);
+  for (int i = 0; i < n_cached; ++i) if (cached_lds[i] == key) per_cu = cached_per_cu[i];
+  if (!per_cu) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, multi ? ba_lm_multi_kernel : ba_lm_kernel, 128, lds) != hipSuccess || per_cu <= 0) return 0;
+    if (n_cached < N_CACHED) { cached_lds[n_cached] = key; cached_per_cu[n_cached++] = per_cu; }
   }
+  return per_cu;
+}
+int ba_lm_admission_cost(int grid, size_t lds, int device, bool multi = false) {
+  (void)ba_fused_budget(device);
+  const int per_cu = ba_lm_per_cu(lds, multi);
+  if (per_cu <= 0) return 1 << 30;
   if (per_cu >= g_fused_per_cu) return grid;
   return (grid * g_fused_per_cu + per_cu - 1) / per_cu;
 }
@@ -3977,9 +3991,11 @@ bool ba_device_lm_wanted() {
 int ba_lm_tab_words(const svo_ba* ba) { return std::max(64, (ba->tab_max_words + 63) & ~63); }
 size_t ba_lm_lds_bytes(const svo_ba* ba, int kw) { return sizeof(double) * ba_lm_lds_doubles(ba->d.n, ba->d.K, ba_lm_tab_words(ba), kw); }
 
-// Chunks per wavefront of a wide solve (ba_lm_multi_kernel for more than one).  SVO_BA_WAVE_CHUNKS=1..4 (developer knob);
-// SVO_BA_WAVE_ORDER=contiguous gives a wavefront neighbouring chunks instead of one per stride (see lm_turns).  Windows of more
-// than 128 chunks (ba_lm_grouped_kernel) keep one chunk per wavefront; so do solves of no more than two chunks (one workgroup either way).
+// Chunks per wavefront a wide solve is offered to the admission with (ba_lm_multi_kernel for more than one; a solve the budget
+// refuses at this k is offered again at larger ones, see ba_device_lm_launch).  SVO_BA_WAVE_CHUNKS=1..LM_MAX_WAVE_CHUNKS (developer
+// knob), svo_ba_set_wave_chunks for one adjuster; SVO_BA_WAVE_ORDER=contiguous gives a wavefront neighbouring chunks instead of one
+// per stride (see lm_turns.h).  Windows of more than 128 chunks (ba_lm_grouped_kernel) keep one chunk per wavefront; so do solves of
+// no more than two chunks (one workgroup either way).
 constexpr int LM_WAVE_CHUNKS_DEFAULT = 3;
 int ba_lm_wave_chunks(const svo_ba* ba) {
   static const int env = [] {
@@ -3988,7 +4004,7 @@ int ba_lm_wave_chunks(const svo_ba* ba) {
     return v < 1 ? 1 : (v > LM_MAX_WAVE_CHUNKS ? LM_MAX_WAVE_CHUNKS : v);
   }();
   if (ba->d.G > 1 || ba->d.C <= LM_CPW) return 1;
-  return env;
+  return ba->lm_wave_chunks > 0 ? ba->lm_wave_chunks : env;
 }
 bool ba_lm_wave_contig() {
   static const bool contig = [] { const char* e = getenv("SVO_BA_WAVE_ORDER"); return e && e[0] == 'c'; }();
@@ -4107,7 +4123,27 @@ int ba_device_lm_launch(svo_ba** bas, int n, hipStream_t st, bool forced, unsign
     if (ba_wants_compact(ba)) { to_compact[i] = true; continue; }
     if (!ba_device_lm_fill(ba, &cost, &lds, forced)) continue;
     if (lds > 32 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) != hipSuccess) continue;
-    if (!ba_resident_admission(ba)->admit(cost, ba->ctx->device)) { to_compact[i] = overflow; continue; }
+    bool admitted = ba_resident_admission(ba)->admit(cost, ba->ctx->device);
+    if (!admitted && form == 2 && ba->lm_wave_chunks <= 0) {
+      // The budget refuses the solve at the default k: it rides this launch on fewer workgroups — the first larger k that fits, as
+      // long as the kernel's workgroups per CU at that k's LDS (k chunk tables per wavefront) stay what they are at the default, so
+      // that the launch's dynamic LDS (the maximum over its solves) takes no residency from the solves beside it.  Same kernel, same
+      // hand-overs, every chunk posts its own partials: the same bits.  What is charged is the cost at the k and the LDS it runs with.
+      const int k0 = ba->h_lane->a.wave_chunks, dev = ba->ctx->device;
+      const int per_cu0 = ba_lm_per_cu(lds, true);
+      int blocks = ba_lm_blocks(ba->d.C, k0);
+      for (int k = k0 + 1; k <= LM_MAX_WAVE_CHUNKS && !admitted; ++k) {
+        if (ba_lm_blocks(ba->d.C, k) == blocks) continue;  // (no workgroup saved)
+        blocks = ba_lm_blocks(ba->d.C, k);
+        const size_t lds_k = ba_lm_lds_bytes(ba, k);
+        if (lds_k > 120 * 1024 || per_cu0 <= 0 || ba_lm_per_cu(lds_k, true) < per_cu0) break;
+        if (lds_k > 32 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) != hipSuccess) break;
+        const int cost_k = ba_lm_admission_cost(blocks, lds_k, dev, true);
+        admitted = ba_resident_admission(ba)->admit(cost_k, dev);
+        if (admitted) { ba->h_lane->a.wave_chunks = k; lds = lds_k; }
+      }
+    }
+    if (!admitted) { to_compact[i] = overflow; continue; }
     // the counter starts from zero: cleared in front of the launch (the adjuster's previous solve no longer touches it
     // once its completion word is out)
     if (ba->lm_counters_dirty || !ba->lm_have_base) {
@@ -4140,6 +4176,7 @@ int ba_device_lm_launch(svo_ba** bas, int n, hipStream_t st, bool forced, unsign
       if (ba->arena_dirty) ba->arena_partial = true;  // the kernel reads the host image in place: the device arena holds the landmark buffers only
       ba->arena_dirty = false;
       ba->lm_inflight = true; ba->lm_compact_inflight = false;
+      ++ba->lm_k_solves[std::min(std::max(ba->h_lane->a.wave_chunks, 1), LM_MAX_WAVE_CHUNKS)];
       ba->lm_stream = st;
       ba->res_export = ba->h_lane->a.export_points != nullptr;
       if (launched_mask) *launched_mask |= 1ull << tidx[i];
@@ -4187,6 +4224,7 @@ int ba_device_lm_launch(svo_ba** bas, int n, hipStream_t st, bool forced, unsign
         if (ba->arena_dirty) ba->arena_partial = true;  // the host image keeps the INITIAL state (see ba_refresh_arena_image)
         ba->arena_dirty = false;
         ba->lm_inflight = true; ba->lm_compact_inflight = true;
+      ++ba->lm_k_solves[0];
         ba->lm_stream = st;
         ba->res_export = ba->h_lane->a.export_points != nullptr;
         if (launched_mask) *launched_mask |= 1ull << cidx[k];
@@ -4681,6 +4719,37 @@ extern "C" int svo_ba_solve_problem(svo_ba* ba, svo_ba_summary* summary) {
   return rc;
 }
 
+extern "C" int svo_ba_solve_problems(svo_ba** bas, int n, svo_ba_summary* summaries) {
+  if (!bas || n < 1 || n > SVO_MAX_LANES) return SVO_ERR_INVALID;
+  for (int i = 0; i < n; ++i) if (!bas[i] || bas[i]->d.K < 1) return SVO_ERR_INVALID;
+  svo_use_device(bas[0]->ctx);
+  for (int i = 0; i < n; ++i) {
+    memset(&bas[i]->stats, 0, sizeof(bas[i]->stats));
+    if (summaries) memset(&summaries[i], 0, sizeof(summaries[i]));
+    if (bas[i]->stream != bas[0]->stream) SVO_HIP_CHECK(bas[i]->ctx, hipStreamSynchronize(bas[i]->stream));  // its upload, before another stream's kernel reads it
+  }
+  unsigned long long mask = 0;
+  const int launched = ba_device_lm_launch(bas, n, bas[0]->stream, true, &mask);
+  int first_error = 0;
+  for (int i = 0; i < n; ++i) {
+    svo_ba* ba = bas[i];
+    svo_ba_summary* sum = summaries ? &summaries[i] : nullptr;
+    int rc;
+    if ((mask >> i) & 1ull) {
+      rc = ba_device_lm_end(ba, sum); ba->d.flag = nullptr;
+      if (rc == SVO_OK) { if (ba->lm_penalty > 0) --ba->lm_penalty; }
+      else {  // gave up: the problem is still loaded — again, compact form or host-driven (see svo_ba_solve_finish)
+        ba_after_giveup(ba);
+        rc = ba_lm(ba, sum);
+        if (rc == SVO_OK) { ba->stats.fallbacks = 1; ba->ctx->err.clear(); }
+      }
+    } else rc = ba_lm(ba, sum);  // not eligible or not admitted: on its own
+    if (!rc) ba->upload_pending = false;
+    else if (!first_error) first_error = rc;  // (the others are still joined: nothing stays in flight)
+  }
+  return first_error ? first_error : launched;
+}
+
 extern "C" int svo_ba_read_problem(svo_ba* ba, double* poses7, double* points3) {
   if (!ba) return SVO_ERR_INVALID;
   svo_ctx* ctx = ba->ctx;
@@ -4888,6 +4957,8 @@ int svo_ba_solve_poll(svo_ba* ba) {
   const int v = __atomic_load_n(ba->h_flag, __ATOMIC_ACQUIRE);
   return (v == ba->seq || (v == -ba->seq && ba->seq != 0)) ? 1 : 0;  // published, or gave up (svo_ba_solve_finish re-runs it): either way the join will not wait
 }
+
+int svo_ba_solve_holds_budget(svo_ba* ba) { return ba && ba->lm_inflight && !ba->lm_compact_inflight ? 1 : 0; }
 
 // finish: join the launched solve (or, if none was launched for this adjuster, run the host-driven loop now) and write
 // poses and landmarks back into the graph (src/bundle_adjuster.cpp:146-155).

@@ -576,6 +576,21 @@ extern "C" int svo_pipeline_group_solve_work(svo_pipeline_group* g, double* out4
   return SVO_OK;
 }
 
+extern "C" int svo_pipeline_group_solve_forms(svo_pipeline_group* g, long* counts, int n, long* gave_up) {
+  if (!g || !counts || n < 1) return SVO_ERR_INVALID;
+  std::vector<long> c((size_t)n);
+  for (int i = 0; i < n; ++i) counts[i] = 0;
+  if (gave_up) *gave_up = 0;
+  for (Lane* l : g->lanes) {
+    long gu = 0;
+    const int rc = svo_ba_solve_forms(l->ba, c.data(), n, &gu);
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i) counts[i] += c[(size_t)i];
+    if (gave_up) *gave_up += gu;
+  }
+  return SVO_OK;
+}
+
 extern "C" int svo_pipeline_group_last_stats(const svo_pipeline_group* g, long* launches6, long* lanes6) {
   if (!g || !launches6 || !lanes6) return SVO_ERR_INVALID;
   for (int i = 0; i < 6; ++i) { launches6[i] = g->launches[i]; lanes6[i] = g->lanes_carried[i]; }
@@ -1146,9 +1161,17 @@ extern "C" int svo_pipeline_group_process_batch_dev(svo_pipeline_group* g, const
             EV(cand[k], "ba_launch", launched);
             l->ba_launch = g->ba_launch_id; l->ba_line = free_line; l->ba_ready_seq = 0; l->ba_state.store(BA_INFLIGHT, std::memory_order_release);
           }
-          if (not_taken >= 0 && g->n_cmp > 0 && !host_solves) {
-            // compact lines (SVO_GROUP_COMPACT_LINES, round 5): what the admission budget refused leaves at once in the one-workgroup
-            // form — no budget, 3-4x the latency — on a line of its own, so that the wide launches' lines stay free
+          // A refused solve waits for the group's next wide launch while a wide solve of this group is in flight: joining it hands
+          // budget back, the solve is offered again in the next pass (at a larger k if need be, ba_device_lm_launch) and rides a launch
+          // that costs the same queue time with or without it — one workgroup for 6 ms holds a hardware queue that the tracking line
+          // shares (4 queues: 12.25 against 12.05 k frames/s at 96 lanes, profiles/r08_runs.txt).
+          bool wide_inflight = false;
+          for (int li = 0; li < S; ++li)
+            wide_inflight |= g->lanes[li]->ba_state.load(std::memory_order_acquire) == BA_INFLIGHT && svo_ba_solve_holds_budget(g->lanes[li]->ba);
+          if (not_taken >= 0 && g->n_cmp > 0 && !host_solves && !wide_inflight) {
+            // compact lines (SVO_GROUP_COMPACT_LINES, round 5): what the admission budget refused while nothing of this group holds any
+            // of it leaves at once in the one-workgroup form — no budget, 3-4x the latency — on a line of its own, so that the wide
+            // launches' lines stay free
             int cline = -1;
             for (int i = g->n_ba; i < g->n_ba + g->n_cmp; ++i) if (!ba_line_busy[i]) { cline = i; break; }
             if (cline >= 0) {
