@@ -59,6 +59,7 @@ class BundleAdjuster {
 
   // ---- adapter plumbing (not part of the reference surface)
   const shared_ptr<svo::BundleAdjuster> &impl() const { return impl_; }
+  const CameraInfo &info() const { return camera_info; }  // what ImageProcessor undistorts with (SVO_ADAPTER_UNDISTORT=1)
   void note_keyframe_image(const cv::Mat &image) { pending_image = image; }  // ImageProcessor: image of the keyframe it just added
 
  private:

@@ -6,7 +6,7 @@
 
 struct CameraInfo {
   double focal, cx, cy;   // intrinsics
-  double k1, k2, p1, p2;  // distortion (never read on this path)
+  double k1, k2, p1, p2;  // distortion: applied to both eyes by ImageProcessor when SVO_ADAPTER_UNDISTORT=1, else never read
   double baseline;
 };
 

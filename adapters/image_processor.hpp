@@ -38,6 +38,8 @@ class ImageProcessor {
   float min_feature_distance;
   float parallax_thresh;
   unique_ptr<svo::ImageProcessor> impl_;
+  bool undistort_ = false, undistort_ready_ = false;  // SVO_ADAPTER_UNDISTORT=1 (image_processor.cpp)
+  bool ensure_undistortion(int w, int h);
 };
 
 #endif

@@ -38,7 +38,10 @@ typedef enum svo_status {
 } svo_status;
 
 /* Mirrors struct CameraInfo, src/camera_info.hpp:4-18 (same field order, so a
- * reference CameraInfo can be reinterpret_cast). k1..p2 are never read. */
+ * reference CameraInfo can be reinterpret_cast).  focal/cx/cy/baseline describe the ideal, row-aligned pinhole pair
+ * every stage works in.  k1..p2 (src/camera_info.hpp:10-14) are not read by svo_pipeline_create, svo_ba_create or any
+ * stage: they are honoured where the caller asks for it, through svo_rectify_eye_from_camera_info and the
+ * svo_*_set_rectification entries below (the reference itself passes zeros, src/vo_node.cpp:110). */
 typedef struct svo_camera_info {
   double focal, cx, cy;
   double k1, k2, p1, p2;
@@ -89,7 +92,8 @@ int svo_reference_constants(svo_reference_constants_t* out);
 
 /* Measurement aid (not a reference interface): time every launch of ONE named kernel with HIP events
  * recorded on the context stream.  kernel: "corner_response", "corner_nms", "corner_select", "pyr_down",
- * "lk_fb", "stereo_at", "triangulate", "pnp_hypotheses", "pnp_refine", "ba_linearize", "ba_backsub", "ba_step";
+ * "lk_fb", "stereo_at", "triangulate", "pnp_hypotheses", "pnp_refine", "ba_linearize", "ba_backsub", "ba_step",
+ * "rectify_remap";
  * NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
@@ -98,6 +102,42 @@ int svo_profile_select(svo_ctx* ctx, const char* kernel);
  * "f64_mfma" (v_mfma_f64_16x16x4_f64), "hbm_copy" (512 MiB device copy).  *value: flop/s or bytes/s (read + write). */
 int svo_measure_peak(svo_ctx* ctx, const char* what, double* value);
 int svo_profile_read(svo_ctx* ctx, double* total_ms, int* launches);
+
+/* ------------------------------------------------------------- rectification --
+ * Raw (distorted, not row-aligned) stereo pairs -> the ideal pinhole pair the pipeline assumes, on the device.  The
+ * reference has no counterpart: it carries k1, k2, p1, p2 in CameraInfo (src/camera_info.hpp:10-14), never reads them and
+ * is fed rectified images (src/vo_node.cpp:110).  One svo_rectify_eye describes one RAW camera; the rectified camera is
+ * the svo_camera_info (focal, cx, cy) of the call, the same for both eyes.  Raw and rectified images have the same size.
+ *
+ * The warp is a precomputed table (one 4-byte record per destination pixel) applied by rectify_remap_kernel:
+ *   map   all f64, every operation rounded separately, only + - x / and rint (host/rectify.cpp states the order): the
+ *         construction of OpenCV's initUndistortRectifyMap followed by its 1/32-pixel fixed-point maps.  Record of pixel
+ *         (u, v): int16 dx = qx - 32 u, int16 dy = qy - 32 v with (qx, qy) the source position in 1/32 pixels;
+ *         (-32768, -32768) = no source (behind the camera, non-finite, or all four taps outside the raw image);
+ *   remap bilinear in exact integers: weights (32-ax)(32-ay), ax(32-ay), (32-ax)ay, ax ay (sum 1024), output
+ *         (sum w p + 512) >> 10, a tap outside the raw image contributes 0, a pixel without source is 0.  The intent: the
+ *         integers of OpenCV's fixed-point INTER_LINEAR remap with a constant-0 border (its 15-bit table is these weights
+ *         times 32); what is pinned by the tests is the arithmetic declared here. */
+typedef struct svo_rectify_eye {
+  double fx, fy, cx, cy;   /* camera matrix of the RAW image */
+  double k1, k2, p1, p2;   /* Brown-Conrady coefficients, in CameraInfo's order (src/camera_info.hpp:10-14) */
+  double R[9];             /* row-major rotation raw camera -> rectified camera (identity: undistortion only) */
+} svo_rectify_eye;
+/* The monocular case of a CameraInfo (src/camera_info.hpp:4-18): fx = fy = focal, the same centre, k1..p2 copied, R = I. */
+int svo_rectify_eye_from_camera_info(const svo_camera_info* cam, svo_rectify_eye* eye);
+/* The table itself (src/camera_info.hpp:10-14 are its coefficients).  Host-only, needs no GPU.  dxdy: width x height x 2
+ * int16, row-major, (dx, dy) per pixel.  A source inside the raw image whose displacement does not fit an int16 (beyond
+ * +-32767 / 32 px) is never clipped: SVO_ERR_INVALID, and svo_last_error(NULL) names it (per thread). */
+int svo_rectify_build_map(const svo_rectify_eye* eye, const svo_camera_info* cam, int width, int height, int16_t* dxdy);
+/* One image, HOST pointers (coefficients: src/camera_info.hpp:10-14): out (tight rows) = raw warped by the table of
+ * (eye, cam).  Stand-alone use; also how a caller gets the rectified keyframe image svo_pipeline_draw_track wants. */
+int svo_rectify_remap(svo_ctx* ctx, const uint8_t* raw, int width, int height, int row_stride, const svo_rectify_eye* eye,
+                      const svo_camera_info* cam, uint8_t* out);
+/* `batch` images of one camera (src/camera_info.hpp:10-14), DEVICE pointers, one launch: raw images image_stride bytes
+ * apart with rows row_stride bytes apart; out: tight rows, images width*height bytes apart.  The table is built and
+ * uploaded by the call (synchronous with respect to the host, asynchronous launch on svo_stream(ctx)). */
+int svo_rectify_remap_batch_dev(svo_ctx* ctx, const uint8_t* raw, int batch, int width, int height, int row_stride,
+                                size_t image_stride, const svo_rectify_eye* eye, const svo_camera_info* cam, uint8_t* out);
 
 /* ------------------------------------------------------------------ a11 --
  * Batched ReprojectionFactor::Evaluate (src/reprojection_factor.cpp:10-88).
@@ -407,6 +447,11 @@ int svo_pipeline_process_batch_dev(svo_pipeline* p, const uint8_t* left, const u
                                    int batch, svo_frame_result* results);
 int svo_pipeline_process_batch(svo_pipeline* p, const uint8_t* left, const uint8_t* right,
                                int batch, svo_frame_result* results);
+/* Raw input (coefficients of src/camera_info.hpp:10-14, per eye): builds both tables for the pipeline's camera and size,
+ * uploads them and allocates the rectified workspace (max_batch x 2 x width x height bytes) once; nothing is allocated per
+ * frame afterwards.  svo_pipeline_process_batch_dev / _batch then take left/right as RAW images: one remap launch in
+ * front, every stage reads the rectified copy.  NULL, NULL turns it off and frees both.  Never called: nothing changes. */
+int svo_pipeline_set_rectification(svo_pipeline* p, const svo_rectify_eye* left, const svo_rectify_eye* right);
 /* Feature-set taps for parity tests: ids + positions the tracker holds after the last frame. */
 int svo_pipeline_get_tracked(svo_pipeline* p, int64_t* ids, float* xy, int capacity, int* n);
 
@@ -444,6 +489,12 @@ int svo_pipeline_group_upload(svo_pipeline_group* g, int slot, int batch);
 int svo_pipeline_group_process_uploaded(svo_pipeline_group* g, int slot, svo_frame_result* results);
 int svo_pipeline_group_process_batch(svo_pipeline_group* g, const uint8_t* left, const uint8_t* right, size_t lane_stride,
                                      int batch, svo_frame_result* results);
+/* svo_pipeline_set_rectification for lane `lane` (-1: every lane; coefficients of src/camera_info.hpp:10-14 per eye).  Lanes
+ * may have different cameras; lanes set from the same pair of models share one copy of the tables in HBM.  Covers
+ * svo_pipeline_group_process_batch_dev, _process_uploaded and _process_batch alike: ONE remap launch per call for all
+ * rectified lanes, issued on the processing side (after the slot's upload has been waited for, so the streaming loop's
+ * overlap of upload and processing is untouched); lanes without a model are neither remapped nor copied. */
+int svo_pipeline_group_set_rectification(svo_pipeline_group* g, int lane, const svo_rectify_eye* left, const svo_rectify_eye* right);
 int svo_pipeline_group_get_tracked(svo_pipeline_group* g, int lane, int64_t* ids, float* xy, int capacity, int* n);
 /* Launch statistics of the last process_batch call, by stage: 0 track (LK + compaction), 1 PnP-RANSAC (hypotheses, bookkeeping and
  * refinement in one launch), 3 dedup / stereo + triangulation, 4 bundle-adjustment solves, 5 corner detection + pyramids;

@@ -25,6 +25,35 @@ class CameraInfo(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("focal", "cx", "cy", "k1", "k2", "p1", "p2", "baseline")]
 
 
+class RectifyEye(C.Structure):
+    """svo_rectify_eye: one RAW camera (matrix, Brown-Conrady k1 k2 p1 p2, rotation raw -> rectified, row-major)."""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double), ("R", C.c_double * 9)]
+
+
+def rectify_eye(fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, R=None):
+    R = np.eye(3) if R is None else np.asarray(R, np.float64).reshape(3, 3)
+    return RectifyEye(fx, fy, cx, cy, k1, k2, p1, p2, (C.c_double * 9)(*R.reshape(-1)))
+
+
+def rectify_eye_from_camera_info(cam):
+    """svo_rectify_eye_from_camera_info: the monocular case (fx = fy = focal, same centre, R = I)."""
+    e = RectifyEye()
+    if lib().svo_rectify_eye_from_camera_info(C.byref(cam), C.byref(e)) != 0:
+        raise SvoError("svo_rectify_eye_from_camera_info failed")
+    return e
+
+
+def rectify_build_map(eye, cam, width, height):
+    """svo_rectify_build_map (host only): (height, width, 2) int16 records (dx, dy) in 1/32 px, (-32768, -32768) = no source."""
+    L = lib()
+    out = np.empty((height, width, 2), np.int16)
+    rc = L.svo_rectify_build_map(C.byref(eye), C.byref(cam), width, height, _p(out))
+    if rc:
+        raise SvoError(f"svo_rectify_build_map rc={rc}: {L.svo_last_error(None).decode()}")
+    return out
+
+
 class BAOptions(C.Structure):
     _fields_ = [("max_iterations", C.c_int), ("max_time_s", C.c_double),
                 ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double),
@@ -169,6 +198,8 @@ SYMBOLS = [
     "svo_pipeline_group_solve_work", "svo_pipeline_group_solve_forms", "svo_pipeline_group_staging", "svo_pipeline_group_upload", "svo_pipeline_group_process_uploaded", "svo_pipeline_group_process_batch",
     "svo_synth_default_params", "svo_synth_render", "svo_synth_pose",
     "svo_image_read_gray", "svo_kitti_read_poses", "svo_ate_rmse", "svo_kitti_run", "svo_cholesky_solve", "svo_cholesky_solve_dev", "svo_draw_track", "svo_pipeline_draw_track",
+    "svo_rectify_eye_from_camera_info", "svo_rectify_build_map", "svo_rectify_remap", "svo_rectify_remap_batch_dev",
+    "svo_pipeline_set_rectification", "svo_pipeline_group_set_rectification",
 ]
 
 
@@ -317,6 +348,22 @@ class Context:
                                            C.c_double(min_distance), _p(xy), C.byref(n)),
                   "svo_corner_detect")
         return xy[:n.value].copy()
+
+    # ---- rectification
+    def rectify_remap(self, raw, eye, cam):
+        """svo_rectify_remap: raw (H, W) uint8 host image (any row stride) -> rectified (H, W)."""
+        raw = np.asarray(raw, np.uint8)
+        if raw.strides[1] != 1:
+            raw = np.ascontiguousarray(raw)
+        h, w = raw.shape
+        out = np.empty((h, w), np.uint8)
+        self._chk(self.L.svo_rectify_remap(self.h, _p(raw), w, h, raw.strides[0], C.byref(eye), C.byref(cam), _p(out)), "svo_rectify_remap")
+        return out
+
+    def rectify_remap_batch_dev(self, raw_ptr, batch, width, height, row_stride, image_stride, eye, cam, out_ptr):
+        """svo_rectify_remap_batch_dev: raw device pointers (ints); out: batch tight (H, W) images."""
+        self._chk(self.L.svo_rectify_remap_batch_dev(self.h, C.c_void_p(raw_ptr), batch, width, height, row_stride, C.c_size_t(image_stride),
+                                                     C.byref(eye), C.byref(cam), C.c_void_p(out_ptr)), "svo_rectify_remap_batch_dev")
 
     # ---- a7
     def stereo_bm(self, left, right, ndisp=48, block=21):
@@ -597,6 +644,12 @@ class Pipeline:
     def reset(self):
         self.ctx._chk(self.L.svo_pipeline_reset(self.h), "svo_pipeline_reset")
 
+    def set_rectification(self, left=None, right=None):
+        """svo_pipeline_set_rectification: RectifyEye per eye (left/right are raw images from then on); None, None: off."""
+        self.L.svo_pipeline_set_rectification.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self.ctx._chk(self.L.svo_pipeline_set_rectification(self.h, C.byref(left) if left is not None else None,
+                                                            C.byref(right) if right is not None else None), "svo_pipeline_set_rectification")
+
     def process_batch(self, left, right):
         """left/right: (B, H, W) uint8 host arrays."""
         left, right = _u8(left), _u8(right)
@@ -653,6 +706,13 @@ class PipelineGroup:
 
     def reset(self):
         self.ctx._chk(self.L.svo_pipeline_group_reset(self.h), "svo_pipeline_group_reset")
+
+    def set_rectification(self, lane, left=None, right=None):
+        """svo_pipeline_group_set_rectification: lane -1 = every lane; None, None turns the lane's rectification off."""
+        self.L.svo_pipeline_group_set_rectification.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self.ctx._chk(self.L.svo_pipeline_group_set_rectification(self.h, lane, C.byref(left) if left is not None else None,
+                                                                  C.byref(right) if right is not None else None),
+                      "svo_pipeline_group_set_rectification")
 
     def process_batch_dev(self, left_ptr, right_ptr, lane_stride, batch):
         """left_ptr/right_ptr: raw device pointers to (n_lanes, B, H, W) uint8 images (lane_stride bytes between lanes).

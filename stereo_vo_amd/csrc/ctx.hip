@@ -4,10 +4,16 @@
 #include <sched.h>
 
 #include "common.h"
+#include "kernels.h"
 
 extern "C" const char* svo_version(void) { return "stereo_vo_amd 0.1 (gfx950, HIP, wave64)"; }
 
-extern "C" const char* svo_last_error(const svo_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
+// ctx == NULL: the text of the calling thread's last context-free call that failed (svo_rectify_build_map)
+extern "C" const char* svo_last_error(const svo_ctx* ctx) {
+  if (ctx) return ctx->err.c_str();
+  const char* t = svo_rectify_error_text();
+  return *t ? t : "null context";
+}
 
 extern "C" void* svo_stream(svo_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
@@ -22,7 +28,7 @@ extern "C" int svo_profile_select(svo_ctx* ctx, const char* kernel) {
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
   static const char* names[] = {"", "corner_response", "corner_nms", "corner_select", "pyr_down", "lk_fb", "stereo_at",
-                                "triangulate", "pnp_hypotheses", "pnp_refine", "ba_linearize", "ba_backsub", "ba_step"};
+                                "triangulate", "pnp_hypotheses", "pnp_refine", "ba_linearize", "ba_backsub", "ba_step", "rectify_remap"};
   int tag = 0;
   if (kernel && kernel[0]) {
     tag = -1;

@@ -56,4 +56,28 @@ int svo_k_pnp(svo_ctx* ctx, SvoScratch& s, const float* d_xyz, const float* d_xy
               double* rvec3, double* tvec3, int iterations, float reproj_err, double confidence, int* d_inliers,
               int* n_inliers, int* h_inliers = nullptr /* pinned: also receives the inlier list */,
               float* d_inlier_xy = nullptr /* device: xy of the inliers, in list order (the dedup stage's input) */);
+// rectification (csrc/rectify.hip, host/rectify.cpp): ONE launch warps every image of a call.  Image z of the launch is
+// (active lane k, frame f, eye e) = (z / eyes / frames, z / eyes % frames, z % eyes); active lane k is lane `lane[k]` of the
+// caller's layout and reads the tables map[k][e] (int32 records, dx in the low half, tight rows of `width`).
+constexpr int SVO_RECT_MAX_LANES = 64;
+constexpr int SVO_RECT_SENTINEL = (int)0x80008000u;  // (dx, dy) = (-32768, -32768): no source
+struct SvoRectifyArgs {
+  const uint8_t* src[2];  // per eye: lane 0's first raw image
+  uint8_t* dst[2];        // per eye: lane 0's first rectified image (tight rows)
+  size_t src_lane_stride, src_image_stride, dst_lane_stride, dst_image_stride;
+  int src_row_stride, width, height, frames, eyes, n_active;
+  const int* map[SVO_RECT_MAX_LANES][2];
+  unsigned char lane[SVO_RECT_MAX_LANES];
+};
+int svo_k_rectify_remap(svo_ctx* ctx, const SvoRectifyArgs& a, hipStream_t st);
+// The tables of one stereo camera (or of one eye: right == nullptr) in HBM, shared by every lane set from the same models.
+struct SvoRectModel {
+  svo_rectify_eye eye[2];
+  int* d_map[2] = {nullptr, nullptr};
+  int refs = 0;
+};
+int svo_rect_model_create(svo_ctx* ctx, const svo_rectify_eye* left, const svo_rectify_eye* right, const svo_camera_info* cam,
+                          int width, int height, SvoRectModel** out);
+void svo_rect_model_destroy(SvoRectModel* m);
+const char* svo_rectify_error_text();  // of the calling thread's last context-free rectification call ("" if none failed)
 #endif

@@ -202,6 +202,11 @@ struct svo_pipeline_group {
   hipStream_t st_copy = nullptr;
   hipEvent_t ev_up[2] = {nullptr, nullptr};
   int up_batch[2] = {0, 0};  // frames per lane of the upload in flight / completed in the slot (0: none)
+  // raw input (svo_pipeline_group_set_rectification): the distinct cameras' tables, which one each lane uses (null: the lane's
+  // images are rectified already), and the rectified workspace [left / right]: n_lanes x max_batch images, allocated with the first model
+  std::vector<SvoRectModel*> rect_models;
+  SvoRectModel* lane_rect[SVO_MAX_LANES] = {};
+  uint8_t* d_rect[2] = {nullptr, nullptr};
 };
 
 namespace {
@@ -308,6 +313,8 @@ extern "C" void svo_pipeline_group_destroy(svo_pipeline_group* g) {
     for (int e = 0; e < 2; ++e) { if (g->h_stage[sl][e]) (void)hipHostFree(g->h_stage[sl][e]); if (g->d_stage[sl][e]) (void)hipFree(g->d_stage[sl][e]); }
   }
   for (Lane* l : g->lanes) { if (l->ba) svo_ba_destroy(l->ba); delete l; }
+  for (SvoRectModel* m : g->rect_models) svo_rect_model_destroy(m);
+  for (int e = 0; e < 2; ++e) if (g->d_rect[e]) (void)hipFree(g->d_rect[e]);
   for (void* p : g->dev_allocs) (void)hipFree(p);
   for (void* p : g->pin_allocs) (void)hipHostFree(p);
   delete g;
@@ -597,17 +604,18 @@ extern "C" int svo_pipeline_group_last_stats(const svo_pipeline_group* g, long* 
   return SVO_OK;
 }
 
-extern "C" int svo_pipeline_group_process_batch_dev(svo_pipeline_group* g, const uint8_t* left, const uint8_t* right, size_t lane_stride,
-                                                    int batch, svo_frame_result* results) {
-  if (!g) return SVO_ERR_INVALID;
+namespace {
+// The batch itself.  lbase[l] / rbase[l]: lane l's `batch` rectified images (tight rows, width*height bytes apart), wherever
+// they live: the caller's buffers, or the rectified workspace for a lane with a camera model.
+int group_process(svo_pipeline_group* g, const uint8_t* const* lbase, const uint8_t* const* rbase, int batch, svo_frame_result* results) {
   svo_ctx* ctx = g->ctx;
-  SVO_REQUIRE(ctx, left && right && results && batch >= 1 && batch <= g->max_batch, "pipeline_group_process_batch: bad arguments");
   const int W = g->prm.width, H = g->prm.height, S = g->n_lanes, mc = g->prm.max_corners;
   const size_t istride = (size_t)W * H;
-  SVO_REQUIRE(ctx, lane_stride >= istride * (size_t)batch, "pipeline_group_process_batch: lanes overlap");
-  ctx->err.clear();
-  SVO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
+  bool tight = true;  // the lanes' images are one contiguous run: the batch-wide launches take all of them at once
+  for (int l = 1; l < S; ++l) tight = tight && lbase[l] == lbase[0] + (size_t)l * batch * istride;
+  const uint8_t* const left = lbase[0];
+  const size_t lane_stride = istride * (size_t)batch;  // (of the contiguous case)
   for (int i = 0; i < 6; ++i) { g->launches[i] = 0; g->lanes_carried[i] = 0; }
 
   // ---- a1 on every frame of every lane + the pyramids (the reference detects on every frame, src/image_processor.cpp:22)
@@ -628,7 +636,7 @@ extern "C" int svo_pipeline_group_process_batch_dev(svo_pipeline_group* g, const
       l->last_l0 = l->d_own_pyr;
     }
   }
-  if (lane_stride == istride * (size_t)batch) {
+  if (tight) {
     rc = svo_corner_detect_batch_dev(ctx, left, S * batch, W, H, W, istride, mc, g->prm.quality, (double)g->prm.min_feature_distance, g->d_corners, g->d_ncorners);
     // level 0 of the pyramids is NOT copied: the tracker reads the caller's images in place (Pyr::l0) — except every lane's
     // last frame, which the next batch tracks from when the caller's buffer may hold other frames
@@ -637,10 +645,10 @@ extern "C" int svo_pipeline_group_process_batch_dev(svo_pipeline_group* g, const
                                        (size_t)batch * g->pyr_stride, st);
   } else {
     for (int l = 0; l < S && !rc; ++l) {
-      rc = svo_corner_detect_batch_dev(ctx, left + l * lane_stride, batch, W, H, W, istride, mc, g->prm.quality, (double)g->prm.min_feature_distance,
+      rc = svo_corner_detect_batch_dev(ctx, lbase[l], batch, W, H, W, istride, mc, g->prm.quality, (double)g->prm.min_feature_distance,
                                        g->d_corners + (size_t)l * batch * 2 * mc, g->d_ncorners + (size_t)l * batch);
-      if (!rc) rc = svo_k_build_pyramid(ctx, left + l * lane_stride, batch, W, H, W, istride, pyr + (size_t)l * batch * g->pyr_stride, g->pyr_stride, true);
-      if (!rc) rc = svo_k_pyramid_level0(ctx, left + l * lane_stride + (size_t)(batch - 1) * istride, 1, W, H, W, istride,
+      if (!rc) rc = svo_k_build_pyramid(ctx, lbase[l], batch, W, H, W, istride, pyr + (size_t)l * batch * g->pyr_stride, g->pyr_stride, true);
+      if (!rc) rc = svo_k_pyramid_level0(ctx, lbase[l] + (size_t)(batch - 1) * istride, 1, W, H, W, istride,
                                          pyr + ((size_t)l * batch + (size_t)(batch - 1)) * g->pyr_stride, g->pyr_stride, st);
     }
   }
@@ -658,10 +666,10 @@ extern "C" int svo_pipeline_group_process_batch_dev(svo_pipeline_group* g, const
   }
 
   auto RES = [&](int lane, int f) -> svo_frame_result& { return results[(size_t)lane * batch + f]; };
-  auto IMG = [&](const uint8_t* base, int lane, int f) { return base + lane * lane_stride + (size_t)f * istride; };
+  auto IMG = [&](const uint8_t* const* base, int lane, int f) { return base[lane] + (size_t)f * istride; };
   auto PYR = [&](int lane, int f) { return pyr + ((size_t)lane * batch + f) * g->pyr_stride; };
   // level 0 of frame f's pyramid: the caller's image, except the batch's last frame (copied into the pyramid above)
-  auto L0 = [&](int lane, int f) -> const uint8_t* { return f == batch - 1 ? PYR(lane, f) : IMG(left, lane, f); };
+  auto L0 = [&](int lane, int f) -> const uint8_t* { return f == batch - 1 ? PYR(lane, f) : IMG(lbase, lane, f); };
   auto DET = [&](int lane, int f) { return g->d_corners + ((size_t)lane * batch + f) * 2 * mc; };
   for (int li = 0; li < S; ++li) {
     Lane* l = g->lanes[li];
@@ -1082,7 +1090,7 @@ extern "C" int svo_pipeline_group_process_batch_dev(svo_pipeline_group* g, const
           }
           pose[15] = 1.f;
         }
-        x.left = IMG(left, li, i); x.right = IMG(right, li, i);
+        x.left = IMG(lbase, li, i); x.right = IMG(rbase, li, i);
         x.n_max = n_det; x.disp = l->d_disp;
         x.M = svo_k_reprojection_matrix(pose, g->K[0], g->K[2], g->K[5], (float)g->prm.cam.baseline);  // :178-189
         x.kept_xy = l->h_tri_xy; x.xyz = l->h_tri_xyz; x.n_kept = l->h_tri_cnt;
@@ -1305,6 +1313,81 @@ extern "C" int svo_pipeline_group_process_batch_dev(svo_pipeline_group* g, const
   }
   if (error) { quiesce_after_error(g); return error; }
   if (!ctx->err.empty()) return SVO_ERR_HIP;
+  return SVO_OK;
+}
+}  // namespace
+
+extern "C" int svo_pipeline_group_process_batch_dev(svo_pipeline_group* g, const uint8_t* left, const uint8_t* right, size_t lane_stride,
+                                                    int batch, svo_frame_result* results) {
+  if (!g) return SVO_ERR_INVALID;
+  svo_ctx* ctx = g->ctx;
+  SVO_REQUIRE(ctx, left && right && results && batch >= 1 && batch <= g->max_batch, "pipeline_group_process_batch: bad arguments");
+  const int W = g->prm.width, H = g->prm.height, S = g->n_lanes;
+  const size_t istride = (size_t)W * H;
+  SVO_REQUIRE(ctx, lane_stride >= istride * (size_t)batch, "pipeline_group_process_batch: lanes overlap");
+  ctx->err.clear();
+  SVO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const uint8_t *lbase[SVO_MAX_LANES], *rbase[SVO_MAX_LANES];
+  for (int l = 0; l < S; ++l) { lbase[l] = left + (size_t)l * lane_stride; rbase[l] = right + (size_t)l * lane_stride; }
+  // raw input: ONE remap launch for every lane that has a camera model, in front of everything (same stream as the batch-wide
+  // stages); those lanes are then read from the workspace (lanes `batch` images apart: contiguous when every lane is rectified).
+  // A lane without a model is neither remapped nor copied.
+  if (!g->rect_models.empty()) {
+    SvoRectifyArgs a{};
+    const size_t ws_lane = istride * (size_t)batch;
+    a.src[0] = left; a.src[1] = right; a.dst[0] = g->d_rect[0]; a.dst[1] = g->d_rect[1];
+    a.src_lane_stride = lane_stride; a.dst_lane_stride = ws_lane;
+    a.src_image_stride = a.dst_image_stride = istride;
+    a.src_row_stride = W; a.width = W; a.height = H; a.frames = batch; a.eyes = 2;
+    for (int l = 0; l < S; ++l) {
+      const SvoRectModel* m = g->lane_rect[l];
+      if (!m) continue;
+      a.map[a.n_active][0] = m->d_map[0]; a.map[a.n_active][1] = m->d_map[1];
+      a.lane[a.n_active++] = (unsigned char)l;
+      lbase[l] = g->d_rect[0] + (size_t)l * ws_lane; rbase[l] = g->d_rect[1] + (size_t)l * ws_lane;
+    }
+    if (a.n_active) {
+      const int rc = svo_k_rectify_remap(ctx, a, ctx->stream);
+      if (rc) return rc;
+    }
+  }
+  return group_process(g, lbase, rbase, batch, results);
+}
+
+// Raw input per lane (include/svo.h).  The tables of a (left, right) pair of models exist once, however many lanes use it.
+extern "C" int svo_pipeline_group_set_rectification(svo_pipeline_group* g, int lane, const svo_rectify_eye* left, const svo_rectify_eye* right) {
+  if (!g) return SVO_ERR_INVALID;
+  svo_ctx* ctx = g->ctx;
+  SVO_REQUIRE(ctx, lane >= -1 && lane < g->n_lanes, "pipeline_group_set_rectification: no such lane");
+  SVO_REQUIRE(ctx, (left != nullptr) == (right != nullptr), "pipeline_group_set_rectification: give both eyes, or neither to turn it off");
+  SVO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  SvoRectModel* m = nullptr;
+  if (left) {
+    for (SvoRectModel* have : g->rect_models)
+      if (!memcmp(&have->eye[0], left, sizeof(*left)) && !memcmp(&have->eye[1], right, sizeof(*right))) m = have;
+    if (!m) {
+      const int rc = svo_rect_model_create(ctx, left, right, &g->prm.cam, g->prm.width, g->prm.height, &m);
+      if (rc) return rc;
+      g->rect_models.push_back(m);
+    }
+    const size_t bytes = (size_t)g->n_lanes * (size_t)g->max_batch * (size_t)g->prm.width * (size_t)g->prm.height;
+    for (int e = 0; e < 2; ++e)
+      if (!g->d_rect[e]) SVO_HIP_CHECK(ctx, hipMalloc((void**)&g->d_rect[e], bytes));
+  }
+  for (int l = 0; l < g->n_lanes; ++l) {
+    if (lane >= 0 && l != lane) continue;
+    if (g->lane_rect[l]) --g->lane_rect[l]->refs;
+    g->lane_rect[l] = m;
+    if (m) ++m->refs;
+  }
+  // tables no lane uses any more go; with the last one the workspace goes too (process_batch* returns with its launches complete)
+  for (size_t i = 0; i < g->rect_models.size();) {
+    if (g->rect_models[i]->refs > 0) { ++i; continue; }
+    svo_rect_model_destroy(g->rect_models[i]);
+    g->rect_models.erase(g->rect_models.begin() + (long)i);
+  }
+  if (g->rect_models.empty())
+    for (int e = 0; e < 2; ++e) { if (g->d_rect[e]) (void)hipFree(g->d_rect[e]); g->d_rect[e] = nullptr; }
   return SVO_OK;
 }
 

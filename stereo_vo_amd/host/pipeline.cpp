@@ -500,6 +500,49 @@ ImageProcessor::~ImageProcessor() {
   void* ptrs[] = {d_corners_, d_ncorners_, d_pyr_, d_xyz_, d_trk_xy_, d_trk_ids_, d_inl_, d_new_xy_, d_disp_, d_kxy_, d_cnt_, d_stage_};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h_arena_) (void)hipHostFree(h_arena_);
+  svo_rect_model_destroy(rect_);
+  if (d_rect_) (void)hipFree(d_rect_);
+}
+
+int ImageProcessor::set_rectification(const svo_rectify_eye* left, const svo_rectify_eye* right, const svo_camera_info* cam, int width,
+                                      int height) {
+  SVO_REQUIRE(ctx_, (left != nullptr) == (right != nullptr), "set_rectification: give both eyes, or neither to turn it off");
+  SVO_HIP_CHECK(ctx_, hipSetDevice(ctx_->device));
+  SVO_HIP_CHECK(ctx_, hipStreamSynchronize(ctx_->stream));  // nothing may still read the tables / the workspace replaced below
+  SvoRectModel* m = nullptr;
+  uint8_t* ws = nullptr;
+  if (left) {
+    SVO_REQUIRE(ctx_, cam && width >= 1 && height >= 1 && width <= ctx_->lim.max_width && height <= ctx_->lim.max_height,
+                "set_rectification: image size outside the context limits");
+    const int rc = svo_rect_model_create(ctx_, left, right, cam, width, height, &m);
+    if (rc) return rc;
+    const hipError_t e = hipMalloc((void**)&ws, (size_t)2 * max_batch_ * width * height);
+    if (e != hipSuccess) {
+      svo_rect_model_destroy(m);
+      ctx_->err = std::string("set_rectification: workspace allocation failed: ") + hipGetErrorString(e);
+      return SVO_ERR_HIP;
+    }
+  }
+  svo_rect_model_destroy(rect_);
+  if (d_rect_) (void)hipFree(d_rect_);
+  rect_ = m; d_rect_ = ws; rect_w_ = width; rect_h_ = height;
+  return SVO_OK;
+}
+
+int ImageProcessor::rectify(const uint8_t** left, const uint8_t** right, int batch) {
+  if (!rect_) return SVO_OK;
+  SVO_REQUIRE(ctx_, batch >= 1 && batch <= max_batch_, "rectify: batch outside the workspace");
+  const size_t istride = (size_t)rect_w_ * rect_h_;
+  SvoRectifyArgs a{};
+  a.src[0] = *left; a.src[1] = *right;
+  a.dst[0] = d_rect_; a.dst[1] = d_rect_ + (size_t)max_batch_ * istride;
+  a.src_image_stride = a.dst_image_stride = istride;
+  a.src_row_stride = rect_w_; a.width = rect_w_; a.height = rect_h_; a.frames = batch; a.eyes = 2; a.n_active = 1;
+  a.map[0][0] = rect_->d_map[0]; a.map[0][1] = rect_->d_map[1]; a.lane[0] = 0;
+  const int rc = svo_k_rectify_remap(ctx_, a, ctx_->stream);
+  if (rc) return rc;
+  *left = a.dst[0]; *right = a.dst[1];
+  return SVO_OK;
 }
 
 void ImageProcessor::reset() {
@@ -578,7 +621,13 @@ int ImageProcessor::process_host(const uint8_t* left, int left_stride, const uin
                                        hipMemcpyHostToDevice, ctx_->stream));
   ctx_->err.clear();
   batch_ = 0;  // no prepared batch: process() detects and builds the pyramid for this frame
-  process(StereoPair(DeviceImage{d_stage_, width, height, width}, DeviceImage{d_stage_ + bytes, width, height, width}, t, -1));
+  const uint8_t *dl = d_stage_, *dr = d_stage_ + bytes;
+  if (rect_) {  // raw input: every stage reads the rectified copy
+    SVO_REQUIRE(ctx_, width == rect_w_ && height == rect_h_, "process_host: image size differs from the rectification tables'");
+    const int rc = rectify(&dl, &dr, 1);
+    if (rc) return rc;
+  }
+  process(StereoPair(DeviceImage{dl, width, height, width}, DeviceImage{dr, width, height, width}, t, -1));
   return ctx_->err.empty() ? SVO_OK : SVO_ERR_HIP;
 }
 
@@ -786,7 +835,9 @@ extern "C" int svo_pipeline_process_batch_dev(svo_pipeline* p, const uint8_t* le
   ctx->err.clear();
   SVO_HIP_CHECK(ctx, hipSetDevice(ctx->device));  // the calling thread may never have selected this GPU
   struct Active { Active() { svo::pipeline_count_add(1); } ~Active() { svo::pipeline_count_add(-1); } } active;  // latency / throughput mode
-  int rc = p->proc->prepare_batch(left, batch, W, H);
+  int rc = p->proc->rectify(&left, &right, batch);  // svo_pipeline_set_rectification: left / right are raw (a no-op otherwise)
+  if (rc) return rc;
+  rc = p->proc->prepare_batch(left, batch, W, H);
   if (rc) return rc;
   // The reference runs process() then bundle_adjust() per frame (src/vo_node.cpp:141-148).  Here the solve of
   // keyframe k runs asynchronously (own stream + worker thread) while frames k+1.. are tracked; it is joined
@@ -852,6 +903,12 @@ extern "C" int svo_pipeline_process_batch(svo_pipeline* p, const uint8_t* left, 
   SVO_HIP_CHECK(ctx, hipMemcpyAsync(p->d_imgs, left, bytes, hipMemcpyHostToDevice, ctx->stream));
   SVO_HIP_CHECK(ctx, hipMemcpyAsync(p->d_imgs + bytes, right, bytes, hipMemcpyHostToDevice, ctx->stream));
   return svo_pipeline_process_batch_dev(p, p->d_imgs, p->d_imgs + bytes, batch, results);
+}
+
+extern "C" int svo_pipeline_set_rectification(svo_pipeline* p, const svo_rectify_eye* left, const svo_rectify_eye* right) {
+  if (!p) return SVO_ERR_INVALID;
+  p->adjuster->wait();
+  return p->proc->set_rectification(left, right, &p->prm.cam, p->prm.width, p->prm.height);
 }
 
 extern "C" int svo_pipeline_draw_track(svo_pipeline* p, const uint8_t* keyframe_gray, int row_stride, uint8_t* rgb) {

@@ -31,6 +31,8 @@
 
 struct svo_ba;
 
+struct SvoRectModel;
+
 namespace svo {
 
 struct Point2f { float x, y; };
@@ -209,6 +211,11 @@ class ImageProcessor {  // src/image_processor.hpp:31-46
   int process_host(const uint8_t* left, int left_stride, const uint8_t* right, int right_stride, int width, int height,
                    double t);
   bool ok() const { return alloc_ok_; }
+  // Raw input (include/svo.h "rectification"): builds and uploads both eyes' tables for (cam, width, height) and allocates the
+  // rectified workspace (max_batch x 2 images) once.  Both null: off, everything freed.  rectify() then replaces *left / *right
+  // (`batch` raw images each, tight rows) by their rectified copies: one launch on the context's stream, a no-op while off.
+  int set_rectification(const svo_rectify_eye* left, const svo_rectify_eye* right, const svo_camera_info* cam, int width, int height);
+  int rectify(const uint8_t** left, const uint8_t** right, int batch);
   // Called by process() right after BundleAdjuster::add_keyframe (before the tracker is re-initialised): lets a driver
   // start the asynchronous solve of the new keyframe while process() finishes.  Unset: nothing happens.
   void on_keyframe_added(std::function<void()> hook) { keyframe_hook_ = std::move(hook); }
@@ -224,6 +231,7 @@ class ImageProcessor {  // src/image_processor.hpp:31-46
   bool alloc_ok_ = false;
   std::function<void()> keyframe_hook_;
   uint8_t* d_stage_ = nullptr; size_t stage_bytes_ = 0;  // process_host: left | right
+  SvoRectModel* rect_ = nullptr; uint8_t* d_rect_ = nullptr; int rect_w_ = 0, rect_h_ = 0;  // set_rectification: tables, left batch | right batch
   float K_[9];
   std::shared_ptr<FeatureTracker> feature_tracker;
   std::shared_ptr<BundleAdjuster> bundle_adjuster;
