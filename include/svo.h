@@ -93,7 +93,8 @@ int svo_reference_constants(svo_reference_constants_t* out);
 /* Measurement aid (not a reference interface): time every launch of ONE named kernel with HIP events
  * recorded on the context stream.  kernel: "corner_response", "corner_nms", "corner_select", "pyr_down",
  * "lk_fb", "stereo_at", "triangulate", "pnp_hypotheses", "pnp_refine", "ba_linearize", "ba_backsub", "ba_step",
- * "rectify_remap";
+ * "rectify_remap", "stereo_bm" (the three launches of svo_stereo_bm as one bracket), "stereo_dense_batch",
+ * "cloud" (the count, scan and write launches of one svo_disparity_cloud_batch_dev as one bracket);
  * NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
@@ -188,6 +189,47 @@ int svo_stereo_disparity_at(svo_ctx* ctx, const uint8_t* left, const uint8_t* ri
 int svo_stereo_disparity_at_dev(svo_ctx* ctx, const uint8_t* left, const uint8_t* right, int width,
                                 int height, int row_stride, int num_disparities, int block_size,
                                 const float* xy, const int* n_dev, int n_max, float* disp);
+
+/* ------------------------------------------------------- dense depth clouds --
+ * The dense form of ImageProcessor::triangulate_stereo (src/image_processor.cpp:173-207): the whole StereoBM map instead of
+ * its samples at the feature pixels, and one 3-D point per kept pixel instead of one per feature.
+ *
+ * svo_stereo_bm_batch_dev (src/image_processor.cpp:173-207, the compute() of :174-175): `batch` pairs in ONE launch, DEVICE
+ * pointers, asynchronous on svo_stream(ctx).  Pair b's images start b * image_stride bytes after left / right, rows row_stride
+ * bytes apart; disp16: batch tight CV_16S maps (width*height each), bit-identical to svo_stereo_bm.  The raw images are read
+ * directly (the X-Sobel prefilter is formed in LDS).  Argument limits as svo_stereo_bm; 1 <= batch <= svo_limits.max_batch. */
+int svo_stereo_bm_batch_dev(svo_ctx* ctx, const uint8_t* left, const uint8_t* right, int batch, int width, int height,
+                            int row_stride, size_t image_stride, int num_disparities, int block_size, int16_t* disp16);
+/* Which pixels of a map become points (src/image_processor.cpp:173-207; the test of :194 generalised): pixel (x, y) is kept
+ * iff x % step == 0, y % step == 0 and d > max(min_disparity, 0) with d = (float)disp16 * 0.0625f (the convertTo of :176).
+ * max_points bounds what is STORED per image, never what is counted. */
+typedef struct svo_cloud_params {
+  int step;             /* 1 */
+  float min_disparity;  /* 0 */
+  int max_points;       /* <= 0 in svo_pipeline*_set_keyframe_clouds: width*height */
+} svo_cloud_params;
+/* Defaults for a width x height map (src/image_processor.cpp:173-207): step 1, min_disparity 0, max_points width*height. */
+int svo_cloud_default_params(svo_cloud_params* p, int width, int height);
+/* One point of a cloud (src/image_processor.cpp:173-207; arithmetic of :196-204 exactly as svo_triangulate for the feature
+ * ((float)x, (float)y) with disparity d).  tag = (y * width + x) | (left[y][x] << 24): pixel index and intensity, hence
+ * width*height <= 2^24. */
+typedef struct svo_cloud_point {
+  float x, y, z;
+  uint32_t tag;
+} svo_cloud_point;
+/* Maps -> compacted point lists in raster order (src/image_processor.cpp:173-207), DEVICE pointers, asynchronous.  disp16:
+ * batch tight maps; left: the left images (strides as above; read for the tag only); pose16: batch x 16 f32 row-major
+ * camera->world, NULL = identity for every pair; points: batch x params->max_points records; counts: batch x 2 ints,
+ * {n_total, n_stored = min(n_total, max_points)} - the first n_stored kept pixels in raster order are stored, records past
+ * them are not written.  One count launch, one scan launch, one write launch for the whole batch. */
+int svo_disparity_cloud_batch_dev(svo_ctx* ctx, const int16_t* disp16, const uint8_t* left, int batch, int width, int height,
+                                  int row_stride, size_t image_stride, const svo_camera_info* cam, const float* pose16,
+                                  const svo_cloud_params* params, svo_cloud_point* points, int* counts);
+/* One pair, HOST pointers, synchronous (src/image_processor.cpp:173-207 end to end): map + cloud.  pose16: 16 f32 or NULL;
+ * points: params->max_points records. */
+int svo_stereo_cloud(svo_ctx* ctx, const uint8_t* left, const uint8_t* right, int width, int height, int row_stride,
+                     int num_disparities, int block_size, const svo_camera_info* cam, const float* pose16,
+                     const svo_cloud_params* params, svo_cloud_point* points, int* n_total, int* n_stored);
 
 /* ------------------------------------------------------------------- a8 --
  * ImageProcessor::triangulate_stereo's reprojection loop
@@ -452,6 +494,28 @@ int svo_pipeline_process_batch(svo_pipeline* p, const uint8_t* left, const uint8
  * frame afterwards.  svo_pipeline_process_batch_dev / _batch then take left/right as RAW images: one remap launch in
  * front, every stage reads the rectified copy.  NULL, NULL turns it off and frees both.  Never called: nothing changes. */
 int svo_pipeline_set_rectification(svo_pipeline* p, const svo_rectify_eye* left, const svo_rectify_eye* right);
+/* Dense depth cloud per keyframe (src/image_processor.cpp:173-207 over the whole image; the reference's own landmark publisher
+ * is commented out at src/vo_node.cpp:133).  params != NULL allocates everything once (maps, points, counts for
+ * max_keyframes_per_call pairs; 0 = the context's max_batch; params->max_points <= 0 = width*height); afterwards every
+ * svo_pipeline_process_batch[_dev] call, once its last frame is finished, runs ONE batched dense launch and ONE cloud launch
+ * sequence over exactly the pairs of this call's frames with results[i].is_keyframe (the rectified copies when rectification
+ * is set), StereoBM(48, 21) as the pipeline itself.  Clouds are in the keyframe's CAMERA frame (pose16 = identity): bundle
+ * adjustment keeps moving keyframe poses, so the caller places a cloud with the keyframe's refined pose7.  The frame loop, the
+ * stage order and svo_frame_result are untouched.  More keyframes in a call than the bound: the frame results are complete,
+ * no cloud is produced and the call returns SVO_ERR_CAPACITY.  NULL turns it off and frees everything.  Never called: no
+ * launch, no allocation, nothing changes. */
+int svo_pipeline_set_keyframe_clouds(svo_pipeline* p, const svo_cloud_params* params, int max_keyframes_per_call);
+/* One entry per keyframe of the last process call, in frame order (src/image_processor.cpp:173-207 per entry). */
+typedef struct svo_keyframe_cloud {
+  int frame;                  /* index in the call */
+  int lane;                   /* 0 for an svo_pipeline */
+  int n_total, n_stored;
+  const svo_cloud_point* dev; /* DEVICE pointer to n_stored records */
+} svo_keyframe_cloud;
+/* The table of the last process call (src/image_processor.cpp:173-207); valid until the next process call. */
+int svo_pipeline_keyframe_clouds(svo_pipeline* p, int* n, const svo_keyframe_cloud** table);
+/* Entry i's points to HOST memory (src/image_processor.cpp:173-207): min(n_stored, capacity) records, synchronous. */
+int svo_pipeline_copy_keyframe_cloud(svo_pipeline* p, int i, svo_cloud_point* host, int capacity);
 /* Feature-set taps for parity tests: ids + positions the tracker holds after the last frame. */
 int svo_pipeline_get_tracked(svo_pipeline* p, int64_t* ids, float* xy, int capacity, int* n);
 
@@ -495,6 +559,15 @@ int svo_pipeline_group_process_batch(svo_pipeline_group* g, const uint8_t* left,
  * rectified lanes, issued on the processing side (after the slot's upload has been waited for, so the streaming loop's
  * overlap of upload and processing is untouched); lanes without a model are neither remapped nor copied. */
 int svo_pipeline_group_set_rectification(svo_pipeline_group* g, int lane, const svo_rectify_eye* left, const svo_rectify_eye* right);
+/* svo_pipeline_set_keyframe_clouds for lane `lane` (-1: every lane; src/image_processor.cpp:173-207 per keyframe).  After the
+ * call's event loop has drained: ONE dense launch and ONE cloud launch sequence for all (lane, frame) keyframes of the call of
+ * the lanes that have clouds on; lanes without cost nothing.  Covers _process_batch_dev, _process_uploaded and _process_batch.
+ * The lanes that have clouds on share one set of parameters and one bound (a differing set while another lane is on:
+ * SVO_ERR_INVALID); max_keyframes_per_call counts all lanes together, 0 = the context's max_batch.  The table is ordered by
+ * lane, then frame. */
+int svo_pipeline_group_set_keyframe_clouds(svo_pipeline_group* g, int lane, const svo_cloud_params* params, int max_keyframes_per_call);
+int svo_pipeline_group_keyframe_clouds(svo_pipeline_group* g, int* n, const svo_keyframe_cloud** table);
+int svo_pipeline_group_copy_keyframe_cloud(svo_pipeline_group* g, int i, svo_cloud_point* host, int capacity);
 int svo_pipeline_group_get_tracked(svo_pipeline_group* g, int lane, int64_t* ids, float* xy, int capacity, int* n);
 /* Launch statistics of the last process_batch call, by stage: 0 track (LK + compaction), 1 PnP-RANSAC (hypotheses, bookkeeping and
  * refinement in one launch), 3 dedup / stereo + triangulation, 4 bundle-adjustment solves, 5 corner detection + pyramids;

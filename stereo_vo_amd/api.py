@@ -82,6 +82,49 @@ class FrameResult(C.Structure):
                 ("percent_lost", C.c_float), ("pose7", C.c_double * 7), ("ba_iterations", C.c_int)]
 
 
+class CloudParams(C.Structure):
+    """svo_cloud_params: which pixels of a disparity map become points, and how many are stored per image."""
+    _fields_ = [("step", C.c_int), ("min_disparity", C.c_float), ("max_points", C.c_int)]
+
+
+class CloudPoint(C.Structure):
+    """svo_cloud_point: 16 bytes; tag = (y * width + x) | (left[y][x] << 24)."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("tag", C.c_uint32)]
+
+
+CLOUD_POINT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("z", np.float32), ("tag", np.uint32)])
+
+
+class KeyframeCloud(C.Structure):
+    """svo_keyframe_cloud: one entry of a pipeline's / group's table of the last process call."""
+    _fields_ = [("frame", C.c_int), ("lane", C.c_int), ("n_total", C.c_int), ("n_stored", C.c_int), ("dev", C.c_void_p)]
+
+
+def cloud_default_params(width, height):
+    """svo_cloud_default_params: step 1, min_disparity 0, max_points width*height."""
+    p = CloudParams()
+    if lib().svo_cloud_default_params(C.byref(p), width, height) != 0:
+        raise SvoError("svo_cloud_default_params failed")
+    return p
+
+
+def _cloud_params(width, height, step, min_disparity, max_points):
+    return CloudParams(int(step), float(min_disparity), int(width * height if max_points is None else max_points))
+
+
+def _keyframe_clouds(ctx, L, h, table_fn, copy_fn):
+    """The table of the last process call as a list of dicts; "points": numpy structured array (CLOUD_POINT_DTYPE) of n_stored records."""
+    n, tab = C.c_int(0), C.POINTER(KeyframeCloud)()
+    ctx._chk(table_fn(h, C.byref(n), C.byref(tab)), table_fn.__name__)
+    out = []
+    for i in range(n.value):
+        e = tab[i]
+        pts = np.empty(e.n_stored, CLOUD_POINT_DTYPE)
+        ctx._chk(copy_fn(h, i, _p(pts), e.n_stored), copy_fn.__name__)
+        out.append({"frame": e.frame, "lane": e.lane, "n_total": e.n_total, "n_stored": e.n_stored, "dev": e.dev, "points": pts})
+    return out
+
+
 class SynthParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("width", C.c_int), ("height", C.c_int), ("focal", C.c_double),
                 ("cx", C.c_double), ("cy", C.c_double), ("baseline", C.c_double), ("step_z", C.c_double),
@@ -200,6 +243,9 @@ SYMBOLS = [
     "svo_image_read_gray", "svo_kitti_read_poses", "svo_ate_rmse", "svo_kitti_run", "svo_cholesky_solve", "svo_cholesky_solve_dev", "svo_draw_track", "svo_pipeline_draw_track",
     "svo_rectify_eye_from_camera_info", "svo_rectify_build_map", "svo_rectify_remap", "svo_rectify_remap_batch_dev",
     "svo_pipeline_set_rectification", "svo_pipeline_group_set_rectification",
+    "svo_stereo_bm_batch_dev", "svo_cloud_default_params", "svo_disparity_cloud_batch_dev", "svo_stereo_cloud",
+    "svo_pipeline_set_keyframe_clouds", "svo_pipeline_keyframe_clouds", "svo_pipeline_copy_keyframe_cloud",
+    "svo_pipeline_group_set_keyframe_clouds", "svo_pipeline_group_keyframe_clouds", "svo_pipeline_group_copy_keyframe_cloud",
 ]
 
 
@@ -218,6 +264,22 @@ def lib():
         L.svo_stream.argtypes = [C.c_void_p]
         L.svo_destroy.argtypes = [C.c_void_p]
         L.svo_destroy.restype = None
+        # dense depth clouds: every entry with its full signature (pointers and size_t do not survive ctypes' int default)
+        vp, ci, sz = C.c_void_p, C.c_int, C.c_size_t
+        L.svo_cloud_default_params.argtypes = [vp, ci, ci]
+        L.svo_stereo_bm_batch_dev.argtypes = [vp, vp, vp, ci, ci, ci, ci, sz, ci, ci, vp]
+        L.svo_disparity_cloud_batch_dev.argtypes = [vp, vp, vp, ci, ci, ci, ci, sz, vp, vp, vp, vp, vp]
+        L.svo_stereo_cloud.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+        L.svo_pipeline_set_keyframe_clouds.argtypes = [vp, vp, ci]
+        L.svo_pipeline_keyframe_clouds.argtypes = [vp, vp, vp]
+        L.svo_pipeline_copy_keyframe_cloud.argtypes = [vp, ci, vp, ci]
+        L.svo_pipeline_group_set_keyframe_clouds.argtypes = [vp, ci, vp, ci]
+        L.svo_pipeline_group_keyframe_clouds.argtypes = [vp, vp, vp]
+        L.svo_pipeline_group_copy_keyframe_cloud.argtypes = [vp, ci, vp, ci]
+        for f in ("svo_cloud_default_params", "svo_stereo_bm_batch_dev", "svo_disparity_cloud_batch_dev", "svo_stereo_cloud",
+                  "svo_pipeline_set_keyframe_clouds", "svo_pipeline_keyframe_clouds", "svo_pipeline_copy_keyframe_cloud",
+                  "svo_pipeline_group_set_keyframe_clouds", "svo_pipeline_group_keyframe_clouds", "svo_pipeline_group_copy_keyframe_cloud"):
+            getattr(L, f).restype = ci
         _LIB = L
     return _LIB
 
@@ -382,6 +444,33 @@ class Context:
         self._chk(self.L.svo_stereo_disparity_at(self.h, _p(left), _p(right), w, h, w, ndisp, block,
                                                  _p(xy), n, _p(d)), "svo_stereo_disparity_at")
         return d
+
+    # ---- dense depth clouds
+    def stereo_bm_batch(self, left_ptr, right_ptr, batch, width, height, row_stride, image_stride, disp16_ptr, ndisp=48, block=21):
+        """svo_stereo_bm_batch_dev: raw device pointers (ints); disp16_ptr: batch tight (H, W) int16 maps.  Asynchronous."""
+        self._chk(self.L.svo_stereo_bm_batch_dev(self.h, left_ptr, right_ptr, batch, width, height, row_stride, image_stride, ndisp, block,
+                                                 disp16_ptr), "svo_stereo_bm_batch_dev")
+
+    def disparity_cloud(self, disp16_ptr, left_ptr, batch, width, height, row_stride, image_stride, cam, pose16_ptr, params, points_ptr,
+                        counts_ptr):
+        """svo_disparity_cloud_batch_dev: raw device pointers (ints; pose16_ptr None = identity); cam: CameraInfo, params: CloudParams;
+        points_ptr: batch x params.max_points records of CLOUD_POINT_DTYPE, counts_ptr: batch x 2 int32.  Asynchronous."""
+        self._chk(self.L.svo_disparity_cloud_batch_dev(self.h, disp16_ptr, left_ptr, batch, width, height, row_stride, image_stride,
+                                                       C.byref(cam) if cam is not None else None, pose16_ptr,
+                                                       C.byref(params) if params is not None else None, points_ptr, counts_ptr),
+                  "svo_disparity_cloud_batch_dev")
+
+    def stereo_cloud(self, left, right, cam, pose16=None, step=1, min_disparity=0.0, max_points=None, ndisp=48, block=21):
+        """svo_stereo_cloud: one host pair -> (points as a CLOUD_POINT_DTYPE array of n_stored records, n_total)."""
+        left, right = _u8(left), _u8(right)
+        h, w = left.shape
+        prm = _cloud_params(w, h, step, min_disparity, max_points)
+        pts = np.empty(max(prm.max_points, 1), CLOUD_POINT_DTYPE)
+        pose = None if pose16 is None else _f32(pose16).reshape(16)
+        nt, ns = C.c_int(0), C.c_int(0)
+        self._chk(self.L.svo_stereo_cloud(self.h, _p(left), _p(right), w, h, w, ndisp, block, C.byref(cam), _p(pose), C.byref(prm), _p(pts),
+                                          C.byref(nt), C.byref(ns)), "svo_stereo_cloud")
+        return pts[:ns.value].copy(), nt.value
 
     # ---- a8
     def triangulate(self, xy, disp, pose16, focal, cx, cy, baseline):
@@ -650,6 +739,17 @@ class Pipeline:
         self.ctx._chk(self.L.svo_pipeline_set_rectification(self.h, C.byref(left) if left is not None else None,
                                                             C.byref(right) if right is not None else None), "svo_pipeline_set_rectification")
 
+    def set_keyframe_clouds(self, params=None, max_keyframes_per_call=0):
+        """svo_pipeline_set_keyframe_clouds: params a CloudParams (max_points <= 0: width*height), or True for the defaults; None: off."""
+        if params is True:
+            params = cloud_default_params(self.prm.width, self.prm.height)
+        self.ctx._chk(self.L.svo_pipeline_set_keyframe_clouds(self.h, C.byref(params) if params is not None else None, max_keyframes_per_call),
+                      "svo_pipeline_set_keyframe_clouds")
+
+    def keyframe_clouds(self):
+        """The keyframes of the last process call: [{frame, lane, n_total, n_stored, dev, points (CLOUD_POINT_DTYPE array)}], in frame order."""
+        return _keyframe_clouds(self.ctx, self.L, self.h, self.L.svo_pipeline_keyframe_clouds, self.L.svo_pipeline_copy_keyframe_cloud)
+
     def process_batch(self, left, right):
         """left/right: (B, H, W) uint8 host arrays."""
         left, right = _u8(left), _u8(right)
@@ -713,6 +813,17 @@ class PipelineGroup:
         self.ctx._chk(self.L.svo_pipeline_group_set_rectification(self.h, lane, C.byref(left) if left is not None else None,
                                                                   C.byref(right) if right is not None else None),
                       "svo_pipeline_group_set_rectification")
+
+    def set_keyframe_clouds(self, lane=-1, params=None, max_keyframes_per_call=0):
+        """svo_pipeline_group_set_keyframe_clouds: lane -1 = every lane; params a CloudParams, True for the defaults, None: off."""
+        if params is True:
+            params = cloud_default_params(self.prm.width, self.prm.height)
+        self.ctx._chk(self.L.svo_pipeline_group_set_keyframe_clouds(self.h, lane, C.byref(params) if params is not None else None,
+                                                                    max_keyframes_per_call), "svo_pipeline_group_set_keyframe_clouds")
+
+    def keyframe_clouds(self):
+        """The keyframes of the last process call over the lanes that have clouds on, ordered by lane, then frame (see Pipeline.keyframe_clouds)."""
+        return _keyframe_clouds(self.ctx, self.L, self.h, self.L.svo_pipeline_group_keyframe_clouds, self.L.svo_pipeline_group_copy_keyframe_cloud)
 
     def process_batch_dev(self, left_ptr, right_ptr, lane_stride, batch):
         """left_ptr/right_ptr: raw device pointers to (n_lanes, B, H, W) uint8 images (lane_stride bytes between lanes).

@@ -28,7 +28,8 @@ extern "C" int svo_profile_select(svo_ctx* ctx, const char* kernel) {
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
   static const char* names[] = {"", "corner_response", "corner_nms", "corner_select", "pyr_down", "lk_fb", "stereo_at",
-                                "triangulate", "pnp_hypotheses", "pnp_refine", "ba_linearize", "ba_backsub", "ba_step", "rectify_remap"};
+                                "triangulate", "pnp_hypotheses", "pnp_refine", "ba_linearize", "ba_backsub", "ba_step", "rectify_remap",
+                                "stereo_bm", "stereo_dense_batch", "cloud"};
   int tag = 0;
   if (kernel && kernel[0]) {
     tag = -1;
@@ -156,7 +157,7 @@ extern "C" void svo_destroy(svo_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   void* ptrs[] = {c->d_ws, c->d_eig, c->d_raw, c->d_maxkey, c->d_cand, c->d_sorted, c->d_state, c->d_ncand,
-                  c->d_cell_count, c->d_cell_start, c->d_status};
+                  c->d_cell_count, c->d_cell_start, c->d_status, c->d_cloud_seg};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& e : c->prof_ev) (void)hipEventDestroy(e);

@@ -119,14 +119,21 @@ int svo_k_gather_xy_ids(svo_ctx* ctx, const int* idx, int n, const float* xy_src
   return svo_k_gather_track(ctx, idx, nullptr, n, xy_src, ids_src, xy_dst, ids_dst);
 }
 
-SvoMat4 svo_k_reprojection_matrix(const float* pose16, float focal, float cx, float cy, float baseline) {
-  float Q[16] = {0};
+SvoMat4 svo_k_reprojection_q(float focal, float cx, float cy, float baseline) {
+  SvoMat4 q{};
+  float* Q = q.m;
   Q[0] = (float)(1.0 / (double)focal);
   Q[5] = (float)(1.0 / (double)focal);
   Q[3] = -cx / focal;
   Q[7] = -cy / focal;
   Q[11] = 1.0f;
   Q[14] = (float)(1.0 / (double)(baseline * focal));
+  return q;
+}
+
+SvoMat4 svo_k_reprojection_matrix(const float* pose16, float focal, float cx, float cy, float baseline) {
+  const SvoMat4 q = svo_k_reprojection_q(focal, cx, cy, baseline);
+  const float* Q = q.m;
   SvoMat4 M;
   for (int i = 0; i < 4; ++i)
     for (int j = 0; j < 4; ++j) {

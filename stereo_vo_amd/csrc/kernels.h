@@ -10,6 +10,7 @@ struct SvoMat4 { float m[16]; };
 
 // a8: M = float(pose * Q) formed on the host in the reference's order (src/image_processor.cpp:183-189,202).
 SvoMat4 svo_k_reprojection_matrix(const float* pose16, float focal, float cx, float cy, float baseline);
+SvoMat4 svo_k_reprojection_q(float focal, float cx, float cy, float baseline);  // the Q of that product alone (pose = identity is NOT applied)
 int svo_k_triangulate(svo_ctx* ctx, const float* xy, const float* disp, const int* n_dev, int n_max,
                       const SvoMat4& M, float* kept_xy, float* xyz, int* kept_index, int* n_kept,
                       const SvoPublish* pub = nullptr);
@@ -79,5 +80,29 @@ struct SvoRectModel {
 int svo_rect_model_create(svo_ctx* ctx, const svo_rectify_eye* left, const svo_rectify_eye* right, const svo_camera_info* cam,
                           int width, int height, SvoRectModel** out);
 void svo_rect_model_destroy(SvoRectModel* m);
+// dense depth clouds (csrc/dense.hip).  Where pair z of a batched launch lives: z * image_stride after left / right, or tab[z]
+// (a DEVICE table) when the pairs are scattered (the keyframes of a call).
+struct SvoCloudPair { const uint8_t* left; const uint8_t* right; };
+struct SvoDensePairs {
+  const uint8_t* left;
+  const uint8_t* right;
+  size_t image_stride;
+  const SvoCloudPair* tab;
+};
+int svo_k_stereo_dense_batch(svo_ctx* ctx, const SvoDensePairs& src, int batch, int W, int H, int stride, int ndisp, int block, int16_t* disp16);
+int svo_k_cloud_chunks(int W, int H, int step);  // ints of `seg` per image
+int svo_k_cloud(svo_ctx* ctx, const int16_t* disp16, const SvoDensePairs& src, int batch, int W, int H, int stride, const svo_camera_info* cam,
+                const float* pose16, const svo_cloud_params* prm, svo_cloud_point* points, int* counts, int* seg);
+// The keyframe clouds of one pipeline or one group: every buffer allocated once by create; run() = one dense launch + one cloud
+// launch sequence over the given pairs on the context's stream, then waits and fills the table.
+struct SvoKfClouds;
+int svo_kfc_create(svo_ctx* ctx, const svo_cloud_params* params, int W, int H, int max_keyframes, SvoKfClouds** out);
+void svo_kfc_destroy(SvoKfClouds* k);
+const svo_cloud_params* svo_kfc_params(const SvoKfClouds* k);  // as resolved by create (max_points > 0)
+int svo_kfc_max_keyframes(const SvoKfClouds* k);
+void svo_kfc_clear(SvoKfClouds* k);
+int svo_kfc_run(SvoKfClouds* k, const svo_camera_info* cam, const SvoCloudPair* pairs, const int* frame, const int* lane, int n);
+int svo_kfc_table(SvoKfClouds* k, int* n, const svo_keyframe_cloud** table);
+int svo_kfc_copy(SvoKfClouds* k, int i, svo_cloud_point* host, int capacity);
 const char* svo_rectify_error_text();  // of the calling thread's last context-free rectification call ("" if none failed)
 #endif

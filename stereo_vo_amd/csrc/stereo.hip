@@ -15,28 +15,10 @@
 #include "common.h"
 #include "group_kernels.h"
 #include "ref_constants.h"
+#include "stereo_common.h"
 #include "tail_device.h"
 
 namespace {
-constexpr int CAP = 31, TEXTURE_THRESHOLD = 10, UNIQUENESS_RATIO = 15;
-constexpr int MAX_NDISP = 64, MAX_BLOCK = 21;
-
-__device__ __forceinline__ int pf_row(int y, int H) {
-  if (y < 0) return H > 1 ? 1 : 0;
-  if (y >= H) return H > 1 ? H - 2 : 0;
-  return y;
-}
-
-// XSOBEL prefilter value at (x,y) from a raw image (global or LDS accessor).
-template <typename Load>
-__device__ __forceinline__ int prefilter_at(Load I, int x, int y, int W, int H) {
-  if (x <= 0 || x >= W - 1) return CAP;
-  if ((H & 1) && y == H - 1) return CAP;  // leftover odd row
-  const int y0 = pf_row(y - 1, H), y2 = pf_row(y + 1, H);
-  const int v = (I(x + 1, y0) - I(x - 1, y0)) + 2 * (I(x + 1, y) - I(x - 1, y)) + (I(x + 1, y2) - I(x - 1, y2));
-  return min(max(v, -CAP), CAP) + CAP;
-}
-
 // Winner selection + uniqueness + sub-pixel from sad[-1..ndisp] (index i = ndisp-1-d). Returns CV_16S value.
 __device__ __forceinline__ int bm_select(int* s /* points at index 0, s[-1] and s[ndisp] writable */, int ndisp,
                                          int tsum) {
@@ -318,13 +300,6 @@ __global__ __launch_bounds__(256) void stereo_prefilter_kernel(const uint8_t* __
 // (3 x 84 column threads of the 256); slot `ndisp` is the texture sum |L - cap| (same window, same machinery).  All
 // SADs of the tile (<= 441 * 62 < 2^16) are kept in LDS as uint16 [slot][pixel]; the winner / uniqueness / sub-pixel
 // selection then reads them per pixel.  Integer arithmetic throughout: bit-identical to the direct double loop.
-namespace {
-constexpr int DT_W = 64, DT_H = 8, DT_PIX = DT_W * DT_H;
-constexpr int DT_TH = DT_H + MAX_BLOCK - 1;         // 28 tile rows
-constexpr int DT_TWL = DT_W + MAX_BLOCK - 1;        // 84 left tile columns
-constexpr int DT_TWR = DT_TWL + MAX_NDISP;          // right tile columns
-constexpr int DT_SLOTS = 3;                         // disparity slots per pass
-}
 __global__ __launch_bounds__(256) void stereo_dense_kernel(const uint8_t* __restrict__ Lp, const uint8_t* __restrict__ Rp,
                                                            int W, int H, int ndisp, int block,
                                                            int16_t* __restrict__ out) {
@@ -412,7 +387,7 @@ __global__ __launch_bounds__(256) void stereo_dense_kernel(const uint8_t* __rest
 }
 
 // ----------------------------------------------------------------------------- host side
-static int stereo_check(svo_ctx* ctx, const void* l, const void* r, int W, int H, int stride, int ndisp, int block) {
+int svo_stereo_check(svo_ctx* ctx, const void* l, const void* r, int W, int H, int stride, int ndisp, int block) {
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
   SVO_REQUIRE(ctx, l && r, "stereo: null image");
@@ -426,7 +401,7 @@ static int stereo_check(svo_ctx* ctx, const void* l, const void* r, int W, int H
 extern "C" int svo_stereo_disparity_at_dev(svo_ctx* ctx, const uint8_t* left, const uint8_t* right, int width,
                                            int height, int row_stride, int num_disparities, int block_size,
                                            const float* xy, const int* n_dev, int n_max, float* disp) {
-  int rc = stereo_check(ctx, left, right, width, height, row_stride, num_disparities, block_size);
+  int rc = svo_stereo_check(ctx, left, right, width, height, row_stride, num_disparities, block_size);
   if (rc) return rc;
   SVO_REQUIRE(ctx, n_max >= 0 && (n_max == 0 || (xy && disp)), "stereo_disparity_at: null buffer");
   if (n_max == 0) return SVO_OK;
@@ -440,7 +415,7 @@ extern "C" int svo_stereo_disparity_at_dev(svo_ctx* ctx, const uint8_t* left, co
 int svo_k_stereo_triangulate(svo_ctx* ctx, const uint8_t* left, const uint8_t* right, int width, int height, int row_stride,
                              int num_disparities, int block_size, const float* xy, const int* n_dev, int n_max, float* disp,
                              const SvoMat4& M, float* kept_xy, float* xyz, int* kept_index, int* n_kept, int word, SvoPublish* pub_out) {
-  int rc = stereo_check(ctx, left, right, width, height, row_stride, num_disparities, block_size);
+  int rc = svo_stereo_check(ctx, left, right, width, height, row_stride, num_disparities, block_size);
   if (rc) return rc;
   SVO_REQUIRE(ctx, n_max >= 1 && xy && disp && kept_xy && xyz && n_kept && pub_out, "stereo_triangulate: null buffer");
   SvoPublish pub = svo_publish_next(ctx, word, n_max);
@@ -456,7 +431,7 @@ int svo_k_stereo_triangulate(svo_ctx* ctx, const uint8_t* left, const uint8_t* r
 extern "C" int svo_stereo_disparity_at(svo_ctx* ctx, const uint8_t* left, const uint8_t* right, int width, int height,
                                        int row_stride, int num_disparities, int block_size, const float* xy, int n,
                                        float* disp) {
-  int rc = stereo_check(ctx, left, right, width, height, row_stride, num_disparities, block_size);
+  int rc = svo_stereo_check(ctx, left, right, width, height, row_stride, num_disparities, block_size);
   if (rc) return rc;
   SVO_REQUIRE(ctx, n >= 0 && (n == 0 || (xy && disp)), "stereo_disparity_at: null buffer");
   if (n == 0) return SVO_OK;
@@ -480,7 +455,7 @@ extern "C" int svo_stereo_disparity_at(svo_ctx* ctx, const uint8_t* left, const 
 
 extern "C" int svo_stereo_bm(svo_ctx* ctx, const uint8_t* left, const uint8_t* right, int width, int height,
                              int row_stride, int num_disparities, int block_size, int16_t* disp16) {
-  int rc = stereo_check(ctx, left, right, width, height, row_stride, num_disparities, block_size);
+  int rc = svo_stereo_check(ctx, left, right, width, height, row_stride, num_disparities, block_size);
   if (rc) return rc;
   SVO_REQUIRE(ctx, disp16, "stereo_bm: null output");
   SvoScratch s(ctx);
@@ -495,12 +470,15 @@ extern "C" int svo_stereo_bm(svo_ctx* ctx, const uint8_t* left, const uint8_t* r
   SVO_HIP_CHECK(ctx, hipMemcpy2DAsync(dL, width, left, row_stride, width, height, hipMemcpyHostToDevice, st));
   SVO_HIP_CHECK(ctx, hipMemcpy2DAsync(dR, width, right, row_stride, width, height, hipMemcpyHostToDevice, st));
   const dim3 g1(svo_div_up(width, 64), svo_div_up(height, 4));
-  hipLaunchKernelGGL(stereo_prefilter_kernel, g1, dim3(256), 0, st, dL, width, height, width, dLp);
-  hipLaunchKernelGGL(stereo_prefilter_kernel, g1, dim3(256), 0, st, dR, width, height, width, dRp);
-  const size_t sad_lds = sizeof(unsigned short) * (size_t)(num_disparities + 1) * DT_PIX;  // <= 66,560 B
-  SVO_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)stereo_dense_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sad_lds));
-  hipLaunchKernelGGL(stereo_dense_kernel, dim3(svo_div_up(width, DT_W), svo_div_up(height, DT_H)), dim3(256), sad_lds, st, dLp,
-                     dRp, width, height, num_disparities, block_size, dD);
+  {  // the three launches, as one "stereo_bm" bracket of svo_profile_select
+    SvoProfScope prof(ctx, SVO_PROF_STEREO_BM);
+    hipLaunchKernelGGL(stereo_prefilter_kernel, g1, dim3(256), 0, st, dL, width, height, width, dLp);
+    hipLaunchKernelGGL(stereo_prefilter_kernel, g1, dim3(256), 0, st, dR, width, height, width, dRp);
+    const size_t sad_lds = sizeof(unsigned short) * (size_t)(num_disparities + 1) * DT_PIX;  // <= 66,560 B
+    SVO_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)stereo_dense_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sad_lds));
+    hipLaunchKernelGGL(stereo_dense_kernel, dim3(svo_div_up(width, DT_W), svo_div_up(height, DT_H)), dim3(256), sad_lds, st, dLp,
+                       dRp, width, height, num_disparities, block_size, dD);
+  }
   SVO_HIP_CHECK(ctx, hipGetLastError());
   SVO_HIP_CHECK(ctx, hipMemcpyAsync(disp16, dD, sizeof(int16_t) * px, hipMemcpyDeviceToHost, st));
   SVO_HIP_CHECK(ctx, hipStreamSynchronize(st));

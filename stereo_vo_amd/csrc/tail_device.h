@@ -45,6 +45,21 @@ __device__ __forceinline__ int svo_compact_slot(bool keep, int& base, int* sWave
   return slot;
 }
 
+// One point of src/image_processor.cpp:196-204: X = M [x y d 1]^T, four rows accumulated in f64 and rounded to f32, then three f32
+// divisions.  The ONE statement of this arithmetic: the sparse triangulation below and the dense cloud (dense.hip) both call it.
+__device__ __forceinline__ void svo_triangulate_point(const SvoMat4& M, float x, float y, float d, float* out3) {
+  const float v[4] = {x, y, d, 1.0f};
+  float wv[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s += (double)M.m[4 * r + k] * (double)v[k];
+    wv[r] = (float)s;
+  }
+  out3[0] = wv[0] / wv[3]; out3[1] = wv[1] / wv[3]; out3[2] = wv[2] / wv[3];
+}
+
 // src/image_processor.cpp:178-207 for n features by one workgroup of T threads.  COHERENT: `disp` was written by other
 // workgroups of this very launch.
 template <int T, bool COHERENT>
@@ -63,17 +78,10 @@ __device__ __forceinline__ void svo_triangulate_block(const float* __restrict__ 
     }
     const int slot = svo_compact_slot<T>(keep, base, sWave);
     if (slot >= 0) {
-      const float v[4] = {x, y, d, 1.0f};
-      float wv[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s += (double)M.m[4 * r + k] * (double)v[k];
-        wv[r] = (float)s;
-      }
+      float p[3];
+      svo_triangulate_point(M, x, y, d, p);
       kept_xy[2 * slot] = x; kept_xy[2 * slot + 1] = y;
-      xyz[3 * slot] = wv[0] / wv[3]; xyz[3 * slot + 1] = wv[1] / wv[3]; xyz[3 * slot + 2] = wv[2] / wv[3];
+      xyz[3 * slot] = p[0]; xyz[3 * slot + 1] = p[1]; xyz[3 * slot + 2] = p[2];
       if (kept_index) kept_index[slot] = i;
     }
   }

@@ -207,6 +207,9 @@ struct svo_pipeline_group {
   std::vector<SvoRectModel*> rect_models;
   SvoRectModel* lane_rect[SVO_MAX_LANES] = {};
   uint8_t* d_rect[2] = {nullptr, nullptr};
+  // keyframe clouds (svo_pipeline_group_set_keyframe_clouds): one set of buffers for the lanes that have them on (null: none has)
+  SvoKfClouds* kfc = nullptr;
+  bool lane_cloud[SVO_MAX_LANES] = {};
 };
 
 namespace {
@@ -313,6 +316,7 @@ extern "C" void svo_pipeline_group_destroy(svo_pipeline_group* g) {
     for (int e = 0; e < 2; ++e) { if (g->h_stage[sl][e]) (void)hipHostFree(g->h_stage[sl][e]); if (g->d_stage[sl][e]) (void)hipFree(g->d_stage[sl][e]); }
   }
   for (Lane* l : g->lanes) { if (l->ba) svo_ba_destroy(l->ba); delete l; }
+  svo_kfc_destroy(g->kfc);
   for (SvoRectModel* m : g->rect_models) svo_rect_model_destroy(m);
   for (int e = 0; e < 2; ++e) if (g->d_rect[e]) (void)hipFree(g->d_rect[e]);
   for (void* p : g->dev_allocs) (void)hipFree(p);
@@ -1327,6 +1331,7 @@ extern "C" int svo_pipeline_group_process_batch_dev(svo_pipeline_group* g, const
   SVO_REQUIRE(ctx, lane_stride >= istride * (size_t)batch, "pipeline_group_process_batch: lanes overlap");
   ctx->err.clear();
   SVO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (g->kfc) svo_kfc_clear(g->kfc);  // the table of the previous call ends here
   const uint8_t *lbase[SVO_MAX_LANES], *rbase[SVO_MAX_LANES];
   for (int l = 0; l < S; ++l) { lbase[l] = left + (size_t)l * lane_stride; rbase[l] = right + (size_t)l * lane_stride; }
   // raw input: ONE remap launch for every lane that has a camera model, in front of everything (same stream as the batch-wide
@@ -1351,7 +1356,69 @@ extern "C" int svo_pipeline_group_process_batch_dev(svo_pipeline_group* g, const
       if (rc) return rc;
     }
   }
-  return group_process(g, lbase, rbase, batch, results);
+  const int rc = group_process(g, lbase, rbase, batch, results);
+  if (rc || !g->kfc) return rc;
+  // keyframe clouds: the event loop has drained and every lane's frames are finished; the images (a rectified lane's: its
+  // workspace copies) are still resident.  ONE dense launch + ONE cloud launch sequence for all (lane, frame) keyframes of
+  // the lanes that have clouds on — nothing of this lives in the loop's state machines.
+  std::vector<SvoCloudPair> pairs;
+  std::vector<int> frame, lane;
+  for (int l = 0; l < S; ++l) {
+    if (!g->lane_cloud[l]) continue;
+    for (int i = 0; i < batch; ++i)
+      if (results[(size_t)l * batch + i].is_keyframe) {
+        pairs.push_back({lbase[l] + (size_t)i * istride, rbase[l] + (size_t)i * istride});
+        frame.push_back(i); lane.push_back(l);
+      }
+  }
+  return svo_kfc_run(g->kfc, &g->prm.cam, pairs.data(), frame.data(), lane.data(), (int)frame.size());
+}
+
+extern "C" int svo_pipeline_group_set_keyframe_clouds(svo_pipeline_group* g, int lane, const svo_cloud_params* params, int max_keyframes_per_call) {
+  if (!g) return SVO_ERR_INVALID;
+  svo_ctx* ctx = g->ctx;
+  SVO_REQUIRE(ctx, lane >= -1 && lane < g->n_lanes, "pipeline_group_set_keyframe_clouds: no such lane");
+  SVO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  bool others = false;  // lanes outside this call's selection that have clouds on
+  for (int l = 0; l < g->n_lanes; ++l) others = others || (g->lane_cloud[l] && lane >= 0 && l != lane);
+  if (params) {
+    bool same = false;
+    if (g->kfc) {
+      const svo_cloud_params* have = svo_kfc_params(g->kfc);
+      const int want_points = params->max_points > 0 ? params->max_points : g->prm.width * g->prm.height;
+      const int want_kf = max_keyframes_per_call ? max_keyframes_per_call : ctx->lim.max_batch;
+      same = have->step == params->step && have->min_disparity == params->min_disparity && have->max_points == want_points &&
+             svo_kfc_max_keyframes(g->kfc) == want_kf;
+    }
+    SVO_REQUIRE(ctx, same || !others, "pipeline_group_set_keyframe_clouds: the lanes that have clouds on share one set of parameters and one bound");
+    if (!same) {
+      SvoKfClouds* k = nullptr;
+      const int rc = svo_kfc_create(ctx, params, g->prm.width, g->prm.height, max_keyframes_per_call, &k);
+      if (rc) return rc;
+      svo_kfc_destroy(g->kfc);
+      g->kfc = k;
+    }
+  }
+  for (int l = 0; l < g->n_lanes; ++l)
+    if (lane < 0 || l == lane) g->lane_cloud[l] = params != nullptr;
+  bool any = false;
+  for (int l = 0; l < g->n_lanes; ++l) any = any || g->lane_cloud[l];
+  if (!any) { svo_kfc_destroy(g->kfc); g->kfc = nullptr; }  // the last lane turned off: everything goes
+  return SVO_OK;
+}
+
+extern "C" int svo_pipeline_group_keyframe_clouds(svo_pipeline_group* g, int* n, const svo_keyframe_cloud** table) {
+  if (!g || !n) return SVO_ERR_INVALID;
+  *n = 0;
+  if (table) *table = nullptr;
+  SVO_REQUIRE(g->ctx, g->kfc, "pipeline_group_keyframe_clouds: keyframe clouds are off on every lane");
+  return svo_kfc_table(g->kfc, n, table);
+}
+
+extern "C" int svo_pipeline_group_copy_keyframe_cloud(svo_pipeline_group* g, int i, svo_cloud_point* host, int capacity) {
+  if (!g) return SVO_ERR_INVALID;
+  SVO_REQUIRE(g->ctx, g->kfc, "pipeline_group_copy_keyframe_cloud: keyframe clouds are off on every lane");
+  return svo_kfc_copy(g->kfc, i, host, capacity);
 }
 
 // Raw input per lane (include/svo.h).  The tables of a (left, right) pair of models exist once, however many lanes use it.

@@ -746,6 +746,7 @@ struct svo_pipeline {
   std::unique_ptr<svo::ImageProcessor> proc;
   uint8_t* d_imgs = nullptr;  // staging for the host-pointer entry point (left batch | right batch)
   size_t d_imgs_bytes = 0;
+  SvoKfClouds* kfc = nullptr;  // svo_pipeline_set_keyframe_clouds (null: off — nothing below touches the device for it)
 };
 
 extern "C" int svo_reference_constants(svo_reference_constants_t* c) {
@@ -814,6 +815,7 @@ extern "C" void svo_pipeline_destroy(svo_pipeline* p) {
     }
   }
   if (p->d_imgs) (void)hipFree(p->d_imgs);
+  svo_kfc_destroy(p->kfc);
   delete p;
 }
 
@@ -835,6 +837,7 @@ extern "C" int svo_pipeline_process_batch_dev(svo_pipeline* p, const uint8_t* le
   ctx->err.clear();
   SVO_HIP_CHECK(ctx, hipSetDevice(ctx->device));  // the calling thread may never have selected this GPU
   struct Active { Active() { svo::pipeline_count_add(1); } ~Active() { svo::pipeline_count_add(-1); } } active;  // latency / throughput mode
+  if (p->kfc) svo_kfc_clear(p->kfc);  // the table of the previous call ends here
   int rc = p->proc->rectify(&left, &right, batch);  // svo_pipeline_set_rectification: left / right are raw (a no-op otherwise)
   if (rc) return rc;
   rc = p->proc->prepare_batch(left, batch, W, H);
@@ -885,6 +888,15 @@ extern "C" int svo_pipeline_process_batch_dev(svo_pipeline* p, const uint8_t* le
   if (pending_from < 0) pending_from = batch;
   fill_pending(batch);
   if (!ctx->err.empty()) return SVO_ERR_HIP;
+  // svo_pipeline_set_keyframe_clouds: every frame of the call is finished; the images (the rectified copies, if any) are
+  // still resident.  One dense launch + one cloud launch sequence over the pairs that became keyframes.
+  if (p->kfc) {
+    std::vector<SvoCloudPair> pairs;
+    std::vector<int> frame;
+    for (int i = 0; i < batch; ++i)
+      if (results[i].is_keyframe) { pairs.push_back({left + i * istride, right + i * istride}); frame.push_back(i); }
+    return svo_kfc_run(p->kfc, &p->prm.cam, pairs.data(), frame.data(), nullptr, (int)frame.size());
+  }
   return SVO_OK;
 }
 
@@ -909,6 +921,33 @@ extern "C" int svo_pipeline_set_rectification(svo_pipeline* p, const svo_rectify
   if (!p) return SVO_ERR_INVALID;
   p->adjuster->wait();
   return p->proc->set_rectification(left, right, &p->prm.cam, p->prm.width, p->prm.height);
+}
+
+extern "C" int svo_pipeline_set_keyframe_clouds(svo_pipeline* p, const svo_cloud_params* params, int max_keyframes_per_call) {
+  if (!p) return SVO_ERR_INVALID;
+  p->adjuster->wait();
+  SvoKfClouds* k = nullptr;
+  if (params) {
+    const int rc = svo_kfc_create(p->ctx, params, p->prm.width, p->prm.height, max_keyframes_per_call, &k);
+    if (rc) return rc;
+  }
+  svo_kfc_destroy(p->kfc);
+  p->kfc = k;
+  return SVO_OK;
+}
+
+extern "C" int svo_pipeline_keyframe_clouds(svo_pipeline* p, int* n, const svo_keyframe_cloud** table) {
+  if (!p || !n) return SVO_ERR_INVALID;
+  *n = 0;
+  if (table) *table = nullptr;
+  SVO_REQUIRE(p->ctx, p->kfc, "pipeline_keyframe_clouds: keyframe clouds are off (svo_pipeline_set_keyframe_clouds)");
+  return svo_kfc_table(p->kfc, n, table);
+}
+
+extern "C" int svo_pipeline_copy_keyframe_cloud(svo_pipeline* p, int i, svo_cloud_point* host, int capacity) {
+  if (!p) return SVO_ERR_INVALID;
+  SVO_REQUIRE(p->ctx, p->kfc, "pipeline_copy_keyframe_cloud: keyframe clouds are off (svo_pipeline_set_keyframe_clouds)");
+  return svo_kfc_copy(p->kfc, i, host, capacity);
 }
 
 extern "C" int svo_pipeline_draw_track(svo_pipeline* p, const uint8_t* keyframe_gray, int row_stride, uint8_t* rgb) {

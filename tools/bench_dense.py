@@ -1,0 +1,180 @@
+#!/usr/bin/env python3
+"""What dense keyframe depth costs on the MI355X (a tool: bench.py is untouched and measures no clouds).
+
+One process, one GPU, HIP events (svo_profile_select) around the launches:
+  1. dense map: the fused batched launch (stereo_dense_batch_kernel, raw images in, 16 pairs per launch) per pair, beside
+     the three-launch sequence inside svo_stereo_bm (two prefilter launches + stereo_dense_kernel, one pair per call) timed
+     in the same run, both at 1241 x 376, StereoBM(48, 21);
+  2. cloud: the count + scan + write launches per pair at steps 1 and 4, with the bytes they move and
+     svo_measure_peak("hbm_copy") of the same run;
+  3. cost to the VO: bench.py's headline load (96 lanes in 3 pipeline groups of 16-frame steps) without and with keyframe
+     clouds at step 4, alternating, as frames/s, their ratio and the spread over the rounds.
+Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import bench  # noqa: E402  (its module level sets the hardware-queue count bench.py measures with, before HIP starts)
+import numpy as np  # noqa: E402
+
+W, H = bench.W, bench.H
+NDISP, BLOCK = 48, 21
+
+
+def standalone(S, torch, batch, warmup, reps):
+    from stereo_vo_amd import api
+    ctx = S.Context(W, H, max_batch=batch, max_corners=64, max_candidates=1 << 12, max_features=64)
+    p = S.synth_default(W, H)
+    cam = S.CameraInfo(p.focal, p.cx, p.cy, 0, 0, 0, 0, p.baseline)
+    pairs = [S.synth_render(p, i) for i in range(batch)]
+    dl = torch.from_numpy(np.stack([x[0] for x in pairs])).cuda()
+    dr = torch.from_numpy(np.stack([x[1] for x in pairs])).cuda()
+    dm = torch.empty((batch, H, W), dtype=torch.int16, device="cuda")
+    torch.cuda.synchronize()
+    copy = ctx.measure_peak("hbm_copy")
+    out = {"batch": batch, "hbm_copy_bytes_per_s": copy}
+
+    def fused():
+        ctx.stereo_bm_batch(dl.data_ptr(), dr.data_ptr(), batch, W, H, W, W * H, dm.data_ptr(), NDISP, BLOCK)
+
+    def timed(tag, fn, n):
+        for _ in range(warmup):
+            fn()
+        ctx.profile_select(tag)
+        for _ in range(n):
+            fn()
+        ms, k = ctx.profile_read()
+        ctx.profile_select("")
+        return ms, k
+
+    ms, k = timed("stereo_dense_batch", fused, reps)
+    out["fused_ms_per_pair"] = ms / k / batch
+    out["fused_launches_timed"] = k
+    # the baseline: svo_stereo_bm's own three launches, one pair per call (its host copies are outside the bracket)
+    ms, k = timed("stereo_bm", lambda: [ctx.stereo_bm(x[0], x[1], NDISP, BLOCK) for x in pairs], max(reps // 4, 2))
+    out["three_launch_ms_per_pair"] = ms / k
+    out["three_launch_calls_timed"] = k
+    same = all(np.array_equal(dm[i].cpu().numpy(), ctx.stereo_bm(pairs[i][0], pairs[i][1], NDISP, BLOCK)) for i in (0, batch - 1))
+    out["fused_equals_three_launch"] = bool(same)
+    # clouds of those maps
+    out["cloud"] = []
+    for step in (1, 4):
+        mp = ((W + step - 1) // step) * ((H + step - 1) // step)
+        pts = torch.empty((batch, mp, 4), dtype=torch.int32, device="cuda")
+        cnt = torch.zeros((batch, 2), dtype=torch.int32, device="cuda")
+        prm = api.CloudParams(step, 0.0, mp)
+        ms, k = timed("cloud", lambda: ctx.disparity_cloud(dm.data_ptr(), dl.data_ptr(), batch, W, H, W, W * H, cam, None, prm, pts.data_ptr(),
+                                                          cnt.data_ptr()), reps)
+        kept = float(cnt.cpu().numpy()[:, 0].mean())
+        # per pair: the map's sampled values read twice (count + write: 2 B each, a whole 64-B sector per sample once step > 1 is
+        # NOT counted), the left pixel of every kept point, 16 B written per point
+        nbytes = 2 * 2 * mp + kept * (1 + 16)
+        per = ms / k / batch * 1e-3
+        out["cloud"].append({"step": step, "ms_per_pair": 1e3 * per, "kept_per_pair": kept, "algorithmic_bytes_per_pair": nbytes,
+                             "bytes_per_s": nbytes / per, "share_of_copy_rate": nbytes / per / copy, "sequences_timed": k})
+    ctx.close()
+    return out
+
+
+def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
+    from stereo_vo_amd import api
+    bench.group_lines(n_groups)
+    seeds = [0x5EED0001 + i for i in range(lanes)]
+    groups = [bench._Group(S, torch, 0, seeds[gi::n_groups], frames) for gi in range(n_groups)]
+    torch.cuda.synchronize()
+    prm = api.CloudParams(step_px, 0.0, ((W + step_px - 1) // step_px) * ((H + step_px - 1) // step_px))
+
+    def run(k):
+        def work(g):
+            for _ in range(k):
+                g.step()
+        bench.run_threads([lambda g=g: work(g) for g in groups])
+
+    def table_len(pipe):  # entries of the last call's table (no point is copied)
+        import ctypes as C
+        n, tab = C.c_int(0), C.c_void_p()
+        pipe.ctx._chk(pipe.L.svo_pipeline_group_keyframe_clouds(pipe.h, C.byref(n), C.byref(tab)), "svo_pipeline_group_keyframe_clouds")
+        return n.value
+
+    def timed(on):
+        for g in groups:
+            g.pipe.set_keyframe_clouds(-1, prm if on else None)
+            g.clear_counters()
+        run(warmup)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run(steps)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        kf = sum(table_len(g.pipe) for g in groups) if on else 0  # of the last step
+        return lanes * frames * steps / dt, 1e3 * dt / steps, kf
+
+    plain, cloud = [], []
+    for _ in range(rounds):  # alternating: other people's work shares the host
+        plain.append(timed(False))
+        cloud.append(timed(True))
+    for g in groups:
+        g.close()
+    med = lambda xs: float(np.median(xs))
+    fp, fc = med([x[0] for x in plain]), med([x[0] for x in cloud])
+    return {"lanes": lanes, "groups": n_groups, "frames_per_step_per_lane": frames, "steps": steps, "rounds": rounds, "cloud_step": step_px,
+            "frames_per_s_plain": fp, "frames_per_s_clouds": fc, "ratio": fc / fp,
+            "step_ms_plain": med([x[1] for x in plain]), "step_ms_clouds": med([x[1] for x in cloud]),
+            "keyframes_in_last_step": [x[2] for x in cloud],
+            "all_plain": [x[0] for x in plain], "all_clouds": [x[0] for x in cloud]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--lanes", type=int, default=96)
+    ap.add_argument("--groups", type=int, default=3)
+    ap.add_argument("--frames", type=int, default=16)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=15)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--cloud-step", type=int, default=4)
+    ap.add_argument("--skip-groups", action="store_true")
+    ap.add_argument("--out", help="write the text report here as well")
+    a = ap.parse_args()
+    import torch
+    import stereo_vo_amd as S
+    if not torch.cuda.is_available():
+        sys.exit("bench_dense: needs the GPU (nothing is measured without it)")
+    res = {"standalone": standalone(S, torch, a.batch, 3, a.reps)}
+    if not a.skip_groups:
+        res["pipeline_groups"] = grouped(S, torch, a.lanes, a.groups, a.frames, a.warmup, a.steps, a.rounds, a.cloud_step)
+    try:
+        res["commit"] = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
+    except OSError:
+        res["commit"] = None
+    print(json.dumps(res))
+    if a.out:
+        s, g = res["standalone"], res.get("pipeline_groups")
+        with open(a.out, "w") as f:
+            f.write(f"dense map, {W} x {H}, StereoBM({NDISP}, {BLOCK}), HIP events:\n"
+                    f"  stereo_dense_batch_kernel, {s['batch']} pairs per launch: {s['fused_ms_per_pair']:.4f} ms per pair (mean of {s['fused_launches_timed']} launches)\n"
+                    f"  the three launches inside svo_stereo_bm, one pair per call: {s['three_launch_ms_per_pair']:.4f} ms per pair "
+                    f"(mean of {s['three_launch_calls_timed']} calls); ratio fused / three-launch {s['fused_ms_per_pair'] / s['three_launch_ms_per_pair']:.3f}; "
+                    f"maps identical: {s['fused_equals_three_launch']}\n")
+            for c in s["cloud"]:
+                f.write(f"cloud (count + scan + write), step {c['step']}: {c['ms_per_pair']:.4f} ms per pair, {c['kept_per_pair']:.0f} points kept per pair, "
+                        f"{c['algorithmic_bytes_per_pair'] / 1e6:.3f} MB per pair -> {c['bytes_per_s'] / 1e12:.3f} TB/s "
+                        f"({100 * c['share_of_copy_rate']:.1f} % of svo_measure_peak(hbm_copy) = {s['hbm_copy_bytes_per_s'] / 1e12:.3f} TB/s, same run)\n")
+            if g:
+                f.write(f"{g['lanes']} lanes in {g['groups']} groups, {g['frames_per_step_per_lane']}-frame steps, median of {g['rounds']} alternating rounds of "
+                        f"{g['steps']} steps, clouds at step {g['cloud_step']}:\n  without clouds {g['frames_per_s_plain']:.0f} frames/s ({g['step_ms_plain']:.1f} ms / step), "
+                        f"with {g['frames_per_s_clouds']:.0f} frames/s ({g['step_ms_clouds']:.1f} ms / step): ratio {g['ratio']:.3f}\n"
+                        f"  rounds without: {[round(x) for x in g['all_plain']]}, with: {[round(x) for x in g['all_clouds']]}; "
+                        f"keyframes in the last step of each round with clouds: {g['keyframes_in_last_step']}\n")
+
+
+if __name__ == "__main__":
+    main()
