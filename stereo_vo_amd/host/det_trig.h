@@ -59,6 +59,28 @@ SVO_HD inline void svo_det_rodrigues_f(const float* rv, float* R9) {
   for (int i = 0; i < 9; ++i) R9[i] = (float)R[i];
 }
 
+// Eigen::Quaternionf(Matrix3f) (src/image_processor.cpp:87-92), float arithmetic, row-major m: host only (both pipelines' after-PnP step)
+inline void svo_det_quat_from_R(const float* m, float* q /*wxyz*/) {
+  float t = m[0] + m[4] + m[8];
+  if (t > 0.f) {
+    t = sqrtf(t + 1.0f);
+    q[0] = 0.5f * t;
+    t = 0.5f / t;
+    q[1] = (m[7] - m[5]) * t; q[2] = (m[2] - m[6]) * t; q[3] = (m[3] - m[1]) * t;
+  } else {
+    int i = 0;
+    if (m[4] > m[0]) i = 1;
+    if (m[8] > m[4 * i]) i = 2;
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    t = sqrtf(m[4 * i] - m[4 * j] - m[4 * k] + 1.0f);
+    q[1 + i] = 0.5f * t;
+    t = 0.5f / t;
+    q[0] = (m[3 * k + j] - m[3 * j + k]) * t;
+    q[1 + j] = (m[3 * j + i] + m[3 * i + j]) * t;
+    q[1 + k] = (m[3 * k + i] + m[3 * i + k]) * t;
+  }
+}
+
 // rvec (as doubles) -> the unit quaternion the PnP solver starts from (extrinsic guess, src/image_processor.cpp:76-80)
 SVO_HD inline void svo_det_quat_from_rvec(const double* rv, double* q /*wxyz*/) {
   const double th = sqrt(rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2]);

@@ -30,40 +30,19 @@
 #include "chain_math.h"
 #include "det_trig.h"
 #include "group_kernels.h"
+#include "group_lines.h"
 #include "ref_constants.h"
 #include "svo.h"
 
 namespace {
 
-// cv::Rodrigues on a CV_32F rvec with declared arithmetic (host/det_trig.h): the same bits on the host, on the device and in the oracle
-inline void rodrigues_f(const float* rv, float* R9) { svo_det_rodrigues_f(rv, R9); }
-
-// Eigen::Quaternionf(Matrix3f) (src/image_processor.cpp:92), float arithmetic, row-major m.
-void quat_from_R(const float* m, float* q /*wxyz*/) {
-  float t = m[0] + m[4] + m[8];
-  if (t > 0.f) {
-    t = sqrtf(t + 1.0f);
-    q[0] = 0.5f * t;
-    t = 0.5f / t;
-    q[1] = (m[7] - m[5]) * t; q[2] = (m[2] - m[6]) * t; q[3] = (m[3] - m[1]) * t;
-  } else {
-    int i = 0;
-    if (m[4] > m[0]) i = 1;
-    if (m[8] > m[4 * i]) i = 2;
-    const int j = (i + 1) % 3, k = (j + 1) % 3;
-    t = sqrtf(m[4 * i] - m[4 * j] - m[4 * k] + 1.0f);
-    q[1 + i] = 0.5f * t;
-    t = 0.5f / t;
-    q[0] = (m[3 * k + j] - m[3 * j + k]) * t;
-    q[1 + j] = (m[3 * j + i] + m[3 * i + j]) * t;
-    q[1 + k] = (m[3 * k + i] + m[3 * i + k]) * t;
-  }
-}
-
 enum LaneState { L_IDLE = 0, L_TRACK_WAIT, L_NEED_SOLVE, L_PNP_WAIT, L_TRI_WAIT, L_DONE };
 enum BaState { BA_NONE = 0, BA_ASSEMBLING, BA_READY, BA_INFLIGHT, BA_HOST_SOLVING, BA_HOST_DONE };
 enum Word { W_TRACK = 0, W_PNP, W_TRI, W_COUNT };
 enum Counter { C_LK = 0, C_PNP, C_TRI, C_COUNT };
+// statistics of a batch, in the order svo_pipeline_group_last_stats returns them: launches by kind and the lanes they carried; ST_HOST_US
+// holds two times instead (microseconds of the driving thread's loop passes that did something, of the call's main loop)
+enum Stat { ST_TRACK = 0, ST_PNP, ST_HOST_US, ST_TRI, ST_SOLVE, ST_FRONT_END, ST_COUNT };
 
 struct Lane {
   int lk_line = 0, chain_line = 0;  // the tracking / keyframe-chain line (stream) its launch in flight went to
@@ -77,7 +56,7 @@ struct Lane {
   bool from_host = false;           // the next track reads its features from h_kf_* (tracker (re)initialised by a keyframe)
   const uint8_t* last_pyr = nullptr;
   const uint8_t* last_l0 = nullptr;  // level 0 of last_pyr: inside it, or (within the batch that produced it) the caller's image read in place
-  uint8_t* d_own_pyr = nullptr;      // the lane's private clone of its last image's pyramid, used when a whole batch went by without tracking (see process_batch)
+  uint8_t* d_own_pyr = nullptr;      // the lane's private clone of its last image's pyramid, used when a whole batch went by without tracking (see Batch::front_end)
   // ---- PnP
   float4* d_store = nullptr; unsigned store_mask = 0;  // device-resident landmark store of the lane, keyed by feature id (get_world_points, src/bundle_adjuster.cpp:159-163)
   double* d_hyp_pose = nullptr; int* d_hyp_count = nullptr; unsigned long long* d_hyp_mask = nullptr;
@@ -182,10 +161,7 @@ struct svo_pipeline_group {
   // SVO_TIMING: host time of the group thread inside the per-keyframe graph calls (ns), and keyframes seen
   double t_get_points = 0, t_add_keyframe = 0, t_finish = 0, t_loop = 0; long n_kf = 0; bool timing = false;
   double gather_us = 0.0;      // > 0: a stage's launch waits up to this long for the other lanes of its line that are still on their way
-  double lk_overlap_us = 0.0;  // > 0: a second tracking line may depart once every launch in flight is at least this old (it is in its tail then)
-  double lk_t0[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // departure time of the launch in flight on each tracking line (us since the call began)
-  hipStream_t st_lk[MAX_LINES + 1] = {}, st_chain[MAX_LINES + 1] = {}, st_ba[MAX_LINES] = {};  // [MAX_LINES]: the express lines (see process_batch)
-  bool express = false;
+  hipStream_t st_lk[MAX_LINES] = {}, st_chain[MAX_LINES] = {}, st_ba[MAX_LINES] = {};
   int ba_launch_id = 0;
   unsigned long long ba_ready_counter = 0;
   // batch-wide front-end outputs
@@ -194,8 +170,7 @@ struct svo_pipeline_group {
   int* h_counts = nullptr;  // pinned: n_lanes x max_batch corner counts + status
   Pool pool;
   int pnp_iterations = 0, mask_words_cap = 0;
-  // statistics of the last batch (launches by kind and the lanes they carried)
-  long launches[6] = {0, 0, 0, 0, 0, 0}, lanes_carried[6] = {0, 0, 0, 0, 0, 0};
+  long launches[ST_COUNT] = {}, lanes_carried[ST_COUNT] = {};  // statistics of the last batch (enum Stat)
   // host-pointer / streaming entry: two pinned staging slots, their device twins, a copy stream (allocated on first use)
   uint8_t* h_stage[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // [slot][left / right]
   uint8_t* d_stage[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
@@ -274,10 +249,10 @@ int finish_solve(svo_pipeline_group* g, Lane* l) {
 // mirrors and completion words), and arrive_total[] / seq[] were advanced for launches that may never have run.  Drain every
 // line, then bring device counters, host totals and completion words back to a common zero.
 void quiesce_after_error(svo_pipeline_group* g) {
-  for (int i = 0; i <= svo_pipeline_group::MAX_LINES; ++i) {
+  for (int i = 0; i < svo_pipeline_group::MAX_LINES; ++i) {
     if (g->st_lk[i]) (void)hipStreamSynchronize(g->st_lk[i]);
     if (g->st_chain[i]) (void)hipStreamSynchronize(g->st_chain[i]);
-    if (i < svo_pipeline_group::MAX_LINES && g->st_ba[i]) (void)hipStreamSynchronize(g->st_ba[i]);
+    if (g->st_ba[i]) (void)hipStreamSynchronize(g->st_ba[i]);
   }
   for (Lane* l : g->lanes) {
     (void)hipMemset(l->d_arrive, 0, sizeof(unsigned) * 16 * C_COUNT);
@@ -305,10 +280,10 @@ extern "C" void svo_pipeline_group_destroy(svo_pipeline_group* g) {
   (void)hipStreamSynchronize(g->ctx->stream);
   for (Lane* l : g->lanes) { if (l->ba) { svo_ba_destroy(l->ba); l->ba = nullptr; } }  // before the lines they work on (svo_ba_use_stream) go
   if (g->counted_lanes) svo_ba_note_group_lanes(-g->counted_lanes);
-  for (int i = 0; i <= svo_pipeline_group::MAX_LINES; ++i) {
+  for (int i = 0; i < svo_pipeline_group::MAX_LINES; ++i) {
     if (g->st_lk[i] && g->st_lk[i] != g->ctx->stream) { (void)hipStreamSynchronize(g->st_lk[i]); (void)hipStreamDestroy(g->st_lk[i]); }
     if (g->st_chain[i]) { (void)hipStreamSynchronize(g->st_chain[i]); (void)hipStreamDestroy(g->st_chain[i]); }
-    if (i < svo_pipeline_group::MAX_LINES && g->st_ba[i]) { (void)hipStreamSynchronize(g->st_ba[i]); (void)hipStreamDestroy(g->st_ba[i]); }
+    if (g->st_ba[i]) { (void)hipStreamSynchronize(g->st_ba[i]); (void)hipStreamDestroy(g->st_ba[i]); }
   }
   if (g->st_copy) { (void)hipStreamSynchronize(g->st_copy); (void)hipStreamDestroy(g->st_copy); }
   for (int sl = 0; sl < 2; ++sl) {
@@ -362,55 +337,18 @@ extern "C" int svo_pipeline_group_create(svo_ctx* ctx, svo_pipeline_group** out,
     g->n_lk = knob("SVO_GROUP_LK_LINES", 1, svo_pipeline_group::MAX_LINES);
     g->timing = getenv("SVO_TIMING") != nullptr;
     { const char* e = getenv("SVO_GROUP_GATHER_US"); g->gather_us = e && *e ? std::max(0.0, atof(e)) : 0.0; }
-    { const char* e = getenv("SVO_GROUP_LK_OVERLAP_US"); g->lk_overlap_us = e && *e ? std::max(0.0, atof(e)) : 0.0; }
     g->n_chain = knob("SVO_GROUP_CHAIN_LINES", 2, svo_pipeline_group::MAX_LINES);
     { const char* e = getenv("SVO_GROUP_LK_XCD"); g->xcd_map = !(e && *e && atoi(e) == 0); }
     { const char* e = getenv("SVO_GROUP_TRI_XCD"); g->xcd_map_tri = !(e && *e && atoi(e) == 0); }
     { const char* e = getenv("SVO_GROUP_XCD_CHUNKS"); if (e && *e) g->xcd_chunks = std::max(8, std::min(64, atoi(e) / 8 * 8)); }  // developer experiments
     g->n_ba = knob("SVO_GROUP_BA_LINES", 4, svo_pipeline_group::MAX_LINES);
     { const char* e = getenv("SVO_GROUP_COMPACT_LINES"); g->n_cmp = e && *e ? std::max(0, std::min(atoi(e), svo_pipeline_group::MAX_LINES - g->n_ba)) : 0; }
+    // plain streams for every line: high-priority chain lines, solve lines of another priority class, the tracker on fewer CUs
+    // were all measured slower (profiles/r03_group_sweep.txt, r05_exp_lanes_groups*.txt)
     g->st_lk[0] = ctx->stream;
-    // experiment knob: the tracker's launches on `keep` of every 32 CUs only (the rest stays free for the short kernels of the
-    // keyframe chains and the solves)
-    int keep = 32;
-    { const char* e = getenv("SVO_GROUP_LK_CU_KEEP"); if (e && *e) keep = std::max(4, std::min(32, atoi(e))); }
-    for (int i = 0; i < g->n_lk; ++i) {
-      if (i == 0 && keep == 32) continue;
-      if (keep < 32) {
-        uint32_t mask[8];
-        for (int w = 0; w < 8; ++w) mask[w] = (uint32_t)((1ull << keep) - 1ull);
-        chk(hipExtStreamCreateWithCUMask(&g->st_lk[i], 8, mask), "stream");
-      } else {
-        chk(hipStreamCreateWithFlags(&g->st_lk[i], hipStreamNonBlocking), "stream");
-      }
-    }
-    // experiment knob SVO_GROUP_CHAIN_PRIORITY=1: the short kernels of the keyframe chains (world-point upload, PnP, dedup,
-    // stereo + triangulation) on high-priority streams.  Under the group load a 2 us kernel takes 76 us on average (it waits
-    // for wavefront slots behind the tracker's thousands of workgroups) — but measured 15.1-15.2 k against 16.6-16.7 k
-    // frames/s with plain streams: off by default.
-    int prio_lo = 0, prio_hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    const char* pe = getenv("SVO_GROUP_CHAIN_PRIORITY");
-    const bool chain_hi = pe && *pe && atoi(pe) != 0 && prio_hi != prio_lo;
-    for (int i = 0; i < g->n_chain; ++i) {
-      if (chain_hi) chk(hipStreamCreateWithPriority(&g->st_chain[i], hipStreamNonBlocking, prio_hi), "stream");
-      else chk(hipStreamCreateWithFlags(&g->st_chain[i], hipStreamNonBlocking), "stream");
-    }
-    {
-      // SVO_GROUP_BA_PRIORITY=low|high: the solve lines as streams of another priority class — the runtime keeps one pool of hardware
-      // queues per class, so they can never share a queue with (and block) a tracking or keyframe-chain launch
-      const char* be = getenv("SVO_GROUP_BA_PRIORITY");
-      const int ba_prio = (be && be[0] == 'l') ? prio_lo : ((be && be[0] == 'h') ? prio_hi : 0);
-      for (int i = 0; i < g->n_ba + g->n_cmp; ++i) {
-        if (ba_prio != 0 && prio_hi != prio_lo) chk(hipStreamCreateWithPriority(&g->st_ba[i], hipStreamNonBlocking, ba_prio), "stream");
-        else chk(hipStreamCreateWithFlags(&g->st_ba[i], hipStreamNonBlocking), "stream");
-      }
-    }
-    { const char* e = getenv("SVO_GROUP_EXPRESS"); g->express = e && *e && atoi(e) != 0; }  // off by default: measured 17.1 k against 18.3 k frames/s on the bench
-    if (g->express) {
-      chk(hipStreamCreateWithFlags(&g->st_lk[svo_pipeline_group::MAX_LINES], hipStreamNonBlocking), "stream");
-      chk(hipStreamCreateWithFlags(&g->st_chain[svo_pipeline_group::MAX_LINES], hipStreamNonBlocking), "stream");
-    }
+    for (int i = 1; i < g->n_lk; ++i) chk(hipStreamCreateWithFlags(&g->st_lk[i], hipStreamNonBlocking), "stream");
+    for (int i = 0; i < g->n_chain; ++i) chk(hipStreamCreateWithFlags(&g->st_chain[i], hipStreamNonBlocking), "stream");
+    for (int i = 0; i < g->n_ba + g->n_cmp; ++i) chk(hipStreamCreateWithFlags(&g->st_ba[i], hipStreamNonBlocking), "stream");
   }
   g->pyr_stride = svo_k_pyramid_bytes(p->width, p->height);
   if (!rc) rc = dev_alloc(g, &g->d_corners, 2 * mc * S * B);
@@ -422,17 +360,11 @@ extern "C" int svo_pipeline_group_create(svo_ctx* ctx, svo_pipeline_group** out,
     // on the creating thread, in a fixed order: the binding becomes a function of the creation order alone.  SVO_GROUP_TOUCH=0: off.
     const char* e = getenv("SVO_GROUP_TOUCH");
     if (!(e && *e && atoi(e) == 0)) {
-      hipStream_t order[3 * (svo_pipeline_group::MAX_LINES + 1)];
+      hipStream_t order[3 * svo_pipeline_group::MAX_LINES];
       int no = 0;
-      if (e && atoi(e) == 2) {  // (experiment: tracking and chain lines first)
-        for (int i = 0; i < g->n_lk; ++i) order[no++] = g->st_lk[i];
-        for (int i = 0; i < g->n_chain; ++i) order[no++] = g->st_chain[i];
-        for (int i = 0; i < g->n_ba + g->n_cmp; ++i) order[no++] = g->st_ba[i];
-      } else {
-        for (int i = 0; i < g->n_ba + g->n_cmp; ++i) order[no++] = g->st_ba[i];
-        for (int i = 0; i < g->n_chain; ++i) order[no++] = g->st_chain[i];
-        for (int i = 0; i < g->n_lk; ++i) order[no++] = g->st_lk[i];
-      }
+      for (int i = 0; i < g->n_ba + g->n_cmp; ++i) order[no++] = g->st_ba[i];
+      for (int i = 0; i < g->n_chain; ++i) order[no++] = g->st_chain[i];
+      for (int i = 0; i < g->n_lk; ++i) order[no++] = g->st_lk[i];
       for (int i = 0; i < no && !rc; ++i) {
         chk(hipMemsetAsync(g->d_corners, 0, 16, order[i]), "hipMemsetAsync");
         chk(hipStreamSynchronize(order[i]), "hipStreamSynchronize");
@@ -510,7 +442,7 @@ extern "C" int svo_pipeline_group_create(svo_ctx* ctx, svo_pipeline_group** out,
     rc = svo_ba_create(ctx, &l->ba, p->window_size, &p->cam, &opt, max_obs, max_obs);
     if (!rc) rc = svo_ba_attach_store(l->ba, l->d_store, l->store_mask);
     // the lane's adjuster works on the group's solve lines (no stream of its own: see the hardware-queue note above)
-    { const char* e = getenv("SVO_GROUP_OWN_BA_STREAMS"); if (!rc && !(e && *e && atoi(e) != 0)) rc = svo_ba_use_stream(l->ba, g->st_ba[li % g->n_ba]); }
+    if (!rc) rc = svo_ba_use_stream(l->ba, g->st_ba[li % g->n_ba]);
     // (the window solves keep the wide form unless SVO_BA_FORM=compact: measured in round 5, one workgroup per solve costs a lane
     // ~10x the solve latency and halves the frame rate at 48 lanes — profiles/r05_exp_compact_lanes.txt; the compact form serves as
     // the overflow of the admission budget, SVO_BA_OVERFLOW, and as the re-run of a solve that gave up)
@@ -551,9 +483,6 @@ extern "C" int svo_pipeline_group_reset(svo_pipeline_group* g) {
     l->fused = false; l->pnp_all = false;
     // (on the context's stream and waited for below: hipMemset on device memory may return before the fill has run, and the group's
     // lines are non-blocking streams — a fill that landed behind the first solve of the next batch wiped its entries; seen under rocprofv3)
-    static const int fill_mode = [] { const char* e = getenv("SVO_GROUP_RESET_FILL"); return e ? atoi(e) : 0; }();  // experiment: 1 = null stream, not waited for (before 954d023); 2 = no fill
-    if (fill_mode == 1) { if (l->d_store && hipMemset(l->d_store, 0xFF, sizeof(float4) * ((size_t)l->store_mask + 1)) != hipSuccess && !rc_join) rc_join = SVO_ERR_HIP; }
-    else if (fill_mode == 0)
     if (l->d_store && hipMemsetAsync(l->d_store, 0xFF, sizeof(float4) * ((size_t)l->store_mask + 1), g->ctx->stream) != hipSuccess && !rc_join) rc_join = SVO_ERR_HIP;
   }
   if (hipStreamSynchronize(g->ctx->stream) != hipSuccess && !rc_join) rc_join = SVO_ERR_HIP;
@@ -604,112 +533,82 @@ extern "C" int svo_pipeline_group_solve_forms(svo_pipeline_group* g, long* count
 
 extern "C" int svo_pipeline_group_last_stats(const svo_pipeline_group* g, long* launches6, long* lanes6) {
   if (!g || !launches6 || !lanes6) return SVO_ERR_INVALID;
-  for (int i = 0; i < 6; ++i) { launches6[i] = g->launches[i]; lanes6[i] = g->lanes_carried[i]; }
+  static_assert(ST_COUNT == 6, "svo_pipeline_group_last_stats returns six slots");
+  for (int i = 0; i < ST_COUNT; ++i) { launches6[i] = g->launches[i]; lanes6[i] = g->lanes_carried[i]; }
   return SVO_OK;
 }
 
 namespace {
-// The batch itself.  lbase[l] / rbase[l]: lane l's `batch` rectified images (tight rows, width*height bytes apart), wherever
-// they live: the caller's buffers, or the rectified workspace for a lane with a camera model.
-int group_process(svo_pipeline_group* g, const uint8_t* const* lbase, const uint8_t* const* rbase, int batch, svo_frame_result* results) {
-  svo_ctx* ctx = g->ctx;
-  const int W = g->prm.width, H = g->prm.height, S = g->n_lanes, mc = g->prm.max_corners;
-  const size_t istride = (size_t)W * H;
-  hipStream_t st = ctx->stream;
-  bool tight = true;  // the lanes' images are one contiguous run: the batch-wide launches take all of them at once
-  for (int l = 1; l < S; ++l) tight = tight && lbase[l] == lbase[0] + (size_t)l * batch * istride;
-  const uint8_t* const left = lbase[0];
-  const size_t lane_stride = istride * (size_t)batch;  // (of the contiguous case)
-  for (int i = 0; i < 6; ++i) { g->launches[i] = 0; g->lanes_carried[i] = 0; }
+bool trace_enabled() { static const bool on = getenv("SVO_GROUP_TRACE") != nullptr; return on; }  // SVO_GROUP_TRACE=1: (microseconds, lane, event) of every call on stderr — where a lane's time goes
+// the keyframe chain without a host turn between PnP and stereo + triangulation (round 5); SVO_GROUP_CHAIN_FUSED=0: one launch,
+// one host turn each, as before — same results either way (tests/test_group.py)
+bool chain_fused_enabled() { static const bool on = [] { const char* e = getenv("SVO_GROUP_CHAIN_FUSED"); return !(e && *e && atoi(e) == 0); }(); return on; }
+// test hook: every window down the host-driven path (the landmark store is then filled by the scatter launch)
+bool host_solves_only() { static const bool on = [] { const char* e = getenv("SVO_GROUP_HOST_SOLVES"); return e && *e && atoi(e) != 0; }(); return on; }
 
-  // ---- a1 on every frame of every lane + the pyramids (the reference detects on every frame, src/image_processor.cpp:22)
-  g->pyr_cur ^= 1;  // the previous batch's pyramids stay valid: a lane's last tracked image lives there (src/feature_tracker.cpp:66)
-  uint8_t* pyr = g->d_pyr[g->pyr_cur];
-  int rc = SVO_OK;
-  // ... but a lane that neither tracked nor made a keyframe during the WHOLE previous batch (every frame below MIN_DETECTED
-  // corners, C-7; with batch = 1 one blank frame is enough) still holds its last image in the buffer that is rebuilt now:
-  // the reference keeps a clone of it (src/feature_tracker.cpp:14,66), so the lane takes a private copy first (same stream
-  // as the rebuild: ordered in front of it).
-  {
-    const uint8_t* lo = pyr;
-    const uint8_t* hi = pyr + g->pyr_stride * (size_t)g->n_lanes * (size_t)g->max_batch;
-    for (Lane* l : g->lanes) {
-      if (!l->last_pyr || l->last_pyr < lo || l->last_pyr >= hi) continue;
-      SVO_HIP_CHECK(ctx, hipMemcpyAsync(l->d_own_pyr, l->last_pyr, g->pyr_stride, hipMemcpyDeviceToDevice, ctx->stream));
-      l->last_pyr = l->d_own_pyr;  // level 0 was cloned into the pyramid at the end of the batch that produced it
-      l->last_l0 = l->d_own_pyr;
-    }
-  }
-  if (tight) {
-    rc = svo_corner_detect_batch_dev(ctx, left, S * batch, W, H, W, istride, mc, g->prm.quality, (double)g->prm.min_feature_distance, g->d_corners, g->d_ncorners);
-    // level 0 of the pyramids is NOT copied: the tracker reads the caller's images in place (Pyr::l0) — except every lane's
-    // last frame, which the next batch tracks from when the caller's buffer may hold other frames
-    if (!rc) rc = svo_k_build_pyramid(ctx, left, S * batch, W, H, W, istride, pyr, g->pyr_stride, true);
-    if (!rc) rc = svo_k_pyramid_level0(ctx, left + (size_t)(batch - 1) * istride, S, W, H, W, lane_stride, pyr + (size_t)(batch - 1) * g->pyr_stride,
-                                       (size_t)batch * g->pyr_stride, st);
-  } else {
-    for (int l = 0; l < S && !rc; ++l) {
-      rc = svo_corner_detect_batch_dev(ctx, lbase[l], batch, W, H, W, istride, mc, g->prm.quality, (double)g->prm.min_feature_distance,
-                                       g->d_corners + (size_t)l * batch * 2 * mc, g->d_ncorners + (size_t)l * batch);
-      if (!rc) rc = svo_k_build_pyramid(ctx, lbase[l], batch, W, H, W, istride, pyr + (size_t)l * batch * g->pyr_stride, g->pyr_stride, true);
-      if (!rc) rc = svo_k_pyramid_level0(ctx, lbase[l] + (size_t)(batch - 1) * istride, 1, W, H, W, istride,
-                                         pyr + ((size_t)l * batch + (size_t)(batch - 1)) * g->pyr_stride, g->pyr_stride, st);
-    }
-  }
-  if (rc) return rc;
-  g->launches[5] += 7; g->lanes_carried[5] += 7 * S;
-  int* hc = g->h_counts;
-  SVO_HIP_CHECK(ctx, hipMemcpyAsync(hc, g->d_ncorners, sizeof(int) * S * batch, hipMemcpyDeviceToHost, st));
-  SVO_HIP_CHECK(ctx, hipMemcpyAsync(hc + S * batch, ctx->d_status, sizeof(int), hipMemcpyDeviceToHost, st));
-  SVO_HIP_CHECK(ctx, hipStreamSynchronize(st));
-  if (hc[S * batch]) {
-    (void)hipMemsetAsync(ctx->d_status, 0, sizeof(int), st);
-    ctx->err = (hc[S * batch] & 8) ? "corner detection: more raw local maxima than the streaming pass's list holds (raw_cap: width x height / 4 per image under a 1 GiB budget)"
-                         : "corner detection exceeded a workspace bound (svo_limits.max_candidates)";
-    return SVO_ERR_CAPACITY;
-  }
+// One call of the batch entry: what its stages share, the per-lane state machine (start_frame ... frame_done, the statements
+// of host/pipeline.cpp's ImageProcessor::process), the launches of a pass and the driver (run).
+// lbase[l] / rbase[l]: lane l's `batch` rectified images (tight rows, width*height bytes apart), wherever they live: the
+// caller's buffers, or the rectified workspace for a lane with a camera model.
+struct Batch {
+  using Clock = std::chrono::steady_clock;
+  struct Ev { double us; int lane; const char* what; int arg; };
+  static constexpr int MAX_LINES = svo_pipeline_group::MAX_LINES;
 
-  auto RES = [&](int lane, int f) -> svo_frame_result& { return results[(size_t)lane * batch + f]; };
-  auto IMG = [&](const uint8_t* const* base, int lane, int f) { return base[lane] + (size_t)f * istride; };
-  auto PYR = [&](int lane, int f) { return pyr + ((size_t)lane * batch + f) * g->pyr_stride; };
-  // level 0 of frame f's pyramid: the caller's image, except the batch's last frame (copied into the pyramid above)
-  auto L0 = [&](int lane, int f) -> const uint8_t* { return f == batch - 1 ? PYR(lane, f) : IMG(lbase, lane, f); };
-  auto DET = [&](int lane, int f) { return g->d_corners + ((size_t)lane * batch + f) * 2 * mc; };
-  for (int li = 0; li < S; ++li) {
-    Lane* l = g->lanes[li];
-    l->frame = 0; l->state = L_IDLE; l->queued = false; l->pending_from = -1;
-    memset(&RES(li, 0), 0, sizeof(svo_frame_result) * batch);
-  }
-
-  // per-pass submission lists
-  std::vector<int> q_track, q_pnp, q_tri, q_ba;
+  svo_pipeline_group* const g;
+  svo_ctx* const ctx;
+  const uint8_t* const* const lbase;
+  const uint8_t* const* const rbase;
+  const int batch;
+  svo_frame_result* const results;
+  const int W, H, S;
+  const size_t istride;
+  uint8_t* pyr = nullptr;  // this batch's pyramids
+  int* hc = nullptr;       // pinned: corner counts of every (lane, frame) + the status word
+  std::vector<int> q_track, q_pnp, q_tri, q_ba;  // per-pass submission lists
   int error = SVO_OK;
   const int MODEL = svo_pnp_model_points();
-  // SVO_GROUP_TRACE=1: (microseconds, lane, event) of this call on stderr — where a lane's time goes
-  static const bool trace_on = getenv("SVO_GROUP_TRACE") != nullptr;
-  // the keyframe chain without a host turn between PnP and stereo + triangulation (round 5); SVO_GROUP_CHAIN_FUSED=0: one launch,
-  // one host turn each, as before — same results either way (tests/test_group.py)
-  static const bool chain_fused = [] { const char* e = getenv("SVO_GROUP_CHAIN_FUSED"); return !(e && *e && atoi(e) == 0); }();
-  struct Ev { double us; int lane; const char* what; int arg; };
+  const bool trace_on = trace_enabled(), chain_fused = chain_fused_enabled();
   std::vector<Ev> evs;
-  const auto t_begin = std::chrono::steady_clock::now();
-  auto EV = [&](int lane, const char* what, int arg) {
-    if (trace_on) evs.push_back({std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_begin).count(), lane, what, arg});
-  };
+  Clock::time_point t_begin, t_pass, last_progress;
+  // ---- the pass in hand
+  bool all_done = false, progressed = false;
+  bool lk_busy[MAX_LINES] = {}, chain_busy[MAX_LINES] = {}, ba_line_busy[MAX_LINES] = {};  // a launch of the line is in flight
+  double t_now_us = 0.0;
+  unsigned idle_spins = 0;
+  double busy_us = 0.0;  // wall time of the loop passes that did something: how much of the call the driving thread was occupied
 
-  auto now_us = [&] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_begin).count(); };
+  Batch(svo_pipeline_group* g_, const uint8_t* const* lb, const uint8_t* const* rb, int batch_, svo_frame_result* res)
+      : g(g_), ctx(g_->ctx), lbase(lb), rbase(rb), batch(batch_), results(res), W(g_->prm.width), H(g_->prm.height), S(g_->n_lanes),
+        istride((size_t)g_->prm.width * g_->prm.height) {}
+
+  svo_frame_result& RES(int lane, int f) const { return results[(size_t)lane * batch + f]; }
+  const uint8_t* IMG(const uint8_t* const* base, int lane, int f) const { return base[lane] + (size_t)f * istride; }
+  uint8_t* PYR(int lane, int f) const { return pyr + ((size_t)lane * batch + f) * g->pyr_stride; }
+  // level 0 of frame f's pyramid: the caller's image, except the batch's last frame (copied into the pyramid by front_end)
+  const uint8_t* L0(int lane, int f) const { return f == batch - 1 ? PYR(lane, f) : IMG(lbase, lane, f); }
+  float* DET(int lane, int f) const { return g->d_corners + ((size_t)lane * batch + f) * 2 * g->prm.max_corners; }
+  double now_us() const { return std::chrono::duration<double, std::micro>(Clock::now() - t_begin).count(); }
+  void EV(int lane, const char* what, int arg) { if (trace_on) evs.push_back({now_us(), lane, what, arg}); }
+  void enqueue(std::vector<int>& q, int li, int state) {  // the lane waits for the next launch of a stage
+    Lane* l = g->lanes[li];
+    q.push_back(li); l->queued = true; l->t_q = now_us(); l->state = state;
+  }
+  void count(Stat s, int lanes) { g->launches[s]++; g->lanes_carried[s] += lanes; progressed = true; }
+
+  // ================================================================ the per-lane state machine
   // frame finished (is_keyframe etc. already in the result): move on
-  auto frame_done = [&](int li) {
+  void frame_done(int li) {
     Lane* l = g->lanes[li];
     svo_frame_result* res = &RES(li, 0);
     const int i = l->frame;
     if (l->has_keyframe && !(res[i].is_keyframe) && l->pending_from < 0) l->pending_from = i;  // no solve started here: the pose is the last solved one (src/vo_node.cpp:146-150)
     l->frame = i + 1;
     l->state = l->frame < batch ? L_IDLE : L_DONE;
-  };
+  }
 
   // src/image_processor.cpp:137-162 once the triangulated new features are on the host: keyframe, solve, tracker
-  auto keyframe_tail = [&](int li) -> int {
+  int keyframe_tail(int li) {
     Lane* l = g->lanes[li];
     svo_frame_result* res = &RES(li, 0);
     const int i = l->frame;
@@ -727,9 +626,9 @@ int group_process(svo_pipeline_group* g, const uint8_t* const* lbase, const uint
     l->new_ids.assign((size_t)(m_new > 0 ? m_new : 1), 0);
     int kept = 0;
     std::vector<int64_t> tid(l->kf_tracked_ids.begin(), l->kf_tracked_ids.end());
-    const auto ta0 = std::chrono::steady_clock::now();
+    const auto ta0 = Clock::now();
     int rc2 = svo_ba_add_keyframe(l->ba, pose7, tid.data(), l->kf_tracked_xy.data(), nt, l->h_tri_xy, l->h_tri_xyz, m_new, l->new_ids.data(), &kept);  // :144
-    if (g->timing) { g->t_add_keyframe += std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - ta0).count(); g->n_kf++; }
+    if (g->timing) { g->t_add_keyframe += std::chrono::duration<double, std::nano>(Clock::now() - ta0).count(); g->n_kf++; }
     if (rc2) return rc2;
     // the previous solve was joined before the graph was edited: its poses are final now
     fill_pending(l, res, i);
@@ -752,11 +651,10 @@ int group_process(svo_pipeline_group* g, const uint8_t* const* lbase, const uint
     res[i].n_new = kept;
     frame_done(li);
     return SVO_OK;
-  };
+  }
 
-  // after PnP (:84-134): keyframe pose, inlier copy; then dedup + sparse stereo + triangulation go out
   // PnP's verdict and pose out of the pinned mirrors: 0 = go on, -1 = error (set) or "launch again with all hypotheses" (queued)
-  auto consume_pnp = [&](int li) -> int {
+  int consume_pnp(int li) {
     Lane* l = g->lanes[li];
     if (*l->h_bad) {
       ctx->err = "pipeline group: a tracked feature's entry of the landmark store belongs to another id (store capacity exceeded?)";
@@ -766,8 +664,7 @@ int group_process(svo_pipeline_group* g, const uint8_t* const* lbase, const uint
     l->best = *l->h_best;  // the launch's own RANSAC bookkeeping (csrc/pnp.hip pnp_group_kernel); -1: no model
     if (l->best == -2) {     // the adaptive cap stayed above the hypotheses of the first launch: all of them now
       l->pnp_all = true;
-      l->state = L_PNP_WAIT;
-      q_pnp.push_back(li); l->queued = true; l->t_q = now_us();
+      enqueue(q_pnp, li, L_PNP_WAIT);
       return -1;
     }
     if (l->best >= 0) {
@@ -777,13 +674,15 @@ int group_process(svo_pipeline_group* g, const uint8_t* const* lbase, const uint
       l->num_inliers = *l->h_nin;
     }
     return 0;
-  };
-  auto after_pnp = [&](int li, bool queue_tri = true) {
+  }
+
+  // after PnP (:84-134): keyframe pose, inlier copy; then dedup + sparse stereo + triangulation go out
+  void after_pnp(int li, bool queue_tri = true) {
     Lane* l = g->lanes[li];
     svo_frame_result* res = &RES(li, 0);
     res[l->frame].n_inliers = l->num_inliers;
-    rodrigues_f(l->rvec, l->rmat);   // :84-85
-    quat_from_R(l->rmat, l->quat);   // :87-92
+    svo_det_rodrigues_f(l->rvec, l->rmat);  // :84-85 cv::Rodrigues on a CV_32F rvec with declared arithmetic: the same bits on the host, on the device and in the oracle
+    svo_det_quat_from_R(l->rmat, l->quat);  // :87-92
     const float* txy = l->h_xy[l->cur];
     const long long* tids = l->h_ids[l->cur];
     l->kf_tracked_ids.resize(l->num_inliers); l->kf_tracked_xy.resize(2 * (size_t)l->num_inliers);
@@ -793,24 +692,24 @@ int group_process(svo_pipeline_group* g, const uint8_t* const* lbase, const uint
       l->kf_tracked_xy[2 * k] = txy[2 * idx]; l->kf_tracked_xy[2 * k + 1] = txy[2 * idx + 1];
     }
     l->first_keyframe = false;
-    if (queue_tri) { q_tri.push_back(li); l->queued = true; l->t_q = now_us(); l->state = L_TRI_WAIT; }
-  };
+    if (queue_tri) enqueue(q_tri, li, L_TRI_WAIT);
+  }
 
   // the keyframe path once the previous solve is joined (:71-82)
-  auto continue_keyframe = [&](int li) -> int {
+  int continue_keyframe(int li) {
     Lane* l = g->lanes[li];
     const int m = l->n;
     l->m_tracked = m;
     l->num_inliers = 0; l->best = -1;
     // :72 get_world_points: nothing to do on the host — the PnP launch reads the tracked features' world points from the lane's
     // device-resident landmark store, which the (joined) solve of the previous keyframe has written
-    if (m >= MODEL) { q_pnp.push_back(li); l->queued = true; l->t_q = now_us(); l->state = L_PNP_WAIT; }
+    if (m >= MODEL) enqueue(q_pnp, li, L_PNP_WAIT);
     else after_pnp(li);
     return SVO_OK;
-  };
+  }
 
   // the keyframe gate after tracking (:63-65)
-  auto after_track = [&](int li) -> int {
+  int after_track(int li) {
     Lane* l = g->lanes[li];
     svo_frame_result& r = RES(li, l->frame);
     const float av = *l->h_av;
@@ -819,9 +718,9 @@ int group_process(svo_pipeline_group* g, const uint8_t* const* lbase, const uint
     if (av <= g->prm.parallax_thresh && (double)pl < svo_ref::KEYFRAME_PERCENT_LOST) { frame_done(li); return SVO_OK; }
     if (l->ba_state.load(std::memory_order_acquire) != BA_NONE) { l->state = L_NEED_SOLVE; EV(li, "need_solve", l->ba_state.load()); return SVO_OK; }
     return continue_keyframe(li);
-  };
+  }
 
-  auto start_frame = [&](int li) -> int {
+  int start_frame(int li) {
     Lane* l = g->lanes[li];
     const int i = l->frame;
     svo_frame_result& r = RES(li, i);
@@ -831,149 +730,180 @@ int group_process(svo_pipeline_group* g, const uint8_t* const* lbase, const uint
     if (!l->has_keyframe) {  // :30-58
       l->first_keyframe = true;
       l->num_inliers = 0;
-      q_tri.push_back(li); l->queued = true; l->t_q = now_us();
-      l->state = L_TRI_WAIT;
+      enqueue(q_tri, li, L_TRI_WAIT);
       return SVO_OK;
     }
     if (l->n <= 0) {  // nothing to track: the kernels would see n = 0 (host/pipeline.cpp: av_parallax = 0)
       l->n = 0; *l->h_av = 0.f;
       return after_track(li);
     }
-    q_track.push_back(li); l->queued = true; l->t_q = now_us();
-    l->state = L_TRACK_WAIT;
+    enqueue(q_track, li, L_TRACK_WAIT);
     return SVO_OK;
-  };
+  }
 
-  unsigned idle_spins = 0;
-  auto last_progress = std::chrono::steady_clock::now();
-  double busy_us = 0.0;  // wall time of the loop passes that did something: how much of the call the driving thread was occupied
-  for (;;) {
-    bool all_done = true, progressed = false;
-    const auto t_pass = std::chrono::steady_clock::now();
-    // ---- advance every lane as far as the host alone can
-    for (int li = 0; li < S && !error; ++li) {
-      Lane* l = g->lanes[li];
-      bool again = true;
-      while (again && !error) {
-        again = false;
-        switch (l->state) {
-          case L_IDLE:
-            error = start_frame(li);
-            progressed = true;
-            again = l->state == L_IDLE;  // the frame ended on the host (too few corners / no keyframe gate): next frame
-            break;
-          case L_TRACK_WAIT:
-            if (!l->queued && word_ready(l, W_TRACK)) {
-              EV(li, "track_done", l->frame);
-              l->cur ^= 1; l->from_host = false;
-              l->n = *l->h_n;
-              l->last_pyr = PYR(li, l->frame);  // :66
-              l->last_l0 = L0(li, l->frame);
-              error = after_track(li);
-              progressed = true; again = l->state == L_IDLE;
-            }
-            break;
-          case L_NEED_SOLVE: {
-            const int bs = l->ba_state.load(std::memory_order_acquire);
-            if ((bs == BA_INFLIGHT && svo_ba_solve_poll(l->ba)) || bs == BA_HOST_DONE) {
-              EV(li, "solve_joined_for_pnp", l->frame);
-              error = finish_solve(g, l);
-              if (!error) error = continue_keyframe(li);
-              progressed = true; again = l->state == L_IDLE;
-            }
-            break;
+  // one lane as far as the host alone can take it
+  void advance_lane(int li) {
+    Lane* l = g->lanes[li];
+    for (bool again = true; again && !error;) {
+      again = false;
+      switch (l->state) {
+        case L_IDLE:
+          error = start_frame(li);
+          progressed = true;
+          again = l->state == L_IDLE;  // the frame ended on the host (too few corners / no keyframe gate): next frame
+          break;
+        case L_TRACK_WAIT:
+          if (l->queued || !word_ready(l, W_TRACK)) break;
+          EV(li, "track_done", l->frame);
+          l->cur ^= 1; l->from_host = false;
+          l->n = *l->h_n;
+          l->last_pyr = PYR(li, l->frame);  // :66
+          l->last_l0 = L0(li, l->frame);
+          error = after_track(li);
+          progressed = true; again = l->state == L_IDLE;
+          break;
+        case L_NEED_SOLVE:
+          if (!solve_came_back(l)) break;
+          EV(li, "solve_joined_for_pnp", l->frame);
+          error = finish_solve(g, l);
+          if (!error) error = continue_keyframe(li);
+          progressed = true; again = l->state == L_IDLE;
+          break;
+        case L_PNP_WAIT:
+          if (l->queued || !word_ready(l, W_PNP)) break;
+          EV(li, "pnp_done", l->frame);
+          progressed = true;
+          if (consume_pnp(li) < 0) break;  // error, or all hypotheses are needed: queued again
+          after_pnp(li, true);
+          break;
+        case L_TRI_WAIT:
+          if (l->queued || !word_ready(l, W_TRI)) break;
+          EV(li, "tri_done", l->frame);
+          progressed = true;
+          if (l->fused) {  // the launch rode behind the lane's PnP launch: PnP's results first (they are complete: same stream, earlier)
+            l->fused = false;
+            if (consume_pnp(li) < 0) break;  // (all hypotheses needed: the triangulation did nothing; both go out again)
+            after_pnp(li, false);
           }
-          case L_PNP_WAIT:
-            if (!l->queued && word_ready(l, W_PNP)) {
-              EV(li, "pnp_done", l->frame);
-              progressed = true;
-              const int verdict = consume_pnp(li);
-              if (verdict < 0) break;        // error, or all hypotheses are needed: queued again
-              after_pnp(li, true);
-            }
-            break;
-          case L_TRI_WAIT:
-            if (!l->queued && word_ready(l, W_TRI)) {
-              EV(li, "tri_done", l->frame);
-              progressed = true;
-              if (l->fused) {  // the launch rode behind the lane's PnP launch: PnP's results first (they are complete: same stream, earlier)
-                l->fused = false;
-                const int verdict = consume_pnp(li);
-                if (verdict < 0) break;      // (all hypotheses needed: the triangulation did nothing; both go out again)
-                after_pnp(li, false);
-              }
-              error = keyframe_tail(li);
-              again = l->state == L_IDLE;
-            }
-            break;
-          default: break;
-        }
+          error = keyframe_tail(li);
+          again = l->state == L_IDLE;
+          break;
+        default: break;
       }
-      if (l->state != L_DONE) all_done = false;
     }
-    if (error) break;
+  }
 
-    // ---- one launch per stage for the lanes that have reached it.  Launch discipline: a stage's kernels go to an in-order
-    // stream, so a launch for ONE lane right now would make the lane that is ready ten microseconds later queue behind it
-    // for a whole kernel duration (tracking: 150-200 us) — measured: 8 lanes, 110 track launches for 120 lane-frames, 3,000
-    // frames/s.  Instead a stage is launched only while none of its launches is in flight; lanes that become ready meanwhile
-    // ride the next launch together (a bus, not taxis).  Nobody waits for a lane that is not ready.
-    // EXPRESS lines (experiment, SVO_GROUP_EXPRESS=1; off by default): a call ends when its slowest lane ends, and lanes differ
-    // (a stream whose windows take 11 LM iterations per solve next to streams that take 4: the other lanes of the group idle for
-    // a fifth of the call).  A lane that has fallen behind the group departs at once on an express line of its stage (one more
-    // stream each for tracking and the keyframe chain) instead of waiting for the bus.  Lanes are independent and every stage
-    // starts only after the host has seen the previous one complete, so which stream carries a launch changes no result.
-    // Measured: no gain (17.1 k against 18.3 k frames/s) — what holds a late lane back is the start of its SOLVES, see below.
-    constexpr int XL = svo_pipeline_group::MAX_LINES;
-    bool lk_busy[XL + 1] = {}, chain_busy[XL + 1] = {};
-    double mean_frame = 0.0;
-    int n_running = 0;
+  // ================================================================ the stages of the driver
+  // a1 on every frame of every lane + the pyramids (the reference detects on every frame, src/image_processor.cpp:22), the
+  // corner counts on the host, and the capacity check
+  int front_end() {
+    const int mc = g->prm.max_corners;
+    hipStream_t st = ctx->stream;
+    bool tight = true;  // the lanes' images are one contiguous run: the batch-wide launches take all of them at once
+    for (int l = 1; l < S; ++l) tight = tight && lbase[l] == lbase[0] + (size_t)l * batch * istride;
+    const uint8_t* const left = lbase[0];
+    const size_t lane_stride = istride * (size_t)batch;  // (of the contiguous case)
+    for (int i = 0; i < ST_COUNT; ++i) { g->launches[i] = 0; g->lanes_carried[i] = 0; }
+    g->pyr_cur ^= 1;  // the previous batch's pyramids stay valid: a lane's last tracked image lives there (src/feature_tracker.cpp:66)
+    pyr = g->d_pyr[g->pyr_cur];
+    int rc = SVO_OK;
+    // ... but a lane that neither tracked nor made a keyframe during the WHOLE previous batch (every frame below MIN_DETECTED
+    // corners, C-7; with batch = 1 one blank frame is enough) still holds its last image in the buffer that is rebuilt now:
+    // the reference keeps a clone of it (src/feature_tracker.cpp:14,66), so the lane takes a private copy first (same stream
+    // as the rebuild: ordered in front of it).
+    const uint8_t* lo = pyr;
+    const uint8_t* hi = pyr + g->pyr_stride * (size_t)g->n_lanes * (size_t)g->max_batch;
+    for (Lane* l : g->lanes) {
+      if (!l->last_pyr || l->last_pyr < lo || l->last_pyr >= hi) continue;
+      SVO_HIP_CHECK(ctx, hipMemcpyAsync(l->d_own_pyr, l->last_pyr, g->pyr_stride, hipMemcpyDeviceToDevice, ctx->stream));
+      l->last_pyr = l->d_own_pyr;  // level 0 was cloned into the pyramid at the end of the batch that produced it
+      l->last_l0 = l->d_own_pyr;
+    }
+    if (tight) {
+      rc = svo_corner_detect_batch_dev(ctx, left, S * batch, W, H, W, istride, mc, g->prm.quality, (double)g->prm.min_feature_distance, g->d_corners, g->d_ncorners);
+      // level 0 of the pyramids is NOT copied: the tracker reads the caller's images in place (Pyr::l0) — except every lane's
+      // last frame, which the next batch tracks from when the caller's buffer may hold other frames
+      if (!rc) rc = svo_k_build_pyramid(ctx, left, S * batch, W, H, W, istride, pyr, g->pyr_stride, true);
+      if (!rc) rc = svo_k_pyramid_level0(ctx, left + (size_t)(batch - 1) * istride, S, W, H, W, lane_stride, pyr + (size_t)(batch - 1) * g->pyr_stride,
+                                         (size_t)batch * g->pyr_stride, st);
+    } else {
+      for (int l = 0; l < S && !rc; ++l) {
+        rc = svo_corner_detect_batch_dev(ctx, lbase[l], batch, W, H, W, istride, mc, g->prm.quality, (double)g->prm.min_feature_distance,
+                                         g->d_corners + (size_t)l * batch * 2 * mc, g->d_ncorners + (size_t)l * batch);
+        if (!rc) rc = svo_k_build_pyramid(ctx, lbase[l], batch, W, H, W, istride, pyr + (size_t)l * batch * g->pyr_stride, g->pyr_stride, true);
+        if (!rc) rc = svo_k_pyramid_level0(ctx, lbase[l] + (size_t)(batch - 1) * istride, 1, W, H, W, istride,
+                                           pyr + ((size_t)l * batch + (size_t)(batch - 1)) * g->pyr_stride, g->pyr_stride, st);
+      }
+    }
+    if (rc) return rc;
+    g->launches[ST_FRONT_END] += 7; g->lanes_carried[ST_FRONT_END] += 7 * S;
+    hc = g->h_counts;
+    SVO_HIP_CHECK(ctx, hipMemcpyAsync(hc, g->d_ncorners, sizeof(int) * S * batch, hipMemcpyDeviceToHost, st));
+    SVO_HIP_CHECK(ctx, hipMemcpyAsync(hc + S * batch, ctx->d_status, sizeof(int), hipMemcpyDeviceToHost, st));
+    SVO_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    if (hc[S * batch]) {
+      (void)hipMemsetAsync(ctx->d_status, 0, sizeof(int), st);
+      ctx->err = (hc[S * batch] & 8) ? "corner detection: more raw local maxima than the streaming pass's list holds (raw_cap: width x height / 4 per image under a 1 GiB budget)"
+                           : "corner detection exceeded a workspace bound (svo_limits.max_candidates)";
+      return SVO_ERR_CAPACITY;
+    }
+    return SVO_OK;
+  }
+
+  // advance every lane as far as the host alone can
+  void advance_lanes() {
+    all_done = true;
+    for (int li = 0; li < S && !error; ++li) {
+      advance_lane(li);
+      if (g->lanes[li]->state != L_DONE) all_done = false;
+    }
+  }
+
+  // Launch discipline of the two stage families below: a stage's kernels go to an in-order stream, so a launch for ONE lane
+  // right now would make the lane that is ready ten microseconds later queue behind it for a whole kernel duration (tracking:
+  // 150-200 us) — measured: 8 lanes, 110 track launches for 120 lane-frames, 3,000 frames/s.  Instead a line launches only
+  // while none of its launches is in flight; lanes that become ready meanwhile ride the next launch together (a bus, not
+  // taxis).  Nobody waits for a lane that is not ready.  Which lanes ride which line and when a launch is ripe: host/group_lines.h.
+  void scan_lines() {
+    for (int i = 0; i < MAX_LINES; ++i) lk_busy[i] = chain_busy[i] = false;
     for (int li = 0; li < S; ++li) {
       const Lane* l = g->lanes[li];
-      if (l->state != L_DONE) { mean_frame += l->frame; ++n_running; }
       if (l->queued) continue;
       lk_busy[l->lk_line] |= l->state == L_TRACK_WAIT;
       chain_busy[l->chain_line] |= l->state == L_PNP_WAIT || l->state == L_TRI_WAIT;
     }
-    mean_frame = n_running ? mean_frame / n_running : 0.0;
-    auto laggard = [&](int li) { return g->express && n_running > 2 && (double)g->lanes[li]->frame + 1.0 < mean_frame; };
-    // the lanes of `q` that ride line `line` (of `n_lines`; XL: the express line takes the laggards), removed from q
-    auto take_line = [&](std::vector<int>& q, int line, int n_lines) {
-      std::vector<int> mine;
-      for (size_t k = 0; k < q.size();) {
-        if (line == XL ? laggard(q[k]) : q[k] % n_lines == line) { mine.push_back(q[k]); q.erase(q.begin() + k); } else ++k;
-      }
-      return mine;
-    };
-    const double t_now_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_begin).count();
-    // GATHER (SVO_GROUP_GATHER_US > 0): a launch lasts as long as its slowest item whatever it carries, so a bus that leaves with
-    // four of the line's lanes while others are a hundred microseconds away costs a whole launch more.  A stage's launch therefore
-    // waits while a lane of its line is NEAR (in the launch in flight of the stage before it), at most gather_us per waiting lane.
-    auto ripe = [&](const std::vector<int>& q, int line, int n_lines, int near_state) {
-      if (g->gather_us <= 0.0 || line == XL) return true;
-      int mine = 0, near = 0;
-      bool waited = false;
-      for (int li : q) if (n_lines <= 1 || li % n_lines == line) { ++mine; waited = waited || t_now_us - g->lanes[li]->t_q >= g->gather_us; }
-      if (!mine || waited) return true;
-      for (int li = 0; li < S; ++li) if ((n_lines <= 1 || li % n_lines == line) && g->lanes[li]->state == near_state && !g->lanes[li]->queued) ++near;
-      return near == 0;
-    };
-    bool tails_only = true;  // every tracking launch in flight is old enough to be in its tail (a few straggling wavefronts)
-    for (int line = 0; line < g->n_lk; ++line) tails_only = tails_only && (!lk_busy[line] || t_now_us - g->lk_t0[line] >= g->lk_overlap_us);
-    for (int pass = g->express ? -1 : 0; pass < g->n_lk && !error; ++pass) {
-      const int line = pass < 0 ? XL : pass;  // the express line first: what it takes no longer waits for a regular line
-      if (lk_busy[line]) continue;
-      std::vector<int> q_now;
-      if (g->lk_overlap_us > 0 && line != XL) {  // dynamic lines: the whole queue departs on a free line, but only next to tails
-        if (!tails_only) break;
-        if (!ripe(q_track, 0, 1, L_TRI_WAIT)) break;
-        q_now.swap(q_track);
-      } else {
-        if (!ripe(q_track, line, g->n_lk, L_TRI_WAIT)) continue;
-        q_now = take_line(q_track, line, g->n_lk);
-      }
+    t_now_us = now_us();
+  }
+  // the gather rule (SVO_GROUP_GATHER_US) for line `line` of a stage whose lanes come out of the launches of `near_state`
+  bool ripe(const std::vector<int>& q, int line, int n_lines, int near_state) const {
+    return svo_line_ripe(q, S, line, n_lines, t_now_us, g->gather_us, [&](int li) { return g->lanes[li]->t_q; },
+                         [&](int li) { return g->lanes[li]->state == near_state && !g->lanes[li]->queued; });
+  }
+
+  void fill_lk_lane(Lane* l, int li, SvoLkLane& x, int workgroups) {
+    const int nxt = l->cur ^ 1;
+    x.pyr_prev = l->last_pyr; x.pyr_next = PYR(li, l->frame);
+    x.l0_prev = l->last_l0; x.l0_next = L0(li, l->frame);
+    x.xy = l->from_host ? l->h_kf_xy : l->d_xy[l->cur];
+    x.init_xy = l->from_host ? l->h_kf_xy : l->d_init[l->cur];
+    x.ids = l->from_host ? l->h_kf_ids : l->d_ids[l->cur];
+    x.n = l->n;
+    x.fwd = l->d_fwd; x.keep = l->d_keep; x.parallax = l->d_par;
+    x.kept_xy = l->d_xy[nxt]; x.init_dst = l->d_init[nxt]; x.ids_dst = l->d_ids[nxt];
+    x.host_xy = l->h_xy[nxt]; x.host_ids = l->h_ids[nxt]; x.host_n = l->h_n; x.host_av = l->h_av;
+    l->arrive_total[C_LK] += (unsigned)workgroups;
+    x.arrive = l->d_arrive + 16 * C_LK; x.arrive_target = l->arrive_total[C_LK];
+    x.word = &l->words[16 * W_TRACK]; x.seq = ++l->seq[W_TRACK];
+    l->queued = false;
+  }
+
+  // WHERE A TRACKING LAUNCH IS DECIDED: a free line takes the queued lanes it carries, once the gather rule lets it
+  void launch_tracking() {
+    scan_lines();
+    for (int line = 0; line < g->n_lk && !error; ++line) {
+      if (lk_busy[line] || !ripe(q_track, line, g->n_lk, L_TRI_WAIT)) continue;
+      const std::vector<int> q_now = svo_line_take(q_track, line, g->n_lk);
       if (q_now.empty()) continue;
-      if (line != XL) g->lk_t0[line] = t_now_us;
       for (int li : q_now) g->lanes[li]->lk_line = line;
       SvoLkLanes a;
       a.w = W; a.h = H;
@@ -988,317 +918,288 @@ int group_process(svo_pipeline_group* g, const uint8_t* const* lbase, const uint
       int k = 0;
       for (int li : q_now) {
         Lane* l = g->lanes[li];
-        SvoLkLane& x = a.lane[k++];
-        const int nxt = l->cur ^ 1;
-        x.pyr_prev = l->last_pyr; x.pyr_next = PYR(li, l->frame);
-        x.l0_prev = l->last_l0; x.l0_next = L0(li, l->frame);
-        x.xy = l->from_host ? l->h_kf_xy : l->d_xy[l->cur];
-        x.init_xy = l->from_host ? l->h_kf_xy : l->d_init[l->cur];
-        x.ids = l->from_host ? l->h_kf_ids : l->d_ids[l->cur];
-        x.n = l->n;
-        x.fwd = l->d_fwd; x.keep = l->d_keep; x.parallax = l->d_par;
-        x.kept_xy = l->d_xy[nxt]; x.init_dst = l->d_init[nxt]; x.ids_dst = l->d_ids[nxt];
-        x.host_xy = l->h_xy[nxt]; x.host_ids = l->h_ids[nxt]; x.host_n = l->h_n; x.host_av = l->h_av;
-        l->arrive_total[C_LK] += (unsigned)(a.map.per_chunk > 0 ? std::max(1, l->n) : gx);
-        x.arrive = l->d_arrive + 16 * C_LK; x.arrive_target = l->arrive_total[C_LK];
-        x.word = &l->words[16 * W_TRACK]; x.seq = ++l->seq[W_TRACK];
-        l->queued = false;
+        fill_lk_lane(l, li, a.lane[k++], a.map.per_chunk > 0 ? std::max(1, l->n) : gx);
       }
-      if ((error = svo_kg_track(ctx, g->st_lk[line], a, k, gx))) break;
+      if ((error = svo_kg_track(ctx, g->st_lk[line], a, k, gx))) return;
       for (int li : q_now) EV(li, "track_launch", k);
-      g->launches[0]++; g->lanes_carried[0] += k;
-      progressed = true;
+      count(ST_TRACK, k);
     }
-    if (error) break;
-    for (int pass = g->express ? -1 : 0; pass < g->n_chain && !error; ++pass) {
-      const int line = pass < 0 ? XL : pass;
+  }
+
+  void fill_pnp_lane(Lane* l, int li, SvoPnpLane& x) {
+    (void)li;
+    const int m = l->m_tracked;
+    x.ids = l->d_ids[l->cur]; x.store = l->d_store; x.store_mask = l->store_mask;
+    x.xy = l->d_xy[l->cur]; x.n = m;
+    x.f = (double)g->K[0]; x.cx = (double)g->K[2]; x.cy = (double)g->K[5];
+    // rvec/tvec are CV_32F in/out, the solver works in double (host/pipeline.cpp; csrc/pnp.hip svo_k_pnp)
+    const double rv[3] = {l->rvec[0], l->rvec[1], l->rvec[2]};
+    svo_det_quat_from_rvec(rv, x.q0);  // declared arithmetic (host/det_trig.h)
+    for (int c = 0; c < 3; ++c) x.t0[c] = (double)l->tvec[c];
+    x.thr2 = (double)svo_ref::PNP_REPROJ_ERROR * (double)svo_ref::PNP_REPROJ_ERROR;
+    x.confidence = svo_ref::PNP_CONFIDENCE; x.iterations = g->pnp_iterations;
+    x.launched = l->pnp_all ? g->pnp_iterations : svo_kg_pnp_first(g->pnp_iterations);
+    l->pnp_all = false;
+    const int wgs = svo_kg_pnp_workgroups(x.launched);
+    x.hyp_pose = l->d_hyp_pose; x.hyp_count = l->d_hyp_count; x.hyp_mask = l->d_hyp_mask; x.mask_words = svo_div_up(m, 64);
+    x.out_pose = l->d_out; x.inliers = l->d_inl; x.n_inliers = l->d_nin; x.inlier_xy = l->d_trk_xy;
+    x.host_pose = l->h_out; x.host_inliers = l->h_inl; x.host_nin = l->h_nin; x.host_best = l->h_best; x.host_bad = l->h_bad;
+    const SvoPublish pb = make_pub(l, W_PNP, C_PNP, wgs);
+    x.arrive = pb.arrive; x.arrive_target = pb.target; x.word = pb.word; x.seq = pb.seq;
+    // fused chain: the launch leaves M / the inlier count / "more hypotheses first" for the stereo launch right behind it
+    x.chain = chain_fused ? l->d_chain : nullptr;
+    for (int c = 0; c < 3; ++c) { x.prev_rvec[c] = l->rvec[c]; x.prev_tvec[c] = l->tvec[c]; }
+    x.cam_f = g->K[0]; x.cam_cx = g->K[2]; x.cam_cy = g->K[5]; x.cam_b = (float)g->prm.cam.baseline;
+    l->queued = false;
+  }
+
+  // the PnP launch of a chain line; with the fused chain its lanes join t_now: their stereo launch rides right behind
+  void launch_pnp(int line, const std::vector<int>& h_now, std::vector<int>& t_now) {
+    SvoPnpLanes a;
+    int k = 0;
+    for (int li : h_now) fill_pnp_lane(g->lanes[li], li, a.lane[k++]);
+    if ((error = svo_kg_pnp(ctx, g->st_chain[line], a, k))) return;
+    for (int li : h_now) EV(li, "pnp_launch", k);
+    count(ST_PNP, k);
+    if (chain_fused) for (int li : h_now) { g->lanes[li]->fused = true; t_now.push_back(li); }
+  }
+
+  void fill_tri_lane(Lane* l, int li, SvoStereoTriLane& x, int workgroups) {
+    const int i = l->frame, n_det = hc[li * batch + i];
+    x.xy = DET(li, i); x.n_dev = nullptr;
+    x.trk = nullptr; x.n_trk = 0; x.min_d = 0.f;
+    x.chain = nullptr;
+    if (l->fused) {  // behind the lane's PnP launch: M and the inlier count are read from its record on the device
+      x.chain = l->d_chain; x.trk = l->d_trk_xy; x.min_d = g->prm.min_feature_distance;
+    } else if (!l->first_keyframe) {
+      // dedup (:113-128) inside the same launch: every corner's workgroup tests it against the tracked inliers first
+      x.trk = l->d_trk_xy; x.n_trk = l->num_inliers; x.min_d = g->prm.min_feature_distance;
+      if (x.n_trk <= 0) x.trk = nullptr;  // no inliers (C-9): nothing to keep away from
+    }
+    x.left = IMG(lbase, li, i); x.right = IMG(rbase, li, i);
+    x.n_max = n_det; x.disp = l->d_disp;
+    // :130-134, :178-189: M = float(hmat * Q), hmat = [R^T | -R^T t] of the keyframe's pose (host/chain_math.h) — of the identity
+    // for frame 0 and for a fused lane, which reads M from the device record instead
+    const float I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, zero3[3] = {0, 0, 0};
+    const bool posed = !l->fused && !l->first_keyframe;
+    svo_chain_matrix_from_R(posed ? l->rmat : I9, posed ? l->tvec : zero3, g->K[0], g->K[2], g->K[5], (float)g->prm.cam.baseline, x.M.m);
+    x.kept_xy = l->h_tri_xy; x.xyz = l->h_tri_xyz; x.n_kept = l->h_tri_cnt;
+    x.pub = make_pub(l, W_TRI, C_TRI, workgroups);
+    l->state = L_TRI_WAIT;
+    l->queued = false;
+  }
+
+  // dedup (:113-128) for the lanes that tracked, then sparse StereoBM + triangulation (:137-142, :34-39 for frame 0)
+  void launch_tri(int line, const std::vector<int>& t_now) {
+    SvoStereoTriLanes t;
+    t.w = W; t.h = H; t.stride = W; t.ndisp = svo_ref::STEREO_NUM_DISPARITIES; t.block = svo_ref::STEREO_BLOCK_SIZE;
+    int kt = 0, gxt = 1;
+    t.map.per_chunk = 0; t.map.total = 0; t.map.chunks = 0;
+    int counts[SVO_MAX_LANES], j = 0;
+    for (int li : t_now) {
+      const int n_det = hc[li * batch + g->lanes[li]->frame];
+      gxt = std::max(gxt, n_det);
+      counts[j++] = n_det;
+    }
+    if (g->xcd_map_tri) svo_xcd_map_fill(t.map, counts, j, g->xcd_chunks);
+    for (int li : t_now) {
+      Lane* l = g->lanes[li];
+      fill_tri_lane(l, li, t.lane[kt++], t.map.per_chunk > 0 ? std::max(1, hc[li * batch + l->frame]) : gxt);
+    }
+    if ((error = svo_kg_stereo_triangulate(ctx, g->st_chain[line], t, kt, gxt))) return;
+    for (int li : t_now) EV(li, "tri_launch", kt);
+    count(ST_TRI, kt);
+  }
+
+  // the keyframe chains: per free chain line one PnP launch (under the gather rule) and one stereo + triangulation launch
+  void launch_chains() {
+    for (int line = 0; line < g->n_chain && !error; ++line) {
       if (chain_busy[line]) continue;
-      hipStream_t stc = g->st_chain[line];
-      const std::vector<int> h_now = ripe(q_pnp, line, g->n_chain, L_TRACK_WAIT) ? take_line(q_pnp, line, g->n_chain) : std::vector<int>();
-      std::vector<int> t_now = take_line(q_tri, line, g->n_chain);
+      const std::vector<int> h_now = ripe(q_pnp, line, g->n_chain, L_TRACK_WAIT) ? svo_line_take(q_pnp, line, g->n_chain) : std::vector<int>();
+      std::vector<int> t_now = svo_line_take(q_tri, line, g->n_chain);
       for (int li : h_now) g->lanes[li]->chain_line = line;
       for (int li : t_now) g->lanes[li]->chain_line = line;
-    if (!h_now.empty()) {
-      SvoPnpLanes a;
-      int k = 0;
-      for (int li : h_now) {
-        Lane* l = g->lanes[li];
-        const int m = l->m_tracked;
-        SvoPnpLane& x = a.lane[k++];
-        x.ids = l->d_ids[l->cur]; x.store = l->d_store; x.store_mask = l->store_mask;
-        x.xy = l->d_xy[l->cur]; x.n = m;
-        x.f = (double)g->K[0]; x.cx = (double)g->K[2]; x.cy = (double)g->K[5];
-        // rvec/tvec are CV_32F in/out, the solver works in double (host/pipeline.cpp; csrc/pnp.hip svo_k_pnp)
-        const double rv[3] = {l->rvec[0], l->rvec[1], l->rvec[2]};
-        svo_det_quat_from_rvec(rv, x.q0);  // declared arithmetic (host/det_trig.h)
-        for (int c = 0; c < 3; ++c) x.t0[c] = (double)l->tvec[c];
-        x.thr2 = (double)svo_ref::PNP_REPROJ_ERROR * (double)svo_ref::PNP_REPROJ_ERROR;
-        x.confidence = svo_ref::PNP_CONFIDENCE; x.iterations = g->pnp_iterations;
-        x.launched = l->pnp_all ? g->pnp_iterations : svo_kg_pnp_first(g->pnp_iterations);
-        l->pnp_all = false;
-        const int wgs = svo_kg_pnp_workgroups(x.launched);
-        x.hyp_pose = l->d_hyp_pose; x.hyp_count = l->d_hyp_count; x.hyp_mask = l->d_hyp_mask; x.mask_words = svo_div_up(m, 64);
-        x.out_pose = l->d_out; x.inliers = l->d_inl; x.n_inliers = l->d_nin; x.inlier_xy = l->d_trk_xy;
-        x.host_pose = l->h_out; x.host_inliers = l->h_inl; x.host_nin = l->h_nin; x.host_best = l->h_best; x.host_bad = l->h_bad;
-        const SvoPublish pb = make_pub(l, W_PNP, C_PNP, wgs);
-        x.arrive = pb.arrive; x.arrive_target = pb.target; x.word = pb.word; x.seq = pb.seq;
-        // fused chain: the launch leaves M / the inlier count / "more hypotheses first" for the stereo launch right behind it
-        x.chain = chain_fused ? l->d_chain : nullptr;
-        for (int c = 0; c < 3; ++c) { x.prev_rvec[c] = l->rvec[c]; x.prev_tvec[c] = l->tvec[c]; }
-        x.cam_f = g->K[0]; x.cam_cx = g->K[2]; x.cam_cy = g->K[5]; x.cam_b = (float)g->prm.cam.baseline;
-        l->queued = false;
-      }
-      if ((error = svo_kg_pnp(ctx, stc, a, k))) break;
-      for (int li : h_now) EV(li, "pnp_launch", k);
-      g->launches[1]++; g->lanes_carried[1] += k;
-      progressed = true;
-      if (chain_fused) for (int li : h_now) { g->lanes[li]->fused = true; t_now.push_back(li); }
+      if (!h_now.empty()) launch_pnp(line, h_now, t_now);
+      if (!error && !t_now.empty()) launch_tri(line, t_now);
     }
-    if (!t_now.empty()) {
-      // dedup (:113-128) for the lanes that tracked, then sparse StereoBM + triangulation (:137-142, :34-39 for frame 0)
-      SvoStereoTriLanes t;
-      t.w = W; t.h = H; t.stride = W; t.ndisp = svo_ref::STEREO_NUM_DISPARITIES; t.block = svo_ref::STEREO_BLOCK_SIZE;
-      int kt = 0, gxt = 1;
-      t.map.per_chunk = 0; t.map.total = 0; t.map.chunks = 0;
-      {
-        int counts[SVO_MAX_LANES], j = 0;
-        for (int li : t_now) {
-          Lane* l = g->lanes[li];
-          const int n_det = hc[li * batch + l->frame];
-          gxt = std::max(gxt, n_det);
-          counts[j++] = n_det;
-        }
-        if (g->xcd_map_tri) svo_xcd_map_fill(t.map, counts, j, g->xcd_chunks);
-      }
-      for (int li : t_now) {
-        Lane* l = g->lanes[li];
-        const int i = l->frame, n_det = hc[li * batch + i];
-        float pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-        SvoStereoTriLane& x = t.lane[kt++];
-        x.xy = DET(li, i); x.n_dev = nullptr;
-        x.trk = nullptr; x.n_trk = 0; x.min_d = 0.f;
-        x.chain = nullptr;
-        if (l->fused) {  // behind the lane's PnP launch: M and the inlier count are read from its record on the device
-          x.chain = l->d_chain; x.trk = l->d_trk_xy; x.min_d = g->prm.min_feature_distance;
-        } else if (!l->first_keyframe) {
-          // dedup (:113-128) inside the same launch: every corner's workgroup tests it against the tracked inliers first
-          x.trk = l->d_trk_xy; x.n_trk = l->num_inliers; x.min_d = g->prm.min_feature_distance;
-          if (x.n_trk <= 0) x.trk = nullptr;  // no inliers (C-9): nothing to keep away from
-          // hmat = [R^T | -R^T t]  :130-134 (float Mats; the product accumulates in double)
-          memset(pose, 0, sizeof(pose));
-          for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) pose[4 * r + c] = l->rmat[3 * c + r];
-            double s = 0.0;
-            for (int c = 0; c < 3; ++c) s += (double)(-l->rmat[3 * c + r]) * (double)l->tvec[c];
-            pose[4 * r + 3] = (float)s;
-          }
-          pose[15] = 1.f;
-        }
-        x.left = IMG(lbase, li, i); x.right = IMG(rbase, li, i);
-        x.n_max = n_det; x.disp = l->d_disp;
-        x.M = svo_k_reprojection_matrix(pose, g->K[0], g->K[2], g->K[5], (float)g->prm.cam.baseline);  // :178-189
-        x.kept_xy = l->h_tri_xy; x.xyz = l->h_tri_xyz; x.n_kept = l->h_tri_cnt;
-        x.pub = make_pub(l, W_TRI, C_TRI, t.map.per_chunk > 0 ? std::max(1, n_det) : gxt);
-        l->state = L_TRI_WAIT;
-        l->queued = false;
-      }
-      if ((error = svo_kg_stereo_triangulate(ctx, stc, t, kt, gxt))) break;
-      for (int li : t_now) EV(li, "tri_launch", kt);
-      g->launches[3]++; g->lanes_carried[3] += kt;
-      progressed = true;
-    }
-    }
-    if (error) break;
-    // ---- solves.  A finished solve is joined right away (its admission is handed back: lanes that are already through
-    // their frames would otherwise keep the budget while others wait for it); the results are the same whenever they are read.
+  }
+
+  static bool solve_came_back(Lane* l) {
+    const int bs = l->ba_state.load(std::memory_order_acquire);
+    return (bs == BA_INFLIGHT && svo_ba_solve_poll(l->ba)) || bs == BA_HOST_DONE;
+  }
+  bool any_solve_in_flight(bool holding_budget) const {
+    bool any = false;
+    for (const Lane* l : g->lanes)
+      any |= l->ba_state.load(std::memory_order_acquire) == BA_INFLIGHT && (!holding_budget || svo_ba_solve_holds_budget(l->ba));
+    return any;
+  }
+
+  // A finished solve is joined right away (its admission is handed back: lanes that are already through their frames would
+  // otherwise keep the budget while others wait for it); the results are the same whenever they are read.
+  void join_finished_solves() {
     for (int li = 0; li < S && !error; ++li) {
       Lane* l = g->lanes[li];
-      const int bs = l->ba_state.load(std::memory_order_acquire);
-      if (l->state != L_NEED_SOLVE && ((bs == BA_INFLIGHT && svo_ba_solve_poll(l->ba)) || bs == BA_HOST_DONE)) { EV(li, "solve_joined", l->frame); error = finish_solve(g, l); progressed = true; }
-    }
-    if (error) break;
-    // everything that has been assembled goes out as one launch once no lane is still assembling
-    {
-      int assembling = 0;
-      q_ba.clear();
-      for (int li = 0; li < S; ++li) {
-        const int bs = g->lanes[li]->ba_state.load(std::memory_order_acquire);
-        assembling += bs == BA_ASSEMBLING;
-        if (bs == BA_READY) {
-          q_ba.push_back(li);
-          if (!g->lanes[li]->ba_ready_seq) g->lanes[li]->ba_ready_seq = ++g->ba_ready_counter;
-        }
-      }
-      // who is offered to the admission first (it may run out of budget behind any of them): a lane whose next keyframe already
-      // waits for this solve, then the solve that has waited longest — in lane order the high lanes of a large group starved
-      // and became the stragglers of the call (profiles/r04_group_sweep.txt: 56 and 64 lanes)
-      std::sort(q_ba.begin(), q_ba.end(), [&](int a, int b) {
-        const Lane* la = g->lanes[a]; const Lane* lb = g->lanes[b];
-        const bool wa = la->state == L_NEED_SOLVE, wb = lb->state == L_NEED_SOLVE;
-        if (wa != wb) return wa;
-        return la->ba_ready_seq < lb->ba_ready_seq;
-      });
-      bool ba_line_busy[svo_pipeline_group::MAX_LINES] = {};
-      for (int li = 0; li < S; ++li) {
-        const Lane* l = g->lanes[li];
-        if (l->ba_state.load(std::memory_order_acquire) == BA_INFLIGHT && !svo_ba_solve_poll(l->ba)) ba_line_busy[l->ba_line] = true;
-      }
-      int free_line = -1;
-      for (int i = 0; i < g->n_ba; ++i) if (!ba_line_busy[i]) { free_line = i; break; }
-      // (rounds 3-4 held ready solves back while ANY lane was still assembling, to launch them together: measured in round 4,
-      // a solve then left 1.1 ms after its assembly was posted on average — as long as it runs — and 3 ms at the 90th
-      // percentile; SVO_GROUP_BA_WAIT_ASSEMBLY=1 restores that)
-      static const bool wait_assembly = [] { const char* e = getenv("SVO_GROUP_BA_WAIT_ASSEMBLY"); return e && *e && atoi(e) != 0; }();
-      if (!q_ba.empty() && (assembling == 0 || !wait_assembly) && free_line >= 0) {
-        svo_ba* bas[SVO_MAX_LANES];
-        std::vector<int> cand;
-        for (int li : q_ba) {
-          Lane* l = g->lanes[li];
-          if (l->ba_rc == 1) { l->ba_ready_seq = 0; l->ba_state.store(BA_NONE, std::memory_order_release); continue; }  // nothing to solve
-          if (l->ba_rc) { error = l->ba_rc; break; }
-          bas[cand.size()] = l->ba;
-          cand.push_back(li);
-        }
-        if (error) break;
-        if (!cand.empty()) {
-          unsigned long long mask = 0;
-          static const bool host_solves = [] { const char* e = getenv("SVO_GROUP_HOST_SOLVES"); return e && *e && atoi(e) != 0; }();  // test hook: every window down the host-driven path (the landmark store is then filled by the scatter launch)
-          const int launched = host_solves ? 0 : svo_ba_solve_launch(bas, (int)cand.size(), g->st_ba[free_line], &mask);
-          if (launched > 0) { g->launches[4]++; g->lanes_carried[4] += launched; progressed = true; }
-          ++g->ba_launch_id;
-          int not_taken = -1;  // the first lane the launch skipped: not eligible, or not admitted right now
-          for (int k = 0; k < (int)cand.size(); ++k) {
-            if (!((mask >> k) & 1ull)) { if (not_taken < 0) not_taken = cand[k]; continue; }
-            Lane* l = g->lanes[cand[k]];
-            EV(cand[k], "ba_launch", launched);
-            l->ba_launch = g->ba_launch_id; l->ba_line = free_line; l->ba_ready_seq = 0; l->ba_state.store(BA_INFLIGHT, std::memory_order_release);
-          }
-          // A refused solve waits for the group's next wide launch while a wide solve of this group is in flight: joining it hands
-          // budget back, the solve is offered again in the next pass (at a larger k if need be, ba_device_lm_launch) and rides a launch
-          // that costs the same queue time with or without it — one workgroup for 6 ms holds a hardware queue that the tracking line
-          // shares (4 queues: 12.25 against 12.05 k frames/s at 96 lanes, profiles/r08_runs.txt).
-          bool wide_inflight = false;
-          for (int li = 0; li < S; ++li)
-            wide_inflight |= g->lanes[li]->ba_state.load(std::memory_order_acquire) == BA_INFLIGHT && svo_ba_solve_holds_budget(g->lanes[li]->ba);
-          if (not_taken >= 0 && g->n_cmp > 0 && !host_solves && !wide_inflight) {
-            // compact lines (SVO_GROUP_COMPACT_LINES, round 5): what the admission budget refused while nothing of this group holds any
-            // of it leaves at once in the one-workgroup form — no budget, 3-4x the latency — on a line of its own, so that the wide
-            // launches' lines stay free
-            int cline = -1;
-            for (int i = g->n_ba; i < g->n_ba + g->n_cmp; ++i) if (!ba_line_busy[i]) { cline = i; break; }
-            if (cline >= 0) {
-              svo_ba* cb[SVO_MAX_LANES];
-              int cl[SVO_MAX_LANES], nc = 0;
-              for (int k = 0; k < (int)cand.size(); ++k) if (!((mask >> k) & 1ull)) { cb[nc] = bas[k]; cl[nc++] = cand[k]; (void)svo_ba_set_solve_form(bas[k], 1); }
-              unsigned long long cmask = 0;
-              const int went = svo_ba_solve_launch(cb, nc, g->st_ba[cline], &cmask);
-              for (int k = 0; k < nc; ++k) (void)svo_ba_set_solve_form(cb[k], -1);
-              if (went > 0) {
-                ++g->ba_launch_id;
-                g->launches[4]++; g->lanes_carried[4] += went; progressed = true;
-                for (int k = 0; k < nc; ++k) {
-                  if (!((cmask >> k) & 1ull)) continue;
-                  Lane* l = g->lanes[cl[k]];
-                  EV(cl[k], "ba_launch_compact", went);
-                  l->ba_launch = g->ba_launch_id; l->ba_line = cline; l->ba_ready_seq = 0; l->ba_state.store(BA_INFLIGHT, std::memory_order_release);
-                }
-                not_taken = -1;
-                for (int k = 0; k < nc; ++k) if (!((cmask >> k) & 1ull)) { not_taken = cl[k]; break; }
-              }
-            }
-          }
-          if (not_taken >= 0) {
-            // if nothing of this group is in flight that could free the admission budget (or the problem is simply not
-            // eligible for the device-resident solve), the lane is solved by the host-driven loop on a worker; otherwise it
-            // is offered again when a solve of this group has been joined
-            bool inflight = false;
-            for (int li = 0; li < S; ++li) inflight |= g->lanes[li]->ba_state.load(std::memory_order_acquire) == BA_INFLIGHT;
-            if (!inflight) {
-              Lane* l = g->lanes[not_taken];
-              l->ba_ready_seq = 0;
-              // SVO_GROUP_STALLED_COMPACT=1 (experiment, round 5): the compact device-resident form instead of the host-driven loop on a
-              // worker.  Measured slower — 29 k against 41 k frames/s at 128 lanes (profiles/r05_exp_lanes_groups.txt): a compact solve
-              // holds its solve line for ~3 ms, the worker's host-driven solve holds none.
-              static const bool stalled_compact = [] { const char* e = getenv("SVO_GROUP_STALLED_COMPACT"); return e && *e && atoi(e) != 0; }();
-              bool went = false;
-              if (stalled_compact && !host_solves) {
-                svo_ba* one = l->ba;
-                (void)svo_ba_set_solve_form(one, 1);
-                went = svo_ba_solve_launch(&one, 1, g->st_ba[free_line], nullptr) == 1;
-                (void)svo_ba_set_solve_form(one, -1);
-                if (went) {
-                  EV(not_taken, "ba_launch_compact", 1);
-                  l->ba_launch = ++g->ba_launch_id; l->ba_line = free_line; l->ba_state.store(BA_INFLIGHT, std::memory_order_release);
-                  g->launches[4]++; g->lanes_carried[4]++;
-                }
-              }
-              if (!went) {
-                l->ba_state.store(BA_HOST_SOLVING, std::memory_order_release);
-                g->pool.post(l, 1);
-              }
-              progressed = true;
-            }
-          }
-        }
-      }
-    }
-    if (all_done) break;
-    if (!progressed) {
-      __builtin_ia32_pause();
-      if (++idle_spins > 2000u && (idle_spins & 255u) == 0) sched_yield();
-      if ((idle_spins & 0xFFFFu) == 0) {  // never hang: a launch that does not come back within seconds is reported with the lanes' states
-        const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - last_progress).count();
-        if (waited > 5.0) {
-          std::string msg = "pipeline group: no progress for 5 s; lanes (state/frame/solve):";
-          for (int li = 0; li < S; ++li) {
-            char b[64];
-            snprintf(b, sizeof(b), " %d/%d/%d%s", g->lanes[li]->state, g->lanes[li]->frame, g->lanes[li]->ba_state.load(), g->lanes[li]->queued ? "q" : "");
-            msg += b;
-          }
-          ctx->err = msg;
-          error = SVO_ERR_HIP;
-          break;
-        }
-      }
-    } else {
-      idle_spins = 0;
-      last_progress = std::chrono::steady_clock::now();
-      busy_us += std::chrono::duration<double, std::micro>(last_progress - t_pass).count();
+      if (l->state == L_NEED_SOLVE || !solve_came_back(l)) continue;  // (a lane in L_NEED_SOLVE joins its own: advance_lane)
+      EV(li, "solve_joined", l->frame);
+      error = finish_solve(g, l);
+      progressed = true;
     }
   }
-  g->launches[2] += (long)busy_us;
-  g->lanes_carried[2] += (long)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_begin).count();
 
-  // ---- end of the batch: join every solve, fill the poses that waited for it
-  for (int li = 0; li < S; ++li) {
+  // THE ONE PLACE WHERE A SOLVE BECOMES IN FLIGHT: a solve launch has left on solve line `line`; it carries the `carried`
+  // lanes of lanes[0..n) whose bit is set in `taken`
+  void solves_departed(const int* lanes, int n, unsigned long long taken, int line, int carried, const char* what) {
+    ++g->ba_launch_id;
+    if (carried > 0) count(ST_SOLVE, carried);
+    for (int k = 0; k < n; ++k) {
+      if (!((taken >> k) & 1ull)) continue;
+      Lane* l = g->lanes[lanes[k]];
+      EV(lanes[k], what, carried);
+      l->ba_launch = g->ba_launch_id; l->ba_line = line; l->ba_ready_seq = 0;
+      l->ba_state.store(BA_INFLIGHT, std::memory_order_release);
+    }
+  }
+  static int first_not_taken(const int* lanes, int n, unsigned long long taken) {
+    for (int k = 0; k < n; ++k) if (!((taken >> k) & 1ull)) return lanes[k];
+    return -1;
+  }
+
+  // the assembled solves in the order of their admission (host/group_lines.h), and which solve lines are busy
+  void collect_ready_solves() {
+    q_ba.clear();
+    for (int li = 0; li < S; ++li) {
+      Lane* l = g->lanes[li];
+      if (l->ba_state.load(std::memory_order_acquire) != BA_READY) continue;
+      q_ba.push_back(li);
+      if (!l->ba_ready_seq) l->ba_ready_seq = ++g->ba_ready_counter;
+    }
+    std::sort(q_ba.begin(), q_ba.end(), [&](int a, int b) {
+      const Lane* la = g->lanes[a]; const Lane* lb = g->lanes[b];
+      return svo_solve_before(la->state == L_NEED_SOLVE, la->ba_ready_seq, lb->state == L_NEED_SOLVE, lb->ba_ready_seq);
+    });
+    for (int i = 0; i < MAX_LINES; ++i) ba_line_busy[i] = false;
+    for (const Lane* l : g->lanes)
+      if (l->ba_state.load(std::memory_order_acquire) == BA_INFLIGHT && !svo_ba_solve_poll(l->ba)) ba_line_busy[l->ba_line] = true;
+  }
+  int free_solve_line(int from, int to) const {
+    for (int i = from; i < to; ++i) if (!ba_line_busy[i]) return i;
+    return -1;
+  }
+
+  // compact lines (SVO_GROUP_COMPACT_LINES, round 5): what the admission budget refused while nothing of this group holds any
+  // of it leaves at once in the one-workgroup form — no budget, 3-4x the latency — on a line of its own, so that the wide
+  // launches' lines stay free.  Returns the first lane that is still not taken (-1: none).
+  int launch_refused_compact(const int* cand, svo_ba* const* bas, int n, unsigned long long mask, int not_taken) {
+    const int cline = free_solve_line(g->n_ba, g->n_ba + g->n_cmp);
+    if (cline < 0) return not_taken;
+    svo_ba* cb[SVO_MAX_LANES];
+    int cl[SVO_MAX_LANES], nc = 0;
+    for (int k = 0; k < n; ++k) if (!((mask >> k) & 1ull)) { cb[nc] = bas[k]; cl[nc++] = cand[k]; (void)svo_ba_set_solve_form(bas[k], 1); }
+    unsigned long long cmask = 0;
+    const int went = svo_ba_solve_launch(cb, nc, g->st_ba[cline], &cmask);
+    for (int k = 0; k < nc; ++k) (void)svo_ba_set_solve_form(cb[k], -1);
+    if (went <= 0) return not_taken;
+    solves_departed(cl, nc, cmask, cline, went, "ba_launch_compact");
+    return first_not_taken(cl, nc, cmask);
+  }
+
+  // Everything that has been assembled goes out as ONE wide launch on a free solve line, at once (rounds 3-4 held ready solves
+  // back while any lane was still assembling, to launch them together: measured in round 4, a solve then left 1.1 ms after its
+  // assembly was posted on average — as long as it runs — and 3 ms at the 90th percentile).
+  // WHERE A REFUSED SOLVE GOES: the three cases at the end of this function.
+  void launch_solves() {
+    collect_ready_solves();
+    const int free_line = free_solve_line(0, g->n_ba);
+    if (q_ba.empty() || free_line < 0) return;
+    svo_ba* bas[SVO_MAX_LANES];
+    int cand[SVO_MAX_LANES], n = 0;
+    for (int li : q_ba) {
+      Lane* l = g->lanes[li];
+      if (l->ba_rc == 1) { l->ba_ready_seq = 0; l->ba_state.store(BA_NONE, std::memory_order_release); continue; }  // nothing to solve
+      if (l->ba_rc) { error = l->ba_rc; return; }
+      bas[n] = l->ba;
+      cand[n++] = li;
+    }
+    if (!n) return;
+    unsigned long long mask = 0;
+    const bool host_solves = host_solves_only();
+    const int launched = host_solves ? 0 : svo_ba_solve_launch(bas, n, g->st_ba[free_line], &mask);
+    solves_departed(cand, n, mask, free_line, launched, "ba_launch");
+    int not_taken = first_not_taken(cand, n, mask);  // the first lane the launch skipped: not eligible, or not admitted right now
+    if (not_taken < 0) return;
+    // 1. A refused solve waits for the group's next wide launch while a wide solve of this group is in flight: joining it hands
+    // budget back, the solve is offered again in the next pass (at a larger k if need be, ba_device_lm_launch) and rides a launch
+    // that costs the same queue time with or without it — one workgroup for 6 ms holds a hardware queue that the tracking line
+    // shares (4 queues: 12.25 against 12.05 k frames/s at 96 lanes, profiles/r08_runs.txt).
+    // 2. Nothing of the group holds budget and it has compact lines: the refused solves leave in the compact form.
+    if (g->n_cmp > 0 && !host_solves && !any_solve_in_flight(true)) not_taken = launch_refused_compact(cand, bas, n, mask, not_taken);
+    // 3. Nothing of this group is in flight that could free the admission budget (or the problem is simply not eligible for
+    // the device-resident solve): the lane is solved by the host-driven loop on a worker (a compact solve here instead was
+    // measured slower, 29 k against 41 k frames/s at 128 lanes, profiles/r05_exp_lanes_groups.txt: it holds its solve line
+    // for ~3 ms, the worker holds none).  Otherwise it is offered again when a solve of this group has been joined.
+    if (not_taken < 0 || any_solve_in_flight(false)) return;
+    Lane* l = g->lanes[not_taken];
+    l->ba_ready_seq = 0;
+    l->ba_state.store(BA_HOST_SOLVING, std::memory_order_release);
+    g->pool.post(l, 1);
+    progressed = true;
+  }
+
+  // a pass that moved nothing: spin politely, and never hang — a launch that does not come back within seconds is reported
+  // with the lanes' states.  False: give up (error is set).
+  bool idle_or_report() {
+    if (progressed) {
+      idle_spins = 0;
+      last_progress = Clock::now();
+      busy_us += std::chrono::duration<double, std::micro>(last_progress - t_pass).count();
+      return true;
+    }
+    __builtin_ia32_pause();
+    if (++idle_spins > 2000u && (idle_spins & 255u) == 0) sched_yield();
+    if ((idle_spins & 0xFFFFu) != 0) return true;
+    if (std::chrono::duration<double>(Clock::now() - last_progress).count() <= 5.0) return true;
+    std::string msg = "pipeline group: no progress for 5 s; lanes (state/frame/solve):";
+    for (const Lane* l : g->lanes) {
+      char b[64];
+      snprintf(b, sizeof(b), " %d/%d/%d%s", l->state, l->frame, l->ba_state.load(), l->queued ? "q" : "");
+      msg += b;
+    }
+    ctx->err = msg;
+    error = SVO_ERR_HIP;
+    return false;
+  }
+
+  // a lane whose assembly is still running at the end of the batch, or whose solve is not launched yet: see it launched
+  void launch_last_solve(int li) {
     Lane* l = g->lanes[li];
-    for (;;) {  // a lane whose assembly is still running, or whose solve is not launched yet
+    for (;;) {
       const int bs = l->ba_state.load(std::memory_order_acquire);
-      if (bs == BA_NONE || bs == BA_INFLIGHT || bs == BA_HOST_DONE) break;
+      if (bs == BA_NONE || bs == BA_INFLIGHT || bs == BA_HOST_DONE) return;
       if (bs == BA_READY) {
-        if (l->ba_rc == 1) { l->ba_state.store(BA_NONE); break; }
-        if (l->ba_rc) { if (!error) error = l->ba_rc; l->ba_state.store(BA_NONE); break; }
+        if (l->ba_rc) {  // 1: nothing to solve
+          if (l->ba_rc != 1 && !error) error = l->ba_rc;
+          l->ba_state.store(BA_NONE);
+          return;
+        }
         svo_ba* one = l->ba;
-        if (svo_ba_solve_launch(&one, 1, g->st_ba[0], nullptr) == 1) { l->ba_launch = ++g->ba_launch_id; l->ba_line = 0; l->ba_state.store(BA_INFLIGHT); g->launches[4]++; g->lanes_carried[4]++; }
+        if (svo_ba_solve_launch(&one, 1, g->st_ba[0], nullptr) == 1) solves_departed(&li, 1, 1ull, 0, 1, "ba_launch_at_end");
         else { l->ba_rc = svo_ba_solve_finish(l->ba, &l->ba_summary); l->ba_state.store(BA_HOST_DONE); }
-        break;
+        return;
       }
       __builtin_ia32_pause();
-      if (std::chrono::duration<double>(std::chrono::steady_clock::now() - last_progress).count() > 60.0) {
+      if (std::chrono::duration<double>(Clock::now() - last_progress).count() > 60.0) {
         if (!error) { error = SVO_ERR_HIP; ctx->err = "pipeline group: a bundle-adjustment worker did not come back"; }
-        break;
+        return;
       }
     }
-    const int rcf = finish_solve(g, l);
-    if (rcf && !error) error = rcf;
-    svo_frame_result* res = &RES(li, 0);
-    if (l->pending_from < 0) l->pending_from = batch;
-    fill_pending(l, res, batch);
   }
+
   // A lane whose last tracked image is NOT the batch's last frame (its later frames had too few corners to track, C-7)
   // still reads that image's level 0 from the caller's buffer: clone it into its pyramid now (src/feature_tracker.cpp:14,66),
   // before the caller may reuse the buffer.
-  {
+  void clone_last_level0() {
+    hipStream_t st = ctx->stream;
     bool copied = false;
     for (int li = 0; li < S && !error; ++li) {
       Lane* l = g->lanes[li];
@@ -1309,15 +1210,56 @@ int group_process(svo_pipeline_group* g, const uint8_t* const* lbase, const uint
     }
     if (copied && hipStreamSynchronize(st) != hipSuccess && !error) { error = SVO_ERR_HIP; ctx->err = "pipeline group: pyramid clone failed"; }
   }
-  if (trace_on) {
-    static std::mutex trace_mu;  // the groups of a process print their calls one after the other
-    std::lock_guard<std::mutex> lk(trace_mu);
-    for (const Ev& e : evs) fprintf(stderr, "[svo group] %10.1f lane %2d %-22s %d\n", e.us, e.lane, e.what, e.arg);
-    fprintf(stderr, "[svo group] %10.1f end\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_begin).count());
+
+  // end of the batch: join every solve, fill the poses that waited for it
+  int end_of_batch() {
+    g->launches[ST_HOST_US] += (long)busy_us;
+    g->lanes_carried[ST_HOST_US] += (long)now_us();
+    for (int li = 0; li < S; ++li) {
+      Lane* l = g->lanes[li];
+      launch_last_solve(li);
+      const int rcf = finish_solve(g, l);
+      if (rcf && !error) error = rcf;
+      if (l->pending_from < 0) l->pending_from = batch;
+      fill_pending(l, &RES(li, 0), batch);
+    }
+    clone_last_level0();
+    if (trace_on) {
+      static std::mutex trace_mu;  // the groups of a process print their calls one after the other
+      std::lock_guard<std::mutex> lk(trace_mu);
+      for (const Ev& e : evs) fprintf(stderr, "[svo group] %10.1f lane %2d %-22s %d\n", e.us, e.lane, e.what, e.arg);
+      fprintf(stderr, "[svo group] %10.1f end\n", now_us());
+    }
+    if (error) { quiesce_after_error(g); return error; }
+    if (!ctx->err.empty()) return SVO_ERR_HIP;
+    return SVO_OK;
   }
-  if (error) { quiesce_after_error(g); return error; }
-  if (!ctx->err.empty()) return SVO_ERR_HIP;
-  return SVO_OK;
+
+  int run() {
+    const int rc = front_end();
+    if (rc) return rc;
+    for (int li = 0; li < S; ++li) {
+      Lane* l = g->lanes[li];
+      l->frame = 0; l->state = L_IDLE; l->queued = false; l->pending_from = -1;
+      memset(&RES(li, 0), 0, sizeof(svo_frame_result) * batch);
+    }
+    t_begin = last_progress = Clock::now();
+    for (;;) {
+      progressed = false;
+      t_pass = Clock::now();
+      advance_lanes();
+      if (!error) launch_tracking();
+      if (!error) launch_chains();
+      if (!error) join_finished_solves();
+      if (!error) launch_solves();
+      if (error || all_done || !idle_or_report()) break;
+    }
+    return end_of_batch();
+  }
+};
+
+int group_process(svo_pipeline_group* g, const uint8_t* const* lbase, const uint8_t* const* rbase, int batch, svo_frame_result* results) {
+  return Batch(g, lbase, rbase, batch, results).run();
 }
 }  // namespace
 

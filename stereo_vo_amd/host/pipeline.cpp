@@ -426,33 +426,6 @@ int FeatureTracker::track_features_host(float& av_parallax, float& percent_lost,
 }
 
 // ------------------------------------------------------------------------------------------ ImageProcessor
-namespace {
-// cv::Rodrigues on a CV_32F rvec with declared arithmetic (host/det_trig.h): the same bits on the host, on the device and in the oracle
-inline void rodrigues_f(const float* rv, float* R9) { svo_det_rodrigues_f(rv, R9); }
-
-// Eigen::Quaternionf(Matrix3f) (src/image_processor.cpp:92), float arithmetic, row-major m.
-void quat_from_R(const float* m, float* q /*wxyz*/) {
-  float t = m[0] + m[4] + m[8];
-  if (t > 0.f) {
-    t = sqrtf(t + 1.0f);
-    q[0] = 0.5f * t;
-    t = 0.5f / t;
-    q[1] = (m[7] - m[5]) * t; q[2] = (m[2] - m[6]) * t; q[3] = (m[3] - m[1]) * t;
-  } else {
-    int i = 0;
-    if (m[4] > m[0]) i = 1;
-    if (m[8] > m[4 * i]) i = 2;
-    const int j = (i + 1) % 3, k = (j + 1) % 3;
-    t = sqrtf(m[4 * i] - m[4 * j] - m[4 * k] + 1.0f);
-    q[1 + i] = 0.5f * t;
-    t = 0.5f / t;
-    q[0] = (m[3 * k + j] - m[3 * j + k]) * t;
-    q[1 + j] = (m[3 * j + i] + m[3 * i + j]) * t;
-    q[1 + k] = (m[3 * k + i] + m[3 * i + k]) * t;
-  }
-}
-}  // namespace
-
 ImageProcessor::ImageProcessor(svo_ctx* ctx, const float K[9], std::shared_ptr<FeatureTracker> tracker,
                                std::shared_ptr<BundleAdjuster> adjuster, float bline, float min_dist, float par_thresh,
                                int max_corners, double quality, int max_batch)
@@ -695,8 +668,8 @@ void ImageProcessor::process(const StereoPair& sp) {  // src/image_processor.cpp
   stats_.n_inliers = num_inliers;
 
   float rmat[9], q[4];
-  rodrigues_f(rvec, rmat);   // :84-85
-  quat_from_R(rmat, q);      // :87-92
+  svo_det_rodrigues_f(rvec, rmat);  // :84-85 cv::Rodrigues on a CV_32F rvec with declared arithmetic: the same bits on the host, on the device and in the oracle
+  svo_det_quat_from_R(rmat, q);     // :87-92
   auto kf = std::make_shared<Keyframe>(Vector3f{{tvec[0], tvec[1], tvec[2]}}, Quaternionf{q[0], q[1], q[2], q[3]}, sp.left,
                                        std::vector<Point2f>(num_inliers), std::vector<size_t>(num_inliers),
                                        std::vector<Point2f>(), std::vector<Point3f>());

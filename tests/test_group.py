@@ -458,11 +458,13 @@ def test_hip_group_solves_that_give_up_are_rerun_and_lose_no_frame():
 @pytest.mark.parametrize("env", [{"SVO_GROUP_CHAIN_FUSED": "0"}, {"SVO_GROUP_GATHER_US": "200"},
                                  {"SVO_GROUP_COMPACT_LINES": "1", "SVO_BA_BUDGET_PERCENT": "25"},
                                  {"SVO_GROUP_COMPACT_LINES": "2", "SVO_GROUP_BA_LINES": "1", "SVO_BA_BUDGET_PERCENT": "12"},
+                                 {"SVO_GROUP_LK_LINES": "2"}, {"SVO_GROUP_TRACE": "1"},
                                  ])
 def test_hip_group_optional_paths_keep_parity(env):
     """Round 5's scheduling knobs of a pipeline group must not change a bit: the keyframe chain with a host turn between the PnP and the
     stereo launch again (default: the stereo launch rides right behind PnP and reads the reprojection matrix from the device record,
-    host/chain_math.h), the gather policy, compact lines (the admission budget cut so far that most solves take them).  Read once per process: one child each; 6 lanes x 16 frames against the oracle."""
+    host/chain_math.h), the gather policy, compact lines (the admission budget cut so far that most solves take them), two tracking lines
+    (lanes alternate between two streams), the event trace.  Read once per process: one child each; 6 lanes x 16 frames against the oracle."""
     import os
     import subprocess
     import sys

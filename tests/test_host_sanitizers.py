@@ -76,3 +76,17 @@ def test_xcd_aware_block_map_serves_every_slot_exactly_once(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "xcd map ok" in r.stdout
+
+
+def test_group_line_policy_partitions_gathers_and_orders_solves(tmp_path):
+    """The line policy of a pipeline group (host/group_lines.h: which queued lanes ride which line, the gather rule, the order in
+    which assembled solves are offered to the admission), the functions host/group.cpp calls, walked on the CPU under ASan + UBSan:
+    the lines partition the queue in queue order, gather off is always ripe, gather on holds a line back in exactly one case, the
+    solve order is a strict weak ordering that never puts a waiting lane behind a non-waiting one."""
+    exe = str(tmp_path / "group_lines_test")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-I", os.path.join(ROOT, "stereo_vo_amd", "host"), os.path.join(ROOT, "tests", "sanitize", "group_lines_test.cpp"), "-o", exe]
+    subprocess.run(cmd, check=True, timeout=300)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "group lines ok" in r.stdout
