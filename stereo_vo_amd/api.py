@@ -411,6 +411,20 @@ class Context:
                   "svo_corner_detect")
         return xy[:n.value].copy()
 
+    def corner_detect_batch_dev(self, imgs, batch, width, height, row_stride, image_stride, max_corners, quality, min_distance, xy, n):
+        """svo_corner_detect_batch_dev on torch device tensors: imgs uint8 (batch images, row_stride bytes per row, image_stride bytes
+        per image), xy float32 (batch, max_corners, 2), n int32 (batch).  Asynchronous on the context's stream (sync() before reading)."""
+        for t, dt in ((imgs, "torch.uint8"), (xy, "torch.float32"), (n, "torch.int32")):
+            if not t.is_cuda or not t.is_contiguous() or str(t.dtype) != dt:
+                raise SvoError(f"corner_detect_batch_dev: expected a contiguous {dt} device tensor")
+        if imgs.numel() < (batch - 1) * image_stride + (height - 1) * row_stride + width or image_stride < row_stride * height:
+            raise SvoError("corner_detect_batch_dev: image buffer smaller than the strides say")
+        if xy.numel() < batch * max_corners * 2 or n.numel() < batch:
+            raise SvoError("corner_detect_batch_dev: output tensors too small")
+        self._chk(self.L.svo_corner_detect_batch_dev(self.h, C.c_void_p(imgs.data_ptr()), batch, width, height, row_stride,
+                                                     C.c_size_t(image_stride), max_corners, C.c_double(quality), C.c_double(min_distance),
+                                                     C.c_void_p(xy.data_ptr()), C.c_void_p(n.data_ptr())), "svo_corner_detect_batch_dev")
+
     # ---- rectification
     def rectify_remap(self, raw, eye, cam):
         """svo_rectify_remap: raw (H, W) uint8 host image (any row stride) -> rectified (H, W)."""
