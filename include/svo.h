@@ -95,7 +95,7 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * "lk_fb", "stereo_at", "triangulate", "pnp_hypotheses", "pnp_refine", "ba_linearize", "ba_backsub", "ba_step",
  * "rectify_remap", "stereo_bm" (the three launches of svo_stereo_bm as one bracket), "stereo_dense_batch",
  * "cloud" (the count, scan and write launches of one svo_disparity_cloud_batch_dev as one bracket),
- * "speckle" (the launches of one speckle filter call as one bracket);
+ * "speckle" (the launches of one speckle filter call as one bracket), "lr_check" (one left-right check call);
  * NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
@@ -259,6 +259,39 @@ int svo_disparity_speckle_filter_batch_dev(svo_ctx* ctx, int16_t* disp16, int ba
 /* One map, HOST pointers, in place, synchronous; n_removed: host int or NULL. */
 int svo_disparity_speckle_filter(svo_ctx* ctx, int16_t* disp16, int width, int height, const svo_speckle_params* params,
                                  int* n_removed);
+
+/* -------------------------------------------------------- left-right check --
+ * What disp12MaxDiff of StereoBM switches on (cv::validateDisparity, which StereoBM::compute runs BEFORE filterSpeckles), on the
+ * device, for a batch of CV_16S maps (4 fractional bits, FILTERED = -16) and the winner's SAD per pixel (no reference counterpart:
+ * the reference leaves disp12MaxDiff off because it samples the map at the features only; a whole-map cloud shows the band of
+ * wrong disparities along every depth edge).  Rows are independent; all arithmetic is int32, >> is the arithmetic shift, any
+ * int16 values are accepted.  Per row: every x with d = disp16[y][x] != FILTERED votes for the right-view column
+ * x2 = x - ((d + 8) >> 4) (a vote outside [0, width) is dropped); a column's winner is the vote with the smallest
+ * (cost16[y][x], x) and d2[x2] is the winner's d; a column without a vote is empty.  Then, for every x with d != FILTERED, with
+ * xa = x - (d >> 4) and xb = x - ((d + 15) >> 4): a look-up at xq is bad iff 0 <= xq < width, d2[xq] is not empty and
+ * |d2[xq] - d| > max_diff16; the pixel becomes FILTERED iff BOTH look-ups are bad.  Nothing else changes.  d2 is formed from the
+ * input row, so the result depends on no order.  The check is not idempotent in general (a removed pixel no longer votes).
+ * max_diff16 is in the map's own unit of 1/16 pixel: disp12MaxDiff = k pixels is max_diff16 = 16 k. */
+typedef struct svo_lr_check_params {
+  int max_diff16;  /* >= 0, 1/16 pixel */
+} svo_lr_check_params;
+/* The widest map the check takes: the row and one 32-bit key per column live in LDS, 6 bytes per column, within the 64 KB a
+ * kernel gets without asking.  A wider map is refused with SVO_ERR_INVALID and a message naming this bound. */
+#define SVO_LR_CHECK_MAX_WIDTH 10240
+/* svo_stereo_bm_batch_dev that also writes cost16[y][x] = the winner's SAD (the minsad of the selection) where the map is not
+ * FILTERED and 0xFFFF where it is (a SAD is at most 21*21*62 = 27,342).  The map is bit-identical to svo_stereo_bm_batch_dev's.
+ * disp16, cost16: `batch` tight maps each, DEVICE pointers. */
+int svo_stereo_bm_cost_batch_dev(svo_ctx* ctx, const uint8_t* left, const uint8_t* right, int batch, int width, int height,
+                                 int row_stride, size_t image_stride, int num_disparities, int block_size, int16_t* disp16,
+                                 uint16_t* cost16);
+/* `batch` tight maps checked in place, DEVICE pointers, asynchronous on svo_stream(ctx): one launch for the whole batch.
+ * 1 <= batch <= 65535, 1 <= width <= SVO_LR_CHECK_MAX_WIDTH, height >= 1.  n_removed: `batch` device ints, the number of pixels
+ * this call set to FILTERED per map (zeroed on the stream before the launch), or NULL. */
+int svo_disparity_lr_check_batch_dev(svo_ctx* ctx, int16_t* disp16, const uint16_t* cost16, int batch, int width, int height,
+                                     const svo_lr_check_params* params, int* n_removed);
+/* One map, HOST pointers, disp16 in place, synchronous; n_removed: host int or NULL. */
+int svo_disparity_lr_check(svo_ctx* ctx, int16_t* disp16, const uint16_t* cost16, int width, int height,
+                           const svo_lr_check_params* params, int* n_removed);
 
 /* ------------------------------------------------------------------- a8 --
  * ImageProcessor::triangulate_stereo's reprojection loop
@@ -541,6 +574,14 @@ int svo_pipeline_set_keyframe_clouds(svo_pipeline* p, const svo_cloud_params* pa
  * filtered: the sparse StereoBM that feeds landmarks, svo_frame_result and the tracked set do not change.  Never called: no
  * launch, no allocation, nothing changes. */
 int svo_pipeline_set_keyframe_speckle_filter(svo_pipeline* p, const svo_speckle_params* params);
+/* Left-right check of the keyframe maps (above, "left-right check"): with params != NULL every process call launches the cost
+ * form of the dense kernel, then the check, then the speckle filter if that is on, then the clouds, on the same stream (the order
+ * of StereoBM::compute).  The two filters are independent switches.  Keyframe clouds must be on already (SVO_ERR_INVALID
+ * otherwise); the cost maps for max_keyframes_per_call maps (2 bytes per pixel) are allocated once here.  NULL turns the check off
+ * and frees them; so does turning the clouds off.  New cloud parameters keep the check.  Only the dense maps are checked: the
+ * sparse StereoBM that feeds landmarks, svo_frame_result and the tracked set do not change.  Never called: no launch, no
+ * allocation, nothing changes, and the dense launch is the plain kernel. */
+int svo_pipeline_set_keyframe_lr_check(svo_pipeline* p, const svo_lr_check_params* params);
 /* One entry per keyframe of the last process call, in frame order (src/image_processor.cpp:173-207 per entry). */
 typedef struct svo_keyframe_cloud {
   int frame;                  /* index in the call */
@@ -605,6 +646,8 @@ int svo_pipeline_group_set_keyframe_clouds(svo_pipeline_group* g, int lane, cons
 /* svo_pipeline_set_keyframe_speckle_filter for the group: the lanes that have clouds on share one set of buffers and one cloud
  * parameter set, so the filter is group-wide as well.  Clouds must be on for at least one lane. */
 int svo_pipeline_group_set_keyframe_speckle_filter(svo_pipeline_group* g, const svo_speckle_params* params);
+/* svo_pipeline_set_keyframe_lr_check for the group, group-wide like the speckle filter.  Clouds must be on for at least one lane. */
+int svo_pipeline_group_set_keyframe_lr_check(svo_pipeline_group* g, const svo_lr_check_params* params);
 int svo_pipeline_group_keyframe_clouds(svo_pipeline_group* g, int* n, const svo_keyframe_cloud** table);
 int svo_pipeline_group_copy_keyframe_cloud(svo_pipeline_group* g, int i, svo_cloud_point* host, int capacity);
 int svo_pipeline_group_get_tracked(svo_pipeline_group* g, int lane, int64_t* ids, float* xy, int capacity, int* n);

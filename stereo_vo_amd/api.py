@@ -97,6 +97,12 @@ class SpeckleParams(C.Structure):
     _fields_ = [("max_size", C.c_int), ("max_diff16", C.c_int)]
 
 
+class LrCheckParams(C.Structure):
+    """svo_lr_check_params: a pixel goes iff both of its right-view look-ups differ from it by more than max_diff16 (1/16 px)."""
+    _fields_ = [("max_diff16", C.c_int)]
+
+
+LR_CHECK_MAX_WIDTH = 10240  # SVO_LR_CHECK_MAX_WIDTH
 SPECKLE_TILE = (64, 16)  # SVO_SPECKLE_TILE_W, SVO_SPECKLE_TILE_H
 
 
@@ -261,6 +267,8 @@ SYMBOLS = [
     "svo_pipeline_group_set_keyframe_clouds", "svo_pipeline_group_keyframe_clouds", "svo_pipeline_group_copy_keyframe_cloud",
     "svo_speckle_workspace_bytes", "svo_disparity_speckle_filter_batch_dev", "svo_disparity_speckle_filter",
     "svo_pipeline_set_keyframe_speckle_filter", "svo_pipeline_group_set_keyframe_speckle_filter",
+    "svo_stereo_bm_cost_batch_dev", "svo_disparity_lr_check_batch_dev", "svo_disparity_lr_check",
+    "svo_pipeline_set_keyframe_lr_check", "svo_pipeline_group_set_keyframe_lr_check",
 ]
 
 
@@ -304,6 +312,15 @@ def lib():
         L.svo_pipeline_group_set_keyframe_speckle_filter.argtypes = [vp, vp]
         for f in ("svo_disparity_speckle_filter_batch_dev", "svo_disparity_speckle_filter", "svo_pipeline_set_keyframe_speckle_filter",
                   "svo_pipeline_group_set_keyframe_speckle_filter"):
+            getattr(L, f).restype = ci
+        # left-right check
+        L.svo_stereo_bm_cost_batch_dev.argtypes = [vp, vp, vp, ci, ci, ci, ci, sz, ci, ci, vp, vp]
+        L.svo_disparity_lr_check_batch_dev.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]
+        L.svo_disparity_lr_check.argtypes = [vp, vp, vp, ci, ci, vp, vp]
+        L.svo_pipeline_set_keyframe_lr_check.argtypes = [vp, vp]
+        L.svo_pipeline_group_set_keyframe_lr_check.argtypes = [vp, vp]
+        for f in ("svo_stereo_bm_cost_batch_dev", "svo_disparity_lr_check_batch_dev", "svo_disparity_lr_check",
+                  "svo_pipeline_set_keyframe_lr_check", "svo_pipeline_group_set_keyframe_lr_check"):
             getattr(L, f).restype = ci
         _LIB = L
     return _LIB
@@ -527,6 +544,32 @@ class Context:
         self._chk(self.L.svo_disparity_speckle_filter_batch_dev(self.h, disp16_ptr, batch, width, height,
                                                                 C.byref(params) if params is not None else None, workspace_ptr,
                                                                 workspace_bytes, n_removed_ptr), "svo_disparity_speckle_filter_batch_dev")
+
+    # ---- left-right check
+    def stereo_bm_cost_batch(self, left_ptr, right_ptr, batch, width, height, row_stride, image_stride, disp16_ptr, cost16_ptr,
+                             ndisp=48, block=21):
+        """svo_stereo_bm_cost_batch_dev: stereo_bm_batch that also writes the winner's SAD per pixel (cost16_ptr: batch tight (H, W)
+        uint16 maps, 0xFFFF where the map is FILTERED).  Raw device pointers (ints).  Asynchronous."""
+        self._chk(self.L.svo_stereo_bm_cost_batch_dev(self.h, left_ptr, right_ptr, batch, width, height, row_stride, image_stride,
+                                                      ndisp, block, disp16_ptr, cost16_ptr), "svo_stereo_bm_cost_batch_dev")
+
+    def lr_check(self, disp16, cost16, max_diff16):
+        """svo_disparity_lr_check: one host (H, W) int16 map and its (H, W) uint16 costs -> (checked copy, n_removed)."""
+        d = np.array(disp16, np.int16, order="C")
+        c = np.ascontiguousarray(cost16, np.uint16)
+        h, w = d.shape
+        assert c.shape == (h, w)
+        n = C.c_int(0)
+        self._chk(self.L.svo_disparity_lr_check(self.h, _p(d), _p(c), w, h, C.byref(LrCheckParams(int(max_diff16))), C.byref(n)),
+                  "svo_disparity_lr_check")
+        return d, n.value
+
+    def lr_check_dev(self, disp16_ptr, cost16_ptr, batch, width, height, params, n_removed_ptr=None):
+        """svo_disparity_lr_check_batch_dev: raw device pointers (ints); disp16_ptr: batch tight (H, W) int16 maps, checked in place;
+        cost16_ptr: their uint16 costs; params: LrCheckParams; n_removed_ptr: batch int32 or None.  Asynchronous."""
+        self._chk(self.L.svo_disparity_lr_check_batch_dev(self.h, disp16_ptr, cost16_ptr, batch, width, height,
+                                                          C.byref(params) if params is not None else None, n_removed_ptr),
+                  "svo_disparity_lr_check_batch_dev")
 
     # ---- a8
     def triangulate(self, xy, disp, pose16, focal, cx, cy, baseline):
@@ -809,6 +852,13 @@ class Pipeline:
         self.ctx._chk(self.L.svo_pipeline_set_keyframe_speckle_filter(self.h, C.byref(prm) if prm is not None else None),
                       "svo_pipeline_set_keyframe_speckle_filter")
 
+    def set_keyframe_lr_check(self, max_diff16=None):
+        """svo_pipeline_set_keyframe_lr_check: the keyframe maps pass the left-right check before the speckle filter and the clouds
+        (clouds must be on); max_diff16 None: off."""
+        prm = None if max_diff16 is None else LrCheckParams(int(max_diff16))
+        self.ctx._chk(self.L.svo_pipeline_set_keyframe_lr_check(self.h, C.byref(prm) if prm is not None else None),
+                      "svo_pipeline_set_keyframe_lr_check")
+
     def keyframe_clouds(self):
         """The keyframes of the last process call: [{frame, lane, n_total, n_stored, dev, points (CLOUD_POINT_DTYPE array)}], in frame order."""
         return _keyframe_clouds(self.ctx, self.L, self.h, self.L.svo_pipeline_keyframe_clouds, self.L.svo_pipeline_copy_keyframe_cloud)
@@ -889,6 +939,12 @@ class PipelineGroup:
         prm = None if max_size is None else SpeckleParams(int(max_size), int(max_diff16))
         self.ctx._chk(self.L.svo_pipeline_group_set_keyframe_speckle_filter(self.h, C.byref(prm) if prm is not None else None),
                       "svo_pipeline_group_set_keyframe_speckle_filter")
+
+    def set_keyframe_lr_check(self, max_diff16=None):
+        """svo_pipeline_group_set_keyframe_lr_check (group-wide; clouds must be on); max_diff16 None: off."""
+        prm = None if max_diff16 is None else LrCheckParams(int(max_diff16))
+        self.ctx._chk(self.L.svo_pipeline_group_set_keyframe_lr_check(self.h, C.byref(prm) if prm is not None else None),
+                      "svo_pipeline_group_set_keyframe_lr_check")
 
     def keyframe_clouds(self):
         """The keyframes of the last process call over the lanes that have clouds on, ordered by lane, then frame (see Pipeline.keyframe_clouds)."""

@@ -33,8 +33,13 @@ __device__ __forceinline__ const uint8_t* pair_image(const SvoDensePairs& s, int
 }
 }  // namespace
 
+// COST: the cost form (svo_stereo_bm_cost_batch_dev, the keyframe maps when the left-right check is on), which also writes the
+// winner's SAD of the selection loop, cost[y][x] (0xFFFF where the map is FILTERED; minsad <= 21 * 21 * 62 = 27,342 never collides).
+// Without COST nothing of it is compiled and `cost` is never read: the plain instantiation is the kernel as it was before the cost
+// form existed, and it is what every plain path launches.
+template <bool COST>
 __global__ __launch_bounds__(256) void stereo_dense_batch_kernel(SvoDensePairs src, int W, int H, int stride, int ndisp, int block,
-                                                                 int16_t* __restrict__ out) {
+                                                                 int16_t* __restrict__ out, uint16_t* __restrict__ cost) {
   __shared__ uint8_t sL[DT_TH][DT_TWL + 4], sR[DT_TH][DT_TWR + 4];
   __shared__ unsigned short sV[DT_SLOTS][DT_H][DT_TWL + 4];
   extern __shared__ __align__(16) unsigned short sSad[];  // [ndisp + 1][DT_PIX]; before the first SAD is written: the raw tiles
@@ -43,6 +48,7 @@ __global__ __launch_bounds__(256) void stereo_dense_batch_kernel(SvoDensePairs s
   const uint8_t* __restrict__ L = pair_image(src, blockIdx.z, 0);
   const uint8_t* __restrict__ R = pair_image(src, blockIdx.z, 1);
   out += (size_t)blockIdx.z * W * H;
+  if (COST) cost += (size_t)blockIdx.z * W * H;
   const int half = block / 2;
   const int x0 = blockIdx.x * DT_W, y0 = blockIdx.y * DT_H;
   const int tid = threadIdx.x;
@@ -111,7 +117,7 @@ __global__ __launch_bounds__(256) void stereo_dense_batch_kernel(SvoDensePairs s
   for (int pix = tid; pix < DT_PIX; pix += 256) {
     const int x = x0 + (pix % DT_W), y = y0 + pix / DT_W;
     if (x >= W || y >= H) continue;
-    int res = -16;
+    int res = -16, won = 0xFFFF;
     if (x >= ndisp - 1 + half && x < W - half && y >= half && y < H - half) {
       auto S = [&](int i) -> int { return sSad[(size_t)i * DT_PIX + pix]; };
       const int tsum = S(ndisp);
@@ -130,11 +136,13 @@ __global__ __launch_bounds__(256) void stereo_dense_batch_kernel(SvoDensePairs s
           const int p = mind + 1 < ndisp ? S(mind + 1) : S(ndisp - 2);
           const int n = mind - 1 >= 0 ? S(mind - 1) : S(1);
           const int dd = p + n - 2 * minsad + abs(p - n);
-          res = (short)(((ndisp - mind - 1) * 256 + (dd != 0 ? (p - n) * 256 / dd : 0) + 15) >> 4);
+          res = (short)(((ndisp - mind - 1) * 256 + (dd != 0 ? (p - n) * 256 / dd : 0) + 15) >> 4);  // >= -8: never FILTERED
+          won = minsad;
         }
       }
     }
     out[(size_t)y * W + x] = (int16_t)res;
+    if (COST) cost[(size_t)y * W + x] = (uint16_t)won;
   }
 }
 
@@ -256,16 +264,19 @@ __global__ __launch_bounds__(CL_T) void cloud_write_kernel(SvoCloudArgs a) {
 
 // ----------------------------------------------------------------------------- host side
 int svo_k_stereo_dense_batch(svo_ctx* ctx, const SvoDensePairs& src, int batch, int W, int H, int stride, int ndisp, int block,
-                             int16_t* disp16) {
+                             int16_t* disp16, uint16_t* cost16) {
   const size_t sad_lds = sizeof(unsigned short) * (size_t)(ndisp + 1) * DT_PIX;
-  // the grant belongs to the device the kernel was loaded on: remembered per context (= per device), not per process
-  if ((int)sad_lds > ctx->dense_lds_granted) {
-    SVO_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)stereo_dense_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DENSE_LDS_MAX));
-    ctx->dense_lds_granted = DENSE_LDS_MAX;
+  // the grant belongs to the device the kernel was loaded on, and to ONE kernel function (hipFuncSetAttribute is per function):
+  // remembered per context (= per device) and per form, not per process
+  int& granted = cost16 ? ctx->dense_cost_lds_granted : ctx->dense_lds_granted;
+  auto* const kernel = cost16 ? stereo_dense_batch_kernel<true> : stereo_dense_batch_kernel<false>;
+  if ((int)sad_lds > granted) {
+    SVO_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DENSE_LDS_MAX));
+    granted = DENSE_LDS_MAX;
   }
   SvoProfScope prof(ctx, SVO_PROF_STEREO_DENSE_BATCH);
-  hipLaunchKernelGGL(stereo_dense_batch_kernel, dim3(svo_div_up(W, DT_W), svo_div_up(H, DT_H), batch), dim3(256), sad_lds, ctx->stream,
-                     src, W, H, stride, ndisp, block, disp16);
+  hipLaunchKernelGGL(kernel, dim3(svo_div_up(W, DT_W), svo_div_up(H, DT_H), batch), dim3(256), sad_lds, ctx->stream,
+                     src, W, H, stride, ndisp, block, disp16, cost16);
   SVO_HIP_CHECK(ctx, hipGetLastError());
   return SVO_OK;
 }
@@ -321,6 +332,19 @@ extern "C" int svo_stereo_bm_batch_dev(svo_ctx* ctx, const uint8_t* left, const 
   SVO_REQUIRE(ctx, batch == 1 || image_stride >= (size_t)row_stride * (size_t)(height - 1) + (size_t)width, "stereo_bm_batch: images overlap");
   SvoDensePairs src{left, right, image_stride, nullptr};
   return svo_k_stereo_dense_batch(ctx, src, batch, width, height, row_stride, num_disparities, block_size, disp16);
+}
+
+extern "C" int svo_stereo_bm_cost_batch_dev(svo_ctx* ctx, const uint8_t* left, const uint8_t* right, int batch, int width, int height,
+                                            int row_stride, size_t image_stride, int num_disparities, int block_size, int16_t* disp16,
+                                            uint16_t* cost16) {
+  int rc = svo_stereo_check(ctx, left, right, width, height, row_stride, num_disparities, block_size);
+  if (rc) return rc;
+  SVO_REQUIRE(ctx, disp16, "stereo_bm_cost_batch: null disp16");
+  SVO_REQUIRE(ctx, cost16, "stereo_bm_cost_batch: null cost16");
+  SVO_REQUIRE(ctx, batch >= 1 && batch <= ctx->lim.max_batch, "stereo_bm_cost_batch: batch outside 1..max_batch");
+  SVO_REQUIRE(ctx, batch == 1 || image_stride >= (size_t)row_stride * (size_t)(height - 1) + (size_t)width, "stereo_bm_cost_batch: images overlap");
+  SvoDensePairs src{left, right, image_stride, nullptr};
+  return svo_k_stereo_dense_batch(ctx, src, batch, width, height, row_stride, num_disparities, block_size, disp16, cost16);
 }
 
 extern "C" int svo_disparity_cloud_batch_dev(svo_ctx* ctx, const int16_t* disp16, const uint8_t* left, int batch, int width, int height,
@@ -397,6 +421,9 @@ struct SvoKfClouds {
   bool speckle_on = false;            // svo_kfc_set_speckle: the maps are filtered before the clouds are formed
   svo_speckle_params speckle{};
   void* d_speckle_ws = nullptr;       // svo_speckle_workspace_bytes(W, H, max_kf)
+  bool lr_on = false;                 // svo_kfc_set_lr_check: the cost form of the dense launch, then the left-right check
+  svo_lr_check_params lr{};
+  uint16_t* d_cost = nullptr;         // max_kf cost maps, 2 * W * H * max_kf bytes
   std::vector<svo_keyframe_cloud> table;
 };
 
@@ -404,7 +431,7 @@ void svo_kfc_destroy(SvoKfClouds* k) {
   if (!k) return;
   (void)hipSetDevice(k->ctx->device);
   (void)hipStreamSynchronize(k->ctx->stream);
-  void* ptrs[] = {k->d_disp, k->d_points, k->d_counts, k->d_seg, k->d_tab, k->d_speckle_ws};
+  void* ptrs[] = {k->d_disp, k->d_points, k->d_counts, k->d_seg, k->d_tab, k->d_speckle_ws, k->d_cost};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (k->h_pinned) (void)hipHostFree(k->h_pinned);
@@ -469,6 +496,33 @@ int svo_kfc_set_speckle(SvoKfClouds* k, const svo_speckle_params* prm) {
   return SVO_OK;
 }
 
+const svo_lr_check_params* svo_kfc_lr_check(const SvoKfClouds* k) { return k->lr_on ? &k->lr : nullptr; }
+
+int svo_kfc_set_lr_check(SvoKfClouds* k, const svo_lr_check_params* prm) {
+  svo_ctx* ctx = k->ctx;
+  svo_use_device(ctx);
+  if (!prm) {
+    SVO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (k->d_cost) (void)hipFree(k->d_cost);
+    k->d_cost = nullptr;
+    k->lr_on = false;
+    return SVO_OK;
+  }
+  const int rc = svo_lr_check_check(ctx, k->W, k->H, k->max_kf, prm);
+  if (rc) return rc;
+  if (!k->d_cost) {
+    const hipError_t e = hipMalloc((void**)&k->d_cost, sizeof(uint16_t) * (size_t)k->W * (size_t)k->H * (size_t)k->max_kf);
+    if (e != hipSuccess) {
+      k->d_cost = nullptr;
+      ctx->err = std::string("set_keyframe_lr_check: allocation failed: ") + hipGetErrorString(e);
+      return SVO_ERR_HIP;
+    }
+  }
+  k->lr = *prm;
+  k->lr_on = true;
+  return SVO_OK;
+}
+
 int svo_kfc_run(SvoKfClouds* k, const svo_camera_info* cam, const SvoCloudPair* pairs, const int* frame, const int* lane, int n) {
   svo_ctx* ctx = k->ctx;
   k->table.clear();
@@ -488,8 +542,13 @@ int svo_kfc_run(SvoKfClouds* k, const svo_camera_info* cam, const SvoCloudPair* 
   memcpy(h_tab, pairs, sizeof(SvoCloudPair) * (size_t)n);
   SVO_HIP_CHECK(ctx, hipMemcpyAsync(k->d_tab, h_tab, sizeof(SvoCloudPair) * (size_t)n, hipMemcpyHostToDevice, st));
   SvoDensePairs src{nullptr, nullptr, 0, k->d_tab};
-  rc = svo_k_stereo_dense_batch(ctx, src, n, k->W, k->H, k->W, svo_ref::STEREO_NUM_DISPARITIES, svo_ref::STEREO_BLOCK_SIZE, k->d_disp);
+  rc = svo_k_stereo_dense_batch(ctx, src, n, k->W, k->H, k->W, svo_ref::STEREO_NUM_DISPARITIES, svo_ref::STEREO_BLOCK_SIZE, k->d_disp,
+                                k->lr_on ? k->d_cost : nullptr);
   if (rc) return rc;
+  if (k->lr_on) {  // same stream, before the speckle filter as in StereoBM::compute
+    rc = svo_k_lr_check(ctx, k->d_disp, k->d_cost, n, k->W, k->H, &k->lr, nullptr);
+    if (rc) return rc;
+  }
   if (k->speckle_on) {  // same stream: the clouds below are those of the filtered maps
     rc = svo_k_speckle(ctx, k->d_disp, n, k->W, k->H, &k->speckle, k->d_speckle_ws, nullptr);
     if (rc) return rc;

@@ -89,7 +89,9 @@ struct SvoDensePairs {
   size_t image_stride;
   const SvoCloudPair* tab;
 };
-int svo_k_stereo_dense_batch(svo_ctx* ctx, const SvoDensePairs& src, int batch, int W, int H, int stride, int ndisp, int block, int16_t* disp16);
+// cost16 != null: the cost form of the kernel, which also writes the winner's SAD per pixel (0xFFFF where the map is FILTERED)
+int svo_k_stereo_dense_batch(svo_ctx* ctx, const SvoDensePairs& src, int batch, int W, int H, int stride, int ndisp, int block, int16_t* disp16,
+                             uint16_t* cost16 = nullptr);
 int svo_k_cloud_chunks(int W, int H, int step);  // ints of `seg` per image
 int svo_k_cloud(svo_ctx* ctx, const int16_t* disp16, const SvoDensePairs& src, int batch, int W, int H, int stride, const svo_camera_info* cam,
                 const float* pose16, const svo_cloud_params* prm, svo_cloud_point* points, int* counts, int* seg);
@@ -97,8 +99,12 @@ int svo_k_cloud(svo_ctx* ctx, const int16_t* disp16, const SvoDensePairs& src, i
 // n_removed: batch device ints or null.  max_size == 0 launches nothing.  svo_speckle_check: the argument rules, with messages.
 int svo_speckle_check(svo_ctx* ctx, int W, int H, int batch, const svo_speckle_params* prm);
 int svo_k_speckle(svo_ctx* ctx, int16_t* disp16, int batch, int W, int H, const svo_speckle_params* prm, void* workspace, int* n_removed);
+// left-right check (csrc/lr_check.hip): one launch over `batch` tight maps, in place, from the winner's SAD per pixel;
+// n_removed: batch device ints or null.  svo_lr_check_check: the argument rules, with messages.
+int svo_lr_check_check(svo_ctx* ctx, int W, int H, int batch, const svo_lr_check_params* prm);
+int svo_k_lr_check(svo_ctx* ctx, int16_t* disp16, const uint16_t* cost16, int batch, int W, int H, const svo_lr_check_params* prm, int* n_removed);
 // The keyframe clouds of one pipeline or one group: every buffer allocated once by create; run() = one dense launch + (with
-// svo_kfc_set_speckle) the speckle filter's launches + one cloud launch sequence over the given pairs on the context's stream,
+// svo_kfc_set_lr_check) the left-right check + (with svo_kfc_set_speckle) the speckle filter's launches + one cloud launch sequence over the given pairs on the context's stream,
 // then waits and fills the table.
 struct SvoKfClouds;
 int svo_kfc_create(svo_ctx* ctx, const svo_cloud_params* params, int W, int H, int max_keyframes, SvoKfClouds** out);
@@ -110,6 +116,10 @@ void svo_kfc_clear(SvoKfClouds* k);
 // non-null call and freed with the object or by a null call.  svo_kfc_speckle: the parameters in force, or null.
 int svo_kfc_set_speckle(SvoKfClouds* k, const svo_speckle_params* prm);
 const svo_speckle_params* svo_kfc_speckle(const SvoKfClouds* k);
+// the left-right check between the dense launch and the speckle filter, likewise: the cost maps for max_keyframes maps are
+// allocated by the first non-null call; while it is on, run() launches the cost form of the dense kernel
+int svo_kfc_set_lr_check(SvoKfClouds* k, const svo_lr_check_params* prm);
+const svo_lr_check_params* svo_kfc_lr_check(const SvoKfClouds* k);
 int svo_kfc_run(SvoKfClouds* k, const svo_camera_info* cam, const SvoCloudPair* pairs, const int* frame, const int* lane, int n);
 int svo_kfc_table(SvoKfClouds* k, int* n, const svo_keyframe_cloud** table);
 int svo_kfc_copy(SvoKfClouds* k, int i, svo_cloud_point* host, int capacity);

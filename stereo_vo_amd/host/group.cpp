@@ -1342,6 +1342,10 @@ extern "C" int svo_pipeline_group_set_keyframe_clouds(svo_pipeline_group* g, int
         const int rs = svo_kfc_set_speckle(k, svo_kfc_speckle(g->kfc));
         if (rs) { svo_kfc_destroy(k); return rs; }
       }
+      if (g->kfc && svo_kfc_lr_check(g->kfc)) {  // and so does a left-right check
+        const int rs = svo_kfc_set_lr_check(k, svo_kfc_lr_check(g->kfc));
+        if (rs) { svo_kfc_destroy(k); return rs; }
+      }
       svo_kfc_destroy(g->kfc);
       g->kfc = k;
     }
@@ -1359,6 +1363,13 @@ extern "C" int svo_pipeline_group_set_keyframe_speckle_filter(svo_pipeline_group
   SVO_HIP_CHECK(g->ctx, hipSetDevice(g->ctx->device));
   SVO_REQUIRE(g->ctx, g->kfc, "pipeline_group_set_keyframe_speckle_filter: keyframe clouds are off on every lane (call svo_pipeline_group_set_keyframe_clouds first)");
   return svo_kfc_set_speckle(g->kfc, params);
+}
+
+extern "C" int svo_pipeline_group_set_keyframe_lr_check(svo_pipeline_group* g, const svo_lr_check_params* params) {
+  if (!g) return SVO_ERR_INVALID;
+  SVO_HIP_CHECK(g->ctx, hipSetDevice(g->ctx->device));
+  SVO_REQUIRE(g->ctx, g->kfc, "pipeline_group_set_keyframe_lr_check: keyframe clouds are off on every lane (call svo_pipeline_group_set_keyframe_clouds first)");
+  return svo_kfc_set_lr_check(g->kfc, params);
 }
 
 extern "C" int svo_pipeline_group_keyframe_clouds(svo_pipeline_group* g, int* n, const svo_keyframe_cloud** table) {

@@ -908,6 +908,10 @@ extern "C" int svo_pipeline_set_keyframe_clouds(svo_pipeline* p, const svo_cloud
       const int rs = svo_kfc_set_speckle(k, svo_kfc_speckle(p->kfc));
       if (rs) { svo_kfc_destroy(k); return rs; }
     }
+    if (p->kfc && svo_kfc_lr_check(p->kfc)) {  // and so does a left-right check
+      const int rs = svo_kfc_set_lr_check(k, svo_kfc_lr_check(p->kfc));
+      if (rs) { svo_kfc_destroy(k); return rs; }
+    }
   }
   svo_kfc_destroy(p->kfc);
   p->kfc = k;
@@ -919,6 +923,13 @@ extern "C" int svo_pipeline_set_keyframe_speckle_filter(svo_pipeline* p, const s
   p->adjuster->wait();
   SVO_REQUIRE(p->ctx, p->kfc, "pipeline_set_keyframe_speckle_filter: keyframe clouds are off (call svo_pipeline_set_keyframe_clouds first)");
   return svo_kfc_set_speckle(p->kfc, params);
+}
+
+extern "C" int svo_pipeline_set_keyframe_lr_check(svo_pipeline* p, const svo_lr_check_params* params) {
+  if (!p) return SVO_ERR_INVALID;
+  p->adjuster->wait();
+  SVO_REQUIRE(p->ctx, p->kfc, "pipeline_set_keyframe_lr_check: keyframe clouds are off (call svo_pipeline_set_keyframe_clouds first)");
+  return svo_kfc_set_lr_check(p->kfc, params);
 }
 
 extern "C" int svo_pipeline_keyframe_clouds(svo_pipeline* p, int* n, const svo_keyframe_cloud** table) {

@@ -9,9 +9,12 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      svo_measure_peak("hbm_copy") of the same run;
   3. speckle filter: the four launches of svo_disparity_speckle_filter_batch_dev per pair on the fused launch's own maps,
      max_size 100 and 400, max_diff16 32, beside the fused launch and the copy rate of the same run;
-  4. cost to the VO: bench.py's headline load (96 lanes in 3 pipeline groups of 16-frame steps) without keyframe clouds, with
-     clouds at step 4, and with clouds and the speckle filter, alternating, as frames/s, their ratios and the spread over the
-     rounds.
+  4. left-right check: the cost form of the fused launch (svo_stereo_bm_cost_batch_dev, which also writes the winner's SAD) per
+     pair beside the plain form, and the one launch of svo_disparity_lr_check_batch_dev per pair on that map and cost,
+     max_diff16 16, beside the copy rate of the same run;
+  5. cost to the VO: bench.py's headline load (96 lanes in 3 pipeline groups of 16-frame steps) without keyframe clouds, with
+     clouds at step 4, with clouds and the speckle filter, and with clouds and the left-right check, alternating, as frames/s,
+     their ratios and the spread over the rounds.
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -29,6 +32,7 @@ import numpy as np  # noqa: E402
 W, H = bench.W, bench.H
 NDISP, BLOCK = 48, 21
 SPECKLE_SIZES, SPECKLE_DIFF = (100, 400), 32
+LR_DIFF = 16
 
 
 def standalone(S, torch, batch, warmup, reps):
@@ -105,6 +109,40 @@ def standalone(S, torch, batch, warmup, reps):
                                "valid_per_pair": float((dm != -16).sum().item()) / batch, "budget_bytes_per_pair": nbytes,
                                "bytes_per_s": nbytes / per, "share_of_copy_rate": nbytes / per / copy,
                                "ratio_to_fused_dense": 1e3 * per / out["fused_ms_per_pair"], "sequences_timed": k})
+    # left-right check: the cost form of the fused launch beside the plain form (alternating blocks, the same bracket), then the
+    # check on that map and cost (in place: every call gets a fresh copy of the map, made outside the timed bracket)
+    dc = torch.empty((batch, H, W), dtype=torch.int16, device="cuda")  # uint16 costs
+    dm2 = torch.empty_like(dm)
+
+    def fused_cost():
+        ctx.stereo_bm_cost_batch(dl.data_ptr(), dr.data_ptr(), batch, W, H, W, W * H, dm2.data_ptr(), dc.data_ptr(), NDISP, BLOCK)
+
+    plain_ms, cost_ms = [], []
+    for _ in range(3):
+        ms, k = timed("stereo_dense_batch", fused, reps)
+        plain_ms.append(ms / k / batch)
+        ms, k = timed("stereo_dense_batch", fused_cost, reps)
+        cost_ms.append(ms / k / batch)
+    ctx.sync()
+    lr = {"max_diff16": LR_DIFF, "plain_ms_per_pair": float(np.median(plain_ms)), "cost_ms_per_pair": float(np.median(cost_ms)),
+          "all_plain_ms": plain_ms, "all_cost_ms": cost_ms, "launches_per_block": reps,
+          "cost_map_equals_plain_map": bool(torch.equal(dm, dm2))}
+    lr["ratio_cost_to_plain"] = lr["cost_ms_per_pair"] / lr["plain_ms_per_pair"]
+    prm = api.LrCheckParams(LR_DIFF)
+
+    def check():
+        work.copy_(dm2)
+        torch.cuda.synchronize()
+        ctx.lr_check_dev(work.data_ptr(), dc.data_ptr(), batch, W, H, prm, nrem.data_ptr())
+        ctx.sync()
+
+    ms, k = timed("lr_check", check, reps)
+    per = ms / k / batch * 1e-3
+    nbytes = 4 * W * H  # map and cost read once, 2 B each; the few FILTERED stores are not counted
+    lr.update({"check_ms_per_pair": 1e3 * per, "removed_per_pair": float(nrem.cpu().numpy().mean()),
+               "valid_per_pair": float((dm2 != -16).sum().item()) / batch, "budget_bytes_per_pair": nbytes, "bytes_per_s": nbytes / per,
+               "share_of_copy_rate": nbytes / per / copy, "ratio_to_fused_dense": 1e3 * per / lr["plain_ms_per_pair"], "calls_timed": k})
+    out["lr_check"] = lr
     ctx.close()
     return out
 
@@ -129,11 +167,12 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
         pipe.ctx._chk(pipe.L.svo_pipeline_group_keyframe_clouds(pipe.h, C.byref(n), C.byref(tab)), "svo_pipeline_group_keyframe_clouds")
         return n.value
 
-    def timed(on, speckle=False):
+    def timed(on, speckle=False, lr=False):
         for g in groups:
             g.pipe.set_keyframe_clouds(-1, prm if on else None)
             if on:
                 g.pipe.set_keyframe_speckle_filter(SPECKLE_SIZES[0] if speckle else None, SPECKLE_DIFF)
+                g.pipe.set_keyframe_lr_check(LR_DIFF if lr else None)
             g.clear_counters()
         run(warmup)
         torch.cuda.synchronize()
@@ -144,22 +183,26 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
         kf = sum(table_len(g.pipe) for g in groups) if on else 0  # of the last step
         return lanes * frames * steps / dt, 1e3 * dt / steps, kf
 
-    plain, cloud, filt = [], [], []
+    plain, cloud, filt, chk = [], [], [], []
     for _ in range(rounds):  # alternating: other people's work shares the host
         plain.append(timed(False))
         cloud.append(timed(True))
         filt.append(timed(True, True))
+        chk.append(timed(True, False, True))
     for g in groups:
         g.close()
     med = lambda xs: float(np.median(xs))
-    fp, fc, ff = med([x[0] for x in plain]), med([x[0] for x in cloud]), med([x[0] for x in filt])
+    fp, fc, ff, fl = med([x[0] for x in plain]), med([x[0] for x in cloud]), med([x[0] for x in filt]), med([x[0] for x in chk])
     return {"lanes": lanes, "groups": n_groups, "frames_per_step_per_lane": frames, "steps": steps, "rounds": rounds, "cloud_step": step_px,
             "frames_per_s_plain": fp, "frames_per_s_clouds": fc, "ratio": fc / fp,
             "step_ms_plain": med([x[1] for x in plain]), "step_ms_clouds": med([x[1] for x in cloud]),
             "keyframes_in_last_step": [x[2] for x in cloud],
             "all_plain": [x[0] for x in plain], "all_clouds": [x[0] for x in cloud],
             "speckle_max_size": SPECKLE_SIZES[0], "speckle_max_diff16": SPECKLE_DIFF, "frames_per_s_clouds_speckle": ff,
-            "ratio_speckle_to_clouds": ff / fc, "step_ms_clouds_speckle": med([x[1] for x in filt]), "all_clouds_speckle": [x[0] for x in filt]}
+            "ratio_speckle_to_clouds": ff / fc, "step_ms_clouds_speckle": med([x[1] for x in filt]), "all_clouds_speckle": [x[0] for x in filt],
+            "lr_max_diff16": LR_DIFF, "frames_per_s_clouds_lr_check": fl, "ratio_lr_check_to_clouds": fl / fc,
+            "step_ms_clouds_lr_check": med([x[1] for x in chk]), "all_clouds_lr_check": [x[0] for x in chk],
+            "round_ratios_lr_check_to_clouds": [b[0] / a[0] for a, b in zip(cloud, chk)]}
 
 
 def main():
@@ -205,6 +248,13 @@ def main():
                         f"(mean of {c['sequences_timed']} sequences of {s['batch']} maps), {c['removed_per_pair']:.0f} of {c['valid_per_pair']:.0f} valid pixels removed per pair; "
                         f"{c['ratio_to_fused_dense']:.3f} x the fused dense launch; 19 A = {c['budget_bytes_per_pair'] / 1e6:.3f} MB per pair -> "
                         f"{c['bytes_per_s'] / 1e12:.3f} TB/s ({100 * c['share_of_copy_rate']:.1f} % of hbm_copy, same run)\n")
+            c = s["lr_check"]
+            f.write(f"left-right check, max_diff16 {c['max_diff16']}: cost form of the fused dense launch {c['cost_ms_per_pair']:.4f} ms per pair beside the plain form "
+                    f"{c['plain_ms_per_pair']:.4f} (medians of 3 alternating blocks of {c['launches_per_block']} launches; plain {[round(x, 4) for x in c['all_plain_ms']]}, "
+                    f"cost {[round(x, 4) for x in c['all_cost_ms']]}): ratio {c['ratio_cost_to_plain']:.3f}; maps identical: {c['cost_map_equals_plain_map']}\n"
+                    f"  the check (one launch): {1e3 * c['check_ms_per_pair']:.1f} us per pair (mean of {c['calls_timed']} calls of {s['batch']} maps), "
+                    f"{c['removed_per_pair']:.0f} of {c['valid_per_pair']:.0f} valid pixels removed per pair; {c['ratio_to_fused_dense']:.3f} x the fused dense launch; "
+                    f"4 A = {c['budget_bytes_per_pair'] / 1e6:.3f} MB per pair -> {c['bytes_per_s'] / 1e12:.3f} TB/s ({100 * c['share_of_copy_rate']:.1f} % of hbm_copy, same run)\n")
             if g:
                 f.write(f"{g['lanes']} lanes in {g['groups']} groups, {g['frames_per_step_per_lane']}-frame steps, median of {g['rounds']} alternating rounds of "
                         f"{g['steps']} steps, clouds at step {g['cloud_step']}:\n  without clouds {g['frames_per_s_plain']:.0f} frames/s ({g['step_ms_plain']:.1f} ms / step), "
@@ -213,7 +263,10 @@ def main():
                         f"keyframes in the last step of each round with clouds: {g['keyframes_in_last_step']}\n"
                         f"  with clouds and the speckle filter (max_size {g['speckle_max_size']}, max_diff16 {g['speckle_max_diff16']}): "
                         f"{g['frames_per_s_clouds_speckle']:.0f} frames/s ({g['step_ms_clouds_speckle']:.1f} ms / step): ratio to clouds alone "
-                        f"{g['ratio_speckle_to_clouds']:.3f}; rounds: {[round(x) for x in g['all_clouds_speckle']]}\n")
+                        f"{g['ratio_speckle_to_clouds']:.3f}; rounds: {[round(x) for x in g['all_clouds_speckle']]}\n"
+                        f"  with clouds and the left-right check (max_diff16 {g['lr_max_diff16']}): {g['frames_per_s_clouds_lr_check']:.0f} frames/s "
+                        f"({g['step_ms_clouds_lr_check']:.1f} ms / step): ratio to clouds alone {g['ratio_lr_check_to_clouds']:.3f}; rounds: "
+                        f"{[round(x) for x in g['all_clouds_lr_check']]}; per round {[round(x, 3) for x in g['round_ratios_lr_check_to_clouds']]}\n")
 
 
 if __name__ == "__main__":
