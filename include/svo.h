@@ -95,7 +95,8 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * "lk_fb", "stereo_at", "triangulate", "pnp_hypotheses", "pnp_refine", "ba_linearize", "ba_backsub", "ba_step",
  * "rectify_remap", "stereo_bm" (the three launches of svo_stereo_bm as one bracket), "stereo_dense_batch",
  * "cloud" (the count, scan and write launches of one svo_disparity_cloud_batch_dev as one bracket),
- * "speckle" (the launches of one speckle filter call as one bracket), "lr_check" (one left-right check call);
+ * "speckle" (the launches of one speckle filter call as one bracket), "lr_check" (one left-right check call),
+ * "stereo_sgm" (the launches of one semi-global matching call as one bracket);
  * NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
@@ -292,6 +293,56 @@ int svo_disparity_lr_check_batch_dev(svo_ctx* ctx, int16_t* disp16, const uint16
 /* One map, HOST pointers, disp16 in place, synchronous; n_removed: host int or NULL. */
 int svo_disparity_lr_check(svo_ctx* ctx, int16_t* disp16, const uint16_t* cost16, int width, int height,
                            const svo_lr_check_params* params, int* n_removed);
+
+/* ------------------------------------------------------ semi-global matching --
+ * Four-path cost aggregation over StereoBM's cost volume, then StereoBM's own selection on the aggregated costs, for a batch of
+ * pairs on the device (no reference counterpart: the reference samples StereoBM at textured features; a whole-map cloud wants
+ * the weakly textured surfaces block matching rejects).  This is the project's own statement; parity with OpenCV's SGBM is NOT
+ * claimed.  Inputs as svo_stereo_bm_batch_dev (raw uint8 pairs, num_disparities 16 / 32 / 48 / 64, block_size odd 5..21) plus
+ * 0 <= p1 <= p2 <= SVO_SGM_MAX_P2.  All arithmetic is exact integer arithmetic.
+ *   1. Cost volume.  Over StereoBM's valid rectangle (x in [ndisp-1+half, W-half), y in [half, H-half), half = block_size / 2)
+ *      C(x, y, d) is exactly the windowed SAD of the prefiltered images that StereoBM minimises (same prefilter, same mirrored
+ *      rows, same window); the texture sum is StereoBM's.
+ *   2. Paths.  Four: left->right, right->left, top->bottom, bottom->top, all inside the valid rectangle.  The first pixel of a
+ *      path has L_r(p, d) = C(p, d); after it, with q the previous pixel and m = min_k L_r(q, k),
+ *        L_r(p, d) = C(p, d) + min(L_r(q, d), L_r(q, d-1) + p1, L_r(q, d+1) + p1, m + p2) - m,
+ *      the d +- 1 terms absent outside [0, ndisp).  Hence L_r <= 27,342 + p2 <= 60,109 (16 bits); S = sum_r L_r <= 240,436.
+ *   3. Selection on S: StereoBM's with s := S.  The winner is the minimum, among equal minima the LARGEST d; the pixel is rejected
+ *      iff some d more than 1 away from the winner has S <= m + m * 15 / 100 (C division), or iff the texture sum < 10; the
+ *      sub-pixel term uses the mirrored ends S[-1] = S[1], S[ndisp] = S[ndisp-2], truncated division and (... + 15) >> 4.
+ *      Output: CV_16S, 4 fractional bits, FILTERED = -16; everything outside the rectangle is FILTERED.
+ *   4. Cost form.  cost16 = min((S_min + 2) >> 2, 0xFFFE) where the map is not FILTERED, 0xFFFF where it is: what
+ *      svo_disparity_lr_check_batch_dev takes.
+ *   5. Identity.  With p1 = p2 = 0, map and cost are bit-identical to svo_stereo_bm_cost_batch_dev's (L_r = C, S = 4 C).
+ *   6. Defaults.  p1 = 2 block_size^2, p2 = 8 block_size^2: chosen on a synthetic scene, NOT tuned on real imagery. */
+typedef struct svo_sgm_params {
+  int p1;  /* >= 0: a disparity step of 1 between path neighbours */
+  int p2;  /* p1 <= p2 <= SVO_SGM_MAX_P2: any larger step */
+} svo_sgm_params;
+/* The largest p2: 27,342 + 32,767 = 60,109 keeps a path cost within 16 bits. */
+#define SVO_SGM_MAX_P2 32767
+/* Keyframe maps of a pipeline / a group are matched this many pairs at a time (svo_pipeline_set_keyframe_sgm): the work space
+ * is allocated for this many pairs, whatever max_keyframes_per_call is. */
+#define SVO_SGM_KEYFRAME_SUB_BATCH 2
+/* p1 = 2 block_size^2, p2 = 8 block_size^2 (block_size odd 5..21, SVO_ERR_INVALID otherwise). */
+int svo_sgm_default_params(svo_sgm_params* params, int block_size);
+/* Bytes of work space for `batch` pairs: per pixel of the valid rectangle, num_disparities u16 costs and as many u32 sums plus
+ * one u16 texture sum, each array rounded up to 256 bytes (about 120 MB per 1241 x 376 pair at 48 disparities); never less than
+ * 256 for an accepted shape.  Pure (no device needed); 0 for a refused shape (width or height < 3, width*height > 2^30, batch
+ * outside 1..65535, a num_disparities or block_size StereoBM refuses). */
+size_t svo_sgm_workspace_bytes(int width, int height, int num_disparities, int block_size, int batch);
+/* `batch` pairs, DEVICE pointers, asynchronous on svo_stream(ctx), ordered by launch: fill, cost volume, four path launches (the
+ * last one selects).  Images and strides as svo_stereo_bm_batch_dev; 1 <= batch <= svo_limits.max_batch.  workspace: 256-byte
+ * aligned device memory of at least svo_sgm_workspace_bytes(...) bytes (nothing behind that is touched; contents before and
+ * after are meaningless).  disp16: batch tight maps; cost16: batch tight maps or NULL.  A refused call (null pointer, p1 > p2,
+ * a negative penalty, p2 over the bound, a bad num_disparities, block_size, batch or shape, a short workspace) returns
+ * SVO_ERR_INVALID with a message naming the argument and launches nothing. */
+int svo_stereo_sgm_batch_dev(svo_ctx* ctx, const uint8_t* left, const uint8_t* right, int batch, int width, int height,
+                             int row_stride, size_t image_stride, int num_disparities, int block_size, const svo_sgm_params* params,
+                             void* workspace, size_t workspace_bytes, int16_t* disp16, uint16_t* cost16);
+/* One pair, HOST pointers, synchronous; the work space is allocated and freed by the call.  cost16: width*height or NULL. */
+int svo_stereo_sgm(svo_ctx* ctx, const uint8_t* left, const uint8_t* right, int width, int height, int row_stride,
+                   int num_disparities, int block_size, const svo_sgm_params* params, int16_t* disp16, uint16_t* cost16);
 
 /* ------------------------------------------------------------------- a8 --
  * ImageProcessor::triangulate_stereo's reprojection loop
@@ -582,6 +633,15 @@ int svo_pipeline_set_keyframe_speckle_filter(svo_pipeline* p, const svo_speckle_
  * sparse StereoBM that feeds landmarks, svo_frame_result and the tracked set do not change.  Never called: no launch, no
  * allocation, nothing changes, and the dense launch is the plain kernel. */
 int svo_pipeline_set_keyframe_lr_check(svo_pipeline* p, const svo_lr_check_params* params);
+/* Semi-global matching for the keyframe maps (above, "semi-global matching"): with params != NULL every process call runs the
+ * matching sequence of svo_stereo_sgm_batch_dev (48, 21) instead of the dense launch, SVO_SGM_KEYFRAME_SUB_BATCH keyframes at a
+ * time, then the left-right check (fed by the cost form of item 4) and the speckle filter if those are on, then the clouds, on
+ * the same stream.  The three switches are independent.  Keyframe clouds must be on already (SVO_ERR_INVALID otherwise); the
+ * work space for SVO_SGM_KEYFRAME_SUB_BATCH pairs is allocated once here, so max_keyframes_per_call does not multiply it.  NULL
+ * returns to block matching and frees it; so does turning the clouds off.  New cloud parameters keep the switch.  Only the
+ * dense maps change: the sparse StereoBM that feeds landmarks, svo_frame_result and the tracked set do not.  Never called: no
+ * launch, no allocation, nothing changes. */
+int svo_pipeline_set_keyframe_sgm(svo_pipeline* p, const svo_sgm_params* params);
 /* One entry per keyframe of the last process call, in frame order (src/image_processor.cpp:173-207 per entry). */
 typedef struct svo_keyframe_cloud {
   int frame;                  /* index in the call */
@@ -648,6 +708,8 @@ int svo_pipeline_group_set_keyframe_clouds(svo_pipeline_group* g, int lane, cons
 int svo_pipeline_group_set_keyframe_speckle_filter(svo_pipeline_group* g, const svo_speckle_params* params);
 /* svo_pipeline_set_keyframe_lr_check for the group, group-wide like the speckle filter.  Clouds must be on for at least one lane. */
 int svo_pipeline_group_set_keyframe_lr_check(svo_pipeline_group* g, const svo_lr_check_params* params);
+/* svo_pipeline_set_keyframe_sgm for the group, group-wide like the two filters.  Clouds must be on for at least one lane. */
+int svo_pipeline_group_set_keyframe_sgm(svo_pipeline_group* g, const svo_sgm_params* params);
 int svo_pipeline_group_keyframe_clouds(svo_pipeline_group* g, int* n, const svo_keyframe_cloud** table);
 int svo_pipeline_group_copy_keyframe_cloud(svo_pipeline_group* g, int i, svo_cloud_point* host, int capacity);
 int svo_pipeline_group_get_tracked(svo_pipeline_group* g, int lane, int64_t* ids, float* xy, int capacity, int* n);

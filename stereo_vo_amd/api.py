@@ -102,7 +102,36 @@ class LrCheckParams(C.Structure):
     _fields_ = [("max_diff16", C.c_int)]
 
 
+class SgmParams(C.Structure):
+    """svo_sgm_params: the penalties of semi-global matching, 0 <= p1 <= p2 <= SGM_MAX_P2."""
+    _fields_ = [("p1", C.c_int), ("p2", C.c_int)]
+
+
 LR_CHECK_MAX_WIDTH = 10240  # SVO_LR_CHECK_MAX_WIDTH
+SGM_MAX_P2 = 32767  # SVO_SGM_MAX_P2
+SGM_KEYFRAME_SUB_BATCH = 2  # SVO_SGM_KEYFRAME_SUB_BATCH
+
+
+def sgm_default_params(block=21):
+    """svo_sgm_default_params: p1 = 2 block^2, p2 = 8 block^2 (chosen on a synthetic scene, not tuned on real imagery)."""
+    prm = SgmParams()
+    if lib().svo_sgm_default_params(C.byref(prm), int(block)) != 0:
+        raise SvoError(f"svo_sgm_default_params: block_size {block} is not odd 5..21")
+    return prm
+
+
+def sgm_workspace_bytes(width, height, ndisp=48, block=21, batch=1):
+    """svo_sgm_workspace_bytes: device bytes semi-global matching needs for `batch` pairs (no GPU involved); 0: a refused shape."""
+    return int(lib().svo_sgm_workspace_bytes(width, height, ndisp, block, batch))
+
+
+def _sgm_params(p1, p2, block=21):
+    prm = sgm_default_params(block)
+    if p1 is not None:
+        prm.p1 = int(p1)
+    if p2 is not None:
+        prm.p2 = int(p2)
+    return prm
 SPECKLE_TILE = (64, 16)  # SVO_SPECKLE_TILE_W, SVO_SPECKLE_TILE_H
 
 
@@ -269,6 +298,8 @@ SYMBOLS = [
     "svo_pipeline_set_keyframe_speckle_filter", "svo_pipeline_group_set_keyframe_speckle_filter",
     "svo_stereo_bm_cost_batch_dev", "svo_disparity_lr_check_batch_dev", "svo_disparity_lr_check",
     "svo_pipeline_set_keyframe_lr_check", "svo_pipeline_group_set_keyframe_lr_check",
+    "svo_sgm_default_params", "svo_sgm_workspace_bytes", "svo_stereo_sgm_batch_dev", "svo_stereo_sgm",
+    "svo_pipeline_set_keyframe_sgm", "svo_pipeline_group_set_keyframe_sgm",
 ]
 
 
@@ -321,6 +352,17 @@ def lib():
         L.svo_pipeline_group_set_keyframe_lr_check.argtypes = [vp, vp]
         for f in ("svo_stereo_bm_cost_batch_dev", "svo_disparity_lr_check_batch_dev", "svo_disparity_lr_check",
                   "svo_pipeline_set_keyframe_lr_check", "svo_pipeline_group_set_keyframe_lr_check"):
+            getattr(L, f).restype = ci
+        # semi-global matching
+        L.svo_sgm_default_params.argtypes = [vp, ci]
+        L.svo_sgm_workspace_bytes.argtypes = [ci, ci, ci, ci, ci]
+        L.svo_sgm_workspace_bytes.restype = sz
+        L.svo_stereo_sgm_batch_dev.argtypes = [vp, vp, vp, ci, ci, ci, ci, sz, ci, ci, vp, vp, sz, vp, vp]
+        L.svo_stereo_sgm.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]
+        L.svo_pipeline_set_keyframe_sgm.argtypes = [vp, vp]
+        L.svo_pipeline_group_set_keyframe_sgm.argtypes = [vp, vp]
+        for f in ("svo_sgm_default_params", "svo_stereo_sgm_batch_dev", "svo_stereo_sgm", "svo_pipeline_set_keyframe_sgm",
+                  "svo_pipeline_group_set_keyframe_sgm"):
             getattr(L, f).restype = ci
         _LIB = L
     return _LIB
@@ -570,6 +612,30 @@ class Context:
         self._chk(self.L.svo_disparity_lr_check_batch_dev(self.h, disp16_ptr, cost16_ptr, batch, width, height,
                                                           C.byref(params) if params is not None else None, n_removed_ptr),
                   "svo_disparity_lr_check_batch_dev")
+
+    # ---- semi-global matching
+    def sgm_workspace_bytes(self, width, height, ndisp=48, block=21, batch=1):
+        """svo_sgm_workspace_bytes (see the module function of the same name)."""
+        return sgm_workspace_bytes(width, height, ndisp, block, batch)
+
+    def stereo_sgm(self, left, right, ndisp=48, block=21, p1=None, p2=None, cost=False):
+        """svo_stereo_sgm: one host pair -> the (H, W) int16 map, or (map, (H, W) uint16 cost) with cost=True.  p1 / p2 None: the
+        defaults 2 block^2 / 8 block^2."""
+        left, right = _u8(left), _u8(right)
+        h, w = left.shape
+        d = np.empty((h, w), np.int16)
+        c = np.empty((h, w), np.uint16) if cost else None
+        prm = _sgm_params(p1, p2, block)
+        self._chk(self.L.svo_stereo_sgm(self.h, _p(left), _p(right), w, h, w, ndisp, block, C.byref(prm), _p(d), _p(c)), "svo_stereo_sgm")
+        return (d, c) if cost else d
+
+    def stereo_sgm_batch(self, left_ptr, right_ptr, batch, width, height, row_stride, image_stride, params, workspace_ptr, workspace_bytes,
+                         disp16_ptr, cost16_ptr=None, ndisp=48, block=21):
+        """svo_stereo_sgm_batch_dev: raw device pointers (ints); params: SgmParams; workspace: sgm_workspace_bytes(...) bytes;
+        disp16_ptr: batch tight (H, W) int16 maps; cost16_ptr: batch tight (H, W) uint16 maps or None.  Asynchronous."""
+        self._chk(self.L.svo_stereo_sgm_batch_dev(self.h, left_ptr, right_ptr, batch, width, height, row_stride, image_stride, ndisp, block,
+                                                  C.byref(params) if params is not None else None, workspace_ptr, workspace_bytes,
+                                                  disp16_ptr, cost16_ptr), "svo_stereo_sgm_batch_dev")
 
     # ---- a8
     def triangulate(self, xy, disp, pose16, focal, cx, cy, baseline):
@@ -859,6 +925,13 @@ class Pipeline:
         self.ctx._chk(self.L.svo_pipeline_set_keyframe_lr_check(self.h, C.byref(prm) if prm is not None else None),
                       "svo_pipeline_set_keyframe_lr_check")
 
+    def set_keyframe_sgm(self, p1=None, p2=None, on=True):
+        """svo_pipeline_set_keyframe_sgm: the keyframe maps come from semi-global matching instead of block matching (clouds must be
+        on); p1 / p2 None: the defaults 2 * 21^2 / 8 * 21^2; on=False: back to block matching."""
+        prm = _sgm_params(p1, p2) if on else None
+        self.ctx._chk(self.L.svo_pipeline_set_keyframe_sgm(self.h, C.byref(prm) if prm is not None else None),
+                      "svo_pipeline_set_keyframe_sgm")
+
     def keyframe_clouds(self):
         """The keyframes of the last process call: [{frame, lane, n_total, n_stored, dev, points (CLOUD_POINT_DTYPE array)}], in frame order."""
         return _keyframe_clouds(self.ctx, self.L, self.h, self.L.svo_pipeline_keyframe_clouds, self.L.svo_pipeline_copy_keyframe_cloud)
@@ -945,6 +1018,12 @@ class PipelineGroup:
         prm = None if max_diff16 is None else LrCheckParams(int(max_diff16))
         self.ctx._chk(self.L.svo_pipeline_group_set_keyframe_lr_check(self.h, C.byref(prm) if prm is not None else None),
                       "svo_pipeline_group_set_keyframe_lr_check")
+
+    def set_keyframe_sgm(self, p1=None, p2=None, on=True):
+        """svo_pipeline_group_set_keyframe_sgm (group-wide; clouds must be on); on=False: back to block matching."""
+        prm = _sgm_params(p1, p2) if on else None
+        self.ctx._chk(self.L.svo_pipeline_group_set_keyframe_sgm(self.h, C.byref(prm) if prm is not None else None),
+                      "svo_pipeline_group_set_keyframe_sgm")
 
     def keyframe_clouds(self):
         """The keyframes of the last process call over the lanes that have clouds on, ordered by lane, then frame (see Pipeline.keyframe_clouds)."""

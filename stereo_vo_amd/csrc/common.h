@@ -65,6 +65,7 @@ struct svo_ctx {
   size_t cloud_seg_ints = 0;
   int dense_lds_granted = 0;
   int dense_cost_lds_granted = 0;
+  int sgm_lds_granted = 0;             // sgm_volume_kernel (sgm.hip), likewise
   // completion words (see SvoPublish)
   int word_seq = 0;
   unsigned arrive_total = 0;
@@ -149,7 +150,8 @@ __device__ __forceinline__ void svo_publish_block_wt(const SvoPublish& p) {
 enum SvoProfTag { SVO_PROF_NONE = 0, SVO_PROF_CORNER_RESPONSE, SVO_PROF_CORNER_NMS, SVO_PROF_CORNER_SELECT,
                   SVO_PROF_PYR_DOWN, SVO_PROF_LK_FB, SVO_PROF_STEREO_AT, SVO_PROF_TRIANGULATE, SVO_PROF_PNP_HYP,
                   SVO_PROF_PNP_REFINE, SVO_PROF_BA_LINEARIZE, SVO_PROF_BA_BACKSUB, SVO_PROF_BA_STEP, SVO_PROF_RECTIFY,
-                  SVO_PROF_STEREO_BM, SVO_PROF_STEREO_DENSE_BATCH, SVO_PROF_CLOUD, SVO_PROF_SPECKLE, SVO_PROF_LR_CHECK };
+                  SVO_PROF_STEREO_BM, SVO_PROF_STEREO_DENSE_BATCH, SVO_PROF_CLOUD, SVO_PROF_SPECKLE, SVO_PROF_LR_CHECK,
+                  SVO_PROF_STEREO_SGM };
 
 // RAII event pair around one launch of the selected kernel (no-op for every other kernel).
 struct SvoProfScope {

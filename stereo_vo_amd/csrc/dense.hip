@@ -424,6 +424,9 @@ struct SvoKfClouds {
   bool lr_on = false;                 // svo_kfc_set_lr_check: the cost form of the dense launch, then the left-right check
   svo_lr_check_params lr{};
   uint16_t* d_cost = nullptr;         // max_kf cost maps, 2 * W * H * max_kf bytes
+  bool sgm_on = false;                // svo_kfc_set_sgm: semi-global matching (sgm.hip) instead of the dense launch
+  svo_sgm_params sgm{};
+  void* d_sgm_ws = nullptr;           // svo_sgm_workspace_bytes for SVO_SGM_KEYFRAME_SUB_BATCH pairs, whatever max_kf is
   std::vector<svo_keyframe_cloud> table;
 };
 
@@ -431,7 +434,7 @@ void svo_kfc_destroy(SvoKfClouds* k) {
   if (!k) return;
   (void)hipSetDevice(k->ctx->device);
   (void)hipStreamSynchronize(k->ctx->stream);
-  void* ptrs[] = {k->d_disp, k->d_points, k->d_counts, k->d_seg, k->d_tab, k->d_speckle_ws, k->d_cost};
+  void* ptrs[] = {k->d_disp, k->d_points, k->d_counts, k->d_seg, k->d_tab, k->d_speckle_ws, k->d_cost, k->d_sgm_ws};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (k->h_pinned) (void)hipHostFree(k->h_pinned);
@@ -523,6 +526,34 @@ int svo_kfc_set_lr_check(SvoKfClouds* k, const svo_lr_check_params* prm) {
   return SVO_OK;
 }
 
+const svo_sgm_params* svo_kfc_sgm(const SvoKfClouds* k) { return k->sgm_on ? &k->sgm : nullptr; }
+
+int svo_kfc_set_sgm(SvoKfClouds* k, const svo_sgm_params* prm) {
+  svo_ctx* ctx = k->ctx;
+  svo_use_device(ctx);
+  if (!prm) {
+    SVO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (k->d_sgm_ws) (void)hipFree(k->d_sgm_ws);
+    k->d_sgm_ws = nullptr;
+    k->sgm_on = false;
+    return SVO_OK;
+  }
+  const int nd = svo_ref::STEREO_NUM_DISPARITIES, bs = svo_ref::STEREO_BLOCK_SIZE;
+  const int rc = svo_sgm_check(ctx, k->W, k->H, nd, bs, SVO_SGM_KEYFRAME_SUB_BATCH, prm);
+  if (rc) return rc;
+  if (!k->d_sgm_ws) {
+    const hipError_t e = hipMalloc(&k->d_sgm_ws, svo_sgm_workspace_bytes(k->W, k->H, nd, bs, SVO_SGM_KEYFRAME_SUB_BATCH));
+    if (e != hipSuccess) {
+      k->d_sgm_ws = nullptr;
+      ctx->err = std::string("set_keyframe_sgm: allocation failed: ") + hipGetErrorString(e);
+      return SVO_ERR_HIP;
+    }
+  }
+  k->sgm = *prm;
+  k->sgm_on = true;
+  return SVO_OK;
+}
+
 int svo_kfc_run(SvoKfClouds* k, const svo_camera_info* cam, const SvoCloudPair* pairs, const int* frame, const int* lane, int n) {
   svo_ctx* ctx = k->ctx;
   k->table.clear();
@@ -542,8 +573,19 @@ int svo_kfc_run(SvoKfClouds* k, const svo_camera_info* cam, const SvoCloudPair* 
   memcpy(h_tab, pairs, sizeof(SvoCloudPair) * (size_t)n);
   SVO_HIP_CHECK(ctx, hipMemcpyAsync(k->d_tab, h_tab, sizeof(SvoCloudPair) * (size_t)n, hipMemcpyHostToDevice, st));
   SvoDensePairs src{nullptr, nullptr, 0, k->d_tab};
-  rc = svo_k_stereo_dense_batch(ctx, src, n, k->W, k->H, k->W, svo_ref::STEREO_NUM_DISPARITIES, svo_ref::STEREO_BLOCK_SIZE, k->d_disp,
-                                k->lr_on ? k->d_cost : nullptr);
+  if (k->sgm_on) {  // the matching sequence per sub-batch: the one workspace is reused, the launches are ordered by the stream
+    const size_t px = (size_t)k->W * (size_t)k->H;
+    for (int b0 = 0; b0 < n; b0 += SVO_SGM_KEYFRAME_SUB_BATCH) {
+      const int nb = n - b0 < SVO_SGM_KEYFRAME_SUB_BATCH ? n - b0 : SVO_SGM_KEYFRAME_SUB_BATCH;
+      SvoDensePairs sub{nullptr, nullptr, 0, k->d_tab + b0};
+      rc = svo_k_stereo_sgm(ctx, sub, nb, k->W, k->H, k->W, svo_ref::STEREO_NUM_DISPARITIES, svo_ref::STEREO_BLOCK_SIZE, &k->sgm, k->d_sgm_ws,
+                            k->d_disp + (size_t)b0 * px, k->lr_on ? k->d_cost + (size_t)b0 * px : nullptr);
+      if (rc) return rc;
+    }
+  } else {
+    rc = svo_k_stereo_dense_batch(ctx, src, n, k->W, k->H, k->W, svo_ref::STEREO_NUM_DISPARITIES, svo_ref::STEREO_BLOCK_SIZE, k->d_disp,
+                                  k->lr_on ? k->d_cost : nullptr);
+  }
   if (rc) return rc;
   if (k->lr_on) {  // same stream, before the speckle filter as in StereoBM::compute
     rc = svo_k_lr_check(ctx, k->d_disp, k->d_cost, n, k->W, k->H, &k->lr, nullptr);

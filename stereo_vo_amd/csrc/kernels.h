@@ -103,7 +103,13 @@ int svo_k_speckle(svo_ctx* ctx, int16_t* disp16, int batch, int W, int H, const 
 // n_removed: batch device ints or null.  svo_lr_check_check: the argument rules, with messages.
 int svo_lr_check_check(svo_ctx* ctx, int W, int H, int batch, const svo_lr_check_params* prm);
 int svo_k_lr_check(svo_ctx* ctx, int16_t* disp16, const uint16_t* cost16, int batch, int W, int H, const svo_lr_check_params* prm, int* n_removed);
-// The keyframe clouds of one pipeline or one group: every buffer allocated once by create; run() = one dense launch + (with
+// semi-global matching (csrc/sgm.hip): fill, cost volume and the four path launches over `batch` pairs as ONE profile bracket;
+// workspace: svo_sgm_workspace_bytes; cost16 may be null.  svo_sgm_check: the argument rules (params, shape), with messages.
+int svo_sgm_check(svo_ctx* ctx, int W, int H, int ndisp, int block, int batch, const svo_sgm_params* prm);
+int svo_k_stereo_sgm(svo_ctx* ctx, const SvoDensePairs& src, int batch, int W, int H, int stride, int ndisp, int block,
+                     const svo_sgm_params* prm, void* workspace, int16_t* disp16, uint16_t* cost16);
+// The keyframe clouds of one pipeline or one group: every buffer allocated once by create; run() = one dense launch (with
+// svo_kfc_set_sgm: the semi-global matching sequence per sub-batch of SVO_SGM_KEYFRAME_SUB_BATCH pairs instead) + (with
 // svo_kfc_set_lr_check) the left-right check + (with svo_kfc_set_speckle) the speckle filter's launches + one cloud launch sequence over the given pairs on the context's stream,
 // then waits and fills the table.
 struct SvoKfClouds;
@@ -120,6 +126,10 @@ const svo_speckle_params* svo_kfc_speckle(const SvoKfClouds* k);
 // allocated by the first non-null call; while it is on, run() launches the cost form of the dense kernel
 int svo_kfc_set_lr_check(SvoKfClouds* k, const svo_lr_check_params* prm);
 const svo_lr_check_params* svo_kfc_lr_check(const SvoKfClouds* k);
+// semi-global matching instead of the dense launch, likewise: the workspace for SVO_SGM_KEYFRAME_SUB_BATCH pairs is allocated by
+// the first non-null call; with the left-right check on, its cost form feeds the check
+int svo_kfc_set_sgm(SvoKfClouds* k, const svo_sgm_params* prm);
+const svo_sgm_params* svo_kfc_sgm(const SvoKfClouds* k);
 int svo_kfc_run(SvoKfClouds* k, const svo_camera_info* cam, const SvoCloudPair* pairs, const int* frame, const int* lane, int n);
 int svo_kfc_table(SvoKfClouds* k, int* n, const svo_keyframe_cloud** table);
 int svo_kfc_copy(SvoKfClouds* k, int i, svo_cloud_point* host, int capacity);

@@ -1346,6 +1346,10 @@ extern "C" int svo_pipeline_group_set_keyframe_clouds(svo_pipeline_group* g, int
         const int rs = svo_kfc_set_lr_check(k, svo_kfc_lr_check(g->kfc));
         if (rs) { svo_kfc_destroy(k); return rs; }
       }
+      if (g->kfc && svo_kfc_sgm(g->kfc)) {  // and semi-global matching
+        const int rs = svo_kfc_set_sgm(k, svo_kfc_sgm(g->kfc));
+        if (rs) { svo_kfc_destroy(k); return rs; }
+      }
       svo_kfc_destroy(g->kfc);
       g->kfc = k;
     }
@@ -1370,6 +1374,13 @@ extern "C" int svo_pipeline_group_set_keyframe_lr_check(svo_pipeline_group* g, c
   SVO_HIP_CHECK(g->ctx, hipSetDevice(g->ctx->device));
   SVO_REQUIRE(g->ctx, g->kfc, "pipeline_group_set_keyframe_lr_check: keyframe clouds are off on every lane (call svo_pipeline_group_set_keyframe_clouds first)");
   return svo_kfc_set_lr_check(g->kfc, params);
+}
+
+extern "C" int svo_pipeline_group_set_keyframe_sgm(svo_pipeline_group* g, const svo_sgm_params* params) {
+  if (!g) return SVO_ERR_INVALID;
+  SVO_HIP_CHECK(g->ctx, hipSetDevice(g->ctx->device));
+  SVO_REQUIRE(g->ctx, g->kfc, "pipeline_group_set_keyframe_sgm: keyframe clouds are off on every lane (call svo_pipeline_group_set_keyframe_clouds first)");
+  return svo_kfc_set_sgm(g->kfc, params);
 }
 
 extern "C" int svo_pipeline_group_keyframe_clouds(svo_pipeline_group* g, int* n, const svo_keyframe_cloud** table) {

@@ -912,6 +912,10 @@ extern "C" int svo_pipeline_set_keyframe_clouds(svo_pipeline* p, const svo_cloud
       const int rs = svo_kfc_set_lr_check(k, svo_kfc_lr_check(p->kfc));
       if (rs) { svo_kfc_destroy(k); return rs; }
     }
+    if (p->kfc && svo_kfc_sgm(p->kfc)) {  // and semi-global matching
+      const int rs = svo_kfc_set_sgm(k, svo_kfc_sgm(p->kfc));
+      if (rs) { svo_kfc_destroy(k); return rs; }
+    }
   }
   svo_kfc_destroy(p->kfc);
   p->kfc = k;
@@ -930,6 +934,13 @@ extern "C" int svo_pipeline_set_keyframe_lr_check(svo_pipeline* p, const svo_lr_
   p->adjuster->wait();
   SVO_REQUIRE(p->ctx, p->kfc, "pipeline_set_keyframe_lr_check: keyframe clouds are off (call svo_pipeline_set_keyframe_clouds first)");
   return svo_kfc_set_lr_check(p->kfc, params);
+}
+
+extern "C" int svo_pipeline_set_keyframe_sgm(svo_pipeline* p, const svo_sgm_params* params) {
+  if (!p) return SVO_ERR_INVALID;
+  p->adjuster->wait();
+  SVO_REQUIRE(p->ctx, p->kfc, "pipeline_set_keyframe_sgm: keyframe clouds are off (call svo_pipeline_set_keyframe_clouds first)");
+  return svo_kfc_set_sgm(p->kfc, params);
 }
 
 extern "C" int svo_pipeline_keyframe_clouds(svo_pipeline* p, int* n, const svo_keyframe_cloud** table) {

@@ -12,9 +12,12 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
   4. left-right check: the cost form of the fused launch (svo_stereo_bm_cost_batch_dev, which also writes the winner's SAD) per
      pair beside the plain form, and the one launch of svo_disparity_lr_check_batch_dev per pair on that map and cost,
      max_diff16 16, beside the copy rate of the same run;
-  5. cost to the VO: bench.py's headline load (96 lanes in 3 pipeline groups of 16-frame steps) without keyframe clouds, with
-     clouds at step 4, with clouds and the speckle filter, and with clouds and the left-right check, alternating, as frames/s,
-     their ratios and the spread over the rounds.
+  5. semi-global matching: the launch sequence of svo_stereo_sgm_batch_dev (fill, cost volume, four paths; defaults, with the cost
+     form) per pair beside the plain fused launch in alternating blocks, its bytes counted from the code against the
+     copy rate of the same run;
+  6. cost to the VO: bench.py's headline load (96 lanes in 3 pipeline groups of 16-frame steps) without keyframe clouds, with
+     clouds at step 4, with clouds and the speckle filter, with clouds and the left-right check, and with clouds from semi-global
+     matching, alternating, as frames/s, their ratios and the spread over the rounds.
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -143,6 +146,33 @@ def standalone(S, torch, batch, warmup, reps):
                "valid_per_pair": float((dm2 != -16).sum().item()) / batch, "budget_bytes_per_pair": nbytes, "bytes_per_s": nbytes / per,
                "share_of_copy_rate": nbytes / per / copy, "ratio_to_fused_dense": 1e3 * per / lr["plain_ms_per_pair"], "calls_timed": k})
     out["lr_check"] = lr
+    # semi-global matching: the whole sequence as one bracket, alternating with the plain fused launch
+    sp = api.sgm_default_params(BLOCK)
+    need = api.sgm_workspace_bytes(W, H, NDISP, BLOCK, batch)
+    del ws
+    sws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+
+    def sgm():
+        ctx.stereo_sgm_batch(dl.data_ptr(), dr.data_ptr(), batch, W, H, W, W * H, sp, sws.data_ptr(), need, dm2.data_ptr(), dc.data_ptr(), NDISP, BLOCK)
+
+    plain_ms, sgm_ms = [], []
+    for _ in range(3):
+        ms, k = timed("stereo_dense_batch", fused, reps)
+        plain_ms.append(ms / k / batch)
+        ms, k = timed("stereo_sgm", sgm, reps)
+        sgm_ms.append(ms / k / batch)
+    ctx.sync()
+    rect = (W - BLOCK - NDISP + 2) * (H - BLOCK + 1)
+    # the volume written once (2 B) and read by each path (4 x 2 B), the sums written by three paths and read by three
+    # (6 x 4 B) per (pixel, disparity); the texture sum written and read; both images read; map and cost filled and written
+    nbytes = 34 * rect * NDISP + 4 * rect + 2 * W * H + 4 * W * H + 4 * rect
+    per = float(np.median(sgm_ms)) * 1e-3
+    out["sgm"] = {"p1": sp.p1, "p2": sp.p2, "plain_ms_per_pair": float(np.median(plain_ms)), "sgm_ms_per_pair": 1e3 * per,
+                  "all_plain_ms": plain_ms, "all_sgm_ms": sgm_ms, "sequences_per_block": reps, "ratio_to_fused_dense": 1e3 * per / float(np.median(plain_ms)),
+                  "workspace_bytes_per_pair": need / batch, "bytes_per_pair": nbytes, "bound_ms_per_pair": 1e3 * nbytes / copy,
+                  "bytes_per_s": nbytes / per, "share_of_copy_rate": nbytes / per / copy,
+                  "valid_per_pair_sgm": float((dm2 != -16).sum().item()) / batch, "valid_per_pair_bm": float((dm != -16).sum().item()) / batch}
     ctx.close()
     return out
 
@@ -167,12 +197,13 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
         pipe.ctx._chk(pipe.L.svo_pipeline_group_keyframe_clouds(pipe.h, C.byref(n), C.byref(tab)), "svo_pipeline_group_keyframe_clouds")
         return n.value
 
-    def timed(on, speckle=False, lr=False):
+    def timed(on, speckle=False, lr=False, sgm=False):
         for g in groups:
             g.pipe.set_keyframe_clouds(-1, prm if on else None)
             if on:
                 g.pipe.set_keyframe_speckle_filter(SPECKLE_SIZES[0] if speckle else None, SPECKLE_DIFF)
                 g.pipe.set_keyframe_lr_check(LR_DIFF if lr else None)
+                g.pipe.set_keyframe_sgm(on=sgm)
             g.clear_counters()
         run(warmup)
         torch.cuda.synchronize()
@@ -183,12 +214,13 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
         kf = sum(table_len(g.pipe) for g in groups) if on else 0  # of the last step
         return lanes * frames * steps / dt, 1e3 * dt / steps, kf
 
-    plain, cloud, filt, chk = [], [], [], []
+    plain, cloud, filt, chk, sg = [], [], [], [], []
     for _ in range(rounds):  # alternating: other people's work shares the host
         plain.append(timed(False))
         cloud.append(timed(True))
         filt.append(timed(True, True))
         chk.append(timed(True, False, True))
+        sg.append(timed(True, sgm=True))
     for g in groups:
         g.close()
     med = lambda xs: float(np.median(xs))
@@ -202,7 +234,15 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
             "ratio_speckle_to_clouds": ff / fc, "step_ms_clouds_speckle": med([x[1] for x in filt]), "all_clouds_speckle": [x[0] for x in filt],
             "lr_max_diff16": LR_DIFF, "frames_per_s_clouds_lr_check": fl, "ratio_lr_check_to_clouds": fl / fc,
             "step_ms_clouds_lr_check": med([x[1] for x in chk]), "all_clouds_lr_check": [x[0] for x in chk],
-            "round_ratios_lr_check_to_clouds": [b[0] / a[0] for a, b in zip(cloud, chk)]}
+            "round_ratios_lr_check_to_clouds": [b[0] / a[0] for a, b in zip(cloud, chk)],
+            "frames_per_s_clouds_sgm": med([x[0] for x in sg]), "ratio_sgm_to_clouds": med([x[0] for x in sg]) / fc,
+            "step_ms_clouds_sgm": med([x[1] for x in sg]), "all_clouds_sgm": [x[0] for x in sg],
+            "round_ratios_sgm_to_clouds": [b[0] / a[0] for a, b in zip(cloud, sg)]}
+
+
+def api_sub():
+    from stereo_vo_amd import api
+    return api.SGM_KEYFRAME_SUB_BATCH
 
 
 def main():
@@ -255,6 +295,13 @@ def main():
                     f"  the check (one launch): {1e3 * c['check_ms_per_pair']:.1f} us per pair (mean of {c['calls_timed']} calls of {s['batch']} maps), "
                     f"{c['removed_per_pair']:.0f} of {c['valid_per_pair']:.0f} valid pixels removed per pair; {c['ratio_to_fused_dense']:.3f} x the fused dense launch; "
                     f"4 A = {c['budget_bytes_per_pair'] / 1e6:.3f} MB per pair -> {c['bytes_per_s'] / 1e12:.3f} TB/s ({100 * c['share_of_copy_rate']:.1f} % of hbm_copy, same run)\n")
+            c = s["sgm"]
+            f.write(f"semi-global matching, p1 {c['p1']}, p2 {c['p2']} (fill + volume + four paths, with the cost form): {c['sgm_ms_per_pair']:.4f} ms per pair beside the plain "
+                    f"fused dense launch {c['plain_ms_per_pair']:.4f} (medians of 3 alternating blocks of {c['sequences_per_block']}; plain "
+                    f"{[round(x, 4) for x in c['all_plain_ms']]}, sgm {[round(x, 4) for x in c['all_sgm_ms']]}): {c['ratio_to_fused_dense']:.2f} x the fused dense launch\n"
+                    f"  bytes counted from the code: {c['bytes_per_pair'] / 1e6:.1f} MB per pair (work space {c['workspace_bytes_per_pair'] / 1e6:.1f} MB per pair) -> "
+                    f"{c['bytes_per_s'] / 1e12:.3f} TB/s = {100 * c['share_of_copy_rate']:.1f} % of hbm_copy, same run (the byte bound is {c['bound_ms_per_pair']:.4f} ms per pair); "
+                    f"valid pixels per pair {c['valid_per_pair_sgm']:.0f} against block matching's {c['valid_per_pair_bm']:.0f}\n")
             if g:
                 f.write(f"{g['lanes']} lanes in {g['groups']} groups, {g['frames_per_step_per_lane']}-frame steps, median of {g['rounds']} alternating rounds of "
                         f"{g['steps']} steps, clouds at step {g['cloud_step']}:\n  without clouds {g['frames_per_s_plain']:.0f} frames/s ({g['step_ms_plain']:.1f} ms / step), "
@@ -266,7 +313,10 @@ def main():
                         f"{g['ratio_speckle_to_clouds']:.3f}; rounds: {[round(x) for x in g['all_clouds_speckle']]}\n"
                         f"  with clouds and the left-right check (max_diff16 {g['lr_max_diff16']}): {g['frames_per_s_clouds_lr_check']:.0f} frames/s "
                         f"({g['step_ms_clouds_lr_check']:.1f} ms / step): ratio to clouds alone {g['ratio_lr_check_to_clouds']:.3f}; rounds: "
-                        f"{[round(x) for x in g['all_clouds_lr_check']]}; per round {[round(x, 3) for x in g['round_ratios_lr_check_to_clouds']]}\n")
+                        f"{[round(x) for x in g['all_clouds_lr_check']]}; per round {[round(x, 3) for x in g['round_ratios_lr_check_to_clouds']]}\n"
+                        f"  with clouds from semi-global matching (defaults, sub-batches of {api_sub()} keyframes): {g['frames_per_s_clouds_sgm']:.0f} frames/s "
+                        f"({g['step_ms_clouds_sgm']:.1f} ms / step): ratio to clouds alone {g['ratio_sgm_to_clouds']:.3f}; rounds: "
+                        f"{[round(x) for x in g['all_clouds_sgm']]}; per round {[round(x, 3) for x in g['round_ratios_sgm_to_clouds']]}\n")
 
 
 if __name__ == "__main__":
