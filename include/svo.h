@@ -96,7 +96,8 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * "rectify_remap", "stereo_bm" (the three launches of svo_stereo_bm as one bracket), "stereo_dense_batch",
  * "cloud" (the count, scan and write launches of one svo_disparity_cloud_batch_dev as one bracket),
  * "speckle" (the launches of one speckle filter call as one bracket), "lr_check" (one left-right check call),
- * "stereo_sgm" (the launches of one semi-global matching call as one bracket);
+ * "stereo_sgm" (the launches of one semi-global matching call as one bracket), "voxel_insert" (one svo_voxel_map_insert_dev),
+ * "voxel_extract" (one svo_voxel_map_extract_dev: the counts' memset and the launch);
  * NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
@@ -343,6 +344,85 @@ int svo_stereo_sgm_batch_dev(svo_ctx* ctx, const uint8_t* left, const uint8_t* r
 /* One pair, HOST pointers, synchronous; the work space is allocated and freed by the call.  cost16: width*height or NULL. */
 int svo_stereo_sgm(svo_ctx* ctx, const uint8_t* left, const uint8_t* right, int width, int height, int row_stride,
                    int num_disparities, int block_size, const svo_sgm_params* params, int16_t* disp16, uint16_t* cost16);
+
+/* ---------------------------------------------------------------- voxel map --
+ * A device-resident sparse voxel grid: clouds (svo_cloud_point records on the device, in a camera frame) are fused into ONE
+ * deduplicated world-frame map under a camera->world transform, keyframe by keyframe, and the occupied voxels come back as a
+ * point list of the same record type (no reference counterpart; this is the project's own statement).  Every quantity is exact:
+ * integers, or f64 operations in the stated order without contraction.
+ *   Transform.  m12: 3 x 4 row-major f64 camera->world, 12 HOST doubles, passed to the kernel by value.
+ *   Per record p = {x, y, z, tag}:
+ *   1. Rejected iff !(p.z > 0.0f), or max_depth > 0 && p.z > max_depth (f32 comparisons on the camera-frame z; a NaN z fails the
+ *      first test).
+ *   2. For r = 0, 1, 2: w_r = m[r][0]*(double)x + m[r][1]*(double)y + m[r][2]*(double)z + m[r][3], f64 products summed left to
+ *      right; q_r = w_r / (double)voxel_size.  Rejected iff any q_r fails q_r >= -1048576.0 && q_r < 1048576.0 (NaN, infinity,
+ *      out of range).
+ *   3. k_r = floor(q_r); key = (k_0 + 2^20) | (k_1 + 2^20) << 21 | (k_2 + 2^20) << 42, below 2^63, so EMPTY = ~0 is never a key.
+ *      f_r = min((uint64)floor((q_r - k_r) * 65536.0), 65535) (the min matters: for a tiny negative q, q - floor(q) rounds to 1.0).
+ *   4. Payload added to the voxel, four u64 words: ci += (1 << 40) | (tag >> 24) (count in bits 40..63, intensity sum in bits
+ *      0..39); sx += f_0; sy += f_1; sz += f_2.  A voxel therefore holds at most 2^24 - 1 points: the CALLER's bound, not checked.
+ *   Table.  Structure of arrays, cap = 2^capacity_log2 slots: keys[cap] u64, then ci, sx, sy, sz, each [cap] u64 (40 bytes per
+ *      slot, 168 MB at the default).  Home slot h = fmix64(key) & (cap - 1) with fmix64(k): k ^= k >> 33; k *= 0xff51afd7ed558ccd;
+ *      k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53; k ^= k >> 33.  Linear probing, at most SVO_VOXEL_MAX_PROBES probes, each a 64-bit
+ *      atomic compare-and-swap of keys[h] from EMPTY to key whose RETURN value decides (EMPTY: claimed; key: found; anything else:
+ *      next slot).  After SVO_VOXEL_MAX_PROBES foreign slots the record is dropped and counted: a full table costs a bounded time.
+ *      The bound is part of the contract.
+ *   Counters.  n_voxels (slots claimed), n_inserted, n_rejected, n_dropped (points); inserted + rejected + dropped = records given.
+ *   Order independence.  While n_dropped == 0 the occupied slot set and every voxel's payload depend on no thread order (the set
+ *      of cells occupied under linear probing does not depend on insertion order; integer sums commute); WHICH slot a key sits in
+ *      is not defined.  Once n_dropped > 0 only this holds: every stored key is a key of some given record, every payload word is
+ *      at most the true one, n_voxels is the number of stored keys, and the counter identity above.
+ *   Extraction.  Every slot with key != EMPTY and count >= min_count becomes one svo_cloud_point: with c = (double)count,
+ *      x = (float)(((double)k_0 + (double)sx / (c * 65536.0)) * (double)voxel_size), likewise y, z (the mean position inside the
+ *      voxel); tag = count | (isum / count) << 24 (integer division; the count fits 24 bits by the bound above).  The output order
+ *      is not defined.  counts = {n_total, n_stored = min(n_total, max_points)}; records behind n_stored are not written.
+ *   Synchronisation.  Relaxed device-scope atomics only; no fence, no waiting on another workgroup or launch; everything on
+ *      svo_stream(ctx), ordered by launch. */
+typedef struct svo_voxel_map_params {
+  float voxel_size;   /* finite, > 0; the units of the clouds (the baseline's) */
+  int capacity_log2;  /* 8..28 */
+  float max_depth;    /* <= 0: no bound on the camera-frame z */
+} svo_voxel_map_params;
+#define SVO_VOXEL_MAX_PROBES 64
+typedef struct svo_voxel_map svo_voxel_map;
+typedef struct svo_voxel_map_stats_t {
+  uint64_t n_voxels, n_inserted, n_rejected, n_dropped;
+} svo_voxel_map_stats_t;
+/* voxel_size 0.1, capacity_log2 22, max_depth 0. */
+int svo_voxel_map_default_params(svo_voxel_map_params* params);
+/* Bytes of the table (what svo_voxel_map_download copies): 40 << capacity_log2.  Pure; SVO_ERR_INVALID and *bytes = 0 for
+ * parameters svo_voxel_map_create refuses. */
+int svo_voxel_map_bytes(const svo_voxel_map_params* params, size_t* bytes);
+/* Allocates the table and clears it.  The map uses ctx's device and stream and must be destroyed before ctx. */
+int svo_voxel_map_create(svo_ctx* ctx, const svo_voxel_map_params* params, svo_voxel_map** out);
+void svo_voxel_map_destroy(svo_voxel_map* map);
+/* Keys to EMPTY, payload and counters to 0; asynchronous. */
+int svo_voxel_map_clear(svo_voxel_map* map);
+/* n records at the DEVICE pointer `points` (4-byte aligned) inserted under m12; asynchronous, one launch.  n == 0 is a no-op. */
+int svo_voxel_map_insert_dev(svo_voxel_map* map, const svo_cloud_point* points, int n, const double* m12);
+/* pose7 = [qw qx qy qz tx ty tz], "world with respect to camera", X_cam = R(q) X_world + t (src/bundle_adjuster.hpp:50,
+ * src/reprojection_factor.cpp:24-33) -> m12 = [R^T | -R^T t], i.e. X_world = R(q)^T (X_cam - t).  With s = 2 / (qw^2 + qx^2 +
+ * qy^2 + qz^2) (so q need not be a unit quaternion):
+ *   R = [1 - s(qy^2 + qz^2), s(qx qy - qw qz), s(qx qz + qw qy);
+ *        s(qx qy + qw qz), 1 - s(qx^2 + qz^2), s(qy qz - qw qx);
+ *        s(qx qz - qw qy), s(qy qz + qw qx), 1 - s(qx^2 + qy^2)],
+ * m12[r][c] = R[c][r], m12[r][3] = -(R[0][r] t_0 + R[1][r] t_1 + R[2][r] t_2).  Pure host arithmetic (a zero quaternion gives
+ * non-finite entries, under which every record is rejected). */
+int svo_pose7_to_cam_to_world(const double* pose7, double* m12);
+/* svo_pose7_to_cam_to_world, then svo_voxel_map_insert_dev. */
+int svo_voxel_map_insert_pose7_dev(svo_voxel_map* map, const svo_cloud_point* points, int n, const double* pose7);
+/* The four counters; synchronises the stream. */
+int svo_voxel_map_stats(svo_voxel_map* map, svo_voxel_map_stats_t* stats);
+/* Extraction into DEVICE memory, asynchronous: points: max_points records (may be NULL when max_points == 0); counts: 2 device
+ * ints, zeroed on the stream before the launch.  min_count >= 1, max_points >= 0. */
+int svo_voxel_map_extract_dev(svo_voxel_map* map, int min_count, svo_cloud_point* points, int max_points, int* counts);
+/* Extraction into HOST memory, synchronous; points: `capacity` records (may be NULL when capacity == 0, which only counts). */
+int svo_voxel_map_extract(svo_voxel_map* map, int min_count, svo_cloud_point* points, int capacity, int* n_total, int* n_stored);
+/* Synchronous copy of the table in the layout above (keys, ci, sx, sy, sz); bytes >= svo_voxel_map_bytes.  What a caller
+ * persists, and what gives the exact sums.  There is no upload.
+ * Every entry above refuses a null pointer, bad parameters, n < 0, min_count < 1, max_points < 0 or a short download buffer with
+ * SVO_ERR_INVALID and a message naming the argument (svo_last_error of the map's context); a refused call launches nothing. */
+int svo_voxel_map_download(svo_voxel_map* map, void* host, size_t bytes);
 
 /* ------------------------------------------------------------------- a8 --
  * ImageProcessor::triangulate_stereo's reprojection loop

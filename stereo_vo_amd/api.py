@@ -132,6 +132,46 @@ def _sgm_params(p1, p2, block=21):
     if p2 is not None:
         prm.p2 = int(p2)
     return prm
+
+
+class VoxelMapParams(C.Structure):
+    """svo_voxel_map_params: voxel edge (finite, > 0), table of 2^capacity_log2 slots (8..28), max_depth <= 0 = no depth bound."""
+    _fields_ = [("voxel_size", C.c_float), ("capacity_log2", C.c_int), ("max_depth", C.c_float)]
+
+
+class VoxelMapStats(C.Structure):
+    """svo_voxel_map_stats_t: slots claimed, and points inserted / rejected / dropped."""
+    _fields_ = [("n_voxels", C.c_uint64), ("n_inserted", C.c_uint64), ("n_rejected", C.c_uint64), ("n_dropped", C.c_uint64)]
+
+
+VOXEL_MAX_PROBES = 64  # SVO_VOXEL_MAX_PROBES
+
+
+def voxel_map_default_params():
+    """svo_voxel_map_default_params: voxel_size 0.1, capacity_log2 22, max_depth 0."""
+    p = VoxelMapParams()
+    if lib().svo_voxel_map_default_params(C.byref(p)) != 0:
+        raise SvoError("svo_voxel_map_default_params failed")
+    return p
+
+
+def voxel_map_bytes(params):
+    """svo_voxel_map_bytes: bytes of the table, 40 per slot (no GPU involved); raises for parameters the map refuses."""
+    n = C.c_size_t(0)
+    if lib().svo_voxel_map_bytes(C.byref(params), C.byref(n)) != 0:
+        raise SvoError("svo_voxel_map_bytes: voxel_size must be finite and > 0, capacity_log2 in 8..28")
+    return int(n.value)
+
+
+def pose7_to_cam_to_world(pose7):
+    """svo_pose7_to_cam_to_world: [qw qx qy qz tx ty tz] (X_cam = R(q) X_world + t) -> the (3, 4) f64 camera->world matrix [R^T | -R^T t]."""
+    q = _f64(pose7).reshape(7)
+    m = np.empty((3, 4), np.float64)
+    if lib().svo_pose7_to_cam_to_world(_p(q), _p(m)) != 0:
+        raise SvoError("svo_pose7_to_cam_to_world failed")
+    return m
+
+
 SPECKLE_TILE = (64, 16)  # SVO_SPECKLE_TILE_W, SVO_SPECKLE_TILE_H
 
 
@@ -300,6 +340,9 @@ SYMBOLS = [
     "svo_pipeline_set_keyframe_lr_check", "svo_pipeline_group_set_keyframe_lr_check",
     "svo_sgm_default_params", "svo_sgm_workspace_bytes", "svo_stereo_sgm_batch_dev", "svo_stereo_sgm",
     "svo_pipeline_set_keyframe_sgm", "svo_pipeline_group_set_keyframe_sgm",
+    "svo_voxel_map_default_params", "svo_voxel_map_bytes", "svo_voxel_map_create", "svo_voxel_map_destroy", "svo_voxel_map_clear",
+    "svo_voxel_map_insert_dev", "svo_pose7_to_cam_to_world", "svo_voxel_map_insert_pose7_dev", "svo_voxel_map_stats",
+    "svo_voxel_map_extract_dev", "svo_voxel_map_extract", "svo_voxel_map_download",
 ]
 
 
@@ -363,6 +406,24 @@ def lib():
         L.svo_pipeline_group_set_keyframe_sgm.argtypes = [vp, vp]
         for f in ("svo_sgm_default_params", "svo_stereo_sgm_batch_dev", "svo_stereo_sgm", "svo_pipeline_set_keyframe_sgm",
                   "svo_pipeline_group_set_keyframe_sgm"):
+            getattr(L, f).restype = ci
+        # voxel map
+        L.svo_voxel_map_default_params.argtypes = [vp]
+        L.svo_voxel_map_bytes.argtypes = [vp, vp]
+        L.svo_voxel_map_create.argtypes = [vp, vp, vp]
+        L.svo_voxel_map_destroy.argtypes = [vp]
+        L.svo_voxel_map_destroy.restype = None
+        L.svo_voxel_map_clear.argtypes = [vp]
+        L.svo_voxel_map_insert_dev.argtypes = [vp, vp, ci, vp]
+        L.svo_pose7_to_cam_to_world.argtypes = [vp, vp]
+        L.svo_voxel_map_insert_pose7_dev.argtypes = [vp, vp, ci, vp]
+        L.svo_voxel_map_stats.argtypes = [vp, vp]
+        L.svo_voxel_map_extract_dev.argtypes = [vp, ci, vp, ci, vp]
+        L.svo_voxel_map_extract.argtypes = [vp, ci, vp, ci, vp, vp]
+        L.svo_voxel_map_download.argtypes = [vp, vp, sz]
+        for f in ("svo_voxel_map_default_params", "svo_voxel_map_bytes", "svo_voxel_map_create", "svo_voxel_map_clear",
+                  "svo_voxel_map_insert_dev", "svo_pose7_to_cam_to_world", "svo_voxel_map_insert_pose7_dev", "svo_voxel_map_stats",
+                  "svo_voxel_map_extract_dev", "svo_voxel_map_extract", "svo_voxel_map_download"):
             getattr(L, f).restype = ci
         _LIB = L
     return _LIB
@@ -712,6 +773,89 @@ class Context:
                                         C.c_float(cy), _p(rv), _p(tv), iterations, C.c_float(reproj_err),
                                         C.c_double(confidence), _p(inl), C.byref(m)), "svo_pnp_ransac")
         return rv, tv, inl[:m.value].copy()
+
+
+class VoxelMap:
+    """svo_voxel_map: a device-resident sparse voxel grid that fuses clouds into one world-frame map (include/svo.h, "voxel map").
+    Close it before its context."""
+
+    def __init__(self, ctx, params=None, voxel_size=None, capacity_log2=None, max_depth=None):
+        self.ctx, self.L = ctx, ctx.L
+        prm = voxel_map_default_params() if params is None else VoxelMapParams(params.voxel_size, params.capacity_log2, params.max_depth)
+        if voxel_size is not None:
+            prm.voxel_size = float(voxel_size)
+        if capacity_log2 is not None:
+            prm.capacity_log2 = int(capacity_log2)
+        if max_depth is not None:
+            prm.max_depth = float(max_depth)
+        self.params = prm
+        self.h = C.c_void_p()
+        ctx._chk(self.L.svo_voxel_map_create(ctx.h, C.byref(prm), C.byref(self.h)), "svo_voxel_map_create")
+        self.capacity = 1 << prm.capacity_log2
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:  # a map that outlived its context cannot be destroyed any more (its table went with the device memory)
+                self.L.svo_voxel_map_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clear(self):
+        self.ctx._chk(self.L.svo_voxel_map_clear(self.h), "svo_voxel_map_clear")
+
+    def insert(self, dev_ptr, n, m12=None, pose7=None):
+        """n CLOUD_POINT_DTYPE records at the device pointer (an int) under m12 (3 x 4 camera->world) or pose7, exactly one of them.
+        Asynchronous on the context's stream."""
+        if (m12 is None) == (pose7 is None):
+            raise ValueError("VoxelMap.insert: give exactly one of m12 and pose7")
+        if m12 is not None:
+            m = _f64(m12).reshape(12)
+            self.ctx._chk(self.L.svo_voxel_map_insert_dev(self.h, dev_ptr, int(n), _p(m)), "svo_voxel_map_insert_dev")
+        else:
+            q = _f64(pose7).reshape(7)
+            self.ctx._chk(self.L.svo_voxel_map_insert_pose7_dev(self.h, dev_ptr, int(n), _p(q)), "svo_voxel_map_insert_pose7_dev")
+
+    def insert_keyframe_clouds(self, table, poses7):
+        """The list Pipeline.keyframe_clouds() / PipelineGroup.keyframe_clouds() returns, one pose7 per entry: every entry's device
+        cloud is inserted from its "dev" pointer (no host copy).  Call before the next process call replaces the clouds."""
+        if len(table) != len(poses7):
+            raise ValueError("VoxelMap.insert_keyframe_clouds: one pose7 per table entry")
+        for e, q in zip(table, poses7):
+            self.insert(e["dev"], e["n_stored"], pose7=q)
+
+    def stats(self):
+        """The four counters as a dict (synchronises)."""
+        s = VoxelMapStats()
+        self.ctx._chk(self.L.svo_voxel_map_stats(self.h, C.byref(s)), "svo_voxel_map_stats")
+        return {"n_voxels": int(s.n_voxels), "n_inserted": int(s.n_inserted), "n_rejected": int(s.n_rejected), "n_dropped": int(s.n_dropped)}
+
+    def extract_dev(self, min_count, points_ptr, max_points, counts_ptr):
+        """svo_voxel_map_extract_dev: raw device pointers (ints); counts_ptr: 2 int32 {n_total, n_stored}.  Asynchronous."""
+        self.ctx._chk(self.L.svo_voxel_map_extract_dev(self.h, int(min_count), points_ptr, int(max_points), counts_ptr),
+                      "svo_voxel_map_extract_dev")
+
+    def extract(self, min_count=1, max_points=None):
+        """(points as a CLOUD_POINT_DTYPE array of n_stored records in no defined order, n_total).  max_points None: all of them."""
+        nt, ns = C.c_int(0), C.c_int(0)
+        if max_points is None:  # count first: the table may be far larger than the map
+            self.ctx._chk(self.L.svo_voxel_map_extract(self.h, int(min_count), None, 0, C.byref(nt), C.byref(ns)), "svo_voxel_map_extract")
+            max_points = nt.value
+        pts = np.empty(max(int(max_points), 1), CLOUD_POINT_DTYPE)
+        self.ctx._chk(self.L.svo_voxel_map_extract(self.h, int(min_count), _p(pts), int(max_points), C.byref(nt), C.byref(ns)),
+                      "svo_voxel_map_extract")
+        return pts[:ns.value].copy(), nt.value
+
+    def download(self):
+        """The table as a dict of numpy uint64 arrays of `capacity` entries: "keys" (EMPTY = 2^64 - 1), "ci" (count << 40 | intensity
+        sum), "sx", "sy", "sz"."""
+        buf = np.empty((5, self.capacity), np.uint64)
+        self.ctx._chk(self.L.svo_voxel_map_download(self.h, _p(buf), buf.nbytes), "svo_voxel_map_download")
+        return {k: buf[i] for i, k in enumerate(("keys", "ci", "sx", "sy", "sz"))}
 
 
 class BA:

@@ -1,0 +1,394 @@
+// Voxel map (include/svo.h, "voxel map"): a sparse voxel grid in HBM, an open-addressing hash table into which clouds of
+// svo_cloud_point records are fused under a camera->world transform, and from which the occupied voxels come back as a point list.
+//
+//   voxel_insert_kernel  : one thread per record, 256-thread workgroups.  Key and payload per record in f64 / integers exactly as
+//                          the header states.  Clouds are in raster order, so neighbouring lanes very often fall into one voxel and
+//                          same-address atomics would serialise: the runs of equal keys inside a wavefront are summed into their
+//                          first lane (a segmented sum, see below) and only those run heads probe (64-bit atomicCAS on keys[],
+//                          linear, at most SVO_VOXEL_MAX_PROBES slots) and issue the four atomicAdds.  Integer sums commute, so the
+//                          table is the same with or without the merge.  The four counters get one atomicAdd per workgroup each.
+//   voxel_extract_kernel : VX_ITEMS * 256 slots per workgroup; svo_compact_slot inside the workgroup, one returning atomicAdd per
+//                          workgroup for its base in the output (whose order is free), one for its share of n_stored.
+//
+// Nothing passes between workgroups except order-independent relaxed device-scope atomics (docs/HISTORY.md, "No cache maintenance
+// inside kernels"): no fence, no acquire / release, no waiting.  The CAS's RETURN value decides a probe, never a plain load; the
+// payload words are only ever added to, and are read by a LATER launch on the same stream (extraction, download).  A full table
+// costs at most 64 probes per run head: bounded work, no spinning.
+#include "kernels.h"
+#include "tail_device.h"
+
+namespace {
+typedef unsigned long long u64;
+constexpr int VX_T = 256;
+constexpr int VX_ITEMS = 8;  // slots per thread of the extraction
+constexpr u64 VX_EMPTY = ~0ull;
+constexpr double VX_LIMIT = 1048576.0;  // 2^20 voxels either side of the origin per axis
+
+struct VoxelTable {
+  u64 *keys, *ci, *sx, *sy, *sz;  // cap each (the download's layout, in this order)
+  u64* counters;                  // n_voxels, n_inserted, n_rejected, n_dropped
+  u64 mask;                       // cap - 1
+};
+
+struct VoxelInsertArgs {
+  const svo_cloud_point* pts;
+  int n;
+  double m[12];
+  float voxel_size, max_depth;
+  VoxelTable t;
+};
+
+struct VoxelExtractArgs {
+  VoxelTable t;
+  unsigned min_count;
+  float voxel_size;
+  svo_cloud_point* out;
+  int max_points;
+  int* counts;  // {n_total, n_stored}, zeroed on the stream before the launch
+};
+
+__host__ __device__ __forceinline__ u64 vx_fmix64(u64 k) {
+  k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
+  k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
+  k ^= k >> 33;
+  return k;
+}
+}  // namespace
+
+struct svo_voxel_map {
+  svo_ctx* ctx = nullptr;
+  svo_voxel_map_params prm{};
+  size_t cap = 0;
+  u64* d_mem = nullptr;  // keys | ci | sx | sy | sz | 4 counters | 2 ints of the synchronous extraction
+  VoxelTable t{};
+  int* d_counts = nullptr;
+};
+
+__global__ __launch_bounds__(VX_T) void voxel_insert_kernel(VoxelInsertArgs a) {
+  __shared__ unsigned sC[4][VX_T / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t i = (size_t)blockIdx.x * VX_T + (size_t)tid;
+  const bool valid = i < (size_t)a.n;
+  u64 key = VX_EMPTY;
+  unsigned ci = 0, fx = 0, fy = 0, fz = 0;  // ci of one record: count << 16 | intensity (a run of 64 sums to < 2^23 | 2^14)
+  if (valid) {
+    const svo_cloud_point p = a.pts[i];  // one 16-byte load (global memory takes it at 4-byte alignment)
+    const float x = p.x, y = p.y, z = p.z;
+    const unsigned tag = p.tag;
+    if (z > 0.0f && !(a.max_depth > 0.0f && z > a.max_depth)) {
+      const double xd = (double)x, yd = (double)y, zd = (double)z, vs = (double)a.voxel_size;
+      double q[3];
+      bool in = true;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const double w = a.m[4 * r] * xd + a.m[4 * r + 1] * yd + a.m[4 * r + 2] * zd + a.m[4 * r + 3];
+        q[r] = w / vs;
+        in = in && q[r] >= -VX_LIMIT && q[r] < VX_LIMIT;
+      }
+      if (in) {
+        u64 k[3];
+        unsigned f[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          const double fl = floor(q[r]);
+          k[r] = (u64)((long long)fl + (1ll << 20));
+          const u64 fr = (u64)floor((q[r] - fl) * 65536.0);
+          f[r] = (unsigned)(fr < 65535ull ? fr : 65535ull);
+        }
+        key = k[0] | (k[1] << 21) | (k[2] << 42);
+        ci = (1u << 16) | (tag >> 24);
+        fx = f[0]; fy = f[1]; fz = f[2];
+      }
+    }
+  }
+  // run heads: lane 0, or a key other than the lane before's (rejected records carry EMPTY: they form runs too and never probe)
+  const u64 prev = __shfl_up(key, 1);
+  const bool head = lane == 0 || prev != key;
+  const u64 heads = __ballot(head);
+  // segmented sum: after the round with offset o a lane holds the sum over [lane, min(lane + 2 o, end of its run)); the rounds
+  // stop (wavefront-uniformly) once no lane has a partner inside its run, which is at once when nothing merges
+  const u64 after = lane == 63 ? 0ull : heads >> (lane + 1);
+  const int end = after ? lane + 1 + __builtin_ctzll(after) : 64;
+  for (int o = 1; o < 64; o <<= 1) {
+    const bool take = lane + o < end;
+    if (!__ballot(take)) break;
+    const unsigned c = __shfl_down(ci, o), sx = __shfl_down(fx, o), sy = __shfl_down(fy, o), sz = __shfl_down(fz, o);
+    if (take) { ci += c; fx += sx; fy += sy; fz += sz; }
+  }
+  bool claimed = false, dropped = false;
+  if (head && key != VX_EMPTY) {
+    u64 h = vx_fmix64(key) & a.t.mask;
+    bool found = false;
+    for (int p = 0; p < SVO_VOXEL_MAX_PROBES; ++p) {
+      u64 expected = VX_EMPTY;
+      __hip_atomic_compare_exchange_strong(&a.t.keys[h], &expected, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (expected == VX_EMPTY) { claimed = true; found = true; break; }
+      if (expected == key) { found = true; break; }
+      h = (h + 1) & a.t.mask;
+    }
+    if (found) {
+      __hip_atomic_fetch_add(&a.t.ci[h], ((u64)(ci >> 16) << 40) | (u64)(ci & 0xFFFFu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(&a.t.sx[h], (u64)fx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(&a.t.sy[h], (u64)fy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(&a.t.sz[h], (u64)fz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+      dropped = true;
+    }
+  }
+  // counters, in points: ballots only, except for the dropped points, which exist only once the table overflows
+  const unsigned n_valid = (unsigned)__popcll(__ballot(valid));
+  const unsigned n_rej = (unsigned)__popcll(__ballot(valid && key == VX_EMPTY));
+  const unsigned n_claim = (unsigned)__popcll(__ballot(claimed));
+  unsigned n_drop = 0;
+  if (__ballot(dropped)) {
+    n_drop = dropped ? ci >> 16 : 0u;
+    for (int o = 32; o > 0; o >>= 1) n_drop += __shfl_xor(n_drop, o);
+  }
+  if (lane == 0) {
+    sC[0][wave] = n_claim; sC[1][wave] = n_valid - n_rej - n_drop; sC[2][wave] = n_rej; sC[3][wave] = n_drop;
+  }
+  __syncthreads();
+  if (tid < 4) {
+    unsigned t = 0;
+    for (int w = 0; w < VX_T / 64; ++w) t += sC[tid][w];
+    if (t) __hip_atomic_fetch_add(&a.t.counters[tid], (u64)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+__global__ __launch_bounds__(VX_T) void voxel_extract_kernel(VoxelExtractArgs a) {
+  __shared__ int sW[VX_T / 64];
+  __shared__ int sBase;
+  const size_t cap = (size_t)a.t.mask + 1;
+  const size_t first = (size_t)blockIdx.x * (VX_T * VX_ITEMS) + (size_t)threadIdx.x;
+  int slot[VX_ITEMS];
+  u64 ci[VX_ITEMS];
+  int total = 0;
+#pragma unroll
+  for (int j = 0; j < VX_ITEMS; ++j) {
+    const size_t s = first + (size_t)j * VX_T;
+    bool keep = false;
+    ci[j] = 0;
+    if (s < cap && a.t.keys[s] != VX_EMPTY) {
+      ci[j] = a.t.ci[s];
+      keep = (ci[j] >> 40) >= (u64)a.min_count;
+    }
+    slot[j] = svo_compact_slot<VX_T>(keep, total, sW);
+  }
+  if (total == 0) return;  // workgroup-uniform
+  if (threadIdx.x == 0) {
+    const int base = __hip_atomic_fetch_add(&a.counts[0], total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // this workgroup's share of n_stored = min(n_total, max_points): the shares of all workgroups add up to it in any order
+    const int lo = min(base, a.max_points), hi = min(base + total, a.max_points);
+    if (hi > lo) __hip_atomic_fetch_add(&a.counts[1], hi - lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    sBase = base;
+  }
+  __syncthreads();
+  const int base = sBase;
+  const double vs = (double)a.voxel_size;
+#pragma unroll
+  for (int j = 0; j < VX_ITEMS; ++j) {
+    if (slot[j] < 0 || base + slot[j] >= a.max_points) continue;
+    const size_t s = first + (size_t)j * VX_T;
+    const u64 key = a.t.keys[s];
+    const u64 count = ci[j] >> 40, isum = ci[j] & ((1ull << 40) - 1ull);
+    const double c = (double)count * 65536.0;
+    const u64 sum[3] = {a.t.sx[s], a.t.sy[s], a.t.sz[s]};
+    float xyz[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const double k = (double)((long long)((key >> (21 * r)) & 0x1FFFFFull) - (1ll << 20));
+      xyz[r] = (float)((k + (double)sum[r] / c) * vs);
+    }
+    svo_cloud_point q;
+    q.x = xyz[0]; q.y = xyz[1]; q.z = xyz[2];
+    q.tag = (uint32_t)count | ((uint32_t)(isum / count) << 24);
+    a.out[(size_t)(base + slot[j])] = q;
+  }
+}
+
+// ----------------------------------------------------------------------------- host side
+static bool voxel_params_ok(const svo_voxel_map_params* p) {
+  return p && p->voxel_size > 0.0f && p->voxel_size <= 3.4028234663852886e38f &&  // finite and > 0 (a NaN fails the first test)
+         p->capacity_log2 >= 8 && p->capacity_log2 <= 28;
+}
+
+extern "C" int svo_voxel_map_default_params(svo_voxel_map_params* params) {
+  if (!params) return SVO_ERR_INVALID;
+  params->voxel_size = 0.1f;
+  params->capacity_log2 = 22;
+  params->max_depth = 0.0f;
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_map_bytes(const svo_voxel_map_params* params, size_t* bytes) {
+  if (!bytes) return SVO_ERR_INVALID;
+  *bytes = 0;
+  if (!voxel_params_ok(params)) return SVO_ERR_INVALID;
+  *bytes = (size_t)40 << params->capacity_log2;
+  return SVO_OK;
+}
+
+extern "C" int svo_pose7_to_cam_to_world(const double* pose7, double* m12) {
+  if (!pose7 || !m12) return SVO_ERR_INVALID;
+  const double w = pose7[0], x = pose7[1], y = pose7[2], z = pose7[3];
+  const double s = 2.0 / (w * w + x * x + y * y + z * z);
+  const double R[9] = {1.0 - s * (y * y + z * z), s * (x * y - w * z), s * (x * z + w * y),
+                       s * (x * y + w * z), 1.0 - s * (x * x + z * z), s * (y * z - w * x),
+                       s * (x * z - w * y), s * (y * z + w * x), 1.0 - s * (x * x + y * y)};
+  const double* t = pose7 + 4;
+  for (int r = 0; r < 3; ++r) {  // [R^T | -R^T t]
+    for (int c = 0; c < 3; ++c) m12[4 * r + c] = R[3 * c + r];
+    m12[4 * r + 3] = -(R[r] * t[0] + R[3 + r] * t[1] + R[6 + r] * t[2]);
+  }
+  return SVO_OK;
+}
+
+static int voxel_clear(svo_voxel_map* m) {
+  svo_ctx* ctx = m->ctx;
+  SVO_HIP_CHECK(ctx, hipMemsetAsync(m->t.keys, 0xFF, 8 * m->cap, ctx->stream));
+  SVO_HIP_CHECK(ctx, hipMemsetAsync(m->t.ci, 0, 32 * m->cap + 4 * sizeof(u64) + 2 * sizeof(int), ctx->stream));
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_map_create(svo_ctx* ctx, const svo_voxel_map_params* params, svo_voxel_map** out) {
+  if (!ctx) return SVO_ERR_INVALID;
+  svo_use_device(ctx);
+  SVO_REQUIRE(ctx, out, "voxel_map_create: null out");
+  *out = nullptr;
+  SVO_REQUIRE(ctx, params, "voxel_map_create: null params");
+  SVO_REQUIRE(ctx, params->voxel_size > 0.0f && params->voxel_size <= 3.4028234663852886e38f, "voxel_map_create: voxel_size must be finite and > 0");
+  SVO_REQUIRE(ctx, params->capacity_log2 >= 8 && params->capacity_log2 <= 28, "voxel_map_create: capacity_log2 outside 8..28");
+  svo_voxel_map* m = new svo_voxel_map();
+  m->ctx = ctx;
+  m->prm = *params;
+  m->cap = (size_t)1 << params->capacity_log2;
+  const hipError_t e = hipMalloc((void**)&m->d_mem, 40 * m->cap + 4 * sizeof(u64) + 2 * sizeof(int));
+  if (e != hipSuccess) {
+    ctx->err = std::string("voxel_map_create: hipMalloc of the table: ") + hipGetErrorString(e);
+    delete m;
+    return SVO_ERR_HIP;
+  }
+  m->t.keys = m->d_mem;
+  m->t.ci = m->d_mem + m->cap; m->t.sx = m->d_mem + 2 * m->cap; m->t.sy = m->d_mem + 3 * m->cap; m->t.sz = m->d_mem + 4 * m->cap;
+  m->t.counters = m->d_mem + 5 * m->cap;
+  m->t.mask = (u64)m->cap - 1;
+  m->d_counts = reinterpret_cast<int*>(m->t.counters + 4);
+  const int rc = voxel_clear(m);
+  if (rc) { (void)hipFree(m->d_mem); delete m; return rc; }
+  *out = m;
+  return SVO_OK;
+}
+
+extern "C" void svo_voxel_map_destroy(svo_voxel_map* m) {
+  if (!m) return;
+  svo_use_device(m->ctx);
+  (void)hipStreamSynchronize(m->ctx->stream);
+  (void)hipFree(m->d_mem);
+  delete m;
+}
+
+extern "C" int svo_voxel_map_clear(svo_voxel_map* m) {
+  if (!m) return SVO_ERR_INVALID;
+  svo_use_device(m->ctx);
+  return voxel_clear(m);
+}
+
+extern "C" int svo_voxel_map_insert_dev(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* m12) {
+  if (!m) return SVO_ERR_INVALID;
+  svo_ctx* ctx = m->ctx;
+  svo_use_device(ctx);
+  SVO_REQUIRE(ctx, n >= 0, "voxel_map_insert: n must not be negative");
+  SVO_REQUIRE(ctx, m12, "voxel_map_insert: null m12");
+  if (n == 0) return SVO_OK;
+  SVO_REQUIRE(ctx, points, "voxel_map_insert: null points");
+  SVO_REQUIRE(ctx, ((uintptr_t)points & 3u) == 0, "voxel_map_insert: points must be 4-byte aligned");
+  VoxelInsertArgs a{};
+  a.pts = points; a.n = n;
+  memcpy(a.m, m12, sizeof(a.m));
+  a.voxel_size = m->prm.voxel_size; a.max_depth = m->prm.max_depth;
+  a.t = m->t;
+  const unsigned blocks = (unsigned)(((size_t)n + VX_T - 1) / VX_T);
+  SvoProfScope prof(ctx, SVO_PROF_VOXEL_INSERT);
+  hipLaunchKernelGGL(voxel_insert_kernel, dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
+  SVO_HIP_CHECK(ctx, hipGetLastError());
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_map_insert_pose7_dev(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* pose7) {
+  if (!m) return SVO_ERR_INVALID;
+  SVO_REQUIRE(m->ctx, pose7, "voxel_map_insert_pose7: null pose7");
+  double m12[12];
+  svo_pose7_to_cam_to_world(pose7, m12);
+  return svo_voxel_map_insert_dev(m, points, n, m12);
+}
+
+extern "C" int svo_voxel_map_stats(svo_voxel_map* m, svo_voxel_map_stats_t* stats) {
+  if (!m) return SVO_ERR_INVALID;
+  svo_ctx* ctx = m->ctx;
+  svo_use_device(ctx);
+  SVO_REQUIRE(ctx, stats, "voxel_map_stats: null stats");
+  u64 c[4] = {0, 0, 0, 0};
+  SVO_HIP_CHECK(ctx, hipMemcpyAsync(c, m->t.counters, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
+  SVO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  stats->n_voxels = c[0]; stats->n_inserted = c[1]; stats->n_rejected = c[2]; stats->n_dropped = c[3];
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_map_extract_dev(svo_voxel_map* m, int min_count, svo_cloud_point* points, int max_points, int* counts) {
+  if (!m) return SVO_ERR_INVALID;
+  svo_ctx* ctx = m->ctx;
+  svo_use_device(ctx);
+  SVO_REQUIRE(ctx, min_count >= 1, "voxel_map_extract: min_count must be at least 1");
+  SVO_REQUIRE(ctx, max_points >= 0, "voxel_map_extract: max_points must not be negative");
+  SVO_REQUIRE(ctx, points || max_points == 0, "voxel_map_extract: null points");
+  SVO_REQUIRE(ctx, counts, "voxel_map_extract: null counts");
+  VoxelExtractArgs a{};
+  a.t = m->t;
+  a.min_count = (unsigned)min_count;
+  a.voxel_size = m->prm.voxel_size;
+  a.out = points; a.max_points = max_points; a.counts = counts;
+  const unsigned blocks = (unsigned)((m->cap + (size_t)VX_T * VX_ITEMS - 1) / ((size_t)VX_T * VX_ITEMS));
+  SvoProfScope prof(ctx, SVO_PROF_VOXEL_EXTRACT);
+  SVO_HIP_CHECK(ctx, hipMemsetAsync(counts, 0, 2 * sizeof(int), ctx->stream));
+  hipLaunchKernelGGL(voxel_extract_kernel, dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
+  SVO_HIP_CHECK(ctx, hipGetLastError());
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_map_extract(svo_voxel_map* m, int min_count, svo_cloud_point* points, int capacity, int* n_total, int* n_stored) {
+  if (!m) return SVO_ERR_INVALID;
+  svo_ctx* ctx = m->ctx;
+  svo_use_device(ctx);
+  SVO_REQUIRE(ctx, min_count >= 1, "voxel_map_extract: min_count must be at least 1");
+  SVO_REQUIRE(ctx, capacity >= 0, "voxel_map_extract: capacity must not be negative");
+  SVO_REQUIRE(ctx, points || capacity == 0, "voxel_map_extract: null points");
+  SVO_REQUIRE(ctx, n_total && n_stored, "voxel_map_extract: null n_total or n_stored");
+  const size_t room = (size_t)capacity < m->cap ? (size_t)capacity : m->cap;  // no more than cap voxels exist
+  svo_cloud_point* d = nullptr;
+  if (room) SVO_HIP_CHECK(ctx, hipMalloc((void**)&d, room * sizeof(svo_cloud_point)));
+  int c[2] = {0, 0};
+  int rc = svo_voxel_map_extract_dev(m, min_count, d, (int)room, m->d_counts);
+  hipError_t e = hipSuccess;
+  if (!rc) e = hipMemcpyAsync(c, m->d_counts, sizeof(c), hipMemcpyDeviceToHost, ctx->stream);
+  if (!rc && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (!rc && e == hipSuccess && c[1] > 0) {
+    e = hipMemcpyAsync(points, d, sizeof(svo_cloud_point) * (size_t)c[1], hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  }
+  if (d) (void)hipFree(d);
+  if (rc) return rc;
+  if (e != hipSuccess) { ctx->err = std::string("voxel_map_extract: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
+  *n_total = c[0]; *n_stored = c[1];
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_map_download(svo_voxel_map* m, void* host, size_t bytes) {
+  if (!m) return SVO_ERR_INVALID;
+  svo_ctx* ctx = m->ctx;
+  svo_use_device(ctx);
+  SVO_REQUIRE(ctx, host, "voxel_map_download: null host buffer");
+  SVO_REQUIRE(ctx, bytes >= 40 * m->cap, "voxel_map_download: bytes is less than svo_voxel_map_bytes");
+  SVO_HIP_CHECK(ctx, hipMemcpyAsync(host, m->d_mem, 40 * m->cap, hipMemcpyDeviceToHost, ctx->stream));
+  SVO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return SVO_OK;
+}

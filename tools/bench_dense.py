@@ -17,7 +17,12 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      copy rate of the same run;
   6. cost to the VO: bench.py's headline load (96 lanes in 3 pipeline groups of 16-frame steps) without keyframe clouds, with
      clouds at step 4, with clouds and the speckle filter, with clouds and the left-right check, and with clouds from semi-global
-     matching, alternating, as frames/s, their ratios and the spread over the rounds.
+     matching, alternating, as frames/s, their ratios and the spread over the rounds;
+  7. voxel map: one svo_voxel_map_insert_dev per cloud ("voxel_insert" bracket) for the 16 clouds of the batch at steps 1 and 4
+     into a map of the default capacity, voxel sizes 0.05 and 0.2 m in three alternating blocks, into the cleared map and again
+     into the filled one, beside the time hbm_copy needs for the records' 16 bytes per point and the run heads per point from
+     tests/voxel_ref.py; the extraction of the resulting table ("voxel_extract") beside its 40 bytes per slot; and the 96-lane
+     load with clouds at step 4 with and without inserting every keyframe's cloud into a map per lane after each call.
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -28,6 +33,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))  # voxel_ref: the restatement counts the run heads
 
 import bench  # noqa: E402  (its module level sets the hardware-queue count bench.py measures with, before HIP starts)
 import numpy as np  # noqa: E402
@@ -36,6 +42,8 @@ W, H = bench.W, bench.H
 NDISP, BLOCK = 48, 21
 SPECKLE_SIZES, SPECKLE_DIFF = (100, 400), 32
 LR_DIFF = 16
+VOXEL_SIZES = (0.05, 0.2)
+VOXEL_LANE_LOG2 = 20  # the 96 per-lane maps of the group load: 42 MB each
 
 
 def standalone(S, torch, batch, warmup, reps):
@@ -173,7 +181,74 @@ def standalone(S, torch, batch, warmup, reps):
                   "workspace_bytes_per_pair": need / batch, "bytes_per_pair": nbytes, "bound_ms_per_pair": 1e3 * nbytes / copy,
                   "bytes_per_s": nbytes / per, "share_of_copy_rate": nbytes / per / copy,
                   "valid_per_pair_sgm": float((dm2 != -16).sum().item()) / batch, "valid_per_pair_bm": float((dm != -16).sum().item()) / batch}
+    out["voxel"] = voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy)
     ctx.close()
+    return out
+
+
+def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy):
+    """Section 7: the batch's clouds into one map.  Cloud i goes in under a small rotation and 0.8 m of forward motion per frame
+    (the synthetic stream's step), so consecutive clouds see almost the same surfaces, as consecutive keyframes do."""
+    import voxel_ref as V
+    from stereo_vo_amd import api
+    out = []
+    m12 = [V.rot_y(0.004 * i, (0.0, 0.0, 0.8 * i)) for i in range(batch)]
+    for step in (1, 4):
+        mp = ((W + step - 1) // step) * ((H + step - 1) // step)
+        pts = torch.empty((batch, mp, 4), dtype=torch.int32, device="cuda")
+        cnt = torch.zeros((batch, 2), dtype=torch.int32, device="cuda")
+        ctx.disparity_cloud(dm.data_ptr(), dl.data_ptr(), batch, W, H, W, W * H, cam, None, api.CloudParams(step, 0.0, mp), pts.data_ptr(), cnt.data_ptr())
+        ctx.sync()
+        n = [int(v) for v in cnt.cpu().numpy()[:, 1]]
+        host0 = pts[0, :n[0]].cpu().numpy().view(np.uint32).copy().view(V.POINT).reshape(-1)
+        rows = {vs: {"fresh": [], "again": []} for vs in VOXEL_SIZES}
+        maps = {vs: S.VoxelMap(ctx, voxel_size=vs) for vs in VOXEL_SIZES}
+        stats = {}
+
+        def insert_all(vm):
+            for i in range(batch):
+                vm.insert(pts[i].data_ptr(), n[i], m12=m12[i])
+
+        for _ in range(3):  # alternating blocks
+            for vs in VOXEL_SIZES:
+                vm = maps[vs]
+                for _ in range(warmup):
+                    vm.clear()
+                    insert_all(vm)
+                vm.clear()
+                ctx.profile_select("voxel_insert")
+                insert_all(vm)
+                ms, k = ctx.profile_read()
+                rows[vs]["fresh"].append(ms / k)
+                stats[vs] = vm.stats()
+                ctx.profile_select("voxel_insert")
+                insert_all(vm)
+                ms, k = ctx.profile_read()
+                rows[vs]["again"].append(ms / k)
+                ctx.profile_select("")
+        mean_n = float(np.mean(n))
+        for vs in VOXEL_SIZES:
+            vm = maps[vs]
+            buf = torch.empty((min(vm.capacity, 2 * stats[vs]["n_voxels"] + 1), 4), dtype=torch.int32, device="cuda")
+            c2 = torch.zeros(2, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            for _ in range(warmup):
+                vm.extract_dev(1, buf.data_ptr(), buf.shape[0], c2.data_ptr())
+            ctx.profile_select("voxel_extract")
+            for _ in range(5):
+                vm.extract_dev(1, buf.data_ptr(), buf.shape[0], c2.data_ptr())
+            ms, k = ctx.profile_read()
+            ctx.profile_select("")
+            fresh, again = float(np.median(rows[vs]["fresh"])), float(np.median(rows[vs]["again"]))
+            bound = 1e3 * 16 * mean_n / copy
+            out.append({"cloud_step": step, "voxel_size": vs, "capacity_log2": vm.params.capacity_log2, "points_per_cloud": mean_n,
+                        "fresh_ms_per_cloud": fresh, "again_ms_per_cloud": again, "all_fresh_ms": rows[vs]["fresh"], "all_again_ms": rows[vs]["again"],
+                        "record_bytes_bound_ms": bound, "fresh_share_of_bound": bound / fresh, "again_share_of_bound": bound / again,
+                        "run_heads_per_point_cloud0": V.run_heads(host0, m12[0], vs) / max(n[0], 1),
+                        "stats_after_fresh": stats[vs], "load": stats[vs]["n_voxels"] / vm.capacity,
+                        "extract_ms": ms / k, "extract_n_total": int(c2.cpu()[0]), "table_bytes_bound_ms": 1e3 * 40 * vm.capacity / copy,
+                        "extract_share_of_bound": (1e3 * 40 * vm.capacity / copy) / (ms / k)})
+            vm.close()
     return out
 
 
@@ -185,11 +260,26 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
     torch.cuda.synchronize()
     prm = api.CloudParams(step_px, 0.0, ((W + step_px - 1) // step_px) * ((H + step_px - 1) // step_px))
 
-    def run(k):
-        def work(g):
+    import ctypes as C
+    lane_maps = [None] * n_groups  # one map per lane, made on first use; never cleared: every step replays the same frames
+
+    def insert_clouds(gi, g):  # every keyframe cloud of the last call into its lane's map, from the table's device pointers
+        if lane_maps[gi] is None:
+            lane_maps[gi] = [S.VoxelMap(g.ctx, capacity_log2=VOXEL_LANE_LOG2) for _ in range(g.pipe.n_lanes)]
+        n, tab = C.c_int(0), C.POINTER(api.KeyframeCloud)()
+        g.ctx._chk(g.pipe.L.svo_pipeline_group_keyframe_clouds(g.pipe.h, C.byref(n), C.byref(tab)), "svo_pipeline_group_keyframe_clouds")
+        for i in range(n.value):
+            e = tab[i]
+            q = list(g.all_res[e.lane][e.frame].pose7)
+            lane_maps[gi][e.lane].insert(e.dev, e.n_stored, pose7=q if any(q[:4]) else [1, 0, 0, 0, 0, 0, 0])
+
+    def run(k, voxel=False):
+        def work(gi, g):
             for _ in range(k):
                 g.step()
-        bench.run_threads([lambda g=g: work(g) for g in groups])
+                if voxel:
+                    insert_clouds(gi, g)
+        bench.run_threads([lambda gi=gi, g=g: work(gi, g) for gi, g in enumerate(groups)])
 
     def table_len(pipe):  # entries of the last call's table (no point is copied)
         import ctypes as C
@@ -197,7 +287,7 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
         pipe.ctx._chk(pipe.L.svo_pipeline_group_keyframe_clouds(pipe.h, C.byref(n), C.byref(tab)), "svo_pipeline_group_keyframe_clouds")
         return n.value
 
-    def timed(on, speckle=False, lr=False, sgm=False):
+    def timed(on, speckle=False, lr=False, sgm=False, voxel=False):
         for g in groups:
             g.pipe.set_keyframe_clouds(-1, prm if on else None)
             if on:
@@ -205,22 +295,27 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
                 g.pipe.set_keyframe_lr_check(LR_DIFF if lr else None)
                 g.pipe.set_keyframe_sgm(on=sgm)
             g.clear_counters()
-        run(warmup)
+        run(warmup, voxel)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run(steps)
+        run(steps, voxel)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         kf = sum(table_len(g.pipe) for g in groups) if on else 0  # of the last step
         return lanes * frames * steps / dt, 1e3 * dt / steps, kf
 
-    plain, cloud, filt, chk, sg = [], [], [], [], []
+    plain, cloud, filt, chk, sg, vox = [], [], [], [], [], []
     for _ in range(rounds):  # alternating: other people's work shares the host
         plain.append(timed(False))
         cloud.append(timed(True))
         filt.append(timed(True, True))
         chk.append(timed(True, False, True))
         sg.append(timed(True, sgm=True))
+        vox.append(timed(True, voxel=True))
+    vstats = {k: sum(m.stats()[k] for ms in lane_maps if ms for m in ms) for k in ("n_voxels", "n_inserted", "n_rejected", "n_dropped")}
+    for ms in lane_maps:
+        for m in ms or []:
+            m.close()
     for g in groups:
         g.close()
     med = lambda xs: float(np.median(xs))
@@ -237,7 +332,11 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
             "round_ratios_lr_check_to_clouds": [b[0] / a[0] for a, b in zip(cloud, chk)],
             "frames_per_s_clouds_sgm": med([x[0] for x in sg]), "ratio_sgm_to_clouds": med([x[0] for x in sg]) / fc,
             "step_ms_clouds_sgm": med([x[1] for x in sg]), "all_clouds_sgm": [x[0] for x in sg],
-            "round_ratios_sgm_to_clouds": [b[0] / a[0] for a, b in zip(cloud, sg)]}
+            "round_ratios_sgm_to_clouds": [b[0] / a[0] for a, b in zip(cloud, sg)],
+            "frames_per_s_clouds_voxel": med([x[0] for x in vox]), "ratio_voxel_to_clouds": med([x[0] for x in vox]) / fc,
+            "step_ms_clouds_voxel": med([x[1] for x in vox]), "all_clouds_voxel": [x[0] for x in vox],
+            "round_ratios_voxel_to_clouds": [b[0] / a[0] for a, b in zip(cloud, vox)], "voxel_lane_log2": VOXEL_LANE_LOG2,
+            "voxel_totals_over_all_lane_maps": vstats}
 
 
 def api_sub():
@@ -302,6 +401,15 @@ def main():
                     f"  bytes counted from the code: {c['bytes_per_pair'] / 1e6:.1f} MB per pair (work space {c['workspace_bytes_per_pair'] / 1e6:.1f} MB per pair) -> "
                     f"{c['bytes_per_s'] / 1e12:.3f} TB/s = {100 * c['share_of_copy_rate']:.1f} % of hbm_copy, same run (the byte bound is {c['bound_ms_per_pair']:.4f} ms per pair); "
                     f"valid pixels per pair {c['valid_per_pair_sgm']:.0f} against block matching's {c['valid_per_pair_bm']:.0f}\n")
+            for c in s["voxel"]:
+                f.write(f"voxel map, clouds at step {c['cloud_step']} ({c['points_per_cloud']:.0f} points per cloud), voxel {c['voxel_size']} m, 2^{c['capacity_log2']} slots: insert "
+                        f"{1e3 * c['fresh_ms_per_cloud']:.1f} us per cloud into the cleared map, {1e3 * c['again_ms_per_cloud']:.1f} us again into the filled one (medians of 3 "
+                        f"alternating blocks of {s['batch']} clouds; fresh {[round(1e3 * x, 1) for x in c['all_fresh_ms']]}, again {[round(1e3 * x, 1) for x in c['all_again_ms']]}); "
+                        f"16 B per point at hbm_copy {1e3 * c['record_bytes_bound_ms']:.2f} us -> {100 * c['fresh_share_of_bound']:.1f} % / {100 * c['again_share_of_bound']:.1f} % "
+                        f"of the byte bound; run heads per point (cloud 0, restatement) {c['run_heads_per_point_cloud0']:.3f}; after the {s['batch']} clouds: "
+                        f"{c['stats_after_fresh']}, load {c['load']:.3f}\n"
+                        f"  extraction (min_count 1): {1e3 * c['extract_ms']:.1f} us for {c['extract_n_total']} voxels; 40 B per slot at hbm_copy "
+                        f"{1e3 * c['table_bytes_bound_ms']:.1f} us -> {100 * c['extract_share_of_bound']:.1f} % of that bound\n")
             if g:
                 f.write(f"{g['lanes']} lanes in {g['groups']} groups, {g['frames_per_step_per_lane']}-frame steps, median of {g['rounds']} alternating rounds of "
                         f"{g['steps']} steps, clouds at step {g['cloud_step']}:\n  without clouds {g['frames_per_s_plain']:.0f} frames/s ({g['step_ms_plain']:.1f} ms / step), "
@@ -316,7 +424,11 @@ def main():
                         f"{[round(x) for x in g['all_clouds_lr_check']]}; per round {[round(x, 3) for x in g['round_ratios_lr_check_to_clouds']]}\n"
                         f"  with clouds from semi-global matching (defaults, sub-batches of {api_sub()} keyframes): {g['frames_per_s_clouds_sgm']:.0f} frames/s "
                         f"({g['step_ms_clouds_sgm']:.1f} ms / step): ratio to clouds alone {g['ratio_sgm_to_clouds']:.3f}; rounds: "
-                        f"{[round(x) for x in g['all_clouds_sgm']]}; per round {[round(x, 3) for x in g['round_ratios_sgm_to_clouds']]}\n")
+                        f"{[round(x) for x in g['all_clouds_sgm']]}; per round {[round(x, 3) for x in g['round_ratios_sgm_to_clouds']]}\n"
+                        f"  with clouds, every keyframe cloud inserted into its lane's voxel map after each call (0.1 m, 2^{g['voxel_lane_log2']} slots per lane): "
+                        f"{g['frames_per_s_clouds_voxel']:.0f} frames/s ({g['step_ms_clouds_voxel']:.1f} ms / step): ratio to clouds alone "
+                        f"{g['ratio_voxel_to_clouds']:.3f}; rounds: {[round(x) for x in g['all_clouds_voxel']]}; per round "
+                        f"{[round(x, 3) for x in g['round_ratios_voxel_to_clouds']]}; totals over all lane maps: {g['voxel_totals_over_all_lane_maps']}\n")
 
 
 if __name__ == "__main__":
