@@ -636,8 +636,15 @@ int svo_ba_set_wave_chunks(svo_ba* ba, int k);
 /* Device-resident solves this adjuster has launched since it was created: counts[0] in the compact form (one workgroup),
  * counts[k] in the wide form at k chunks per wavefront; entries beyond the limit are 0.  gave_up (may be null): how many of
  * them gave up within their bounded waits and were run again (compact form, else host-driven) — such a solve counts in both
- * forms. */
+ * forms.  counts[svo_ba_wave_chunks_limit() + 1], where n reaches that far: continuation launches of the finished wide solves
+ * that stepped aside (svo_ba_set_yield_iterations); such a solve counts once, at the k of its first launch. */
 int svo_ba_solve_forms(svo_ba* ba, long* counts, int n, long* gave_up);
+/* LM iterations a WIDE device-resident solve of this adjuster (several chunks per wavefront) runs in one launch before it steps
+ * aside: its state stays on the device and its next launch continues it, with the same bits as the uninterrupted solve.  A launch
+ * shared by several solves lasts as long as its longest one; with n > 0 none outlasts n iterations.  0: never; -1 (default): what
+ * SVO_BA_YIELD_ITERS says, else never.  svo_ba_solve_problem(s) and svo_ba_solve launch a solve again until it is done.  Solves
+ * with a wall-clock cap (max_time_s > 0) never step aside.  Not while a solve of the adjuster is in flight or waits to continue. */
+int svo_ba_set_yield_iterations(svo_ba* ba, int n);
 int svo_ba_solve_problem(svo_ba* ba, svo_ba_summary* summary);
 /* svo_ba_solve_problem for the loaded problems of n adjusters (of one context, n <= 64) at once: those that are eligible for the
  * wide device-resident form and admitted leave as ONE launch — as the lanes of a pipeline group do —, the others are solved one
@@ -804,6 +811,9 @@ int svo_pipeline_group_last_stats(const svo_pipeline_group* g, long* launches6, 
 int svo_pipeline_group_solve_work(svo_pipeline_group* g, double* out4, int reset);
 /* svo_ba_solve_forms summed over the lanes' adjusters: "compact solves" and "wide solves at k" of a profile. */
 int svo_pipeline_group_solve_forms(svo_pipeline_group* g, long* counts, int n, long* gave_up);
+/* svo_ba_set_yield_iterations for every lane's adjuster (n >= 0): a solve that stepped aside rides the group's next wide launch,
+ * in front of the solves that have never run.  A group starts with SVO_BA_YIELD_ITERS, else with the library's default. */
+int svo_pipeline_group_set_solve_yield(svo_pipeline_group* g, int n);
 
 /* FeatureTracker::draw_track + get_drawing (src/feature_tracker.cpp:74-91; used by src/vo_node.cpp:137,188):
  * the keyframe image as RGB (3 bytes per pixel, width*height*3 output) with one green arrow of thickness 4 per feature

@@ -320,13 +320,13 @@ SYMBOLS = [
     "svo_pnp_ransac",
     "svo_ba_default_options", "svo_ba_create", "svo_ba_destroy", "svo_ba_reset", "svo_ba_add_keyframe", "svo_ba_solve",
     "svo_ba_get_pose", "svo_ba_window_count", "svo_ba_get_points", "svo_ba_load_problem",
-    "svo_ba_set_allreduce", "svo_ba_set_device_lm", "svo_ba_set_bulk_control", "svo_ba_set_solve_form", "svo_ba_wave_chunks_limit", "svo_ba_set_wave_chunks", "svo_ba_solve_forms", "svo_ba_solve_problem", "svo_ba_solve_problems", "svo_ba_read_problem", "svo_ba_set_comm", "svo_ba_last_stats", "svo_lm_solve", "svo_lm_decide_step",
+    "svo_ba_set_allreduce", "svo_ba_set_device_lm", "svo_ba_set_bulk_control", "svo_ba_set_solve_form", "svo_ba_wave_chunks_limit", "svo_ba_set_wave_chunks", "svo_ba_set_yield_iterations", "svo_ba_solve_forms", "svo_ba_solve_problem", "svo_ba_solve_problems", "svo_ba_read_problem", "svo_ba_set_comm", "svo_ba_last_stats", "svo_lm_solve", "svo_lm_decide_step",
     "svo_rccl_unique_id", "svo_rccl_comm_create", "svo_rccl_comm_destroy",
     "svo_pipeline_default_params", "svo_pipeline_create", "svo_pipeline_destroy", "svo_pipeline_reset",
     "svo_pipeline_process_batch_dev", "svo_pipeline_process_batch", "svo_pipeline_get_tracked",
     "svo_pipeline_group_create", "svo_pipeline_group_destroy", "svo_pipeline_group_reset", "svo_pipeline_group_lanes",
     "svo_pipeline_group_process_batch_dev", "svo_pipeline_group_get_tracked", "svo_pipeline_group_last_stats",
-    "svo_pipeline_group_solve_work", "svo_pipeline_group_solve_forms", "svo_pipeline_group_staging", "svo_pipeline_group_upload", "svo_pipeline_group_process_uploaded", "svo_pipeline_group_process_batch",
+    "svo_pipeline_group_solve_work", "svo_pipeline_group_solve_forms", "svo_pipeline_group_set_solve_yield", "svo_pipeline_group_staging", "svo_pipeline_group_upload", "svo_pipeline_group_process_uploaded", "svo_pipeline_group_process_batch",
     "svo_synth_default_params", "svo_synth_render", "svo_synth_pose",
     "svo_image_read_gray", "svo_kitti_read_poses", "svo_ate_rmse", "svo_kitti_run", "svo_cholesky_solve", "svo_cholesky_solve_dev", "svo_draw_track", "svo_pipeline_draw_track",
     "svo_rectify_eye_from_camera_info", "svo_rectify_build_map", "svo_rectify_remap", "svo_rectify_remap_batch_dev",
@@ -931,6 +931,18 @@ class BA:
         self.ctx._chk(self.L.svo_ba_solve_forms(self.h, out, n, C.byref(gu)), "svo_ba_solve_forms")
         return list(out), gu.value
 
+    def set_yield_iterations(self, n):
+        """LM iterations a wide device-resident solve of this adjuster runs per launch before it steps aside and is launched again
+        (0: never, -1: SVO_BA_YIELD_ITERS, else never)."""
+        self.ctx._chk(self.L.svo_ba_set_yield_iterations(self.h, int(n)), "svo_ba_set_yield_iterations")
+
+    def solve_resumes(self):
+        """Continuation launches of this adjuster's finished wide solves that stepped aside (set_yield_iterations)."""
+        n = self.L.svo_ba_wave_chunks_limit() + 2
+        out = (C.c_long * n)()
+        self.ctx._chk(self.L.svo_ba_solve_forms(self.h, out, n, None), "svo_ba_solve_forms")
+        return out[n - 1]
+
     @staticmethod
     def solve_problems(bas):
         """solve_problem for the loaded problems of several adjusters of one context at once: the admitted wide solves share ONE launch
@@ -1234,6 +1246,17 @@ class PipelineGroup:
         out, gu = (C.c_long * n)(), C.c_long(0)
         self.ctx._chk(self.L.svo_pipeline_group_solve_forms(self.h, out, n, C.byref(gu)), "svo_pipeline_group_solve_forms")
         return list(out), gu.value
+
+    def set_solve_yield(self, n):
+        """LM iterations a lane's wide window solve runs per launch before it steps aside and rides the group's next wide launch (0: never)."""
+        self.ctx._chk(self.L.svo_pipeline_group_set_solve_yield(self.h, int(n)), "svo_pipeline_group_set_solve_yield")
+
+    def solve_resumes(self):
+        """Continuation launches of the lanes' finished wide solves that stepped aside, since the group was created."""
+        n = self.L.svo_ba_wave_chunks_limit() + 2
+        out = (C.c_long * n)()
+        self.ctx._chk(self.L.svo_pipeline_group_solve_forms(self.h, out, n, None), "svo_pipeline_group_solve_forms")
+        return out[n - 1]
 
     def last_stats(self):
         """{stage: (launches, lane-stages carried)} of the last process_batch_dev call; "host_thread_busy_us_of_call_us": (microseconds of the

@@ -1810,18 +1810,28 @@ struct LmDevArgs {
   int test_giveup;          // test hook (SVO_BA_TEST_GIVEUP): the wide launch reports "gave up" at once, as if a bounded wait had run out
   int wave_chunks;          // chunks every wavefront takes in turn (1: ba_lm_kernel / ba_lm_grouped_kernel; 2..LM_MAX_WAVE_CHUNKS: ba_lm_multi_kernel), chosen per solve where it is admitted
   int wave_contig;          // ba_lm_multi_kernel: a wavefront's chunks are neighbours (1) or one per stride of 2 x workgroups (0)
+  int yield_after;          // ba_lm_multi_kernel: the solve steps aside after this many LM iterations of one launch (0: never) and leaves its state in yield_rec
+  int resume;               // ... 0: a solve from its problem image; otherwise host_seq of the launch that yielded: this one continues from yield_rec
+  double* yield_rec;        // device granules (YR_*): step-control scalars | Jacobi scales of the pose columns (n) | current poses (7 K)
 };
+// The yield record.  The tag of the command in flight and the delivery counter are not in it: a launch's tags carry its own host_seq (old
+// granules can never match), and the counter's base comes with every launch (base_arrive) because k, hence the number of arrivals, may change.
+enum { YR_RADIUS = 0, YR_DF, YR_COST, YR_INITIAL_COST, YR_MCC, YR_ITERATIONS, YR_SUCCESSFUL, YR_SEL, YR_SATURATED, YR_NEED_LINEARIZE, YR_OP_COUNT,
+       YR_LIN_CALLS, YR_STEP_CALLS, YR_SAME_SWEEPS, YR_NEXT_USED, YR_SCALARS = 16 };
+constexpr double LM_TERMINATION_CONTINUES = 2.0;  // LMR_TERMINATION of a launch that yielded (0 / 1: the solve's own terminations)
+__host__ __device__ static inline unsigned long long lm_yield_tag(int host_seq) { return (1ull << 61) | (unsigned long long)(unsigned)host_seq; }
 enum { LMC_ARRIVE = 0, LMC_WORDS = 16 };
 enum { LMR_ITERATIONS = 0, LMR_SUCCESSFUL, LMR_TERMINATION, LMR_INITIAL_COST, LMR_FINAL_COST, LMR_LINEARIZE_CALLS, LMR_STEP_CALLS, LMR_SEL,
        LMR_T_WAIT, LMR_T_CTL, LMR_T_BODY, LMR_T_TOTAL, LMR_SAME_SWEEP, LMR_NEXT_USED, LMR_C_ARRIVE, LMR_TP0, LMR_DOUBLES = LMR_TP0 + 14 };
-enum { LMS_START = 0, LMS_FIRST, LMS_RELIN, LMS_STEP, LMS_ACCEPT_RELIN, LMS_DELIVER };
-enum { LMOP_EXIT = 0, LMOP_LINEARIZE, LMOP_ITERATE, LMOP_DELIVER, LMOP_ABORT };
+enum { LMS_START = 0, LMS_FIRST, LMS_RELIN, LMS_STEP, LMS_ACCEPT_RELIN, LMS_DELIVER, LMS_RESUME };
+enum { LMOP_EXIT = 0, LMOP_LINEARIZE, LMOP_ITERATE, LMOP_DELIVER, LMOP_ABORT, LMOP_YIELD };
 
 struct LmDevState {
   double radius, df, cost, initial_cost, mcc, spec;  // spec: radius of the same-sweep pass A of the step in flight (0: none)
   double elapsed;                                    // seconds since workgroup 0's first pass, as posted with the last reduction
   double pay2[6];                                    // payload2 (+ accept, next radius) of a chained step, formed by lm_iterate
   int iterations, successful, termination, need_linearize, state, sel, chain, first, saturated;
+  int iter_base;            // LM iterations the solve had behind it when this launch began (a resumed launch: the record's)
   unsigned arrive_total;
   int lin_calls, step_calls, same_sweeps, next_used;
   int go, act, use_next, accepted, relin, bad, flag;
@@ -1952,11 +1962,11 @@ __device__ __attribute__((noinline)) int lm_controller(const BaDev& P, const LmD
   double* cCand = sStep + nn;
   double* cPose = cCand + 7 * K;
   const LmDevOpt& opt = a.opt;
-  enum { ACT_NONE = 0, ACT_LOOPTOP, ACT_FINISH, ACT_ACCEPT_TAIL, ACT_SOLVE };
+  enum { ACT_NONE = 0, ACT_LOOPTOP, ACT_FINISH, ACT_ACCEPT_TAIL, ACT_SOLVE, ACT_YIELD };
   int act = ACT_NONE;
   auto issue = [&](int op) {
     if (tid == 0) {
-      if (op == LMOP_DELIVER) cs.arrive_total += (unsigned)grid;
+      if (op == LMOP_DELIVER || op == LMOP_YIELD) cs.arrive_total += (unsigned)grid;
       cs.tag = (1ull << 62) | ((unsigned long long)(unsigned)a.host_seq << 20) | (unsigned long long)(++cs.op_count & 0xFFFFFu);
       const long long tn = (long long)wall_clock64();
       cs.t_ctl += tn - cs.t_mark; cs.t_mark = tn;
@@ -1978,9 +1988,37 @@ __device__ __attribute__((noinline)) int lm_controller(const BaDev& P, const LmD
       cs.lin_calls = 1; cs.step_calls = 0; cs.same_sweeps = 0; cs.next_used = 0; cs.bad = 0; cs.op_count = 0; cs.tag = 0;
       cs.t_wait = cs.t_ctl = cs.t_body = 0;
       for (int i = 0; i < 14; ++i) cs.tp[i] = 0;
-      cs.state = LMS_FIRST; cs.first = 1;
+      cs.state = LMS_FIRST; cs.first = 1; cs.iter_base = 0;
     }
     __syncthreads();
+    if constexpr (MULTI) {
+      if (a.resume) {
+        // A continuation: the record the yielding launch left (tagged granules: a record that is not the awaited one is a give-up, never
+        // a wrong solve) instead of the problem image's poses.  The linearisation is not in it: pass A runs again at the current point
+        // with the current radius — the totals the yielding launch held (a riding linearisation is adopted only at that very radius), or
+        // the stand-alone linearisation that was pending (then it is that call, counted as such).
+        const unsigned long long rt = lm_yield_tag(a.resume);
+        double* sc = cTerm;  // (nn + 14 K >= YR_SCALARS + 1 for every window)
+        for (int i = tid; i < YR_SCALARS + n + 7 * K; i += nt) {
+          double v = 0.0;
+          if (!granule_wait(a.yield_rec, i, rt, v)) cs.bad = 1;
+          if (i < YR_SCALARS) sc[i] = v; else if (i < YR_SCALARS + n) cSc[i - YR_SCALARS] = v; else cPose[i - YR_SCALARS - n] = v;
+        }
+        __syncthreads();
+        if (cs.bad) return LMOP_ABORT;
+        if (tid == 0) {
+          cs.radius = sc[YR_RADIUS]; cs.df = sc[YR_DF]; cs.cost = sc[YR_COST]; cs.initial_cost = sc[YR_INITIAL_COST]; cs.mcc = sc[YR_MCC];
+          cs.iterations = (int)sc[YR_ITERATIONS]; cs.successful = (int)sc[YR_SUCCESSFUL]; cs.sel = (int)sc[YR_SEL]; cs.saturated = (int)sc[YR_SATURATED];
+          cs.op_count = (unsigned)sc[YR_OP_COUNT];
+          cs.lin_calls = (int)sc[YR_LIN_CALLS] + (sc[YR_NEED_LINEARIZE] != 0.0 ? 1 : 0);
+          cs.step_calls = (int)sc[YR_STEP_CALLS]; cs.same_sweeps = (int)sc[YR_SAME_SWEEPS]; cs.next_used = (int)sc[YR_NEXT_USED];
+          cs.iter_base = cs.iterations;
+          cs.state = LMS_RESUME; cs.first = 0;
+        }
+        __syncthreads();
+        return issue(LMOP_LINEARIZE);
+      }
+    }
     {
       const ptrdiff_t shift = a.arena_src ? reinterpret_cast<const char*>(a.arena_src) - reinterpret_cast<const char*>(a.arena_dst) : 0;
       for (int i = tid; i < 7 * K; i += nt) cPose[i] = sys_load(&P.poses[i], shift);
@@ -2093,6 +2131,8 @@ __device__ __attribute__((noinline)) int lm_controller(const BaDev& P, const LmD
     } else if (st == LMS_RELIN) {
       if (tid == 0) cs.need_linearize = 0;
       act = ACT_SOLVE;
+    } else if (MULTI && st == LMS_RESUME) {
+      act = ACT_LOOPTOP;  // where the yielding launch left (its caps were tested there: they pass again)
     } else {
       act = ACT_ACCEPT_TAIL;
     }
@@ -2121,6 +2161,8 @@ __device__ __attribute__((noinline)) int lm_controller(const BaDev& P, const LmD
         if (cs.iterations >= opt.max_iterations) { cs.termination = 1; a_ = ACT_FINISH; }
         else if (opt.max_time_s > 0 && cs.elapsed >= opt.max_time_s) { cs.termination = 1; a_ = ACT_FINISH; }  // src/bundle_adjuster.cpp:11, on workgroup 0's posted clock
         else if (cs.radius <= LM_MIN_RADIUS) { cs.termination = 0; a_ = ACT_FINISH; }
+        // step aside: decided on cs.iterations, which is the same number in every workgroup of the solve (a clock is not)
+        else if (MULTI && a.yield_after > 0 && !(opt.max_time_s > 0) && cs.iterations - cs.iter_base >= a.yield_after) a_ = ACT_YIELD;
         else {
           ++cs.iterations;
           if (cs.need_linearize) { ++cs.lin_calls; cs.state = LMS_RELIN; a_ = ACT_NONE; }
@@ -2132,13 +2174,29 @@ __device__ __attribute__((noinline)) int lm_controller(const BaDev& P, const LmD
       __syncthreads();
       if (act == ACT_NONE) return issue(LMOP_LINEARIZE);
     }
-    if (act == ACT_FINISH) {
+    if (act == ACT_FINISH || (MULTI && act == ACT_YIELD)) {
+      const bool yield = MULTI && act == ACT_YIELD;  // the launch ends for this solve either way; a yield leaves the record instead of the results
       if (tid == 0) cs.state = LMS_DELIVER;
       if (blockIdx.x == 0) {
+        if constexpr (MULTI) {
+          if (yield) {
+            const unsigned long long rt = lm_yield_tag(a.host_seq);
+            double* yr = a.yield_rec;
+            if (tid == 0) {
+              const double sc[YR_SCALARS] = {cs.radius, cs.df, cs.cost, cs.initial_cost, cs.mcc, (double)cs.iterations, (double)cs.successful, (double)cs.sel,
+                                             (double)cs.saturated, (double)cs.need_linearize, (double)cs.op_count, (double)cs.lin_calls, (double)cs.step_calls,
+                                             (double)cs.same_sweeps, (double)cs.next_used, 0.0};
+#pragma unroll
+              for (int i = 0; i < YR_SCALARS; ++i) granule_store(&yr[2 * i], sc[i], rt);  // (unrolled: the array stays in registers)
+            }
+            for (int i = tid; i < n; i += nt) granule_store(&yr[2 * (YR_SCALARS + i)], cSc[i], rt);
+            for (int i = tid; i < 7 * K; i += nt) granule_store(&yr[2 * (YR_SCALARS + n + i)], cPose[i], rt);
+          }
+        }
         if (tid == 0) {
           double* r = a.host_result;
           pay_store(&r[LMR_ITERATIONS], (double)cs.iterations); pay_store(&r[LMR_SUCCESSFUL], (double)cs.successful);
-          pay_store(&r[LMR_TERMINATION], (double)cs.termination); pay_store(&r[LMR_INITIAL_COST], cs.initial_cost);
+          pay_store(&r[LMR_TERMINATION], yield ? LM_TERMINATION_CONTINUES : (double)cs.termination); pay_store(&r[LMR_INITIAL_COST], cs.initial_cost);
           pay_store(&r[LMR_FINAL_COST], cs.cost); pay_store(&r[LMR_LINEARIZE_CALLS], (double)cs.lin_calls);
           pay_store(&r[LMR_STEP_CALLS], (double)cs.step_calls); pay_store(&r[LMR_SEL], (double)cs.sel);
           const long long tn = (long long)wall_clock64();
@@ -2150,7 +2208,7 @@ __device__ __attribute__((noinline)) int lm_controller(const BaDev& P, const LmD
         }
         for (int i = tid; i < 7 * K; i += nt) pay_store(&a.host_result[LMR_DOUBLES + i], cPose[i]);
       }
-      return issue(LMOP_DELIVER);
+      return issue(yield ? LMOP_YIELD : LMOP_DELIVER);
     }
     // ACT_SOLVE: scaled, damped reduced camera system (host/lm.cpp) -> Cholesky -> pose step
     const double radius = cs.radius;
@@ -2495,7 +2553,13 @@ __device__ __forceinline__ void ba_lm_body(const LmLanePtrs& lanes) {
     if (shift && W.R.active && lane == W.R.first) { a.points_a[3 * W.R.j] = W.R.p.x; a.points_a[3 * W.R.j + 1] = W.R.p.y; a.points_a[3 * W.R.j + 2] = W.R.p.z; }
     load_chunk_table(P, my_chunk, tabs, shift);
   }
-  if (MULTI) {
+  if (MULTI && a.resume) {
+    // a continuation: observations, landmark buffers and Jacobi scales are where the earlier launches of this solve left them (plain
+    // stores by other wavefronts, possibly on another XCD: released there before the yield was published, acquired here) — only the
+    // chunk tables come from the image again.  The image's landmarks are the INITIAL ones: they must not reach points_a.
+    for (int t = 0; t < turns.count; ++t) load_chunk_table(P, turns.chunk(t), tabs + t * a.tab_words, shift);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  } else if (MULTI) {
     // every chunk of the wavefront: table -> LDS; observations and landmarks -> the device arena / the current landmark buffer, where
     // every later turn reads them (plain loads: written by this wavefront)
     for (int t = 0; t < turns.count; ++t) {
@@ -2535,7 +2599,14 @@ __device__ __forceinline__ void ba_lm_body(const LmLanePtrs& lanes) {
     P.cand_points = sel ? a.points_a : a.points_b;
     P.pay_tag = cs.tag;
     P.pay_parity = (int)(cs.op_count & 1u);
-    if (op == LMOP_DELIVER) {
+    const bool yielding = MULTI && op == LMOP_YIELD;
+    if (yielding) {
+      // what the continuation reads and this launch wrote with plain stores (landmark buffers, Jacobi scales, the observation records
+      // in the arena) leaves this XCD's L2: one agent-scope release per workgroup and yield, while the kernel runs on for its other solves
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    }
+    if (op == LMOP_DELIVER || yielding) {
+      if (!yielding) {
       if (a.export_points && my_wave_works) {
         ObsRec R = W.R;  // the landmarks of the buffer the step control selected (a chained pass A may have run ahead of a step that was not taken)
         if (R.active) R.p = D3{P.points[3 * R.j], P.points[3 * R.j + 1], P.points[3 * R.j + 2]};
@@ -2566,6 +2637,7 @@ __device__ __forceinline__ void ba_lm_body(const LmLanePtrs& lanes) {
         const float x = (float)P.points[3 * j], y = (float)P.points[3 * j + 1], z = (float)P.points[3 * j + 2];
         const unsigned long long lo = ((unsigned long long)__float_as_uint(y) << 32) | __float_as_uint(x), hi = ((unsigned long long)key << 32) | __float_as_uint(z);
         slot_store2<true>(reinterpret_cast<double*>(a.store + (key & a.store_mask)), __longlong_as_double((long long)lo), __longlong_as_double((long long)hi));
+      }
       }
       if (a.dbg && tid == 0) {  // SVO_BA_TRACE: this workgroup's own split (ticks), for the spread over the workgroups of a solve
         unsigned* g = a.dbg + 16 * blockIdx.x;
@@ -3180,6 +3252,14 @@ struct svo_ba {
   long wide_launches = 0;        // (test hook SVO_BA_TEST_GIVEUP counts them)
   long fallbacks = 0;            // device-resident solves that gave up and were re-run (svo_lm_stats.fallbacks of the last solve: 0 / 1)
   bool lm_inflight = false;      // a ba_lm_kernel has been launched and not yet joined
+  // a wide solve that stepped aside (ba_lm_multi_kernel, LmDevArgs::yield_after): its state is on the device, the next launch continues it
+  double* d_yield = nullptr;     // the yield record (granules)
+  int yield_iters = -1;          // svo_ba_set_yield_iterations: LM iterations per launch (0: never yields, -1: SVO_BA_YIELD_ITERS, else 0)
+  bool lm_yielded = false;       // loaded, state on the device: the next wide launch of this adjuster is a continuation
+  int lm_yield_seq = 0;          // ... of the launch with this completion sequence number
+  const void* lm_yield_src = nullptr;  // ... which read its problem image from here (LmDevArgs::arena_src)
+  int lm_resumes_now = 0;        // continuation launches of the solve in progress
+  long lm_resumes = 0;           // ... of every finished solve (svo_ba_solve_forms)
   hipStream_t lm_stream = nullptr;  // ... on this stream
   LmLane* h_lane = nullptr;      // pinned launch record of this adjuster's solve
   unsigned lm_base = 0;            // where the last solve left the delivery counter
@@ -3237,6 +3317,8 @@ static int ba_alloc(svo_ba* ba) {
   // when it was tried in round 3: 38 workgroups had added to a counter that read 37).  The granule stores (partials, totals)
   // are sized by the problem: ba_ensure_partials.
   A(ba->d_lmc, unsigned, LMC_WORDS);
+  A(ba->d_yield, double, 2 * (YR_SCALARS + (nmax > 0 ? nmax : 1) + 7 * Kmax));
+  SVO_HIP_CHECK(ctx, hipMemset(ba->d_yield, 0, sizeof(double) * 2 * (YR_SCALARS + (nmax > 0 ? nmax : 1) + 7 * Kmax)));
   SVO_HIP_CHECK(ctx, hipHostMalloc((void**)&ba->h_lane, sizeof(LmLane), hipHostMallocCoherent));
   if (getenv("SVO_BA_TRACE")) A(ba->d_lmdbg, unsigned, 16 * 4096);
   SVO_HIP_CHECK(ctx, hipMemset(ba->d_lmc, 0, LMC_WORDS * sizeof(unsigned)));
@@ -3355,7 +3437,7 @@ extern "C" void svo_ba_destroy(svo_ba* ba) {
   if (getenv("SVO_TIMING") && ba->lm_n) {  // (svo_ba_solve_forms)
     fprintf(stderr, "[svo ba] solve forms: compact %ld, wide at k = 1..%d:", ba->lm_k_solves[0], LM_MAX_WAVE_CHUNKS);
     for (int k = 1; k <= LM_MAX_WAVE_CHUNKS; ++k) fprintf(stderr, " %ld", ba->lm_k_solves[k]);
-    fprintf(stderr, "; gave up %ld\n", ba->fallbacks);
+    fprintf(stderr, "; gave up %ld; continuation launches of solves that stepped aside %ld (%.2f per solve)\n", ba->fallbacks, ba->lm_resumes, (double)ba->lm_resumes / ba->lm_n);
   }
   const bool wide_traced = ba->lm_iters_wide > 0 && ba->d_lmdbg != nullptr;  // (the split of the wide solves: per LM iteration of theirs)
   const double wi = (double)std::max(ba->lm_iters_wide, 1l), ci = (double)std::max(ba->lmc_iters, 1l);
@@ -3379,7 +3461,7 @@ extern "C" void svo_ba_destroy(svo_ba* ba) {
                     "system build %.2f, Cholesky %.2f, step tail %.2f\n", ba->lmc_n, (double)ba->lmc_iters / std::max(ba->lmc_n, 1l), ba->lmc_tp[13] / ci, 1e-2 * ba->lmc_tp[0] / ci,
             1e-2 * ba->lmc_tp[3] / ci, 1e-2 * ba->lmc_tp[1] / ci, 1e-2 * ba->lmc_tp[2] / ci, 1e-2 * ba->lmc_tp[6] / ci, 1e-2 * ba->lmc_tp[7] / ci, 1e-2 * ba->lmc_tp[8] / ci, 1e-2 * ba->lmc_tp[9] / ci);
   if (ba->stream) (void)hipStreamSynchronize(ba->stream);
-  void* ptrs[] = {ba->d_res, ba->d_lmdbg, ba->d_lmc, ba->d_arrive, ba->d_pay, ba->d_step, ba->d_bctl, d.sp, d.part1, d.part2, ba->d_arena};
+  void* ptrs[] = {ba->d_res, ba->d_lmdbg, ba->d_lmc, ba->d_yield, ba->d_arrive, ba->d_pay, ba->d_step, ba->d_bctl, d.sp, d.part1, d.part2, ba->d_arena};
   if (ba->h_bstat) (void)hipHostFree(ba->h_bstat);
   if (ba->h_arena) (void)hipHostFree(ba->h_arena);
   if (ba->h_store_stage) (void)hipHostFree(ba->h_store_stage);
@@ -3444,8 +3526,14 @@ extern "C" int svo_ba_set_wave_chunks(svo_ba* ba, int k) {
 
 extern "C" int svo_ba_solve_forms(svo_ba* ba, long* counts, int n, long* gave_up) {
   if (!ba || !counts || n < 1) return SVO_ERR_INVALID;
-  for (int i = 0; i < n; ++i) counts[i] = i <= LM_MAX_WAVE_CHUNKS ? ba->lm_k_solves[i] : 0;
+  for (int i = 0; i < n; ++i) counts[i] = i <= LM_MAX_WAVE_CHUNKS ? ba->lm_k_solves[i] : (i == LM_MAX_WAVE_CHUNKS + 1 ? ba->lm_resumes : 0);  // behind the forms: continuation launches
   if (gave_up) *gave_up = ba->fallbacks;
+  return SVO_OK;
+}
+
+extern "C" int svo_ba_set_yield_iterations(svo_ba* ba, int n) {
+  if (!ba || n < -1 || ba->lm_inflight || ba->lm_yielded) return SVO_ERR_INVALID;
+  ba->yield_iters = n;
   return SVO_OK;
 }
 
@@ -3704,6 +3792,7 @@ static int ba_upload_checked(svo_ba* ba, int K, const double* poses7, int npts, 
 // svo_ba_read_problem copies nothing.
 static int ba_upload(svo_ba* ba, int K, const double* poses7, int npts, const double* points3, int M,
                      const int32_t* op, const int32_t* oj, const double* uv) {
+  ba->lm_yielded = false; ba->lm_resumes_now = 0;  // (a solve that stepped aside and was never continued goes with its problem)
   const int rc = ba_upload_checked(ba, K, poses7, npts, points3, M, op, oj, uv);
   if (rc != SVO_OK) {
     ba->d.K = 0; ba->d.n = 0; ba->d.M = 0; ba->d.L = 0; ba->d.C = 0;
@@ -4033,6 +4122,13 @@ bool ba_wants_compact(const svo_ba* ba) {
   return env == 1;
 }
 
+// LM iterations a wide solve of this adjuster runs per launch before it steps aside (0: never): svo_ba_set_yield_iterations (a pipeline
+// group sets its lanes' adjusters: svo_pipeline_group_set_solve_yield), else SVO_BA_YIELD_ITERS, else never
+int ba_lm_yield_iters(const svo_ba* ba) {
+  static const int env = [] { const char* e = getenv("SVO_BA_YIELD_ITERS"); const int v = e && *e ? atoi(e) : 0; return v < 0 ? 0 : v; }();
+  return ba->yield_iters >= 0 ? ba->yield_iters : env;
+}
+
 bool ba_device_lm_fill(svo_ba* ba, int* cost, size_t* lds_out, bool forced, bool compact = false, int* waves_out = nullptr) {
   BaDev& d = ba->d;
   if (!d.det || d.C <= 0 || !ba_zero_copy(ba) || !(forced || ba->device_lm == 1 || (ba->device_lm < 0 && ba_device_lm_wanted())) || !ba->h_lane) return false;
@@ -4056,12 +4152,13 @@ bool ba_device_lm_fill(svo_ba* ba, int* cost, size_t* lds_out, bool forced, bool
   }
   d.points = ba->cur_points; d.cand_points = ba->cand_points; d.poses = ba->cur_poses; d.cand_poses = ba->cand_poses;
   d.flag = nullptr;
-  if (ba->arena_partial && ba_refresh_arena_image(ba)) return false;  // a re-solve after a zero-copy solve: the host image takes the solved state first
+  const bool resume = ba->lm_yielded && !compact;  // (the image keeps the INITIAL state while the solve is on its way: a give-up re-runs from it)
+  if (!resume && ba->arena_partial && ba_refresh_arena_image(ba)) return false;  // a re-solve after a zero-copy solve: the host image takes the solved state first
   LmLane& L = *ba->h_lane;
   L.P = d;
   LmDevArgs& a = L.a;
   a.cnt = ba->d_lmc;
-  a.arena_src = ba->arena_dirty ? ba->h_arena : nullptr;  // read in place by the kernel (zero copy); null: the device arena is complete
+  a.arena_src = resume ? ba->lm_yield_src : (ba->arena_dirty ? ba->h_arena : nullptr);  // read in place by the kernel (zero copy); null: the device arena is complete
   a.arena_dst = ba->d_arena; a.arena_bytes = ba->arena_bytes;
   a.points_a = ba->cur_points; a.points_b = ba->cand_points;
   a.export_points = ba->n_points ? ba->h_out_points : nullptr;
@@ -4076,6 +4173,9 @@ bool ba_device_lm_fill(svo_ba* ba, int* cost, size_t* lds_out, bool forced, bool
   a.tab_words = compact ? ba_lmc_tab_words(ba) : ba_lm_tab_words(ba);
   a.wave_chunks = kw;
   a.wave_contig = ba_lm_wave_contig() ? 1 : 0;
+  a.yield_after = kw > 1 ? ba_lm_yield_iters(ba) : 0;  // ba_lm_multi_kernel only
+  a.resume = resume ? ba->lm_yield_seq : 0;
+  a.yield_rec = ba->d_yield;
   a.opt.max_iterations = ba->opt.max_iterations;
   a.opt.function_tolerance = ba->opt.function_tolerance; a.opt.gradient_tolerance = ba->opt.gradient_tolerance;
   a.opt.parameter_tolerance = ba->opt.parameter_tolerance; a.opt.initial_radius = ba->opt.initial_radius;
@@ -4120,7 +4220,7 @@ int ba_device_lm_launch(svo_ba** bas, int n, hipStream_t st, bool forced, unsign
     int cost = 0;
     size_t lds = 0;
     if ((ba->d.G > 1 ? 1 : (ba_lm_wave_chunks(ba) > 1 ? 2 : 0)) != form) continue;
-    if (ba_wants_compact(ba)) { to_compact[i] = true; continue; }
+    if (ba_wants_compact(ba) && !ba->lm_yielded) { to_compact[i] = true; continue; }
     if (!ba_device_lm_fill(ba, &cost, &lds, forced)) continue;
     if (lds > 32 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) != hipSuccess) continue;
     bool admitted = ba_resident_admission(ba)->admit(cost, ba->ctx->device);
@@ -4143,7 +4243,7 @@ int ba_device_lm_launch(svo_ba** bas, int n, hipStream_t st, bool forced, unsign
         if (admitted) { ba->h_lane->a.wave_chunks = k; lds = lds_k; }
       }
     }
-    if (!admitted) { to_compact[i] = overflow; continue; }
+    if (!admitted) { to_compact[i] = overflow && !ba->lm_yielded; continue; }
     // the counter starts from zero: cleared in front of the launch (the adjuster's previous solve no longer touches it
     // once its completion word is out)
     if (ba->lm_counters_dirty || !ba->lm_have_base) {
@@ -4176,7 +4276,8 @@ int ba_device_lm_launch(svo_ba** bas, int n, hipStream_t st, bool forced, unsign
       if (ba->arena_dirty) ba->arena_partial = true;  // the kernel reads the host image in place: the device arena holds the landmark buffers only
       ba->arena_dirty = false;
       ba->lm_inflight = true; ba->lm_compact_inflight = false;
-      ++ba->lm_k_solves[std::min(std::max(ba->h_lane->a.wave_chunks, 1), LM_MAX_WAVE_CHUNKS)];
+      if (ba->lm_yielded) ++ba->lm_resumes_now;  // (a solve is counted once, at the k of its first launch)
+      else { ++ba->lm_k_solves[std::min(std::max(ba->h_lane->a.wave_chunks, 1), LM_MAX_WAVE_CHUNKS)]; ba->lm_yield_src = ba->h_lane->a.arena_src; }
       ba->lm_stream = st;
       ba->res_export = ba->h_lane->a.export_points != nullptr;
       if (launched_mask) *launched_mask |= 1ull << tidx[i];
@@ -4234,7 +4335,9 @@ int ba_device_lm_launch(svo_ba** bas, int n, hipStream_t st, bool forced, unsign
   return launched + n_compact;
 }
 
-// Joins the launch: completion word, then poses / summary / counters out of the pinned result block.
+// Joins the launch: completion word, then poses / summary / counters out of the pinned result block.  SVO_BA_CONTINUES: the solve
+// stepped aside (yield_after) — the adjuster stays "loaded, state on the device" and its next wide launch continues the solve.
+constexpr int SVO_BA_CONTINUES = 1, SVO_BA_REFUSED = 2;
 int ba_device_lm_end(svo_ba* ba, svo_ba_summary* sum) {
   if (!ba->lm_inflight) return SVO_ERR_INVALID;
   svo_ctx* ctx = ba->ctx;
@@ -4268,6 +4371,15 @@ int ba_device_lm_end(svo_ba* ba, svo_ba_summary* sum) {
   }
   const double* r = ba->h_result;
   if (!was_compact) { ba->lm_base = (unsigned)r[LMR_C_ARRIVE]; ba->lm_have_base = true; }
+  if (!was_compact && r[LMR_TERMINATION] == LM_TERMINATION_CONTINUES) {
+    // the solve stepped aside: its budget is back (above), its state stays on the device — nothing of it is read, the buffers keep
+    // their roles (the record's sel says which holds the current landmarks); only this launch's ticks join the running sums
+    for (int i = 0; i < 14; ++i) ba->lm_tp[i] += r[LMR_TP0 + i];
+    ba->lm_t_wait += r[LMR_T_WAIT]; ba->lm_t_ctl += r[LMR_T_CTL]; ba->lm_t_body += r[LMR_T_BODY]; ba->lm_t_total += r[LMR_T_TOTAL];
+    ba->lm_yielded = true; ba->lm_yield_seq = ba->seq;
+    return SVO_BA_CONTINUES;
+  }
+  ba->lm_resumes += ba->lm_resumes_now; ba->lm_resumes_now = 0; ba->lm_yielded = false;
   memcpy(ba->h_poses.data(), r + LMR_DOUBLES, sizeof(double) * 7 * (size_t)d.K);
   if (r[LMR_SEL] != 0.0) { std::swap(ba->cur_points, ba->cand_points); std::swap(ba->cur_poses, ba->cand_poses); }
   ba->host_points_valid = ba->res_export;
@@ -4657,6 +4769,26 @@ static void ba_after_giveup(svo_ba* ba) {
   ba->upload_pending = false;
   ba->lm_penalty = 64;
   ++ba->fallbacks;
+  ba->lm_yielded = false; ba->lm_resumes_now = 0;  // (a continuation that gave up: the solve starts again from its image)
+}
+
+// A solve that stepped aside and cannot be continued (its next launch is not admitted and nobody will hand budget back, or the caller
+// wants another path): back to "loaded, not uploaded" — the image was only read — and whoever solves it starts from the beginning.
+static void ba_drop_yield(svo_ba* ba) {
+  if (!ba->lm_yielded) return;
+  const int penalty = ba->lm_penalty; const long fallbacks = ba->fallbacks;
+  ba_after_giveup(ba);
+  ba->lm_penalty = penalty; ba->fallbacks = fallbacks;
+}
+
+// The join of a caller that owns no schedule (a lone pipeline, svo_ba_solve_problem(s)): a solve that stepped aside is launched again,
+// alone, on the stream it ran on, until it is done.  SVO_BA_REFUSED: a continuation was not admitted — the solve is dropped back to its image.
+static int ba_device_lm_join(svo_ba* ba, svo_ba_summary* sum) {
+  for (;;) {
+    const int rc = ba_device_lm_end(ba, sum);
+    if (rc != SVO_BA_CONTINUES) return rc;
+    if (ba_device_lm_launch(&ba, 1, ba->lm_stream, true, nullptr) != 1) { ba_drop_yield(ba); return SVO_BA_REFUSED; }
+  }
 }
 
 // ceres::Solve for the loaded problem: host/lm.cpp's step control over the HIP passes.
@@ -4670,19 +4802,22 @@ static int ba_lm(svo_ba* ba, svo_ba_summary* sum) {
   ops.accept = op_accept;
   memset(&ba->stats, 0, sizeof(ba->stats));
   int fell_back = 0;
-  if (ba_device_lm_launch(&ba, 1, ba->stream, false, nullptr) == 1) {  // the whole solve is one launch: nothing for the host to do until the completion word
-    const int rcd = ba_device_lm_end(ba, sum);
+  if (ba_device_lm_launch(&ba, 1, ba->lm_yielded ? ba->lm_stream : ba->stream, ba->lm_yielded, nullptr) == 1) {  // the whole solve is one launch (or, where it yields, a few): nothing for the host to do until the completion word
+    const int rcd = ba_device_lm_join(ba, sum);
     d.flag = nullptr;
     if (rcd == SVO_OK) { if (ba->lm_penalty > 0) --ba->lm_penalty; return rcd; }
+    if (rcd != SVO_BA_REFUSED) {
     ba_after_giveup(ba);  // the problem is still loaded (pinned image untouched): solve it again below, never lose the keyframe
     fell_back = 1;
-    if (ba_device_lm_launch(&ba, 1, ba->stream, true, nullptr) == 1) {  // (the compact form: one workgroup, nothing it could wait for)
+    }
+    if (rcd != SVO_BA_REFUSED && ba_device_lm_launch(&ba, 1, ba->stream, true, nullptr) == 1) {  // (the compact form: one workgroup, nothing it could wait for)
       const int rc2 = ba_device_lm_end(ba, sum);
       d.flag = nullptr;
       if (rc2 == SVO_OK) { ba->stats.fallbacks = 1; ctx->err.clear(); return rc2; }
       ba_after_giveup(ba);
     }
   }
+  ba_drop_yield(ba);  // (a continuation that was not launched at all)
   if (ba_bulk_control_wanted(ba)) return ba_lm_bulk_device(ba, sum);  // bulk / sharded: nothing on the host inside an LM iteration
   {
     const int rcf = ba_flush_arena(ba);
@@ -4736,8 +4871,9 @@ extern "C" int svo_ba_solve_problems(svo_ba** bas, int n, svo_ba_summary* summar
     svo_ba_summary* sum = summaries ? &summaries[i] : nullptr;
     int rc;
     if ((mask >> i) & 1ull) {
-      rc = ba_device_lm_end(ba, sum); ba->d.flag = nullptr;
+      rc = ba_device_lm_join(ba, sum); ba->d.flag = nullptr;
       if (rc == SVO_OK) { if (ba->lm_penalty > 0) --ba->lm_penalty; }
+      else if (rc == SVO_BA_REFUSED) rc = ba_lm(ba, sum);
       else {  // gave up: the problem is still loaded — again, compact form or host-driven (see svo_ba_solve_finish)
         ba_after_giveup(ba);
         rc = ba_lm(ba, sum);
@@ -4958,6 +5094,18 @@ int svo_ba_solve_poll(svo_ba* ba) {
   return (v == ba->seq || (v == -ba->seq && ba->seq != 0)) ? 1 : 0;  // published, or gave up (svo_ba_solve_finish re-runs it): either way the join will not wait
 }
 
+// 1: the launched solve has stepped aside (LmDevArgs::yield_after) and is joined as such — its budget is back, the adjuster waits for
+// its next wide launch (svo_ba_solve_launch) with its state on the device; 0: anything else (svo_ba_solve_finish joins it)
+int svo_ba_solve_continues(svo_ba* ba) {
+  if (!ba || !ba->lm_inflight || ba->lm_compact_inflight) return 0;
+  if (__atomic_load_n(ba->h_flag, __ATOMIC_ACQUIRE) != ba->seq) return 0;
+  if (ba->h_result[LMR_TERMINATION] != LM_TERMINATION_CONTINUES) return 0;
+  svo_use_device(ba->ctx);
+  return ba_device_lm_end(ba, nullptr) == SVO_BA_CONTINUES ? 1 : 0;
+}
+// 1: the adjuster holds a solve that stepped aside and waits to be continued
+int svo_ba_solve_yielded(svo_ba* ba) { return ba && ba->lm_yielded ? 1 : 0; }
+
 int svo_ba_solve_holds_budget(svo_ba* ba) { return ba && ba->lm_inflight && !ba->lm_compact_inflight ? 1 : 0; }
 
 // finish: join the launched solve (or, if none was launched for this adjuster, run the host-driven loop now) and write
@@ -4974,8 +5122,9 @@ int svo_ba_solve_finish(svo_ba* ba, svo_ba_summary* summary) {
   const bool on_device = ba->lm_inflight;
   bool on_device_ok = on_device;
   if (ba->lm_inflight) {
-    rc = ba_device_lm_end(ba, summary); ba->d.flag = nullptr;
+    rc = ba_device_lm_join(ba, summary); ba->d.flag = nullptr;
     if (rc == SVO_OK) { if (ba->lm_penalty > 0) --ba->lm_penalty; }
+    else if (rc == SVO_BA_REFUSED) { rc = ba_lm(ba, summary); on_device_ok = false; }
     else {  // gave up: never lose the keyframe — the problem is still loaded, solve it again (compact form, else host-driven)
       ba_after_giveup(ba);
       rc = ba_lm(ba, summary);

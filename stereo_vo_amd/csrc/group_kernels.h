@@ -72,6 +72,8 @@ int svo_kg_stereo_triangulate(svo_ctx* ctx, hipStream_t st, const SvoStereoTriLa
 int svo_ba_solve_prepare(svo_ba* ba);                          // 1: nothing to solve, 0: a problem is loaded, < 0: svo_status
 int svo_ba_solve_launch(svo_ba** bas, int n, void* stream, unsigned long long* launched_mask);  // number launched; bit i of the mask: bas[i] was (an ineligible or not admitted adjuster is skipped)
 int svo_ba_solve_poll(svo_ba* ba);                             // 1: finish will not block
+int svo_ba_solve_continues(svo_ba* ba);                        // 1: the launched solve stepped aside after its LM iterations per launch and has been joined as such (budget back): launch it again
+int svo_ba_solve_yielded(svo_ba* ba);                          // 1: the adjuster holds a solve that stepped aside and waits for its next launch
 int svo_ba_solve_holds_budget(svo_ba* ba);                     // 1: a launched, not yet joined solve of the wide form (its join hands admission budget back)
 int svo_ba_solve_finish(svo_ba* ba, svo_ba_summary* summary);  // join (or solve host-driven) + write back into the graph
 void svo_ba_work(svo_ba* ba, double* out4, int reset);

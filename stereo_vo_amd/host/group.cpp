@@ -36,6 +36,15 @@
 
 namespace {
 
+// LM iterations per launch after which a lane's wide window solve steps aside and rides the group's next wide launch (0: never):
+// a wide launch holds its solve line, and the hardware queue behind it, as long as its LONGEST solve runs.  SVO_BA_YIELD_ITERS
+// overrides, svo_pipeline_group_set_solve_yield sets it for a group.  The default is the best median of profiles/r09_yield_sweep.txt.
+constexpr int GROUP_SOLVE_YIELD_DEFAULT = 8;
+int group_solve_yield_default() {
+  const char* e = getenv("SVO_BA_YIELD_ITERS");
+  return e && *e ? std::max(0, atoi(e)) : GROUP_SOLVE_YIELD_DEFAULT;
+}
+
 enum LaneState { L_IDLE = 0, L_TRACK_WAIT, L_NEED_SOLVE, L_PNP_WAIT, L_TRI_WAIT, L_DONE };
 enum BaState { BA_NONE = 0, BA_ASSEMBLING, BA_READY, BA_INFLIGHT, BA_HOST_SOLVING, BA_HOST_DONE };
 enum Word { W_TRACK = 0, W_PNP, W_TRI, W_COUNT };
@@ -78,6 +87,7 @@ struct Lane {
   int ba_rc = 0;
   int ba_launch = 0, ba_line = 0;  // which solve launch of the group carries this lane's solve, on which solve line
   unsigned long long ba_ready_seq = 0;  // when its assembled solve was first seen waiting for a launch (0: none waits); the order of admission
+  bool ba_yielded = false;              // the solve that waits has run before: it stepped aside after its LM iterations per launch (it keeps its ba_ready_seq)
   bool has_keyframe = false;
   double solved_pose[7] = {1, 0, 0, 0, 0, 0, 0};
   int last_iterations = 0;
@@ -229,6 +239,7 @@ void fill_pending(Lane* l, svo_frame_result* res, int upto) {
 int finish_solve(svo_pipeline_group* g, Lane* l) {
   const int st = l->ba_state.load(std::memory_order_acquire);
   l->ba_ready_seq = 0;  // (no solve of this lane waits for a launch any more)
+  l->ba_yielded = false;
   if (st == BA_NONE) return SVO_OK;
   int rc = SVO_OK;
   const auto tf0 = std::chrono::steady_clock::now();
@@ -443,6 +454,7 @@ extern "C" int svo_pipeline_group_create(svo_ctx* ctx, svo_pipeline_group** out,
     if (!rc) rc = svo_ba_attach_store(l->ba, l->d_store, l->store_mask);
     // the lane's adjuster works on the group's solve lines (no stream of its own: see the hardware-queue note above)
     if (!rc) rc = svo_ba_use_stream(l->ba, g->st_ba[li % g->n_ba]);
+    if (!rc) rc = svo_ba_set_yield_iterations(l->ba, group_solve_yield_default());
     // (the window solves keep the wide form unless SVO_BA_FORM=compact: measured in round 5, one workgroup per solve costs a lane
     // ~10x the solve latency and halves the frame rate at 48 lanes — profiles/r05_exp_compact_lanes.txt; the compact form serves as
     // the overflow of the admission budget, SVO_BA_OVERFLOW, and as the re-run of a solve that gave up)
@@ -501,6 +513,15 @@ extern "C" int svo_pipeline_group_get_tracked(svo_pipeline_group* g, int lane, i
   for (int i = 0; i < l->n && i < capacity; ++i) {
     if (ids) ids[i] = (int64_t)si[i];
     if (xy) { xy[2 * i] = sx[2 * i]; xy[2 * i + 1] = sx[2 * i + 1]; }
+  }
+  return SVO_OK;
+}
+
+extern "C" int svo_pipeline_group_set_solve_yield(svo_pipeline_group* g, int n) {
+  if (!g || n < 0) return SVO_ERR_INVALID;
+  for (Lane* l : g->lanes) {
+    const int rc = svo_ba_set_yield_iterations(l->ba, n);
+    if (rc) return rc;
   }
   return SVO_OK;
 }
@@ -1024,8 +1045,16 @@ struct Batch {
     }
   }
 
-  static bool solve_came_back(Lane* l) {
+  // (a solve that stepped aside has not come back: it is joined as such here — budget back, line free once the launch's other words
+  // are out — and waits for the group's next wide launch, in front of the solves that have never run)
+  bool solve_came_back(Lane* l) {
     const int bs = l->ba_state.load(std::memory_order_acquire);
+    if (bs == BA_INFLIGHT && svo_ba_solve_poll(l->ba) && svo_ba_solve_continues(l->ba)) {
+      l->ba_yielded = true;
+      l->ba_state.store(BA_READY, std::memory_order_release);
+      progressed = true;
+      return false;
+    }
     return (bs == BA_INFLIGHT && svo_ba_solve_poll(l->ba)) || bs == BA_HOST_DONE;
   }
   bool any_solve_in_flight(bool holding_budget) const {
@@ -1051,12 +1080,15 @@ struct Batch {
   // lanes of lanes[0..n) whose bit is set in `taken`
   void solves_departed(const int* lanes, int n, unsigned long long taken, int line, int carried, const char* what) {
     ++g->ba_launch_id;
-    if (carried > 0) count(ST_SOLVE, carried);
+    int fresh = 0;  // (a solve is counted once: with its first launch)
+    for (int k = 0; k < n; ++k) fresh += ((taken >> k) & 1ull) && !g->lanes[lanes[k]]->ba_yielded;
+    if (fresh > 0) count(ST_SOLVE, fresh);
+    else if (carried > 0) progressed = true;
     for (int k = 0; k < n; ++k) {
       if (!((taken >> k) & 1ull)) continue;
       Lane* l = g->lanes[lanes[k]];
       EV(lanes[k], what, carried);
-      l->ba_launch = g->ba_launch_id; l->ba_line = line; l->ba_ready_seq = 0;
+      l->ba_launch = g->ba_launch_id; l->ba_line = line;  // (ba_ready_seq stays until the join: a solve that steps aside keeps its place)
       l->ba_state.store(BA_INFLIGHT, std::memory_order_release);
     }
   }
@@ -1076,7 +1108,7 @@ struct Batch {
     }
     std::sort(q_ba.begin(), q_ba.end(), [&](int a, int b) {
       const Lane* la = g->lanes[a]; const Lane* lb = g->lanes[b];
-      return svo_solve_before(la->state == L_NEED_SOLVE, la->ba_ready_seq, lb->state == L_NEED_SOLVE, lb->ba_ready_seq);
+      return svo_solve_before(la->state == L_NEED_SOLVE, la->ba_yielded, la->ba_ready_seq, lb->state == L_NEED_SOLVE, lb->ba_yielded, lb->ba_ready_seq);
     });
     for (int i = 0; i < MAX_LINES; ++i) ba_line_busy[i] = false;
     for (const Lane* l : g->lanes)
@@ -1095,9 +1127,9 @@ struct Batch {
     if (cline < 0) return not_taken;
     svo_ba* cb[SVO_MAX_LANES];
     int cl[SVO_MAX_LANES], nc = 0;
-    for (int k = 0; k < n; ++k) if (!((mask >> k) & 1ull)) { cb[nc] = bas[k]; cl[nc++] = cand[k]; (void)svo_ba_set_solve_form(bas[k], 1); }
+    for (int k = 0; k < n; ++k) if (!((mask >> k) & 1ull) && !g->lanes[cand[k]]->ba_yielded) { cb[nc] = bas[k]; cl[nc++] = cand[k]; (void)svo_ba_set_solve_form(bas[k], 1); }
     unsigned long long cmask = 0;
-    const int went = svo_ba_solve_launch(cb, nc, g->st_ba[cline], &cmask);
+    const int went = nc ? svo_ba_solve_launch(cb, nc, g->st_ba[cline], &cmask) : 0;  // (a solve that stepped aside stays wide: it waits)
     for (int k = 0; k < nc; ++k) (void)svo_ba_set_solve_form(cb[k], -1);
     if (went <= 0) return not_taken;
     solves_departed(cl, nc, cmask, cline, went, "ba_launch_compact");

@@ -40,4 +40,12 @@ inline bool svo_solve_before(bool a_waits, unsigned long long a_ready_seq, bool 
   if (a_waits != b_waits) return a_waits;
   return a_ready_seq < b_ready_seq;
 }
+// ... with solves that stepped aside after their LM iterations per launch (they keep the ready_seq of their first offer): behind the
+// lanes whose keyframe waits, in front of the solves that have never run — what is half done is finished first, so that a solve's
+// latency grows by the launches it needs and not by the queue behind it; first come, first served within each class.
+inline bool svo_solve_before(bool a_waits, bool a_yielded, unsigned long long a_ready_seq, bool b_waits, bool b_yielded, unsigned long long b_ready_seq) {
+  if (a_waits != b_waits) return a_waits;
+  if (a_yielded != b_yielded) return a_yielded;
+  return a_ready_seq < b_ready_seq;
+}
 #endif
