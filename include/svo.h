@@ -97,7 +97,8 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * "cloud" (the count, scan and write launches of one svo_disparity_cloud_batch_dev as one bracket),
  * "speckle" (the launches of one speckle filter call as one bracket), "lr_check" (one left-right check call),
  * "stereo_sgm" (the launches of one semi-global matching call as one bracket), "voxel_insert" (one svo_voxel_map_insert_dev),
- * "voxel_extract" (one svo_voxel_map_extract_dev: the counts' memset and the launch);
+ * "voxel_extract" (one svo_voxel_map_extract_dev: the counts' memset and the launch), "voxel_carve" (one
+ * svo_voxel_map_carve_dev: the counts' memset and the launch), "voxel_copy" (one svo_voxel_map_copy_live_dev);
  * NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
@@ -424,6 +425,65 @@ int svo_voxel_map_extract(svo_voxel_map* map, int min_count, svo_cloud_point* po
  * SVO_ERR_INVALID and a message naming the argument (svo_last_error of the map's context); a refused call launches nothing. */
 int svo_voxel_map_download(svo_voxel_map* map, void* host, size_t bytes);
 
+/* Free-space carving: a keyframe's disparity map is evidence that the voxels it sees THROUGH are empty.  One launch over the
+ * table, one thread per slot; disp16 is a tight width x height CV_16S map in sixteenths (FILTERED = -16) on the device, cam the
+ * camera it was matched with (focal, cx, cy, baseline are read), w2c12 the 3 x 4 row-major f64 WORLD->CAMERA transform of that
+ * keyframe (12 HOST doubles, passed to the kernel by value).  Every step is an integer or an f64 operation in the stated order,
+ * without contraction:
+ *   1. A slot is live iff key != EMPTY and count = ci >> 40 >= 1.  Other slots are skipped.
+ *   2. World position, the extraction's mean before its cast to float:
+ *      p_r = ((double)k_r + (double)s_r / ((double)count * 65536.0)) * (double)voxel_size.
+ *   3. Camera position: c_r = m[r][0]*p_0 + m[r][1]*p_1 + m[r][2]*p_2 + m[r][3], summed left to right.
+ *   4. Projection.  Not tested unless c_2 > 0.0.  u = focal*c_0 / c_2 + cx, v = focal*c_1 / c_2 + cy (multiply, divide, add);
+ *      px = floor(u + 0.5), py = floor(v + 0.5).  Tested iff px >= radius && px <= width-1-radius && py >= radius &&
+ *      py <= height-1-radius, compared in f64 (NaN and infinity fail).
+ *   5. Window.  The (2 radius + 1)^2 values of disp16 around (px, py).  Any value <= 0 (filtered, or no disparity) is no
+ *      evidence: the voxel is not carved.  Otherwise dmax is the window's maximum: the nearest surface any of these rays met,
+ *      which keeps a depth edge from carving the neighbours of the background.
+ *   6. Predicted disparity of the voxel in sixteenths: dv16 = (focal*baseline) / c_2 * 16.0.
+ *   7. See-through iff (double)(dmax + margin16) < dv16 (strict).
+ *   8. Carved iff see-through and not protected; protected means keep_count > 0 && count >= keep_count.  A carved slot gets
+ *      ci = sx = sy = sz = 0 by plain stores (each thread writes its own slot only).  THE KEY STAYS: probe chains and "the
+ *      CAS's return decides" are untouched, there are no tombstones, a later insert finds the key and starts the voxel again,
+ *      n_voxels keeps meaning "slots claimed", and the extraction skips the slot because count < min_count.  Only a copy
+ *      (below) gives such slots back.
+ *   9. counts = {n_live, n_tested, n_carved}: 3 u64 on the device, zeroed on the stream before the launch, one relaxed
+ *      atomicAdd per workgroup and non-zero counter; or NULL.
+ *  10. SVO_ERR_INVALID with the argument named, and no launch, for: a null map, disp16, cam, w2c12 or params; radius outside
+ *      0..3; margin16 outside 0..32767; keep_count < 0; width or height < 2 radius + 1 or beyond the context's limits;
+ *      focal == 0 or baseline == 0.
+ * The defaults (radius 1, margin16 8 = half a pixel of disparity, keep_count 0) are NOT tuned on real imagery: half a pixel is
+ * above the quantisation and the noise of the synthetic scenes of the tests, whose own view carves nothing with them.
+ * The pipeline never carves by itself: only the caller knows when a keyframe's pose is final. */
+typedef struct svo_voxel_carve_params {
+  int radius;     /* 0..3: half width of the window */
+  int margin16;   /* 0..32767: sixteenths of disparity a voxel must lie in front of the seen surface */
+  int keep_count; /* 0: off; > 0: voxels with at least this many points are never carved */
+} svo_voxel_carve_params;
+int svo_voxel_carve_default_params(svo_voxel_carve_params* params);
+/* Asynchronous on svo_stream(ctx), one launch (and the counts' memset). */
+int svo_voxel_map_carve_dev(svo_voxel_map* map, const int16_t* disp16, int width, int height, const svo_camera_info* cam,
+                            const double* w2c12, const svo_voxel_carve_params* params, uint64_t* counts);
+/* pose7 as svo_pose7_to_cam_to_world takes it -> m12 = [R | t] with the same R (s = 2 / |q|^2), i.e. X_cam = R(q) X_world + t:
+ * m12[r][c] = R[r][c], m12[r][3] = t_r.  Pure host arithmetic. */
+int svo_pose7_to_world_to_cam(const double* pose7, double* m12);
+/* svo_pose7_to_world_to_cam, then svo_voxel_map_carve_dev. */
+int svo_voxel_map_carve_pose7_dev(svo_voxel_map* map, const int16_t* disp16, int width, int height, const svo_camera_info* cam,
+                                  const double* pose7, const svo_voxel_carve_params* params, uint64_t* counts);
+/* disp16 in HOST memory, synchronous: upload, carve, counts[3] = {n_live, n_tested, n_carved} on the host (may be NULL). */
+int svo_voxel_map_carve(svo_voxel_map* map, const int16_t* disp16, int width, int height, const svo_camera_info* cam,
+                        const double* w2c12, const svo_voxel_carve_params* params, uint64_t* counts);
+/* Copy of the live voxels (reclaim carved slots into a fresh table, cut a window out of a map, merge two maps): every slot of
+ * src with key != EMPTY and count >= min_count (>= 1) - and, with box6 = {lo_0, lo_1, lo_2, hi_0, hi_1, hi_2} != NULL (6 HOST
+ * doubles, not NaN), klo_r <= k_r <= khi_r for r = 0, 1, 2 with klo_r = floor(lo_r / (double)voxel_size), khi_r = floor(hi_r /
+ * (double)voxel_size) computed on the host and compared as integers - is looked up or claimed in dst by the insert's own probe
+ * loop, and its four words are added to dst's with the four atomicAdds: copying into a non-empty dst is a merge.  dst counters:
+ * n_voxels += slots claimed, n_inserted += counts moved, n_dropped += counts that found no slot in SVO_VOXEL_MAX_PROBES probes
+ * (then dst holds the overflow invariants of "Order independence").  src is only read.  Asynchronous, one launch.
+ * SVO_ERR_INVALID and no launch for a null map, src == dst, maps of different contexts, voxel sizes that differ in a bit,
+ * min_count < 1, a NaN in box6. */
+int svo_voxel_map_copy_live_dev(svo_voxel_map* src, svo_voxel_map* dst, int min_count, const double* box6);
+
 /* ------------------------------------------------------------------- a8 --
  * ImageProcessor::triangulate_stereo's reprojection loop
  * (src/image_processor.cpp:178-207): keep i iff disp[i] > 0; X = pose * Q * [x y d 1]^T,
@@ -740,6 +800,12 @@ typedef struct svo_keyframe_cloud {
 int svo_pipeline_keyframe_clouds(svo_pipeline* p, int* n, const svo_keyframe_cloud** table);
 /* Entry i's points to HOST memory (src/image_processor.cpp:173-207): min(n_stored, capacity) records, synchronous. */
 int svo_pipeline_copy_keyframe_cloud(svo_pipeline* p, int i, svo_cloud_point* host, int capacity);
+/* Entry i's disparity map as its cloud was formed from it (after whichever of the left-right check and the speckle filter are
+ * on): *dev is a DEVICE pointer to a tight width x height CV_16S map, valid until the next process call like the table.  What
+ * svo_voxel_map_carve_pose7_dev takes; svo_keyframe_cloud itself is unchanged. */
+int svo_pipeline_keyframe_disparity(svo_pipeline* p, int i, const int16_t** dev);
+/* The same map to HOST memory (width * height int16), synchronous: what a caller keeps to carve later, and what the tests restate. */
+int svo_pipeline_copy_keyframe_disparity(svo_pipeline* p, int i, int16_t* host);
 /* Feature-set taps for parity tests: ids + positions the tracker holds after the last frame. */
 int svo_pipeline_get_tracked(svo_pipeline* p, int64_t* ids, float* xy, int capacity, int* n);
 
@@ -799,6 +865,9 @@ int svo_pipeline_group_set_keyframe_lr_check(svo_pipeline_group* g, const svo_lr
 int svo_pipeline_group_set_keyframe_sgm(svo_pipeline_group* g, const svo_sgm_params* params);
 int svo_pipeline_group_keyframe_clouds(svo_pipeline_group* g, int* n, const svo_keyframe_cloud** table);
 int svo_pipeline_group_copy_keyframe_cloud(svo_pipeline_group* g, int i, svo_cloud_point* host, int capacity);
+/* svo_pipeline_keyframe_disparity for entry i of the group's table. */
+int svo_pipeline_group_keyframe_disparity(svo_pipeline_group* g, int i, const int16_t** dev);
+int svo_pipeline_group_copy_keyframe_disparity(svo_pipeline_group* g, int i, int16_t* host);
 int svo_pipeline_group_get_tracked(svo_pipeline_group* g, int lane, int64_t* ids, float* xy, int capacity, int* n);
 /* Launch statistics of the last process_batch call, by stage: 0 track (LK + compaction), 1 PnP-RANSAC (hypotheses, bookkeeping and
  * refinement in one launch), 3 dedup / stereo + triangulation, 4 bundle-adjustment solves, 5 corner detection + pyramids;

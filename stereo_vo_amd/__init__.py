@@ -8,4 +8,5 @@ GPU is visible, compute entry points raise.
 from .api import (SvoError, lib, lib_path, Context, Limits, SynthParams, synth_render, synth_pose,  # noqa: F401
                   CameraInfo, BAOptions, BASummary, PipelineParams, FrameResult, BA, Pipeline, PipelineGroup,
                   pipeline_default_params, synth_default, image_read_gray, kitti_read_poses, ate_rmse, kitti_run, lm_solve, LmStats,
-                  RectifyEye, rectify_eye, rectify_eye_from_camera_info, rectify_build_map, VoxelMap, VoxelMapParams)
+                  RectifyEye, rectify_eye, rectify_eye_from_camera_info, rectify_build_map, VoxelMap, VoxelMapParams,
+                  VoxelCarveParams)

@@ -172,6 +172,39 @@ def pose7_to_cam_to_world(pose7):
     return m
 
 
+class VoxelCarveParams(C.Structure):
+    """svo_voxel_carve_params: window half width (0..3), margin in sixteenths of disparity (0..32767), keep_count (0 = off)."""
+    _fields_ = [("radius", C.c_int), ("margin16", C.c_int), ("keep_count", C.c_int)]
+
+
+def voxel_carve_default_params():
+    """svo_voxel_carve_default_params: radius 1, margin16 8, keep_count 0 (not tuned on real imagery)."""
+    p = VoxelCarveParams()
+    if lib().svo_voxel_carve_default_params(C.byref(p)) != 0:
+        raise SvoError("svo_voxel_carve_default_params failed")
+    return p
+
+
+def _carve_params(params, radius, margin16, keep_count):
+    prm = voxel_carve_default_params() if params is None else VoxelCarveParams(params.radius, params.margin16, params.keep_count)
+    if radius is not None:
+        prm.radius = int(radius)
+    if margin16 is not None:
+        prm.margin16 = int(margin16)
+    if keep_count is not None:
+        prm.keep_count = int(keep_count)
+    return prm
+
+
+def pose7_to_world_to_cam(pose7):
+    """svo_pose7_to_world_to_cam: [qw qx qy qz tx ty tz] (X_cam = R(q) X_world + t) -> the (3, 4) f64 world->camera matrix [R | t]."""
+    q = _f64(pose7).reshape(7)
+    m = np.empty((3, 4), np.float64)
+    if lib().svo_pose7_to_world_to_cam(_p(q), _p(m)) != 0:
+        raise SvoError("svo_pose7_to_world_to_cam failed")
+    return m
+
+
 SPECKLE_TILE = (64, 16)  # SVO_SPECKLE_TILE_W, SVO_SPECKLE_TILE_H
 
 
@@ -198,6 +231,19 @@ def cloud_default_params(width, height):
 
 def _cloud_params(width, height, step, min_disparity, max_points):
     return CloudParams(int(step), float(min_disparity), int(width * height if max_points is None else max_points))
+
+
+def _keyframe_disparity(ctx, h, fn, i):
+    """Entry i's device map pointer (an int) of the last process call."""
+    dev = C.c_void_p()
+    ctx._chk(fn(h, int(i), C.byref(dev)), fn.__name__)
+    return dev.value
+
+
+def _keyframe_disparity_host(ctx, h, fn, i, width, height):
+    d = np.empty((height, width), np.int16)
+    ctx._chk(fn(h, int(i), _p(d)), fn.__name__)
+    return d
 
 
 def _keyframe_clouds(ctx, L, h, table_fn, copy_fn):
@@ -343,6 +389,9 @@ SYMBOLS = [
     "svo_voxel_map_default_params", "svo_voxel_map_bytes", "svo_voxel_map_create", "svo_voxel_map_destroy", "svo_voxel_map_clear",
     "svo_voxel_map_insert_dev", "svo_pose7_to_cam_to_world", "svo_voxel_map_insert_pose7_dev", "svo_voxel_map_stats",
     "svo_voxel_map_extract_dev", "svo_voxel_map_extract", "svo_voxel_map_download",
+    "svo_voxel_carve_default_params", "svo_voxel_map_carve_dev", "svo_pose7_to_world_to_cam", "svo_voxel_map_carve_pose7_dev",
+    "svo_voxel_map_carve", "svo_voxel_map_copy_live_dev", "svo_pipeline_keyframe_disparity", "svo_pipeline_group_keyframe_disparity",
+    "svo_pipeline_copy_keyframe_disparity", "svo_pipeline_group_copy_keyframe_disparity",
 ]
 
 
@@ -424,6 +473,22 @@ def lib():
         for f in ("svo_voxel_map_default_params", "svo_voxel_map_bytes", "svo_voxel_map_create", "svo_voxel_map_clear",
                   "svo_voxel_map_insert_dev", "svo_pose7_to_cam_to_world", "svo_voxel_map_insert_pose7_dev", "svo_voxel_map_stats",
                   "svo_voxel_map_extract_dev", "svo_voxel_map_extract", "svo_voxel_map_download"):
+            getattr(L, f).restype = ci
+        # carving and the copy of the live voxels
+        L.svo_voxel_carve_default_params.argtypes = [vp]
+        L.svo_voxel_map_carve_dev.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp]
+        L.svo_pose7_to_world_to_cam.argtypes = [vp, vp]
+        L.svo_voxel_map_carve_pose7_dev.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp]
+        L.svo_voxel_map_carve.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp]
+        L.svo_voxel_map_copy_live_dev.argtypes = [vp, vp, ci, vp]
+        L.svo_pipeline_keyframe_disparity.argtypes = [vp, ci, vp]
+        L.svo_pipeline_group_keyframe_disparity.argtypes = [vp, ci, vp]
+        L.svo_pipeline_copy_keyframe_disparity.argtypes = [vp, ci, vp]
+        L.svo_pipeline_group_copy_keyframe_disparity.argtypes = [vp, ci, vp]
+        for f in ("svo_voxel_carve_default_params", "svo_voxel_map_carve_dev", "svo_pose7_to_world_to_cam", "svo_voxel_map_carve_pose7_dev",
+                  "svo_voxel_map_carve", "svo_voxel_map_copy_live_dev", "svo_pipeline_keyframe_disparity",
+                  "svo_pipeline_group_keyframe_disparity", "svo_pipeline_copy_keyframe_disparity",
+                  "svo_pipeline_group_copy_keyframe_disparity"):
             getattr(L, f).restype = ci
         _LIB = L
     return _LIB
@@ -828,6 +893,43 @@ class VoxelMap:
         for e, q in zip(table, poses7):
             self.insert(e["dev"], e["n_stored"], pose7=q)
 
+    def carve(self, disp_ptr, width, height, cam, w2c12=None, pose7=None, params=None, radius=None, margin16=None, keep_count=None,
+              counts_ptr=None):
+        """svo_voxel_map_carve_dev / _pose7_dev: the voxels the keyframe whose tight CV_16S map sits at the device pointer saw through
+        lose their payload (the key stays).  Exactly one of w2c12 (3 x 4 world->camera) and pose7; counts_ptr: 3 uint64 on the
+        device {n_live, n_tested, n_carved}, or None.  Asynchronous on the context's stream."""
+        if (w2c12 is None) == (pose7 is None):
+            raise ValueError("VoxelMap.carve: give exactly one of w2c12 and pose7")
+        prm = _carve_params(params, radius, margin16, keep_count)
+        if w2c12 is not None:
+            m = _f64(w2c12).reshape(12)
+            self.ctx._chk(self.L.svo_voxel_map_carve_dev(self.h, disp_ptr, int(width), int(height), C.byref(cam), _p(m), C.byref(prm), counts_ptr),
+                          "svo_voxel_map_carve_dev")
+        else:
+            q = _f64(pose7).reshape(7)
+            self.ctx._chk(self.L.svo_voxel_map_carve_pose7_dev(self.h, disp_ptr, int(width), int(height), C.byref(cam), _p(q), C.byref(prm),
+                                                               counts_ptr), "svo_voxel_map_carve_pose7_dev")
+
+    def carve_host(self, disp16, cam, w2c12=None, pose7=None, params=None, radius=None, margin16=None, keep_count=None):
+        """svo_voxel_map_carve: disp16 a (height, width) int16 numpy map; synchronous.  Returns {"n_live", "n_tested", "n_carved"}."""
+        if (w2c12 is None) == (pose7 is None):
+            raise ValueError("VoxelMap.carve_host: give exactly one of w2c12 and pose7")
+        d = np.ascontiguousarray(disp16, np.int16)
+        if d.ndim != 2:
+            raise ValueError("VoxelMap.carve_host: disp16 must be a (height, width) map")
+        m = _f64(pose7_to_world_to_cam(pose7) if w2c12 is None else w2c12).reshape(12)
+        prm = _carve_params(params, radius, margin16, keep_count)
+        c = np.zeros(3, np.uint64)
+        self.ctx._chk(self.L.svo_voxel_map_carve(self.h, _p(d), d.shape[1], d.shape[0], C.byref(cam), _p(m), C.byref(prm), _p(c)),
+                      "svo_voxel_map_carve")
+        return {"n_live": int(c[0]), "n_tested": int(c[1]), "n_carved": int(c[2])}
+
+    def copy_live_to(self, dst, min_count=1, box=None):
+        """svo_voxel_map_copy_live_dev: every voxel with count >= min_count (inside box = (lo_xyz, hi_xyz) in map units, if given) is
+        added to dst: a fresh dst gives the map without its carved slots, a non-empty one a merge.  Asynchronous."""
+        b = None if box is None else _f64(np.asarray(box, np.float64)).reshape(6)
+        self.ctx._chk(self.L.svo_voxel_map_copy_live_dev(self.h, dst.h, int(min_count), _p(b)), "svo_voxel_map_copy_live_dev")
+
     def stats(self):
         """The four counters as a dict (synchronises)."""
         s = VoxelMapStats()
@@ -1092,6 +1194,15 @@ class Pipeline:
         """The keyframes of the last process call: [{frame, lane, n_total, n_stored, dev, points (CLOUD_POINT_DTYPE array)}], in frame order."""
         return _keyframe_clouds(self.ctx, self.L, self.h, self.L.svo_pipeline_keyframe_clouds, self.L.svo_pipeline_copy_keyframe_cloud)
 
+    def keyframe_disparity(self, i):
+        """svo_pipeline_keyframe_disparity: the device pointer (an int) of entry i's tight CV_16S map as its cloud was formed from it;
+        valid until the next process call."""
+        return _keyframe_disparity(self.ctx, self.h, self.L.svo_pipeline_keyframe_disparity, i)
+
+    def copy_keyframe_disparity(self, i):
+        """svo_pipeline_copy_keyframe_disparity: entry i's map as a (height, width) int16 numpy array (synchronous)."""
+        return _keyframe_disparity_host(self.ctx, self.h, self.L.svo_pipeline_copy_keyframe_disparity, i, self.prm.width, self.prm.height)
+
     def process_batch(self, left, right):
         """left/right: (B, H, W) uint8 host arrays."""
         left, right = _u8(left), _u8(right)
@@ -1184,6 +1295,14 @@ class PipelineGroup:
     def keyframe_clouds(self):
         """The keyframes of the last process call over the lanes that have clouds on, ordered by lane, then frame (see Pipeline.keyframe_clouds)."""
         return _keyframe_clouds(self.ctx, self.L, self.h, self.L.svo_pipeline_group_keyframe_clouds, self.L.svo_pipeline_group_copy_keyframe_cloud)
+
+    def keyframe_disparity(self, i):
+        """svo_pipeline_group_keyframe_disparity: the device pointer (an int) of entry i of keyframe_clouds()."""
+        return _keyframe_disparity(self.ctx, self.h, self.L.svo_pipeline_group_keyframe_disparity, i)
+
+    def copy_keyframe_disparity(self, i):
+        """svo_pipeline_group_copy_keyframe_disparity: entry i's map as a (height, width) int16 numpy array (synchronous)."""
+        return _keyframe_disparity_host(self.ctx, self.h, self.L.svo_pipeline_group_copy_keyframe_disparity, i, self.prm.width, self.prm.height)
 
     def process_batch_dev(self, left_ptr, right_ptr, lane_stride, batch):
         """left_ptr/right_ptr: raw device pointers to (n_lanes, B, H, W) uint8 images (lane_stride bytes between lanes).

@@ -626,3 +626,24 @@ int svo_kfc_copy(SvoKfClouds* k, int i, svo_cloud_point* host, int capacity) {
   }
   return SVO_OK;
 }
+
+int svo_kfc_disparity(SvoKfClouds* k, int i, const int16_t** dev) {
+  svo_ctx* ctx = k->ctx;
+  SVO_REQUIRE(ctx, dev, "keyframe_disparity: null dev");
+  *dev = nullptr;
+  SVO_REQUIRE(ctx, i >= 0 && i < (int)k->table.size(), "keyframe_disparity: no such entry");
+  *dev = k->d_disp + (size_t)i * (size_t)k->W * (size_t)k->H;
+  return SVO_OK;
+}
+
+int svo_kfc_copy_disparity(SvoKfClouds* k, int i, int16_t* host) {
+  svo_ctx* ctx = k->ctx;
+  svo_use_device(ctx);
+  SVO_REQUIRE(ctx, host, "copy_keyframe_disparity: null buffer");
+  const int16_t* dev = nullptr;
+  const int rc = svo_kfc_disparity(k, i, &dev);
+  if (rc) return rc;
+  SVO_HIP_CHECK(ctx, hipMemcpyAsync(host, dev, sizeof(int16_t) * (size_t)k->W * (size_t)k->H, hipMemcpyDeviceToHost, ctx->stream));
+  SVO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return SVO_OK;
+}

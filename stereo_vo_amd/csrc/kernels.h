@@ -133,5 +133,7 @@ const svo_sgm_params* svo_kfc_sgm(const SvoKfClouds* k);
 int svo_kfc_run(SvoKfClouds* k, const svo_camera_info* cam, const SvoCloudPair* pairs, const int* frame, const int* lane, int n);
 int svo_kfc_table(SvoKfClouds* k, int* n, const svo_keyframe_cloud** table);
 int svo_kfc_copy(SvoKfClouds* k, int i, svo_cloud_point* host, int capacity);
+int svo_kfc_disparity(SvoKfClouds* k, int i, const int16_t** dev);  // entry i's map as its cloud was formed from it
+int svo_kfc_copy_disparity(SvoKfClouds* k, int i, int16_t* host);   // the same, W * H values to the host, synchronous
 const char* svo_rectify_error_text();  // of the calling thread's last context-free rectification call ("" if none failed)
 #endif

@@ -10,9 +10,20 @@
 //   voxel_extract_kernel : VX_ITEMS * 256 slots per workgroup; svo_compact_slot inside the workgroup, one returning atomicAdd per
 //                          workgroup for its base in the output (whose order is free), one for its share of n_stored.
 //
+//   voxel_carve_kernel   : the extraction's tiling, one thread per slot (keys first, payload only where live).  A live voxel's mean
+//                          is projected into a keyframe's disparity map in f64 as the header states, the window around the pixel
+//                          is read, and a voxel the keyframe saw through gets its four payload words zeroed by plain stores: its
+//                          own slot, which no other thread of the launch touches.  The key stays, so no probe chain changes.
+//                          Slots sit where the hash put them, so the lanes of a wavefront read unrelated pixels: a gather that
+//                          no ordering of the table's walk would coalesce.  A keyframe map (0.9 MB at 1241 x 376) stays in L2; each window
+//                          row is 2 radius + 1 adjacent shorts, read by a wavefront-uniform loop (no lane-dependent trip count).
+//   voxel_copy_kernel    : the same tiling over src; a qualifying slot probes dst by vx_probe, the insert's loop, and adds its
+//                          four words with the insert's four atomicAdds.
+//
 // Nothing passes between workgroups except order-independent relaxed device-scope atomics (docs/HISTORY.md, "No cache maintenance
 // inside kernels"): no fence, no acquire / release, no waiting.  The CAS's RETURN value decides a probe, never a plain load; the
-// payload words are only ever added to, and are read by a LATER launch on the same stream (extraction, download).  A full table
+// payload words are only ever added to by inserts and copies, zeroed only by a carve (a launch of its own, ordered by the stream,
+// each thread its own slot), and are read by a LATER launch on the same stream (extraction, carve, copy, download).  A full table
 // costs at most 64 probes per run head: bounded work, no spinning.
 #include "kernels.h"
 #include "tail_device.h"
@@ -53,6 +64,45 @@ __host__ __device__ __forceinline__ u64 vx_fmix64(u64 k) {
   k ^= k >> 33;
   return k;
 }
+
+// The probe loop of the contract, written once: linear from the home slot, at most SVO_VOXEL_MAX_PROBES 64-bit CASes of keys[h]
+// from EMPTY to key, whose RETURN value decides.  0: no slot (dropped), 1: found, 2: claimed; h is the slot for 1 and 2.
+__device__ __forceinline__ int vx_probe(const VoxelTable& t, u64 key, u64& h) {
+  h = vx_fmix64(key) & t.mask;
+  for (int p = 0; p < SVO_VOXEL_MAX_PROBES; ++p) {
+    u64 expected = VX_EMPTY;
+    __hip_atomic_compare_exchange_strong(&t.keys[h], &expected, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (expected == VX_EMPTY) return 2;
+    if (expected == key) return 1;
+    h = (h + 1) & t.mask;
+  }
+  return 0;
+}
+
+__device__ __forceinline__ void vx_add(const VoxelTable& t, u64 h, u64 ci, u64 sx, u64 sy, u64 sz) {
+  __hip_atomic_fetch_add(&t.ci[h], ci, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_fetch_add(&t.sx[h], sx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_fetch_add(&t.sy[h], sy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_fetch_add(&t.sz[h], sz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+struct VoxelCarveArgs {
+  VoxelTable t;
+  const int16_t* disp;
+  int width, height, radius, margin16;
+  unsigned keep_count;
+  float voxel_size;
+  double m[12];
+  double focal, cx, cy, baseline;
+  u64* counts;  // {n_live, n_tested, n_carved}, zeroed on the stream before the launch; or null
+};
+
+struct VoxelCopyArgs {
+  VoxelTable src, dst;
+  unsigned min_count;
+  int boxed;
+  int klo[3], khi[3];
+};
 }  // namespace
 
 struct svo_voxel_map {
@@ -117,23 +167,11 @@ __global__ __launch_bounds__(VX_T) void voxel_insert_kernel(VoxelInsertArgs a) {
   }
   bool claimed = false, dropped = false;
   if (head && key != VX_EMPTY) {
-    u64 h = vx_fmix64(key) & a.t.mask;
-    bool found = false;
-    for (int p = 0; p < SVO_VOXEL_MAX_PROBES; ++p) {
-      u64 expected = VX_EMPTY;
-      __hip_atomic_compare_exchange_strong(&a.t.keys[h], &expected, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (expected == VX_EMPTY) { claimed = true; found = true; break; }
-      if (expected == key) { found = true; break; }
-      h = (h + 1) & a.t.mask;
-    }
-    if (found) {
-      __hip_atomic_fetch_add(&a.t.ci[h], ((u64)(ci >> 16) << 40) | (u64)(ci & 0xFFFFu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_fetch_add(&a.t.sx[h], (u64)fx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_fetch_add(&a.t.sy[h], (u64)fy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_fetch_add(&a.t.sz[h], (u64)fz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      dropped = true;
-    }
+    u64 h;
+    const int got = vx_probe(a.t, key, h);
+    claimed = got == 2;
+    if (got) vx_add(a.t, h, ((u64)(ci >> 16) << 40) | (u64)(ci & 0xFFFFu), (u64)fx, (u64)fy, (u64)fz);
+    else dropped = true;
   }
   // counters, in points: ballots only, except for the dropped points, which exist only once the table overflows
   const unsigned n_valid = (unsigned)__popcll(__ballot(valid));
@@ -203,6 +241,114 @@ __global__ __launch_bounds__(VX_T) void voxel_extract_kernel(VoxelExtractArgs a)
     q.x = xyz[0]; q.y = xyz[1]; q.z = xyz[2];
     q.tag = (uint32_t)count | ((uint32_t)(isum / count) << 24);
     a.out[(size_t)(base + slot[j])] = q;
+  }
+}
+
+__global__ __launch_bounds__(VX_T) void voxel_carve_kernel(VoxelCarveArgs a) {
+  __shared__ unsigned sC[3][VX_T / 64];
+  const size_t cap = (size_t)a.t.mask + 1;
+  const size_t first = (size_t)blockIdx.x * (VX_T * VX_ITEMS) + (size_t)threadIdx.x;
+  const double vs = (double)a.voxel_size;
+  const double xlo = (double)a.radius, xhi = (double)(a.width - 1 - a.radius), yhi = (double)(a.height - 1 - a.radius);
+  unsigned n_live = 0, n_tested = 0, n_carved = 0;
+#pragma unroll
+  for (int j = 0; j < VX_ITEMS; ++j) {
+    const size_t s = first + (size_t)j * VX_T;
+    if (s >= cap) continue;
+    const u64 key = a.t.keys[s];
+    if (key == VX_EMPTY) continue;
+    const u64 count = a.t.ci[s] >> 40;
+    if (count == 0) continue;
+    ++n_live;
+    const double c = (double)count * 65536.0;
+    const u64 sum[3] = {a.t.sx[s], a.t.sy[s], a.t.sz[s]};
+    double p[3], q[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const double k = (double)((long long)((key >> (21 * r)) & 0x1FFFFFull) - (1ll << 20));
+      p[r] = (k + (double)sum[r] / c) * vs;
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) q[r] = a.m[4 * r] * p[0] + a.m[4 * r + 1] * p[1] + a.m[4 * r + 2] * p[2] + a.m[4 * r + 3];
+    if (!(q[2] > 0.0)) continue;
+    const double fpx = floor(a.focal * q[0] / q[2] + a.cx + 0.5), fpy = floor(a.focal * q[1] / q[2] + a.cy + 0.5);
+    if (!(fpx >= xlo && fpx <= xhi && fpy >= xlo && fpy <= yhi)) continue;  // NaN and infinity fail
+    ++n_tested;
+    const int px = (int)fpx, py = (int)fpy;  // inside the map with the whole window, by the test above
+    int dmax = 0;
+    bool evidence = true;
+    for (int dy = -a.radius; dy <= a.radius; ++dy) {
+      const int16_t* row = a.disp + (size_t)(py + dy) * (size_t)a.width + (size_t)px;
+      for (int dx = -a.radius; dx <= a.radius; ++dx) {
+        const int d = (int)row[dx];
+        evidence = evidence && d > 0;
+        dmax = d > dmax ? d : dmax;
+      }
+    }
+    if (!evidence) continue;
+    const double dv16 = a.focal * a.baseline / q[2] * 16.0;
+    if (!((double)(dmax + a.margin16) < dv16)) continue;
+    if (a.keep_count > 0u && count >= (u64)a.keep_count) continue;
+    a.t.ci[s] = 0ull; a.t.sx[s] = 0ull; a.t.sy[s] = 0ull; a.t.sz[s] = 0ull;
+    ++n_carved;
+  }
+  if (!a.counts) return;  // uniform over the launch
+  for (int o = 32; o > 0; o >>= 1) {
+    n_live += __shfl_xor(n_live, o); n_tested += __shfl_xor(n_tested, o); n_carved += __shfl_xor(n_carved, o);
+  }
+  const int tid = threadIdx.x;
+  if ((tid & 63) == 0) { sC[0][tid >> 6] = n_live; sC[1][tid >> 6] = n_tested; sC[2][tid >> 6] = n_carved; }
+  __syncthreads();
+  if (tid < 3) {
+    unsigned t = 0;
+    for (int w = 0; w < VX_T / 64; ++w) t += sC[tid][w];
+    if (t) __hip_atomic_fetch_add(&a.counts[tid], (u64)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+__global__ __launch_bounds__(VX_T) void voxel_copy_kernel(VoxelCopyArgs a) {
+  __shared__ u64 sC[3][VX_T / 64];
+  const size_t cap = (size_t)a.src.mask + 1;
+  const size_t first = (size_t)blockIdx.x * (VX_T * VX_ITEMS) + (size_t)threadIdx.x;
+  u64 n_claim = 0, n_moved = 0, n_drop = 0;  // a slot's count is below 2^24, a workgroup's 2,048 slots sum past 32 bits
+#pragma unroll
+  for (int j = 0; j < VX_ITEMS; ++j) {
+    const size_t s = first + (size_t)j * VX_T;
+    if (s >= cap) continue;
+    const u64 key = a.src.keys[s];
+    if (key == VX_EMPTY) continue;
+    const u64 ci = a.src.ci[s], count = ci >> 40;
+    if (count < (u64)a.min_count) continue;
+    if (a.boxed) {
+      bool in = true;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const int k = (int)((key >> (21 * r)) & 0x1FFFFFull) - (1 << 20);
+        in = in && k >= a.klo[r] && k <= a.khi[r];
+      }
+      if (!in) continue;
+    }
+    u64 h;
+    const int got = vx_probe(a.dst, key, h);
+    if (got) {
+      vx_add(a.dst, h, ci, a.src.sx[s], a.src.sy[s], a.src.sz[s]);
+      n_claim += got == 2 ? 1ull : 0ull;
+      n_moved += count;
+    } else {
+      n_drop += count;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    n_claim += __shfl_xor(n_claim, o); n_moved += __shfl_xor(n_moved, o); n_drop += __shfl_xor(n_drop, o);
+  }
+  const int tid = threadIdx.x;
+  if ((tid & 63) == 0) { sC[0][tid >> 6] = n_claim; sC[1][tid >> 6] = n_moved; sC[2][tid >> 6] = n_drop; }
+  __syncthreads();
+  if (tid < 3) {
+    u64 t = 0;
+    for (int w = 0; w < VX_T / 64; ++w) t += sC[tid][w];
+    // counters: n_voxels, n_inserted, (n_rejected), n_dropped
+    if (t) __hip_atomic_fetch_add(&a.dst.counters[tid == 2 ? 3 : tid], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -390,5 +536,128 @@ extern "C" int svo_voxel_map_download(svo_voxel_map* m, void* host, size_t bytes
   SVO_REQUIRE(ctx, bytes >= 40 * m->cap, "voxel_map_download: bytes is less than svo_voxel_map_bytes");
   SVO_HIP_CHECK(ctx, hipMemcpyAsync(host, m->d_mem, 40 * m->cap, hipMemcpyDeviceToHost, ctx->stream));
   SVO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return SVO_OK;
+}
+
+// ----------------------------------------------------------------------------- carving and the copy of the live voxels
+extern "C" int svo_voxel_carve_default_params(svo_voxel_carve_params* params) {
+  if (!params) return SVO_ERR_INVALID;
+  params->radius = 1;
+  params->margin16 = 8;
+  params->keep_count = 0;
+  return SVO_OK;
+}
+
+extern "C" int svo_pose7_to_world_to_cam(const double* pose7, double* m12) {
+  if (!pose7 || !m12) return SVO_ERR_INVALID;
+  const double w = pose7[0], x = pose7[1], y = pose7[2], z = pose7[3];
+  const double s = 2.0 / (w * w + x * x + y * y + z * z);
+  const double R[9] = {1.0 - s * (y * y + z * z), s * (x * y - w * z), s * (x * z + w * y),
+                       s * (x * y + w * z), 1.0 - s * (x * x + z * z), s * (y * z - w * x),
+                       s * (x * z - w * y), s * (y * z + w * x), 1.0 - s * (x * x + y * y)};
+  for (int r = 0; r < 3; ++r) {  // [R | t]
+    for (int c = 0; c < 3; ++c) m12[4 * r + c] = R[3 * r + c];
+    m12[4 * r + 3] = pose7[4 + r];
+  }
+  return SVO_OK;
+}
+
+static int voxel_carve_check(svo_voxel_map* m, const int16_t* disp16, int width, int height, const svo_camera_info* cam, const double* w2c12,
+                             const svo_voxel_carve_params* prm) {
+  svo_ctx* ctx = m->ctx;
+  SVO_REQUIRE(ctx, disp16, "voxel_map_carve: null disp16");
+  SVO_REQUIRE(ctx, cam, "voxel_map_carve: null cam");
+  SVO_REQUIRE(ctx, w2c12, "voxel_map_carve: null w2c12");
+  SVO_REQUIRE(ctx, prm, "voxel_map_carve: null params");
+  SVO_REQUIRE(ctx, prm->radius >= 0 && prm->radius <= 3, "voxel_map_carve: radius outside 0..3");
+  SVO_REQUIRE(ctx, prm->margin16 >= 0 && prm->margin16 <= 32767, "voxel_map_carve: margin16 outside 0..32767");
+  SVO_REQUIRE(ctx, prm->keep_count >= 0, "voxel_map_carve: keep_count must not be negative");
+  SVO_REQUIRE(ctx, width >= 2 * prm->radius + 1 && width <= ctx->lim.max_width, "voxel_map_carve: width below 2 radius + 1 or beyond the context's limit");
+  SVO_REQUIRE(ctx, height >= 2 * prm->radius + 1 && height <= ctx->lim.max_height, "voxel_map_carve: height below 2 radius + 1 or beyond the context's limit");
+  SVO_REQUIRE(ctx, cam->focal != 0.0 && cam->baseline != 0.0, "voxel_map_carve: focal and baseline must not be 0");
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_map_carve_dev(svo_voxel_map* m, const int16_t* disp16, int width, int height, const svo_camera_info* cam,
+                                       const double* w2c12, const svo_voxel_carve_params* prm, uint64_t* counts) {
+  if (!m) return SVO_ERR_INVALID;
+  svo_ctx* ctx = m->ctx;
+  svo_use_device(ctx);
+  const int rc = voxel_carve_check(m, disp16, width, height, cam, w2c12, prm);
+  if (rc) return rc;
+  VoxelCarveArgs a{};
+  a.t = m->t;
+  a.disp = disp16; a.width = width; a.height = height;
+  a.radius = prm->radius; a.margin16 = prm->margin16; a.keep_count = (unsigned)prm->keep_count;
+  a.voxel_size = m->prm.voxel_size;
+  memcpy(a.m, w2c12, sizeof(a.m));
+  a.focal = cam->focal; a.cx = cam->cx; a.cy = cam->cy; a.baseline = cam->baseline;
+  a.counts = reinterpret_cast<u64*>(counts);
+  const unsigned blocks = (unsigned)((m->cap + (size_t)VX_T * VX_ITEMS - 1) / ((size_t)VX_T * VX_ITEMS));
+  SvoProfScope prof(ctx, SVO_PROF_VOXEL_CARVE);
+  if (counts) SVO_HIP_CHECK(ctx, hipMemsetAsync(counts, 0, 3 * sizeof(u64), ctx->stream));
+  hipLaunchKernelGGL(voxel_carve_kernel, dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
+  SVO_HIP_CHECK(ctx, hipGetLastError());
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_map_carve_pose7_dev(svo_voxel_map* m, const int16_t* disp16, int width, int height, const svo_camera_info* cam,
+                                             const double* pose7, const svo_voxel_carve_params* prm, uint64_t* counts) {
+  if (!m) return SVO_ERR_INVALID;
+  SVO_REQUIRE(m->ctx, pose7, "voxel_map_carve_pose7: null pose7");
+  double m12[12];
+  svo_pose7_to_world_to_cam(pose7, m12);
+  return svo_voxel_map_carve_dev(m, disp16, width, height, cam, m12, prm, counts);
+}
+
+extern "C" int svo_voxel_map_carve(svo_voxel_map* m, const int16_t* disp16, int width, int height, const svo_camera_info* cam,
+                                   const double* w2c12, const svo_voxel_carve_params* prm, uint64_t* counts) {
+  if (!m) return SVO_ERR_INVALID;
+  svo_ctx* ctx = m->ctx;
+  svo_use_device(ctx);
+  int rc = voxel_carve_check(m, disp16, width, height, cam, w2c12, prm);
+  if (rc) return rc;
+  const size_t bytes = sizeof(int16_t) * (size_t)width * (size_t)height;
+  u64* d = nullptr;  // 3 counts | the map
+  SVO_HIP_CHECK(ctx, hipMalloc((void**)&d, 4 * sizeof(u64) + bytes));
+  int16_t* d_disp = reinterpret_cast<int16_t*>(d + 4);
+  u64 c[3] = {0, 0, 0};
+  hipError_t e = hipMemcpyAsync(d_disp, disp16, bytes, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) rc = svo_voxel_map_carve_dev(m, d_disp, width, height, cam, w2c12, prm, reinterpret_cast<uint64_t*>(d));
+  if (e == hipSuccess && !rc) e = hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // also before the free, whatever failed
+  if (e == hipSuccess) e = e2;
+  (void)hipFree(d);
+  if (rc) return rc;
+  if (e != hipSuccess) { ctx->err = std::string("voxel_map_carve: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
+  if (counts) { counts[0] = c[0]; counts[1] = c[1]; counts[2] = c[2]; }
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_map_copy_live_dev(svo_voxel_map* src, svo_voxel_map* dst, int min_count, const double* box6) {
+  if (!src || !dst) return SVO_ERR_INVALID;
+  svo_ctx* ctx = dst->ctx;
+  svo_use_device(ctx);
+  SVO_REQUIRE(ctx, src != dst, "voxel_map_copy_live: src and dst are the same map");
+  SVO_REQUIRE(ctx, src->ctx == dst->ctx, "voxel_map_copy_live: src and dst belong to different contexts");
+  SVO_REQUIRE(ctx, memcmp(&src->prm.voxel_size, &dst->prm.voxel_size, sizeof(float)) == 0, "voxel_map_copy_live: voxel_size of src and dst differ");
+  SVO_REQUIRE(ctx, min_count >= 1, "voxel_map_copy_live: min_count must be at least 1");
+  VoxelCopyArgs a{};
+  a.src = src->t; a.dst = dst->t;
+  a.min_count = (unsigned)min_count;
+  if (box6) {
+    const double vs = (double)src->prm.voxel_size, far = 2097152.0;  // 2^21: beyond every key on either side
+    for (int i = 0; i < 6; ++i) {
+      SVO_REQUIRE(ctx, box6[i] == box6[i], "voxel_map_copy_live: box6 holds a NaN");
+      double k = floor(box6[i] / vs);
+      k = k < -far ? -far : (k > far ? far : k);
+      (i < 3 ? a.klo[i] : a.khi[i - 3]) = (int)k;
+    }
+    a.boxed = 1;
+  }
+  const unsigned blocks = (unsigned)((src->cap + (size_t)VX_T * VX_ITEMS - 1) / ((size_t)VX_T * VX_ITEMS));
+  SvoProfScope prof(ctx, SVO_PROF_VOXEL_COPY);
+  hipLaunchKernelGGL(voxel_copy_kernel, dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
+  SVO_HIP_CHECK(ctx, hipGetLastError());
   return SVO_OK;
 }

@@ -1429,6 +1429,18 @@ extern "C" int svo_pipeline_group_copy_keyframe_cloud(svo_pipeline_group* g, int
   return svo_kfc_copy(g->kfc, i, host, capacity);
 }
 
+extern "C" int svo_pipeline_group_keyframe_disparity(svo_pipeline_group* g, int i, const int16_t** dev) {
+  if (!g) return SVO_ERR_INVALID;
+  SVO_REQUIRE(g->ctx, g->kfc, "pipeline_group_keyframe_disparity: keyframe clouds are off on every lane");
+  return svo_kfc_disparity(g->kfc, i, dev);
+}
+
+extern "C" int svo_pipeline_group_copy_keyframe_disparity(svo_pipeline_group* g, int i, int16_t* host) {
+  if (!g) return SVO_ERR_INVALID;
+  SVO_REQUIRE(g->ctx, g->kfc, "pipeline_group_copy_keyframe_disparity: keyframe clouds are off on every lane");
+  return svo_kfc_copy_disparity(g->kfc, i, host);
+}
+
 // Raw input per lane (include/svo.h).  The tables of a (left, right) pair of models exist once, however many lanes use it.
 extern "C" int svo_pipeline_group_set_rectification(svo_pipeline_group* g, int lane, const svo_rectify_eye* left, const svo_rectify_eye* right) {
   if (!g) return SVO_ERR_INVALID;

@@ -957,6 +957,18 @@ extern "C" int svo_pipeline_copy_keyframe_cloud(svo_pipeline* p, int i, svo_clou
   return svo_kfc_copy(p->kfc, i, host, capacity);
 }
 
+extern "C" int svo_pipeline_keyframe_disparity(svo_pipeline* p, int i, const int16_t** dev) {
+  if (!p) return SVO_ERR_INVALID;
+  SVO_REQUIRE(p->ctx, p->kfc, "pipeline_keyframe_disparity: keyframe clouds are off (svo_pipeline_set_keyframe_clouds)");
+  return svo_kfc_disparity(p->kfc, i, dev);
+}
+
+extern "C" int svo_pipeline_copy_keyframe_disparity(svo_pipeline* p, int i, int16_t* host) {
+  if (!p) return SVO_ERR_INVALID;
+  SVO_REQUIRE(p->ctx, p->kfc, "pipeline_copy_keyframe_disparity: keyframe clouds are off (svo_pipeline_set_keyframe_clouds)");
+  return svo_kfc_copy_disparity(p->kfc, i, host);
+}
+
 extern "C" int svo_pipeline_draw_track(svo_pipeline* p, const uint8_t* keyframe_gray, int row_stride, uint8_t* rgb) {
   if (!p || !keyframe_gray || !rgb) return SVO_ERR_INVALID;
   (void)hipSetDevice(p->ctx->device);

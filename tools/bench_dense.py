@@ -22,7 +22,12 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      into a map of the default capacity, voxel sizes 0.05 and 0.2 m in three alternating blocks, into the cleared map and again
      into the filled one, beside the time hbm_copy needs for the records' 16 bytes per point and the run heads per point from
      tests/voxel_ref.py; the extraction of the resulting table ("voxel_extract") beside its 40 bytes per slot; and the 96-lane
-     load with clouds at step 4 with and without inserting every keyframe's cloud into a map per lane after each call.
+     load with clouds at step 4 with and without inserting every keyframe's cloud into a map per lane after each call;
+  8. carving and the copy of the live voxels: one svo_voxel_map_copy_live_dev of each filled map of section 7 into a cleared map of
+     the same capacity ("voxel_copy") and one svo_voxel_map_carve_dev of it with the batch's last disparity map under its pose
+     ("voxel_carve": first with keep_count 1, which walks, projects and reads the windows but protects every voxel, then the real
+     one), each beside the time hbm_copy needs for 8 bytes per slot + 32 per live slot (+ 40 per copied voxel); and the 96-lane
+     load with every keyframe inserted against every keyframe's map carving its lane's map before its cloud is inserted.
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -248,8 +253,46 @@ def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy):
                         "stats_after_fresh": stats[vs], "load": stats[vs]["n_voxels"] / vm.capacity,
                         "extract_ms": ms / k, "extract_n_total": int(c2.cpu()[0]), "table_bytes_bound_ms": 1e3 * 40 * vm.capacity / copy,
                         "extract_share_of_bound": (1e3 * 40 * vm.capacity / copy) / (ms / k)})
+            out[-1].update(carve_and_copy(S, torch, ctx, cam, dm, vm, np.asarray(m12[batch - 1]), warmup, copy))
             vm.close()
     return out
+
+
+def carve_and_copy(S, torch, ctx, cam, dm, vm, c2w, warmup, copy):
+    """Section 8 for one filled map: the copy into a cleared map of the same shape, then the carve with the last map of the batch."""
+    live = vm.stats()["n_voxels"]  # nothing was carved yet: every claimed slot is live
+    dst = S.VoxelMap(ctx, voxel_size=vm.params.voxel_size, capacity_log2=vm.params.capacity_log2)
+    for _ in range(warmup):
+        dst.clear()
+        vm.copy_live_to(dst)
+    dst.clear()
+    ctx.profile_select("voxel_copy")
+    vm.copy_live_to(dst)
+    copy_ms, _ = ctx.profile_read()
+    ctx.profile_select("")
+    copied = dst.stats()
+    dst.close()
+    w2c = np.linalg.inv(np.vstack([c2w.reshape(3, 4), [0, 0, 0, 1]]))[:3].reshape(12)
+    cnt = torch.zeros(3, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    last = dm[dm.shape[0] - 1]
+    for _ in range(warmup):
+        vm.carve(last.data_ptr(), W, H, cam, w2c12=w2c, keep_count=1, counts_ptr=cnt.data_ptr())
+    ctx.profile_select("voxel_carve")
+    for _ in range(5):
+        vm.carve(last.data_ptr(), W, H, cam, w2c12=w2c, keep_count=1, counts_ptr=cnt.data_ptr())
+    dry_ms, k = ctx.profile_read()
+    dry = [int(v) for v in cnt.cpu()]
+    ctx.profile_select("voxel_carve")
+    vm.carve(last.data_ptr(), W, H, cam, w2c12=w2c, counts_ptr=cnt.data_ptr())
+    carve_ms, _ = ctx.profile_read()
+    ctx.profile_select("")
+    real = [int(v) for v in cnt.cpu()]
+    carve_bound = 1e3 * (8 * vm.capacity + 32 * live) / copy
+    copy_bound = 1e3 * (8 * vm.capacity + 32 * live + 40 * copied["n_voxels"]) / copy
+    return {"live_slots": live, "copy_ms": copy_ms, "copy_stats": copied, "copy_bound_ms": copy_bound, "copy_share_of_bound": copy_bound / copy_ms,
+            "carve_dry_ms": dry_ms / k, "carve_dry_counts": dry, "carve_ms": carve_ms, "carve_counts": real, "carve_bound_ms": carve_bound,
+            "carve_dry_share_of_bound": carve_bound / (dry_ms / k), "carve_share_of_bound": carve_bound / carve_ms}
 
 
 def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
@@ -263,7 +306,7 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
     import ctypes as C
     lane_maps = [None] * n_groups  # one map per lane, made on first use; never cleared: every step replays the same frames
 
-    def insert_clouds(gi, g):  # every keyframe cloud of the last call into its lane's map, from the table's device pointers
+    def insert_clouds(gi, g, carve=False):  # every keyframe cloud of the last call into its lane's map, from the table's device pointers
         if lane_maps[gi] is None:
             lane_maps[gi] = [S.VoxelMap(g.ctx, capacity_log2=VOXEL_LANE_LOG2) for _ in range(g.pipe.n_lanes)]
         n, tab = C.c_int(0), C.POINTER(api.KeyframeCloud)()
@@ -271,14 +314,17 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
         for i in range(n.value):
             e = tab[i]
             q = list(g.all_res[e.lane][e.frame].pose7)
-            lane_maps[gi][e.lane].insert(e.dev, e.n_stored, pose7=q if any(q[:4]) else [1, 0, 0, 0, 0, 0, 0])
+            q = q if any(q[:4]) else [1, 0, 0, 0, 0, 0, 0]
+            if carve:  # the keyframe's own map first carves what the earlier keyframes left in its view (defaults)
+                lane_maps[gi][e.lane].carve(g.pipe.keyframe_disparity(i), W, H, g.pipe.prm.cam, pose7=q)
+            lane_maps[gi][e.lane].insert(e.dev, e.n_stored, pose7=q)
 
-    def run(k, voxel=False):
+    def run(k, voxel=False, carve=False):
         def work(gi, g):
             for _ in range(k):
                 g.step()
                 if voxel:
-                    insert_clouds(gi, g)
+                    insert_clouds(gi, g, carve)
         bench.run_threads([lambda gi=gi, g=g: work(gi, g) for gi, g in enumerate(groups)])
 
     def table_len(pipe):  # entries of the last call's table (no point is copied)
@@ -287,7 +333,7 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
         pipe.ctx._chk(pipe.L.svo_pipeline_group_keyframe_clouds(pipe.h, C.byref(n), C.byref(tab)), "svo_pipeline_group_keyframe_clouds")
         return n.value
 
-    def timed(on, speckle=False, lr=False, sgm=False, voxel=False):
+    def timed(on, speckle=False, lr=False, sgm=False, voxel=False, carve=False):
         for g in groups:
             g.pipe.set_keyframe_clouds(-1, prm if on else None)
             if on:
@@ -295,16 +341,16 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
                 g.pipe.set_keyframe_lr_check(LR_DIFF if lr else None)
                 g.pipe.set_keyframe_sgm(on=sgm)
             g.clear_counters()
-        run(warmup, voxel)
+        run(warmup, voxel, carve)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run(steps, voxel)
+        run(steps, voxel, carve)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         kf = sum(table_len(g.pipe) for g in groups) if on else 0  # of the last step
         return lanes * frames * steps / dt, 1e3 * dt / steps, kf
 
-    plain, cloud, filt, chk, sg, vox = [], [], [], [], [], []
+    plain, cloud, filt, chk, sg, vox, crv = [], [], [], [], [], [], []
     for _ in range(rounds):  # alternating: other people's work shares the host
         plain.append(timed(False))
         cloud.append(timed(True))
@@ -312,6 +358,8 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
         chk.append(timed(True, False, True))
         sg.append(timed(True, sgm=True))
         vox.append(timed(True, voxel=True))
+        crv.append(timed(True, voxel=True, carve=True))
+        print(f"bench_dense: round {len(crv)} of {rounds} done", file=sys.stderr, flush=True)
     vstats = {k: sum(m.stats()[k] for ms in lane_maps if ms for m in ms) for k in ("n_voxels", "n_inserted", "n_rejected", "n_dropped")}
     for ms in lane_maps:
         for m in ms or []:
@@ -336,7 +384,10 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
             "frames_per_s_clouds_voxel": med([x[0] for x in vox]), "ratio_voxel_to_clouds": med([x[0] for x in vox]) / fc,
             "step_ms_clouds_voxel": med([x[1] for x in vox]), "all_clouds_voxel": [x[0] for x in vox],
             "round_ratios_voxel_to_clouds": [b[0] / a[0] for a, b in zip(cloud, vox)], "voxel_lane_log2": VOXEL_LANE_LOG2,
-            "voxel_totals_over_all_lane_maps": vstats}
+            "voxel_totals_over_all_lane_maps": vstats,
+            "frames_per_s_clouds_voxel_carve": med([x[0] for x in crv]), "ratio_carve_to_voxel": med([x[0] for x in crv]) / med([x[0] for x in vox]),
+            "step_ms_clouds_voxel_carve": med([x[1] for x in crv]), "all_clouds_voxel_carve": [x[0] for x in crv],
+            "round_ratios_carve_to_voxel": [b[0] / a[0] for a, b in zip(vox, crv)]}
 
 
 def api_sub():
@@ -363,6 +414,7 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_dense: needs the GPU (nothing is measured without it)")
     res = {"standalone": standalone(S, torch, a.batch, 3, a.reps)}
+    print("bench_dense: standalone sections done", file=sys.stderr, flush=True)
     if not a.skip_groups:
         res["pipeline_groups"] = grouped(S, torch, a.lanes, a.groups, a.frames, a.warmup, a.steps, a.rounds, a.cloud_step)
     try:
@@ -409,7 +461,13 @@ def main():
                         f"of the byte bound; run heads per point (cloud 0, restatement) {c['run_heads_per_point_cloud0']:.3f}; after the {s['batch']} clouds: "
                         f"{c['stats_after_fresh']}, load {c['load']:.3f}\n"
                         f"  extraction (min_count 1): {1e3 * c['extract_ms']:.1f} us for {c['extract_n_total']} voxels; 40 B per slot at hbm_copy "
-                        f"{1e3 * c['table_bytes_bound_ms']:.1f} us -> {100 * c['extract_share_of_bound']:.1f} % of that bound\n")
+                        f"{1e3 * c['table_bytes_bound_ms']:.1f} us -> {100 * c['extract_share_of_bound']:.1f} % of that bound\n"
+                        f"  copy of the live voxels into a cleared map of the same capacity: {1e3 * c['copy_ms']:.1f} us (one launch), {c['copy_stats']}; 8 B per slot + 32 B "
+                        f"per live slot ({c['live_slots']}) + 40 B per copied voxel at hbm_copy {1e3 * c['copy_bound_ms']:.1f} us -> {100 * c['copy_share_of_bound']:.1f} % of that bound\n"
+                        f"  carve with the batch's last map under its pose (radius 1, margin16 8): keep_count 1 (every voxel protected) {1e3 * c['carve_dry_ms']:.1f} us "
+                        f"(mean of 5), counts {c['carve_dry_counts']}; keep_count 0 {1e3 * c['carve_ms']:.1f} us (one launch), counts {c['carve_counts']} (live, tested, carved); "
+                        f"8 B per slot + 32 B per live slot at hbm_copy {1e3 * c['carve_bound_ms']:.1f} us -> {100 * c['carve_dry_share_of_bound']:.1f} % / "
+                        f"{100 * c['carve_share_of_bound']:.1f} % of that bound\n")
             if g:
                 f.write(f"{g['lanes']} lanes in {g['groups']} groups, {g['frames_per_step_per_lane']}-frame steps, median of {g['rounds']} alternating rounds of "
                         f"{g['steps']} steps, clouds at step {g['cloud_step']}:\n  without clouds {g['frames_per_s_plain']:.0f} frames/s ({g['step_ms_plain']:.1f} ms / step), "
@@ -428,7 +486,10 @@ def main():
                         f"  with clouds, every keyframe cloud inserted into its lane's voxel map after each call (0.1 m, 2^{g['voxel_lane_log2']} slots per lane): "
                         f"{g['frames_per_s_clouds_voxel']:.0f} frames/s ({g['step_ms_clouds_voxel']:.1f} ms / step): ratio to clouds alone "
                         f"{g['ratio_voxel_to_clouds']:.3f}; rounds: {[round(x) for x in g['all_clouds_voxel']]}; per round "
-                        f"{[round(x, 3) for x in g['round_ratios_voxel_to_clouds']]}; totals over all lane maps: {g['voxel_totals_over_all_lane_maps']}\n")
+                        f"{[round(x, 3) for x in g['round_ratios_voxel_to_clouds']]}; totals over all lane maps: {g['voxel_totals_over_all_lane_maps']}\n"
+                        f"  the same with every keyframe's map carving its lane's map before its cloud goes in (defaults): {g['frames_per_s_clouds_voxel_carve']:.0f} frames/s "
+                        f"({g['step_ms_clouds_voxel_carve']:.1f} ms / step): ratio to insert only {g['ratio_carve_to_voxel']:.3f}; rounds: "
+                        f"{[round(x) for x in g['all_clouds_voxel_carve']]}; per round {[round(x, 3) for x in g['round_ratios_carve_to_voxel']]}\n")
 
 
 if __name__ == "__main__":
