@@ -2,7 +2,9 @@
 // whose solve is ceres::Solve with DENSE_SCHUR (:9-12,140) over ReprojectionFactor residuals
 // (src/reprojection_factor.cpp:10-88), quaternion (x) identity local parameterization (:19-20,123),
 // oldest pose constant (:130).  LM semantics: SURVEY.md Appendix B; the step control itself is host/lm.cpp
-// (svo_lm_solve), this file provides its two passes as HIP kernels plus the graph bookkeeping.
+// (svo_lm_solve), this file provides its two passes as HIP kernels.  What never calls HIP is plain C++ under host/: the sliding-window
+// graph (ba_graph.h), the problem layout — CSR, chunks, destination tables, staging image — (ba_layout.h) and the admission ledger
+// (ba_admission.h); the C-ABI entry points here are thin wrappers over them.
 //
 // Pass A "linearize" and pass B "backsub" are single sweeps over the observations (landmark-major CSR, wave chunks of
 // <= 64 observations made of whole landmarks, lane = observation):
@@ -43,22 +45,17 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include <errno.h>
-#include <fcntl.h>
-#include <signal.h>
-#include <sys/mman.h>
-#include <sys/types.h>
-#include <unistd.h>
-
 #include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <sched.h>
 #include <chrono>
-#include <deque>
 #include <memory>
 #include <vector>
 
+#include "ba_admission.h"
+#include "ba_graph.h"
+#include "ba_layout.h"
 #include "kernels.h"
 #include "group_kernels.h"
 #include "lm_decide.h"
@@ -71,99 +68,27 @@ int svo_rccl_allreduce_f64(void* buf, size_t count, void* comm, hipStream_t stre
 bool svo_throughput_mode();  // host/pipeline.cpp: more than two pipelines share the process
 
 namespace {
-std::atomic<int> g_group_lanes{0};  // lanes of the live pipeline groups of this process (svo_ba_note_group_lanes)
 int g_ba_cu_share = 32;  // CUs of every 32 the adjusters' streams may use (SVO_BA_CU_SHARE; 32 = unmasked)
-// Workgroups of admitted kernels whose workgroups wait for each other (see ba_fused_budget), per device: a process that drives
-// several GPUs (one svo_ctx each) must not let one device's adjusters draw from another device's budget.
+// Workgroups of admitted kernels whose workgroups wait for each other (see ba_fused_budget) are counted per device — a process that
+// drives several GPUs (one svo_ctx each) must not let one device's adjusters draw from another device's budget — and across
+// PROCESSES (round 5): host/ba_admission.h.  The shared table is /dev/shm/svo_admit_<PCI bus id>; SVO_BA_XPROC=0 keeps the
+// admission per process.
 constexpr int SVO_MAX_DEVICES = 16;
-std::atomic<int> g_fused_blocks[SVO_MAX_DEVICES];
 int ba_fused_budget(int device);
-// ... and across PROCESSES (round 5): the budget belongs to the GPU, not to a process.  /dev/shm/svo_admit_<PCI bus id> holds 64
-// slots {pid, admitted workgroups}; a process claims a slot (or the slot of a process that no longer exists), mirrors its own
-// admitted total there and counts the live slots of the others against the same budget.  Without /dev/shm (or with
-// SVO_BA_XPROC=0) the admission is per process as before; a solve that still cannot become co-resident gives up within its
-// bound and is re-run (ba_after_giveup), it is never lost.
-struct XprocTable { int magic; int pad; int slot[64][2]; };
-struct Xproc {
-  XprocTable* t = nullptr;
-  int mine = -1;
-  bool tried = false;
-};
-Xproc g_xproc[SVO_MAX_DEVICES];
-std::mutex g_xproc_mu;
-Xproc& xproc_for(int dev) {
-  Xproc& x = g_xproc[dev];
-  std::lock_guard<std::mutex> g(g_xproc_mu);
-  if (x.tried) return x;
-  x.tried = true;
-  if (const char* e = getenv("SVO_BA_XPROC")) if (*e && atoi(e) == 0) return x;
-  char bus[64] = {0};
-  if (hipDeviceGetPCIBusId(bus, sizeof(bus) - 1, dev) != hipSuccess) return x;
-  for (char* c = bus; *c; ++c) if (*c == ':' || *c == '.') *c = '_';
-  char path[128];
-  snprintf(path, sizeof(path), "/dev/shm/svo_admit_%s", bus);
-  const int fd = open(path, O_RDWR | O_CREAT, 0666);
-  if (fd < 0) return x;
-  if (ftruncate(fd, sizeof(XprocTable)) != 0) { close(fd); return x; }
-  void* m = mmap(nullptr, sizeof(XprocTable), PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-  close(fd);
-  if (m == MAP_FAILED) return x;
-  XprocTable* t = static_cast<XprocTable*>(m);
-  const int me = (int)getpid();
-  for (int pass = 0; pass < 2 && x.mine < 0; ++pass)
-    for (int i = 0; i < 64 && x.mine < 0; ++i) {
-      int owner = __atomic_load_n(&t->slot[i][0], __ATOMIC_ACQUIRE);
-      const bool dead = owner != 0 && owner != me && kill(owner, 0) != 0 && errno == ESRCH;
-      if (owner == me || (pass == 1 && (owner == 0 || dead))) {
-        if (owner == me || __atomic_compare_exchange_n(&t->slot[i][0], &owner, me, false, __ATOMIC_ACQ_REL, __ATOMIC_ACQUIRE)) {
-          __atomic_store_n(&t->slot[i][1], 0, __ATOMIC_RELEASE);
-          x.mine = i;
-        }
-      }
-    }
-  if (x.mine >= 0) x.t = t; else munmap(m, sizeof(XprocTable));
-  return x;
+BaLedger& ba_ledger(int dev) {
+  static std::mutex mu;
+  static BaLedger* ledger[SVO_MAX_DEVICES];  // live as long as the process
+  dev = dev >= 0 && dev < SVO_MAX_DEVICES ? dev : 0;
+  std::lock_guard<std::mutex> g(mu);
+  if (ledger[dev]) return *ledger[dev];
+  char bus[64] = {0}, path[128] = {0};
+  const char* e = getenv("SVO_BA_XPROC");
+  if (!(e && *e && atoi(e) == 0) && hipDeviceGetPCIBusId(bus, sizeof(bus) - 1, dev) == hipSuccess) {
+    for (char* c = bus; *c; ++c) if (*c == ':' || *c == '.') *c = '_';
+    snprintf(path, sizeof(path), "/dev/shm/svo_admit_%s", bus);
+  }
+  return *(ledger[dev] = new BaLedger(path[0] ? path : nullptr, dev));
 }
-// workgroups the OTHER live processes have admitted on this device
-int xproc_others(Xproc& x) {
-  if (!x.t) return 0;
-  int sum = 0;
-  for (int i = 0; i < 64; ++i) {
-    if (i == x.mine) continue;
-    const int owner = __atomic_load_n(&x.t->slot[i][0], __ATOMIC_ACQUIRE);
-    if (owner == 0) continue;
-    const int b = __atomic_load_n(&x.t->slot[i][1], __ATOMIC_ACQUIRE);
-    if (b > 0 && (kill(owner, 0) == 0 || errno != ESRCH)) sum += b;
-  }
-  return sum;
-}
-struct FusedAdmission {
-  int blocks = 0, device = 0;
-  bool admit(int n, int dev) {
-    dev = dev >= 0 && dev < SVO_MAX_DEVICES ? dev : 0;
-    const int budget = ba_fused_budget(dev);
-    if (g_fused_blocks[dev].fetch_add(n, std::memory_order_acq_rel) + n > budget) { g_fused_blocks[dev].fetch_sub(n, std::memory_order_acq_rel); return false; }
-    Xproc& x = xproc_for(dev);
-    if (x.t) {  // publish first, then look at the others: two processes racing may both back off, never both pass
-      const int mine_now = __atomic_add_fetch(&x.t->slot[x.mine][1], n, __ATOMIC_ACQ_REL);
-      if (mine_now + xproc_others(x) > budget) {
-        __atomic_sub_fetch(&x.t->slot[x.mine][1], n, __ATOMIC_ACQ_REL);
-        g_fused_blocks[dev].fetch_sub(n, std::memory_order_acq_rel);
-        return false;
-      }
-    }
-    blocks = n; device = dev;
-    return true;
-  }
-  void release() {
-    if (!blocks) return;
-    g_fused_blocks[device].fetch_sub(blocks, std::memory_order_acq_rel);
-    Xproc& x = g_xproc[device];
-    if (x.t) __atomic_sub_fetch(&x.t->slot[x.mine][1], blocks, __ATOMIC_ACQ_REL);
-    blocks = 0;
-  }
-  ~FusedAdmission() { release(); }
-};
 constexpr double MIN_DIAG = 1e-6, MAX_DIAG = 1e32, LM_MIN_RADIUS_BULK = 1e-32;
 constexpr int BULK_RING = 8;   // status records of the device-side step control (bulk path) the host may lag behind
 constexpr int PAY2_SLOTS = 8;  // payload2 (4 doubles) is padded to 8 so that payload1 starts 64-byte aligned behind it
@@ -3202,7 +3127,7 @@ struct svo_ba {
   svo_ctx* ctx = nullptr;
   svo_camera_info cam{};
   svo_ba_options opt{};
-  int window_size = 5, max_landmarks = 0, max_obs = 0, max_poses = 0;
+  int max_landmarks = 0, max_obs = 0, max_poses = 0;
   svo_allreduce_fn allreduce = nullptr;   // in-process emulation of the collective (tests)
   void* allreduce_user = nullptr;
   void* comm = nullptr;                   // ncclComm_t of a sharded run (svo_ba_set_comm)
@@ -3212,9 +3137,8 @@ struct svo_ba {
   size_t cap_part1 = 0, cap_part2 = 0, cap_res = 0;   // granules of the partial store / of ba_lm_kernel's totals
   double* d_res = nullptr;          // ba_lm_kernel: the E wire totals of the running iteration (+ the posted clock), tagged granules
   unsigned long long tag_seq = 0;   // host-driven launches: one tag per op (ba_next_tag)
-  int tab_max_words = 0;            // largest chunk table of the loaded problem (u16 words)
-  double flops_iter = 0, bytes_iter = 0;                       // SURVEY 8(d) algorithmic f64 flops / bytes of ONE LM iteration of the loaded problem
-  double acc_flops = 0, acc_bytes = 0, acc_solves = 0, acc_iters = 0;  // ... summed over the solves since the last svo_ba_work(reset)
+  BaLayout layout;                  // CSR, chunks, tables and image offsets of the loaded problem (host/ba_layout.h)
+  double acc_flops = 0, acc_bytes = 0, acc_solves = 0, acc_iters = 0;  // layout.flops_iter / bytes_iter summed over the solves since the last svo_ba_work(reset)
   std::vector<double> h_poses;            // K x 7 current poses (updated in place by svo_lm_solve)
   int n_points = 0;
   uint8_t* d_arena = nullptr;     // all per-solve inputs in one allocation: one H2D per solve
@@ -3234,11 +3158,10 @@ struct svo_ba {
   int* h_flag = nullptr;
   double* h_step = nullptr;
   bool res_export = false;       // the device-resident solve delivers the landmarks into pinned memory
-  bool host_points_valid = false;  // ... and did: h_arena + arena_pts_off holds the solved landmarks
-  size_t arena_pts_off = 0, arena_bytes = 0;
+  bool host_points_valid = false;  // ... and did: h_out_points holds the solved landmarks
   bool arena_dirty = false;      // h_arena holds a problem image that is not on the device yet
   double* h_out_points = nullptr;  // pinned, GPU-written only
-  FusedAdmission res_admission;  // ba_lm_kernel's workgroups, admitted for the duration of a solve
+  BaAdmission res_admission;     // ba_lm_kernel's workgroups, admitted for the duration of a solve
   // device-resident solve (ba_lm_kernel): counter block, pinned result block, state of the launch in flight
   unsigned* d_lmc = nullptr;
   unsigned* d_lmdbg = nullptr;   // SVO_BA_TRACE: last command of every workgroup of ba_lm_kernel
@@ -3266,30 +3189,15 @@ struct svo_ba {
   bool lm_counters_dirty = false;  // the last kernel did not leave through its clean exit: zero the counter before the next launch
   bool lm_have_base = false;       // lm_base describes the counter (false until the first clean solve)
   bool arena_partial = false;      // the last solve read the problem image from h_arena in place: d_arena lacks the tables, h_arena the solved state
-  size_t arena_cpts_off = 0, arena_p0_off = 0, arena_p1_off = 0;
   std::chrono::steady_clock::time_point lm_t0;
   double* h_pay = nullptr;
   // current / candidate buffers of the running solve (swapped on every accepted step)
   double *cur_points = nullptr, *cand_points = nullptr, *cur_poses = nullptr, *cand_poses = nullptr;
-  bool have_scale = false;
-  std::vector<double> mirror;     // bulk modes: S with the pair blocks mirrored
-  // sliding-window graph (BundleAdjuster state, host side; ids sequential — SURVEY C-3)
-  struct Obs { float u, v; int64_t id; };
-  struct PoseVar { double pose[7]; std::vector<Obs> obs; };
-  std::deque<PoseVar> window;
-  std::vector<double> feat_pos;  // 3 per feature id
-  bool new_frame_added = false;
-  std::vector<int64_t> solve_lm_ids;
-  bool upload_has_ids = false;   // solve_lm_ids describes the landmarks of the problem being uploaded (svo_ba_solve_prepare)
+  BaGraph graph;                 // sliding-window graph (BundleAdjuster state, host/ba_graph.h)
   float4* store = nullptr; unsigned store_mask = 0;  // device-resident landmark store of the stream (svo_ba_attach_store), keyed by feature id
-  float4* h_store_stage = nullptr; unsigned* h_store_slot = nullptr; size_t store_stage_cap = 0;  // pinned staging of the scatter behind a host-driven solve
-  std::vector<double> s_poses, s_points, s_uv, s_out_pts;   // per-solve scratch of svo_ba_solve (kept: no allocation per keyframe)
-  std::vector<int32_t> s_op, s_oj;
-  std::vector<int32_t> u_lm_start, u_chunks, u_cnt;  // scratch of ba_upload
-  std::vector<uint16_t> u_tab; std::vector<uint32_t> u_tab_off;  // the chunk tables of the loaded problem
+  float4* h_store_stage = nullptr; size_t store_stage_cap = 0;  // pinned staging of the scatter behind a host-driven solve
   unsigned* d_arrive = nullptr; unsigned arrive_total = 0; int seq = 0;
   bool upload_pending = false;  // H2D of the problem image enqueued, not yet known complete
-  bool mfma_ok = false;   // bulk problem eligible for ba_linearize_mfma_kernel (n <= 128, one observation per (landmark, pose))
   svo_lm_stats stats{};
   // SVO_TIMING accumulators
   double lm_tp[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -3389,18 +3297,6 @@ static int ba_alloc(svo_ba* ba) {
   return SVO_OK;
 }
 
-extern "C" void svo_ba_default_options(svo_ba_options* o) {
-  if (!o) return;
-  o->max_iterations = 50;                           // Ceres default
-  o->max_time_s = svo_ref::BA_MAX_SOLVER_TIME_S;    // src/bundle_adjuster.cpp:11
-  o->function_tolerance = 1e-6;
-  o->gradient_tolerance = 1e-10;
-  o->parameter_tolerance = 1e-8;
-  o->initial_radius = 1e4;
-  o->max_features = svo_ref::MAX_FEATURES;          // src/bundle_adjuster.hpp:75
-  o->accumulation = SVO_BA_ACC_AUTO;
-}
-
 extern "C" int svo_ba_create(svo_ctx* ctx, svo_ba** out, int window_size, const svo_camera_info* cam,
                              const svo_ba_options* opt, int max_landmarks, int max_observations) {
   if (!ctx || !out || !cam) return SVO_ERR_INVALID;
@@ -3411,7 +3307,7 @@ extern "C" int svo_ba_create(svo_ctx* ctx, svo_ba** out, int window_size, const 
   ba->ctx = ctx;
   ba->cam = *cam;
   if (opt) ba->opt = *opt; else svo_ba_default_options(&ba->opt);
-  ba->window_size = window_size;
+  ba->graph.init(window_size, ba->opt.max_features);
   ba->max_poses = window_size + 1 > 2 ? window_size + 1 : 2;
   if (ba->max_poses > 64) ba->max_poses = 64;
   ba->max_landmarks = max_landmarks;
@@ -3507,9 +3403,6 @@ int svo_ba_use_stream(svo_ba* ba, void* stream) {
   return SVO_OK;
 }
 
-// host/group.cpp: a pipeline group of `delta` lanes was created (> 0) or destroyed (< 0)
-void svo_ba_note_group_lanes(int delta) { g_group_lanes.fetch_add(delta, std::memory_order_relaxed); }
-
 extern "C" int svo_ba_set_solve_form(svo_ba* ba, int form) {
   if (!ba || form < -1 || form > 1) return SVO_ERR_INVALID;
   ba->lm_form = form;
@@ -3550,10 +3443,6 @@ extern "C" int svo_ba_last_stats(svo_ba* ba, svo_lm_stats* stats) {
 }
 
 
-// Upload a landmark-major problem (shared by the bulk API and the sliding-window solve).
-// Destination index of pose-pair block (ka <= kb) among the F (F + 1) / 2 upper blocks, row-major.
-static inline int ba_upper_index(int ka, int kb, int F) { return ka * F - ka * (ka - 1) / 2 + (kb - ka); }
-
 // The granule stores of the loaded problem: partials of pass A (NG x Epad), of pass B (2 x NG x 4), ba_lm_kernel's totals
 // (E + 1).  Window-sized problems reach their sizes within a few keyframes; nothing is allocated per solve afterwards.
 // Fresh stores are zeroed: no command ever carries tag 0.
@@ -3581,220 +3470,56 @@ static int ba_ensure_partials(svo_ba* ba) {
   return rc;
 }
 
+// Upload a landmark-major problem (shared by the bulk API and the sliding-window solve; lm_ids: the landmarks' feature ids, the keys
+// of their landmark-store entries — null: the problem has none): plan the layout, grow the arena if needed, fill the pinned staging
+// image, hand the dimensions and `device arena + offset` pointers to the kernels' view of the problem.
+static_assert(sizeof(BaSlotRec) == sizeof(int4), "the kernels read a slot record as one int4");
 static int ba_upload_checked(svo_ba* ba, int K, const double* poses7, int npts, const double* points3, int M,
-                     const int32_t* op, const int32_t* oj, const double* uv) {
+                     const int32_t* op, const int32_t* oj, const double* uv, const int64_t* lm_ids) {
   svo_ctx* ctx = ba->ctx;
   SVO_REQUIRE(ctx, K >= 1 && K <= ba->max_poses, "ba: pose count outside the window capacity");
   SVO_REQUIRE(ctx, npts >= 0 && (size_t)npts <= ba->cap_points && M >= 0 && (size_t)M <= ba->cap_obs, "ba: problem exceeds capacity");
   BaDev& d = ba->d;
+  BaLayout& l = ba->layout;
   if (ba->upload_pending) { SVO_HIP_CHECK(ctx, hipStreamSynchronize(ba->stream)); ba->upload_pending = false; }
-  d.K = K; d.n = 6 * (K - 1); d.M = M; d.f = ba->cam.focal; d.cx = ba->cam.cx; d.cy = ba->cam.cy;
-  ba->n_points = npts;
-  // CSR over landmark index + wave chunks (<= 64 observations, whole landmarks).  All scratch vectors are members:
-  // a keyframe's solve allocates nothing.
-  std::vector<int32_t>&lm_start = ba->u_lm_start, &chunks = ba->u_chunks;
-  lm_start.assign((size_t)npts + 1, 0);
-  chunks.clear();
-  for (int o = 0; o < M; ++o) {
-    SVO_REQUIRE(ctx, oj[o] >= 0 && oj[o] < npts && op[o] >= 0 && op[o] < K, "ba: observation index out of range");
-    SVO_REQUIRE(ctx, o == 0 || oj[o] >= oj[o - 1], "ba: observations must be sorted by landmark");
-    lm_start[oj[o] + 1]++;
-  }
-  bool has_empty_landmark = false;
-  for (int j = 0; j < npts; ++j) {
-    SVO_REQUIRE(ctx, lm_start[j + 1] <= 64, "ba: a landmark has more than 64 observations");
-    has_empty_landmark |= lm_start[j + 1] == 0;
-    lm_start[j + 1] += lm_start[j];
-  }
-  // chunks (declared with the summation order, oracle/ora_ba.cpp): whole landmarks, greedily, at most 64 observations each
-  chunks.push_back(0);
-  int cur = 0;
-  for (int j = 0; j < npts; ++j) {
-    const int len = lm_start[j + 1] - lm_start[j];
-    if (len == 0) continue;
-    if (cur + len > 64) { chunks.push_back(lm_start[j]); cur = 0; }
-    cur += len;
-  }
-  chunks.push_back(M);
-  d.C = (int)chunks.size() - 1;
-  d.L = npts;
-  {
-    // 466 flops per observation + per landmark 50 + 144 L + 216 L (L + 1) / 2; 24 B per observation, 48 B per landmark, 56 B per pose
-    double fl = 466.0 * M;
-    int n_seen = 0;
-    for (int j = 0; j < npts; ++j) {
-      const double Lj = lm_start[j + 1] - lm_start[j];
-      if (Lj > 0) { fl += 50.0 + 144.0 * Lj + 108.0 * Lj * (Lj + 1.0); ++n_seen; }
-    }
-    ba->flops_iter = fl;
-    ba->bytes_iter = 24.0 * M + 48.0 * n_seen + 56.0 * K;
-  }
-  hipStream_t st = ba->stream;
-  std::vector<uint16_t>& tab = ba->u_tab;
-  std::vector<uint32_t>& tab_off = ba->u_tab_off;
-  tab.clear(); tab_off.clear();
-  ba->tab_max_words = 0;
-  {
-    const int F = K - 1;
-    bool dup = false;
-    for (int j = 0; j < npts; ++j) {
-      uint64_t seen = 0;
-      for (int o = lm_start[j]; o < lm_start[j + 1]; ++o) {
-        const uint64_t bit = 1ull << op[o];
-        dup |= (seen & bit) != 0;
-        seen |= bit;
-      }
-    }
-    // deterministic mode ("chunk order"): G chunks per group, NG groups, E wire elements; the partial store holds E x NG granules
-    const int nU = F * (F + 1) / 2;
-    d.G = d.C <= 128 ? 1 : (d.C + 127) / 128;
-    // partials in the store: one per chunk (the groups of G are applied by the level-2 sums) while that stays below 64 MB —
-    // a 1280x720 window: 1,500 chunks x 1,920 elements = 46 MB; config 4 (6,900 chunks x 7,472 elements) keeps one partial per GROUP
-    // (and at most 2,048 partials: the level-2 reducers hold all partials of an element in 4,096 doubles of LDS)
-    d.CPW = ((size_t)((36 * nU + 33 * F + 2 + 7) & ~7) * (size_t)d.C * 16 <= ((size_t)64 << 20) && d.C <= 2048) ? 1 : d.G;
-    d.GS = d.G / d.CPW;
-    d.NG = d.C > 0 ? (d.C + d.CPW - 1) / d.CPW : 0;
-    d.E = 36 * nU + 33 * F + 2;
-    d.Epad = (d.E + 7) & ~7;
-    d.det = (size_t)d.Epad * (size_t)(d.NG > 0 ? d.NG : 1) * 16 <= ((size_t)512 << 20) ? 1 : 0;
-    if (ba->opt.accumulation == SVO_BA_ACC_ATOMICS || ba->opt.accumulation == SVO_BA_ACC_MFMA) d.det = 0;
-    SVO_REQUIRE(ctx, !(ba->opt.accumulation == SVO_BA_ACC_DETERMINISTIC && !d.det), "ba: problem too large for deterministic accumulation");
-    ba->mfma_ok = !dup && d.n <= 128 && d.n > 0 && ba->opt.accumulation != SVO_BA_ACC_ATOMICS;
-    SVO_REQUIRE(ctx, !(ba->opt.accumulation == SVO_BA_ACC_MFMA && !ba->mfma_ok), "ba: MFMA accumulation needs <= 22 poses and one observation per (landmark, pose)");
-    if (d.det) {
-      // Chunk tables (ChunkTab): per chunk the pair entries of every UPPER pose-pair block in (landmark, i, t) order — pair
-      // (i, t >= i) enters block (k_i, k_t) when k_i <= k_t and, transposed, block (k_t, k_i) when t != i and k_t <= k_i (two
-      // observations of one landmark in one pose: both, the direct entry first) — and the lanes of every free pose.
-      std::vector<int32_t>& cur = ba->u_cnt;  // fill cursors: nU block lists, then F pose lists
-      tab_off.reserve((size_t)d.C + 1);
-      tab.reserve((size_t)M * 3 + (size_t)d.C * (size_t)(nU + F + 4));
-      for (int c = 0; c < d.C; ++c) {
-        const int c0 = chunks[c], c1 = chunks[c + 1];
-        cur.assign((size_t)nU + (size_t)F + 2, 0);
-        // pass 1: list lengths
-        for (int i = c0; i < c1; ++i) {
-          const int ki = op[i] - 1;
-          if (ki < 0) continue;
-          cur[nU + ki]++;
-          const int o1 = lm_start[oj[i] + 1];
-          for (int t = i; t < o1; ++t) {
-            const int kt = op[t] - 1;
-            if (kt < 0) continue;
-            if (ki <= kt) cur[ba_upper_index(ki, kt, F)]++;
-            if (t != i && kt <= ki) cur[ba_upper_index(kt, ki, F)]++;
-          }
-        }
-        tab_off.push_back((uint32_t)tab.size());
-        const size_t t0 = tab.size();
-        int n_ent = 0, n_free = 0;
-        for (int q = 0; q < nU; ++q) { const int len = cur[q]; cur[q] = n_ent; tab.push_back((uint16_t)n_ent); n_ent += len; }
-        tab.push_back((uint16_t)n_ent);
-        for (int k = 0; k < F; ++k) { const int len = cur[nU + k]; cur[nU + k] = n_free; tab.push_back((uint16_t)n_free); n_free += len; }
-        tab.push_back((uint16_t)n_free);
-        const size_t e_at = tab.size();
-        tab.resize(e_at + (size_t)n_ent + (size_t)((n_free + 1) / 2), 0);
-        uint16_t* ent = tab.data() + e_at;
-        uint8_t* plane = reinterpret_cast<uint8_t*>(ent + n_ent);
-        // pass 2: fill, every list in (landmark, i, t) / lane order
-        for (int i = c0; i < c1; ++i) {
-          const int ki = op[i] - 1;
-          if (ki < 0) continue;
-          plane[cur[nU + ki]++] = (uint8_t)(i - c0);
-          const int o1 = lm_start[oj[i] + 1];
-          for (int t = i; t < o1; ++t) {
-            const int kt = op[t] - 1;
-            if (kt < 0) continue;
-            if (ki <= kt) ent[cur[ba_upper_index(ki, kt, F)]++] = (uint16_t)((i - c0) | ((t - c0) << 8));
-            if (t != i && kt <= ki) ent[cur[ba_upper_index(kt, ki, F)]++] = (uint16_t)((i - c0) | 0x80 | ((t - c0) << 8));
-          }
-        }
-        if ((tab.size() - t0) & 1) tab.push_back(0);  // tables start on even u16 offsets (read as 32-bit words)
-        ba->tab_max_words = std::max(ba->tab_max_words, (int)(tab.size() - t0));
-      }
-      tab_off.push_back((uint32_t)tab.size());
-    }
-  }
-  // ---- one pinned staging image, one H2D: [points | points (candidate copy) | per-slot records | per-slot uv |
-  //      chunk tables | table offsets | poses x 2]
-  const size_t nslots = (size_t)d.C * 64;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  size_t off = 0;
-  const size_t o_pts = off; off = al(off + sizeof(double) * 3 * (size_t)npts);
-  ba->arena_pts_off = o_pts; ba->host_points_valid = false;
-  const size_t o_cpts = off; off = al(off + sizeof(double) * 3 * (size_t)npts);
-  const size_t o_rec = off; off = al(off + sizeof(int4) * nslots);
-  const size_t o_uv = off; off = al(off + sizeof(double) * 2 * nslots);
-  const size_t o_tab = off; off = al(off + sizeof(uint16_t) * tab.size());
-  const size_t o_toff = off; off = al(off + sizeof(uint32_t) * tab_off.size());
-  const bool with_keys = ba->upload_has_ids && ba->store && (int)ba->solve_lm_ids.size() == npts;
-  const size_t o_key = off; if (with_keys) off = al(off + sizeof(unsigned) * (size_t)npts);
-  const size_t o_p0 = off; off = al(off + sizeof(double) * 7 * (size_t)K);
-  const size_t o_p1 = off; off = al(off + sizeof(double) * 7 * (size_t)K);
-  const size_t total = off;
-  if (total > ba->arena_cap) {
+  const char* why = nullptr;
+  if (l.plan(K, npts, M, op, oj, ba->opt.accumulation, lm_ids && ba->store, &why) != SVO_OK) { ctx->err = why; return SVO_ERR_INVALID; }
+  if (l.total > ba->arena_cap) {
     if (ba->d_arena) (void)hipFree(ba->d_arena);
     if (ba->h_arena) (void)hipHostFree(ba->h_arena);
     ba->d_arena = nullptr; ba->h_arena = nullptr;
-    ba->arena_cap = total + total / 4 + 4096;
+    ba->arena_cap = l.total + l.total / 4 + 4096;
     SVO_HIP_CHECK(ctx, hipMalloc((void**)&ba->d_arena, ba->arena_cap));
     SVO_HIP_CHECK(ctx, hipHostMalloc((void**)&ba->h_arena, ba->arena_cap, hipHostMallocDefault));
   }
-  uint8_t* h = ba->h_arena;
-  if (npts) { memcpy(h + o_pts, points3, sizeof(double) * 3 * (size_t)npts); memcpy(h + o_cpts, points3, sizeof(double) * 3 * (size_t)npts); }
-  {
-    int4* rec = reinterpret_cast<int4*>(h + o_rec);
-    double* suv = reinterpret_cast<double*>(h + o_uv);
-    for (int c = 0; c < d.C; ++c) {
-      const int c0 = chunks[c], c1 = chunks[c + 1];
-      for (int lane = 0; lane < 64; ++lane) {
-        const size_t slot = (size_t)c * 64 + lane;
-        const int o = c0 + lane;
-        if (o < c1) {
-          const int j = oj[o];
-          rec[slot] = int4{op[o], j, lm_start[j] - c0, lm_start[j + 1] - lm_start[j]};
-          suv[2 * slot] = uv[2 * (size_t)o]; suv[2 * slot + 1] = uv[2 * (size_t)o + 1];
-        } else {
-          rec[slot] = int4{-1, 0, lane, 0};
-          suv[2 * slot] = 0.0; suv[2 * slot + 1] = 0.0;
-        }
-      }
-    }
-  }
-  if (!tab.empty()) memcpy(h + o_tab, tab.data(), sizeof(uint16_t) * tab.size());
-  if (!tab_off.empty()) memcpy(h + o_toff, tab_off.data(), sizeof(uint32_t) * tab_off.size());
-  if (with_keys) { unsigned* k = reinterpret_cast<unsigned*>(h + o_key); for (int j = 0; j < npts; ++j) k[j] = (unsigned)ba->solve_lm_ids[(size_t)j]; }
-  uint8_t* D = ba->d_arena;
-  d.points = (double*)(D + o_pts); d.cand_points = (double*)(D + o_cpts);
-  ba->cur_points = (double*)(D + o_pts); ba->cand_points = (double*)(D + o_cpts);
-  ba->cur_poses = (double*)(D + o_p0); ba->cand_poses = (double*)(D + o_p1);
-  d.rec = (const int4*)(D + o_rec); d.obs_uv = (const double*)(D + o_uv);
-  d.tab = (const uint16_t*)(D + o_tab); d.tab_off = (const uint32_t*)(D + o_toff);
-  d.tab_lds_words = (d.det && ba->tab_max_words > 0 && ba->tab_max_words <= 4096) ? ((ba->tab_max_words + 3) & ~3) : 0;  // host-driven kernels: the chunk's table in LDS (8 KB at most)
-  d.lm_key = with_keys ? (const unsigned*)(D + o_key) : nullptr;
-  memcpy(h + o_p0, poses7, sizeof(double) * 7 * (size_t)K);
-  memcpy(h + o_p1, poses7, sizeof(double) * 7 * (size_t)K);
+  l.write_image(ba->h_arena, op, oj, points3, poses7, uv, lm_ids);
   ba->h_poses.assign(poses7, poses7 + 7 * (size_t)K);
-  d.poses = (double*)(D + o_p0);
-  d.cand_poses = (double*)(D + o_p1);
+  ba->n_points = npts; ba->host_points_valid = false;
+  d.K = l.K; d.n = l.n; d.M = l.M; d.L = l.L; d.C = l.C; d.f = ba->cam.focal; d.cx = ba->cam.cx; d.cy = ba->cam.cy;
+  d.G = l.G; d.NG = l.NG; d.Epad = l.Epad; d.E = l.E; d.CPW = l.CPW; d.GS = l.GS; d.det = l.det;
+  uint8_t* D = ba->d_arena;
+  d.points = ba->cur_points = (double*)(D + l.o_pts); d.cand_points = ba->cand_points = (double*)(D + l.o_cpts);
+  d.poses = ba->cur_poses = (double*)(D + l.o_p0); d.cand_poses = ba->cand_poses = (double*)(D + l.o_p1);
+  d.rec = (const int4*)(D + l.o_rec); d.obs_uv = (const double*)(D + l.o_uv);
+  d.tab = (const uint16_t*)(D + l.o_tab); d.tab_off = (const uint32_t*)(D + l.o_toff);
+  d.tab_lds_words = l.tab_lds_words();
+  d.lm_key = l.with_keys ? (const unsigned*)(D + l.o_key) : nullptr;
   // the image goes up when the solve knows how: read in place by ba_lm_kernel (no blit, no extra launch in front of it), or
   // by one H2D copy (ba_flush_arena)
-  ba->arena_bytes = (total + 15) & ~(size_t)15;
   ba->arena_dirty = true;
   ba->arena_partial = false;
-  ba->arena_cpts_off = o_cpts; ba->arena_p0_off = o_p0; ba->arena_p1_off = o_p1;
-  (void)has_empty_landmark; (void)st;
-  if (d.det) { const int rcp = ba_ensure_partials(ba); if (rcp) return rcp; }
-  return SVO_OK;
+  return d.det ? ba_ensure_partials(ba) : SVO_OK;
 }
 
 // A rejected problem must not leave a half-committed one behind (dimensions of the new problem over the chunk layout and
 // the host copies of the old one): after a failed load the adjuster holds NO problem — svo_ba_solve_problem refuses,
 // svo_ba_read_problem copies nothing.
 static int ba_upload(svo_ba* ba, int K, const double* poses7, int npts, const double* points3, int M,
-                     const int32_t* op, const int32_t* oj, const double* uv) {
+                     const int32_t* op, const int32_t* oj, const double* uv, const int64_t* lm_ids = nullptr) {
   ba->lm_yielded = false; ba->lm_resumes_now = 0;  // (a solve that stepped aside and was never continued goes with its problem)
-  const int rc = ba_upload_checked(ba, K, poses7, npts, points3, M, op, oj, uv);
+  const int rc = ba_upload_checked(ba, K, poses7, npts, points3, M, op, oj, uv, lm_ids);
   if (rc != SVO_OK) {
+    ba->layout.clear();
     ba->d.K = 0; ba->d.n = 0; ba->d.M = 0; ba->d.L = 0; ba->d.C = 0;
     ba->n_points = 0;
     ba->host_points_valid = false;
@@ -3810,29 +3535,26 @@ static int ba_refresh_arena_image(svo_ba* ba) {
   svo_ctx* ctx = ba->ctx;
   const size_t npts = (size_t)ba->n_points;
   if (npts) {
-    double* img = reinterpret_cast<double*>(ba->h_arena + ba->arena_pts_off);
-    if (ba->host_points_valid) {
-      const std::vector<int32_t>& lm = ba->u_lm_start;
-      for (size_t j = 0; j < npts; ++j) {
-        if (j + 1 < lm.size() && lm[j + 1] == lm[j]) continue;  // never observed: keeps its uploaded value
-        img[3 * j] = ba->h_out_points[3 * j]; img[3 * j + 1] = ba->h_out_points[3 * j + 1]; img[3 * j + 2] = ba->h_out_points[3 * j + 2];
-      }
-    } else {
-      std::vector<double> tmp(3 * npts);
+    double* img = reinterpret_cast<double*>(ba->h_arena + ba->layout.o_pts);
+    std::vector<double> tmp;
+    const double* solved = ba->h_out_points;
+    if (!ba->host_points_valid) {
+      tmp.resize(3 * npts);
       SVO_HIP_CHECK(ctx, hipMemcpy(tmp.data(), ba->d.points, sizeof(double) * 3 * npts, hipMemcpyDeviceToHost));
-      const std::vector<int32_t>& lm = ba->u_lm_start;
-      for (size_t j = 0; j < npts; ++j) {
-        if (j + 1 < lm.size() && lm[j + 1] == lm[j]) continue;
-        img[3 * j] = tmp[3 * j]; img[3 * j + 1] = tmp[3 * j + 1]; img[3 * j + 2] = tmp[3 * j + 2];
-      }
+      solved = tmp.data();
     }
-    memcpy(ba->h_arena + ba->arena_cpts_off, img, sizeof(double) * 3 * npts);
+    const std::vector<int32_t>& lm = ba->layout.lm_start;
+    for (size_t j = 0; j < npts; ++j) {
+      if (j + 1 < lm.size() && lm[j + 1] == lm[j]) continue;  // never observed: keeps its uploaded value
+      img[3 * j] = solved[3 * j]; img[3 * j + 1] = solved[3 * j + 1]; img[3 * j + 2] = solved[3 * j + 2];
+    }
+    memcpy(ba->h_arena + ba->layout.o_cpts, img, sizeof(double) * 3 * npts);
   }
-  memcpy(ba->h_arena + ba->arena_p0_off, ba->h_poses.data(), sizeof(double) * 7 * (size_t)ba->d.K);
-  memcpy(ba->h_arena + ba->arena_p1_off, ba->h_poses.data(), sizeof(double) * 7 * (size_t)ba->d.K);
+  memcpy(ba->h_arena + ba->layout.o_p0, ba->h_poses.data(), sizeof(double) * 7 * (size_t)ba->d.K);
+  memcpy(ba->h_arena + ba->layout.o_p1, ba->h_poses.data(), sizeof(double) * 7 * (size_t)ba->d.K);
   uint8_t* D = ba->d_arena;
-  ba->cur_points = (double*)(D + ba->arena_pts_off); ba->cand_points = (double*)(D + ba->arena_cpts_off);
-  ba->cur_poses = (double*)(D + ba->arena_p0_off); ba->cand_poses = (double*)(D + ba->arena_p1_off);
+  ba->cur_points = (double*)(D + ba->layout.o_pts); ba->cand_points = (double*)(D + ba->layout.o_cpts);
+  ba->cur_poses = (double*)(D + ba->layout.o_p0); ba->cand_poses = (double*)(D + ba->layout.o_p1);
   ba->d.points = ba->cur_points; ba->d.cand_points = ba->cand_points; ba->d.poses = ba->cur_poses; ba->d.cand_poses = ba->cand_poses;
   ba->arena_partial = false;
   ba->arena_dirty = true;
@@ -3844,7 +3566,7 @@ static int ba_flush_arena(svo_ba* ba) {
   if (ba->arena_partial) { const int rc = ba_refresh_arena_image(ba); if (rc) return rc; }
   if (!ba->arena_dirty) return SVO_OK;
   svo_ctx* ctx = ba->ctx;
-  SVO_HIP_CHECK(ctx, hipMemcpyAsync(ba->d_arena, ba->h_arena, ba->arena_bytes, hipMemcpyHostToDevice, ba->stream));
+  SVO_HIP_CHECK(ctx, hipMemcpyAsync(ba->d_arena, ba->h_arena, ba->layout.image_bytes(), hipMemcpyHostToDevice, ba->stream));
   ba->arena_dirty = false;
   // no wait here: the pinned staging image is next touched by the host after the solve that follows has
   // drained this stream (ba_lm)
@@ -3923,7 +3645,7 @@ void ba_payload1_out(svo_ba* ba, const double* src, double* dst) {
     double* dU = gc + n;
     for (int ka = 0; ka < F; ++ka)
       for (int kb = ka; kb < F; ++kb) {
-        const double* blk = src + 36 * (size_t)ba_upper_index(ka, kb, F);
+        const double* blk = src + 36 * (size_t)BaLayout::upper_index(ka, kb, F);
         const double* U = src + 36 * (size_t)nU + 33 * (size_t)ka + 12;
         for (int a = 0; a < 6; ++a)
           for (int b = 0; b < 6; ++b) {
@@ -3970,7 +3692,7 @@ int ba_launch_bulk_linearize(svo_ba* ba, double radius, int first, const double*
   const int n = d.n;
   const size_t pay1 = (size_t)n * n + 3 * (size_t)n + 2;
   SvoProfScope prof(ctx, SVO_PROF_BA_LINEARIZE, ba->stream);
-  if (ba->mfma_ok) {
+  if (ba->layout.mfma_ok) {
     const size_t mfma_lds = ba_mfma_lds_bytes(n, d.K - 1);
     const int mfma_grid = std::max(1, std::min(svo_div_up(d.C, MF_WAVES), 256));
     SVO_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)ba_linearize_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mfma_lds));
@@ -4060,7 +3782,7 @@ int ba_lm_admission_cost(int grid, size_t lds, int device, bool multi = false) {
   return (grid * g_fused_per_cu + per_cu - 1) / per_cu;
 }
 
-inline FusedAdmission* ba_resident_admission(svo_ba* ba) { return &ba->res_admission; }
+inline bool ba_admit(svo_ba* ba, int cost, int device) { BaLedger& l = ba_ledger(device); return ba->res_admission.admit(l, cost, ba_fused_budget(l.device)); }
 
 // ---- device-resident solve (ba_lm_kernel): host side -------------------------------------------------------------
 // SVO_BA_DEVICE_LM=0 / 1 forces; default since the end of round 4: ON for every window-sized single-rank deterministic solve that
@@ -4077,7 +3799,7 @@ bool ba_device_lm_wanted() {
   return svo_throughput_mode();
 }
 
-int ba_lm_tab_words(const svo_ba* ba) { return std::max(64, (ba->tab_max_words + 63) & ~63); }
+int ba_lm_tab_words(const svo_ba* ba) { return std::max(64, (ba->layout.tab_max_words + 63) & ~63); }
 size_t ba_lm_lds_bytes(const svo_ba* ba, int kw) { return sizeof(double) * ba_lm_lds_doubles(ba->d.n, ba->d.K, ba_lm_tab_words(ba), kw); }
 
 // Chunks per wavefront a wide solve is offered to the admission with (ba_lm_multi_kernel for more than one; a solve the budget
@@ -4106,7 +3828,7 @@ bool ba_lm_wave_contig() {
 constexpr size_t LMC_LDS_BUDGET = 156 * 1024;
 constexpr int LM_MAX_CHUNKS_GROUPED = 288;   // wide form: 129..288 chunks go to ba_lm_grouped_kernel (144 workgroups at one per CU fit the admission budget)
 constexpr int LMC_MAX_CHUNKS = 256;   // beyond, a single workgroup's rounds take longer than the host-driven loop's launches
-int ba_lmc_tab_words(const svo_ba* ba) { return std::max(64, (ba->tab_max_words + 63) & ~63); }
+int ba_lmc_tab_words(const svo_ba* ba) { return std::max(64, (ba->layout.tab_max_words + 63) & ~63); }
 int ba_lmc_waves(const svo_ba* ba) {
   static const int cap = [] { const char* e = getenv("SVO_BA_COMPACT_WAVES"); const int v = e ? atoi(e) : LMC_MAX_WAVES; return v < 1 ? 1 : (v > LMC_MAX_WAVES ? LMC_MAX_WAVES : v); }();
   const BaDev& d = ba->d;
@@ -4135,14 +3857,14 @@ bool ba_device_lm_fill(svo_ba* ba, int* cost, size_t* lds_out, bool forced, bool
   size_t lds = 0;
   int nw = 0, kw = 1;
   if (compact) {
-    if (d.C > LMC_MAX_CHUNKS || ba->tab_max_words > 4096) return false;
+    if (d.C > LMC_MAX_CHUNKS || ba->layout.tab_max_words > 4096) return false;
     nw = ba_lmc_waves(ba);
     if (nw < 1) return false;
     lds = sizeof(double) * ba_lmc_lds_doubles(d.n, d.K, ba_lmc_tab_words(ba), nw);
   } else {
   // every chunk table in LDS, every chunk its own partial (beyond 128 chunks the grouped kernel sums groups of G chunks first), and
   // the launch must fit the admission budget at all (workgroups that wait for each other): window-sized problems
-  if (d.C > LM_MAX_CHUNKS_GROUPED || d.CPW != 1 || ba->tab_max_words > TAB_LDS_WORDS) return false;
+  if (d.C > LM_MAX_CHUNKS_GROUPED || d.CPW != 1 || ba->layout.tab_max_words > TAB_LDS_WORDS) return false;
   // beyond 128 chunks (ba_lm_grouped_kernel) only on request: measured on configs[2]'s 10-keyframe windows (~210 chunks, E = 2,312 wire
   // elements) the host-driven loop is faster — 780 against 590 frames/s (profiles/r05_exp_single_stream_paths.txt)
   if (d.G > 1 && ba->device_lm != 1) return false;
@@ -4159,7 +3881,7 @@ bool ba_device_lm_fill(svo_ba* ba, int* cost, size_t* lds_out, bool forced, bool
   LmDevArgs& a = L.a;
   a.cnt = ba->d_lmc;
   a.arena_src = resume ? ba->lm_yield_src : (ba->arena_dirty ? ba->h_arena : nullptr);  // read in place by the kernel (zero copy); null: the device arena is complete
-  a.arena_dst = ba->d_arena; a.arena_bytes = ba->arena_bytes;
+  a.arena_dst = ba->d_arena; a.arena_bytes = ba->layout.image_bytes();
   a.points_a = ba->cur_points; a.points_b = ba->cand_points;
   a.export_points = ba->n_points ? ba->h_out_points : nullptr;
   a.store = d.lm_key ? ba->store : nullptr; a.store_mask = ba->store_mask;
@@ -4203,7 +3925,6 @@ int ba_device_lm_launch(svo_ba** bas, int n, hipStream_t st, bool forced, unsign
   // on 16 queues: 30 k against 25 k frames/s at 128 lanes); with one hardware queue per stream the wide form alone is faster (37-51 k
   // against 27-36 k) — a 3 ms compact solve holds its line for 3 ms.
   static const bool overflow = [] { const char* e = getenv("SVO_BA_OVERFLOW"); return e && *e && atoi(e) != 0; }();
-  (void)g_group_lanes;
   bool to_compact[SVO_MAX_LANES] = {};
   // ---- the wide form (ba_lm_kernel): admitted against the budget of co-resident waiting workgroups
   int launched_total = 0;
@@ -4223,7 +3944,7 @@ int ba_device_lm_launch(svo_ba** bas, int n, hipStream_t st, bool forced, unsign
     if (ba_wants_compact(ba) && !ba->lm_yielded) { to_compact[i] = true; continue; }
     if (!ba_device_lm_fill(ba, &cost, &lds, forced)) continue;
     if (lds > 32 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) != hipSuccess) continue;
-    bool admitted = ba_resident_admission(ba)->admit(cost, ba->ctx->device);
+    bool admitted = ba_admit(ba, cost, ba->ctx->device);
     if (!admitted && form == 2 && ba->lm_wave_chunks <= 0) {
       // The budget refuses the solve at the default k: it rides this launch on fewer workgroups — the first larger k that fits, as
       // long as the kernel's workgroups per CU at that k's LDS (k chunk tables per wavefront) stay what they are at the default, so
@@ -4239,7 +3960,7 @@ int ba_device_lm_launch(svo_ba** bas, int n, hipStream_t st, bool forced, unsign
         if (lds_k > 120 * 1024 || per_cu0 <= 0 || ba_lm_per_cu(lds_k, true) < per_cu0) break;
         if (lds_k > 32 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) != hipSuccess) break;
         const int cost_k = ba_lm_admission_cost(blocks, lds_k, dev, true);
-        admitted = ba_resident_admission(ba)->admit(cost_k, dev);
+        admitted = ba_admit(ba, cost_k, dev);
         if (admitted) { ba->h_lane->a.wave_chunks = k; lds = lds_k; }
       }
     }
@@ -4247,7 +3968,7 @@ int ba_device_lm_launch(svo_ba** bas, int n, hipStream_t st, bool forced, unsign
     // the counter starts from zero: cleared in front of the launch (the adjuster's previous solve no longer touches it
     // once its completion word is out)
     if (ba->lm_counters_dirty || !ba->lm_have_base) {
-      if (hipMemsetAsync(ba->d_lmc, 0, LMC_WORDS * sizeof(unsigned), st) != hipSuccess) { ba_resident_admission(ba)->release(); continue; }
+      if (hipMemsetAsync(ba->d_lmc, 0, LMC_WORDS * sizeof(unsigned), st) != hipSuccess) { ba->res_admission.release(); continue; }
     }
     ba->lm_counters_dirty = false;
     ptrs.p[launched] = ba->h_lane;
@@ -4266,7 +3987,7 @@ int ba_device_lm_launch(svo_ba** bas, int n, hipStream_t st, bool forced, unsign
       else hipLaunchKernelGGL(ba_lm_kernel, dim3(max_c, launched), dim3(128), max_lds, st, ptrs);
     }
     if (hipGetLastError() != hipSuccess) {
-      for (int i = 0; i < launched; ++i) ba_resident_admission(took[i])->release();
+      for (int i = 0; i < launched; ++i) took[i]->res_admission.release();
       launched = 0;
     }
     for (int i = 0; i < launched; ++i) {
@@ -4346,7 +4067,7 @@ int ba_device_lm_end(svo_ba* ba, svo_ba_summary* sum) {
   const bool was_compact = ba->lm_compact_inflight;
   ba->lm_compact_inflight = false;
   const int rc = ba_wait_flag(ba, ba->seq);
-  ba_resident_admission(ba)->release();
+  ba->res_admission.release();
   if (rc) {
     // a wait inside the kernel gave up (or the launch never ran): drain, and never trust the counter again
     (void)hipStreamSynchronize(ba->lm_stream);
@@ -4412,7 +4133,7 @@ int ba_device_lm_end(svo_ba* ba, svo_ba_summary* sum) {
         const int nU = (d.K - 1) * d.K / 2, F = d.K - 1;
         for (int b = 0; b < nb; ++b) {
           const int c = b * LM_CPW * (ba->h_lane->a.wave_contig ? kw : 1);  // the first chunk of the workgroup's first wavefront
-          const uint16_t* w = ba->u_tab.data() + ba->u_tab_off[(size_t)c];
+          const uint16_t* w = ba->layout.tab.data() + ba->layout.tab_off[(size_t)c];
           int ne = 0, longest = 0, plong = 0;
           for (int q = 0; q < nU; ++q) { const int len = w[q + 1] - w[q]; ne += len > 0; longest = std::max(longest, len); }
           for (int k = 0; k < F; ++k) plong = std::max(plong, (int)w[nU + 1 + k + 1] - (int)w[nU + 1 + k]);
@@ -4760,8 +4481,8 @@ static int ba_lm_bulk_device(svo_ba* ba, svo_ba_summary* sum) {
 // host-driven loop, the same bits.  The wide form is avoided for the next 64 solves of this adjuster.
 static void ba_after_giveup(svo_ba* ba) {
   uint8_t* D = ba->d_arena;
-  ba->cur_points = (double*)(D + ba->arena_pts_off); ba->cand_points = (double*)(D + ba->arena_cpts_off);
-  ba->cur_poses = (double*)(D + ba->arena_p0_off); ba->cand_poses = (double*)(D + ba->arena_p1_off);
+  ba->cur_points = (double*)(D + ba->layout.o_pts); ba->cand_points = (double*)(D + ba->layout.o_cpts);
+  ba->cur_poses = (double*)(D + ba->layout.o_p0); ba->cand_poses = (double*)(D + ba->layout.o_p1);
   ba->d.points = ba->cur_points; ba->d.cand_points = ba->cand_points; ba->d.poses = ba->cur_poses; ba->d.cand_poses = ba->cand_poses;
   ba->arena_partial = false;
   ba->arena_dirty = true;
@@ -4893,13 +4614,13 @@ extern "C" int svo_ba_read_problem(svo_ba* ba, double* poses7, double* points3) 
   if (points3 && ba->n_points && ba->host_points_valid) {
     // delivered by ba_lm_kernel; a landmark without observations was never touched: it keeps its uploaded value
     memcpy(points3, ba->h_out_points, sizeof(double) * 3 * (size_t)ba->n_points);
-    const double* in = reinterpret_cast<const double*>(ba->h_arena + ba->arena_pts_off);
-    const std::vector<int32_t>& lm = ba->u_lm_start;
+    const double* in = reinterpret_cast<const double*>(ba->h_arena + ba->layout.o_pts);
+    const std::vector<int32_t>& lm = ba->layout.lm_start;
     for (int j = 0; j < ba->n_points && (size_t)j + 1 < lm.size(); ++j)
       if (lm[j + 1] == lm[j]) { points3[3 * j] = in[3 * j]; points3[3 * j + 1] = in[3 * j + 1]; points3[3 * j + 2] = in[3 * j + 2]; }
   } else if (points3 && ba->n_points && ba->arena_dirty) {
     // loaded, never solved: the image is still on the host
-    memcpy(points3, ba->h_arena + ba->arena_pts_off, sizeof(double) * 3 * (size_t)ba->n_points);
+    memcpy(points3, ba->h_arena + ba->layout.o_pts, sizeof(double) * 3 * (size_t)ba->n_points);
   } else if (points3 && ba->n_points) {
     // through the pinned arena (idle once the solve has finished): the runtime's pageable path would stage and wait
     const size_t bytes = sizeof(double) * 3 * (size_t)ba->n_points;
@@ -4921,58 +4642,36 @@ extern "C" int svo_ba_add_keyframe(svo_ba* ba, const double* pose7, const int64_
   SVO_REQUIRE(ctx, pose7 && n_tracked >= 0 && n_new >= 0 && n_new_out, "ba_add_keyframe: bad arguments");
   SVO_REQUIRE(ctx, (n_tracked == 0 || (tracked_ids && tracked_xy)) && (n_new == 0 || (new_xy && new_xyz && new_ids)),
               "ba_add_keyframe: null buffer");
-  svo_ba::PoseVar pv;
-  memcpy(pv.pose, pose7, sizeof(pv.pose));  // src/bundle_adjuster.cpp:63-70
-  const int64_t nfeat = (int64_t)(ba->feat_pos.size() / 3);
-  for (int i = 0; i < n_tracked; ++i) {   // :72-83
-    SVO_REQUIRE(ctx, tracked_ids[i] >= 0 && tracked_ids[i] < nfeat, "ba_add_keyframe: unknown feature id");
-    pv.obs.push_back({tracked_xy[2 * i], tracked_xy[2 * i + 1], tracked_ids[i]});
-  }
-  const int maxf = ba->opt.max_features;
-  const int max_new = n_tracked > maxf ? 0 : maxf - n_tracked;  // :85-90 with the C-5 guard
-  const int keep = n_new > max_new ? max_new : n_new;
-  for (int i = 0; i < keep; ++i) {        // :92-122; ids sequential (C-3), new_ids = real ids only (C-4)
-    const int64_t id = (int64_t)(ba->feat_pos.size() / 3);
-    ba->feat_pos.push_back(new_xyz[3 * i]); ba->feat_pos.push_back(new_xyz[3 * i + 1]); ba->feat_pos.push_back(new_xyz[3 * i + 2]);
-    new_ids[i] = id;
-    pv.obs.push_back({new_xy[2 * i], new_xy[2 * i + 1], id});
-  }
-  *n_new_out = keep;
-  ba->window.push_back(std::move(pv));
-  if ((int)ba->window.size() > ba->window_size) ba->window.pop_front();  // :126-128 (remove_oldest_pose)
-  ba->new_frame_added = true;                                            // :134
-  return SVO_OK;
+  const char* why = nullptr;
+  const int rc = ba->graph.add_keyframe(pose7, tracked_ids, tracked_xy, n_tracked, new_xy, new_xyz, n_new, new_ids, n_new_out, &why);
+  if (rc) ctx->err = why;
+  return rc;
 }
 
 extern "C" int svo_ba_reset(svo_ba* ba) {
   if (!ba) return SVO_ERR_INVALID;
-  ba->window.clear();
-  ba->feat_pos.clear();
-  ba->new_frame_added = false;
+  ba->graph.reset();
   ba->d.K = 0;
   return SVO_OK;
 }
 
-extern "C" int svo_ba_window_count(svo_ba* ba) { return ba ? (int)ba->window.size() : 0; }
+extern "C" int svo_ba_window_count(svo_ba* ba) { return ba ? ba->graph.window_count() : 0; }
 
 extern "C" int svo_ba_get_pose(svo_ba* ba, int k, double* pose7) {
   if (!ba || !pose7) return SVO_ERR_INVALID;
-  const int K = (int)ba->window.size();
-  if (k < 0) k += K;
-  SVO_REQUIRE(ba->ctx, k >= 0 && k < K, "ba_get_pose: slot out of range");
-  memcpy(pose7, ba->window[k].pose, 7 * sizeof(double));
-  return SVO_OK;
+  const char* why = nullptr;
+  const int rc = ba->graph.get_pose(k, pose7, &why);
+  if (rc) ba->ctx->err = why;
+  return rc;
 }
 
 extern "C" int svo_ba_get_points(svo_ba* ba, const int64_t* ids, int n, float* xyz) {
   if (!ba) return SVO_ERR_INVALID;
   SVO_REQUIRE(ba->ctx, n >= 0 && (n == 0 || (ids && xyz)), "ba_get_points: null buffer");
-  const int64_t nfeat = (int64_t)(ba->feat_pos.size() / 3);
-  for (int i = 0; i < n; ++i) {  // src/bundle_adjuster.cpp:159-163 (double -> float)
-    SVO_REQUIRE(ba->ctx, ids[i] >= 0 && ids[i] < nfeat, "ba_get_points: unknown feature id");
-    for (int a = 0; a < 3; ++a) xyz[3 * i + a] = (float)ba->feat_pos[3 * ids[i] + a];
-  }
-  return SVO_OK;
+  const char* why = nullptr;
+  const int rc = ba->graph.get_points(ids, n, xyz, &why);
+  if (rc) ba->ctx->err = why;
+  return rc;
 }
 
 // The landmark store behind a HOST-DRIVEN solve (a lane whose window was not eligible or not admitted for ba_lm_kernel): the
@@ -4985,7 +4684,7 @@ __global__ __launch_bounds__(256) void ba_store_scatter_kernel(const float4* __r
   store[__float_as_uint(e.w) & mask] = e;
 }
 
-static int ba_store_scatter(svo_ba* ba, const std::vector<int64_t>& ids, const std::vector<double>& pts) {
+static int ba_store_scatter(svo_ba* ba, const std::vector<int64_t>& ids, const double* pts) {
   svo_ctx* ctx = ba->ctx;
   const size_t n = ids.size();
   if (n > ba->store_stage_cap) {
@@ -5020,59 +4719,12 @@ int svo_ba_attach_store(svo_ba* ba, float4* store, unsigned mask) {
 int svo_ba_solve_prepare(svo_ba* ba) {
   if (!ba) return SVO_ERR_INVALID;
   svo_use_device(ba->ctx);
-  if (!ba->new_frame_added) return 1;  // src/bundle_adjuster.cpp:138
+  if (!ba->graph.new_frame_added()) return 1;  // src/bundle_adjuster.cpp:138
   const auto tp0 = std::chrono::steady_clock::now();
-  const int K = (int)ba->window.size();
-  // Observations sorted by (landmark id, window slot) — the order ceres would visit nothing in particular, but the
-  // declared summation order is defined on it.  Every keyframe's observation list is ascending in id when it comes
-  // from the pipeline (tracked ids keep their order, new ids are larger), so a K-way merge replaces the sort; lists
-  // from other callers are checked and fall back to a stable sort.
-  std::vector<double>& poses = ba->s_poses; std::vector<double>& points = ba->s_points; std::vector<double>& uv = ba->s_uv;
-  std::vector<int32_t>& op = ba->s_op; std::vector<int32_t>& oj = ba->s_oj;
-  std::vector<int64_t>& lm_ids = ba->solve_lm_ids;
-  poses.resize(7 * (size_t)K); points.clear(); uv.clear(); op.clear(); oj.clear(); lm_ids.clear();
-  points.reserve(3 * 4096); uv.reserve(2 * 4096); op.reserve(4096); oj.reserve(4096); lm_ids.reserve(4096);
-  for (int k = 0; k < K; ++k) memcpy(&poses[7 * k], ba->window[k].pose, 7 * sizeof(double));
-  bool ascending = true;
-  size_t total = 0;
-  for (int k = 0; k < K; ++k) {
-    const auto& o = ba->window[k].obs;
-    total += o.size();
-    for (size_t i = 1; i < o.size() && ascending; ++i) ascending = o[i - 1].id <= o[i].id;
-  }
-  auto emit = [&](int k, const svo_ba::Obs& o) {
-    if (lm_ids.empty() || lm_ids.back() != o.id) {
-      lm_ids.push_back(o.id);
-      for (int a = 0; a < 3; ++a) points.push_back(ba->feat_pos[3 * o.id + a]);
-    }
-    op.push_back(k); oj.push_back((int32_t)lm_ids.size() - 1);
-    uv.push_back(o.u); uv.push_back(o.v);
-  };
-  if (ascending && K <= 64) {
-    const svo_ba::Obs* cur[64];
-    const svo_ba::Obs* end[64];
-    for (int k = 0; k < K; ++k) { const auto& o = ba->window[k].obs; cur[k] = o.data(); end[k] = o.data() + o.size(); }
-    for (size_t done = 0; done < total; ++done) {
-      int best = -1;
-      int64_t best_id = 0;
-      for (int k = 0; k < K; ++k)  // smallest id first; equal ids in window-slot order (what the stable sort gives)
-        if (cur[k] != end[k] && (best < 0 || cur[k]->id < best_id)) { best = k; best_id = cur[k]->id; }
-      emit(best, *cur[best]++);
-    }
-  } else {
-    struct Flat { int k; const svo_ba::Obs* o; };
-    std::vector<Flat> flat;
-    flat.reserve(total);
-    for (int k = 0; k < K; ++k)
-      for (const auto& o : ba->window[k].obs) flat.push_back({k, &o});
-    std::stable_sort(flat.begin(), flat.end(), [](const Flat& a, const Flat& b) { return a.o->id < b.o->id; });
-    for (const Flat& f : flat) emit(f.k, *f.o);
-  }
+  const BaProblemView v = ba->graph.gather();
   const auto tu0 = std::chrono::steady_clock::now();
   ba->t_prep += std::chrono::duration<double, std::milli>(tu0 - tp0).count();
-  ba->upload_has_ids = true;   // the landmark-store keys of this problem = lm_ids
-  int rc = ba_upload(ba, K, poses.data(), (int)lm_ids.size(), points.data(), (int)op.size(), op.data(), oj.data(), uv.data());
-  ba->upload_has_ids = false;
+  const int rc = ba_upload(ba, v.K, v.poses, v.n_points, v.points, v.M, v.op, v.oj, v.uv, v.lm_ids);  // the landmark-store keys of this problem = lm_ids
   if (rc) return rc;
   ba->t_upload += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tu0).count();
   return SVO_OK;
@@ -5115,9 +4767,6 @@ int svo_ba_solve_finish(svo_ba* ba, svo_ba_summary* summary) {
   svo_use_device(ba->ctx);
   if (summary) memset(summary, 0, sizeof(*summary));
   const auto tu0 = std::chrono::steady_clock::now();
-  const int K = ba->d.K;
-  std::vector<double>& poses = ba->s_poses; std::vector<double>& points = ba->s_points;
-  std::vector<int64_t>& lm_ids = ba->solve_lm_ids;
   int rc;
   const bool on_device = ba->lm_inflight;
   bool on_device_ok = on_device;
@@ -5138,17 +4787,15 @@ int svo_ba_solve_finish(svo_ba* ba, svo_ba_summary* summary) {
   if (rc) return rc;
   if (summary && on_device) {  // device-resident solves only: the launches bench.py times with HIP events carry exactly these
     const double its = summary->iterations + 1;  // + the first linearisation
-    ba->acc_flops += its * ba->flops_iter; ba->acc_bytes += its * ba->bytes_iter; ba->acc_solves += 1; ba->acc_iters += summary->iterations;
+    ba->acc_flops += its * ba->layout.flops_iter; ba->acc_bytes += its * ba->layout.bytes_iter; ba->acc_solves += 1; ba->acc_iters += summary->iterations;
   }
   const auto tr0 = std::chrono::steady_clock::now();
-  std::vector<double>& out_pts = ba->s_out_pts;
-  out_pts.resize(points.size());
-  rc = svo_ba_read_problem(ba, poses.data(), out_pts.data());
+  double* poses = ba->graph.solved_poses();
+  double* out_pts = ba->graph.solved_points();
+  rc = svo_ba_read_problem(ba, poses, out_pts);
   if (rc) return rc;
-  for (int k = 0; k < K; ++k) memcpy(ba->window[k].pose, &poses[7 * k], 7 * sizeof(double));
-  for (size_t l = 0; l < lm_ids.size(); ++l)
-    for (int a = 0; a < 3; ++a) ba->feat_pos[3 * lm_ids[l] + a] = out_pts[3 * l + a];
-  ba->new_frame_added = false;  // :155
+  ba->graph.write_back(poses, out_pts);
+  const std::vector<int64_t>& lm_ids = ba->graph.gathered_ids();
   if (ba->store && !on_device_ok && !lm_ids.empty()) {  // the device-resident solve wrote the landmark store itself
     rc = ba_store_scatter(ba, lm_ids, out_pts);
     if (rc) return rc;

@@ -30,6 +30,7 @@
 
 #include "lm_decide.h"
 #include "lm_math.h"
+#include "ref_constants.h"
 #include "svo.h"
 
 bool svo_host_cholesky_solve(double* A, double* b, int n);  // host/linalg.cpp
@@ -46,6 +47,18 @@ extern "C" int svo_lm_decide_step(double cost, double mcc, double radius, double
   *accept = d.accept;
   *next_radius = d.next_radius;
   return SVO_OK;
+}
+
+extern "C" void svo_ba_default_options(svo_ba_options* o) {
+  if (!o) return;
+  o->max_iterations = 50;                           // Ceres default
+  o->max_time_s = svo_ref::BA_MAX_SOLVER_TIME_S;    // src/bundle_adjuster.cpp:11
+  o->function_tolerance = 1e-6;
+  o->gradient_tolerance = 1e-10;
+  o->parameter_tolerance = 1e-8;
+  o->initial_radius = 1e4;
+  o->max_features = svo_ref::MAX_FEATURES;          // src/bundle_adjuster.hpp:75
+  o->accumulation = SVO_BA_ACC_AUTO;
 }
 
 extern "C" int svo_lm_solve(int n_poses, double* poses7, const svo_lm_ops* ops, const svo_ba_options* opt_in,

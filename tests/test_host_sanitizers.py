@@ -1,6 +1,8 @@
 """AddressSanitizer + UndefinedBehaviorSanitizer over the GPU-free host code of the product (the step control
-host/lm.cpp, the dense Cholesky, the KITTI-layout decoders, the track rasteriser, the synthetic renderer), on the CPU:
-GPU sanitizers are not available on the target pool, and these are the pieces that parse files and index host arrays."""
+host/lm.cpp, the dense Cholesky, the KITTI-layout decoders, the track rasteriser, the synthetic renderer, and the three
+GPU-free pieces of the bundle adjuster: the sliding-window graph host/ba_graph.h, the problem layout host/ba_layout.h, the
+admission ledger host/ba_admission.h), on the CPU: GPU sanitizers are not available on the target pool, and these are the
+pieces that parse files and index host arrays.  Every program is stand-alone (its own main); nothing is loaded into Python."""
 import os
 import struct
 import subprocess
@@ -90,3 +92,37 @@ def test_group_line_policy_partitions_gathers_and_orders_solves(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "group lines ok" in r.stdout
+
+
+def _run_sanitized(tmp_path, name, ok, *args):
+    exe = str(tmp_path / name)
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "stereo_vo_amd", "host"),
+           os.path.join(ROOT, "tests", "sanitize", name + ".cpp"), "-o", exe, "-lpthread"]
+    subprocess.run(cmd, check=True, timeout=300)
+    r = subprocess.run([exe] + list(args), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert ok in r.stdout
+
+
+def test_ba_graph_ids_truncation_window_gather_and_write_back(tmp_path):
+    """The sliding-window graph of the bundle adjuster (host/ba_graph.h), walked on the CPU under ASan + UBSan: sequential ids,
+    truncation at max_features, the window pop, an unknown id rejected with nothing committed, gather() against a sort-based
+    restatement on the merge path and on the stable-sort path (and the two on the same observations), write_back, reset."""
+    _run_sanitized(tmp_path, "ba_graph_test", "ba graph ok")
+
+
+def test_ba_layout_tables_match_a_brute_force_restatement(tmp_path):
+    """The host half of the declared summation order (host/ba_layout.h), walked on the CPU under ASan + UBSan: chunks, dimensions
+    and the per-chunk destination tables against a brute-force restatement, entry for entry and in order, for K = 1, 2, 3, 5, 9;
+    chunk boundaries; more than 128 and more than 2,048 chunks; the staging image; every rejection at its boundary."""
+    _run_sanitized(tmp_path, "ba_layout_test", "ba layout ok")
+
+
+def test_ba_admission_ledger_within_and_across_processes(tmp_path):
+    """The admission ledger (host/ba_admission.h), walked on the CPU under ASan + UBSan with its table file in a temporary
+    directory: the budget within a process, a forked child's workgroups counted against the parent's budget, the slot of a
+    process that died without releasing, and the per-process admission without a file."""
+    d = tmp_path / "table"
+    d.mkdir()
+    _run_sanitized(tmp_path, "ba_admission_test", "ba admission ok", str(d))
