@@ -98,7 +98,8 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * "speckle" (the launches of one speckle filter call as one bracket), "lr_check" (one left-right check call),
  * "stereo_sgm" (the launches of one semi-global matching call as one bracket), "voxel_insert" (one svo_voxel_map_insert_dev),
  * "voxel_extract" (one svo_voxel_map_extract_dev: the counts' memset and the launch), "voxel_carve" (one
- * svo_voxel_map_carve_dev: the counts' memset and the launch), "voxel_copy" (one svo_voxel_map_copy_live_dev);
+ * svo_voxel_map_carve_dev: the counts' memset and the launch), "voxel_copy" (one svo_voxel_map_copy_live_dev), "voxel_render" (one
+ * svo_voxel_map_render_dev: the two memsets and both launches);
  * NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
@@ -483,6 +484,67 @@ int svo_voxel_map_carve(svo_voxel_map* map, const int16_t* disp16, int width, in
  * SVO_ERR_INVALID and no launch for a null map, src == dst, maps of different contexts, voxel sizes that differ in a bit,
  * min_count < 1, a NaN in box6. */
 int svo_voxel_map_copy_live_dev(svo_voxel_map* src, svo_voxel_map* dst, int min_count, const double* box6);
+
+/* Voxel map render: what the map predicts for a camera at a pose, as a tight width x height CV_16S disparity map in sixteenths
+ * (FILTERED = -16 where no voxel is seen) and a u8 intensity image: the formats of the dense track, so the view can carve another
+ * map (svo_voxel_map_carve*), become the cloud of the visible surface (svo_disparity_cloud_batch_dev with the intensity image as
+ * `left`), pass the speckle filter, or be subtracted from a keyframe's measured map.  cam: focal, cx, cy, baseline are read;
+ * w2c12: WORLD->CAMERA, 12 HOST doubles, passed to the kernel by value.  Every step is an integer or an f64 operation in the stated
+ * order, without contraction; steps 2-4 are the carve's:
+ *   1. A slot qualifies iff key != EMPTY and count = ci >> 40 >= min_count (>= 1).  Carved slots have count 0: they never qualify.
+ *   2. p_r = ((double)k_r + (double)s_r / ((double)count * 65536.0)) * (double)voxel_size.
+ *   3. c_r = m[r][0]*p_0 + m[r][1]*p_1 + m[r][2]*p_2 + m[r][3], summed left to right.
+ *   4. Not drawn unless c_2 > 0.0.  u = focal*c_0 / c_2 + cx, v = focal*c_1 / c_2 + cy; px = floor(u + 0.5), py = floor(v + 0.5).
+ *   5. dv16 = (focal*baseline) / c_2 * 16.0 (the carve's step 6); d16 = floor(dv16 + 0.5).  Not drawn unless 1.0 <= d16 &&
+ *      d16 <= 32767.0, compared in f64 (NaN and infinity fail).
+ *   6. Footprint.  The voxel's cube of side voxel_size projects to a half width of h = focal*(double)voxel_size / c_2 * 0.5 pixels;
+ *      r = min((double)max_radius, floor(h + 0.5)): the smallest half width whose 2r+1 pixels cover the 2h pixels between the means
+ *      of neighbouring voxels of a surface that faces the camera.
+ *   7. Drawn iff -r <= px && px <= width-1+r && -r <= py && py <= height-1+r, in f64.  Its pixels are all (x, y) with |x - px| <= r
+ *      and |y - py| <= r, clipped to the image: a voxel whose centre is just outside still draws the part of its footprint inside.
+ *   8. Z-buffer.  pix32 = (uint32)d16 << 8 | (uint32)(isum / count), isum the low 40 bits of ci; never 0.  Every pixel of the
+ *      footprint gets pix[y*width + x] = max(pix[...], pix32) by a relaxed device-scope 32-bit atomicMax: the largest disparity (the
+ *      nearest surface) wins, among equal disparities the larger mean intensity.  max commutes: the image depends on no thread
+ *      order and on no slot placement.
+ *   9. Resolve, a second launch on the same stream: pix == 0 gives disp16 = -16 and intensity = 0; otherwise disp16 = pix >> 8 and
+ *      intensity = pix & 255.
+ *  10. counts = {n_qualifying, n_drawn, n_splat, n_pixels}: 4 u64 on the device, or NULL.  n_splat: the sum over drawn voxels of
+ *      their clipped footprint areas (the contract's number of max operations); n_pixels: pixels with pix != 0, counted by the
+ *      resolve.  The workspace and the counts are zeroed on the stream before the first launch; one relaxed atomicAdd per
+ *      workgroup and non-zero counter.
+ *  11. SVO_ERR_INVALID with the argument named, and nothing launched, for: a null map, cam, w2c12, params, workspace or disp16;
+ *      min_count < 1; max_radius outside 0..16; width or height < 1 or beyond the context's limits; focal or baseline not finite
+ *      or <= 0; a workspace that is not 4-byte aligned.
+ * workspace: svo_voxel_render_workspace_bytes(width, height) = 4*width*height bytes of device memory, one u32 per pixel (contents
+ * before are meaningless, afterwards the z-buffer).  disp16: tight int16; intensity: tight u8 or NULL.  The resolve moves four
+ * pixels per thread by vector accesses when workspace, disp16 and intensity are 16-, 8- and 4-byte aligned, and pixel by pixel
+ * otherwise: the same bytes either way.
+ * KNOWN PROPERTY: this is point splatting, not ray casting.  A surface seen at a grazing angle has voxel means more than 2r+1
+ * pixels apart and shows holes, through which whatever lies behind is visible.
+ * The defaults (min_count 1, max_radius 8) are NOT tuned on real imagery.  The pipeline never renders by itself. */
+typedef struct svo_voxel_render_params {
+  int min_count;  /* >= 1: voxels with fewer points are not drawn */
+  int max_radius; /* 0..16: bound on the footprint's half width in pixels (0: one pixel per voxel) */
+} svo_voxel_render_params;
+int svo_voxel_render_default_params(svo_voxel_render_params* params);
+/* 4*width*height; 0 for width or height < 1.  Pure. */
+size_t svo_voxel_render_workspace_bytes(int width, int height);
+/* DEVICE pointers, asynchronous on svo_stream(ctx): two memsets and two launches. */
+int svo_voxel_map_render_dev(svo_voxel_map* map, int width, int height, const svo_camera_info* cam, const double* w2c12,
+                             const svo_voxel_render_params* params, void* workspace, int16_t* disp16, uint8_t* intensity,
+                             uint64_t* counts);
+/* svo_pose7_to_world_to_cam, then svo_voxel_map_render_dev. */
+int svo_voxel_map_render_pose7_dev(svo_voxel_map* map, int width, int height, const svo_camera_info* cam, const double* pose7,
+                                   const svo_voxel_render_params* params, void* workspace, int16_t* disp16, uint8_t* intensity,
+                                   uint64_t* counts);
+/* HOST outputs, synchronous: the workspace and the device outputs are allocated and freed by the call.  intensity: width*height
+ * bytes or NULL; counts: 4 u64 on the host or NULL. */
+int svo_voxel_map_render(svo_voxel_map* map, int width, int height, const svo_camera_info* cam, const double* w2c12,
+                         const svo_voxel_render_params* params, int16_t* disp16, uint8_t* intensity, uint64_t* counts);
+/* Measurement aid: how the splat launch draws.  cooperative != 0: footprints with r > 1 are drawn by the whole wavefront in turn
+ * (else every lane draws its own); precheck != 0: a plain load skips the atomic where the pixel already holds at least the value.
+ * Neither can change a bit of the outputs.  Default: cooperative on, precheck off (DESIGN 7h gives the figures). */
+int svo_voxel_render_set_mode(svo_voxel_map* map, int cooperative, int precheck);
 
 /* ------------------------------------------------------------------- a8 --
  * ImageProcessor::triangulate_stereo's reprojection loop

@@ -205,6 +205,33 @@ def pose7_to_world_to_cam(pose7):
     return m
 
 
+class VoxelRenderParams(C.Structure):
+    """svo_voxel_render_params: min_count (>= 1), bound on the footprint's half width in pixels (0..16)."""
+    _fields_ = [("min_count", C.c_int), ("max_radius", C.c_int)]
+
+
+def voxel_render_default_params():
+    """svo_voxel_render_default_params: min_count 1, max_radius 8 (not tuned on real imagery)."""
+    p = VoxelRenderParams()
+    if lib().svo_voxel_render_default_params(C.byref(p)) != 0:
+        raise SvoError("svo_voxel_render_default_params failed")
+    return p
+
+
+def voxel_render_workspace_bytes(width, height):
+    """svo_voxel_render_workspace_bytes: 4 * width * height (no GPU involved); 0 for width or height < 1."""
+    return int(lib().svo_voxel_render_workspace_bytes(int(width), int(height)))
+
+
+def _render_params(params, min_count, max_radius):
+    prm = voxel_render_default_params() if params is None else VoxelRenderParams(params.min_count, params.max_radius)
+    if min_count is not None:
+        prm.min_count = int(min_count)
+    if max_radius is not None:
+        prm.max_radius = int(max_radius)
+    return prm
+
+
 SPECKLE_TILE = (64, 16)  # SVO_SPECKLE_TILE_W, SVO_SPECKLE_TILE_H
 
 
@@ -392,6 +419,8 @@ SYMBOLS = [
     "svo_voxel_carve_default_params", "svo_voxel_map_carve_dev", "svo_pose7_to_world_to_cam", "svo_voxel_map_carve_pose7_dev",
     "svo_voxel_map_carve", "svo_voxel_map_copy_live_dev", "svo_pipeline_keyframe_disparity", "svo_pipeline_group_keyframe_disparity",
     "svo_pipeline_copy_keyframe_disparity", "svo_pipeline_group_copy_keyframe_disparity",
+    "svo_voxel_render_default_params", "svo_voxel_render_workspace_bytes", "svo_voxel_map_render_dev", "svo_voxel_map_render_pose7_dev",
+    "svo_voxel_map_render", "svo_voxel_render_set_mode",
 ]
 
 
@@ -489,6 +518,17 @@ def lib():
                   "svo_voxel_map_carve", "svo_voxel_map_copy_live_dev", "svo_pipeline_keyframe_disparity",
                   "svo_pipeline_group_keyframe_disparity", "svo_pipeline_copy_keyframe_disparity",
                   "svo_pipeline_group_copy_keyframe_disparity"):
+            getattr(L, f).restype = ci
+        # the render
+        L.svo_voxel_render_default_params.argtypes = [vp]
+        L.svo_voxel_render_workspace_bytes.argtypes = [ci, ci]
+        L.svo_voxel_render_workspace_bytes.restype = sz
+        L.svo_voxel_map_render_dev.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+        L.svo_voxel_map_render_pose7_dev.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+        L.svo_voxel_map_render.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp]
+        L.svo_voxel_render_set_mode.argtypes = [vp, ci, ci]
+        for f in ("svo_voxel_render_default_params", "svo_voxel_map_render_dev", "svo_voxel_map_render_pose7_dev", "svo_voxel_map_render",
+                  "svo_voxel_render_set_mode"):
             getattr(L, f).restype = ci
         _LIB = L
     return _LIB
@@ -929,6 +969,47 @@ class VoxelMap:
         added to dst: a fresh dst gives the map without its carved slots, a non-empty one a merge.  Asynchronous."""
         b = None if box is None else _f64(np.asarray(box, np.float64)).reshape(6)
         self.ctx._chk(self.L.svo_voxel_map_copy_live_dev(self.h, dst.h, int(min_count), _p(b)), "svo_voxel_map_copy_live_dev")
+
+    def render(self, width, height, cam, w2c12=None, pose7=None, params=None, min_count=None, max_radius=None, workspace_ptr=None,
+               disp_ptr=None, intensity_ptr=None, counts_ptr=None):
+        """svo_voxel_map_render_dev / _pose7_dev: the map seen by `cam` at the pose, exactly one of w2c12 (3 x 4 world->camera) and
+        pose7.  All pointers are the caller's device memory, as everywhere in this class: workspace_ptr
+        voxel_render_workspace_bytes(width, height) bytes, disp_ptr width * height int16, intensity_ptr as many uint8 or None,
+        counts_ptr 4 uint64 {n_qualifying, n_drawn, n_splat, n_pixels} or None.  Asynchronous on the context's stream; returns
+        {"disp16", "intensity", "counts", "workspace", "width", "height"}: the pointers the outputs are behind once the stream
+        reaches this point."""
+        if (w2c12 is None) == (pose7 is None):
+            raise ValueError("VoxelMap.render: give exactly one of w2c12 and pose7")
+        prm = _render_params(params, min_count, max_radius)
+        if w2c12 is not None:
+            m = _f64(w2c12).reshape(12)
+            self.ctx._chk(self.L.svo_voxel_map_render_dev(self.h, int(width), int(height), C.byref(cam), _p(m), C.byref(prm), workspace_ptr,
+                                                          disp_ptr, intensity_ptr, counts_ptr), "svo_voxel_map_render_dev")
+        else:
+            q = _f64(pose7).reshape(7)
+            self.ctx._chk(self.L.svo_voxel_map_render_pose7_dev(self.h, int(width), int(height), C.byref(cam), _p(q), C.byref(prm),
+                                                                workspace_ptr, disp_ptr, intensity_ptr, counts_ptr),
+                          "svo_voxel_map_render_pose7_dev")
+        return {"disp16": disp_ptr, "intensity": intensity_ptr, "counts": counts_ptr, "workspace": workspace_ptr,
+                "width": int(width), "height": int(height)}
+
+    def render_host(self, width, height, cam, w2c12=None, pose7=None, params=None, min_count=None, max_radius=None):
+        """svo_voxel_map_render: synchronous.  Returns (disp16 (height, width) int16 with FILTERED = -16 where nothing is seen,
+        intensity (height, width) uint8, {"n_qualifying", "n_drawn", "n_splat", "n_pixels"})."""
+        if (w2c12 is None) == (pose7 is None):
+            raise ValueError("VoxelMap.render_host: give exactly one of w2c12 and pose7")
+        m = _f64(pose7_to_world_to_cam(pose7) if w2c12 is None else w2c12).reshape(12)
+        prm = _render_params(params, min_count, max_radius)
+        d = np.empty((max(int(height), 1), max(int(width), 1)), np.int16)
+        g = np.empty(d.shape, np.uint8)
+        c = np.zeros(4, np.uint64)
+        self.ctx._chk(self.L.svo_voxel_map_render(self.h, int(width), int(height), C.byref(cam), _p(m), C.byref(prm), _p(d), _p(g), _p(c)),
+                      "svo_voxel_map_render")
+        return d, g, {"n_qualifying": int(c[0]), "n_drawn": int(c[1]), "n_splat": int(c[2]), "n_pixels": int(c[3])}
+
+    def render_set_mode(self, cooperative=True, precheck=False):
+        """svo_voxel_render_set_mode (measurement aid): how the splat launch draws; no bit of a render depends on it."""
+        self.ctx._chk(self.L.svo_voxel_render_set_mode(self.h, int(bool(cooperative)), int(bool(precheck))), "svo_voxel_render_set_mode")
 
     def stats(self):
         """The four counters as a dict (synchronises)."""

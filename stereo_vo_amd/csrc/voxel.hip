@@ -20,6 +20,19 @@
 //   voxel_copy_kernel    : the same tiling over src; a qualifying slot probes dst by vx_probe, the insert's loop, and adds its
 //                          four words with the insert's four atomicAdds.
 //
+//   voxel_splat_kernel   : the map seen from a pose.  The carve's tiling and its projection; a qualifying voxel in front
+//                          of the camera becomes a (2 r + 1)^2 footprint of one 32-bit value, disparity << 8 | mean intensity, and
+//                          every pixel of it takes the maximum by a relaxed atomicMax on the caller's workspace.  The trip count
+//                          of a footprint depends on the lane (1 .. 33^2 pixels), so footprints with r > 1 are collected by a
+//                          ballot and drawn by the whole wavefront in turn, 64 pixels of consecutive columns per step; the small
+//                          ones are drawn by their own lane (1.7 to 3.8 times faster than every lane drawing its own).
+//                          Optionally a plain load skips the atomic where the pixel already holds at least the value: values only
+//                          grow within the launch and the memset precedes it on the stream, so a stale load costs a needless
+//                          atomic, never a wrong skip.  It is OFF by default: the wait for the load costs more than the atomics
+//                          it saves on three of the four measured maps.  Neither choice can change the image.
+//   voxel_resolve_kernel : the workspace -> the CV_16S map and the u8 image, four pixels per thread (16-byte load, 8-byte and 4-byte
+//                          stores where the pointers allow it, else and in the tail pixel by pixel); counts the covered pixels.
+//
 // Nothing passes between workgroups except order-independent relaxed device-scope atomics (docs/HISTORY.md, "No cache maintenance
 // inside kernels"): no fence, no acquire / release, no waiting.  The CAS's RETURN value decides a probe, never a plain load; the
 // payload words are only ever added to by inserts and copies, zeroed only by a carve (a launch of its own, ordered by the stream,
@@ -103,6 +116,26 @@ struct VoxelCopyArgs {
   int boxed;
   int klo[3], khi[3];
 };
+
+struct VoxelSplatArgs {
+  VoxelTable t;
+  unsigned* pix;  // width * height, zeroed on the stream before the launch
+  int width, height, max_radius;
+  unsigned min_count;
+  float voxel_size;
+  double m[12];
+  double focal, cx, cy, baseline;
+  u64* counts;  // {n_qualifying, n_drawn, n_splat, n_pixels}, zeroed on the stream before the launch; or null
+};
+
+struct VoxelResolveArgs {
+  const unsigned* pix;
+  int16_t* disp;
+  uint8_t* inten;  // or null
+  size_t n;        // width * height
+  int vec;         // pix 16-byte, disp 8-byte and inten 4-byte aligned: the vector form
+  u64* counts;
+};
 }  // namespace
 
 struct svo_voxel_map {
@@ -112,6 +145,7 @@ struct svo_voxel_map {
   u64* d_mem = nullptr;  // keys | ci | sx | sy | sz | 4 counters | 2 ints of the synchronous extraction
   VoxelTable t{};
   int* d_counts = nullptr;
+  int render_coop = 1, render_pre = 0;  // svo_voxel_render_set_mode; the defaults are the measured choice
 };
 
 __global__ __launch_bounds__(VX_T) void voxel_insert_kernel(VoxelInsertArgs a) {
@@ -349,6 +383,139 @@ __global__ __launch_bounds__(VX_T) void voxel_copy_kernel(VoxelCopyArgs a) {
     for (int w = 0; w < VX_T / 64; ++w) t += sC[tid][w];
     // counters: n_voxels, n_inserted, (n_rejected), n_dropped
     if (t) __hip_atomic_fetch_add(&a.dst.counters[tid == 2 ? 3 : tid], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// One pixel of a footprint.
+template <bool PRE>
+__device__ __forceinline__ void vx_splat_max(unsigned* p, unsigned v) {
+  if (PRE && *p >= v) return;
+  __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <bool PRE, bool COOP>
+__global__ __launch_bounds__(VX_T) void voxel_splat_kernel(VoxelSplatArgs a) {
+  __shared__ unsigned sC[3][VX_T / 64];
+  const size_t cap = (size_t)a.t.mask + 1;
+  const size_t first = (size_t)blockIdx.x * (VX_T * VX_ITEMS) + (size_t)threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const double vs = (double)a.voxel_size, rmax = (double)a.max_radius;
+  const double xhi = (double)(a.width - 1), yhi = (double)(a.height - 1);
+  unsigned n_qual = 0, n_drawn = 0, n_splat = 0;
+#pragma unroll
+  for (int j = 0; j < VX_ITEMS; ++j) {  // no lane leaves the loop early: the ballot below is the whole wavefront's
+    const size_t s = first + (size_t)j * VX_T;
+    int px = 0, py = 0, r = -1;  // r >= 0: drawn
+    unsigned v = 0;
+    if (s < cap) {
+      const u64 key = a.t.keys[s];
+      if (key != VX_EMPTY) {
+        const u64 ci = a.t.ci[s], count = ci >> 40;
+        if (count >= (u64)a.min_count) {
+          ++n_qual;
+          const double c = (double)count * 65536.0;
+          const u64 sum[3] = {a.t.sx[s], a.t.sy[s], a.t.sz[s]};
+          double p[3], q[3];
+#pragma unroll
+          for (int k3 = 0; k3 < 3; ++k3) {
+            const double k = (double)((long long)((key >> (21 * k3)) & 0x1FFFFFull) - (1ll << 20));
+            p[k3] = (k + (double)sum[k3] / c) * vs;
+          }
+#pragma unroll
+          for (int k3 = 0; k3 < 3; ++k3) q[k3] = a.m[4 * k3] * p[0] + a.m[4 * k3 + 1] * p[1] + a.m[4 * k3 + 2] * p[2] + a.m[4 * k3 + 3];
+          if (q[2] > 0.0) {
+            const double fpx = floor(a.focal * q[0] / q[2] + a.cx + 0.5), fpy = floor(a.focal * q[1] / q[2] + a.cy + 0.5);
+            const double d16 = floor(a.focal * a.baseline / q[2] * 16.0 + 0.5);
+            const double h = floor(a.focal * vs / q[2] * 0.5 + 0.5);
+            const double fr = h < rmax ? h : rmax;
+            // NaN and infinity fail
+            if (d16 >= 1.0 && d16 <= 32767.0 && fpx >= -fr && fpx <= xhi + fr && fpy >= -fr && fpy <= yhi + fr) {
+              ++n_drawn;
+              px = (int)fpx; py = (int)fpy; r = (int)fr;
+              v = ((unsigned)d16 << 8) | (unsigned)((ci & ((1ull << 40) - 1ull)) / count);
+            }
+          }
+        }
+      }
+    }
+    if (r >= 0) {  // the footprint clipped to the image: not empty, by the test above
+      const int x0 = max(px - r, 0), x1 = min(px + r, a.width - 1), y0 = max(py - r, 0), y1 = min(py + r, a.height - 1);
+      n_splat += (unsigned)((x1 - x0 + 1) * (y1 - y0 + 1));
+      if (!COOP || r <= 1) {
+        for (int y = y0; y <= y1; ++y) {
+          unsigned* row = a.pix + (size_t)y * (size_t)a.width;
+          for (int x = x0; x <= x1; ++x) vx_splat_max<PRE>(row + x, v);
+        }
+      }
+    }
+    if (COOP) {
+      u64 todo = __ballot(r > 1);
+      while (todo) {  // wavefront-uniform
+        const int src = __builtin_ctzll(todo);
+        todo &= todo - 1ull;
+        const int bx = __shfl(px, src), by = __shfl(py, src), br = __shfl(r, src);
+        const unsigned bv = __shfl(v, src);
+        const int x0 = max(bx - br, 0), x1 = min(bx + br, a.width - 1), y0 = max(by - br, 0), y1 = min(by + br, a.height - 1);
+        const int bw = x1 - x0 + 1, n = bw * (y1 - y0 + 1);  // 1 <= bw <= 33
+        const int sy = 64 / bw, sx = 64 - sy * bw;           // one step of 64 pixels in rows and columns
+        int yy = lane / bw, xx = lane - yy * bw;
+        for (int i = lane; i < n; i += 64) {
+          vx_splat_max<PRE>(a.pix + (size_t)(y0 + yy) * (size_t)a.width + (size_t)(x0 + xx), bv);
+          yy += sy; xx += sx;
+          if (xx >= bw) { xx -= bw; ++yy; }
+        }
+      }
+    }
+  }
+  if (!a.counts) return;  // uniform over the launch
+  for (int o = 32; o > 0; o >>= 1) {
+    n_qual += __shfl_xor(n_qual, o); n_drawn += __shfl_xor(n_drawn, o); n_splat += __shfl_xor(n_splat, o);
+  }
+  const int tid = threadIdx.x;
+  if ((tid & 63) == 0) { sC[0][tid >> 6] = n_qual; sC[1][tid >> 6] = n_drawn; sC[2][tid >> 6] = n_splat; }
+  __syncthreads();
+  if (tid < 3) {
+    unsigned t = 0;
+    for (int w = 0; w < VX_T / 64; ++w) t += sC[tid][w];
+    if (t) __hip_atomic_fetch_add(&a.counts[tid], (u64)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+__global__ __launch_bounds__(VX_T) void voxel_resolve_kernel(VoxelResolveArgs a) {
+  __shared__ unsigned sC[VX_T / 64];
+  const size_t i0 = ((size_t)blockIdx.x * VX_T + (size_t)threadIdx.x) * 4;
+  const int here = i0 < a.n ? (int)(a.n - i0 < 4 ? a.n - i0 : 4) : 0;
+  unsigned covered = 0;  // one bit per pixel
+  if (here == 4 && a.vec) {
+    const uint4 p = *reinterpret_cast<const uint4*>(a.pix + i0);
+    covered = (p.x ? 1u : 0u) | (p.y ? 2u : 0u) | (p.z ? 4u : 0u) | (p.w ? 8u : 0u);
+    short4 d;
+    d.x = p.x ? (short)(p.x >> 8) : (short)-16; d.y = p.y ? (short)(p.y >> 8) : (short)-16;
+    d.z = p.z ? (short)(p.z >> 8) : (short)-16; d.w = p.w ? (short)(p.w >> 8) : (short)-16;
+    *reinterpret_cast<short4*>(a.disp + i0) = d;
+    if (a.inten) {
+      uchar4 g;
+      g.x = (unsigned char)(p.x & 255u); g.y = (unsigned char)(p.y & 255u); g.z = (unsigned char)(p.z & 255u); g.w = (unsigned char)(p.w & 255u);
+      *reinterpret_cast<uchar4*>(a.inten + i0) = g;
+    }
+  } else {
+    for (int k = 0; k < here; ++k) {  // the tail, or pointers the vector form cannot take
+      const unsigned p = a.pix[i0 + k];
+      covered |= p ? 1u << k : 0u;
+      a.disp[i0 + k] = p ? (int16_t)(p >> 8) : (int16_t)-16;
+      if (a.inten) a.inten[i0 + k] = (uint8_t)(p & 255u);
+    }
+  }
+  if (!a.counts) return;  // uniform over the launch
+  unsigned n = (unsigned)__popc(covered);
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+  const int tid = threadIdx.x;
+  if ((tid & 63) == 0) sC[tid >> 6] = n;
+  __syncthreads();
+  if (tid == 0) {
+    unsigned t = 0;
+    for (int w = 0; w < VX_T / 64; ++w) t += sC[w];
+    if (t) __hip_atomic_fetch_add(&a.counts[3], (u64)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -659,5 +826,122 @@ extern "C" int svo_voxel_map_copy_live_dev(svo_voxel_map* src, svo_voxel_map* ds
   SvoProfScope prof(ctx, SVO_PROF_VOXEL_COPY);
   hipLaunchKernelGGL(voxel_copy_kernel, dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
   SVO_HIP_CHECK(ctx, hipGetLastError());
+  return SVO_OK;
+}
+
+// ----------------------------------------------------------------------------- the render
+extern "C" int svo_voxel_render_default_params(svo_voxel_render_params* params) {
+  if (!params) return SVO_ERR_INVALID;
+  params->min_count = 1;
+  params->max_radius = 8;
+  return SVO_OK;
+}
+
+extern "C" size_t svo_voxel_render_workspace_bytes(int width, int height) {
+  return width < 1 || height < 1 ? 0 : 4 * (size_t)width * (size_t)height;
+}
+
+extern "C" int svo_voxel_render_set_mode(svo_voxel_map* m, int cooperative, int precheck) {
+  if (!m) return SVO_ERR_INVALID;
+  m->render_coop = cooperative != 0;
+  m->render_pre = precheck != 0;
+  return SVO_OK;
+}
+
+static int voxel_render_check(svo_voxel_map* m, int width, int height, const svo_camera_info* cam, const double* w2c12,
+                              const svo_voxel_render_params* prm) {
+  svo_ctx* ctx = m->ctx;
+  const double big = 1.7976931348623157e308;
+  SVO_REQUIRE(ctx, cam, "voxel_map_render: null cam");
+  SVO_REQUIRE(ctx, w2c12, "voxel_map_render: null w2c12");
+  SVO_REQUIRE(ctx, prm, "voxel_map_render: null params");
+  SVO_REQUIRE(ctx, prm->min_count >= 1, "voxel_map_render: min_count must be at least 1");
+  SVO_REQUIRE(ctx, prm->max_radius >= 0 && prm->max_radius <= 16, "voxel_map_render: max_radius outside 0..16");
+  SVO_REQUIRE(ctx, width >= 1 && width <= ctx->lim.max_width, "voxel_map_render: width below 1 or beyond the context's limit");
+  SVO_REQUIRE(ctx, height >= 1 && height <= ctx->lim.max_height, "voxel_map_render: height below 1 or beyond the context's limit");
+  SVO_REQUIRE(ctx, cam->focal > 0.0 && cam->focal <= big, "voxel_map_render: focal must be finite and > 0");
+  SVO_REQUIRE(ctx, cam->baseline > 0.0 && cam->baseline <= big, "voxel_map_render: baseline must be finite and > 0");
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_map_render_dev(svo_voxel_map* m, int width, int height, const svo_camera_info* cam, const double* w2c12,
+                                        const svo_voxel_render_params* prm, void* workspace, int16_t* disp16, uint8_t* intensity,
+                                        uint64_t* counts) {
+  if (!m) return SVO_ERR_INVALID;
+  svo_ctx* ctx = m->ctx;
+  svo_use_device(ctx);
+  const int rc = voxel_render_check(m, width, height, cam, w2c12, prm);
+  if (rc) return rc;
+  SVO_REQUIRE(ctx, workspace, "voxel_map_render: null workspace");
+  SVO_REQUIRE(ctx, ((uintptr_t)workspace & 3u) == 0, "voxel_map_render: workspace must be 4-byte aligned");
+  SVO_REQUIRE(ctx, disp16, "voxel_map_render: null disp16");
+  VoxelSplatArgs a{};
+  a.t = m->t;
+  a.pix = static_cast<unsigned*>(workspace);
+  a.width = width; a.height = height; a.max_radius = prm->max_radius;
+  a.min_count = (unsigned)prm->min_count;
+  a.voxel_size = m->prm.voxel_size;
+  memcpy(a.m, w2c12, sizeof(a.m));
+  a.focal = cam->focal; a.cx = cam->cx; a.cy = cam->cy; a.baseline = cam->baseline;
+  a.counts = reinterpret_cast<u64*>(counts);
+  VoxelResolveArgs b{};
+  b.pix = a.pix; b.disp = disp16; b.inten = intensity;
+  b.n = (size_t)width * (size_t)height;
+  b.vec = ((uintptr_t)workspace & 15u) == 0 && ((uintptr_t)disp16 & 7u) == 0 && ((uintptr_t)intensity & 3u) == 0;
+  b.counts = a.counts;
+  const unsigned blocks = (unsigned)((m->cap + (size_t)VX_T * VX_ITEMS - 1) / ((size_t)VX_T * VX_ITEMS));
+  const unsigned rblocks = (unsigned)((b.n + (size_t)VX_T * 4 - 1) / ((size_t)VX_T * 4));
+  SvoProfScope prof(ctx, SVO_PROF_VOXEL_RENDER);
+  SVO_HIP_CHECK(ctx, hipMemsetAsync(workspace, 0, 4 * b.n, ctx->stream));
+  if (counts) SVO_HIP_CHECK(ctx, hipMemsetAsync(counts, 0, 4 * sizeof(u64), ctx->stream));
+  if (m->render_coop) {
+    if (m->render_pre) hipLaunchKernelGGL((voxel_splat_kernel<true, true>), dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((voxel_splat_kernel<false, true>), dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
+  } else {
+    if (m->render_pre) hipLaunchKernelGGL((voxel_splat_kernel<true, false>), dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((voxel_splat_kernel<false, false>), dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
+  }
+  SVO_HIP_CHECK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(voxel_resolve_kernel, dim3(rblocks), dim3(VX_T), 0, ctx->stream, b);
+  SVO_HIP_CHECK(ctx, hipGetLastError());
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_map_render_pose7_dev(svo_voxel_map* m, int width, int height, const svo_camera_info* cam, const double* pose7,
+                                              const svo_voxel_render_params* prm, void* workspace, int16_t* disp16, uint8_t* intensity,
+                                              uint64_t* counts) {
+  if (!m) return SVO_ERR_INVALID;
+  SVO_REQUIRE(m->ctx, pose7, "voxel_map_render_pose7: null pose7");
+  double m12[12];
+  svo_pose7_to_world_to_cam(pose7, m12);
+  return svo_voxel_map_render_dev(m, width, height, cam, m12, prm, workspace, disp16, intensity, counts);
+}
+
+extern "C" int svo_voxel_map_render(svo_voxel_map* m, int width, int height, const svo_camera_info* cam, const double* w2c12,
+                                    const svo_voxel_render_params* prm, int16_t* disp16, uint8_t* intensity, uint64_t* counts) {
+  if (!m) return SVO_ERR_INVALID;
+  svo_ctx* ctx = m->ctx;
+  svo_use_device(ctx);
+  int rc = voxel_render_check(m, width, height, cam, w2c12, prm);
+  if (rc) return rc;
+  SVO_REQUIRE(ctx, disp16, "voxel_map_render: null disp16");
+  const size_t n = (size_t)width * (size_t)height, n16 = (n + 15) & ~(size_t)15;  // every part 16-byte aligned
+  unsigned char* d = nullptr;                                                      // 4 counts | pix | disp16 | intensity
+  SVO_HIP_CHECK(ctx, hipMalloc((void**)&d, 4 * sizeof(u64) + 7 * n16));
+  unsigned char* d_pix = d + 4 * sizeof(u64);
+  int16_t* d_disp = reinterpret_cast<int16_t*>(d_pix + 4 * n16);
+  uint8_t* d_int = d_pix + 6 * n16;
+  u64 c[4] = {0, 0, 0, 0};
+  rc = svo_voxel_map_render_dev(m, width, height, cam, w2c12, prm, d_pix, d_disp, intensity ? d_int : nullptr, reinterpret_cast<uint64_t*>(d));
+  hipError_t e = hipSuccess;
+  if (!rc) e = hipMemcpyAsync(disp16, d_disp, sizeof(int16_t) * n, hipMemcpyDeviceToHost, ctx->stream);
+  if (!rc && e == hipSuccess && intensity) e = hipMemcpyAsync(intensity, d_int, n, hipMemcpyDeviceToHost, ctx->stream);
+  if (!rc && e == hipSuccess) e = hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // also before the free, whatever failed
+  if (e == hipSuccess) e = e2;
+  (void)hipFree(d);
+  if (rc) return rc;
+  if (e != hipSuccess) { ctx->err = std::string("voxel_map_render: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
+  if (counts) for (int i = 0; i < 4; ++i) counts[i] = c[i];
   return SVO_OK;
 }

@@ -27,7 +27,12 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      the same capacity ("voxel_copy") and one svo_voxel_map_carve_dev of it with the batch's last disparity map under its pose
      ("voxel_carve": first with keep_count 1, which walks, projects and reads the windows but protects every voxel, then the real
      one), each beside the time hbm_copy needs for 8 bytes per slot + 32 per live slot (+ 40 per copied voxel); and the 96-lane
-     load with every keyframe inserted against every keyframe's map carving its lane's map before its cloud is inserted.
+     load with every keyframe inserted against every keyframe's map carving its lane's map before its cloud is inserted;
+  9. render: one svo_voxel_map_render_dev of each filled map of section 7 (before section 8 carves it) at 1241 x 376 under the last
+     cloud's pose ("voxel_render" bracket: two memsets and both launches, mean of 5), at the defaults and with max_radius 0, with the
+     four counts, n_splat as the number of atomic requests, and the time hbm_copy needs for 8 bytes per slot + 32 per qualifying
+     slot + 11 per pixel (memset, resolve read, two writes); and the default render again in the splat launch's other three drawing
+     modes (svo_voxel_render_set_mode).  No 96-lane figure: a render is per published view, not per keyframe.
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -253,8 +258,48 @@ def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy):
                         "stats_after_fresh": stats[vs], "load": stats[vs]["n_voxels"] / vm.capacity,
                         "extract_ms": ms / k, "extract_n_total": int(c2.cpu()[0]), "table_bytes_bound_ms": 1e3 * 40 * vm.capacity / copy,
                         "extract_share_of_bound": (1e3 * 40 * vm.capacity / copy) / (ms / k)})
+            out[-1].update(render_view(S, torch, ctx, cam, vm, np.asarray(m12[batch - 1]), warmup, copy))  # before the carve changes the map
             out[-1].update(carve_and_copy(S, torch, ctx, cam, dm, vm, np.asarray(m12[batch - 1]), warmup, copy))
             vm.close()
+    return out
+
+
+def render_view(S, torch, ctx, cam, vm, c2w, warmup, copy):
+    """Section 9 for one filled map: what it shows a camera at the last cloud's pose."""
+    w2c = np.linalg.inv(np.vstack([c2w.reshape(3, 4), [0, 0, 0, 1]]))[:3].reshape(12)
+    ws = torch.empty(W * H, dtype=torch.int32, device="cuda")
+    dd = torch.empty(W * H, dtype=torch.int16, device="cuda")
+    gg = torch.empty(W * H, dtype=torch.uint8, device="cuda")
+    cnt = torch.zeros(4, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+
+    def timed(max_radius, coop=True, pre=False):
+        vm.render_set_mode(coop, pre)
+        kw = dict(w2c12=w2c, max_radius=max_radius, workspace_ptr=ws.data_ptr(), disp_ptr=dd.data_ptr(), intensity_ptr=gg.data_ptr(),
+                  counts_ptr=cnt.data_ptr())
+        for _ in range(warmup):
+            vm.render(W, H, cam, **kw)
+        ctx.profile_select("voxel_render")
+        for _ in range(5):
+            vm.render(W, H, cam, **kw)
+        ms, k = ctx.profile_read()
+        ctx.profile_select("")
+        vm.render_set_mode()  # back to the defaults
+        return ms / k, [int(v) for v in cnt.cpu()], dd.cpu().numpy().tobytes(), gg.cpu().numpy().tobytes()
+
+    prm = S.api.voxel_render_default_params()
+    out = {}
+    for name, radius in (("render", prm.max_radius), ("render_r0", 0)):
+        ms, counts, _, _ = timed(radius)
+        bound = 1e3 * (8 * vm.capacity + 32 * counts[0] + 11 * W * H) / copy
+        out.update({name + "_ms": ms, name + "_counts": counts, name + "_bound_ms": bound, name + "_share_of_bound": bound / ms})
+    ref = timed(prm.max_radius)
+    modes = {}
+    for coop, pre in ((True, True), (True, False), (False, True), (False, False)):
+        got = timed(prm.max_radius, coop, pre)
+        modes[("cooperative" if coop else "own lane") + (", pre-check" if pre else ", no pre-check")] = got[0]
+        assert got[1:] == ref[1:], "a drawing mode changed the render"
+    out.update({"render_max_radius": prm.max_radius, "render_modes_ms": modes})
     return out
 
 
@@ -467,7 +512,14 @@ def main():
                         f"  carve with the batch's last map under its pose (radius 1, margin16 8): keep_count 1 (every voxel protected) {1e3 * c['carve_dry_ms']:.1f} us "
                         f"(mean of 5), counts {c['carve_dry_counts']}; keep_count 0 {1e3 * c['carve_ms']:.1f} us (one launch), counts {c['carve_counts']} (live, tested, carved); "
                         f"8 B per slot + 32 B per live slot at hbm_copy {1e3 * c['carve_bound_ms']:.1f} us -> {100 * c['carve_dry_share_of_bound']:.1f} % / "
-                        f"{100 * c['carve_share_of_bound']:.1f} % of that bound\n")
+                        f"{100 * c['carve_share_of_bound']:.1f} % of that bound\n"
+                        f"  render at {W} x {H} under the last cloud's pose (two memsets + splat + resolve, mean of 5): max_radius {c['render_max_radius']} "
+                        f"{1e3 * c['render_ms']:.1f} us, counts {c['render_counts']} (qualifying, drawn, splat = atomic requests, pixels); 8 B per slot + 32 B per "
+                        f"qualifying slot + 11 B per pixel at hbm_copy {1e3 * c['render_bound_ms']:.1f} us -> {100 * c['render_share_of_bound']:.1f} % of that bound; "
+                        f"max_radius 0 {1e3 * c['render_r0_ms']:.1f} us, counts {c['render_r0_counts']}, {100 * c['render_r0_share_of_bound']:.1f} % of its bound "
+                        f"({1e3 * c['render_r0_bound_ms']:.1f} us)\n"
+                        f"  the default render by drawing mode of the splat launch (same image in all four, us): "
+                        f"{ {k: round(1e3 * v, 1) for k, v in c['render_modes_ms'].items()} }\n")
             if g:
                 f.write(f"{g['lanes']} lanes in {g['groups']} groups, {g['frames_per_step_per_lane']}-frame steps, median of {g['rounds']} alternating rounds of "
                         f"{g['steps']} steps, clouds at step {g['cloud_step']}:\n  without clouds {g['frames_per_s_plain']:.0f} frames/s ({g['step_ms_plain']:.1f} ms / step), "
