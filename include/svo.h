@@ -99,7 +99,9 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * "stereo_sgm" (the launches of one semi-global matching call as one bracket), "voxel_insert" (one svo_voxel_map_insert_dev),
  * "voxel_extract" (one svo_voxel_map_extract_dev: the counts' memset and the launch), "voxel_carve" (one
  * svo_voxel_map_carve_dev: the counts' memset and the launch), "voxel_copy" (one svo_voxel_map_copy_live_dev), "voxel_render" (one
- * svo_voxel_map_render_dev: the two memsets and both launches);
+ * svo_voxel_map_render_dev: the two memsets and both launches), "voxel_remove" (one svo_voxel_map_remove_dev: the counts' memset and
+ * the launch), "voxel_move" (one svo_voxel_map_move_dev: the counts' memset, the removal and the insert; the launches inside it
+ * are not counted as "voxel_remove" or "voxel_insert");
  * NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
@@ -367,7 +369,8 @@ int svo_stereo_sgm(svo_ctx* ctx, const uint8_t* left, const uint8_t* right, int 
  *      slot, 168 MB at the default).  Home slot h = fmix64(key) & (cap - 1) with fmix64(k): k ^= k >> 33; k *= 0xff51afd7ed558ccd;
  *      k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53; k ^= k >> 33.  Linear probing, at most SVO_VOXEL_MAX_PROBES probes, each a 64-bit
  *      atomic compare-and-swap of keys[h] from EMPTY to key whose RETURN value decides (EMPTY: claimed; key: found; anything else:
- *      next slot).  After SVO_VOXEL_MAX_PROBES foreign slots the record is dropped and counted: a full table costs a bounded time.
+ *      next slot).  That rule is about launches that CLAIM slots (insert, copy); a launch that claims nothing (extraction, carve,
+ *      render, removal) reads keys written by earlier launches on the same stream, and there a load may decide.  After SVO_VOXEL_MAX_PROBES foreign slots the record is dropped and counted: a full table costs a bounded time.
  *      The bound is part of the contract.
  *   Counters.  n_voxels (slots claimed), n_inserted, n_rejected, n_dropped (points); inserted + rejected + dropped = records given.
  *   Order independence.  While n_dropped == 0 the occupied slot set and every voxel's payload depend on no thread order (the set
@@ -545,6 +548,84 @@ int svo_voxel_map_render(svo_voxel_map* map, int width, int height, const svo_ca
  * (else every lane draws its own); precheck != 0: a plain load skips the atomic where the pixel already holds at least the value.
  * Neither can change a bit of the outputs.  Default: cooperative on, precheck off (DESIGN 7h gives the figures). */
 int svo_voxel_render_set_mode(svo_voxel_map* map, int cooperative, int precheck);
+
+/* Voxel map removal: a cloud taken back out of the map, the exact inverse of its insert, and the move of a cloud from one pose to
+ * another (a keyframe whose pose bundle adjustment refined).  A voxel's payload is four integer sums and a record's contribution is
+ * a pure function of the record's bytes, the matrix bits and voxel_size, so subtracting the same contribution undoes the insert bit
+ * for bit, in any order.  Integers, or f64 operations in the stated order without contraction.  Inputs: the map, n records at a
+ * DEVICE pointer (4-byte aligned), m12 (camera->world, 12 HOST doubles, by value), optional counts (4 u64 on the device, 8-byte
+ * aligned, zeroed on the stream before the launch).
+ *   1. Reject, transform, key and fractions are items 1-3 of the voxel map, word for word.  A record's contribution is the insert's:
+ *      c = 1, i = tag >> 24, f_0, f_1, f_2.
+ *   2. Find, never claim.  From the home slot fmix64(key) & (cap - 1), linear probing, at most SVO_VOXEL_MAX_PROBES slots:
+ *      keys[h] == key: found; EMPTY: absent; anything else: next slot; after 64 foreign slots the key is absent.  A removal writes no
+ *      key, and every key it reads was written by an earlier launch on the same stream: a load decides.  keys, n_voxels and the other
+ *      three map counters are byte-identical after any removal (n_inserted keeps counting what was ever inserted).
+ *   3. Saturating subtraction, per field.  Over a whole launch a voxel holding (count, isum, sx, sy, sz) whose found contributions sum
+ *      to (C, I, F_0, F_1, F_2) ends with count' = max(0, count - C).  count' == 0: isum' = sx' = sy' = sz' = 0 - a voxel emptied by a
+ *      removal is exactly a carved voxel: the key stays and a later insert starts it again.  Otherwise isum' = max(0, isum - I) and
+ *      s_r' = max(0, s_r - F_r).  Successive saturating subtractions equal one saturating subtraction of the sum, and a count that
+ *      reached 0 stays 0 for the rest of the launch: the result depends on no thread order, also where item 4 does not hold.
+ *   4. Exact inverse.  If the removal has the record bytes, the m12 bits, the voxel_size and the max_depth of an earlier insert, that
+ *      insert's n_dropped did not grow, and no carve has zeroed one of its voxels since, then afterwards every payload word is what
+ *      the map would hold had that insert never happened, and n_short == 0 and n_missing == 0.
+ *   5. counts = {n_removed, n_rejected, n_missing, n_short}, in points.  n_removed: records whose key was found; n_missing: key
+ *      absent; removed + rejected + missing = n.  n_short: over all found contributions the part of C the count field no longer
+ *      held, sum of c - min(c, count before that step), which is C - (count - count') per voxel in any order.  One relaxed atomicAdd
+ *      per workgroup and non-zero counter.
+ *   6. KNOWN PROPERTY.  A voxel that was carved, then refilled by other clouds, and only then has the old cloud removed loses mass that
+ *      was not the old cloud's; n_short sees it only when the count runs out.  A per-voxel record of who contributed is what a hash
+ *      of sums cannot hold.  The order of use that avoids it: update poses BEFORE carving with them (see the ledger below).
+ *   7. SVO_ERR_INVALID with the argument named, nothing launched and the map usable afterwards: a null map, points (with n > 0), m12,
+ *      from_m12 or to_m12 (pose7 for the pose entries); n < 0; points not 4-byte or counts not 8-byte aligned.  n == 0 is a no-op:
+ *      nothing is launched and counts is not written.
+ * Synchronisation as for the voxel map: relaxed device-scope atomics only, everything on svo_stream(ctx), ordered by launch. */
+/* Asynchronous: the counts' memset and one launch. */
+int svo_voxel_map_remove_dev(svo_voxel_map* map, const svo_cloud_point* points, int n, const double* m12, uint64_t* counts);
+/* svo_pose7_to_cam_to_world, then svo_voxel_map_remove_dev. */
+int svo_voxel_map_remove_pose7_dev(svo_voxel_map* map, const svo_cloud_point* points, int n, const double* pose7, uint64_t* counts);
+/* svo_voxel_map_remove_dev with counts of its own, synchronous: counts[4] on the HOST (not NULL; all 0 for n == 0). */
+int svo_voxel_map_remove_sync(svo_voxel_map* map, const svo_cloud_point* points, int n, const double* m12, uint64_t* counts);
+/* The removal under from_m12, then the insert under to_m12: two launches on the stream; counts are the removal's.  When the two
+ * matrices are equal in every bit nothing is launched, counts is not written, and the call succeeds.  There is no fused launch:
+ * saturation does not commute with additions, so one launch would make the result depend on the thread order. */
+int svo_voxel_map_move_dev(svo_voxel_map* map, const svo_cloud_point* points, int n, const double* from_m12, const double* to_m12,
+                           uint64_t* counts);
+/* svo_pose7_to_cam_to_world of both poses, then svo_voxel_map_move_dev. */
+int svo_voxel_map_move_pose7_dev(svo_voxel_map* map, const svo_cloud_point* points, int n, const double* from_pose7,
+                                 const double* to_pose7, uint64_t* counts);
+
+/* Voxel map ledger: the clouds of the keyframes still in the bundle adjuster's window, kept on the device with the pose each was
+ * inserted under, so that "this keyframe's pose is now X" is one call.  The ledger owns a copy of every held cloud (a pipeline's
+ * cloud is valid only until the next process call) and remembers the matrix bits of its insert, which the removal needs.
+ * Order of use: insert each new keyframe's cloud, update the held ones whenever newer poses exist, retire a keyframe when it leaves
+ * the window, and carve only AFTER updating (item 6 above).  create is the only allocation; every other entry is asynchronous on
+ * the map's stream, without synchronisation or device allocation.  Refusals are SVO_ERR_INVALID with the argument named and nothing
+ * launched. */
+typedef struct svo_voxel_ledger_params {
+  int max_keyframes; /* >= 1: clouds held at once */
+  int max_points;    /* >= 1: records per cloud */
+} svo_voxel_ledger_params;
+typedef struct svo_voxel_ledger svo_voxel_ledger;
+/* Device bytes a ledger allocates: 16 * max_keyframes * max_points.  Pure; SVO_ERR_INVALID and *bytes = 0 for refused parameters. */
+int svo_voxel_ledger_bytes(const svo_voxel_ledger_params* params, size_t* bytes);
+/* Destroy the ledger before its map. */
+int svo_voxel_ledger_create(svo_voxel_map* map, const svo_voxel_ledger_params* params, svo_voxel_ledger** out);
+void svo_voxel_ledger_destroy(svo_voxel_ledger* ledger);
+/* Copies the n records device->device into a free slot, inserts the copy into the map under pose7 and records pose7 and the matrix
+ * computed from it.  Refused when the id is held, when no slot is free, when n > max_points or n < 0. */
+int svo_voxel_ledger_insert_pose7_dev(svo_voxel_ledger* ledger, int64_t id, const svo_cloud_point* points, int n, const double* pose7);
+/* svo_voxel_map_move_dev of the held copy from the recorded matrix to pose7's, then records pose7.  counts: the removal's, or NULL.
+ * An unknown id is refused. */
+int svo_voxel_ledger_update_pose7(svo_voxel_ledger* ledger, int64_t id, const double* pose7, uint64_t* counts);
+/* The pose is final: the map is untouched and the slot is free for the next insert (safe: everything is ordered on one stream). */
+int svo_voxel_ledger_retire(svo_voxel_ledger* ledger, int64_t id);
+/* Removes the held copy from the map (svo_voxel_map_remove_dev under the recorded matrix) and frees the slot. */
+int svo_voxel_ledger_remove(svo_voxel_ledger* ledger, int64_t id, uint64_t* counts);
+/* The held ids in ascending order: at most `capacity` are written (ids may be NULL when capacity == 0), *n is how many are held. */
+int svo_voxel_ledger_ids(svo_voxel_ledger* ledger, int64_t* ids, int capacity, int* n);
+/* What is held under id: the recorded pose7 (7 doubles), the record count and the DEVICE pointer of the copy; each may be NULL. */
+int svo_voxel_ledger_get(svo_voxel_ledger* ledger, int64_t id, double* pose7, int* n, const svo_cloud_point** points);
 
 /* ------------------------------------------------------------------- a8 --
  * ImageProcessor::triangulate_stereo's reprojection loop

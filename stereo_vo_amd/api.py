@@ -172,6 +172,22 @@ def pose7_to_cam_to_world(pose7):
     return m
 
 
+class VoxelLedgerParams(C.Structure):
+    """svo_voxel_ledger_params: clouds held at once (>= 1), records per cloud (>= 1)."""
+    _fields_ = [("max_keyframes", C.c_int), ("max_points", C.c_int)]
+
+
+def voxel_ledger_bytes(max_keyframes, max_points):
+    """svo_voxel_ledger_bytes: 16 * max_keyframes * max_points (no GPU involved); raises for parameters the ledger refuses."""
+    n = C.c_size_t(0)
+    if lib().svo_voxel_ledger_bytes(C.byref(VoxelLedgerParams(int(max_keyframes), int(max_points))), C.byref(n)) != 0:
+        raise SvoError("svo_voxel_ledger_bytes: max_keyframes and max_points must be at least 1")
+    return int(n.value)
+
+
+REMOVE_COUNTS = ("n_removed", "n_rejected", "n_missing", "n_short")
+
+
 class VoxelCarveParams(C.Structure):
     """svo_voxel_carve_params: window half width (0..3), margin in sixteenths of disparity (0..32767), keep_count (0 = off)."""
     _fields_ = [("radius", C.c_int), ("margin16", C.c_int), ("keep_count", C.c_int)]
@@ -421,6 +437,9 @@ SYMBOLS = [
     "svo_pipeline_copy_keyframe_disparity", "svo_pipeline_group_copy_keyframe_disparity",
     "svo_voxel_render_default_params", "svo_voxel_render_workspace_bytes", "svo_voxel_map_render_dev", "svo_voxel_map_render_pose7_dev",
     "svo_voxel_map_render", "svo_voxel_render_set_mode",
+    "svo_voxel_map_remove_dev", "svo_voxel_map_remove_pose7_dev", "svo_voxel_map_remove_sync", "svo_voxel_map_move_dev", "svo_voxel_map_move_pose7_dev",
+    "svo_voxel_ledger_bytes", "svo_voxel_ledger_create", "svo_voxel_ledger_destroy", "svo_voxel_ledger_insert_pose7_dev",
+    "svo_voxel_ledger_update_pose7", "svo_voxel_ledger_retire", "svo_voxel_ledger_remove", "svo_voxel_ledger_ids", "svo_voxel_ledger_get",
 ]
 
 
@@ -529,6 +548,27 @@ def lib():
         L.svo_voxel_render_set_mode.argtypes = [vp, ci, ci]
         for f in ("svo_voxel_render_default_params", "svo_voxel_map_render_dev", "svo_voxel_map_render_pose7_dev", "svo_voxel_map_render",
                   "svo_voxel_render_set_mode"):
+            getattr(L, f).restype = ci
+        # removal, move and the keyframe ledger
+        i64 = C.c_int64
+        L.svo_voxel_map_remove_dev.argtypes = [vp, vp, ci, vp, vp]
+        L.svo_voxel_map_remove_pose7_dev.argtypes = [vp, vp, ci, vp, vp]
+        L.svo_voxel_map_remove_sync.argtypes = [vp, vp, ci, vp, vp]
+        L.svo_voxel_map_move_dev.argtypes = [vp, vp, ci, vp, vp, vp]
+        L.svo_voxel_map_move_pose7_dev.argtypes = [vp, vp, ci, vp, vp, vp]
+        L.svo_voxel_ledger_bytes.argtypes = [vp, vp]
+        L.svo_voxel_ledger_create.argtypes = [vp, vp, vp]
+        L.svo_voxel_ledger_destroy.argtypes = [vp]
+        L.svo_voxel_ledger_destroy.restype = None
+        L.svo_voxel_ledger_insert_pose7_dev.argtypes = [vp, i64, vp, ci, vp]
+        L.svo_voxel_ledger_update_pose7.argtypes = [vp, i64, vp, vp]
+        L.svo_voxel_ledger_retire.argtypes = [vp, i64]
+        L.svo_voxel_ledger_remove.argtypes = [vp, i64, vp]
+        L.svo_voxel_ledger_ids.argtypes = [vp, vp, ci, vp]
+        L.svo_voxel_ledger_get.argtypes = [vp, i64, vp, vp, vp]
+        for f in ("svo_voxel_map_remove_dev", "svo_voxel_map_remove_pose7_dev", "svo_voxel_map_remove_sync", "svo_voxel_map_move_dev", "svo_voxel_map_move_pose7_dev",
+                  "svo_voxel_ledger_bytes", "svo_voxel_ledger_create", "svo_voxel_ledger_insert_pose7_dev", "svo_voxel_ledger_update_pose7",
+                  "svo_voxel_ledger_retire", "svo_voxel_ledger_remove", "svo_voxel_ledger_ids", "svo_voxel_ledger_get"):
             getattr(L, f).restype = ci
         _LIB = L
     return _LIB
@@ -925,6 +965,41 @@ class VoxelMap:
             q = _f64(pose7).reshape(7)
             self.ctx._chk(self.L.svo_voxel_map_insert_pose7_dev(self.h, dev_ptr, int(n), _p(q)), "svo_voxel_map_insert_pose7_dev")
 
+    def remove(self, dev_ptr, n, m12=None, pose7=None, counts_ptr=None):
+        """svo_voxel_map_remove_dev / _pose7_dev: the n records at the device pointer taken back out under m12 or pose7 (exactly one):
+        the exact inverse of the insert that had the same records and the same matrix bits.  counts_ptr: 4 uint64 on the device
+        {n_removed, n_rejected, n_missing, n_short}, or None.  Asynchronous on the context's stream."""
+        if (m12 is None) == (pose7 is None):
+            raise ValueError("VoxelMap.remove: give exactly one of m12 and pose7")
+        if m12 is not None:
+            m = _f64(m12).reshape(12)
+            self.ctx._chk(self.L.svo_voxel_map_remove_dev(self.h, dev_ptr, int(n), _p(m), counts_ptr), "svo_voxel_map_remove_dev")
+        else:
+            q = _f64(pose7).reshape(7)
+            self.ctx._chk(self.L.svo_voxel_map_remove_pose7_dev(self.h, dev_ptr, int(n), _p(q), counts_ptr), "svo_voxel_map_remove_pose7_dev")
+
+    def remove_host_counts(self, dev_ptr, n, m12=None, pose7=None):
+        """remove() with counts of its own, synchronous: returns {"n_removed", "n_rejected", "n_missing", "n_short"}."""
+        if (m12 is None) == (pose7 is None):
+            raise ValueError("VoxelMap.remove_host_counts: give exactly one of m12 and pose7")
+        m = _f64(pose7_to_cam_to_world(pose7) if m12 is None else m12).reshape(12)
+        c = np.zeros(4, np.uint64)
+        self.ctx._chk(self.L.svo_voxel_map_remove_sync(self.h, dev_ptr, int(n), _p(m), _p(c)), "svo_voxel_map_remove_sync")
+        return dict(zip(REMOVE_COUNTS, (int(v) for v in c)))
+
+    def move(self, dev_ptr, n, from_m12=None, to_m12=None, from_pose7=None, to_pose7=None, counts_ptr=None):
+        """svo_voxel_map_move_dev / _pose7_dev: the removal under from_..., then the insert under to_... (both as m12 or both as
+        pose7).  Matrices equal in every bit launch nothing.  counts_ptr: the removal's counts, or None.  Asynchronous."""
+        by_m, by_q = from_m12 is not None and to_m12 is not None, from_pose7 is not None and to_pose7 is not None
+        if by_m == by_q or (by_m and (from_pose7 is not None or to_pose7 is not None)) or (by_q and (from_m12 is not None or to_m12 is not None)):
+            raise ValueError("VoxelMap.move: give from_m12 and to_m12, or from_pose7 and to_pose7")
+        if by_m:
+            a, b = _f64(from_m12).reshape(12), _f64(to_m12).reshape(12)
+            self.ctx._chk(self.L.svo_voxel_map_move_dev(self.h, dev_ptr, int(n), _p(a), _p(b), counts_ptr), "svo_voxel_map_move_dev")
+        else:
+            a, b = _f64(from_pose7).reshape(7), _f64(to_pose7).reshape(7)
+            self.ctx._chk(self.L.svo_voxel_map_move_pose7_dev(self.h, dev_ptr, int(n), _p(a), _p(b), counts_ptr), "svo_voxel_map_move_pose7_dev")
+
     def insert_keyframe_clouds(self, table, poses7):
         """The list Pipeline.keyframe_clouds() / PipelineGroup.keyframe_clouds() returns, one pose7 per entry: every entry's device
         cloud is inserted from its "dev" pointer (no host copy).  Call before the next process call replaces the clouds."""
@@ -1039,6 +1114,67 @@ class VoxelMap:
         buf = np.empty((5, self.capacity), np.uint64)
         self.ctx._chk(self.L.svo_voxel_map_download(self.h, _p(buf), buf.nbytes), "svo_voxel_map_download")
         return {k: buf[i] for i, k in enumerate(("keys", "ci", "sx", "sy", "sz"))}
+
+
+class VoxelLedger:
+    """svo_voxel_ledger: the clouds of the keyframes still in the window, held on the device with the pose each was inserted under
+    (include/svo.h, "voxel map ledger").  insert each new keyframe, update the held ones when newer poses exist, retire one when it
+    leaves the window, carve only after updating.  Close it before its map."""
+
+    def __init__(self, vmap, max_keyframes, max_points):
+        self.map, self.ctx, self.L = vmap, vmap.ctx, vmap.L
+        self.params = VoxelLedgerParams(int(max_keyframes), int(max_points))
+        self.h = C.c_void_p()
+        self.ctx._chk(self.L.svo_voxel_ledger_create(vmap.h, C.byref(self.params), C.byref(self.h)), "svo_voxel_ledger_create")
+
+    def close(self):
+        if self.h:
+            if self.map.h and self.ctx.h:
+                self.L.svo_voxel_ledger_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def insert(self, id, dev_ptr, n, pose7):
+        """The n records at the device pointer are copied into the ledger and the copy is inserted into the map under pose7."""
+        q = _f64(pose7).reshape(7)
+        self.ctx._chk(self.L.svo_voxel_ledger_insert_pose7_dev(self.h, int(id), dev_ptr, int(n), _p(q)), "svo_voxel_ledger_insert_pose7_dev")
+
+    def update(self, id, pose7, counts_ptr=None):
+        """The held cloud moves from the pose it was last inserted under to pose7 (nothing is launched when the matrices agree)."""
+        q = _f64(pose7).reshape(7)
+        self.ctx._chk(self.L.svo_voxel_ledger_update_pose7(self.h, int(id), _p(q), counts_ptr), "svo_voxel_ledger_update_pose7")
+
+    def update_all(self, poses7):
+        """{id: pose7}: update() of each, in ascending id order."""
+        for k in sorted(poses7):
+            self.update(k, poses7[k])
+
+    def retire(self, id):
+        """The pose is final: the map keeps the cloud, the slot is free."""
+        self.ctx._chk(self.L.svo_voxel_ledger_retire(self.h, int(id)), "svo_voxel_ledger_retire")
+
+    def remove(self, id, counts_ptr=None):
+        """The held cloud is taken out of the map and the slot is free."""
+        self.ctx._chk(self.L.svo_voxel_ledger_remove(self.h, int(id), counts_ptr), "svo_voxel_ledger_remove")
+
+    def ids(self):
+        """The held ids, ascending."""
+        out = np.zeros(self.params.max_keyframes, np.int64)
+        n = C.c_int(0)
+        self.ctx._chk(self.L.svo_voxel_ledger_ids(self.h, _p(out), len(out), C.byref(n)), "svo_voxel_ledger_ids")
+        return [int(v) for v in out[:n.value]]
+
+    def get(self, id):
+        """{"pose7", "n", "dev"}: the recorded pose, the record count and the device pointer of the held copy."""
+        q = np.zeros(7, np.float64)
+        n, dev = C.c_int(0), C.c_void_p()
+        self.ctx._chk(self.L.svo_voxel_ledger_get(self.h, int(id), _p(q), C.byref(n), C.byref(dev)), "svo_voxel_ledger_get")
+        return {"pose7": q, "n": n.value, "dev": dev.value or 0}
 
 
 class BA:

@@ -7,6 +7,11 @@
 //                          first lane (a segmented sum, see below) and only those run heads probe (64-bit atomicCAS on keys[],
 //                          linear, at most SVO_VOXEL_MAX_PROBES slots) and issue the four atomicAdds.  Integer sums commute, so the
 //                          table is the same with or without the merge.  The four counters get one atomicAdd per workgroup each.
+//   voxel_remove_kernel  : the insert's exact inverse: the insert's front half and wavefront merge, then a run head
+//                          FINDS its slot by plain loads (it never claims: keys[] and the map's counters are only read)
+//                          and subtracts its sums, saturating at 0 per field: one 64-bit CAS loop on the count | intensity word,
+//                          then either three saturating CAS loops on the sums or, in the step that takes the count to 0, three
+//                          non-returning atomic ANDs with 0.  No thread can see a wrapped word, so the result depends on no order.
 //   voxel_extract_kernel : VX_ITEMS * 256 slots per workgroup; svo_compact_slot inside the workgroup, one returning atomicAdd per
 //                          workgroup for its base in the output (whose order is free), one for its share of n_stored.
 //
@@ -34,12 +39,16 @@
 //                          stores where the pointers allow it, else and in the tail pixel by pixel); counts the covered pixels.
 //
 // Nothing passes between workgroups except order-independent relaxed device-scope atomics (docs/HISTORY.md, "No cache maintenance
-// inside kernels"): no fence, no acquire / release, no waiting.  The CAS's RETURN value decides a probe, never a plain load; the
-// payload words are only ever added to by inserts and copies, zeroed only by a carve (a launch of its own, ordered by the stream,
-// each thread its own slot), and are read by a LATER launch on the same stream (extraction, carve, copy, download).  A full table
-// costs at most 64 probes per run head: bounded work, no spinning.
+// inside kernels"): no fence, no acquire / release, no waiting.  In a launch that CLAIMS slots (insert, copy) the CAS's RETURN value
+// decides a probe, never a plain load; a launch that claims nothing (extraction, carve, splat, removal) reads keys an earlier launch
+// on the same stream wrote, and there a load may decide.  The payload words are added to by inserts and copies, subtracted from
+// (saturating) by a removal, zeroed by a carve (a launch of its own, ordered by the stream, each thread its own slot), and are read
+// by a LATER launch on the same stream (extraction, carve, copy, download).  A full table costs at most 64 probes per run head:
+// bounded work, no spinning; the removal's CAS loops retry only when another head's subtraction got in first, and every head
+// subtracts a bounded number of times.
 #include "kernels.h"
 #include "tail_device.h"
+#include "voxel_ledger.h"
 
 namespace {
 typedef unsigned long long u64;
@@ -60,6 +69,15 @@ struct VoxelInsertArgs {
   double m[12];
   float voxel_size, max_depth;
   VoxelTable t;
+};
+
+struct VoxelRemoveArgs {
+  const svo_cloud_point* pts;
+  int n;
+  double m[12];
+  float voxel_size, max_depth;
+  VoxelTable t;
+  u64* counts;  // {n_removed, n_rejected, n_missing, n_short}, zeroed on the stream before the launch; or null
 };
 
 struct VoxelExtractArgs {
@@ -224,6 +242,149 @@ __global__ __launch_bounds__(VX_T) void voxel_insert_kernel(VoxelInsertArgs a) {
     unsigned t = 0;
     for (int w = 0; w < VX_T / 64; ++w) t += sC[tid][w];
     if (t) __hip_atomic_fetch_add(&a.t.counters[tid], (u64)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// The removal.  Its front half (items 1-3 of the contract: reject, transform, key and fractions) and its wavefront merge
+// are the insert's, statement for statement, written a second time: as functions shared with voxel_insert_kernel they changed that
+// kernel's code (34 -> 50 SGPRs, another branch structure), and the insert keeps its code.  A rejected (or absent) record leaves
+// key = EMPTY and a zero contribution.
+__device__ __forceinline__ void vx_record(const VoxelRemoveArgs& a, size_t i, bool valid, u64& key, unsigned& ci, unsigned& fx, unsigned& fy, unsigned& fz) {
+  key = VX_EMPTY;
+  ci = 0; fx = 0; fy = 0; fz = 0;
+  if (valid) {
+    const svo_cloud_point p = a.pts[i];  // one 16-byte load (global memory takes it at 4-byte alignment)
+    const float x = p.x, y = p.y, z = p.z;
+    const unsigned tag = p.tag;
+    if (z > 0.0f && !(a.max_depth > 0.0f && z > a.max_depth)) {
+      const double xd = (double)x, yd = (double)y, zd = (double)z, vs = (double)a.voxel_size;
+      double q[3];
+      bool in = true;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const double w = a.m[4 * r] * xd + a.m[4 * r + 1] * yd + a.m[4 * r + 2] * zd + a.m[4 * r + 3];
+        q[r] = w / vs;
+        in = in && q[r] >= -VX_LIMIT && q[r] < VX_LIMIT;
+      }
+      if (in) {
+        u64 k[3];
+        unsigned f[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          const double fl = floor(q[r]);
+          k[r] = (u64)((long long)fl + (1ll << 20));
+          const u64 fr = (u64)floor((q[r] - fl) * 65536.0);
+          f[r] = (unsigned)(fr < 65535ull ? fr : 65535ull);
+        }
+        key = k[0] | (k[1] << 21) | (k[2] << 42);
+        ci = (1u << 16) | (tag >> 24);
+        fx = f[0]; fy = f[1]; fz = f[2];
+      }
+    }
+  }
+}
+
+// The wavefront merge: the runs of equal keys inside a wavefront are summed into their first lane.  Returns whether
+// this lane is a run head; afterwards a head holds its run's sums.
+__device__ __forceinline__ bool vx_merge(int lane, u64 key, unsigned& ci, unsigned& fx, unsigned& fy, unsigned& fz) {
+  // run heads: lane 0, or a key other than the lane before's (rejected records carry EMPTY: they form runs too and never probe)
+  const u64 prev = __shfl_up(key, 1);
+  const bool head = lane == 0 || prev != key;
+  const u64 heads = __ballot(head);
+  // segmented sum: after the round with offset o a lane holds the sum over [lane, min(lane + 2 o, end of its run)); the rounds
+  // stop (wavefront-uniformly) once no lane has a partner inside its run, which is at once when nothing merges
+  const u64 after = lane == 63 ? 0ull : heads >> (lane + 1);
+  const int end = after ? lane + 1 + __builtin_ctzll(after) : 64;
+  for (int o = 1; o < 64; o <<= 1) {
+    const bool take = lane + o < end;
+    if (!__ballot(take)) break;
+    const unsigned c = __shfl_down(ci, o), sx = __shfl_down(fx, o), sy = __shfl_down(fy, o), sz = __shfl_down(fz, o);
+    if (take) { ci += c; fx += sx; fy += sy; fz += sz; }
+  }
+  return head;
+}
+
+// The removal's find (item 2 of "Voxel map removal"): the insert's walk with a load in place of the CAS.  A removal writes no key, and
+// every key it reads was written by an earlier launch on the same stream, so here a load may decide.
+__device__ __forceinline__ bool vx_find(const VoxelTable& t, u64 key, u64& h) {
+  h = vx_fmix64(key) & t.mask;
+  for (int p = 0; p < SVO_VOXEL_MAX_PROBES; ++p) {
+    const u64 k = t.keys[h];
+    if (k == key) return true;
+    if (k == VX_EMPTY) return false;
+    h = (h + 1) & t.mask;
+  }
+  return false;
+}
+
+// *p = max(0, *p - v): a compare-and-swap loop whose every step is the saturating subtraction of the value it replaces, so that no
+// other thread ever sees a wrapped word.
+__device__ __forceinline__ void vx_sub_sat(u64* p, u64 v) {
+  if (v == 0ull) return;
+  u64 old = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  while (old != 0ull) {
+    const u64 now = old > v ? old - v : 0ull;
+    if (__hip_atomic_compare_exchange_strong(p, &old, now, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+  }
+}
+
+__global__ __launch_bounds__(VX_T) void voxel_remove_kernel(VoxelRemoveArgs a) {
+  __shared__ unsigned sC[4][VX_T / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t i = (size_t)blockIdx.x * VX_T + (size_t)tid;
+  const bool valid = i < (size_t)a.n;
+  u64 key;
+  unsigned ci, fx, fy, fz;
+  vx_record(a, i, valid, key, ci, fx, fy, fz);
+  const bool head = vx_merge(lane, key, ci, fx, fy, fz);
+  bool missing = false;
+  unsigned n_short = 0;
+  if (head && key != VX_EMPTY) {
+    u64 h;
+    if (vx_find(a.t, key, h)) {
+      // count and intensity sum share a word: one CAS applies item 3 to both.  Once the count is 0 the word is 0 and stays 0.
+      const u64 C = (u64)(ci >> 16), I = (u64)(ci & 0xFFFFu), lo40 = (1ull << 40) - 1ull;
+      u64 old = __hip_atomic_load(&a.t.ci[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), count, left;
+      for (;;) {
+        count = old >> 40;
+        left = count > C ? count - C : 0ull;
+        const u64 isum = old & lo40;
+        const u64 now = left ? (left << 40) | (isum > I ? isum - I : 0ull) : 0ull;
+        if (now == old) break;
+        if (__hip_atomic_compare_exchange_strong(&a.t.ci[h], &old, now, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+      }
+      n_short = (unsigned)(C - (count - left));
+      if (left) {
+        vx_sub_sat(&a.t.sx[h], (u64)fx); vx_sub_sat(&a.t.sy[h], (u64)fy); vx_sub_sat(&a.t.sz[h], (u64)fz);
+      } else if (count) {  // the step that emptied the voxel: whatever the other heads still subtract, 0 stays 0
+        __hip_atomic_fetch_and(&a.t.sx[h], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_and(&a.t.sy[h], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_and(&a.t.sz[h], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    } else {
+      missing = true;
+    }
+  }
+  if (!a.counts) return;  // uniform over the launch
+  // counts, in points: ballots, and sums only where a wavefront has something to sum
+  const unsigned n_valid = (unsigned)__popcll(__ballot(valid));
+  const unsigned n_rej = (unsigned)__popcll(__ballot(valid && key == VX_EMPTY));
+  unsigned n_miss = 0;
+  if (__ballot(missing)) {
+    n_miss = missing ? ci >> 16 : 0u;
+    for (int o = 32; o > 0; o >>= 1) n_miss += __shfl_xor(n_miss, o);
+  }
+  if (__ballot(n_short != 0u)) {
+    for (int o = 32; o > 0; o >>= 1) n_short += __shfl_xor(n_short, o);
+  }
+  if (lane == 0) {
+    sC[0][wave] = n_valid - n_rej - n_miss; sC[1][wave] = n_rej; sC[2][wave] = n_miss; sC[3][wave] = n_short;
+  }
+  __syncthreads();
+  if (tid < 4) {
+    unsigned t = 0;
+    for (int w = 0; w < VX_T / 64; ++w) t += sC[tid][w];
+    if (t) __hip_atomic_fetch_add(&a.counts[tid], (u64)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -606,25 +767,38 @@ extern "C" int svo_voxel_map_clear(svo_voxel_map* m) {
   return voxel_clear(m);
 }
 
-extern "C" int svo_voxel_map_insert_dev(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* m12) {
-  if (!m) return SVO_ERR_INVALID;
+// The arguments every entry that takes a cloud shares (insert, removal, move): `what` opens the message.
+static int voxel_cloud_check(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* m12, const char* what, const char* m12_name) {
   svo_ctx* ctx = m->ctx;
-  svo_use_device(ctx);
-  SVO_REQUIRE(ctx, n >= 0, "voxel_map_insert: n must not be negative");
-  SVO_REQUIRE(ctx, m12, "voxel_map_insert: null m12");
+  if (n < 0) { ctx->err = std::string(what) + ": n must not be negative"; return SVO_ERR_INVALID; }
+  if (!m12) { ctx->err = std::string(what) + ": null " + m12_name; return SVO_ERR_INVALID; }
   if (n == 0) return SVO_OK;
-  SVO_REQUIRE(ctx, points, "voxel_map_insert: null points");
-  SVO_REQUIRE(ctx, ((uintptr_t)points & 3u) == 0, "voxel_map_insert: points must be 4-byte aligned");
+  if (!points) { ctx->err = std::string(what) + ": null points"; return SVO_ERR_INVALID; }
+  if (((uintptr_t)points & 3u) != 0) { ctx->err = std::string(what) + ": points must be 4-byte aligned"; return SVO_ERR_INVALID; }
+  return SVO_OK;
+}
+
+static int voxel_insert_launch(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* m12) {
+  svo_ctx* ctx = m->ctx;
   VoxelInsertArgs a{};
   a.pts = points; a.n = n;
   memcpy(a.m, m12, sizeof(a.m));
   a.voxel_size = m->prm.voxel_size; a.max_depth = m->prm.max_depth;
   a.t = m->t;
   const unsigned blocks = (unsigned)(((size_t)n + VX_T - 1) / VX_T);
-  SvoProfScope prof(ctx, SVO_PROF_VOXEL_INSERT);
   hipLaunchKernelGGL(voxel_insert_kernel, dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
   SVO_HIP_CHECK(ctx, hipGetLastError());
   return SVO_OK;
+}
+
+extern "C" int svo_voxel_map_insert_dev(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* m12) {
+  if (!m) return SVO_ERR_INVALID;
+  svo_ctx* ctx = m->ctx;
+  svo_use_device(ctx);
+  const int rc = voxel_cloud_check(m, points, n, m12, "voxel_map_insert", "m12");
+  if (rc || n == 0) return rc;
+  SvoProfScope prof(ctx, SVO_PROF_VOXEL_INSERT);
+  return voxel_insert_launch(m, points, n, m12);
 }
 
 extern "C" int svo_voxel_map_insert_pose7_dev(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* pose7) {
@@ -943,5 +1117,212 @@ extern "C" int svo_voxel_map_render(svo_voxel_map* m, int width, int height, con
   if (rc) return rc;
   if (e != hipSuccess) { ctx->err = std::string("voxel_map_render: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
   if (counts) for (int i = 0; i < 4; ++i) counts[i] = c[i];
+  return SVO_OK;
+}
+
+// ----------------------------------------------------------------------------- removal and move
+static int voxel_counts_check(svo_voxel_map* m, const uint64_t* counts, const char* what) {
+  if (((uintptr_t)counts & 7u) != 0) { m->ctx->err = std::string(what) + ": counts must be 8-byte aligned"; return SVO_ERR_INVALID; }
+  return SVO_OK;
+}
+
+static int voxel_remove_launch(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* m12, uint64_t* counts) {
+  svo_ctx* ctx = m->ctx;
+  VoxelRemoveArgs a{};
+  a.pts = points; a.n = n;
+  memcpy(a.m, m12, sizeof(a.m));
+  a.voxel_size = m->prm.voxel_size; a.max_depth = m->prm.max_depth;
+  a.t = m->t;
+  a.counts = reinterpret_cast<u64*>(counts);
+  const unsigned blocks = (unsigned)(((size_t)n + VX_T - 1) / VX_T);
+  if (counts) SVO_HIP_CHECK(ctx, hipMemsetAsync(counts, 0, 4 * sizeof(u64), ctx->stream));
+  hipLaunchKernelGGL(voxel_remove_kernel, dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
+  SVO_HIP_CHECK(ctx, hipGetLastError());
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_map_remove_dev(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* m12, uint64_t* counts) {
+  if (!m) return SVO_ERR_INVALID;
+  svo_ctx* ctx = m->ctx;
+  svo_use_device(ctx);
+  int rc = voxel_cloud_check(m, points, n, m12, "voxel_map_remove", "m12");
+  if (!rc) rc = voxel_counts_check(m, counts, "voxel_map_remove");
+  if (rc || n == 0) return rc;
+  SvoProfScope prof(ctx, SVO_PROF_VOXEL_REMOVE);
+  return voxel_remove_launch(m, points, n, m12, counts);
+}
+
+extern "C" int svo_voxel_map_remove_pose7_dev(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* pose7, uint64_t* counts) {
+  if (!m) return SVO_ERR_INVALID;
+  SVO_REQUIRE(m->ctx, pose7, "voxel_map_remove_pose7: null pose7");
+  double m12[12];
+  svo_pose7_to_cam_to_world(pose7, m12);
+  return svo_voxel_map_remove_dev(m, points, n, m12, counts);
+}
+
+extern "C" int svo_voxel_map_remove_sync(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* m12, uint64_t* counts) {
+  if (!m) return SVO_ERR_INVALID;
+  svo_ctx* ctx = m->ctx;
+  svo_use_device(ctx);
+  SVO_REQUIRE(ctx, counts, "voxel_map_remove_sync: null counts");
+  u64 c[4] = {0, 0, 0, 0};
+  SvoScratch scratch(ctx);
+  u64* d = scratch.take<u64>(4);  // the context's scratch: this call ends with the stream drained
+  SVO_REQUIRE(ctx, d, "voxel_map_remove_sync: the context has no scratch");
+  const int rc = svo_voxel_map_remove_dev(m, points, n, m12, reinterpret_cast<uint64_t*>(d));
+  if (rc) return rc;
+  if (n > 0) SVO_HIP_CHECK(ctx, hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
+  SVO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  for (int i = 0; i < 4; ++i) counts[i] = c[i];
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_map_move_dev(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* from_m12, const double* to_m12,
+                                      uint64_t* counts) {
+  if (!m) return SVO_ERR_INVALID;
+  svo_ctx* ctx = m->ctx;
+  svo_use_device(ctx);
+  int rc = voxel_cloud_check(m, points, n, from_m12, "voxel_map_move", "from_m12");
+  if (!rc && !to_m12) { ctx->err = "voxel_map_move: null to_m12"; rc = SVO_ERR_INVALID; }
+  if (!rc) rc = voxel_counts_check(m, counts, "voxel_map_move");
+  if (rc || n == 0) return rc;
+  if (memcmp(from_m12, to_m12, 12 * sizeof(double)) == 0) return SVO_OK;  // the same bits: the cloud is where it belongs
+  SvoProfScope prof(ctx, SVO_PROF_VOXEL_MOVE);
+  rc = voxel_remove_launch(m, points, n, from_m12, counts);
+  return rc ? rc : voxel_insert_launch(m, points, n, to_m12);
+}
+
+extern "C" int svo_voxel_map_move_pose7_dev(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* from_pose7,
+                                            const double* to_pose7, uint64_t* counts) {
+  if (!m) return SVO_ERR_INVALID;
+  SVO_REQUIRE(m->ctx, from_pose7, "voxel_map_move_pose7: null from_pose7");
+  SVO_REQUIRE(m->ctx, to_pose7, "voxel_map_move_pose7: null to_pose7");
+  double from[12], to[12];
+  svo_pose7_to_cam_to_world(from_pose7, from);
+  svo_pose7_to_cam_to_world(to_pose7, to);
+  return svo_voxel_map_move_dev(m, points, n, from, to, counts);
+}
+
+// ----------------------------------------------------------------------------- the keyframe ledger
+// The bookkeeping is host/voxel_ledger.h; here are the device copy of the held clouds and the calls.
+struct svo_voxel_ledger {
+  svo_voxel_map* map = nullptr;
+  VoxelLedgerTable table;
+  svo_cloud_point* d_points = nullptr;  // max_keyframes slots of max_points records
+  svo_cloud_point* at(int slot) const { return d_points + (size_t)slot * (size_t)table.max_points(); }
+};
+
+extern "C" int svo_voxel_ledger_bytes(const svo_voxel_ledger_params* params, size_t* bytes) { return VoxelLedgerTable::bytes(params, bytes); }
+
+extern "C" int svo_voxel_ledger_create(svo_voxel_map* map, const svo_voxel_ledger_params* params, svo_voxel_ledger** out) {
+  if (!map) return SVO_ERR_INVALID;
+  svo_ctx* ctx = map->ctx;
+  svo_use_device(ctx);
+  SVO_REQUIRE(ctx, out, "voxel_ledger_create: null out");
+  *out = nullptr;
+  svo_voxel_ledger* l = new svo_voxel_ledger();
+  l->map = map;
+  const char* err = nullptr;
+  if (l->table.init(params, &err)) { ctx->err = err; delete l; return SVO_ERR_INVALID; }
+  size_t bytes = 0;
+  VoxelLedgerTable::bytes(params, &bytes);
+  const hipError_t e = hipMalloc((void**)&l->d_points, bytes);
+  if (e != hipSuccess) {
+    ctx->err = std::string("voxel_ledger_create: hipMalloc of the held clouds: ") + hipGetErrorString(e);
+    delete l;
+    return SVO_ERR_HIP;
+  }
+  *out = l;
+  return SVO_OK;
+}
+
+extern "C" void svo_voxel_ledger_destroy(svo_voxel_ledger* l) {
+  if (!l) return;
+  svo_use_device(l->map->ctx);
+  (void)hipStreamSynchronize(l->map->ctx->stream);
+  (void)hipFree(l->d_points);
+  delete l;
+}
+
+extern "C" int svo_voxel_ledger_insert_pose7_dev(svo_voxel_ledger* l, int64_t id, const svo_cloud_point* points, int n, const double* pose7) {
+  if (!l) return SVO_ERR_INVALID;
+  svo_voxel_map* m = l->map;
+  svo_ctx* ctx = m->ctx;
+  svo_use_device(ctx);
+  SVO_REQUIRE(ctx, pose7, "voxel_ledger_insert: null pose7");
+  SVO_REQUIRE(ctx, points || n <= 0, "voxel_ledger_insert: null points");
+  SVO_REQUIRE(ctx, ((uintptr_t)points & 3u) == 0, "voxel_ledger_insert: points must be 4-byte aligned");
+  const char* err = nullptr;
+  int slot = -1;
+  if (l->table.admit(id, n, &slot, &err)) { ctx->err = err; return SVO_ERR_INVALID; }
+  double m12[12];
+  svo_pose7_to_cam_to_world(pose7, m12);
+  if (n > 0) {  // the ledger's own copy first: the caller's cloud is valid only until its next process call
+    SVO_HIP_CHECK(ctx, hipMemcpyAsync(l->at(slot), points, sizeof(svo_cloud_point) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
+    SvoProfScope prof(ctx, SVO_PROF_VOXEL_INSERT);
+    const int rc = voxel_insert_launch(m, l->at(slot), n, m12);
+    if (rc) return rc;
+  }
+  l->table.hold(slot, id, n, pose7, m12);
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_ledger_update_pose7(svo_voxel_ledger* l, int64_t id, const double* pose7, uint64_t* counts) {
+  if (!l) return SVO_ERR_INVALID;
+  svo_ctx* ctx = l->map->ctx;
+  svo_use_device(ctx);
+  SVO_REQUIRE(ctx, pose7, "voxel_ledger_update: null pose7");
+  const char* err = nullptr;
+  int slot = -1;
+  if (l->table.find(id, &slot, "voxel_ledger_update: unknown id", &err)) { ctx->err = err; return SVO_ERR_INVALID; }
+  double m12[12];
+  svo_pose7_to_cam_to_world(pose7, m12);
+  const VoxelLedgerSlot& s = l->table.slot(slot);
+  const int rc = svo_voxel_map_move_dev(l->map, l->at(slot), s.n, s.m12, m12, counts);
+  if (rc) return rc;
+  l->table.moved(slot, pose7, m12);
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_ledger_retire(svo_voxel_ledger* l, int64_t id) {
+  if (!l) return SVO_ERR_INVALID;
+  svo_ctx* ctx = l->map->ctx;
+  const char* err = nullptr;
+  int slot = -1;
+  if (l->table.find(id, &slot, "voxel_ledger_retire: unknown id", &err)) { ctx->err = err; return SVO_ERR_INVALID; }
+  l->table.release(slot);  // the next copy into the slot is behind every launch that read it: one stream
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_ledger_remove(svo_voxel_ledger* l, int64_t id, uint64_t* counts) {
+  if (!l) return SVO_ERR_INVALID;
+  svo_ctx* ctx = l->map->ctx;
+  svo_use_device(ctx);
+  const char* err = nullptr;
+  int slot = -1;
+  if (l->table.find(id, &slot, "voxel_ledger_remove: unknown id", &err)) { ctx->err = err; return SVO_ERR_INVALID; }
+  const VoxelLedgerSlot& s = l->table.slot(slot);
+  const int rc = svo_voxel_map_remove_dev(l->map, l->at(slot), s.n, s.m12, counts);
+  if (rc) return rc;
+  l->table.release(slot);
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_ledger_ids(svo_voxel_ledger* l, int64_t* ids, int capacity, int* n) {
+  if (!l) return SVO_ERR_INVALID;
+  const char* err = nullptr;
+  if (l->table.ids(ids, capacity, n, &err)) { l->map->ctx->err = err; return SVO_ERR_INVALID; }
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_ledger_get(svo_voxel_ledger* l, int64_t id, double* pose7, int* n, const svo_cloud_point** points) {
+  if (!l) return SVO_ERR_INVALID;
+  const char* err = nullptr;
+  int slot = -1;
+  if (l->table.find(id, &slot, "voxel_ledger_get: unknown id", &err)) { l->map->ctx->err = err; return SVO_ERR_INVALID; }
+  const VoxelLedgerSlot& s = l->table.slot(slot);
+  if (pose7) memcpy(pose7, s.pose7, sizeof(s.pose7));
+  if (n) *n = s.n;
+  if (points) *points = l->at(slot);
   return SVO_OK;
 }

@@ -33,6 +33,11 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      four counts, n_splat as the number of atomic requests, and the time hbm_copy needs for 8 bytes per slot + 32 per qualifying
      slot + 11 per pixel (memset, resolve read, two writes); and the default render again in the splat launch's other three drawing
      modes (svo_voxel_render_set_mode).  No 96-lane figure: a render is per published view, not per keyframe.
+ 10. removal and move: on each filled map of section 7 (before sections 8 and 9), one svo_voxel_map_remove_dev of the last inserted
+     cloud ("voxel_remove") and one svo_voxel_map_move_dev of it to a pose 1 cm and 0.1 degrees away ("voxel_move"), mean of 5 each,
+     beside one more svo_voxel_map_insert_dev of the same cloud in the same run and the time hbm_copy needs for its 16 bytes per
+     record; and the 96-lane load with clouds at step 4 with every lane's ledger holding four keyframes and moving all of them after
+     each call, beside clouds alone (--ledger-only runs just these two).
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -258,9 +263,49 @@ def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy):
                         "stats_after_fresh": stats[vs], "load": stats[vs]["n_voxels"] / vm.capacity,
                         "extract_ms": ms / k, "extract_n_total": int(c2.cpu()[0]), "table_bytes_bound_ms": 1e3 * 40 * vm.capacity / copy,
                         "extract_share_of_bound": (1e3 * 40 * vm.capacity / copy) / (ms / k)})
+            out[-1].update(remove_and_move(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, copy))
             out[-1].update(render_view(S, torch, ctx, cam, vm, np.asarray(m12[batch - 1]), warmup, copy))  # before the carve changes the map
             out[-1].update(carve_and_copy(S, torch, ctx, cam, dm, vm, np.asarray(m12[batch - 1]), warmup, copy))
             vm.close()
+    return out
+
+
+def remove_and_move(torch, ctx, vm, cloud, n, angle, forward, warmup, copy):
+    """Section 10 for one filled map: the last inserted cloud taken out ("voxel_remove"), moved to a pose 1 cm and 0.1 degrees away
+    ("voxel_move": the removal and the insert) and, as the yardstick of the same run, inserted once more ("voxel_insert"); mean of 5
+    each.  Every timed call is undone by its untimed inverse, so the map is afterwards what it was."""
+    import voxel_ref as V
+    here, there = V.rot_y(angle, (0.0, 0.0, forward)), V.rot_y(angle + np.deg2rad(0.1), (0.01, 0.0, forward))
+    cnt = torch.zeros(4, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    p, c = cloud.data_ptr(), cnt.data_ptr()
+    calls = {"remove": (lambda: vm.remove(p, n, m12=here, counts_ptr=c), lambda: vm.insert(p, n, m12=here), "voxel_remove"),
+             "move": (lambda: vm.move(p, n, from_m12=here, to_m12=there, counts_ptr=c), lambda: vm.move(p, n, from_m12=there, to_m12=here), "voxel_move"),
+             "insert": (lambda: vm.insert(p, n, m12=here), lambda: vm.remove(p, n, m12=here), "voxel_insert")}
+    out, before = {}, vm.stats()
+    for name, (do, undo, bracket) in calls.items():
+        for _ in range(warmup):
+            do()
+            undo()
+        total = 0.0
+        for _ in range(5):
+            ctx.profile_select(bracket)
+            do()
+            ms, k = ctx.profile_read()
+            assert k == 1, (bracket, k)
+            total += ms
+            ctx.profile_select("")
+            if name != "insert":
+                counts = [int(v) for v in cnt.cpu()]
+            undo()
+        out[name + "_ms"] = total / 5
+        if name != "insert":
+            out[name + "_counts"] = counts
+            assert counts[2] == 0 and counts[3] == 0, (name, counts)  # nothing missing, nothing short: the exact inverse
+    after = vm.stats()
+    assert after["n_dropped"] == before["n_dropped"], (before, after)
+    out["remove_move_bound_ms"] = 1e3 * 16 * n / copy
+    out["remove_move_points"] = n
     return out
 
 
@@ -340,7 +385,11 @@ def carve_and_copy(S, torch, ctx, cam, dm, vm, c2w, warmup, copy):
             "carve_dry_share_of_bound": carve_bound / (dry_ms / k), "carve_share_of_bound": carve_bound / carve_ms}
 
 
-def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
+LEDGER_HELD = 4
+LEDGER_DELTA = np.array([0.0, 0.0, 0.5 * np.deg2rad(0.1), 0.0, 0.01, 0.0, 0.0])  # pose7: 0.1 degrees about y and 1 cm
+
+
+def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px, ledger_only=False):
     from stereo_vo_amd import api
     bench.group_lines(n_groups)
     seeds = [0x5EED0001 + i for i in range(lanes)]
@@ -364,12 +413,37 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
                 lane_maps[gi][e.lane].carve(g.pipe.keyframe_disparity(i), W, H, g.pipe.prm.cam, pose7=q)
             lane_maps[gi][e.lane].insert(e.dev, e.n_stored, pose7=q)
 
-    def run(k, voxel=False, carve=False):
+    lane_ledgers = [None] * n_groups  # per lane: its own map, a ledger on it, and what the ledger holds as [id, pose7, moved?]
+
+    def ledger_clouds(gi, g):  # the ledger loop of INTEGRATION 4a: retire the oldest of four, insert the new, then move every held one
+        if lane_ledgers[gi] is None:
+            maps = [S.VoxelMap(g.ctx, capacity_log2=VOXEL_LANE_LOG2) for _ in range(g.pipe.n_lanes)]
+            lane_ledgers[gi] = [{"map": m, "led": S.VoxelLedger(m, LEDGER_HELD, prm.max_points), "held": [], "next": 0} for m in maps]
+        n, tab = C.c_int(0), C.POINTER(api.KeyframeCloud)()
+        g.ctx._chk(g.pipe.L.svo_pipeline_group_keyframe_clouds(g.pipe.h, C.byref(n), C.byref(tab)), "svo_pipeline_group_keyframe_clouds")
+        for i in range(n.value):
+            e = tab[i]
+            q = list(g.all_res[e.lane][e.frame].pose7)
+            q = np.array(q if any(q[:4]) else [1, 0, 0, 0, 0, 0, 0], np.float64)
+            st = lane_ledgers[gi][e.lane]
+            if len(st["held"]) == LEDGER_HELD:
+                st["led"].retire(st["held"].pop(0)[0])
+            st["led"].insert(st["next"], e.dev, e.n_stored, q)
+            st["held"].append([st["next"], q, False])
+            st["next"] += 1
+        for st in lane_ledgers[gi]:
+            for h in st["held"]:  # there and back in turn: every update moves the cloud
+                h[2] = not h[2]
+                st["led"].update(h[0], h[1] + LEDGER_DELTA if h[2] else h[1])
+
+    def run(k, voxel=False, carve=False, ledger=False):
         def work(gi, g):
             for _ in range(k):
                 g.step()
                 if voxel:
                     insert_clouds(gi, g, carve)
+                if ledger:
+                    ledger_clouds(gi, g)
         bench.run_threads([lambda gi=gi, g=g: work(gi, g) for gi, g in enumerate(groups)])
 
     def table_len(pipe):  # entries of the last call's table (no point is copied)
@@ -378,7 +452,7 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
         pipe.ctx._chk(pipe.L.svo_pipeline_group_keyframe_clouds(pipe.h, C.byref(n), C.byref(tab)), "svo_pipeline_group_keyframe_clouds")
         return n.value
 
-    def timed(on, speckle=False, lr=False, sgm=False, voxel=False, carve=False):
+    def timed(on, speckle=False, lr=False, sgm=False, voxel=False, carve=False, ledger=False):
         for g in groups:
             g.pipe.set_keyframe_clouds(-1, prm if on else None)
             if on:
@@ -386,19 +460,45 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
                 g.pipe.set_keyframe_lr_check(LR_DIFF if lr else None)
                 g.pipe.set_keyframe_sgm(on=sgm)
             g.clear_counters()
-        run(warmup, voxel, carve)
+        run(warmup, voxel, carve, ledger)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run(steps, voxel, carve)
+        run(steps, voxel, carve, ledger)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         kf = sum(table_len(g.pipe) for g in groups) if on else 0  # of the last step
         return lanes * frames * steps / dt, 1e3 * dt / steps, kf
 
-    plain, cloud, filt, chk, sg, vox, crv = [], [], [], [], [], [], []
+    plain, cloud, filt, chk, sg, vox, crv, led = [], [], [], [], [], [], [], []
+
+    def ledger_result():
+        held = sum(len(st["held"]) for sts in lane_ledgers if sts for st in sts)
+        lstats = {k: sum(st["map"].stats()[k] for sts in lane_ledgers if sts for st in sts) for k in ("n_voxels", "n_inserted", "n_rejected", "n_dropped")}
+        for sts in lane_ledgers:
+            for st in sts or []:
+                st["led"].close()
+                st["map"].close()
+        return {"lanes": lanes, "groups": n_groups, "frames_per_step_per_lane": frames, "steps": steps, "rounds": rounds, "cloud_step": step_px,
+                "ledger_held_per_lane": LEDGER_HELD, "ledger_held_at_the_end": held, "ledger_totals_over_all_lane_maps": lstats,
+                "frames_per_s_clouds": float(np.median([x[0] for x in cloud])), "step_ms_clouds": float(np.median([x[1] for x in cloud])),
+                "all_clouds": [x[0] for x in cloud], "frames_per_s_clouds_ledger": float(np.median([x[0] for x in led])),
+                "step_ms_clouds_ledger": float(np.median([x[1] for x in led])), "all_clouds_ledger": [x[0] for x in led],
+                "ratio_ledger_to_clouds": float(np.median([x[0] for x in led])) / float(np.median([x[0] for x in cloud])),
+                "round_ratios_ledger_to_clouds": [b[0] / a[0] for a, b in zip(cloud, led)]}
+
+    if ledger_only:
+        for _ in range(rounds):
+            cloud.append(timed(True))
+            led.append(timed(True, ledger=True))
+            print(f"bench_dense: ledger round {len(led)} of {rounds} done", file=sys.stderr, flush=True)
+        out = ledger_result()
+        for g in groups:
+            g.close()
+        return out
     for _ in range(rounds):  # alternating: other people's work shares the host
         plain.append(timed(False))
         cloud.append(timed(True))
+        led.append(timed(True, ledger=True))
         filt.append(timed(True, True))
         chk.append(timed(True, False, True))
         sg.append(timed(True, sgm=True))
@@ -409,6 +509,7 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
     for ms in lane_maps:
         for m in ms or []:
             m.close()
+    ledger = ledger_result()  # reads the lane maps' counters and closes them: before their contexts go
     for g in groups:
         g.close()
     med = lambda xs: float(np.median(xs))
@@ -432,7 +533,8 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px):
             "voxel_totals_over_all_lane_maps": vstats,
             "frames_per_s_clouds_voxel_carve": med([x[0] for x in crv]), "ratio_carve_to_voxel": med([x[0] for x in crv]) / med([x[0] for x in vox]),
             "step_ms_clouds_voxel_carve": med([x[1] for x in crv]), "all_clouds_voxel_carve": [x[0] for x in crv],
-            "round_ratios_carve_to_voxel": [b[0] / a[0] for a, b in zip(vox, crv)]}
+            "round_ratios_carve_to_voxel": [b[0] / a[0] for a, b in zip(vox, crv)],
+            **{k: v for k, v in ledger.items() if "ledger" in k}}
 
 
 def api_sub():
@@ -452,6 +554,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--cloud-step", type=int, default=4)
     ap.add_argument("--skip-groups", action="store_true")
+    ap.add_argument("--ledger-only", action="store_true", help="of the 96-lane loads only clouds alone and clouds with the ledger loop")
     ap.add_argument("--out", help="write the text report here as well")
     a = ap.parse_args()
     import torch
@@ -461,7 +564,7 @@ def main():
     res = {"standalone": standalone(S, torch, a.batch, 3, a.reps)}
     print("bench_dense: standalone sections done", file=sys.stderr, flush=True)
     if not a.skip_groups:
-        res["pipeline_groups"] = grouped(S, torch, a.lanes, a.groups, a.frames, a.warmup, a.steps, a.rounds, a.cloud_step)
+        res["pipeline_groups"] = grouped(S, torch, a.lanes, a.groups, a.frames, a.warmup, a.steps, a.rounds, a.cloud_step, a.ledger_only)
     try:
         res["commit"] = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
     except OSError:
@@ -519,8 +622,20 @@ def main():
                         f"max_radius 0 {1e3 * c['render_r0_ms']:.1f} us, counts {c['render_r0_counts']}, {100 * c['render_r0_share_of_bound']:.1f} % of its bound "
                         f"({1e3 * c['render_r0_bound_ms']:.1f} us)\n"
                         f"  the default render by drawing mode of the splat launch (same image in all four, us): "
-                        f"{ {k: round(1e3 * v, 1) for k, v in c['render_modes_ms'].items()} }\n")
-            if g:
+                        f"{ {k: round(1e3 * v, 1) for k, v in c['render_modes_ms'].items()} }\n"
+                        f"  removal of the last inserted cloud ({c['remove_move_points']} points, mean of 5): {1e3 * c['remove_ms']:.1f} us, counts {c['remove_counts']} "
+                        f"(removed, rejected, missing, short); move to a pose 1 cm and 0.1 degrees away (removal + insert): {1e3 * c['move_ms']:.1f} us, counts "
+                        f"{c['move_counts']}; the same cloud inserted once more, same run: {1e3 * c['insert_ms']:.1f} us -> removal / insert "
+                        f"{c['remove_ms'] / c['insert_ms']:.2f}, move / insert {c['move_ms'] / c['insert_ms']:.2f}; 16 B per record at hbm_copy "
+                        f"{1e3 * c['remove_move_bound_ms']:.2f} us\n")
+            if g and "ratio_ledger_to_clouds" in g:
+                f.write(f"{g['lanes']} lanes in {g['groups']} groups, {g['frames_per_step_per_lane']}-frame steps, {g['rounds']} alternating rounds of {g['steps']} steps, clouds at "
+                        f"step {g['cloud_step']}, every lane's ledger holding {g['ledger_held_per_lane']} keyframes and moving all of them (1 cm, 0.1 degrees) after each call: "
+                        f"{g['frames_per_s_clouds_ledger']:.0f} frames/s ({g['step_ms_clouds_ledger']:.1f} ms / step) beside clouds alone {g['frames_per_s_clouds']:.0f}: ratio "
+                        f"{g['ratio_ledger_to_clouds']:.3f}; rounds: {[round(x) for x in g['all_clouds_ledger']]} beside {[round(x) for x in g['all_clouds']]}; per round "
+                        f"{[round(x, 3) for x in g['round_ratios_ledger_to_clouds']]}; held at the end {g['ledger_held_at_the_end']}; totals over all lane maps: "
+                        f"{g['ledger_totals_over_all_lane_maps']}\n")
+            if g and "frames_per_s_plain" in g:
                 f.write(f"{g['lanes']} lanes in {g['groups']} groups, {g['frames_per_step_per_lane']}-frame steps, median of {g['rounds']} alternating rounds of "
                         f"{g['steps']} steps, clouds at step {g['cloud_step']}:\n  without clouds {g['frames_per_s_plain']:.0f} frames/s ({g['step_ms_plain']:.1f} ms / step), "
                         f"with {g['frames_per_s_clouds']:.0f} frames/s ({g['step_ms_clouds']:.1f} ms / step): ratio {g['ratio']:.3f}\n"
