@@ -147,6 +147,17 @@ class VoxelMapStats(C.Structure):
 VOXEL_MAX_PROBES = 64  # SVO_VOXEL_MAX_PROBES
 
 
+def _params(default, given, **overrides):
+    """A copy of `given` (or default() when it is None), then the overrides that are not None, each as its field's own type."""
+    prm = default()
+    for name, _ in prm._fields_:
+        if given is not None:
+            setattr(prm, name, getattr(given, name))
+        if overrides.get(name) is not None:
+            setattr(prm, name, type(getattr(prm, name))(overrides[name]))
+    return prm
+
+
 def voxel_map_default_params():
     """svo_voxel_map_default_params: voxel_size 0.1, capacity_log2 22, max_depth 0."""
     p = VoxelMapParams()
@@ -202,14 +213,7 @@ def voxel_carve_default_params():
 
 
 def _carve_params(params, radius, margin16, keep_count):
-    prm = voxel_carve_default_params() if params is None else VoxelCarveParams(params.radius, params.margin16, params.keep_count)
-    if radius is not None:
-        prm.radius = int(radius)
-    if margin16 is not None:
-        prm.margin16 = int(margin16)
-    if keep_count is not None:
-        prm.keep_count = int(keep_count)
-    return prm
+    return _params(voxel_carve_default_params, params, radius=radius, margin16=margin16, keep_count=keep_count)
 
 
 def pose7_to_world_to_cam(pose7):
@@ -240,12 +244,7 @@ def voxel_render_workspace_bytes(width, height):
 
 
 def _render_params(params, min_count, max_radius):
-    prm = voxel_render_default_params() if params is None else VoxelRenderParams(params.min_count, params.max_radius)
-    if min_count is not None:
-        prm.min_count = int(min_count)
-    if max_radius is not None:
-        prm.max_radius = int(max_radius)
-    return prm
+    return _params(voxel_render_default_params, params, min_count=min_count, max_radius=max_radius)
 
 
 SPECKLE_TILE = (64, 16)  # SVO_SPECKLE_TILE_W, SVO_SPECKLE_TILE_H
@@ -926,13 +925,7 @@ class VoxelMap:
 
     def __init__(self, ctx, params=None, voxel_size=None, capacity_log2=None, max_depth=None):
         self.ctx, self.L = ctx, ctx.L
-        prm = voxel_map_default_params() if params is None else VoxelMapParams(params.voxel_size, params.capacity_log2, params.max_depth)
-        if voxel_size is not None:
-            prm.voxel_size = float(voxel_size)
-        if capacity_log2 is not None:
-            prm.capacity_log2 = int(capacity_log2)
-        if max_depth is not None:
-            prm.max_depth = float(max_depth)
+        prm = _params(voxel_map_default_params, params, voxel_size=voxel_size, capacity_log2=capacity_log2, max_depth=max_depth)
         self.params = prm
         self.h = C.c_void_p()
         ctx._chk(self.L.svo_voxel_map_create(ctx.h, C.byref(prm), C.byref(self.h)), "svo_voxel_map_create")
@@ -953,38 +946,34 @@ class VoxelMap:
     def clear(self):
         self.ctx._chk(self.L.svo_voxel_map_clear(self.h), "svo_voxel_map_clear")
 
+    def _by_pose(self, who, name, matrix, pose7, entry, head, tail=(), to_matrix=None):
+        """Exactly one of the 3 x 4 matrix (the argument called `name`) and pose7: svo_voxel_map_<entry>_dev(map, *head, matrix, *tail)
+        or its _pose7_dev form; for an entry that has no pose7 form, to_matrix makes the matrix and svo_voxel_map_<entry> is called."""
+        if (matrix is None) == (pose7 is None):
+            raise ValueError(f"VoxelMap.{who}: give exactly one of {name} and pose7")
+        if to_matrix is not None:
+            fn, a = "svo_voxel_map_" + entry, _f64(to_matrix(pose7) if matrix is None else matrix).reshape(12)
+        elif pose7 is None:
+            fn, a = f"svo_voxel_map_{entry}_dev", _f64(matrix).reshape(12)
+        else:
+            fn, a = f"svo_voxel_map_{entry}_pose7_dev", _f64(pose7).reshape(7)
+        self.ctx._chk(getattr(self.L, fn)(self.h, *head, _p(a), *tail), fn)
+
     def insert(self, dev_ptr, n, m12=None, pose7=None):
         """n CLOUD_POINT_DTYPE records at the device pointer (an int) under m12 (3 x 4 camera->world) or pose7, exactly one of them.
         Asynchronous on the context's stream."""
-        if (m12 is None) == (pose7 is None):
-            raise ValueError("VoxelMap.insert: give exactly one of m12 and pose7")
-        if m12 is not None:
-            m = _f64(m12).reshape(12)
-            self.ctx._chk(self.L.svo_voxel_map_insert_dev(self.h, dev_ptr, int(n), _p(m)), "svo_voxel_map_insert_dev")
-        else:
-            q = _f64(pose7).reshape(7)
-            self.ctx._chk(self.L.svo_voxel_map_insert_pose7_dev(self.h, dev_ptr, int(n), _p(q)), "svo_voxel_map_insert_pose7_dev")
+        self._by_pose("insert", "m12", m12, pose7, "insert", (dev_ptr, int(n)))
 
     def remove(self, dev_ptr, n, m12=None, pose7=None, counts_ptr=None):
         """svo_voxel_map_remove_dev / _pose7_dev: the n records at the device pointer taken back out under m12 or pose7 (exactly one):
         the exact inverse of the insert that had the same records and the same matrix bits.  counts_ptr: 4 uint64 on the device
         {n_removed, n_rejected, n_missing, n_short}, or None.  Asynchronous on the context's stream."""
-        if (m12 is None) == (pose7 is None):
-            raise ValueError("VoxelMap.remove: give exactly one of m12 and pose7")
-        if m12 is not None:
-            m = _f64(m12).reshape(12)
-            self.ctx._chk(self.L.svo_voxel_map_remove_dev(self.h, dev_ptr, int(n), _p(m), counts_ptr), "svo_voxel_map_remove_dev")
-        else:
-            q = _f64(pose7).reshape(7)
-            self.ctx._chk(self.L.svo_voxel_map_remove_pose7_dev(self.h, dev_ptr, int(n), _p(q), counts_ptr), "svo_voxel_map_remove_pose7_dev")
+        self._by_pose("remove", "m12", m12, pose7, "remove", (dev_ptr, int(n)), (counts_ptr,))
 
     def remove_host_counts(self, dev_ptr, n, m12=None, pose7=None):
         """remove() with counts of its own, synchronous: returns {"n_removed", "n_rejected", "n_missing", "n_short"}."""
-        if (m12 is None) == (pose7 is None):
-            raise ValueError("VoxelMap.remove_host_counts: give exactly one of m12 and pose7")
-        m = _f64(pose7_to_cam_to_world(pose7) if m12 is None else m12).reshape(12)
         c = np.zeros(4, np.uint64)
-        self.ctx._chk(self.L.svo_voxel_map_remove_sync(self.h, dev_ptr, int(n), _p(m), _p(c)), "svo_voxel_map_remove_sync")
+        self._by_pose("remove_host_counts", "m12", m12, pose7, "remove_sync", (dev_ptr, int(n)), (_p(c),), pose7_to_cam_to_world)
         return dict(zip(REMOVE_COUNTS, (int(v) for v in c)))
 
     def move(self, dev_ptr, n, from_m12=None, to_m12=None, from_pose7=None, to_pose7=None, counts_ptr=None):
@@ -1013,30 +1002,18 @@ class VoxelMap:
         """svo_voxel_map_carve_dev / _pose7_dev: the voxels the keyframe whose tight CV_16S map sits at the device pointer saw through
         lose their payload (the key stays).  Exactly one of w2c12 (3 x 4 world->camera) and pose7; counts_ptr: 3 uint64 on the
         device {n_live, n_tested, n_carved}, or None.  Asynchronous on the context's stream."""
-        if (w2c12 is None) == (pose7 is None):
-            raise ValueError("VoxelMap.carve: give exactly one of w2c12 and pose7")
         prm = _carve_params(params, radius, margin16, keep_count)
-        if w2c12 is not None:
-            m = _f64(w2c12).reshape(12)
-            self.ctx._chk(self.L.svo_voxel_map_carve_dev(self.h, disp_ptr, int(width), int(height), C.byref(cam), _p(m), C.byref(prm), counts_ptr),
-                          "svo_voxel_map_carve_dev")
-        else:
-            q = _f64(pose7).reshape(7)
-            self.ctx._chk(self.L.svo_voxel_map_carve_pose7_dev(self.h, disp_ptr, int(width), int(height), C.byref(cam), _p(q), C.byref(prm),
-                                                               counts_ptr), "svo_voxel_map_carve_pose7_dev")
+        self._by_pose("carve", "w2c12", w2c12, pose7, "carve", (disp_ptr, int(width), int(height), C.byref(cam)), (C.byref(prm), counts_ptr))
 
     def carve_host(self, disp16, cam, w2c12=None, pose7=None, params=None, radius=None, margin16=None, keep_count=None):
         """svo_voxel_map_carve: disp16 a (height, width) int16 numpy map; synchronous.  Returns {"n_live", "n_tested", "n_carved"}."""
-        if (w2c12 is None) == (pose7 is None):
-            raise ValueError("VoxelMap.carve_host: give exactly one of w2c12 and pose7")
         d = np.ascontiguousarray(disp16, np.int16)
         if d.ndim != 2:
             raise ValueError("VoxelMap.carve_host: disp16 must be a (height, width) map")
-        m = _f64(pose7_to_world_to_cam(pose7) if w2c12 is None else w2c12).reshape(12)
         prm = _carve_params(params, radius, margin16, keep_count)
         c = np.zeros(3, np.uint64)
-        self.ctx._chk(self.L.svo_voxel_map_carve(self.h, _p(d), d.shape[1], d.shape[0], C.byref(cam), _p(m), C.byref(prm), _p(c)),
-                      "svo_voxel_map_carve")
+        self._by_pose("carve_host", "w2c12", w2c12, pose7, "carve", (_p(d), d.shape[1], d.shape[0], C.byref(cam)), (C.byref(prm), _p(c)),
+                      pose7_to_world_to_cam)
         return {"n_live": int(c[0]), "n_tested": int(c[1]), "n_carved": int(c[2])}
 
     def copy_live_to(self, dst, min_count=1, box=None):
@@ -1053,33 +1030,21 @@ class VoxelMap:
         counts_ptr 4 uint64 {n_qualifying, n_drawn, n_splat, n_pixels} or None.  Asynchronous on the context's stream; returns
         {"disp16", "intensity", "counts", "workspace", "width", "height"}: the pointers the outputs are behind once the stream
         reaches this point."""
-        if (w2c12 is None) == (pose7 is None):
-            raise ValueError("VoxelMap.render: give exactly one of w2c12 and pose7")
         prm = _render_params(params, min_count, max_radius)
-        if w2c12 is not None:
-            m = _f64(w2c12).reshape(12)
-            self.ctx._chk(self.L.svo_voxel_map_render_dev(self.h, int(width), int(height), C.byref(cam), _p(m), C.byref(prm), workspace_ptr,
-                                                          disp_ptr, intensity_ptr, counts_ptr), "svo_voxel_map_render_dev")
-        else:
-            q = _f64(pose7).reshape(7)
-            self.ctx._chk(self.L.svo_voxel_map_render_pose7_dev(self.h, int(width), int(height), C.byref(cam), _p(q), C.byref(prm),
-                                                                workspace_ptr, disp_ptr, intensity_ptr, counts_ptr),
-                          "svo_voxel_map_render_pose7_dev")
+        self._by_pose("render", "w2c12", w2c12, pose7, "render", (int(width), int(height), C.byref(cam)),
+                      (C.byref(prm), workspace_ptr, disp_ptr, intensity_ptr, counts_ptr))
         return {"disp16": disp_ptr, "intensity": intensity_ptr, "counts": counts_ptr, "workspace": workspace_ptr,
                 "width": int(width), "height": int(height)}
 
     def render_host(self, width, height, cam, w2c12=None, pose7=None, params=None, min_count=None, max_radius=None):
         """svo_voxel_map_render: synchronous.  Returns (disp16 (height, width) int16 with FILTERED = -16 where nothing is seen,
         intensity (height, width) uint8, {"n_qualifying", "n_drawn", "n_splat", "n_pixels"})."""
-        if (w2c12 is None) == (pose7 is None):
-            raise ValueError("VoxelMap.render_host: give exactly one of w2c12 and pose7")
-        m = _f64(pose7_to_world_to_cam(pose7) if w2c12 is None else w2c12).reshape(12)
         prm = _render_params(params, min_count, max_radius)
         d = np.empty((max(int(height), 1), max(int(width), 1)), np.int16)
         g = np.empty(d.shape, np.uint8)
         c = np.zeros(4, np.uint64)
-        self.ctx._chk(self.L.svo_voxel_map_render(self.h, int(width), int(height), C.byref(cam), _p(m), C.byref(prm), _p(d), _p(g), _p(c)),
-                      "svo_voxel_map_render")
+        self._by_pose("render_host", "w2c12", w2c12, pose7, "render", (int(width), int(height), C.byref(cam)), (C.byref(prm), _p(d), _p(g), _p(c)),
+                      pose7_to_world_to_cam)
         return d, g, {"n_qualifying": int(c[0]), "n_drawn": int(c[1]), "n_splat": int(c[2]), "n_pixels": int(c[3])}
 
     def render_set_mode(self, cooperative=True, precheck=False):

@@ -46,14 +46,19 @@
 // by a LATER launch on the same stream (extraction, carve, copy, download).  A full table costs at most 64 probes per run head:
 // bounded work, no spinning; the removal's CAS loops retry only when another head's subtraction got in first, and every head
 // subtracts a bounded number of times.
+//
+// Written once: vx_record, vx_merge (insert, removal), vx_probe, vx_add (insert, copy), vx_walk_first (the table walks), vx_mean
+// (extraction, carve, splat), vx_to_camera, vx_pixel (carve, splat), vx_wave_sum, vx_tally (every count but the copy's).  The host
+// logic that needs no GPU (argument checks, pose7 -> matrix, the box, launch geometry) is host/voxel_args.h.
 #include "kernels.h"
 #include "tail_device.h"
+#include "voxel_args.h"
 #include "voxel_ledger.h"
 
 namespace {
 typedef unsigned long long u64;
-constexpr int VX_T = 256;
-constexpr int VX_ITEMS = 8;  // slots per thread of the extraction
+constexpr int VX_T = VOXEL_THREADS;
+constexpr int VX_ITEMS = VOXEL_WALK_ITEMS;  // slots per thread of a launch that walks the table
 constexpr u64 VX_EMPTY = ~0ull;
 constexpr double VX_LIMIT = 1048576.0;  // 2^20 voxels either side of the origin per axis
 
@@ -71,12 +76,7 @@ struct VoxelInsertArgs {
   VoxelTable t;
 };
 
-struct VoxelRemoveArgs {
-  const svo_cloud_point* pts;
-  int n;
-  double m[12];
-  float voxel_size, max_depth;
-  VoxelTable t;
+struct VoxelRemoveArgs : VoxelInsertArgs {
   u64* counts;  // {n_removed, n_rejected, n_missing, n_short}, zeroed on the stream before the launch; or null
 };
 
@@ -166,92 +166,36 @@ struct svo_voxel_map {
   int render_coop = 1, render_pre = 0;  // svo_voxel_render_set_mode; the defaults are the measured choice
 };
 
-__global__ __launch_bounds__(VX_T) void voxel_insert_kernel(VoxelInsertArgs a) {
-  __shared__ unsigned sC[4][VX_T / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const size_t i = (size_t)blockIdx.x * VX_T + (size_t)tid;
-  const bool valid = i < (size_t)a.n;
-  u64 key = VX_EMPTY;
-  unsigned ci = 0, fx = 0, fy = 0, fz = 0;  // ci of one record: count << 16 | intensity (a run of 64 sums to < 2^23 | 2^14)
-  if (valid) {
-    const svo_cloud_point p = a.pts[i];  // one 16-byte load (global memory takes it at 4-byte alignment)
-    const float x = p.x, y = p.y, z = p.z;
-    const unsigned tag = p.tag;
-    if (z > 0.0f && !(a.max_depth > 0.0f && z > a.max_depth)) {
-      const double xd = (double)x, yd = (double)y, zd = (double)z, vs = (double)a.voxel_size;
-      double q[3];
-      bool in = true;
+// The counts of a launch.  vx_wave_sum: per-thread tallies -> their sums over the wavefront, in every lane.  vx_tally: a wavefront's
+// totals -> LDS -> one atomicAdd per non-zero total of the workgroup, total k to dst[k].
+template <int N, typename T>
+__device__ __forceinline__ void vx_wave_sum(T (&n)[N]) {
+  for (int o = 32; o > 0; o >>= 1) {
 #pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        const double w = a.m[4 * r] * xd + a.m[4 * r + 1] * yd + a.m[4 * r + 2] * zd + a.m[4 * r + 3];
-        q[r] = w / vs;
-        in = in && q[r] >= -VX_LIMIT && q[r] < VX_LIMIT;
-      }
-      if (in) {
-        u64 k[3];
-        unsigned f[3];
+    for (int k = 0; k < N; ++k) n[k] += __shfl_xor(n[k], o);
+  }
+}
+template <int N, typename T>
+__device__ __forceinline__ void vx_tally(const T (&n)[N], u64* dst) {
+  __shared__ T sC[N][VX_T / 64];
+  const int tid = threadIdx.x;
+  if ((tid & 63) == 0) {
 #pragma unroll
-        for (int r = 0; r < 3; ++r) {
-          const double fl = floor(q[r]);
-          k[r] = (u64)((long long)fl + (1ll << 20));
-          const u64 fr = (u64)floor((q[r] - fl) * 65536.0);
-          f[r] = (unsigned)(fr < 65535ull ? fr : 65535ull);
-        }
-        key = k[0] | (k[1] << 21) | (k[2] << 42);
-        ci = (1u << 16) | (tag >> 24);
-        fx = f[0]; fy = f[1]; fz = f[2];
-      }
-    }
-  }
-  // run heads: lane 0, or a key other than the lane before's (rejected records carry EMPTY: they form runs too and never probe)
-  const u64 prev = __shfl_up(key, 1);
-  const bool head = lane == 0 || prev != key;
-  const u64 heads = __ballot(head);
-  // segmented sum: after the round with offset o a lane holds the sum over [lane, min(lane + 2 o, end of its run)); the rounds
-  // stop (wavefront-uniformly) once no lane has a partner inside its run, which is at once when nothing merges
-  const u64 after = lane == 63 ? 0ull : heads >> (lane + 1);
-  const int end = after ? lane + 1 + __builtin_ctzll(after) : 64;
-  for (int o = 1; o < 64; o <<= 1) {
-    const bool take = lane + o < end;
-    if (!__ballot(take)) break;
-    const unsigned c = __shfl_down(ci, o), sx = __shfl_down(fx, o), sy = __shfl_down(fy, o), sz = __shfl_down(fz, o);
-    if (take) { ci += c; fx += sx; fy += sy; fz += sz; }
-  }
-  bool claimed = false, dropped = false;
-  if (head && key != VX_EMPTY) {
-    u64 h;
-    const int got = vx_probe(a.t, key, h);
-    claimed = got == 2;
-    if (got) vx_add(a.t, h, ((u64)(ci >> 16) << 40) | (u64)(ci & 0xFFFFu), (u64)fx, (u64)fy, (u64)fz);
-    else dropped = true;
-  }
-  // counters, in points: ballots only, except for the dropped points, which exist only once the table overflows
-  const unsigned n_valid = (unsigned)__popcll(__ballot(valid));
-  const unsigned n_rej = (unsigned)__popcll(__ballot(valid && key == VX_EMPTY));
-  const unsigned n_claim = (unsigned)__popcll(__ballot(claimed));
-  unsigned n_drop = 0;
-  if (__ballot(dropped)) {
-    n_drop = dropped ? ci >> 16 : 0u;
-    for (int o = 32; o > 0; o >>= 1) n_drop += __shfl_xor(n_drop, o);
-  }
-  if (lane == 0) {
-    sC[0][wave] = n_claim; sC[1][wave] = n_valid - n_rej - n_drop; sC[2][wave] = n_rej; sC[3][wave] = n_drop;
+    for (int k = 0; k < N; ++k) sC[k][tid >> 6] = n[k];
   }
   __syncthreads();
-  if (tid < 4) {
-    unsigned t = 0;
+  if (tid < N) {
+    T t = 0;
     for (int w = 0; w < VX_T / 64; ++w) t += sC[tid][w];
-    if (t) __hip_atomic_fetch_add(&a.t.counters[tid], (u64)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t) __hip_atomic_fetch_add(&dst[tid], (u64)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
-// The removal.  Its front half (items 1-3 of the contract: reject, transform, key and fractions) and its wavefront merge
-// are the insert's, statement for statement, written a second time: as functions shared with voxel_insert_kernel they changed that
-// kernel's code (34 -> 50 SGPRs, another branch structure), and the insert keeps its code.  A rejected (or absent) record leaves
-// key = EMPTY and a zero contribution.
-__device__ __forceinline__ void vx_record(const VoxelRemoveArgs& a, size_t i, bool valid, u64& key, unsigned& ci, unsigned& fx, unsigned& fy, unsigned& fz) {
+// The front half of the insert and of the removal (items 1-3 of the contract: reject, transform, key and fractions).  A rejected (or
+// absent) record leaves key = EMPTY and a zero contribution.
+__device__ __forceinline__ void vx_record(const VoxelInsertArgs& a, size_t i, bool valid, u64& key, unsigned& ci, unsigned& fx, unsigned& fy, unsigned& fz) {
   key = VX_EMPTY;
-  ci = 0; fx = 0; fy = 0; fz = 0;
+  ci = 0; fx = 0; fy = 0; fz = 0;  // ci of one record: count << 16 | intensity (a run of 64 sums to < 2^23 | 2^14)
   if (valid) {
     const svo_cloud_point p = a.pts[i];  // one 16-byte load (global memory takes it at 4-byte alignment)
     const float x = p.x, y = p.y, z = p.z;
@@ -304,6 +248,35 @@ __device__ __forceinline__ bool vx_merge(int lane, u64 key, unsigned& ci, unsign
   return head;
 }
 
+__global__ __launch_bounds__(VX_T) void voxel_insert_kernel(VoxelInsertArgs a) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const size_t i = (size_t)blockIdx.x * VX_T + (size_t)tid;
+  const bool valid = i < (size_t)a.n;
+  u64 key;
+  unsigned ci, fx, fy, fz;
+  vx_record(a, i, valid, key, ci, fx, fy, fz);
+  const bool head = vx_merge(lane, key, ci, fx, fy, fz);
+  bool claimed = false, dropped = false;
+  if (head && key != VX_EMPTY) {
+    u64 h;
+    const int got = vx_probe(a.t, key, h);
+    claimed = got == 2;
+    if (got) vx_add(a.t, h, ((u64)(ci >> 16) << 40) | (u64)(ci & 0xFFFFu), (u64)fx, (u64)fy, (u64)fz);
+    else dropped = true;
+  }
+  // counters, in points: ballots only, except for the dropped points, which exist only once the table overflows
+  const unsigned n_valid = (unsigned)__popcll(__ballot(valid));
+  const unsigned n_rej = (unsigned)__popcll(__ballot(valid && key == VX_EMPTY));
+  const unsigned n_claim = (unsigned)__popcll(__ballot(claimed));
+  unsigned n_drop = 0;
+  if (__ballot(dropped)) {
+    n_drop = dropped ? ci >> 16 : 0u;
+    for (int o = 32; o > 0; o >>= 1) n_drop += __shfl_xor(n_drop, o);
+  }
+  const unsigned n[4] = {n_claim, n_valid - n_rej - n_drop, n_rej, n_drop};
+  vx_tally(n, a.t.counters);
+}
+
 // The removal's find (item 2 of "Voxel map removal"): the insert's walk with a load in place of the CAS.  A removal writes no key, and
 // every key it reads was written by an earlier launch on the same stream, so here a load may decide.
 __device__ __forceinline__ bool vx_find(const VoxelTable& t, u64 key, u64& h) {
@@ -329,8 +302,7 @@ __device__ __forceinline__ void vx_sub_sat(u64* p, u64 v) {
 }
 
 __global__ __launch_bounds__(VX_T) void voxel_remove_kernel(VoxelRemoveArgs a) {
-  __shared__ unsigned sC[4][VX_T / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const size_t i = (size_t)blockIdx.x * VX_T + (size_t)tid;
   const bool valid = i < (size_t)a.n;
   u64 key;
@@ -377,22 +349,32 @@ __global__ __launch_bounds__(VX_T) void voxel_remove_kernel(VoxelRemoveArgs a) {
   if (__ballot(n_short != 0u)) {
     for (int o = 32; o > 0; o >>= 1) n_short += __shfl_xor(n_short, o);
   }
-  if (lane == 0) {
-    sC[0][wave] = n_valid - n_rej - n_miss; sC[1][wave] = n_rej; sC[2][wave] = n_miss; sC[3][wave] = n_short;
-  }
-  __syncthreads();
-  if (tid < 4) {
-    unsigned t = 0;
-    for (int w = 0; w < VX_T / 64; ++w) t += sC[tid][w];
-    if (t) __hip_atomic_fetch_add(&a.counts[tid], (u64)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  const unsigned n[4] = {n_valid - n_rej - n_miss, n_rej, n_miss, n_short};
+  vx_tally(n, a.counts);
 }
+
+// The first slot of this thread in a launch that walks the table: VX_ITEMS slots per thread, VX_T apart.
+__device__ __forceinline__ size_t vx_walk_first() { return (size_t)blockIdx.x * (VX_T * VX_ITEMS) + (size_t)threadIdx.x; }
+
+// Axis r of a voxel's mean point in map units: its key's index plus the mean fraction, times the voxel size.
+__device__ __forceinline__ double vx_mean(u64 key, int r, u64 sum, u64 count, double vs) {
+  const double k = (double)((long long)((key >> (21 * r)) & 0x1FFFFFull) - (1ll << 20));
+  return (k + (double)sum / ((double)count * 65536.0)) * vs;
+}
+
+// q = [R | t] p with the launch's 3 x 4 world->camera matrix, and a pixel coordinate of q rounded to the nearest (as a double:
+// the caller's range test is what NaN and infinity fail).
+template <typename Args>
+__device__ __forceinline__ double vx_to_camera(const Args& a, int r, const double (&p)[3]) {
+  return a.m[4 * r] * p[0] + a.m[4 * r + 1] * p[1] + a.m[4 * r + 2] * p[2] + a.m[4 * r + 3];
+}
+__device__ __forceinline__ double vx_pixel(double focal, double q, double qz, double centre) { return floor(focal * q / qz + centre + 0.5); }
 
 __global__ __launch_bounds__(VX_T) void voxel_extract_kernel(VoxelExtractArgs a) {
   __shared__ int sW[VX_T / 64];
   __shared__ int sBase;
   const size_t cap = (size_t)a.t.mask + 1;
-  const size_t first = (size_t)blockIdx.x * (VX_T * VX_ITEMS) + (size_t)threadIdx.x;
+  const size_t first = vx_walk_first();
   int slot[VX_ITEMS];
   u64 ci[VX_ITEMS];
   int total = 0;
@@ -424,14 +406,10 @@ __global__ __launch_bounds__(VX_T) void voxel_extract_kernel(VoxelExtractArgs a)
     const size_t s = first + (size_t)j * VX_T;
     const u64 key = a.t.keys[s];
     const u64 count = ci[j] >> 40, isum = ci[j] & ((1ull << 40) - 1ull);
-    const double c = (double)count * 65536.0;
     const u64 sum[3] = {a.t.sx[s], a.t.sy[s], a.t.sz[s]};
     float xyz[3];
 #pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      const double k = (double)((long long)((key >> (21 * r)) & 0x1FFFFFull) - (1ll << 20));
-      xyz[r] = (float)((k + (double)sum[r] / c) * vs);
-    }
+    for (int r = 0; r < 3; ++r) xyz[r] = (float)vx_mean(key, r, sum[r], count, vs);
     svo_cloud_point q;
     q.x = xyz[0]; q.y = xyz[1]; q.z = xyz[2];
     q.tag = (uint32_t)count | ((uint32_t)(isum / count) << 24);
@@ -440,9 +418,8 @@ __global__ __launch_bounds__(VX_T) void voxel_extract_kernel(VoxelExtractArgs a)
 }
 
 __global__ __launch_bounds__(VX_T) void voxel_carve_kernel(VoxelCarveArgs a) {
-  __shared__ unsigned sC[3][VX_T / 64];
   const size_t cap = (size_t)a.t.mask + 1;
-  const size_t first = (size_t)blockIdx.x * (VX_T * VX_ITEMS) + (size_t)threadIdx.x;
+  const size_t first = vx_walk_first();
   const double vs = (double)a.voxel_size;
   const double xlo = (double)a.radius, xhi = (double)(a.width - 1 - a.radius), yhi = (double)(a.height - 1 - a.radius);
   unsigned n_live = 0, n_tested = 0, n_carved = 0;
@@ -455,18 +432,14 @@ __global__ __launch_bounds__(VX_T) void voxel_carve_kernel(VoxelCarveArgs a) {
     const u64 count = a.t.ci[s] >> 40;
     if (count == 0) continue;
     ++n_live;
-    const double c = (double)count * 65536.0;
     const u64 sum[3] = {a.t.sx[s], a.t.sy[s], a.t.sz[s]};
     double p[3], q[3];
 #pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      const double k = (double)((long long)((key >> (21 * r)) & 0x1FFFFFull) - (1ll << 20));
-      p[r] = (k + (double)sum[r] / c) * vs;
-    }
+    for (int r = 0; r < 3; ++r) p[r] = vx_mean(key, r, sum[r], count, vs);
 #pragma unroll
-    for (int r = 0; r < 3; ++r) q[r] = a.m[4 * r] * p[0] + a.m[4 * r + 1] * p[1] + a.m[4 * r + 2] * p[2] + a.m[4 * r + 3];
+    for (int r = 0; r < 3; ++r) q[r] = vx_to_camera(a, r, p);
     if (!(q[2] > 0.0)) continue;
-    const double fpx = floor(a.focal * q[0] / q[2] + a.cx + 0.5), fpy = floor(a.focal * q[1] / q[2] + a.cy + 0.5);
+    const double fpx = vx_pixel(a.focal, q[0], q[2], a.cx), fpy = vx_pixel(a.focal, q[1], q[2], a.cy);
     if (!(fpx >= xlo && fpx <= xhi && fpy >= xlo && fpy <= yhi)) continue;  // NaN and infinity fail
     ++n_tested;
     const int px = (int)fpx, py = (int)fpy;  // inside the map with the whole window, by the test above
@@ -488,23 +461,14 @@ __global__ __launch_bounds__(VX_T) void voxel_carve_kernel(VoxelCarveArgs a) {
     ++n_carved;
   }
   if (!a.counts) return;  // uniform over the launch
-  for (int o = 32; o > 0; o >>= 1) {
-    n_live += __shfl_xor(n_live, o); n_tested += __shfl_xor(n_tested, o); n_carved += __shfl_xor(n_carved, o);
-  }
-  const int tid = threadIdx.x;
-  if ((tid & 63) == 0) { sC[0][tid >> 6] = n_live; sC[1][tid >> 6] = n_tested; sC[2][tid >> 6] = n_carved; }
-  __syncthreads();
-  if (tid < 3) {
-    unsigned t = 0;
-    for (int w = 0; w < VX_T / 64; ++w) t += sC[tid][w];
-    if (t) __hip_atomic_fetch_add(&a.counts[tid], (u64)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  unsigned n[3] = {n_live, n_tested, n_carved};
+  vx_wave_sum(n);
+  vx_tally(n, a.counts);
 }
 
 __global__ __launch_bounds__(VX_T) void voxel_copy_kernel(VoxelCopyArgs a) {
-  __shared__ u64 sC[3][VX_T / 64];
   const size_t cap = (size_t)a.src.mask + 1;
-  const size_t first = (size_t)blockIdx.x * (VX_T * VX_ITEMS) + (size_t)threadIdx.x;
+  const size_t first = vx_walk_first();
   u64 n_claim = 0, n_moved = 0, n_drop = 0;  // a slot's count is below 2^24, a workgroup's 2,048 slots sum past 32 bits
 #pragma unroll
   for (int j = 0; j < VX_ITEMS; ++j) {
@@ -533,6 +497,9 @@ __global__ __launch_bounds__(VX_T) void voxel_copy_kernel(VoxelCopyArgs a) {
       n_drop += count;
     }
   }
+  // vx_wave_sum and vx_tally written out, in u64: through them this kernel's three runs were slower than all five of the parent's
+  // on one map (73.1, 70.4, 70.1 us against 69.0 .. 69.8) and above their middle on two more (profiles/voxel_written_once.txt).
+  __shared__ u64 sC[3][VX_T / 64];
   for (int o = 32; o > 0; o >>= 1) {
     n_claim += __shfl_xor(n_claim, o); n_moved += __shfl_xor(n_moved, o); n_drop += __shfl_xor(n_drop, o);
   }
@@ -541,8 +508,7 @@ __global__ __launch_bounds__(VX_T) void voxel_copy_kernel(VoxelCopyArgs a) {
   __syncthreads();
   if (tid < 3) {
     u64 t = 0;
-    for (int w = 0; w < VX_T / 64; ++w) t += sC[tid][w];
-    // counters: n_voxels, n_inserted, (n_rejected), n_dropped
+    for (int w = 0; w < VX_T / 64; ++w) t += sC[tid][w];  // counters: n_voxels, n_inserted, (n_rejected), n_dropped
     if (t) __hip_atomic_fetch_add(&a.dst.counters[tid == 2 ? 3 : tid], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
@@ -556,9 +522,8 @@ __device__ __forceinline__ void vx_splat_max(unsigned* p, unsigned v) {
 
 template <bool PRE, bool COOP>
 __global__ __launch_bounds__(VX_T) void voxel_splat_kernel(VoxelSplatArgs a) {
-  __shared__ unsigned sC[3][VX_T / 64];
   const size_t cap = (size_t)a.t.mask + 1;
-  const size_t first = (size_t)blockIdx.x * (VX_T * VX_ITEMS) + (size_t)threadIdx.x;
+  const size_t first = vx_walk_first();
   const int lane = threadIdx.x & 63;
   const double vs = (double)a.voxel_size, rmax = (double)a.max_radius;
   const double xhi = (double)(a.width - 1), yhi = (double)(a.height - 1);
@@ -574,18 +539,14 @@ __global__ __launch_bounds__(VX_T) void voxel_splat_kernel(VoxelSplatArgs a) {
         const u64 ci = a.t.ci[s], count = ci >> 40;
         if (count >= (u64)a.min_count) {
           ++n_qual;
-          const double c = (double)count * 65536.0;
           const u64 sum[3] = {a.t.sx[s], a.t.sy[s], a.t.sz[s]};
           double p[3], q[3];
 #pragma unroll
-          for (int k3 = 0; k3 < 3; ++k3) {
-            const double k = (double)((long long)((key >> (21 * k3)) & 0x1FFFFFull) - (1ll << 20));
-            p[k3] = (k + (double)sum[k3] / c) * vs;
-          }
+          for (int k3 = 0; k3 < 3; ++k3) p[k3] = vx_mean(key, k3, sum[k3], count, vs);
 #pragma unroll
-          for (int k3 = 0; k3 < 3; ++k3) q[k3] = a.m[4 * k3] * p[0] + a.m[4 * k3 + 1] * p[1] + a.m[4 * k3 + 2] * p[2] + a.m[4 * k3 + 3];
+          for (int k3 = 0; k3 < 3; ++k3) q[k3] = vx_to_camera(a, k3, p);
           if (q[2] > 0.0) {
-            const double fpx = floor(a.focal * q[0] / q[2] + a.cx + 0.5), fpy = floor(a.focal * q[1] / q[2] + a.cy + 0.5);
+            const double fpx = vx_pixel(a.focal, q[0], q[2], a.cx), fpy = vx_pixel(a.focal, q[1], q[2], a.cy);
             const double d16 = floor(a.focal * a.baseline / q[2] * 16.0 + 0.5);
             const double h = floor(a.focal * vs / q[2] * 0.5 + 0.5);
             const double fr = h < rmax ? h : rmax;
@@ -629,21 +590,12 @@ __global__ __launch_bounds__(VX_T) void voxel_splat_kernel(VoxelSplatArgs a) {
     }
   }
   if (!a.counts) return;  // uniform over the launch
-  for (int o = 32; o > 0; o >>= 1) {
-    n_qual += __shfl_xor(n_qual, o); n_drawn += __shfl_xor(n_drawn, o); n_splat += __shfl_xor(n_splat, o);
-  }
-  const int tid = threadIdx.x;
-  if ((tid & 63) == 0) { sC[0][tid >> 6] = n_qual; sC[1][tid >> 6] = n_drawn; sC[2][tid >> 6] = n_splat; }
-  __syncthreads();
-  if (tid < 3) {
-    unsigned t = 0;
-    for (int w = 0; w < VX_T / 64; ++w) t += sC[tid][w];
-    if (t) __hip_atomic_fetch_add(&a.counts[tid], (u64)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  unsigned n[3] = {n_qual, n_drawn, n_splat};
+  vx_wave_sum(n);
+  vx_tally(n, a.counts);
 }
 
 __global__ __launch_bounds__(VX_T) void voxel_resolve_kernel(VoxelResolveArgs a) {
-  __shared__ unsigned sC[VX_T / 64];
   const size_t i0 = ((size_t)blockIdx.x * VX_T + (size_t)threadIdx.x) * 4;
   const int here = i0 < a.n ? (int)(a.n - i0 < 4 ? a.n - i0 : 4) : 0;
   unsigned covered = 0;  // one bit per pixel
@@ -668,52 +620,57 @@ __global__ __launch_bounds__(VX_T) void voxel_resolve_kernel(VoxelResolveArgs a)
     }
   }
   if (!a.counts) return;  // uniform over the launch
-  unsigned n = (unsigned)__popc(covered);
-  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
-  const int tid = threadIdx.x;
-  if ((tid & 63) == 0) sC[tid >> 6] = n;
-  __syncthreads();
-  if (tid == 0) {
-    unsigned t = 0;
-    for (int w = 0; w < VX_T / 64; ++w) t += sC[w];
-    if (t) __hip_atomic_fetch_add(&a.counts[3], (u64)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  unsigned n[1] = {(unsigned)__popc(covered)};
+  vx_wave_sum(n);
+  vx_tally(n, a.counts + 3);  // n_pixels
 }
 
 // ----------------------------------------------------------------------------- host side
-static bool voxel_params_ok(const svo_voxel_map_params* p) {
-  return p && p->voxel_size > 0.0f && p->voxel_size <= 3.4028234663852886e38f &&  // finite and > 0 (a NaN fails the first test)
-         p->capacity_log2 >= 8 && p->capacity_log2 <= 28;
+// A refusal of host/voxel_args.h goes into the context: `call` is one of its checks with `&err` as its last argument.
+#define VOXEL_CHECK(ctx, call) do { const char* err = nullptr; if (call) { (ctx)->err = err; return SVO_ERR_INVALID; } } while (0)
+
+// A temporary device allocation of a synchronous entry, freed when the entry returns.
+struct VoxelTemp { void* p; ~VoxelTemp() { if (p) (void)hipFree(p); } };
+
+// What every synchronous entry does around its _dev entry: `dev` runs it (unless the copy in before it failed), `back` queues
+// the copies back to the host; the stream is drained before the caller's temporary buffer goes away, whatever failed; the _dev
+// entry's refusal is reported first (its message stands), a HIP error second.
+template <typename Dev, typename Back>
+static int voxel_sync(svo_ctx* ctx, const char* what, hipError_t e, Dev dev, Back back) {
+  const int rc = e == hipSuccess ? dev() : SVO_OK;
+  if (e == hipSuccess && !rc) e = back();
+  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+  if (rc) return rc;
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) { ctx->err = std::string(what) + ": " + hipGetErrorString(e); return SVO_ERR_HIP; }
+  return SVO_OK;
+}
+
+// The head of every pose7 entry: null refused under the entry's own name, then the matrix its matrix form takes.
+static int voxel_pose7(svo_voxel_map* m, const double* pose7, void (*to_matrix)(const double*, double*), double* m12, const char* null_text) {
+  if (!m) return SVO_ERR_INVALID;
+  SVO_REQUIRE(m->ctx, pose7, null_text);
+  to_matrix(pose7, m12);
+  return SVO_OK;
 }
 
 extern "C" int svo_voxel_map_default_params(svo_voxel_map_params* params) {
   if (!params) return SVO_ERR_INVALID;
-  params->voxel_size = 0.1f;
-  params->capacity_log2 = 22;
-  params->max_depth = 0.0f;
+  params->voxel_size = 0.1f; params->capacity_log2 = 22; params->max_depth = 0.0f;
   return SVO_OK;
 }
 
-extern "C" int svo_voxel_map_bytes(const svo_voxel_map_params* params, size_t* bytes) {
-  if (!bytes) return SVO_ERR_INVALID;
-  *bytes = 0;
-  if (!voxel_params_ok(params)) return SVO_ERR_INVALID;
-  *bytes = (size_t)40 << params->capacity_log2;
-  return SVO_OK;
-}
+extern "C" int svo_voxel_map_bytes(const svo_voxel_map_params* params, size_t* bytes) { return voxel_table_bytes(params, bytes); }
 
 extern "C" int svo_pose7_to_cam_to_world(const double* pose7, double* m12) {
   if (!pose7 || !m12) return SVO_ERR_INVALID;
-  const double w = pose7[0], x = pose7[1], y = pose7[2], z = pose7[3];
-  const double s = 2.0 / (w * w + x * x + y * y + z * z);
-  const double R[9] = {1.0 - s * (y * y + z * z), s * (x * y - w * z), s * (x * z + w * y),
-                       s * (x * y + w * z), 1.0 - s * (x * x + z * z), s * (y * z - w * x),
-                       s * (x * z - w * y), s * (y * z + w * x), 1.0 - s * (x * x + y * y)};
-  const double* t = pose7 + 4;
-  for (int r = 0; r < 3; ++r) {  // [R^T | -R^T t]
-    for (int c = 0; c < 3; ++c) m12[4 * r + c] = R[3 * c + r];
-    m12[4 * r + 3] = -(R[r] * t[0] + R[3 + r] * t[1] + R[6 + r] * t[2]);
-  }
+  voxel_pose7_to_cam_to_world(pose7, m12);
+  return SVO_OK;
+}
+
+extern "C" int svo_pose7_to_world_to_cam(const double* pose7, double* m12) {
+  if (!pose7 || !m12) return SVO_ERR_INVALID;
+  voxel_pose7_to_world_to_cam(pose7, m12);
   return SVO_OK;
 }
 
@@ -729,14 +686,12 @@ extern "C" int svo_voxel_map_create(svo_ctx* ctx, const svo_voxel_map_params* pa
   svo_use_device(ctx);
   SVO_REQUIRE(ctx, out, "voxel_map_create: null out");
   *out = nullptr;
-  SVO_REQUIRE(ctx, params, "voxel_map_create: null params");
-  SVO_REQUIRE(ctx, params->voxel_size > 0.0f && params->voxel_size <= 3.4028234663852886e38f, "voxel_map_create: voxel_size must be finite and > 0");
-  SVO_REQUIRE(ctx, params->capacity_log2 >= 8 && params->capacity_log2 <= 28, "voxel_map_create: capacity_log2 outside 8..28");
+  VOXEL_CHECK(ctx, voxel_params_check(params, &err));
   svo_voxel_map* m = new svo_voxel_map();
   m->ctx = ctx;
   m->prm = *params;
   m->cap = (size_t)1 << params->capacity_log2;
-  const hipError_t e = hipMalloc((void**)&m->d_mem, 40 * m->cap + 4 * sizeof(u64) + 2 * sizeof(int));
+  const hipError_t e = hipMalloc((void**)&m->d_mem, VOXEL_SLOT_BYTES * m->cap + 4 * sizeof(u64) + 2 * sizeof(int));
   if (e != hipSuccess) {
     ctx->err = std::string("voxel_map_create: hipMalloc of the table: ") + hipGetErrorString(e);
     delete m;
@@ -767,26 +722,13 @@ extern "C" int svo_voxel_map_clear(svo_voxel_map* m) {
   return voxel_clear(m);
 }
 
-// The arguments every entry that takes a cloud shares (insert, removal, move): `what` opens the message.
-static int voxel_cloud_check(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* m12, const char* what, const char* m12_name) {
-  svo_ctx* ctx = m->ctx;
-  if (n < 0) { ctx->err = std::string(what) + ": n must not be negative"; return SVO_ERR_INVALID; }
-  if (!m12) { ctx->err = std::string(what) + ": null " + m12_name; return SVO_ERR_INVALID; }
-  if (n == 0) return SVO_OK;
-  if (!points) { ctx->err = std::string(what) + ": null points"; return SVO_ERR_INVALID; }
-  if (((uintptr_t)points & 3u) != 0) { ctx->err = std::string(what) + ": points must be 4-byte aligned"; return SVO_ERR_INVALID; }
-  return SVO_OK;
-}
-
 static int voxel_insert_launch(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* m12) {
   svo_ctx* ctx = m->ctx;
   VoxelInsertArgs a{};
-  a.pts = points; a.n = n;
+  a.pts = points; a.n = n; a.t = m->t;
   memcpy(a.m, m12, sizeof(a.m));
   a.voxel_size = m->prm.voxel_size; a.max_depth = m->prm.max_depth;
-  a.t = m->t;
-  const unsigned blocks = (unsigned)(((size_t)n + VX_T - 1) / VX_T);
-  hipLaunchKernelGGL(voxel_insert_kernel, dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
+  hipLaunchKernelGGL(voxel_insert_kernel, dim3((unsigned)voxel_record_groups(n)), dim3(VX_T), 0, ctx->stream, a);
   SVO_HIP_CHECK(ctx, hipGetLastError());
   return SVO_OK;
 }
@@ -795,18 +737,16 @@ extern "C" int svo_voxel_map_insert_dev(svo_voxel_map* m, const svo_cloud_point*
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = m->ctx;
   svo_use_device(ctx);
-  const int rc = voxel_cloud_check(m, points, n, m12, "voxel_map_insert", "m12");
-  if (rc || n == 0) return rc;
+  VOXEL_CHECK(ctx, voxel_cloud_check(points, n, m12, VOXEL_INSERT_TEXTS, &err));
+  if (n == 0) return SVO_OK;
   SvoProfScope prof(ctx, SVO_PROF_VOXEL_INSERT);
   return voxel_insert_launch(m, points, n, m12);
 }
 
 extern "C" int svo_voxel_map_insert_pose7_dev(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* pose7) {
-  if (!m) return SVO_ERR_INVALID;
-  SVO_REQUIRE(m->ctx, pose7, "voxel_map_insert_pose7: null pose7");
   double m12[12];
-  svo_pose7_to_cam_to_world(pose7, m12);
-  return svo_voxel_map_insert_dev(m, points, n, m12);
+  const int rc = voxel_pose7(m, pose7, voxel_pose7_to_cam_to_world, m12, "voxel_map_insert_pose7: null pose7");
+  return rc ? rc : svo_voxel_map_insert_dev(m, points, n, m12);
 }
 
 extern "C" int svo_voxel_map_stats(svo_voxel_map* m, svo_voxel_map_stats_t* stats) {
@@ -834,10 +774,9 @@ extern "C" int svo_voxel_map_extract_dev(svo_voxel_map* m, int min_count, svo_cl
   a.min_count = (unsigned)min_count;
   a.voxel_size = m->prm.voxel_size;
   a.out = points; a.max_points = max_points; a.counts = counts;
-  const unsigned blocks = (unsigned)((m->cap + (size_t)VX_T * VX_ITEMS - 1) / ((size_t)VX_T * VX_ITEMS));
   SvoProfScope prof(ctx, SVO_PROF_VOXEL_EXTRACT);
   SVO_HIP_CHECK(ctx, hipMemsetAsync(counts, 0, 2 * sizeof(int), ctx->stream));
-  hipLaunchKernelGGL(voxel_extract_kernel, dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
+  hipLaunchKernelGGL(voxel_extract_kernel, dim3((unsigned)voxel_walk_groups(m->cap)), dim3(VX_T), 0, ctx->stream, a);
   SVO_HIP_CHECK(ctx, hipGetLastError());
   return SVO_OK;
 }
@@ -853,18 +792,17 @@ extern "C" int svo_voxel_map_extract(svo_voxel_map* m, int min_count, svo_cloud_
   const size_t room = (size_t)capacity < m->cap ? (size_t)capacity : m->cap;  // no more than cap voxels exist
   svo_cloud_point* d = nullptr;
   if (room) SVO_HIP_CHECK(ctx, hipMalloc((void**)&d, room * sizeof(svo_cloud_point)));
+  VoxelTemp hold{d};
   int c[2] = {0, 0};
-  int rc = svo_voxel_map_extract_dev(m, min_count, d, (int)room, m->d_counts);
-  hipError_t e = hipSuccess;
-  if (!rc) e = hipMemcpyAsync(c, m->d_counts, sizeof(c), hipMemcpyDeviceToHost, ctx->stream);
-  if (!rc && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (!rc && e == hipSuccess && c[1] > 0) {
-    e = hipMemcpyAsync(points, d, sizeof(svo_cloud_point) * (size_t)c[1], hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  }
-  if (d) (void)hipFree(d);
+  const int rc = voxel_sync(
+      ctx, "voxel_map_extract", hipSuccess, [&] { return svo_voxel_map_extract_dev(m, min_count, d, (int)room, m->d_counts); },
+      [&] {  // the counts first: they say how many points there are to copy
+        hipError_t e = hipMemcpyAsync(c, m->d_counts, sizeof(c), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess && c[1] > 0) e = hipMemcpyAsync(points, d, sizeof(svo_cloud_point) * (size_t)c[1], hipMemcpyDeviceToHost, ctx->stream);
+        return e;
+      });
   if (rc) return rc;
-  if (e != hipSuccess) { ctx->err = std::string("voxel_map_extract: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
   *n_total = c[0]; *n_stored = c[1];
   return SVO_OK;
 }
@@ -874,8 +812,8 @@ extern "C" int svo_voxel_map_download(svo_voxel_map* m, void* host, size_t bytes
   svo_ctx* ctx = m->ctx;
   svo_use_device(ctx);
   SVO_REQUIRE(ctx, host, "voxel_map_download: null host buffer");
-  SVO_REQUIRE(ctx, bytes >= 40 * m->cap, "voxel_map_download: bytes is less than svo_voxel_map_bytes");
-  SVO_HIP_CHECK(ctx, hipMemcpyAsync(host, m->d_mem, 40 * m->cap, hipMemcpyDeviceToHost, ctx->stream));
+  SVO_REQUIRE(ctx, bytes >= VOXEL_SLOT_BYTES * m->cap, "voxel_map_download: bytes is less than svo_voxel_map_bytes");
+  SVO_HIP_CHECK(ctx, hipMemcpyAsync(host, m->d_mem, VOXEL_SLOT_BYTES * m->cap, hipMemcpyDeviceToHost, ctx->stream));
   SVO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return SVO_OK;
 }
@@ -883,39 +821,7 @@ extern "C" int svo_voxel_map_download(svo_voxel_map* m, void* host, size_t bytes
 // ----------------------------------------------------------------------------- carving and the copy of the live voxels
 extern "C" int svo_voxel_carve_default_params(svo_voxel_carve_params* params) {
   if (!params) return SVO_ERR_INVALID;
-  params->radius = 1;
-  params->margin16 = 8;
-  params->keep_count = 0;
-  return SVO_OK;
-}
-
-extern "C" int svo_pose7_to_world_to_cam(const double* pose7, double* m12) {
-  if (!pose7 || !m12) return SVO_ERR_INVALID;
-  const double w = pose7[0], x = pose7[1], y = pose7[2], z = pose7[3];
-  const double s = 2.0 / (w * w + x * x + y * y + z * z);
-  const double R[9] = {1.0 - s * (y * y + z * z), s * (x * y - w * z), s * (x * z + w * y),
-                       s * (x * y + w * z), 1.0 - s * (x * x + z * z), s * (y * z - w * x),
-                       s * (x * z - w * y), s * (y * z + w * x), 1.0 - s * (x * x + y * y)};
-  for (int r = 0; r < 3; ++r) {  // [R | t]
-    for (int c = 0; c < 3; ++c) m12[4 * r + c] = R[3 * r + c];
-    m12[4 * r + 3] = pose7[4 + r];
-  }
-  return SVO_OK;
-}
-
-static int voxel_carve_check(svo_voxel_map* m, const int16_t* disp16, int width, int height, const svo_camera_info* cam, const double* w2c12,
-                             const svo_voxel_carve_params* prm) {
-  svo_ctx* ctx = m->ctx;
-  SVO_REQUIRE(ctx, disp16, "voxel_map_carve: null disp16");
-  SVO_REQUIRE(ctx, cam, "voxel_map_carve: null cam");
-  SVO_REQUIRE(ctx, w2c12, "voxel_map_carve: null w2c12");
-  SVO_REQUIRE(ctx, prm, "voxel_map_carve: null params");
-  SVO_REQUIRE(ctx, prm->radius >= 0 && prm->radius <= 3, "voxel_map_carve: radius outside 0..3");
-  SVO_REQUIRE(ctx, prm->margin16 >= 0 && prm->margin16 <= 32767, "voxel_map_carve: margin16 outside 0..32767");
-  SVO_REQUIRE(ctx, prm->keep_count >= 0, "voxel_map_carve: keep_count must not be negative");
-  SVO_REQUIRE(ctx, width >= 2 * prm->radius + 1 && width <= ctx->lim.max_width, "voxel_map_carve: width below 2 radius + 1 or beyond the context's limit");
-  SVO_REQUIRE(ctx, height >= 2 * prm->radius + 1 && height <= ctx->lim.max_height, "voxel_map_carve: height below 2 radius + 1 or beyond the context's limit");
-  SVO_REQUIRE(ctx, cam->focal != 0.0 && cam->baseline != 0.0, "voxel_map_carve: focal and baseline must not be 0");
+  params->radius = 1; params->margin16 = 8; params->keep_count = 0;
   return SVO_OK;
 }
 
@@ -924,8 +830,7 @@ extern "C" int svo_voxel_map_carve_dev(svo_voxel_map* m, const int16_t* disp16, 
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = m->ctx;
   svo_use_device(ctx);
-  const int rc = voxel_carve_check(m, disp16, width, height, cam, w2c12, prm);
-  if (rc) return rc;
+  VOXEL_CHECK(ctx, voxel_carve_check(disp16, width, height, cam, w2c12, prm, ctx->lim.max_width, ctx->lim.max_height, &err));
   VoxelCarveArgs a{};
   a.t = m->t;
   a.disp = disp16; a.width = width; a.height = height;
@@ -934,21 +839,18 @@ extern "C" int svo_voxel_map_carve_dev(svo_voxel_map* m, const int16_t* disp16, 
   memcpy(a.m, w2c12, sizeof(a.m));
   a.focal = cam->focal; a.cx = cam->cx; a.cy = cam->cy; a.baseline = cam->baseline;
   a.counts = reinterpret_cast<u64*>(counts);
-  const unsigned blocks = (unsigned)((m->cap + (size_t)VX_T * VX_ITEMS - 1) / ((size_t)VX_T * VX_ITEMS));
   SvoProfScope prof(ctx, SVO_PROF_VOXEL_CARVE);
   if (counts) SVO_HIP_CHECK(ctx, hipMemsetAsync(counts, 0, 3 * sizeof(u64), ctx->stream));
-  hipLaunchKernelGGL(voxel_carve_kernel, dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
+  hipLaunchKernelGGL(voxel_carve_kernel, dim3((unsigned)voxel_walk_groups(m->cap)), dim3(VX_T), 0, ctx->stream, a);
   SVO_HIP_CHECK(ctx, hipGetLastError());
   return SVO_OK;
 }
 
 extern "C" int svo_voxel_map_carve_pose7_dev(svo_voxel_map* m, const int16_t* disp16, int width, int height, const svo_camera_info* cam,
                                              const double* pose7, const svo_voxel_carve_params* prm, uint64_t* counts) {
-  if (!m) return SVO_ERR_INVALID;
-  SVO_REQUIRE(m->ctx, pose7, "voxel_map_carve_pose7: null pose7");
   double m12[12];
-  svo_pose7_to_world_to_cam(pose7, m12);
-  return svo_voxel_map_carve_dev(m, disp16, width, height, cam, m12, prm, counts);
+  const int rc = voxel_pose7(m, pose7, voxel_pose7_to_world_to_cam, m12, "voxel_map_carve_pose7: null pose7");
+  return rc ? rc : svo_voxel_map_carve_dev(m, disp16, width, height, cam, m12, prm, counts);
 }
 
 extern "C" int svo_voxel_map_carve(svo_voxel_map* m, const int16_t* disp16, int width, int height, const svo_camera_info* cam,
@@ -956,21 +858,18 @@ extern "C" int svo_voxel_map_carve(svo_voxel_map* m, const int16_t* disp16, int 
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = m->ctx;
   svo_use_device(ctx);
-  int rc = voxel_carve_check(m, disp16, width, height, cam, w2c12, prm);
-  if (rc) return rc;
+  VOXEL_CHECK(ctx, voxel_carve_check(disp16, width, height, cam, w2c12, prm, ctx->lim.max_width, ctx->lim.max_height, &err));
   const size_t bytes = sizeof(int16_t) * (size_t)width * (size_t)height;
   u64* d = nullptr;  // 3 counts | the map
   SVO_HIP_CHECK(ctx, hipMalloc((void**)&d, 4 * sizeof(u64) + bytes));
+  VoxelTemp hold{d};
   int16_t* d_disp = reinterpret_cast<int16_t*>(d + 4);
   u64 c[3] = {0, 0, 0};
-  hipError_t e = hipMemcpyAsync(d_disp, disp16, bytes, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) rc = svo_voxel_map_carve_dev(m, d_disp, width, height, cam, w2c12, prm, reinterpret_cast<uint64_t*>(d));
-  if (e == hipSuccess && !rc) e = hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, ctx->stream);
-  const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // also before the free, whatever failed
-  if (e == hipSuccess) e = e2;
-  (void)hipFree(d);
+  const int rc = voxel_sync(
+      ctx, "voxel_map_carve", hipMemcpyAsync(d_disp, disp16, bytes, hipMemcpyHostToDevice, ctx->stream),
+      [&] { return svo_voxel_map_carve_dev(m, d_disp, width, height, cam, w2c12, prm, reinterpret_cast<uint64_t*>(d)); },
+      [&] { return hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, ctx->stream); });
   if (rc) return rc;
-  if (e != hipSuccess) { ctx->err = std::string("voxel_map_carve: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
   if (counts) { counts[0] = c[0]; counts[1] = c[1]; counts[2] = c[2]; }
   return SVO_OK;
 }
@@ -987,18 +886,11 @@ extern "C" int svo_voxel_map_copy_live_dev(svo_voxel_map* src, svo_voxel_map* ds
   a.src = src->t; a.dst = dst->t;
   a.min_count = (unsigned)min_count;
   if (box6) {
-    const double vs = (double)src->prm.voxel_size, far = 2097152.0;  // 2^21: beyond every key on either side
-    for (int i = 0; i < 6; ++i) {
-      SVO_REQUIRE(ctx, box6[i] == box6[i], "voxel_map_copy_live: box6 holds a NaN");
-      double k = floor(box6[i] / vs);
-      k = k < -far ? -far : (k > far ? far : k);
-      (i < 3 ? a.klo[i] : a.khi[i - 3]) = (int)k;
-    }
+    VOXEL_CHECK(ctx, voxel_box_keys(box6, src->prm.voxel_size, a.klo, a.khi, &err));
     a.boxed = 1;
   }
-  const unsigned blocks = (unsigned)((src->cap + (size_t)VX_T * VX_ITEMS - 1) / ((size_t)VX_T * VX_ITEMS));
   SvoProfScope prof(ctx, SVO_PROF_VOXEL_COPY);
-  hipLaunchKernelGGL(voxel_copy_kernel, dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
+  hipLaunchKernelGGL(voxel_copy_kernel, dim3((unsigned)voxel_walk_groups(src->cap)), dim3(VX_T), 0, ctx->stream, a);
   SVO_HIP_CHECK(ctx, hipGetLastError());
   return SVO_OK;
 }
@@ -1006,8 +898,7 @@ extern "C" int svo_voxel_map_copy_live_dev(svo_voxel_map* src, svo_voxel_map* ds
 // ----------------------------------------------------------------------------- the render
 extern "C" int svo_voxel_render_default_params(svo_voxel_render_params* params) {
   if (!params) return SVO_ERR_INVALID;
-  params->min_count = 1;
-  params->max_radius = 8;
+  params->min_count = 1; params->max_radius = 8;
   return SVO_OK;
 }
 
@@ -1017,26 +908,13 @@ extern "C" size_t svo_voxel_render_workspace_bytes(int width, int height) {
 
 extern "C" int svo_voxel_render_set_mode(svo_voxel_map* m, int cooperative, int precheck) {
   if (!m) return SVO_ERR_INVALID;
-  m->render_coop = cooperative != 0;
-  m->render_pre = precheck != 0;
+  m->render_coop = cooperative != 0; m->render_pre = precheck != 0;
   return SVO_OK;
 }
 
-static int voxel_render_check(svo_voxel_map* m, int width, int height, const svo_camera_info* cam, const double* w2c12,
-                              const svo_voxel_render_params* prm) {
-  svo_ctx* ctx = m->ctx;
-  const double big = 1.7976931348623157e308;
-  SVO_REQUIRE(ctx, cam, "voxel_map_render: null cam");
-  SVO_REQUIRE(ctx, w2c12, "voxel_map_render: null w2c12");
-  SVO_REQUIRE(ctx, prm, "voxel_map_render: null params");
-  SVO_REQUIRE(ctx, prm->min_count >= 1, "voxel_map_render: min_count must be at least 1");
-  SVO_REQUIRE(ctx, prm->max_radius >= 0 && prm->max_radius <= 16, "voxel_map_render: max_radius outside 0..16");
-  SVO_REQUIRE(ctx, width >= 1 && width <= ctx->lim.max_width, "voxel_map_render: width below 1 or beyond the context's limit");
-  SVO_REQUIRE(ctx, height >= 1 && height <= ctx->lim.max_height, "voxel_map_render: height below 1 or beyond the context's limit");
-  SVO_REQUIRE(ctx, cam->focal > 0.0 && cam->focal <= big, "voxel_map_render: focal must be finite and > 0");
-  SVO_REQUIRE(ctx, cam->baseline > 0.0 && cam->baseline <= big, "voxel_map_render: baseline must be finite and > 0");
-  return SVO_OK;
-}
+// The splat launch's four forms, [cooperative][pre-check] (svo_voxel_render_set_mode).
+static void (*const voxel_splat_form[2][2])(VoxelSplatArgs) = {{voxel_splat_kernel<false, false>, voxel_splat_kernel<true, false>},
+                                                               {voxel_splat_kernel<false, true>, voxel_splat_kernel<true, true>}};
 
 extern "C" int svo_voxel_map_render_dev(svo_voxel_map* m, int width, int height, const svo_camera_info* cam, const double* w2c12,
                                         const svo_voxel_render_params* prm, void* workspace, int16_t* disp16, uint8_t* intensity,
@@ -1044,8 +922,7 @@ extern "C" int svo_voxel_map_render_dev(svo_voxel_map* m, int width, int height,
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = m->ctx;
   svo_use_device(ctx);
-  const int rc = voxel_render_check(m, width, height, cam, w2c12, prm);
-  if (rc) return rc;
+  VOXEL_CHECK(ctx, voxel_render_check(width, height, cam, w2c12, prm, ctx->lim.max_width, ctx->lim.max_height, &err));
   SVO_REQUIRE(ctx, workspace, "voxel_map_render: null workspace");
   SVO_REQUIRE(ctx, ((uintptr_t)workspace & 3u) == 0, "voxel_map_render: workspace must be 4-byte aligned");
   SVO_REQUIRE(ctx, disp16, "voxel_map_render: null disp16");
@@ -1061,22 +938,14 @@ extern "C" int svo_voxel_map_render_dev(svo_voxel_map* m, int width, int height,
   VoxelResolveArgs b{};
   b.pix = a.pix; b.disp = disp16; b.inten = intensity;
   b.n = (size_t)width * (size_t)height;
-  b.vec = ((uintptr_t)workspace & 15u) == 0 && ((uintptr_t)disp16 & 7u) == 0 && ((uintptr_t)intensity & 3u) == 0;
+  b.vec = voxel_resolve_vector_ok(workspace, disp16, intensity);
   b.counts = a.counts;
-  const unsigned blocks = (unsigned)((m->cap + (size_t)VX_T * VX_ITEMS - 1) / ((size_t)VX_T * VX_ITEMS));
-  const unsigned rblocks = (unsigned)((b.n + (size_t)VX_T * 4 - 1) / ((size_t)VX_T * 4));
   SvoProfScope prof(ctx, SVO_PROF_VOXEL_RENDER);
   SVO_HIP_CHECK(ctx, hipMemsetAsync(workspace, 0, 4 * b.n, ctx->stream));
   if (counts) SVO_HIP_CHECK(ctx, hipMemsetAsync(counts, 0, 4 * sizeof(u64), ctx->stream));
-  if (m->render_coop) {
-    if (m->render_pre) hipLaunchKernelGGL((voxel_splat_kernel<true, true>), dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((voxel_splat_kernel<false, true>), dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
-  } else {
-    if (m->render_pre) hipLaunchKernelGGL((voxel_splat_kernel<true, false>), dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((voxel_splat_kernel<false, false>), dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
-  }
+  hipLaunchKernelGGL(voxel_splat_form[m->render_coop][m->render_pre], dim3((unsigned)voxel_walk_groups(m->cap)), dim3(VX_T), 0, ctx->stream, a);
   SVO_HIP_CHECK(ctx, hipGetLastError());
-  hipLaunchKernelGGL(voxel_resolve_kernel, dim3(rblocks), dim3(VX_T), 0, ctx->stream, b);
+  hipLaunchKernelGGL(voxel_resolve_kernel, dim3((unsigned)voxel_resolve_groups(b.n)), dim3(VX_T), 0, ctx->stream, b);
   SVO_HIP_CHECK(ctx, hipGetLastError());
   return SVO_OK;
 }
@@ -1084,11 +953,9 @@ extern "C" int svo_voxel_map_render_dev(svo_voxel_map* m, int width, int height,
 extern "C" int svo_voxel_map_render_pose7_dev(svo_voxel_map* m, int width, int height, const svo_camera_info* cam, const double* pose7,
                                               const svo_voxel_render_params* prm, void* workspace, int16_t* disp16, uint8_t* intensity,
                                               uint64_t* counts) {
-  if (!m) return SVO_ERR_INVALID;
-  SVO_REQUIRE(m->ctx, pose7, "voxel_map_render_pose7: null pose7");
   double m12[12];
-  svo_pose7_to_world_to_cam(pose7, m12);
-  return svo_voxel_map_render_dev(m, width, height, cam, m12, prm, workspace, disp16, intensity, counts);
+  const int rc = voxel_pose7(m, pose7, voxel_pose7_to_world_to_cam, m12, "voxel_map_render_pose7: null pose7");
+  return rc ? rc : svo_voxel_map_render_dev(m, width, height, cam, m12, prm, workspace, disp16, intensity, counts);
 }
 
 extern "C" int svo_voxel_map_render(svo_voxel_map* m, int width, int height, const svo_camera_info* cam, const double* w2c12,
@@ -1096,47 +963,40 @@ extern "C" int svo_voxel_map_render(svo_voxel_map* m, int width, int height, con
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = m->ctx;
   svo_use_device(ctx);
-  int rc = voxel_render_check(m, width, height, cam, w2c12, prm);
-  if (rc) return rc;
+  VOXEL_CHECK(ctx, voxel_render_check(width, height, cam, w2c12, prm, ctx->lim.max_width, ctx->lim.max_height, &err));
   SVO_REQUIRE(ctx, disp16, "voxel_map_render: null disp16");
   const size_t n = (size_t)width * (size_t)height, n16 = (n + 15) & ~(size_t)15;  // every part 16-byte aligned
   unsigned char* d = nullptr;                                                      // 4 counts | pix | disp16 | intensity
   SVO_HIP_CHECK(ctx, hipMalloc((void**)&d, 4 * sizeof(u64) + 7 * n16));
+  VoxelTemp hold{d};
   unsigned char* d_pix = d + 4 * sizeof(u64);
   int16_t* d_disp = reinterpret_cast<int16_t*>(d_pix + 4 * n16);
   uint8_t* d_int = d_pix + 6 * n16;
   u64 c[4] = {0, 0, 0, 0};
-  rc = svo_voxel_map_render_dev(m, width, height, cam, w2c12, prm, d_pix, d_disp, intensity ? d_int : nullptr, reinterpret_cast<uint64_t*>(d));
-  hipError_t e = hipSuccess;
-  if (!rc) e = hipMemcpyAsync(disp16, d_disp, sizeof(int16_t) * n, hipMemcpyDeviceToHost, ctx->stream);
-  if (!rc && e == hipSuccess && intensity) e = hipMemcpyAsync(intensity, d_int, n, hipMemcpyDeviceToHost, ctx->stream);
-  if (!rc && e == hipSuccess) e = hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, ctx->stream);
-  const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // also before the free, whatever failed
-  if (e == hipSuccess) e = e2;
-  (void)hipFree(d);
+  const int rc = voxel_sync(
+      ctx, "voxel_map_render", hipSuccess,
+      [&] { return svo_voxel_map_render_dev(m, width, height, cam, w2c12, prm, d_pix, d_disp, intensity ? d_int : nullptr, reinterpret_cast<uint64_t*>(d)); },
+      [&] {
+        hipError_t e = hipMemcpyAsync(disp16, d_disp, sizeof(int16_t) * n, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && intensity) e = hipMemcpyAsync(intensity, d_int, n, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, ctx->stream);
+        return e;
+      });
   if (rc) return rc;
-  if (e != hipSuccess) { ctx->err = std::string("voxel_map_render: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
   if (counts) for (int i = 0; i < 4; ++i) counts[i] = c[i];
   return SVO_OK;
 }
 
 // ----------------------------------------------------------------------------- removal and move
-static int voxel_counts_check(svo_voxel_map* m, const uint64_t* counts, const char* what) {
-  if (((uintptr_t)counts & 7u) != 0) { m->ctx->err = std::string(what) + ": counts must be 8-byte aligned"; return SVO_ERR_INVALID; }
-  return SVO_OK;
-}
-
 static int voxel_remove_launch(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* m12, uint64_t* counts) {
   svo_ctx* ctx = m->ctx;
   VoxelRemoveArgs a{};
-  a.pts = points; a.n = n;
+  a.pts = points; a.n = n; a.t = m->t;
   memcpy(a.m, m12, sizeof(a.m));
   a.voxel_size = m->prm.voxel_size; a.max_depth = m->prm.max_depth;
-  a.t = m->t;
   a.counts = reinterpret_cast<u64*>(counts);
-  const unsigned blocks = (unsigned)(((size_t)n + VX_T - 1) / VX_T);
   if (counts) SVO_HIP_CHECK(ctx, hipMemsetAsync(counts, 0, 4 * sizeof(u64), ctx->stream));
-  hipLaunchKernelGGL(voxel_remove_kernel, dim3(blocks), dim3(VX_T), 0, ctx->stream, a);
+  hipLaunchKernelGGL(voxel_remove_kernel, dim3((unsigned)voxel_record_groups(n)), dim3(VX_T), 0, ctx->stream, a);
   SVO_HIP_CHECK(ctx, hipGetLastError());
   return SVO_OK;
 }
@@ -1145,19 +1005,17 @@ extern "C" int svo_voxel_map_remove_dev(svo_voxel_map* m, const svo_cloud_point*
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = m->ctx;
   svo_use_device(ctx);
-  int rc = voxel_cloud_check(m, points, n, m12, "voxel_map_remove", "m12");
-  if (!rc) rc = voxel_counts_check(m, counts, "voxel_map_remove");
-  if (rc || n == 0) return rc;
+  VOXEL_CHECK(ctx, voxel_cloud_check(points, n, m12, VOXEL_REMOVE_TEXTS, &err));
+  VOXEL_CHECK(ctx, voxel_counts_check(counts, VOXEL_REMOVE_TEXTS, &err));
+  if (n == 0) return SVO_OK;
   SvoProfScope prof(ctx, SVO_PROF_VOXEL_REMOVE);
   return voxel_remove_launch(m, points, n, m12, counts);
 }
 
 extern "C" int svo_voxel_map_remove_pose7_dev(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* pose7, uint64_t* counts) {
-  if (!m) return SVO_ERR_INVALID;
-  SVO_REQUIRE(m->ctx, pose7, "voxel_map_remove_pose7: null pose7");
   double m12[12];
-  svo_pose7_to_cam_to_world(pose7, m12);
-  return svo_voxel_map_remove_dev(m, points, n, m12, counts);
+  const int rc = voxel_pose7(m, pose7, voxel_pose7_to_cam_to_world, m12, "voxel_map_remove_pose7: null pose7");
+  return rc ? rc : svo_voxel_map_remove_dev(m, points, n, m12, counts);
 }
 
 extern "C" int svo_voxel_map_remove_sync(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* m12, uint64_t* counts) {
@@ -1169,10 +1027,10 @@ extern "C" int svo_voxel_map_remove_sync(svo_voxel_map* m, const svo_cloud_point
   SvoScratch scratch(ctx);
   u64* d = scratch.take<u64>(4);  // the context's scratch: this call ends with the stream drained
   SVO_REQUIRE(ctx, d, "voxel_map_remove_sync: the context has no scratch");
-  const int rc = svo_voxel_map_remove_dev(m, points, n, m12, reinterpret_cast<uint64_t*>(d));
+  const int rc = voxel_sync(
+      ctx, "voxel_map_remove_sync", hipSuccess, [&] { return svo_voxel_map_remove_dev(m, points, n, m12, reinterpret_cast<uint64_t*>(d)); },
+      [&] { return n > 0 ? hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; });
   if (rc) return rc;
-  if (n > 0) SVO_HIP_CHECK(ctx, hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
-  SVO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   for (int i = 0; i < 4; ++i) counts[i] = c[i];
   return SVO_OK;
 }
@@ -1182,25 +1040,22 @@ extern "C" int svo_voxel_map_move_dev(svo_voxel_map* m, const svo_cloud_point* p
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = m->ctx;
   svo_use_device(ctx);
-  int rc = voxel_cloud_check(m, points, n, from_m12, "voxel_map_move", "from_m12");
-  if (!rc && !to_m12) { ctx->err = "voxel_map_move: null to_m12"; rc = SVO_ERR_INVALID; }
-  if (!rc) rc = voxel_counts_check(m, counts, "voxel_map_move");
-  if (rc || n == 0) return rc;
+  VOXEL_CHECK(ctx, voxel_cloud_check(points, n, from_m12, VOXEL_MOVE_TEXTS, &err));
+  SVO_REQUIRE(ctx, to_m12, "voxel_map_move: null to_m12");
+  VOXEL_CHECK(ctx, voxel_counts_check(counts, VOXEL_MOVE_TEXTS, &err));
+  if (n == 0) return SVO_OK;
   if (memcmp(from_m12, to_m12, 12 * sizeof(double)) == 0) return SVO_OK;  // the same bits: the cloud is where it belongs
   SvoProfScope prof(ctx, SVO_PROF_VOXEL_MOVE);
-  rc = voxel_remove_launch(m, points, n, from_m12, counts);
+  const int rc = voxel_remove_launch(m, points, n, from_m12, counts);
   return rc ? rc : voxel_insert_launch(m, points, n, to_m12);
 }
 
 extern "C" int svo_voxel_map_move_pose7_dev(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* from_pose7,
                                             const double* to_pose7, uint64_t* counts) {
-  if (!m) return SVO_ERR_INVALID;
-  SVO_REQUIRE(m->ctx, from_pose7, "voxel_map_move_pose7: null from_pose7");
-  SVO_REQUIRE(m->ctx, to_pose7, "voxel_map_move_pose7: null to_pose7");
   double from[12], to[12];
-  svo_pose7_to_cam_to_world(from_pose7, from);
-  svo_pose7_to_cam_to_world(to_pose7, to);
-  return svo_voxel_map_move_dev(m, points, n, from, to, counts);
+  int rc = voxel_pose7(m, from_pose7, voxel_pose7_to_cam_to_world, from, "voxel_map_move_pose7: null from_pose7");
+  if (!rc) rc = voxel_pose7(m, to_pose7, voxel_pose7_to_cam_to_world, to, "voxel_map_move_pose7: null to_pose7");
+  return rc ? rc : svo_voxel_map_move_dev(m, points, n, from, to, counts);
 }
 
 // ----------------------------------------------------------------------------- the keyframe ledger
@@ -1256,7 +1111,7 @@ extern "C" int svo_voxel_ledger_insert_pose7_dev(svo_voxel_ledger* l, int64_t id
   int slot = -1;
   if (l->table.admit(id, n, &slot, &err)) { ctx->err = err; return SVO_ERR_INVALID; }
   double m12[12];
-  svo_pose7_to_cam_to_world(pose7, m12);
+  voxel_pose7_to_cam_to_world(pose7, m12);
   if (n > 0) {  // the ledger's own copy first: the caller's cloud is valid only until its next process call
     SVO_HIP_CHECK(ctx, hipMemcpyAsync(l->at(slot), points, sizeof(svo_cloud_point) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
     SvoProfScope prof(ctx, SVO_PROF_VOXEL_INSERT);
@@ -1276,7 +1131,7 @@ extern "C" int svo_voxel_ledger_update_pose7(svo_voxel_ledger* l, int64_t id, co
   int slot = -1;
   if (l->table.find(id, &slot, "voxel_ledger_update: unknown id", &err)) { ctx->err = err; return SVO_ERR_INVALID; }
   double m12[12];
-  svo_pose7_to_cam_to_world(pose7, m12);
+  voxel_pose7_to_cam_to_world(pose7, m12);
   const VoxelLedgerSlot& s = l->table.slot(slot);
   const int rc = svo_voxel_map_move_dev(l->map, l->at(slot), s.n, s.m12, m12, counts);
   if (rc) return rc;

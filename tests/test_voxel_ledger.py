@@ -1,9 +1,10 @@
 """The voxel map's keyframe ledger (include/svo.h, "Voxel map ledger").
 
 CPU: the GPU-free table stereo_vo_amd/host/voxel_ledger.h walked by tests/sanitize/voxel_ledger_test.cpp under ASan + UBSan, a
-stand-alone program.  GPU: clouds held, moved, retired and removed through the ledger leave the map the restatement
-(tests/voxel_remove_ref.py) gives for the same sequence of inserts, moves and removals, with == on the whole table; the ledger
-owns its copies (the caller's buffer is overwritten after every insert); every refusal launches nothing.
+stand-alone program, and beside it the voxel map's other GPU-free host logic, stereo_vo_amd/host/voxel_args.h, walked by
+tests/sanitize/voxel_args_test.cpp the same way.  GPU: clouds held, moved, retired and removed through the ledger leave the map
+the restatement (tests/voxel_remove_ref.py) gives for the same sequence of inserts, moves and removals, with == on the whole
+table; the ledger owns its copies (the caller's buffer is overwritten after every insert); every refusal launches nothing.
 """
 import numpy as np
 import pytest
@@ -20,6 +21,14 @@ def test_ledger_table_fill_refusals_release_orders_and_random_walk(tmp_path):
     """host/voxel_ledger.h on the CPU under ASan + UBSan: fill, refuse when full, duplicate and unknown ids, oversize n; release in
     every order and slot reuse; the recorded matrix is the inserted one; 10,000 random operations against a std::map model."""
     _run_sanitized(tmp_path, "voxel_ledger_test", "voxel ledger ok")
+
+
+def test_voxel_args_every_refusal_at_its_boundary_matrices_box_and_geometry(tmp_path):
+    """host/voxel_args.h on the CPU under ASan + UBSan: the map's parameters and bytes, the cloud, counts, carve and render
+    argument checks with code and exact message on either side of every boundary, the copy's box -> key range (NaN, a voxel
+    face and one ulp below it, the clamp at +-2^21), the two matrices of a pose7 (identity and a half turn exactly, composition
+    and the 2 / |q|^2 normalisation within 4 ulp for ten seeded poses), the launch geometry without 32-bit wrap."""
+    _run_sanitized(tmp_path, "voxel_args_test", "voxel args ok")
 
 
 def _pose(k, step=0):
