@@ -579,6 +579,11 @@ def _p(a, t=None):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _ref(x):
+    """byref(x), or None (a null pointer) for None."""
+    return None if x is None else C.byref(x)
+
+
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
@@ -759,8 +764,7 @@ class Context:
         """svo_disparity_cloud_batch_dev: raw device pointers (ints; pose16_ptr None = identity); cam: CameraInfo, params: CloudParams;
         points_ptr: batch x params.max_points records of CLOUD_POINT_DTYPE, counts_ptr: batch x 2 int32.  Asynchronous."""
         self._chk(self.L.svo_disparity_cloud_batch_dev(self.h, disp16_ptr, left_ptr, batch, width, height, row_stride, image_stride,
-                                                       C.byref(cam) if cam is not None else None, pose16_ptr,
-                                                       C.byref(params) if params is not None else None, points_ptr, counts_ptr),
+                                                       _ref(cam), pose16_ptr, _ref(params), points_ptr, counts_ptr),
                   "svo_disparity_cloud_batch_dev")
 
     def stereo_cloud(self, left, right, cam, pose16=None, step=1, min_disparity=0.0, max_points=None, ndisp=48, block=21):
@@ -789,8 +793,8 @@ class Context:
         """svo_disparity_speckle_filter_batch_dev: raw device pointers (ints); disp16_ptr: batch tight (H, W) int16 maps, filtered in
         place; params: SpeckleParams; n_removed_ptr: batch int32 or None.  Asynchronous."""
         self._chk(self.L.svo_disparity_speckle_filter_batch_dev(self.h, disp16_ptr, batch, width, height,
-                                                                C.byref(params) if params is not None else None, workspace_ptr,
-                                                                workspace_bytes, n_removed_ptr), "svo_disparity_speckle_filter_batch_dev")
+                                                                _ref(params), workspace_ptr, workspace_bytes, n_removed_ptr),
+                  "svo_disparity_speckle_filter_batch_dev")
 
     # ---- left-right check
     def stereo_bm_cost_batch(self, left_ptr, right_ptr, batch, width, height, row_stride, image_stride, disp16_ptr, cost16_ptr,
@@ -815,7 +819,7 @@ class Context:
         """svo_disparity_lr_check_batch_dev: raw device pointers (ints); disp16_ptr: batch tight (H, W) int16 maps, checked in place;
         cost16_ptr: their uint16 costs; params: LrCheckParams; n_removed_ptr: batch int32 or None.  Asynchronous."""
         self._chk(self.L.svo_disparity_lr_check_batch_dev(self.h, disp16_ptr, cost16_ptr, batch, width, height,
-                                                          C.byref(params) if params is not None else None, n_removed_ptr),
+                                                          _ref(params), n_removed_ptr),
                   "svo_disparity_lr_check_batch_dev")
 
     # ---- semi-global matching
@@ -839,8 +843,8 @@ class Context:
         """svo_stereo_sgm_batch_dev: raw device pointers (ints); params: SgmParams; workspace: sgm_workspace_bytes(...) bytes;
         disp16_ptr: batch tight (H, W) int16 maps; cost16_ptr: batch tight (H, W) uint16 maps or None.  Asynchronous."""
         self._chk(self.L.svo_stereo_sgm_batch_dev(self.h, left_ptr, right_ptr, batch, width, height, row_stride, image_stride, ndisp, block,
-                                                  C.byref(params) if params is not None else None, workspace_ptr, workspace_bytes,
-                                                  disp16_ptr, cost16_ptr), "svo_stereo_sgm_batch_dev")
+                                                  _ref(params), workspace_ptr, workspace_bytes, disp16_ptr, cost16_ptr),
+                  "svo_stereo_sgm_batch_dev")
 
     # ---- a8
     def triangulate(self, xy, disp, pose16, focal, cx, cy, baseline):
@@ -1315,8 +1319,49 @@ def pipeline_default_params():
     return p
 
 
-class Pipeline:
+class _KeyframeCloudMethods:
+    """What Pipeline and PipelineGroup both offer on their keyframe clouds.  `_ENTRY` is the C entry prefix, "svo_pipeline" or
+    "svo_pipeline_group": every method below calls (and, on failure, names) the entry `_ENTRY + "_" + <its own name>`."""
+
+    def _kfc(self, name, *args):
+        name = self._ENTRY + "_" + name
+        self.ctx._chk(getattr(self.L, name)(self.h, *args), name)
+
+    def set_keyframe_speckle_filter(self, max_size=None, max_diff16=0):
+        """svo_pipeline[_group]_set_keyframe_speckle_filter: the keyframe maps are speckle-filtered before the clouds are formed (clouds
+        must be on; group-wide in a group); max_size None: off."""
+        self._kfc("set_keyframe_speckle_filter", _ref(None if max_size is None else SpeckleParams(int(max_size), int(max_diff16))))
+
+    def set_keyframe_lr_check(self, max_diff16=None):
+        """svo_pipeline[_group]_set_keyframe_lr_check: the keyframe maps pass the left-right check before the speckle filter and the clouds
+        (clouds must be on; group-wide in a group); max_diff16 None: off."""
+        self._kfc("set_keyframe_lr_check", _ref(None if max_diff16 is None else LrCheckParams(int(max_diff16))))
+
+    def set_keyframe_sgm(self, p1=None, p2=None, on=True):
+        """svo_pipeline[_group]_set_keyframe_sgm: the keyframe maps come from semi-global matching instead of block matching (clouds must
+        be on; group-wide in a group); p1 / p2 None: the defaults 2 * 21^2 / 8 * 21^2; on=False: back to block matching."""
+        self._kfc("set_keyframe_sgm", _ref(_sgm_params(p1, p2) if on else None))
+
+    def keyframe_clouds(self):
+        """The keyframes of the last process call: [{frame, lane, n_total, n_stored, dev, points (CLOUD_POINT_DTYPE array)}], in frame
+        order; of a group: over the lanes that have clouds on, ordered by lane, then frame."""
+        return _keyframe_clouds(self.ctx, self.L, self.h, getattr(self.L, self._ENTRY + "_keyframe_clouds"),
+                                getattr(self.L, self._ENTRY + "_copy_keyframe_cloud"))
+
+    def keyframe_disparity(self, i):
+        """svo_pipeline[_group]_keyframe_disparity: the device pointer (an int) of the tight CV_16S map of entry i of keyframe_clouds(), as
+        its cloud was formed from it; valid until the next process call."""
+        return _keyframe_disparity(self.ctx, self.h, getattr(self.L, self._ENTRY + "_keyframe_disparity"), i)
+
+    def copy_keyframe_disparity(self, i):
+        """svo_pipeline[_group]_copy_keyframe_disparity: entry i's map as a (height, width) int16 numpy array (synchronous)."""
+        return _keyframe_disparity_host(self.ctx, self.h, getattr(self.L, self._ENTRY + "_copy_keyframe_disparity"), i, self.prm.width, self.prm.height)
+
+
+class Pipeline(_KeyframeCloudMethods):
     """svo_pipeline wrapper: ImageProcessor::process + BundleAdjuster::bundle_adjust per frame."""
+
+    _ENTRY = "svo_pipeline"
 
     def __init__(self, ctx, params):
         self.ctx, self.L, self.prm = ctx, ctx.L, params
@@ -1341,49 +1386,14 @@ class Pipeline:
     def set_rectification(self, left=None, right=None):
         """svo_pipeline_set_rectification: RectifyEye per eye (left/right are raw images from then on); None, None: off."""
         self.L.svo_pipeline_set_rectification.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        self.ctx._chk(self.L.svo_pipeline_set_rectification(self.h, C.byref(left) if left is not None else None,
-                                                            C.byref(right) if right is not None else None), "svo_pipeline_set_rectification")
+        self.ctx._chk(self.L.svo_pipeline_set_rectification(self.h, _ref(left), _ref(right)), "svo_pipeline_set_rectification")
 
     def set_keyframe_clouds(self, params=None, max_keyframes_per_call=0):
         """svo_pipeline_set_keyframe_clouds: params a CloudParams (max_points <= 0: width*height), or True for the defaults; None: off."""
         if params is True:
             params = cloud_default_params(self.prm.width, self.prm.height)
-        self.ctx._chk(self.L.svo_pipeline_set_keyframe_clouds(self.h, C.byref(params) if params is not None else None, max_keyframes_per_call),
+        self.ctx._chk(self.L.svo_pipeline_set_keyframe_clouds(self.h, _ref(params), max_keyframes_per_call),
                       "svo_pipeline_set_keyframe_clouds")
-
-    def set_keyframe_speckle_filter(self, max_size=None, max_diff16=0):
-        """svo_pipeline_set_keyframe_speckle_filter: the keyframe maps are speckle-filtered before the clouds are formed (clouds must be
-        on); max_size None: off."""
-        prm = None if max_size is None else SpeckleParams(int(max_size), int(max_diff16))
-        self.ctx._chk(self.L.svo_pipeline_set_keyframe_speckle_filter(self.h, C.byref(prm) if prm is not None else None),
-                      "svo_pipeline_set_keyframe_speckle_filter")
-
-    def set_keyframe_lr_check(self, max_diff16=None):
-        """svo_pipeline_set_keyframe_lr_check: the keyframe maps pass the left-right check before the speckle filter and the clouds
-        (clouds must be on); max_diff16 None: off."""
-        prm = None if max_diff16 is None else LrCheckParams(int(max_diff16))
-        self.ctx._chk(self.L.svo_pipeline_set_keyframe_lr_check(self.h, C.byref(prm) if prm is not None else None),
-                      "svo_pipeline_set_keyframe_lr_check")
-
-    def set_keyframe_sgm(self, p1=None, p2=None, on=True):
-        """svo_pipeline_set_keyframe_sgm: the keyframe maps come from semi-global matching instead of block matching (clouds must be
-        on); p1 / p2 None: the defaults 2 * 21^2 / 8 * 21^2; on=False: back to block matching."""
-        prm = _sgm_params(p1, p2) if on else None
-        self.ctx._chk(self.L.svo_pipeline_set_keyframe_sgm(self.h, C.byref(prm) if prm is not None else None),
-                      "svo_pipeline_set_keyframe_sgm")
-
-    def keyframe_clouds(self):
-        """The keyframes of the last process call: [{frame, lane, n_total, n_stored, dev, points (CLOUD_POINT_DTYPE array)}], in frame order."""
-        return _keyframe_clouds(self.ctx, self.L, self.h, self.L.svo_pipeline_keyframe_clouds, self.L.svo_pipeline_copy_keyframe_cloud)
-
-    def keyframe_disparity(self, i):
-        """svo_pipeline_keyframe_disparity: the device pointer (an int) of entry i's tight CV_16S map as its cloud was formed from it;
-        valid until the next process call."""
-        return _keyframe_disparity(self.ctx, self.h, self.L.svo_pipeline_keyframe_disparity, i)
-
-    def copy_keyframe_disparity(self, i):
-        """svo_pipeline_copy_keyframe_disparity: entry i's map as a (height, width) int16 numpy array (synchronous)."""
-        return _keyframe_disparity_host(self.ctx, self.h, self.L.svo_pipeline_copy_keyframe_disparity, i, self.prm.width, self.prm.height)
 
     def process_batch(self, left, right):
         """left/right: (B, H, W) uint8 host arrays."""
@@ -1415,9 +1425,10 @@ class Pipeline:
         return ids[:n.value].copy(), xy[:n.value].copy()
 
 
-class PipelineGroup:
+class PipelineGroup(_KeyframeCloudMethods):
     """svo_pipeline_group wrapper: n_lanes independent stereo streams behind one caller thread (stream-batched launches)."""
 
+    _ENTRY = "svo_pipeline_group"
     STAGES = ("track", "pnp_ransac", "host_thread_busy_us_of_call_us", "dedup_stereo_triangulate", "bundle_adjust", "corners_pyramids")
 
     def __init__(self, ctx, params, n_lanes):
@@ -1445,46 +1456,14 @@ class PipelineGroup:
     def set_rectification(self, lane, left=None, right=None):
         """svo_pipeline_group_set_rectification: lane -1 = every lane; None, None turns the lane's rectification off."""
         self.L.svo_pipeline_group_set_rectification.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        self.ctx._chk(self.L.svo_pipeline_group_set_rectification(self.h, lane, C.byref(left) if left is not None else None,
-                                                                  C.byref(right) if right is not None else None),
-                      "svo_pipeline_group_set_rectification")
+        self.ctx._chk(self.L.svo_pipeline_group_set_rectification(self.h, lane, _ref(left), _ref(right)), "svo_pipeline_group_set_rectification")
 
     def set_keyframe_clouds(self, lane=-1, params=None, max_keyframes_per_call=0):
         """svo_pipeline_group_set_keyframe_clouds: lane -1 = every lane; params a CloudParams, True for the defaults, None: off."""
         if params is True:
             params = cloud_default_params(self.prm.width, self.prm.height)
-        self.ctx._chk(self.L.svo_pipeline_group_set_keyframe_clouds(self.h, lane, C.byref(params) if params is not None else None,
-                                                                    max_keyframes_per_call), "svo_pipeline_group_set_keyframe_clouds")
-
-    def set_keyframe_speckle_filter(self, max_size=None, max_diff16=0):
-        """svo_pipeline_group_set_keyframe_speckle_filter (group-wide; clouds must be on); max_size None: off."""
-        prm = None if max_size is None else SpeckleParams(int(max_size), int(max_diff16))
-        self.ctx._chk(self.L.svo_pipeline_group_set_keyframe_speckle_filter(self.h, C.byref(prm) if prm is not None else None),
-                      "svo_pipeline_group_set_keyframe_speckle_filter")
-
-    def set_keyframe_lr_check(self, max_diff16=None):
-        """svo_pipeline_group_set_keyframe_lr_check (group-wide; clouds must be on); max_diff16 None: off."""
-        prm = None if max_diff16 is None else LrCheckParams(int(max_diff16))
-        self.ctx._chk(self.L.svo_pipeline_group_set_keyframe_lr_check(self.h, C.byref(prm) if prm is not None else None),
-                      "svo_pipeline_group_set_keyframe_lr_check")
-
-    def set_keyframe_sgm(self, p1=None, p2=None, on=True):
-        """svo_pipeline_group_set_keyframe_sgm (group-wide; clouds must be on); on=False: back to block matching."""
-        prm = _sgm_params(p1, p2) if on else None
-        self.ctx._chk(self.L.svo_pipeline_group_set_keyframe_sgm(self.h, C.byref(prm) if prm is not None else None),
-                      "svo_pipeline_group_set_keyframe_sgm")
-
-    def keyframe_clouds(self):
-        """The keyframes of the last process call over the lanes that have clouds on, ordered by lane, then frame (see Pipeline.keyframe_clouds)."""
-        return _keyframe_clouds(self.ctx, self.L, self.h, self.L.svo_pipeline_group_keyframe_clouds, self.L.svo_pipeline_group_copy_keyframe_cloud)
-
-    def keyframe_disparity(self, i):
-        """svo_pipeline_group_keyframe_disparity: the device pointer (an int) of entry i of keyframe_clouds()."""
-        return _keyframe_disparity(self.ctx, self.h, self.L.svo_pipeline_group_keyframe_disparity, i)
-
-    def copy_keyframe_disparity(self, i):
-        """svo_pipeline_group_copy_keyframe_disparity: entry i's map as a (height, width) int16 numpy array (synchronous)."""
-        return _keyframe_disparity_host(self.ctx, self.h, self.L.svo_pipeline_group_copy_keyframe_disparity, i, self.prm.width, self.prm.height)
+        self.ctx._chk(self.L.svo_pipeline_group_set_keyframe_clouds(self.h, lane, _ref(params), max_keyframes_per_call),
+                      "svo_pipeline_group_set_keyframe_clouds")
 
     def process_batch_dev(self, left_ptr, right_ptr, lane_stride, batch):
         """left_ptr/right_ptr: raw device pointers to (n_lanes, B, H, W) uint8 images (lane_stride bytes between lanes).

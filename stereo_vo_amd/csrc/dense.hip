@@ -10,9 +10,8 @@
 //                               first: kept pixels per chunk of 2048 candidates, an exclusive scan per image by one
 //                               workgroup, then the write pass recomputes the predicate and compacts inside its chunk.
 // No kernel here has a fence, cache maintenance or an ordered atomic (docs/HISTORY.md, "No cache maintenance inside kernels"):
-// each pass reads what the PREVIOUS launch of the same stream wrote.
-#include <new>
-
+// each pass reads what the PREVIOUS launch of the same stream wrote.  The argument rules, the chunk counts and the LDS sizes are
+// host/dense_args.h's; the keyframe clouds of a pipeline that call in here are host/keyframe_clouds.cpp.
 #include "kernels.h"
 #include "ref_constants.h"
 #include "stereo_common.h"
@@ -22,10 +21,10 @@ namespace {
 constexpr int RAW_H = DT_TH + 2;                      // raw tile rows (halo 1)
 constexpr int RAW_LP = (DT_TWL + 2 + 3) & ~3;         // raw left tile pitch (88)
 constexpr int RAW_RP = (DT_TWR + 2 + 3) & ~3;         // raw right tile pitch (152)
-constexpr int DENSE_LDS_MAX = (int)sizeof(unsigned short) * (MAX_NDISP + 1) * DT_PIX;  // 66,560 B
 static_assert(RAW_H * (RAW_LP + RAW_RP) <= (int)sizeof(unsigned short) * (16 + 1) * DT_PIX, "the raw tiles must fit the smallest SAD region (16 disparities)");
 
-constexpr int CL_T = 256, CL_ITEMS = 8, CL_CHUNK = CL_T * CL_ITEMS;  // candidates per workgroup of the count / write passes
+constexpr int CL_T = 256, CL_ITEMS = 8;  // threads and candidates per thread of a workgroup of the count / write passes
+static_assert(CL_T * CL_ITEMS == CL_CHUNK, "a workgroup takes one chunk");
 
 __device__ __forceinline__ const uint8_t* pair_image(const SvoDensePairs& s, int z, int eye) {
   if (s.tab) return eye ? s.tab[z].right : s.tab[z].left;
@@ -265,7 +264,7 @@ __global__ __launch_bounds__(CL_T) void cloud_write_kernel(SvoCloudArgs a) {
 // ----------------------------------------------------------------------------- host side
 int svo_k_stereo_dense_batch(svo_ctx* ctx, const SvoDensePairs& src, int batch, int W, int H, int stride, int ndisp, int block,
                              int16_t* disp16, uint16_t* cost16) {
-  const size_t sad_lds = sizeof(unsigned short) * (size_t)(ndisp + 1) * DT_PIX;
+  const size_t sad_lds = dense_sad_lds(ndisp);
   // the grant belongs to the device the kernel was loaded on, and to ONE kernel function (hipFuncSetAttribute is per function):
   // remembered per context (= per device) and per form, not per process
   int& granted = cost16 ? ctx->dense_cost_lds_granted : ctx->dense_lds_granted;
@@ -281,18 +280,13 @@ int svo_k_stereo_dense_batch(svo_ctx* ctx, const SvoDensePairs& src, int batch, 
   return SVO_OK;
 }
 
-int svo_k_cloud_chunks(int W, int H, int step) {
-  const long n = (long)svo_div_up(W, step) * svo_div_up(H, step);
-  return (int)((n + CL_CHUNK - 1) / CL_CHUNK);
-}
-
 int svo_k_cloud(svo_ctx* ctx, const int16_t* disp16, const SvoDensePairs& src, int batch, int W, int H, int stride,
                 const svo_camera_info* cam, const float* pose16, const svo_cloud_params* prm, svo_cloud_point* points, int* counts,
                 int* seg) {
   SvoCloudArgs a{};
   a.disp = disp16; a.src = src; a.W = W; a.H = H; a.stride = stride;
-  a.step = prm->step; a.nx = svo_div_up(W, prm->step); a.n_cand = a.nx * svo_div_up(H, prm->step);
-  a.n_chunks = svo_k_cloud_chunks(W, H, prm->step);
+  a.step = prm->step; a.nx = cloud_nx(W, prm->step); a.n_cand = cloud_n_cand(W, H, prm->step);
+  a.n_chunks = cloud_chunks(W, H, prm->step);
   a.thr = prm->min_disparity > 0.f ? prm->min_disparity : 0.f;
   a.max_points = prm->max_points;
   a.Q = svo_k_reprojection_q((float)cam->focal, (float)cam->cx, (float)cam->cy, (float)cam->baseline);
@@ -305,46 +299,31 @@ int svo_k_cloud(svo_ctx* ctx, const int16_t* disp16, const SvoDensePairs& src, i
   return SVO_OK;
 }
 
-static int cloud_check(svo_ctx* ctx, int W, int H, int stride, const svo_camera_info* cam, const svo_cloud_params* prm) {
-  SVO_REQUIRE(ctx, cam && prm, "cloud: null camera or parameters");
-  SVO_REQUIRE(ctx, W >= 1 && H >= 1 && (long)W * (long)H <= (1L << 24), "cloud: width*height must be at most 2^24 (the tag holds the pixel index in 24 bits)");
-  SVO_REQUIRE(ctx, W <= ctx->lim.max_width && H <= ctx->lim.max_height && stride >= W, "cloud: image size outside limits");
-  SVO_REQUIRE(ctx, prm->step >= 1, "cloud: step must be at least 1");
-  SVO_REQUIRE(ctx, prm->max_points >= 1, "cloud: max_points must be at least 1");
-  SVO_REQUIRE(ctx, cam->focal != 0.0 && cam->baseline != 0.0, "cloud: focal length and baseline must not be 0");
-  return SVO_OK;
-}
+extern "C" int svo_cloud_default_params(svo_cloud_params* p, int width, int height) { return cloud_default_params(p, width, height); }
 
-extern "C" int svo_cloud_default_params(svo_cloud_params* p, int width, int height) {
-  if (!p || width < 1 || height < 1 || (long)width * (long)height > (1L << 24)) return SVO_ERR_INVALID;
-  p->step = 1;
-  p->min_disparity = 0.f;
-  p->max_points = width * height;
-  return SVO_OK;
+// The plain and the cost form of the batched dense entry: `t` tells them apart (t.null_cost: the cost map is required).
+static int stereo_bm_batch(svo_ctx* ctx, const uint8_t* left, const uint8_t* right, int batch, int width, int height, int row_stride,
+                           size_t image_stride, int num_disparities, int block_size, int16_t* disp16, uint16_t* cost16, const DenseBatchTexts& t) {
+  int rc = svo_stereo_check(ctx, left, right, width, height, row_stride, num_disparities, block_size);
+  if (rc) return rc;
+  SVO_REQUIRE(ctx, disp16, t.null_disp);
+  if (t.null_cost) SVO_REQUIRE(ctx, cost16, t.null_cost);
+  DENSE_CHECK(ctx, dense_batch_check(batch, ctx->lim.max_batch, width, height, row_stride, image_stride, t, &err));
+  SvoDensePairs src{left, right, image_stride, nullptr};
+  return svo_k_stereo_dense_batch(ctx, src, batch, width, height, row_stride, num_disparities, block_size, disp16, cost16);
 }
 
 extern "C" int svo_stereo_bm_batch_dev(svo_ctx* ctx, const uint8_t* left, const uint8_t* right, int batch, int width, int height,
                                        int row_stride, size_t image_stride, int num_disparities, int block_size, int16_t* disp16) {
-  int rc = svo_stereo_check(ctx, left, right, width, height, row_stride, num_disparities, block_size);
-  if (rc) return rc;
-  SVO_REQUIRE(ctx, disp16, "stereo_bm_batch: null output");
-  SVO_REQUIRE(ctx, batch >= 1 && batch <= ctx->lim.max_batch, "stereo_bm_batch: batch outside 1..max_batch");
-  SVO_REQUIRE(ctx, batch == 1 || image_stride >= (size_t)row_stride * (size_t)(height - 1) + (size_t)width, "stereo_bm_batch: images overlap");
-  SvoDensePairs src{left, right, image_stride, nullptr};
-  return svo_k_stereo_dense_batch(ctx, src, batch, width, height, row_stride, num_disparities, block_size, disp16);
+  return stereo_bm_batch(ctx, left, right, batch, width, height, row_stride, image_stride, num_disparities, block_size, disp16, nullptr,
+                         STEREO_BM_BATCH_TEXTS);
 }
 
 extern "C" int svo_stereo_bm_cost_batch_dev(svo_ctx* ctx, const uint8_t* left, const uint8_t* right, int batch, int width, int height,
                                             int row_stride, size_t image_stride, int num_disparities, int block_size, int16_t* disp16,
                                             uint16_t* cost16) {
-  int rc = svo_stereo_check(ctx, left, right, width, height, row_stride, num_disparities, block_size);
-  if (rc) return rc;
-  SVO_REQUIRE(ctx, disp16, "stereo_bm_cost_batch: null disp16");
-  SVO_REQUIRE(ctx, cost16, "stereo_bm_cost_batch: null cost16");
-  SVO_REQUIRE(ctx, batch >= 1 && batch <= ctx->lim.max_batch, "stereo_bm_cost_batch: batch outside 1..max_batch");
-  SVO_REQUIRE(ctx, batch == 1 || image_stride >= (size_t)row_stride * (size_t)(height - 1) + (size_t)width, "stereo_bm_cost_batch: images overlap");
-  SvoDensePairs src{left, right, image_stride, nullptr};
-  return svo_k_stereo_dense_batch(ctx, src, batch, width, height, row_stride, num_disparities, block_size, disp16, cost16);
+  return stereo_bm_batch(ctx, left, right, batch, width, height, row_stride, image_stride, num_disparities, block_size, disp16, cost16,
+                         STEREO_BM_COST_BATCH_TEXTS);
 }
 
 extern "C" int svo_disparity_cloud_batch_dev(svo_ctx* ctx, const int16_t* disp16, const uint8_t* left, int batch, int width, int height,
@@ -353,11 +332,10 @@ extern "C" int svo_disparity_cloud_batch_dev(svo_ctx* ctx, const int16_t* disp16
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
   SVO_REQUIRE(ctx, disp16 && left && points && counts, "disparity_cloud: null buffer");
-  int rc = cloud_check(ctx, width, height, row_stride, cam, params);
-  if (rc) return rc;
+  DENSE_CHECK(ctx, cloud_check(width, height, row_stride, cam, params, ctx->lim.max_width, ctx->lim.max_height, &err));
   SVO_REQUIRE(ctx, batch >= 1 && batch <= ctx->lim.max_batch, "disparity_cloud: batch outside 1..max_batch");
   // per-chunk counts for the largest call this context takes, once
-  const size_t need = (size_t)ctx->lim.max_batch * (size_t)svo_k_cloud_chunks(ctx->lim.max_width, ctx->lim.max_height, 1);
+  const size_t need = (size_t)ctx->lim.max_batch * (size_t)cloud_chunks(ctx->lim.max_width, ctx->lim.max_height, 1);
   if (ctx->cloud_seg_ints < need) {
     SVO_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_cloud_seg, need * sizeof(int)));
     ctx->cloud_seg_ints = need;
@@ -372,8 +350,7 @@ extern "C" int svo_stereo_cloud(svo_ctx* ctx, const uint8_t* left, const uint8_t
   int rc = svo_stereo_check(ctx, left, right, width, height, row_stride, num_disparities, block_size);
   if (rc) return rc;
   SVO_REQUIRE(ctx, points && n_total && n_stored, "stereo_cloud: null output");
-  rc = cloud_check(ctx, width, height, row_stride, cam, params);
-  if (rc) return rc;
+  DENSE_CHECK(ctx, cloud_check(width, height, row_stride, cam, params, ctx->lim.max_width, ctx->lim.max_height, &err));
   SvoScratch s(ctx);
   const size_t px = (size_t)width * height;
   uint8_t* dL = s.take<uint8_t>(px);
@@ -381,8 +358,8 @@ extern "C" int svo_stereo_cloud(svo_ctx* ctx, const uint8_t* left, const uint8_t
   int16_t* dD = s.take<int16_t>(px);
   float* dP = s.take<float>(16);
   int* dC = s.take<int>(2);
-  int* dS = s.take<int>((size_t)svo_k_cloud_chunks(width, height, params->step));
-  const size_t cap = (size_t)params->max_points < px ? (size_t)params->max_points : px;  // no more than px points exist
+  int* dS = s.take<int>((size_t)cloud_chunks(width, height, params->step));
+  const size_t cap = cloud_store_cap(params->max_points, px);
   svo_cloud_point* dQ = s.take<svo_cloud_point>(cap);
   if (!dL || !dR || !dD || !dP || !dC || !dS || !dQ) { ctx->err = "stereo_cloud: workspace too small"; return SVO_ERR_CAPACITY; }
   hipStream_t st = ctx->stream;
@@ -404,246 +381,5 @@ extern "C" int svo_stereo_cloud(svo_ctx* ctx, const uint8_t* left, const uint8_t
     SVO_HIP_CHECK(ctx, hipMemcpyAsync(points, dQ, sizeof(svo_cloud_point) * (size_t)c[1], hipMemcpyDeviceToHost, st));
     SVO_HIP_CHECK(ctx, hipStreamSynchronize(st));
   }
-  return SVO_OK;
-}
-
-// ----------------------------------------------------------------------------- keyframe clouds of a pipeline / a group
-struct SvoKfClouds {
-  svo_ctx* ctx = nullptr;
-  svo_cloud_params prm{};
-  int W = 0, H = 0, max_kf = 0;
-  int16_t* d_disp = nullptr;          // max_kf maps
-  svo_cloud_point* d_points = nullptr;  // max_kf x max_points
-  int* d_counts = nullptr;            // max_kf x 2
-  int* d_seg = nullptr;               // max_kf x chunks
-  SvoCloudPair* d_tab = nullptr;      // max_kf
-  void* h_pinned = nullptr;           // [max_kf pairs | max_kf x 2 counts]
-  bool speckle_on = false;            // svo_kfc_set_speckle: the maps are filtered before the clouds are formed
-  svo_speckle_params speckle{};
-  void* d_speckle_ws = nullptr;       // svo_speckle_workspace_bytes(W, H, max_kf)
-  bool lr_on = false;                 // svo_kfc_set_lr_check: the cost form of the dense launch, then the left-right check
-  svo_lr_check_params lr{};
-  uint16_t* d_cost = nullptr;         // max_kf cost maps, 2 * W * H * max_kf bytes
-  bool sgm_on = false;                // svo_kfc_set_sgm: semi-global matching (sgm.hip) instead of the dense launch
-  svo_sgm_params sgm{};
-  void* d_sgm_ws = nullptr;           // svo_sgm_workspace_bytes for SVO_SGM_KEYFRAME_SUB_BATCH pairs, whatever max_kf is
-  std::vector<svo_keyframe_cloud> table;
-};
-
-void svo_kfc_destroy(SvoKfClouds* k) {
-  if (!k) return;
-  (void)hipSetDevice(k->ctx->device);
-  (void)hipStreamSynchronize(k->ctx->stream);
-  void* ptrs[] = {k->d_disp, k->d_points, k->d_counts, k->d_seg, k->d_tab, k->d_speckle_ws, k->d_cost, k->d_sgm_ws};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (k->h_pinned) (void)hipHostFree(k->h_pinned);
-  delete k;
-}
-
-int svo_kfc_create(svo_ctx* ctx, const svo_cloud_params* params, int W, int H, int max_kf, SvoKfClouds** out) {
-  *out = nullptr;
-  svo_use_device(ctx);
-  svo_cloud_params prm = *params;
-  SVO_REQUIRE(ctx, (long)W * (long)H <= (1L << 24), "set_keyframe_clouds: width*height must be at most 2^24");
-  if (prm.max_points <= 0) prm.max_points = W * H;
-  SVO_REQUIRE(ctx, prm.step >= 1, "set_keyframe_clouds: step must be at least 1");
-  if (max_kf == 0) max_kf = ctx->lim.max_batch;
-  SVO_REQUIRE(ctx, max_kf >= 1 && max_kf <= 65535, "set_keyframe_clouds: max_keyframes_per_call must be 0 or 1..65535");
-  SvoKfClouds* k = new (std::nothrow) SvoKfClouds();
-  if (!k) return SVO_ERR_HIP;
-  k->ctx = ctx; k->prm = prm; k->W = W; k->H = H; k->max_kf = max_kf;
-  const size_t px = (size_t)W * H, n = (size_t)max_kf;
-  hipError_t e = hipMalloc((void**)&k->d_disp, n * px * sizeof(int16_t));
-  if (e == hipSuccess) e = hipMalloc((void**)&k->d_points, n * (size_t)prm.max_points * sizeof(svo_cloud_point));
-  if (e == hipSuccess) e = hipMalloc((void**)&k->d_counts, n * 2 * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc((void**)&k->d_seg, n * (size_t)svo_k_cloud_chunks(W, H, prm.step) * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc((void**)&k->d_tab, n * sizeof(SvoCloudPair));
-  if (e == hipSuccess) e = hipHostMalloc(&k->h_pinned, n * (sizeof(SvoCloudPair) + 2 * sizeof(int)), hipHostMallocDefault);
-  if (e != hipSuccess) {
-    ctx->err = std::string("set_keyframe_clouds: allocation failed: ") + hipGetErrorString(e);
-    svo_kfc_destroy(k);
-    return SVO_ERR_HIP;
-  }
-  *out = k;
-  return SVO_OK;
-}
-
-const svo_cloud_params* svo_kfc_params(const SvoKfClouds* k) { return &k->prm; }
-int svo_kfc_max_keyframes(const SvoKfClouds* k) { return k->max_kf; }
-void svo_kfc_clear(SvoKfClouds* k) { k->table.clear(); }
-const svo_speckle_params* svo_kfc_speckle(const SvoKfClouds* k) { return k->speckle_on ? &k->speckle : nullptr; }
-
-int svo_kfc_set_speckle(SvoKfClouds* k, const svo_speckle_params* prm) {
-  svo_ctx* ctx = k->ctx;
-  svo_use_device(ctx);
-  if (!prm) {
-    SVO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (k->d_speckle_ws) (void)hipFree(k->d_speckle_ws);
-    k->d_speckle_ws = nullptr;
-    k->speckle_on = false;
-    return SVO_OK;
-  }
-  const int rc = svo_speckle_check(ctx, k->W, k->H, k->max_kf, prm);
-  if (rc) return rc;
-  if (!k->d_speckle_ws) {
-    const hipError_t e = hipMalloc(&k->d_speckle_ws, svo_speckle_workspace_bytes(k->W, k->H, k->max_kf));
-    if (e != hipSuccess) {
-      k->d_speckle_ws = nullptr;
-      ctx->err = std::string("set_keyframe_speckle_filter: allocation failed: ") + hipGetErrorString(e);
-      return SVO_ERR_HIP;
-    }
-  }
-  k->speckle = *prm;
-  k->speckle_on = true;
-  return SVO_OK;
-}
-
-const svo_lr_check_params* svo_kfc_lr_check(const SvoKfClouds* k) { return k->lr_on ? &k->lr : nullptr; }
-
-int svo_kfc_set_lr_check(SvoKfClouds* k, const svo_lr_check_params* prm) {
-  svo_ctx* ctx = k->ctx;
-  svo_use_device(ctx);
-  if (!prm) {
-    SVO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (k->d_cost) (void)hipFree(k->d_cost);
-    k->d_cost = nullptr;
-    k->lr_on = false;
-    return SVO_OK;
-  }
-  const int rc = svo_lr_check_check(ctx, k->W, k->H, k->max_kf, prm);
-  if (rc) return rc;
-  if (!k->d_cost) {
-    const hipError_t e = hipMalloc((void**)&k->d_cost, sizeof(uint16_t) * (size_t)k->W * (size_t)k->H * (size_t)k->max_kf);
-    if (e != hipSuccess) {
-      k->d_cost = nullptr;
-      ctx->err = std::string("set_keyframe_lr_check: allocation failed: ") + hipGetErrorString(e);
-      return SVO_ERR_HIP;
-    }
-  }
-  k->lr = *prm;
-  k->lr_on = true;
-  return SVO_OK;
-}
-
-const svo_sgm_params* svo_kfc_sgm(const SvoKfClouds* k) { return k->sgm_on ? &k->sgm : nullptr; }
-
-int svo_kfc_set_sgm(SvoKfClouds* k, const svo_sgm_params* prm) {
-  svo_ctx* ctx = k->ctx;
-  svo_use_device(ctx);
-  if (!prm) {
-    SVO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (k->d_sgm_ws) (void)hipFree(k->d_sgm_ws);
-    k->d_sgm_ws = nullptr;
-    k->sgm_on = false;
-    return SVO_OK;
-  }
-  const int nd = svo_ref::STEREO_NUM_DISPARITIES, bs = svo_ref::STEREO_BLOCK_SIZE;
-  const int rc = svo_sgm_check(ctx, k->W, k->H, nd, bs, SVO_SGM_KEYFRAME_SUB_BATCH, prm);
-  if (rc) return rc;
-  if (!k->d_sgm_ws) {
-    const hipError_t e = hipMalloc(&k->d_sgm_ws, svo_sgm_workspace_bytes(k->W, k->H, nd, bs, SVO_SGM_KEYFRAME_SUB_BATCH));
-    if (e != hipSuccess) {
-      k->d_sgm_ws = nullptr;
-      ctx->err = std::string("set_keyframe_sgm: allocation failed: ") + hipGetErrorString(e);
-      return SVO_ERR_HIP;
-    }
-  }
-  k->sgm = *prm;
-  k->sgm_on = true;
-  return SVO_OK;
-}
-
-int svo_kfc_run(SvoKfClouds* k, const svo_camera_info* cam, const SvoCloudPair* pairs, const int* frame, const int* lane, int n) {
-  svo_ctx* ctx = k->ctx;
-  k->table.clear();
-  if (n <= 0) return SVO_OK;
-  if (n > k->max_kf) {
-    ctx->err = "keyframe clouds: " + std::to_string(n) + " keyframes in this call, max_keyframes_per_call is " + std::to_string(k->max_kf) +
-               " (no cloud was produced; the frame results are complete)";
-    return SVO_ERR_CAPACITY;
-  }
-  svo_cloud_params one{};
-  one.step = 1; one.max_points = 1;
-  int rc = cloud_check(ctx, k->W, k->H, k->W, cam, &one);
-  if (rc) return rc;
-  hipStream_t st = ctx->stream;
-  SvoCloudPair* h_tab = static_cast<SvoCloudPair*>(k->h_pinned);
-  int* h_counts = reinterpret_cast<int*>(h_tab + k->max_kf);
-  memcpy(h_tab, pairs, sizeof(SvoCloudPair) * (size_t)n);
-  SVO_HIP_CHECK(ctx, hipMemcpyAsync(k->d_tab, h_tab, sizeof(SvoCloudPair) * (size_t)n, hipMemcpyHostToDevice, st));
-  SvoDensePairs src{nullptr, nullptr, 0, k->d_tab};
-  if (k->sgm_on) {  // the matching sequence per sub-batch: the one workspace is reused, the launches are ordered by the stream
-    const size_t px = (size_t)k->W * (size_t)k->H;
-    for (int b0 = 0; b0 < n; b0 += SVO_SGM_KEYFRAME_SUB_BATCH) {
-      const int nb = n - b0 < SVO_SGM_KEYFRAME_SUB_BATCH ? n - b0 : SVO_SGM_KEYFRAME_SUB_BATCH;
-      SvoDensePairs sub{nullptr, nullptr, 0, k->d_tab + b0};
-      rc = svo_k_stereo_sgm(ctx, sub, nb, k->W, k->H, k->W, svo_ref::STEREO_NUM_DISPARITIES, svo_ref::STEREO_BLOCK_SIZE, &k->sgm, k->d_sgm_ws,
-                            k->d_disp + (size_t)b0 * px, k->lr_on ? k->d_cost + (size_t)b0 * px : nullptr);
-      if (rc) return rc;
-    }
-  } else {
-    rc = svo_k_stereo_dense_batch(ctx, src, n, k->W, k->H, k->W, svo_ref::STEREO_NUM_DISPARITIES, svo_ref::STEREO_BLOCK_SIZE, k->d_disp,
-                                  k->lr_on ? k->d_cost : nullptr);
-  }
-  if (rc) return rc;
-  if (k->lr_on) {  // same stream, before the speckle filter as in StereoBM::compute
-    rc = svo_k_lr_check(ctx, k->d_disp, k->d_cost, n, k->W, k->H, &k->lr, nullptr);
-    if (rc) return rc;
-  }
-  if (k->speckle_on) {  // same stream: the clouds below are those of the filtered maps
-    rc = svo_k_speckle(ctx, k->d_disp, n, k->W, k->H, &k->speckle, k->d_speckle_ws, nullptr);
-    if (rc) return rc;
-  }
-  rc = svo_k_cloud(ctx, k->d_disp, src, n, k->W, k->H, k->W, cam, nullptr, &k->prm, k->d_points, k->d_counts, k->d_seg);
-  if (rc) return rc;
-  SVO_HIP_CHECK(ctx, hipMemcpyAsync(h_counts, k->d_counts, sizeof(int) * 2 * (size_t)n, hipMemcpyDeviceToHost, st));
-  SVO_HIP_CHECK(ctx, hipStreamSynchronize(st));
-  k->table.resize((size_t)n);
-  for (int i = 0; i < n; ++i) {
-    svo_keyframe_cloud& t = k->table[(size_t)i];
-    t.frame = frame[i]; t.lane = lane ? lane[i] : 0;
-    t.n_total = h_counts[2 * i]; t.n_stored = h_counts[2 * i + 1];
-    t.dev = k->d_points + (size_t)i * (size_t)k->prm.max_points;
-  }
-  return SVO_OK;
-}
-
-int svo_kfc_table(SvoKfClouds* k, int* n, const svo_keyframe_cloud** table) {
-  *n = (int)k->table.size();
-  if (table) *table = k->table.empty() ? nullptr : k->table.data();
-  return SVO_OK;
-}
-
-int svo_kfc_copy(SvoKfClouds* k, int i, svo_cloud_point* host, int capacity) {
-  svo_ctx* ctx = k->ctx;
-  svo_use_device(ctx);
-  SVO_REQUIRE(ctx, i >= 0 && i < (int)k->table.size() && capacity >= 0 && (host || capacity == 0), "copy_keyframe_cloud: no such entry, or null buffer");
-  const int m = k->table[(size_t)i].n_stored < capacity ? k->table[(size_t)i].n_stored : capacity;
-  if (m > 0) {
-    SVO_HIP_CHECK(ctx, hipMemcpyAsync(host, k->table[(size_t)i].dev, sizeof(svo_cloud_point) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-    SVO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return SVO_OK;
-}
-
-int svo_kfc_disparity(SvoKfClouds* k, int i, const int16_t** dev) {
-  svo_ctx* ctx = k->ctx;
-  SVO_REQUIRE(ctx, dev, "keyframe_disparity: null dev");
-  *dev = nullptr;
-  SVO_REQUIRE(ctx, i >= 0 && i < (int)k->table.size(), "keyframe_disparity: no such entry");
-  *dev = k->d_disp + (size_t)i * (size_t)k->W * (size_t)k->H;
-  return SVO_OK;
-}
-
-int svo_kfc_copy_disparity(SvoKfClouds* k, int i, int16_t* host) {
-  svo_ctx* ctx = k->ctx;
-  svo_use_device(ctx);
-  SVO_REQUIRE(ctx, host, "copy_keyframe_disparity: null buffer");
-  const int16_t* dev = nullptr;
-  const int rc = svo_kfc_disparity(k, i, &dev);
-  if (rc) return rc;
-  SVO_HIP_CHECK(ctx, hipMemcpyAsync(host, dev, sizeof(int16_t) * (size_t)k->W * (size_t)k->H, hipMemcpyDeviceToHost, ctx->stream));
-  SVO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return SVO_OK;
 }

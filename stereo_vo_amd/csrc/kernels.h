@@ -92,44 +92,42 @@ struct SvoDensePairs {
 // cost16 != null: the cost form of the kernel, which also writes the winner's SAD per pixel (0xFFFF where the map is FILTERED)
 int svo_k_stereo_dense_batch(svo_ctx* ctx, const SvoDensePairs& src, int batch, int W, int H, int stride, int ndisp, int block, int16_t* disp16,
                              uint16_t* cost16 = nullptr);
-int svo_k_cloud_chunks(int W, int H, int step);  // ints of `seg` per image
 int svo_k_cloud(svo_ctx* ctx, const int16_t* disp16, const SvoDensePairs& src, int batch, int W, int H, int stride, const svo_camera_info* cam,
-                const float* pose16, const svo_cloud_params* prm, svo_cloud_point* points, int* counts, int* seg);
-// speckle filter (csrc/speckle.hip): the four launches over `batch` tight maps, in place; workspace: svo_speckle_workspace_bytes;
-// n_removed: batch device ints or null.  max_size == 0 launches nothing.  svo_speckle_check: the argument rules, with messages.
-int svo_speckle_check(svo_ctx* ctx, int W, int H, int batch, const svo_speckle_params* prm);
+                const float* pose16, const svo_cloud_params* prm, svo_cloud_point* points, int* counts, int* seg);  // seg: cloud_chunks ints per image
+// The argument rules of everything from here to the keyframe clouds, their messages, the buffer sizes and the launch geometry are
+// host/dense_args.h (plain C++, walked on a CPU by tests/sanitize/dense_args_test.cpp); the svo_k_* below trust their arguments.
+// speckle filter (csrc/speckle.hip): the four launches over `batch` tight maps, in place; workspace: speckle_workspace_bytes;
+// n_removed: batch device ints or null.  max_size == 0 launches nothing.
 int svo_k_speckle(svo_ctx* ctx, int16_t* disp16, int batch, int W, int H, const svo_speckle_params* prm, void* workspace, int* n_removed);
 // left-right check (csrc/lr_check.hip): one launch over `batch` tight maps, in place, from the winner's SAD per pixel;
-// n_removed: batch device ints or null.  svo_lr_check_check: the argument rules, with messages.
-int svo_lr_check_check(svo_ctx* ctx, int W, int H, int batch, const svo_lr_check_params* prm);
+// n_removed: batch device ints or null.
 int svo_k_lr_check(svo_ctx* ctx, int16_t* disp16, const uint16_t* cost16, int batch, int W, int H, const svo_lr_check_params* prm, int* n_removed);
 // semi-global matching (csrc/sgm.hip): fill, cost volume and the four path launches over `batch` pairs as ONE profile bracket;
-// workspace: svo_sgm_workspace_bytes; cost16 may be null.  svo_sgm_check: the argument rules (params, shape), with messages.
-int svo_sgm_check(svo_ctx* ctx, int W, int H, int ndisp, int block, int batch, const svo_sgm_params* prm);
+// workspace: sgm_workspace_bytes; cost16 may be null.
 int svo_k_stereo_sgm(svo_ctx* ctx, const SvoDensePairs& src, int batch, int W, int H, int stride, int ndisp, int block,
                      const svo_sgm_params* prm, void* workspace, int16_t* disp16, uint16_t* cost16);
-// The keyframe clouds of one pipeline or one group: every buffer allocated once by create; run() = one dense launch (with
-// svo_kfc_set_sgm: the semi-global matching sequence per sub-batch of SVO_SGM_KEYFRAME_SUB_BATCH pairs instead) + (with
-// svo_kfc_set_lr_check) the left-right check + (with svo_kfc_set_speckle) the speckle filter's launches + one cloud launch sequence over the given pairs on the context's stream,
-// then waits and fills the table.
+// The keyframe clouds of one pipeline or one group (host/keyframe_clouds.cpp): every buffer allocated once by create; run() = one
+// dense launch (with svo_kfc_set_sgm: the semi-global matching sequence per sub-batch of SVO_SGM_KEYFRAME_SUB_BATCH pairs instead)
+// + (with svo_kfc_set_lr_check) the left-right check + (with svo_kfc_set_speckle) the speckle filter's launches + one cloud launch
+// sequence over the given pairs on the context's stream, then waits and fills the table.
 struct SvoKfClouds;
 int svo_kfc_create(svo_ctx* ctx, const svo_cloud_params* params, int W, int H, int max_keyframes, SvoKfClouds** out);
 void svo_kfc_destroy(SvoKfClouds* k);
+// *slot (may be null) gives way to a fresh object for these parameters, and the switches that were on are carried over.  On any
+// failure *slot stays as it is and the fresh object is destroyed.
+int svo_kfc_replace(svo_ctx* ctx, SvoKfClouds** slot, const svo_cloud_params* params, int W, int H, int max_keyframes);
 const svo_cloud_params* svo_kfc_params(const SvoKfClouds* k);  // as resolved by create (max_points > 0)
 int svo_kfc_max_keyframes(const SvoKfClouds* k);
 void svo_kfc_clear(SvoKfClouds* k);
-// the speckle filter between the dense launch and the clouds: its work space for max_keyframes maps is allocated by the first
-// non-null call and freed with the object or by a null call.  svo_kfc_speckle: the parameters in force, or null.
+// The three switches, one pattern: a non-null call checks the parameters, allocates the stage's buffer if this is the first, and
+// switches the stage on; a null call waits for the stream, frees the buffer and switches it off.
+//   speckle : the filter between the matcher and the clouds; its work space for max_keyframes maps
+//   lr_check: the check between the matcher and the speckle filter; the cost maps for max_keyframes maps.  While it is on, run()
+//             launches the cost form of the dense kernel (or of the semi-global matching)
+//   sgm     : semi-global matching instead of the dense launch; the workspace for SVO_SGM_KEYFRAME_SUB_BATCH pairs
 int svo_kfc_set_speckle(SvoKfClouds* k, const svo_speckle_params* prm);
-const svo_speckle_params* svo_kfc_speckle(const SvoKfClouds* k);
-// the left-right check between the dense launch and the speckle filter, likewise: the cost maps for max_keyframes maps are
-// allocated by the first non-null call; while it is on, run() launches the cost form of the dense kernel
 int svo_kfc_set_lr_check(SvoKfClouds* k, const svo_lr_check_params* prm);
-const svo_lr_check_params* svo_kfc_lr_check(const SvoKfClouds* k);
-// semi-global matching instead of the dense launch, likewise: the workspace for SVO_SGM_KEYFRAME_SUB_BATCH pairs is allocated by
-// the first non-null call; with the left-right check on, its cost form feeds the check
 int svo_kfc_set_sgm(SvoKfClouds* k, const svo_sgm_params* prm);
-const svo_sgm_params* svo_kfc_sgm(const SvoKfClouds* k);
 int svo_kfc_run(SvoKfClouds* k, const svo_camera_info* cam, const SvoCloudPair* pairs, const int* frame, const int* lane, int n);
 int svo_kfc_table(SvoKfClouds* k, int* n, const svo_keyframe_cloud** table);
 int svo_kfc_copy(SvoKfClouds* k, int i, svo_cloud_point* host, int capacity);

@@ -13,13 +13,13 @@
 // for the value), which fits the 64 KB every kernel gets without asking up to SVO_LR_CHECK_MAX_WIDTH; a key whose cost is 0xFFFF
 // cannot equal the empty key 0xFFFFFFFF because x < 0xFFFF at that width.  Votes of adjacent x go to adjacent columns except at
 // disparity steps, so the atomics of a wavefront fall on distinct banks except where pixels truly collide.
+#include "dense_args.h"
 #include "kernels.h"
 
 namespace {
 constexpr int LR_T = 256;
 constexpr int LR_FILTERED = -16;
 constexpr unsigned LR_EMPTY = 0xFFFFFFFFu;
-static_assert(6 * SVO_LR_CHECK_MAX_WIDTH <= 64 * 1024 - 64, "key and row must fit the LDS granted without a request");
 static_assert(SVO_LR_CHECK_MAX_WIDTH < 0xFFFF, "x must not reach 0xFFFF: (0xFFFF << 16) | x would be the empty key");
 
 struct LrCheckArgs {
@@ -78,16 +78,6 @@ __global__ __launch_bounds__(LR_T) void lr_check_kernel(LrCheckArgs a) {
 }
 
 // ----------------------------------------------------------------------------- host side
-int svo_lr_check_check(svo_ctx* ctx, int W, int H, int batch, const svo_lr_check_params* prm) {
-  SVO_REQUIRE(ctx, W >= 1, "lr_check: width must be at least 1");
-  SVO_REQUIRE(ctx, H >= 1, "lr_check: height must be at least 1");
-  SVO_REQUIRE(ctx, W <= SVO_LR_CHECK_MAX_WIDTH, "lr_check: width exceeds SVO_LR_CHECK_MAX_WIDTH (the row and its keys live in LDS)");
-  SVO_REQUIRE(ctx, batch >= 1 && batch <= 65535, "lr_check: batch outside 1..65535");
-  SVO_REQUIRE(ctx, prm, "lr_check: null params");
-  SVO_REQUIRE(ctx, prm->max_diff16 >= 0, "lr_check: max_diff16 must not be negative");
-  return SVO_OK;
-}
-
 int svo_k_lr_check(svo_ctx* ctx, int16_t* disp16, const uint16_t* cost16, int batch, int W, int H, const svo_lr_check_params* prm,
                    int* n_removed) {
   LrCheckArgs a{};
@@ -95,7 +85,7 @@ int svo_k_lr_check(svo_ctx* ctx, int16_t* disp16, const uint16_t* cost16, int ba
   a.W = W; a.H = H; a.max_diff = prm->max_diff16;
   SvoProfScope prof(ctx, SVO_PROF_LR_CHECK);
   if (n_removed) SVO_HIP_CHECK(ctx, hipMemsetAsync(n_removed, 0, sizeof(int) * (size_t)batch, ctx->stream));
-  hipLaunchKernelGGL(lr_check_kernel, dim3((unsigned)H, (unsigned)batch), dim3(LR_T), 6 * (size_t)W, ctx->stream, a);
+  hipLaunchKernelGGL(lr_check_kernel, dim3((unsigned)H, (unsigned)batch), dim3(LR_T), lr_check_lds(W), ctx->stream, a);
   SVO_HIP_CHECK(ctx, hipGetLastError());
   return SVO_OK;
 }
@@ -106,8 +96,7 @@ extern "C" int svo_disparity_lr_check_batch_dev(svo_ctx* ctx, int16_t* disp16, c
   svo_use_device(ctx);
   SVO_REQUIRE(ctx, disp16, "lr_check: null disp16");
   SVO_REQUIRE(ctx, cost16, "lr_check: null cost16");
-  const int rc = svo_lr_check_check(ctx, width, height, batch, params);
-  if (rc) return rc;
+  DENSE_CHECK(ctx, lr_check_check(width, height, batch, params, &err));
   return svo_k_lr_check(ctx, disp16, cost16, batch, width, height, params, n_removed);
 }
 
@@ -117,8 +106,7 @@ extern "C" int svo_disparity_lr_check(svo_ctx* ctx, int16_t* disp16, const uint1
   svo_use_device(ctx);
   SVO_REQUIRE(ctx, disp16, "lr_check: null disp16");
   SVO_REQUIRE(ctx, cost16, "lr_check: null cost16");
-  int rc = svo_lr_check_check(ctx, width, height, 1, params);
-  if (rc) return rc;
+  DENSE_CHECK(ctx, lr_check_check(width, height, 1, params, &err));
   SvoScratch s(ctx);
   const size_t px = (size_t)width * (size_t)height;
   int16_t* dD = s.take<int16_t>(px);
@@ -128,7 +116,7 @@ extern "C" int svo_disparity_lr_check(svo_ctx* ctx, int16_t* disp16, const uint1
   hipStream_t st = ctx->stream;
   SVO_HIP_CHECK(ctx, hipMemcpyAsync(dD, disp16, px * sizeof(int16_t), hipMemcpyHostToDevice, st));
   SVO_HIP_CHECK(ctx, hipMemcpyAsync(dC, cost16, px * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-  rc = svo_k_lr_check(ctx, dD, dC, 1, width, height, params, dN);
+  const int rc = svo_k_lr_check(ctx, dD, dC, 1, width, height, params, dN);
   if (rc) return rc;
   SVO_HIP_CHECK(ctx, hipMemcpyAsync(disp16, dD, px * sizeof(int16_t), hipMemcpyDeviceToHost, st));
   int n = 0;

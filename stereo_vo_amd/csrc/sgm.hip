@@ -21,11 +21,8 @@
 
 namespace {
 constexpr int SGM_FILTERED = -16;
-constexpr int SGM_SP = DT_PIX + 2;     // u16 pitch of one SAD plane in LDS: 257 dwords, so the planes of one pixel fall on 64 different banks
-constexpr int SGM_LDS_MAX = (int)sizeof(unsigned short) * (MAX_NDISP + 1) * SGM_SP;  // 66,820 B
 constexpr int SGM_BIG = 1 << 29;       // "no value": above every L (<= 60,109) and every S << 6 | i (< 2^24), + p1 / p2 stays in int32
 constexpr int SGM_PF = 4;              // path steps whose loads are in flight ahead of the arithmetic
-constexpr int SGM_T = 256;
 
 __device__ __forceinline__ const uint8_t* sgm_image(const SvoDensePairs& s, int z, int eye) {
   if (s.tab) return eye ? s.tab[z].right : s.tab[z].left;
@@ -43,24 +40,6 @@ struct SgmArgs {
   int16_t* out;    // batch x H x W
   uint16_t* cost;  // batch x H x W or null
 };
-
-struct SgmLayout { size_t vol, sum, tex, total; };
-inline size_t sgm_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// false: a shape svo_stereo_sgm_batch_dev refuses
-bool sgm_layout(int W, int H, int ndisp, int block, int batch, SgmLayout* l) {
-  if (W < 3 || H < 3 || batch < 1 || batch > 65535 || ndisp < 16 || ndisp > MAX_NDISP || ndisp % 16 || block < 5 || block > MAX_BLOCK ||
-      !(block & 1) || (long)W * (long)H > (1L << 30))
-    return false;
-  const long vw = (long)W - block - ndisp + 2, vh = (long)H - block + 1;
-  const size_t px = (vw > 0 && vh > 0) ? (size_t)vw * (size_t)vh * (size_t)batch : 0;
-  l->vol = 0;
-  l->sum = sgm_up(px * ndisp * sizeof(uint16_t));
-  l->tex = l->sum + sgm_up(px * ndisp * sizeof(uint32_t));
-  l->total = l->tex + sgm_up(px * sizeof(uint16_t));
-  if (l->total < 256) l->total = 256;  // an empty rectangle needs nothing, but a workspace is never 0 bytes
-  return true;
-}
 }  // namespace
 
 __global__ __launch_bounds__(SGM_T) void sgm_fill_kernel(int16_t* __restrict__ out, uint16_t* __restrict__ cost, size_t n) {
@@ -245,44 +224,27 @@ __global__ __launch_bounds__(SGM_T) void sgm_path_kernel(SgmArgs a) {
 namespace {
 template <int DIR>
 void sgm_launch_path(const SgmArgs& a, int batch, hipStream_t st) {
-  const int lps = a.ndisp <= 16 ? 16 : a.ndisp <= 32 ? 32 : 64;
-  const int nlines = DIR < 2 ? a.VH : a.VW;
-  const dim3 grid((unsigned)svo_div_up(nlines, (SGM_T / 64) * (64 / lps)), (unsigned)batch);
+  const int lps = sgm_lps(a.ndisp);
+  const dim3 grid((unsigned)sgm_path_groups(DIR, SgmRect{a.rx0, a.ry0, a.VW, a.VH}, lps), (unsigned)batch);
   if (lps == 16) hipLaunchKernelGGL((sgm_path_kernel<DIR, 16>), grid, dim3(SGM_T), 0, st, a);
   else if (lps == 32) hipLaunchKernelGGL((sgm_path_kernel<DIR, 32>), grid, dim3(SGM_T), 0, st, a);
   else hipLaunchKernelGGL((sgm_path_kernel<DIR, 64>), grid, dim3(SGM_T), 0, st, a);
 }
-
-int sgm_params_check(svo_ctx* ctx, const svo_sgm_params* prm) {
-  SVO_REQUIRE(ctx, prm, "stereo_sgm: null params");
-  SVO_REQUIRE(ctx, prm->p1 >= 0, "stereo_sgm: p1 must not be negative");
-  SVO_REQUIRE(ctx, prm->p2 >= prm->p1, "stereo_sgm: p2 must be at least p1");
-  SVO_REQUIRE(ctx, prm->p2 <= SVO_SGM_MAX_P2, "stereo_sgm: p2 exceeds SVO_SGM_MAX_P2 (a path cost must fit 16 bits)");
-  return SVO_OK;
-}
 }  // namespace
-
-int svo_sgm_check(svo_ctx* ctx, int W, int H, int ndisp, int block, int batch, const svo_sgm_params* prm) {
-  const int rc = sgm_params_check(ctx, prm);
-  if (rc) return rc;
-  SgmLayout l;
-  SVO_REQUIRE(ctx, sgm_layout(W, H, ndisp, block, batch, &l), "stereo_sgm: width, height, num_disparities, block_size or batch outside the limits");
-  return SVO_OK;
-}
 
 int svo_k_stereo_sgm(svo_ctx* ctx, const SvoDensePairs& src, int batch, int W, int H, int stride, int ndisp, int block,
                      const svo_sgm_params* prm, void* workspace, int16_t* disp16, uint16_t* cost16) {
   SgmLayout l;
   if (!sgm_layout(W, H, ndisp, block, batch, &l)) { ctx->err = "stereo_sgm: shape outside the limits"; return SVO_ERR_INVALID; }
-  const size_t sad_lds = sizeof(unsigned short) * (size_t)(ndisp + 1) * SGM_SP;
+  const size_t sad_lds = sgm_sad_lds(ndisp);
   if ((int)sad_lds > ctx->sgm_lds_granted) {  // per context (= per device), as the dense kernels' grants
     SVO_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)sgm_volume_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SGM_LDS_MAX));
     ctx->sgm_lds_granted = SGM_LDS_MAX;
   }
   SgmArgs a{};
   a.src = src; a.W = W; a.H = H; a.stride = stride; a.ndisp = ndisp; a.block = block;
-  a.rx0 = ndisp - 1 + block / 2; a.ry0 = block / 2;
-  a.VW = W - block - ndisp + 2; a.VH = H - block + 1;
+  const SgmRect r = sgm_rect(W, H, ndisp, block);
+  a.rx0 = r.rx0; a.ry0 = r.ry0; a.VW = r.VW; a.VH = r.VH;
   a.p1 = prm->p1; a.p2 = prm->p2;
   uint8_t* const ws = static_cast<uint8_t*>(workspace);
   a.vol = reinterpret_cast<uint16_t*>(ws + l.vol);
@@ -304,16 +266,10 @@ int svo_k_stereo_sgm(svo_ctx* ctx, const SvoDensePairs& src, int batch, int W, i
   return SVO_OK;
 }
 
-extern "C" int svo_sgm_default_params(svo_sgm_params* p, int block_size) {
-  if (!p || block_size < 5 || block_size > MAX_BLOCK || !(block_size & 1)) return SVO_ERR_INVALID;
-  p->p1 = 2 * block_size * block_size;
-  p->p2 = 8 * block_size * block_size;
-  return SVO_OK;
-}
+extern "C" int svo_sgm_default_params(svo_sgm_params* p, int block_size) { return sgm_default_params(p, block_size); }
 
 extern "C" size_t svo_sgm_workspace_bytes(int width, int height, int num_disparities, int block_size, int batch) {
-  SgmLayout l;
-  return sgm_layout(width, height, num_disparities, block_size, batch, &l) ? l.total : 0;
+  return sgm_workspace_bytes(width, height, num_disparities, block_size, batch);
 }
 
 extern "C" int svo_stereo_sgm_batch_dev(svo_ctx* ctx, const uint8_t* left, const uint8_t* right, int batch, int width, int height,
@@ -322,13 +278,11 @@ extern "C" int svo_stereo_sgm_batch_dev(svo_ctx* ctx, const uint8_t* left, const
                                         uint16_t* cost16) {
   int rc = svo_stereo_check(ctx, left, right, width, height, row_stride, num_disparities, block_size);
   if (rc) return rc;
-  SVO_REQUIRE(ctx, disp16, "stereo_sgm: null disp16");
+  SVO_REQUIRE(ctx, disp16, STEREO_SGM_BATCH_TEXTS.null_disp);
   SVO_REQUIRE(ctx, workspace, "stereo_sgm: null workspace");
-  SVO_REQUIRE(ctx, batch >= 1 && batch <= ctx->lim.max_batch, "stereo_sgm: batch outside 1..max_batch");
-  SVO_REQUIRE(ctx, batch == 1 || image_stride >= (size_t)row_stride * (size_t)(height - 1) + (size_t)width, "stereo_sgm: images overlap (image_stride)");
-  rc = svo_sgm_check(ctx, width, height, num_disparities, block_size, batch, params);
-  if (rc) return rc;
-  SVO_REQUIRE(ctx, workspace_bytes >= svo_sgm_workspace_bytes(width, height, num_disparities, block_size, batch),
+  DENSE_CHECK(ctx, dense_batch_check(batch, ctx->lim.max_batch, width, height, row_stride, image_stride, STEREO_SGM_BATCH_TEXTS, &err));
+  DENSE_CHECK(ctx, sgm_check(width, height, num_disparities, block_size, batch, params, &err));
+  SVO_REQUIRE(ctx, workspace_bytes >= sgm_workspace_bytes(width, height, num_disparities, block_size, batch),
               "stereo_sgm: workspace_bytes is less than svo_sgm_workspace_bytes for this call");
   SvoDensePairs src{left, right, image_stride, nullptr};
   return svo_k_stereo_sgm(ctx, src, batch, width, height, row_stride, num_disparities, block_size, params, workspace, disp16, cost16);
@@ -338,23 +292,21 @@ extern "C" int svo_stereo_sgm(svo_ctx* ctx, const uint8_t* left, const uint8_t* 
                               int num_disparities, int block_size, const svo_sgm_params* params, int16_t* disp16, uint16_t* cost16) {
   int rc = svo_stereo_check(ctx, left, right, width, height, row_stride, num_disparities, block_size);
   if (rc) return rc;
-  SVO_REQUIRE(ctx, disp16, "stereo_sgm: null disp16");
-  rc = svo_sgm_check(ctx, width, height, num_disparities, block_size, 1, params);
-  if (rc) return rc;
+  SVO_REQUIRE(ctx, disp16, STEREO_SGM_BATCH_TEXTS.null_disp);
+  DENSE_CHECK(ctx, sgm_check(width, height, num_disparities, block_size, 1, params, &err));
   // the volume of one pair is far larger than the context's scratch: one allocation for this call, freed before it returns
   const size_t px = (size_t)width * (size_t)height;
-  const size_t ws_bytes = svo_sgm_workspace_bytes(width, height, num_disparities, block_size, 1);
-  const size_t o_l = ws_bytes, o_r = o_l + sgm_up(px), o_d = o_r + sgm_up(px), o_c = o_d + sgm_up(2 * px), total = o_c + sgm_up(2 * px);
+  const SgmOneShot o = sgm_one_shot(sgm_workspace_bytes(width, height, num_disparities, block_size, 1), px);
   uint8_t* d = nullptr;
-  SVO_HIP_CHECK(ctx, hipMalloc((void**)&d, total));
+  SVO_HIP_CHECK(ctx, hipMalloc((void**)&d, o.total));
   hipStream_t st = ctx->stream;
-  int16_t* dD = reinterpret_cast<int16_t*>(d + o_d);
-  uint16_t* dC = reinterpret_cast<uint16_t*>(d + o_c);
-  hipError_t e = hipMemcpy2DAsync(d + o_l, width, left, row_stride, width, height, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpy2DAsync(d + o_r, width, right, row_stride, width, height, hipMemcpyHostToDevice, st);
+  int16_t* dD = reinterpret_cast<int16_t*>(d + o.disp);
+  uint16_t* dC = reinterpret_cast<uint16_t*>(d + o.cost);
+  hipError_t e = hipMemcpy2DAsync(d + o.left, width, left, row_stride, width, height, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(d + o.right, width, right, row_stride, width, height, hipMemcpyHostToDevice, st);
   rc = SVO_OK;
   if (e == hipSuccess) {
-    SvoDensePairs src{d + o_l, d + o_r, px, nullptr};
+    SvoDensePairs src{d + o.left, d + o.right, px, nullptr};
     rc = svo_k_stereo_sgm(ctx, src, 1, width, height, width, num_disparities, block_size, params, d, dD, cost16 ? dC : nullptr);
   }
   if (e == hipSuccess && rc == SVO_OK) e = hipMemcpyAsync(disp16, dD, px * sizeof(int16_t), hipMemcpyDeviceToHost, st);

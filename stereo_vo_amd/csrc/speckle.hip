@@ -15,10 +15,10 @@
 // no acquire / release, no loop whose exit depends on another workgroup's progress.  A plain load of a label may be stale: a
 // label only ever decreases and every value it ever held is a pixel of the same component, so a stale value is a valid, merely
 // longer, way to the root.  What a launch must see of another launch's plain stores comes from the kernel boundary.
+#include "dense_args.h"
 #include "kernels.h"
 
 namespace {
-constexpr int SP_TW = SVO_SPECKLE_TILE_W, SP_TH = SVO_SPECKLE_TILE_H, SP_PIX = SP_TW * SP_TH, SP_T = 256;
 constexpr int SP_FILTERED = -16;
 constexpr unsigned SP_NONE = 0xFFFFFFFFu;
 static_assert(SP_TW == 64 && SP_PIX % SP_T == 0, "a tile row is one wavefront; whole passes of the workgroup over the tile");
@@ -170,24 +170,7 @@ __global__ __launch_bounds__(SP_T) void speckle_apply_kernel(SpeckleArgs a) {
 }
 
 // ----------------------------------------------------------------------------- host side
-static bool speckle_shape_ok(int W, int H, int batch) {
-  return W >= 1 && H >= 1 && (long)W * (long)H < (1L << 31) && batch >= 1 && batch <= 65535;
-}
-
-extern "C" size_t svo_speckle_workspace_bytes(int width, int height, int batch) {
-  if (!speckle_shape_ok(width, height, batch)) return 0;
-  return 2 * sizeof(unsigned) * (size_t)width * (size_t)height * (size_t)batch;  // labels, then counts
-}
-
-int svo_speckle_check(svo_ctx* ctx, int W, int H, int batch, const svo_speckle_params* prm) {
-  SVO_REQUIRE(ctx, W >= 1 && H >= 1, "speckle_filter: width and height must be at least 1");
-  SVO_REQUIRE(ctx, (long)W * (long)H < (1L << 31), "speckle_filter: width*height must be below 2^31");
-  SVO_REQUIRE(ctx, batch >= 1 && batch <= 65535, "speckle_filter: batch outside 1..65535");
-  SVO_REQUIRE(ctx, prm, "speckle_filter: null params");
-  SVO_REQUIRE(ctx, prm->max_size >= 0, "speckle_filter: max_size must not be negative");
-  SVO_REQUIRE(ctx, prm->max_diff16 >= 0, "speckle_filter: max_diff16 must not be negative");
-  return SVO_OK;
-}
+extern "C" size_t svo_speckle_workspace_bytes(int width, int height, int batch) { return speckle_workspace_bytes(width, height, batch); }
 
 int svo_k_speckle(svo_ctx* ctx, int16_t* disp16, int batch, int W, int H, const svo_speckle_params* prm, void* workspace, int* n_removed) {
   if (prm->max_size == 0) return SVO_OK;  // no component has 0 pixels: the identity, and no launch
@@ -197,17 +180,15 @@ int svo_k_speckle(svo_ctx* ctx, int16_t* disp16, int batch, int W, int H, const 
   a.label = static_cast<unsigned*>(workspace);
   a.count = a.label + A * (size_t)batch;
   a.n_removed = n_removed;
-  a.W = W; a.H = H; a.tiles_x = svo_div_up(W, SP_TW);
+  const SpeckleGrid g = speckle_grid(W, H);
+  a.W = W; a.H = H; a.tiles_x = g.tiles_x;
   a.max_size = prm->max_size; a.max_diff = prm->max_diff16;
-  const int tiles_y = svo_div_up(H, SP_TH);
-  a.n_vert = (unsigned)(a.tiles_x - 1) * (unsigned)H;
-  a.n_seam = a.n_vert + (unsigned)(tiles_y - 1) * (unsigned)W;  // < A / 64 + A / 16
-  const unsigned px_blocks = (unsigned)((A + SP_T - 1) / SP_T);
+  a.n_vert = g.n_vert; a.n_seam = g.n_seam;
   SvoProfScope prof(ctx, SVO_PROF_SPECKLE);
-  hipLaunchKernelGGL(speckle_tile_kernel, dim3((unsigned)a.tiles_x * (unsigned)tiles_y, batch), dim3(SP_T), 0, ctx->stream, a);
+  hipLaunchKernelGGL(speckle_tile_kernel, dim3((unsigned)g.tiles_x * (unsigned)g.tiles_y, batch), dim3(SP_T), 0, ctx->stream, a);
   if (a.n_seam) hipLaunchKernelGGL(speckle_seam_kernel, dim3((a.n_seam + SP_T - 1) / SP_T, batch), dim3(SP_T), 0, ctx->stream, a);
-  hipLaunchKernelGGL(speckle_count_kernel, dim3(px_blocks, batch), dim3(SP_T), 0, ctx->stream, a);
-  hipLaunchKernelGGL(speckle_apply_kernel, dim3(px_blocks, batch), dim3(SP_T), 0, ctx->stream, a);
+  hipLaunchKernelGGL(speckle_count_kernel, dim3(g.px_blocks, batch), dim3(SP_T), 0, ctx->stream, a);
+  hipLaunchKernelGGL(speckle_apply_kernel, dim3(g.px_blocks, batch), dim3(SP_T), 0, ctx->stream, a);
   SVO_HIP_CHECK(ctx, hipGetLastError());
   return SVO_OK;
 }
@@ -218,8 +199,7 @@ extern "C" int svo_disparity_speckle_filter_batch_dev(svo_ctx* ctx, int16_t* dis
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
   SVO_REQUIRE(ctx, disp16, "speckle_filter: null disp16");
-  const int rc = svo_speckle_check(ctx, width, height, batch, params);
-  if (rc) return rc;
+  DENSE_CHECK(ctx, speckle_check(width, height, batch, params, &err));
   if (params->max_size == 0) return SVO_OK;
   SVO_REQUIRE(ctx, workspace && ((uintptr_t)workspace & 3) == 0, "speckle_filter: workspace is null or not 4-byte aligned");
   SVO_REQUIRE(ctx, workspace_bytes >= svo_speckle_workspace_bytes(width, height, batch),
@@ -232,8 +212,7 @@ extern "C" int svo_disparity_speckle_filter(svo_ctx* ctx, int16_t* disp16, int w
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
   SVO_REQUIRE(ctx, disp16, "speckle_filter: null disp16");
-  int rc = svo_speckle_check(ctx, width, height, 1, params);
-  if (rc) return rc;
+  DENSE_CHECK(ctx, speckle_check(width, height, 1, params, &err));
   if (n_removed) *n_removed = 0;
   if (params->max_size == 0) return SVO_OK;
   SvoScratch s(ctx);
@@ -244,7 +223,7 @@ extern "C" int svo_disparity_speckle_filter(svo_ctx* ctx, int16_t* disp16, int w
   if (!dD || !dN || !dW) { ctx->err = "speckle_filter: the context's workspace is too small for this map (svo_limits.max_width / max_height)"; return SVO_ERR_CAPACITY; }
   hipStream_t st = ctx->stream;
   SVO_HIP_CHECK(ctx, hipMemcpyAsync(dD, disp16, px * sizeof(int16_t), hipMemcpyHostToDevice, st));
-  rc = svo_k_speckle(ctx, dD, 1, width, height, params, dW, dN);
+  const int rc = svo_k_speckle(ctx, dD, 1, width, height, params, dW, dN);
   if (rc) return rc;
   SVO_HIP_CHECK(ctx, hipMemcpyAsync(disp16, dD, px * sizeof(int16_t), hipMemcpyDeviceToHost, st));
   int n = 0;

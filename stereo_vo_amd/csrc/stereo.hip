@@ -390,11 +390,7 @@ __global__ __launch_bounds__(256) void stereo_dense_kernel(const uint8_t* __rest
 int svo_stereo_check(svo_ctx* ctx, const void* l, const void* r, int W, int H, int stride, int ndisp, int block) {
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
-  SVO_REQUIRE(ctx, l && r, "stereo: null image");
-  SVO_REQUIRE(ctx, W >= 3 && H >= 3 && W <= ctx->lim.max_width && H <= ctx->lim.max_height && stride >= W,
-              "stereo: image size outside limits");
-  SVO_REQUIRE(ctx, ndisp >= 16 && ndisp <= MAX_NDISP && ndisp % 16 == 0, "stereo: numDisparities must be 16..64, multiple of 16");
-  SVO_REQUIRE(ctx, block >= 5 && block <= MAX_BLOCK && (block & 1), "stereo: blockSize must be odd, 5..21");
+  DENSE_CHECK(ctx, stereo_shape_check(l, r, W, H, stride, ndisp, block, ctx->lim.max_width, ctx->lim.max_height, &err));
   return SVO_OK;
 }
 
@@ -474,7 +470,7 @@ extern "C" int svo_stereo_bm(svo_ctx* ctx, const uint8_t* left, const uint8_t* r
     SvoProfScope prof(ctx, SVO_PROF_STEREO_BM);
     hipLaunchKernelGGL(stereo_prefilter_kernel, g1, dim3(256), 0, st, dL, width, height, width, dLp);
     hipLaunchKernelGGL(stereo_prefilter_kernel, g1, dim3(256), 0, st, dR, width, height, width, dRp);
-    const size_t sad_lds = sizeof(unsigned short) * (size_t)(num_disparities + 1) * DT_PIX;  // <= 66,560 B
+    const size_t sad_lds = dense_sad_lds(num_disparities);  // <= 66,560 B
     SVO_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)stereo_dense_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sad_lds));
     hipLaunchKernelGGL(stereo_dense_kernel, dim3(svo_div_up(width, DT_W), svo_div_up(height, DT_H)), dim3(256), sad_lds, st, dLp,
                        dRp, width, height, num_disparities, block_size, dD);

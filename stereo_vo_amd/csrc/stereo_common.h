@@ -1,12 +1,13 @@
-// What the sparse / dense block matchers of stereo.hip and the batched dense matcher of dense.hip share: StereoBM's constants
-// (src/image_processor.cpp:173-176), the X-Sobel prefilter and the tile geometry of the dense kernels.
+// What the sparse / dense block matchers of stereo.hip, the batched dense matcher of dense.hip and sgm.hip share: StereoBM's
+// constants (src/image_processor.cpp:173-176) and the X-Sobel prefilter.  The limits MAX_NDISP / MAX_BLOCK and
+// the tile geometry of the dense kernels (DT_*) are host/dense_args.h's, with the argument rules.
 #ifndef SVO_STEREO_COMMON_H_
 #define SVO_STEREO_COMMON_H_
 #include "common.h"
+#include "dense_args.h"
 
 namespace {
 constexpr int CAP = 31, TEXTURE_THRESHOLD = 10, UNIQUENESS_RATIO = 15;
-constexpr int MAX_NDISP = 64, MAX_BLOCK = 21;
 
 __device__ __forceinline__ int pf_row(int y, int H) {
   if (y < 0) return H > 1 ? 1 : 0;
@@ -25,15 +26,6 @@ __device__ __forceinline__ int prefilter_at(Load I, int x, int y, int W, int H) 
 }
 }  // namespace
 
-// Dense kernels: workgroup = 64 columns x 8 rows of output (see stereo_dense_kernel).
-namespace {
-constexpr int DT_W = 64, DT_H = 8, DT_PIX = DT_W * DT_H;
-constexpr int DT_TH = DT_H + MAX_BLOCK - 1;         // 28 tile rows
-constexpr int DT_TWL = DT_W + MAX_BLOCK - 1;        // 84 left tile columns
-constexpr int DT_TWR = DT_TWL + MAX_NDISP;          // right tile columns
-constexpr int DT_SLOTS = 3;                         // disparity slots per pass
-}
-
-// argument limits of every StereoBM entry point (stereo.hip)
+// argument limits of every StereoBM entry point (stereo.hip): null context, device selection, then stereo_shape_check
 int svo_stereo_check(svo_ctx* ctx, const void* l, const void* r, int W, int H, int stride, int ndisp, int block);
 #endif  // SVO_STEREO_COMMON_H_

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "chain_math.h"
+#include "dense_args.h"
 #include "det_trig.h"
 #include "group_kernels.h"
 #include "group_lines.h"
@@ -1355,31 +1356,15 @@ extern "C" int svo_pipeline_group_set_keyframe_clouds(svo_pipeline_group* g, int
     bool same = false;
     if (g->kfc) {
       const svo_cloud_params* have = svo_kfc_params(g->kfc);
-      const int want_points = params->max_points > 0 ? params->max_points : g->prm.width * g->prm.height;
-      const int want_kf = max_keyframes_per_call ? max_keyframes_per_call : ctx->lim.max_batch;
+      const int want_points = kfc_max_points(params->max_points, g->prm.width, g->prm.height);
+      const int want_kf = kfc_max_keyframes(max_keyframes_per_call, ctx->lim.max_batch);
       same = have->step == params->step && have->min_disparity == params->min_disparity && have->max_points == want_points &&
              svo_kfc_max_keyframes(g->kfc) == want_kf;
     }
     SVO_REQUIRE(ctx, same || !others, "pipeline_group_set_keyframe_clouds: the lanes that have clouds on share one set of parameters and one bound");
     if (!same) {
-      SvoKfClouds* k = nullptr;
-      const int rc = svo_kfc_create(ctx, params, g->prm.width, g->prm.height, max_keyframes_per_call, &k);
+      const int rc = svo_kfc_replace(ctx, &g->kfc, params, g->prm.width, g->prm.height, max_keyframes_per_call);  // the switches that were on stay on
       if (rc) return rc;
-      // new buffers for other cloud parameters: a speckle filter that was on stays on
-      if (g->kfc && svo_kfc_speckle(g->kfc)) {
-        const int rs = svo_kfc_set_speckle(k, svo_kfc_speckle(g->kfc));
-        if (rs) { svo_kfc_destroy(k); return rs; }
-      }
-      if (g->kfc && svo_kfc_lr_check(g->kfc)) {  // and so does a left-right check
-        const int rs = svo_kfc_set_lr_check(k, svo_kfc_lr_check(g->kfc));
-        if (rs) { svo_kfc_destroy(k); return rs; }
-      }
-      if (g->kfc && svo_kfc_sgm(g->kfc)) {  // and semi-global matching
-        const int rs = svo_kfc_set_sgm(k, svo_kfc_sgm(g->kfc));
-        if (rs) { svo_kfc_destroy(k); return rs; }
-      }
-      svo_kfc_destroy(g->kfc);
-      g->kfc = k;
     }
   }
   for (int l = 0; l < g->n_lanes; ++l)

@@ -899,26 +899,10 @@ extern "C" int svo_pipeline_set_rectification(svo_pipeline* p, const svo_rectify
 extern "C" int svo_pipeline_set_keyframe_clouds(svo_pipeline* p, const svo_cloud_params* params, int max_keyframes_per_call) {
   if (!p) return SVO_ERR_INVALID;
   p->adjuster->wait();
-  SvoKfClouds* k = nullptr;
-  if (params) {
-    const int rc = svo_kfc_create(p->ctx, params, p->prm.width, p->prm.height, max_keyframes_per_call, &k);
-    if (rc) return rc;
-    // new buffers for other cloud parameters: a speckle filter that was on stays on
-    if (p->kfc && svo_kfc_speckle(p->kfc)) {
-      const int rs = svo_kfc_set_speckle(k, svo_kfc_speckle(p->kfc));
-      if (rs) { svo_kfc_destroy(k); return rs; }
-    }
-    if (p->kfc && svo_kfc_lr_check(p->kfc)) {  // and so does a left-right check
-      const int rs = svo_kfc_set_lr_check(k, svo_kfc_lr_check(p->kfc));
-      if (rs) { svo_kfc_destroy(k); return rs; }
-    }
-    if (p->kfc && svo_kfc_sgm(p->kfc)) {  // and semi-global matching
-      const int rs = svo_kfc_set_sgm(k, svo_kfc_sgm(p->kfc));
-      if (rs) { svo_kfc_destroy(k); return rs; }
-    }
-  }
+  // new buffers for other cloud parameters: the switches that were on stay on
+  if (params) return svo_kfc_replace(p->ctx, &p->kfc, params, p->prm.width, p->prm.height, max_keyframes_per_call);
   svo_kfc_destroy(p->kfc);
-  p->kfc = k;
+  p->kfc = nullptr;
   return SVO_OK;
 }
 

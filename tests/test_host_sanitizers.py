@@ -1,7 +1,8 @@
 """AddressSanitizer + UndefinedBehaviorSanitizer over the GPU-free host code of the product (the step control
 host/lm.cpp, the dense Cholesky, the KITTI-layout decoders, the track rasteriser, the synthetic renderer, and the three
 GPU-free pieces of the bundle adjuster: the sliding-window graph host/ba_graph.h, the problem layout host/ba_layout.h, the
-admission ledger host/ba_admission.h), on the CPU: GPU sanitizers are not available on the target pool, and these are the
+admission ledger host/ba_admission.h, and the argument rules, sizes and launch geometry of the dense keyframe chain
+host/dense_args.h), on the CPU: GPU sanitizers are not available on the target pool, and these are the
 pieces that parse files and index host arrays.  Every program is stand-alone (its own main); nothing is loaded into Python."""
 import os
 import struct
@@ -126,3 +127,11 @@ def test_ba_admission_ledger_within_and_across_processes(tmp_path):
     d = tmp_path / "table"
     d.mkdir()
     _run_sanitized(tmp_path, "ba_admission_test", "ba admission ok", str(d))
+
+
+def test_dense_args_rules_sizes_and_launch_geometry_at_their_boundaries(tmp_path):
+    """The dense keyframe chain's host logic (host/dense_args.h), walked on the CPU under ASan + UBSan: the StereoBM shape and batch
+    rules, the cloud, speckle, left-right and SGM rules, each accepted at its limit and refused one step beyond with its entry's
+    message; chunk, seam and path-grid counts against brute-force counts; the SGM workspace's regions aligned and disjoint, up to
+    2^30 pixels; the keyframe clouds' resolved parameters, buffer sizes and sub-batch split."""
+    _run_sanitized(tmp_path, "dense_args_test", "dense args ok")

@@ -230,6 +230,12 @@ def test_group_clouds_are_those_of_the_sgm_maps_with_a_rectified_lane(ctx):
     g.set_keyframe_speckle_filter(*SPECKLE)
     got, seen = run(True, True)
     assert got == plain and seen >= lanes
+    # the group's carry-over: max_points one below the default means new buffers (every cloud is far below either bound), and
+    # semi-global matching, the check and the speckle filter stay on: run() compares every cloud with the restatement of all three
+    g.set_keyframe_clouds(-1, api.CloudParams(1, 0.0, W * H - 1), lanes * batch)
+    g.reset()
+    got, seen = run(True, True)
+    assert got == plain and seen >= lanes
     g.reset()
     g.set_keyframe_sgm(on=False)
     got, seen = run(False, True)
