@@ -455,6 +455,32 @@ __device__ __forceinline__ void linearize_prefix(const BaDev& P, const ObsRec& R
   q.maxlen = maxlen;
 }
 
+// The bulk modes eliminate a landmark through the Cholesky factor of its damped block, Vd = L L^T: Z = (W s) L^-T by forward
+// substitution, Schur products -Z_i Z_t^T, g_red = -Z (L^-1 (g_p s)).  Their sums are in hardware order anyway; only the deterministic
+// mode is tied to the oracle's declared V^-1 (inv3_sym), whose cofactors lose on ill-conditioned blocks what the factor keeps: on
+// badly started windows the steps of the bulk modes were several times further from the exact one (tests/test_ba_ref.py) while they
+// formed V^-1, or the factor of V^-1, first.  r: the pivots' reciprocals; a non-positive pivot leaves 0 and that column of Z drops out.
+struct Chol3 { double l10, l20, l21, r0, r1, r2; };
+__device__ __forceinline__ Chol3 chol3(const double* V) {
+  Chol3 c = {0, 0, 0, 0, 0, 0};
+  if (V[0] > 0) {
+    c.r0 = 1.0 / sqrt(V[0]); c.l10 = V[3] * c.r0; c.l20 = V[6] * c.r0;
+    const double d1 = V[4] - c.l10 * c.l10;
+    if (d1 > 0) {
+      c.r1 = 1.0 / sqrt(d1); c.l21 = (V[7] - c.l20 * c.l10) * c.r1;
+      const double d2 = V[8] - c.l20 * c.l20 - c.l21 * c.l21;
+      if (d2 > 0) c.r2 = 1.0 / sqrt(d2);
+    }
+  }
+  return c;
+}
+// x = L^-1 w (equally: the row x with x L^T = w)
+__device__ __forceinline__ void chol3_fwd(const Chol3& c, const double* w, double* x) {
+  x[0] = w[0] * c.r0;
+  x[1] = (w[1] - c.l10 * x[0]) * c.r1;
+  x[2] = (w[2] - c.l20 * x[0] - c.l21 * x[1]) * c.r2;
+}
+
 // Pass A behind the prefix, bulk modes (hardware-order sums): into the workgroup's LDS image of payload1 (ds_add_f64),
 // lgp2 accumulates this lane's share of sum g_p^2.
 __device__ __forceinline__ void linearize_suffix_bulk(const BaDev& P, const ObsRec& R, const LinPre& q, double radius, int first_pass, double* sS, double* sGred,
@@ -479,7 +505,7 @@ __device__ __forceinline__ void linearize_suffix_bulk(const BaDev& P, const ObsR
     }
     if (lane == first) lgp2 += gp[0] * gp[0] + gp[1] * gp[1] + gp[2] * gp[2];
   }
-  double Vd[9], Vi[9], gps[3];
+  double Vd[9], gps[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     gps[a] = gp[a] * s[a];
@@ -488,24 +514,25 @@ __device__ __forceinline__ void linearize_suffix_bulk(const BaDev& P, const ObsR
   }
 #pragma unroll
   for (int a = 0; a < 3; ++a) Vd[4 * a] += fmin(fmax(Vd[4 * a], MIN_DIAG), MAX_DIAG) / radius;
-  inv3_sym(Vd, Vi);
-  double Ws[18], Y[18];
+  const Chol3 ch = chol3(Vd);
+  double h[3];
+  chol3_fwd(ch, gps, h);
+  double Z[18];
   const bool freep = active && k > 0;
   const int base = 6 * (k - 1);
 #pragma unroll
-  for (int a = 0; a < 6; ++a)
+  for (int a = 0; a < 6; ++a) {
+    double w[3];
 #pragma unroll
-    for (int b = 0; b < 3; ++b) Ws[3 * a + b] = freep ? (Jc[a] * Jp[b] + Jc[6 + a] * Jp[3 + b]) * s[b] : 0.0;
-#pragma unroll
-  for (int a = 0; a < 6; ++a)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) Y[3 * a + b] = Ws[3 * a] * Vi[b] + Ws[3 * a + 1] * Vi[3 + b] + Ws[3 * a + 2] * Vi[6 + b];
+    for (int b = 0; b < 3; ++b) w[b] = freep ? (Jc[a] * Jp[b] + Jc[6 + a] * Jp[3 + b]) * s[b] : 0.0;
+    chol3_fwd(ch, w, Z + 3 * a);
+  }
   if (freep) {
 #pragma unroll
     for (int a = 0; a < 6; ++a) {
       atomicAdd(&sGc[base + a], Jc[a] * r[0] + Jc[6 + a] * r[1]);
       atomicAdd(&sDU[base + a], Jc[a] * Jc[a] + Jc[6 + a] * Jc[6 + a]);
-      atomicAdd(&sGred[base + a], -(Y[3 * a] * gps[0] + Y[3 * a + 1] * gps[1] + Y[3 * a + 2] * gps[2]));
+      atomicAdd(&sGred[base + a], -(Z[3 * a] * h[0] + Z[3 * a + 1] * h[1] + Z[3 * a + 2] * h[2]));
 #pragma unroll
       for (int b = 0; b < 6; ++b) atomicAdd(&sS[(base + a) * n + base + b], Jc[a] * Jc[b] + Jc[6 + a] * Jc[6 + b]);
     }
@@ -513,17 +540,24 @@ __device__ __forceinline__ void linearize_suffix_bulk(const BaDev& P, const ObsR
   for (int t = 0; t < maxlen; ++t) {
     const int src = (first + t) & 63;
     const int kt = __shfl(k, src);
-    double Wt[18];
+    double Zt[18];
 #pragma unroll
-    for (int i = 0; i < 18; ++i) Wt[i] = shfl_d(Ws[i], src);
+    for (int i = 0; i < 18; ++i) Zt[i] = shfl_d(Z[i], src);
     if (freep && t < len && kt > 0 && src >= lane) {
+      // every unordered observation pair once, into the UPPER pose-pair block (what ba_payload1_out and the device step control
+      // read): transposed when this lane's pose is the later one (a landmark's observations need not be in pose order), and both
+      // ways into the diagonal block for two different observations by ONE pose
       const int bt = 6 * (kt - 1);
+      const bool swap = kt < k, twice = kt == k && src != lane;
+      const int o = swap ? bt * n + base : base * n + bt, sa = swap ? 1 : n, sb = swap ? n : 1;
 #pragma unroll
       for (int a = 0; a < 6; ++a)
 #pragma unroll
-        for (int b = 0; b < 6; ++b)
-          atomicAdd(&sS[(base + a) * n + bt + b],
-                    -(Y[3 * a] * Wt[3 * b] + Y[3 * a + 1] * Wt[3 * b + 1] + Y[3 * a + 2] * Wt[3 * b + 2]));
+        for (int b = 0; b < 6; ++b) {
+          const double v = -(Z[3 * a] * Zt[3 * b] + Z[3 * a + 1] * Zt[3 * b + 1] + Z[3 * a + 2] * Zt[3 * b + 2]);
+          atomicAdd(&sS[o + a * sa + b * sb], v);
+          if (twice) atomicAdd(&sS[o + b * n + a], v);
+        }
     }
   }
 }
@@ -2834,7 +2868,7 @@ __global__ __launch_bounds__(64 * LMC_MAX_WAVES) void ba_lm_compact_kernel(LmLan
 // ---------------------------------------------------------------------------------------------------
 // Bulk (non-deterministic) linearisation with the Schur products on the f64 matrix cores.
 //
-// For a landmark with V^-1 = Lc Lc^T (3x3 Cholesky) and Z_i = (W_i s) Lc (6x3 per observing pose), its whole
+// For a landmark with V = L L^T (3x3 Cholesky) and Z_i = (W_i s) L^-T (6x3 per observing pose), its whole
 // contribution to the reduced camera matrix is  -Z Z^T  with Z the (6 x poses) x 3 stack: one rank-3 update
 // of S.  S (n <= 128) is cut into 16x16 tiles; v_mfma_f64_16x16x4_f64 applies the update to one tile with
 // K = 3 of its 4 k-slots used.  A workgroup is 8 waves; the accumulators are shared by the workgroup, not
@@ -2959,7 +2993,7 @@ __global__ __launch_bounds__(512) void ba_linearize_mfma_kernel(BaDev P, double 
         }
         if (lane == first) lgp2 += gp[0] * gp[0] + gp[1] * gp[1] + gp[2] * gp[2];
       }
-      double Vd[9], Vi[9], gps[3];
+      double Vd[9], gps[3];
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         gps[a] = gp[a] * s[a];
@@ -2968,18 +3002,10 @@ __global__ __launch_bounds__(512) void ba_linearize_mfma_kernel(BaDev P, double 
       }
 #pragma unroll
       for (int a = 0; a < 3; ++a) Vd[4 * a] += fmin(fmax(Vd[4 * a], MIN_DIAG), MAX_DIAG) / radius;
-      inv3_sym(Vd, Vi);
-      // V^-1 = Lc Lc^T
-      double l00 = 0, l10 = 0, l20 = 0, l11 = 0, l21 = 0, l22 = 0;
-      if (Vi[0] > 0) {
-        l00 = sqrt(Vi[0]); l10 = Vi[3] / l00; l20 = Vi[6] / l00;
-        const double d1 = Vi[4] - l10 * l10;
-        if (d1 > 0) {
-          l11 = sqrt(d1); l21 = (Vi[7] - l20 * l10) / l11;
-          const double d2 = Vi[8] - l20 * l20 - l21 * l21;
-          if (d2 > 0) l22 = sqrt(d2);
-        }
-      }
+      // Vd = L L^T: Z = (W s) L^-T, g_red through the same factor (chol3 above)
+      const Chol3 ch = chol3(Vd);
+      double h[3];
+      chol3_fwd(ch, gps, h);
       const bool freep = active && k > 0;
       const int base = 6 * (k - 1);
       const unsigned long long flags = __ballot(active && lane == first);
@@ -2993,15 +3019,10 @@ __global__ __launch_bounds__(512) void ba_linearize_mfma_kernel(BaDev P, double 
         double w[3];
 #pragma unroll
         for (int b = 0; b < 3; ++b) w[b] = freep ? (Jc[a] * Jp[b] + Jc[6 + a] * Jp[3 + b]) * s[b] : 0.0;
-        Z[3 * a] = w[0] * l00 + w[1] * l10 + w[2] * l20;
-        Z[3 * a + 1] = w[1] * l11 + w[2] * l21;
-        Z[3 * a + 2] = w[2] * l22;
+        chol3_fwd(ch, w, Z + 3 * a);
         if (freep) {
-          // g_red part: -(W s) V^-1 (g_p s)
-          double y = 0;
-#pragma unroll
-          for (int b = 0; b < 3; ++b) y += (w[0] * Vi[b] + w[1] * Vi[3 + b] + w[2] * Vi[6 + b]) * gps[b];
-          atomicAdd(&sGred[base + a], -y);
+          // g_red part: -(W s) V^-1 (g_p s) = -Z (L^-1 (g_p s))
+          atomicAdd(&sGred[base + a], -(Z[3 * a] * h[0] + Z[3 * a + 1] * h[1] + Z[3 * a + 2] * h[2]));
           atomicAdd(&sGc[base + a], Jc[a] * r[0] + Jc[6 + a] * r[1]);
         }
       }
