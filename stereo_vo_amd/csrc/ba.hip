@@ -3,8 +3,10 @@
 // (src/reprojection_factor.cpp:10-88), quaternion (x) identity local parameterization (:19-20,123),
 // oldest pose constant (:130).  LM semantics: SURVEY.md Appendix B; the step control itself is host/lm.cpp
 // (svo_lm_solve), this file provides its two passes as HIP kernels.  What never calls HIP is plain C++ under host/: the sliding-window
-// graph (ba_graph.h), the problem layout — CSR, chunks, destination tables, staging image — (ba_layout.h) and the admission ledger
-// (ba_admission.h); the C-ABI entry points here are thin wrappers over them.
+// graph (ba_graph.h), the problem layout — CSR, chunks, destination tables, staging image — (ba_layout.h), the admission ledger
+// (ba_admission.h) and the launch planning of the device-resident solve — knobs, eligibility, form, k, LDS, workgroups, cost, the raise
+// of k, compact waves — (ba_plan.h, over the kernels' LDS sizes in csrc/lm_lds.h, which the kernels carve by); the C-ABI entry points
+// here are thin wrappers over them.
 //
 // Pass A "linearize" and pass B "backsub" are single sweeps over the observations (landmark-major CSR, wave chunks of
 // <= 64 observations made of whole landmarks, lane = observation):
@@ -56,10 +58,12 @@
 #include "ba_admission.h"
 #include "ba_graph.h"
 #include "ba_layout.h"
+#include "ba_plan.h"
 #include "kernels.h"
 #include "group_kernels.h"
 #include "lm_decide.h"
 #include "lm_device.h"
+#include "lm_lds.h"
 #include "lm_turns.h"
 #include "ref_constants.h"
 #include "reproj_device.h"
@@ -574,14 +578,7 @@ __device__ __forceinline__ void linearize_suffix_bulk(const BaDev& P, const ObsR
 //            partial to the group's running sum, kept in the partial store itself;
 //   level 2  reduce_elements: thread = element, the NG group sums added sequentially.
 // Partials travel as tagged granules {value, tag} (granule_store): a reader takes a value only under the awaited tag.
-constexpr int REC_STRIDE = 38;        // doubles per lane of the staging rows (36 used; even: 16-byte alignment)
-constexpr int LMS_STRIDE = 4;         // pass B: four scalars per landmark of a chunk, in the (idle) staging rows
-constexpr int LMS_COL = 36;           // pass A: cost and g_p^2 of the landmark of rank r in the spare columns 36, 37 of row r
-constexpr int PST_MAX = 2048;         // wire elements a wavefront stages in LDS before it posts them (larger E: posted one by one)
-// LDS of an owner set (doubles): the staging rows (their two spare columns carry pass A's landmark scalars; pass B, which does
-// not stage, keeps its four scalars per landmark in the rows themselves) | the E partials of the chunk on their way out
-// (consecutive threads then post consecutive granules: whole lines) | 4 ints
-__host__ __device__ static inline int wg_lds_doubles(int E) { return 64 * REC_STRIDE + (E <= PST_MAX ? ((E + 1) & ~1) : 0) + 2; }
+// (REC_STRIDE, LMS_STRIDE, LMS_COL, PST_MAX, TAB_LDS_WORDS and the LDS of an owner set, wg_lds_doubles: lm_lds.h)
 struct WgLds { double* rec; double* pst; int* s_ne; uint16_t* tab; };  // tab: the host-driven kernels' LDS copy of the chunk table (behind wg_lds_doubles(E))
 __device__ __forceinline__ WgLds wg_lds(double* base, int E) {
   WgLds L;
@@ -592,7 +589,6 @@ __device__ __forceinline__ WgLds wg_lds(double* base, int E) {
   L.tab = reinterpret_cast<uint16_t*>(base + 64 * REC_STRIDE + pst_doubles + 2);
   return L;
 }
-constexpr int TAB_LDS_WORDS = 1024;   // u16 words of a chunk table ba_lm_kernel keeps in LDS (larger tables: host-driven path)
 
 // A chunk's destination table (host: ba_build_tables), u16 words:
 //   bstart[nU + 1]  entry range of every upper pose-pair block (bstart[nU] = number of entries)
@@ -1801,21 +1797,8 @@ struct LmDevState {
 };
 constexpr double LM_MIN_RADIUS = 1e-32, LM_MAX_RADIUS = 1e16;
 
-// controller workspace (doubles) — it lives in the LDS of the staging rows (a pass and a controller turn never overlap):
-// payload image, 4 vectors of n, term scratch, U staging
-__host__ __device__ static inline size_t ba_lm_ctl_doubles(int n, int K) { return (size_t)n * n + 3 * (size_t)n + 2 + 4 * (size_t)(n > 0 ? n : 1) + (size_t)(n > 0 ? n : 1) + 14 * (size_t)K + 21 * (size_t)(K > 1 ? K - 1 : 1) + 8; }
-// dynamic LDS of ba_lm_kernel (doubles): [staging rows + landmark scalars of CPW wavefronts | controller workspace] (union) |
-// chunk tables | Jacobi scales of the pose columns | step block [dc | candidate poses | current poses]
-// A workgroup is LM_CPW wavefronts; each takes `kw` chunks in turn (ba_lm_multi_kernel; kw = 1: ba_lm_kernel, one chunk per wavefront).
-// (LM_CPW, LM_MAX_WAVE_CHUNKS, ba_lm_blocks: lm_turns.h)
-__host__ __device__ static inline int ba_wire_elements(int K) { const int F = K - 1; return 18 * F * (F + 1) + 33 * F + 2; }
-__host__ __device__ static inline size_t ba_lm_union_doubles(int n, int K) { const size_t a = (size_t)LM_CPW * (size_t)wg_lds_doubles(ba_wire_elements(K)), b = ba_lm_ctl_doubles(n, K); return a > b ? a : b; }
-__host__ __device__ static inline size_t ba_lm_lds_doubles(int n, int K, int tab_words /* per chunk, a multiple of 4, <= TAB_LDS_WORDS */, int kw = 1) {
-  // behind the union and the kw tables of every wavefront: Jacobi scales (nn) | spare (nn) | step block [dc (nn) | candidate poses (7 K) | current poses (7 K)] — the kernel's
-  // carve-up (cSc, sStep).  (Until the end of round 4 this said 2 nn: the current poses' tail lay nn doubles beyond the allocation, inside the
-  // allocation granule for the 5-keyframe window and outside it from n = 36 on — NaN poses, found when larger windows first took this kernel.)
-  return ba_lm_union_doubles(n, K) + (size_t)LM_CPW * (size_t)kw * (size_t)tab_words / 4 + 3 * (size_t)(n > 0 ? n : 1) + 14 * (size_t)K;
-}
+// (the controller workspace ba_lm_ctl_doubles, the wire format's size ba_wire_elements and the dynamic LDS of ba_lm_kernel,
+// ba_lm_union_doubles / ba_lm_lds_doubles: lm_lds.h; LM_CPW, LM_MAX_WAVE_CHUNKS, ba_lm_blocks: lm_turns.h)
 
 // wire total e -> its place in the payload image (cP) or the U triangles (cU)
 __device__ __forceinline__ void lm_place_total(int e, double v, double* cP, double* cU, int F, int n) {
@@ -2646,18 +2629,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(SVO_LM_WAVE
 // Per solve: 1/16 of the wide form's wavefronts and LDS for ~5x its latency — what a GPU shared by dozens of streams wants.
 // The problem image is copied from pinned host memory into the device arena by the kernel itself (16-byte system-scope loads,
 // eight in flight per thread) and read from there by plain loads (one workgroup = one CU = one L2: coherent by construction).
-constexpr int LMC_MAX_WAVES = 6;
-__host__ __device__ static inline int lmc_wave_doubles(int E) { return 64 * REC_STRIDE + ((E + 1) & ~1) + 2 + 4; }  // rows | partials | 4 ints | pass B's four sums
-__host__ __device__ static inline size_t ba_lmc_union_doubles(int n, int K, int NW) {
-  const size_t a = (size_t)NW * (size_t)lmc_wave_doubles(ba_wire_elements(K)), b = ba_lm_ctl_doubles(n, K);
-  return a > b ? a : b;
-}
-// dynamic LDS (doubles): [NW wave areas | controller workspace] (union) | NW chunk tables | running totals (E) | running group sums (E) |
-// pass B's totals and group sums (4 + 4) | Jacobi scales of the pose columns (nn) | spare (nn) | step block [dc (nn) | candidate poses (7 K) | current poses (7 K)]
-__host__ __device__ static inline size_t ba_lmc_lds_doubles(int n, int K, int tab_words, int NW) {
-  const size_t Ep = ((size_t)ba_wire_elements(K) + 1) & ~(size_t)1, nn = n > 0 ? n : 1;
-  return ba_lmc_union_doubles(n, K, NW) + (size_t)NW * (size_t)tab_words / 4 + 2 * Ep + 8 + 3 * nn + 14 * (size_t)K;
-}
+// (LMC_MAX_WAVES and the form's LDS, lmc_wave_doubles / ba_lmc_union_doubles / ba_lmc_lds_doubles: lm_lds.h)
 
 // element `idx` of the running sums takes chunk c's partial p: groups of G consecutive chunks are summed from their first, the
 // groups from the first (grouped_seq_sum's additions in its order)
@@ -3187,18 +3159,14 @@ struct svo_ba {
   unsigned* d_lmc = nullptr;
   unsigned* d_lmdbg = nullptr;   // SVO_BA_TRACE: last command of every workgroup of ba_lm_kernel
   double* h_result = nullptr;    // pinned [LMR_DOUBLES | poses 7 Kmax], inside h_pin
-  int device_lm = -1;            // svo_ba_set_device_lm: -1 automatic, 0 never, 1 whenever eligible
-  int lm_form = -1;              // svo_ba_set_solve_form: which device-resident form — 0 wide (ba_lm_kernel: many workgroups, lowest latency), 1 compact (ba_lm_compact_kernel: one workgroup, smallest footprint), -1 automatic (SVO_BA_FORM, else wide)
+  BaOverrides ov;                // what this adjuster sets for its own device-resident solves (svo_ba_set_device_lm, _solve_form, _wave_chunks, _yield_iterations; the give-up penalty): host/ba_plan.h
   bool lm_compact_inflight = false;  // the launch in flight is the compact form (nothing admitted, no counter)
-  int lm_wave_chunks = 0;        // svo_ba_set_wave_chunks: chunks per wavefront of this adjuster's wide solves (0: the process default, raised where the admission budget asks for it)
   long lm_k_solves[LM_MAX_WAVE_CHUNKS + 1] = {};  // svo_ba_solve_forms: device-resident solves launched in the compact form [0] and in the wide form at k chunks per wavefront [k]
-  int lm_penalty = 0;            // solves left that avoid the wide form after one of its launches gave up
   long wide_launches = 0;        // (test hook SVO_BA_TEST_GIVEUP counts them)
   long fallbacks = 0;            // device-resident solves that gave up and were re-run (svo_lm_stats.fallbacks of the last solve: 0 / 1)
   bool lm_inflight = false;      // a ba_lm_kernel has been launched and not yet joined
   // a wide solve that stepped aside (ba_lm_multi_kernel, LmDevArgs::yield_after): its state is on the device, the next launch continues it
   double* d_yield = nullptr;     // the yield record (granules)
-  int yield_iters = -1;          // svo_ba_set_yield_iterations: LM iterations per launch (0: never yields, -1: SVO_BA_YIELD_ITERS, else 0)
   bool lm_yielded = false;       // loaded, state on the device: the next wide launch of this adjuster is a continuation
   int lm_yield_seq = 0;          // ... of the launch with this completion sequence number
   const void* lm_yield_src = nullptr;  // ... which read its problem image from here (LmDevArgs::arena_src)
@@ -3405,7 +3373,7 @@ extern "C" int svo_ba_set_comm(svo_ba* ba, void* nccl_comm) {
 
 extern "C" int svo_ba_set_device_lm(svo_ba* ba, int mode) {
   if (!ba || mode < -1 || mode > 1) return SVO_ERR_INVALID;
-  ba->device_lm = mode;
+  ba->ov.device_lm = mode;
   return SVO_OK;
 }
 
@@ -3426,7 +3394,7 @@ int svo_ba_use_stream(svo_ba* ba, void* stream) {
 
 extern "C" int svo_ba_set_solve_form(svo_ba* ba, int form) {
   if (!ba || form < -1 || form > 1) return SVO_ERR_INVALID;
-  ba->lm_form = form;
+  ba->ov.lm_form = form;
   return SVO_OK;
 }
 
@@ -3434,7 +3402,7 @@ extern "C" int svo_ba_wave_chunks_limit(void) { return LM_MAX_WAVE_CHUNKS; }
 
 extern "C" int svo_ba_set_wave_chunks(svo_ba* ba, int k) {
   if (!ba || k < 0 || k > LM_MAX_WAVE_CHUNKS) return SVO_ERR_INVALID;
-  ba->lm_wave_chunks = k;
+  ba->ov.lm_wave_chunks = k;
   return SVO_OK;
 }
 
@@ -3447,7 +3415,7 @@ extern "C" int svo_ba_solve_forms(svo_ba* ba, long* counts, int n, long* gave_up
 
 extern "C" int svo_ba_set_yield_iterations(svo_ba* ba, int n) {
   if (!ba || n < -1 || ba->lm_inflight || ba->lm_yielded) return SVO_ERR_INVALID;
-  ba->yield_iters = n;
+  ba->ov.yield_iters = n;
   return SVO_OK;
 }
 
@@ -3765,21 +3733,11 @@ int ba_fused_budget(int device) {
   g_fused_per_cu = per_cu;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return 0;
   share_of[device] = g_ba_cu_share;
-  // LDS is handed out in contiguous pieces: between the tracker's small workgroups a CU may not have room for the last
-  // workgroup the occupancy query promises, so one per CU is left out of the count
-  const int usable = per_cu >= 3 ? per_cu - 1 : (per_cu >= 1 ? 1 : 0);
-  budget[device] = usable * cus / 8 * 7 * g_ba_cu_share / 32;  // a CU-masked stream holds proportionally fewer workgroups
-  if (const char* e = getenv("SVO_BA_BUDGET_PERCENT")) {  // developer experiments (profiles/r04_exp_admission_budget.txt)
-    const int pct = atoi(e);
-    if (pct >= 10 && pct <= 400) budget[device] = (int)((long long)budget[device] * pct / 100);
-  }
-  return budget[device];
+  return budget[device] = ba_plan_budget(per_cu, cus, g_ba_cu_share, ba_knobs().budget_percent);
 }
 
-// What `grid` workgroups of ba_lm_kernel with `lds` bytes of dynamic LDS cost in the units of that budget: a
-// larger reduced camera system (10-keyframe windows) lowers the kernel's occupancy, its workgroups then count for more.
-// (multi: ba_lm_multi_kernel's workgroups — the same 128 threads at 256 VGPRs; its kw chunk tables per wavefront make the LDS larger)
 // workgroups per CU of the wide solve's kernel at `lds` bytes of dynamic LDS (0: the query failed)
+// (multi: ba_lm_multi_kernel's workgroups — the same 128 threads at 256 VGPRs; its kw chunk tables per wavefront make the LDS larger)
 int ba_lm_per_cu(size_t lds, bool multi) {
   static std::mutex mu;
   constexpr int N_CACHED = 32;  // (lds grows with k and with the chunk tables' size: a few dozen values per process)
@@ -3795,12 +3753,10 @@ int ba_lm_per_cu(size_t lds, bool multi) {
   }
   return per_cu;
 }
-int ba_lm_admission_cost(int grid, size_t lds, int device, bool multi = false) {
+// What `grid` workgroups of ba_lm_kernel with `lds` bytes of dynamic LDS cost in the units of that budget (ba_plan_cost)
+int ba_lm_admission_cost(int grid, size_t lds, int device, bool multi) {
   (void)ba_fused_budget(device);
-  const int per_cu = ba_lm_per_cu(lds, multi);
-  if (per_cu <= 0) return 1 << 30;
-  if (per_cu >= g_fused_per_cu) return grid;
-  return (grid * g_fused_per_cu + per_cu - 1) / per_cu;
+  return ba_plan_cost(grid, ba_lm_per_cu(lds, multi), g_fused_per_cu);
 }
 
 inline bool ba_admit(svo_ba* ba, int cost, int device) { BaLedger& l = ba_ledger(device); return ba->res_admission.admit(l, cost, ba_fused_budget(l.device)); }
@@ -3814,85 +3770,19 @@ inline bool ba_admit(svo_ba* ba, int cost, int device) { BaLedger& l = ba_ledger
 // Round 5: measured again with both loops in the tree — one stream alone: 1,803 frames/s host-driven against 1,700 device-resident
 // (profiles/r05_exp_single_stream_paths.txt) — so a single pipeline takes the device-resident solve only while more than two
 // pipelines are inside svo_pipeline_process_batch* (then the host thread per stream is what hurts); pipeline groups always do.
-bool ba_device_lm_wanted() {
-  static const char* e = getenv("SVO_BA_DEVICE_LM");
-  if (e && *e) return atoi(e) != 0;
-  return svo_throughput_mode();
+bool ba_device_lm_on(const svo_ba* ba, bool forced) {
+  const int mode = ba_plan_device_lm(ba->ov, ba_knobs());
+  return forced || (mode < 0 ? svo_throughput_mode() : mode != 0);
 }
 
-int ba_lm_tab_words(const svo_ba* ba) { return std::max(64, (ba->layout.tab_max_words + 63) & ~63); }
-size_t ba_lm_lds_bytes(const svo_ba* ba, int kw) { return sizeof(double) * ba_lm_lds_doubles(ba->d.n, ba->d.K, ba_lm_tab_words(ba), kw); }
+// the loaded problem as the planning sees it (host/ba_plan.h: eligibility, form, k, LDS, workgroups, cost, compact waves)
+BaShape ba_shape(const svo_ba* ba) { const BaDev& d = ba->d; return {d.det != 0, d.C, d.K, d.n, d.G, d.CPW, ba->layout.tab_max_words}; }
 
-// Chunks per wavefront a wide solve is offered to the admission with (ba_lm_multi_kernel for more than one; a solve the budget
-// refuses at this k is offered again at larger ones, see ba_device_lm_launch).  SVO_BA_WAVE_CHUNKS=1..LM_MAX_WAVE_CHUNKS (developer
-// knob), svo_ba_set_wave_chunks for one adjuster; SVO_BA_WAVE_ORDER=contiguous gives a wavefront neighbouring chunks instead of one
-// per stride (see lm_turns.h).  Windows of more than 128 chunks (ba_lm_grouped_kernel) keep one chunk per wavefront; so do solves of
-// no more than two chunks (one workgroup either way).
-constexpr int LM_WAVE_CHUNKS_DEFAULT = 3;
-int ba_lm_wave_chunks(const svo_ba* ba) {
-  static const int env = [] {
-    const char* e = getenv("SVO_BA_WAVE_CHUNKS");
-    const int v = e && *e ? atoi(e) : LM_WAVE_CHUNKS_DEFAULT;
-    return v < 1 ? 1 : (v > LM_MAX_WAVE_CHUNKS ? LM_MAX_WAVE_CHUNKS : v);
-  }();
-  if (ba->d.G > 1 || ba->d.C <= LM_CPW) return 1;
-  return ba->lm_wave_chunks > 0 ? ba->lm_wave_chunks : env;
-}
-bool ba_lm_wave_contig() {
-  static const bool contig = [] { const char* e = getenv("SVO_BA_WAVE_ORDER"); return e && e[0] == 'c'; }();
-  return contig;
-}
-
-// Fills the adjuster's launch record for the loaded problem; false: not eligible (use the host-driven path).
-// compact form: the waves per workgroup that fit 156 KB of dynamic LDS (the kernel keeps ~1.5 KB of static LDS), at most
-// SVO_BA_COMPACT_WAVES (default 6) and not more than the problem has chunks; 0: not eligible
-constexpr size_t LMC_LDS_BUDGET = 156 * 1024;
-constexpr int LM_MAX_CHUNKS_GROUPED = 288;   // wide form: 129..288 chunks go to ba_lm_grouped_kernel (144 workgroups at one per CU fit the admission budget)
-constexpr int LMC_MAX_CHUNKS = 256;   // beyond, a single workgroup's rounds take longer than the host-driven loop's launches
-int ba_lmc_tab_words(const svo_ba* ba) { return std::max(64, (ba->layout.tab_max_words + 63) & ~63); }
-int ba_lmc_waves(const svo_ba* ba) {
-  static const int cap = [] { const char* e = getenv("SVO_BA_COMPACT_WAVES"); const int v = e ? atoi(e) : LMC_MAX_WAVES; return v < 1 ? 1 : (v > LMC_MAX_WAVES ? LMC_MAX_WAVES : v); }();
-  const BaDev& d = ba->d;
-  int nw = std::min(cap, std::max(1, d.C));
-  while (nw >= 1 && sizeof(double) * ba_lmc_lds_doubles(d.n, d.K, ba_lmc_tab_words(ba), nw) > LMC_LDS_BUDGET) --nw;
-  return nw;
-}
-// which device-resident form a solve of this adjuster takes (see svo_ba_set_solve_form)
-bool ba_wants_compact(const svo_ba* ba) {
-  if (ba->lm_penalty > 0) return true;
-  if (ba->lm_form >= 0) return ba->lm_form == 1;
-  static const int env = [] { const char* e = getenv("SVO_BA_FORM"); return !e || !*e ? -1 : (e[0] == 'c' ? 1 : (e[0] == 'w' ? 0 : -1)); }();
-  return env == 1;
-}
-
-// LM iterations a wide solve of this adjuster runs per launch before it steps aside (0: never): svo_ba_set_yield_iterations (a pipeline
-// group sets its lanes' adjusters: svo_pipeline_group_set_solve_yield), else SVO_BA_YIELD_ITERS, else never
-int ba_lm_yield_iters(const svo_ba* ba) {
-  static const int env = [] { const char* e = getenv("SVO_BA_YIELD_ITERS"); const int v = e && *e ? atoi(e) : 0; return v < 0 ? 0 : v; }();
-  return ba->yield_iters >= 0 ? ba->yield_iters : env;
-}
-
-bool ba_device_lm_fill(svo_ba* ba, int* cost, size_t* lds_out, bool forced, bool compact = false, int* waves_out = nullptr) {
+// Fills the adjuster's launch record for the loaded problem, planned as `wide` (null: the compact form); false: use the host-driven path.
+bool ba_device_lm_fill(svo_ba* ba, bool forced, const BaWidePlan* wide) {
   BaDev& d = ba->d;
-  if (!d.det || d.C <= 0 || !ba_zero_copy(ba) || !(forced || ba->device_lm == 1 || (ba->device_lm < 0 && ba_device_lm_wanted())) || !ba->h_lane) return false;
-  size_t lds = 0;
-  int nw = 0, kw = 1;
-  if (compact) {
-    if (d.C > LMC_MAX_CHUNKS || ba->layout.tab_max_words > 4096) return false;
-    nw = ba_lmc_waves(ba);
-    if (nw < 1) return false;
-    lds = sizeof(double) * ba_lmc_lds_doubles(d.n, d.K, ba_lmc_tab_words(ba), nw);
-  } else {
-  // every chunk table in LDS, every chunk its own partial (beyond 128 chunks the grouped kernel sums groups of G chunks first), and
-  // the launch must fit the admission budget at all (workgroups that wait for each other): window-sized problems
-  if (d.C > LM_MAX_CHUNKS_GROUPED || d.CPW != 1 || ba->layout.tab_max_words > TAB_LDS_WORDS) return false;
-  // beyond 128 chunks (ba_lm_grouped_kernel) only on request: measured on configs[2]'s 10-keyframe windows (~210 chunks, E = 2,312 wire
-  // elements) the host-driven loop is faster — 780 against 590 frames/s (profiles/r05_exp_single_stream_paths.txt)
-  if (d.G > 1 && ba->device_lm != 1) return false;
-  kw = ba_lm_wave_chunks(ba);
-  lds = ba_lm_lds_bytes(ba, kw);
-  if (lds > 120 * 1024) return false;  // n <= 100 or so; window problems are n <= 60
-  }
+  if (!ba_zero_copy(ba) || !ba_device_lm_on(ba, forced) || !ba->h_lane) return false;
+  const bool compact = !wide;
   d.points = ba->cur_points; d.cand_points = ba->cand_points; d.poses = ba->cur_poses; d.cand_poses = ba->cand_poses;
   d.flag = nullptr;
   const bool resume = ba->lm_yielded && !compact;  // (the image keeps the INITIAL state while the solve is on its way: a give-up re-runs from it)
@@ -3913,10 +3803,10 @@ bool ba_device_lm_fill(svo_ba* ba, int* cost, size_t* lds_out, bool forced, bool
   // unless the last one did not leave cleanly
   const bool fresh = ba->lm_counters_dirty || !ba->lm_have_base;
   a.base_arrive = fresh ? 0 : ba->lm_base;
-  a.tab_words = compact ? ba_lmc_tab_words(ba) : ba_lm_tab_words(ba);
-  a.wave_chunks = kw;
-  a.wave_contig = ba_lm_wave_contig() ? 1 : 0;
-  a.yield_after = kw > 1 ? ba_lm_yield_iters(ba) : 0;  // ba_lm_multi_kernel only
+  a.tab_words = ba_plan_tab_words(ba->layout.tab_max_words);
+  a.wave_chunks = wide ? wide->k : 1;
+  a.wave_contig = ba_knobs().wave_contig ? 1 : 0;
+  a.yield_after = wide ? wide->yield_after : 0;  // ba_lm_multi_kernel only
   a.resume = resume ? ba->lm_yield_seq : 0;
   a.yield_rec = ba->d_yield;
   a.opt.max_iterations = ba->opt.max_iterations;
@@ -3929,10 +3819,21 @@ bool ba_device_lm_fill(svo_ba* ba, int* cost, size_t* lds_out, bool forced, bool
     static const int every = [] { const char* e = getenv("SVO_BA_TEST_GIVEUP"); return e && *e ? atoi(e) : 0; }();
     a.test_giveup = (!compact && every > 0 && (++ba->wide_launches % every) == 0) ? 1 : 0;
   }
-  *cost = compact ? 0 : ba_lm_admission_cost(ba_lm_blocks(d.C, kw), lds, ba->ctx->device, kw > 1);
-  *lds_out = lds;
-  if (waves_out) *waves_out = nw;
   return true;
+}
+
+// a solve of `ba` has been launched on `st` at t0: the adjuster's state of a launch in flight (joined by ba_device_lm_end)
+void ba_mark_launched(svo_ba* ba, hipStream_t st, std::chrono::steady_clock::time_point t0, bool compact) {
+  ++ba->seq;  // = a.host_seq
+  ba->lm_t0 = t0;
+  if (ba->arena_dirty) ba->arena_partial = true;  // the kernel reads the host image in place: the device arena holds the landmark buffers only (the host image keeps the INITIAL state, see ba_refresh_arena_image)
+  ba->arena_dirty = false;
+  ba->lm_inflight = true; ba->lm_compact_inflight = compact;
+  if (compact) ++ba->lm_k_solves[0];
+  else if (ba->lm_yielded) ++ba->lm_resumes_now;  // (a solve is counted once, at the k of its first launch)
+  else { ++ba->lm_k_solves[std::min(std::max(ba->h_lane->a.wave_chunks, 1), LM_MAX_WAVE_CHUNKS)]; ba->lm_yield_src = ba->h_lane->a.arena_src; }
+  ba->lm_stream = st;
+  ba->res_export = ba->h_lane->a.export_points != nullptr;
 }
 
 // ONE launch for the solves of `n` adjusters (the lanes of a pipeline group that reached a keyframe together; n = 1: a
@@ -3941,140 +3842,103 @@ bool ba_device_lm_fill(svo_ba* ba, int* cost, size_t* lds_out, bool forced, bool
 // offered again later, or solved by the host-driven path.
 int ba_device_lm_launch(svo_ba** bas, int n, hipStream_t st, bool forced, unsigned long long* launched_mask) {
   if (launched_mask) *launched_mask = 0;
-  // SVO_BA_OVERFLOW=1: a solve the admission budget refuses takes the compact form at once instead of waiting for the budget.  Off by
-  // default: measured in round 5 (profiles/r05_exp_lanes_groups.txt) it helps only while streams share hardware queues (7 lines per group
-  // on 16 queues: 30 k against 25 k frames/s at 128 lanes); with one hardware queue per stream the wide form alone is faster (37-51 k
-  // against 27-36 k) — a 3 ms compact solve holds its line for 3 ms.
-  static const bool overflow = [] { const char* e = getenv("SVO_BA_OVERFLOW"); return e && *e && atoi(e) != 0; }();
-  bool to_compact[SVO_MAX_LANES] = {};
-  // ---- the wide form (ba_lm_kernel): admitted against the budget of co-resident waiting workgroups
+  const BaKnobs& knobs = ba_knobs();
+  n = std::min(n, SVO_MAX_LANES);
+  // ---- plan each solve: the form it asks for, and in the wide form its kernel, k, LDS and workgroups
+  bool to_compact[SVO_MAX_LANES] = {}, wide_ok[SVO_MAX_LANES];
+  BaShape shape[SVO_MAX_LANES];
+  BaWidePlan plan[SVO_MAX_LANES];
+  for (int i = 0; i < n; ++i) {
+    bas[i]->lm_inflight = false;
+    shape[i] = ba_shape(bas[i]);
+    wide_ok[i] = ba_plan_wide(shape[i], bas[i]->ov, knobs, &plan[i]);
+    to_compact[i] = ba_plan_wants_compact(bas[i]->ov, knobs, bas[i]->lm_yielded);
+  }
+  // ---- the wide form (ba_lm_kernel): admitted against the budget of co-resident waiting workgroups, one launch per kernel
   int launched_total = 0;
-  for (int i = 0; i < n && i < SVO_MAX_LANES; ++i) bas[i]->lm_inflight = false;
-  for (int form = 0; form < 3; ++form) {  // windows of up to 128 chunks: ba_lm_kernel, or ba_lm_multi_kernel (form 2, several chunks per wavefront); beyond: ba_lm_grouped_kernel (form 1)
-  const void* kernel = form == 0 ? (const void*)ba_lm_kernel : (form == 1 ? (const void*)ba_lm_grouped_kernel : (const void*)ba_lm_multi_kernel);
-  LmLanePtrs ptrs;
-  int launched = 0, max_c = 0;
-  size_t max_lds = 0;
-  svo_ba* took[SVO_MAX_LANES];
-  int tidx[SVO_MAX_LANES];
-  for (int i = 0; i < n && i < SVO_MAX_LANES; ++i) {
-    svo_ba* ba = bas[i];
-    int cost = 0;
-    size_t lds = 0;
-    if ((ba->d.G > 1 ? 1 : (ba_lm_wave_chunks(ba) > 1 ? 2 : 0)) != form) continue;
-    if (ba_wants_compact(ba) && !ba->lm_yielded) { to_compact[i] = true; continue; }
-    if (!ba_device_lm_fill(ba, &cost, &lds, forced)) continue;
-    if (lds > 32 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) != hipSuccess) continue;
-    bool admitted = ba_admit(ba, cost, ba->ctx->device);
-    if (!admitted && form == 2 && ba->lm_wave_chunks <= 0) {
-      // The budget refuses the solve at the default k: it rides this launch on fewer workgroups — the first larger k that fits, as
-      // long as the kernel's workgroups per CU at that k's LDS (k chunk tables per wavefront) stay what they are at the default, so
-      // that the launch's dynamic LDS (the maximum over its solves) takes no residency from the solves beside it.  Same kernel, same
-      // hand-overs, every chunk posts its own partials: the same bits.  What is charged is the cost at the k and the LDS it runs with.
-      const int k0 = ba->h_lane->a.wave_chunks, dev = ba->ctx->device;
-      const int per_cu0 = ba_lm_per_cu(lds, true);
-      int blocks = ba_lm_blocks(ba->d.C, k0);
-      for (int k = k0 + 1; k <= LM_MAX_WAVE_CHUNKS && !admitted; ++k) {
-        if (ba_lm_blocks(ba->d.C, k) == blocks) continue;  // (no workgroup saved)
-        blocks = ba_lm_blocks(ba->d.C, k);
-        const size_t lds_k = ba_lm_lds_bytes(ba, k);
-        if (lds_k > 120 * 1024 || per_cu0 <= 0 || ba_lm_per_cu(lds_k, true) < per_cu0) break;
-        if (lds_k > 32 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) != hipSuccess) break;
-        const int cost_k = ba_lm_admission_cost(blocks, lds_k, dev, true);
-        admitted = ba_admit(ba, cost_k, dev);
-        if (admitted) { ba->h_lane->a.wave_chunks = k; lds = lds_k; }
+  for (int form = 0; form < BA_WIDE_FORMS; ++form) {
+    const void* kernel = form == BA_FORM_PLAIN ? (const void*)ba_lm_kernel : (form == BA_FORM_GROUPED ? (const void*)ba_lm_grouped_kernel : (const void*)ba_lm_multi_kernel);
+    const bool multi = form == BA_FORM_MULTI;
+    const auto allow = [&](size_t lds) { return lds <= 32 * 1024 || hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LM_LDS_LIMIT) == hipSuccess; };
+    LmLanePtrs ptrs;
+    int launched = 0, max_c = 0;
+    size_t max_lds = 0;
+    svo_ba* took[SVO_MAX_LANES];
+    int tidx[SVO_MAX_LANES];
+    for (int i = 0; i < n; ++i) {
+      svo_ba* ba = bas[i];
+      BaWidePlan& p = plan[i];
+      if (p.form != form || to_compact[i] || !wide_ok[i]) continue;
+      if (!ba_device_lm_fill(ba, forced, &p) || !allow(p.lds)) continue;
+      const int dev = ba->ctx->device;
+      // a solve the budget refuses at its k is offered again at larger ones (ba_plan_raise_k)
+      const bool admitted = ba_admit(ba, ba_lm_admission_cost(p.blocks, p.lds, dev, multi), dev) ||
+                            ba_plan_raise_k(shape[i], ba->ov, g_fused_per_cu, &p, [&](size_t lds) { return ba_lm_per_cu(lds, true); }, allow,
+                                            [&](int cost) { return ba_admit(ba, cost, dev); });
+      if (!admitted) { to_compact[i] = knobs.overflow && !ba->lm_yielded; continue; }
+      ba->h_lane->a.wave_chunks = p.k;
+      // the counter starts from zero: cleared in front of the launch (the adjuster's previous solve no longer touches it
+      // once its completion word is out)
+      if (ba->lm_counters_dirty || !ba->lm_have_base) {
+        if (hipMemsetAsync(ba->d_lmc, 0, LMC_WORDS * sizeof(unsigned), st) != hipSuccess) { ba->res_admission.release(); continue; }
+      }
+      ba->lm_counters_dirty = false;
+      ptrs.p[launched] = ba->h_lane;
+      took[launched] = ba;
+      tidx[launched] = i;
+      max_c = std::max(max_c, p.blocks);
+      max_lds = std::max(max_lds, p.lds);
+      ++launched;
+    }
+    if (launched) {
+      const auto t0 = now();
+      {
+        SvoProfScope prof(took[0]->ctx, SVO_PROF_BA_STEP, st);
+        if (form == BA_FORM_GROUPED) hipLaunchKernelGGL(ba_lm_grouped_kernel, dim3(max_c, launched), dim3(128), max_lds, st, ptrs);
+        else if (form == BA_FORM_MULTI) hipLaunchKernelGGL(ba_lm_multi_kernel, dim3(max_c, launched), dim3(128), max_lds, st, ptrs);
+        else hipLaunchKernelGGL(ba_lm_kernel, dim3(max_c, launched), dim3(128), max_lds, st, ptrs);
+      }
+      if (hipGetLastError() != hipSuccess) {
+        for (int i = 0; i < launched; ++i) took[i]->res_admission.release();
+        launched = 0;
+      }
+      for (int i = 0; i < launched; ++i) {
+        ba_mark_launched(took[i], st, t0, false);
+        if (launched_mask) *launched_mask |= 1ull << tidx[i];
       }
     }
-    if (!admitted) { to_compact[i] = overflow && !ba->lm_yielded; continue; }
-    // the counter starts from zero: cleared in front of the launch (the adjuster's previous solve no longer touches it
-    // once its completion word is out)
-    if (ba->lm_counters_dirty || !ba->lm_have_base) {
-      if (hipMemsetAsync(ba->d_lmc, 0, LMC_WORDS * sizeof(unsigned), st) != hipSuccess) { ba->res_admission.release(); continue; }
-    }
-    ba->lm_counters_dirty = false;
-    ptrs.p[launched] = ba->h_lane;
-    took[launched] = ba;
-    tidx[launched] = i;
-    max_c = std::max(max_c, ba_lm_blocks(ba->d.C, ba->h_lane->a.wave_chunks));
-    max_lds = std::max(max_lds, lds);
-    ++launched;
+    launched_total += launched;
   }
-  if (launched) {
-    const auto t0 = now();
-    {
-      SvoProfScope prof(took[0]->ctx, SVO_PROF_BA_STEP, st);
-      if (form == 1) hipLaunchKernelGGL(ba_lm_grouped_kernel, dim3(max_c, launched), dim3(128), max_lds, st, ptrs);
-      else if (form == 2) hipLaunchKernelGGL(ba_lm_multi_kernel, dim3(max_c, launched), dim3(128), max_lds, st, ptrs);
-      else hipLaunchKernelGGL(ba_lm_kernel, dim3(max_c, launched), dim3(128), max_lds, st, ptrs);
-    }
-    if (hipGetLastError() != hipSuccess) {
-      for (int i = 0; i < launched; ++i) took[i]->res_admission.release();
-      launched = 0;
-    }
-    for (int i = 0; i < launched; ++i) {
-      svo_ba* ba = took[i];
-      ++ba->seq;  // = a.host_seq
-      ba->lm_t0 = t0;
-      if (ba->arena_dirty) ba->arena_partial = true;  // the kernel reads the host image in place: the device arena holds the landmark buffers only
-      ba->arena_dirty = false;
-      ba->lm_inflight = true; ba->lm_compact_inflight = false;
-      if (ba->lm_yielded) ++ba->lm_resumes_now;  // (a solve is counted once, at the k of its first launch)
-      else { ++ba->lm_k_solves[std::min(std::max(ba->h_lane->a.wave_chunks, 1), LM_MAX_WAVE_CHUNKS)]; ba->lm_yield_src = ba->h_lane->a.arena_src; }
-      ba->lm_stream = st;
-      ba->res_export = ba->h_lane->a.export_points != nullptr;
-      if (launched_mask) *launched_mask |= 1ull << tidx[i];
-    }
-  }
-  launched_total += launched;
-  }
-  const int launched = launched_total;
   // ---- the compact form (ba_lm_compact_kernel: one workgroup per solve; nothing to admit, nothing to clear)
   int n_compact = 0;
-  {
-    LmLanePtrs cptrs;
-    svo_ba* ctook[SVO_MAX_LANES];
-    int cidx[SVO_MAX_LANES];
-    int nw = LMC_MAX_WAVES;
-    for (int i = 0; i < n && i < SVO_MAX_LANES; ++i) {
-      svo_ba* ba = bas[i];
-      if (!to_compact[i]) continue;
-      int cost = 0, waves = 0;
-      size_t lds = 0;
-      if (!ba_device_lm_fill(ba, &cost, &lds, forced, true, &waves)) continue;
-      cptrs.p[n_compact] = ba->h_lane; ctook[n_compact] = ba; cidx[n_compact] = i;
-      nw = std::min(nw, waves);
-      ++n_compact;
+  LmLanePtrs cptrs;
+  svo_ba* ctook[SVO_MAX_LANES];
+  int cidx[SVO_MAX_LANES], cwaves[SVO_MAX_LANES];
+  BaShape cshape[SVO_MAX_LANES];
+  for (int i = 0; i < n; ++i) {
+    svo_ba* ba = bas[i];
+    if (!to_compact[i] || !(cwaves[n_compact] = ba_plan_compact_waves(shape[i], knobs.compact_waves)) || !ba_device_lm_fill(ba, forced, nullptr)) continue;
+    cptrs.p[n_compact] = ba->h_lane; ctook[n_compact] = ba; cidx[n_compact] = i; cshape[n_compact] = shape[i];
+    ++n_compact;
+  }
+  if (n_compact) {
+    const BaCompactLaunch l = ba_plan_compact_launch(cshape, cwaves, n_compact);  // one launch = one workgroup shape
+    static bool attr_set = false;
+    if (!attr_set) attr_set = hipFuncSetAttribute((const void*)ba_lm_compact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LMC_LDS_BUDGET) == hipSuccess;
+    const auto t0 = now();
+    bool ok = attr_set;
+    if (ok) {
+      SvoProfScope prof(ctook[0]->ctx, SVO_PROF_BA_STEP, st);
+      hipLaunchKernelGGL(ba_lm_compact_kernel, dim3(1, n_compact), dim3(64 * l.waves), l.lds, st, cptrs);
+      ok = hipGetLastError() == hipSuccess;
     }
-    if (n_compact) {
-      // one launch = one workgroup shape: the smallest wave count of its solves (fewer waves need less LDS), LDS of the largest
-      size_t clds = 0;
-      for (int k = 0; k < n_compact; ++k)
-        clds = std::max(clds, sizeof(double) * ba_lmc_lds_doubles(ctook[k]->d.n, ctook[k]->d.K, ctook[k]->h_lane->a.tab_words, nw));
-      static bool attr_set = false;
-      if (!attr_set) attr_set = hipFuncSetAttribute((const void*)ba_lm_compact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LMC_LDS_BUDGET) == hipSuccess;
-      const auto t0 = now();
-      bool ok = attr_set;
-      if (ok) {
-        SvoProfScope prof(ctook[0]->ctx, SVO_PROF_BA_STEP, st);
-        hipLaunchKernelGGL(ba_lm_compact_kernel, dim3(1, n_compact), dim3(64 * nw), clds, st, cptrs);
-        ok = hipGetLastError() == hipSuccess;
-      }
-      if (!ok) n_compact = 0;
-      for (int k = 0; k < n_compact; ++k) {
-        svo_ba* ba = ctook[k];
-        ++ba->seq;  // = a.host_seq
-        ba->lm_t0 = t0;
-        if (ba->arena_dirty) ba->arena_partial = true;  // the host image keeps the INITIAL state (see ba_refresh_arena_image)
-        ba->arena_dirty = false;
-        ba->lm_inflight = true; ba->lm_compact_inflight = true;
-      ++ba->lm_k_solves[0];
-        ba->lm_stream = st;
-        ba->res_export = ba->h_lane->a.export_points != nullptr;
-        if (launched_mask) *launched_mask |= 1ull << cidx[k];
-      }
+    if (!ok) n_compact = 0;
+    for (int k = 0; k < n_compact; ++k) {
+      ba_mark_launched(ctook[k], st, t0, true);
+      if (launched_mask) *launched_mask |= 1ull << cidx[k];
     }
   }
-  return launched + n_compact;
+  return launched_total + n_compact;
 }
 
 // Joins the launch: completion word, then poses / summary / counters out of the pinned result block.  SVO_BA_CONTINUES: the solve
@@ -4509,7 +4373,7 @@ static void ba_after_giveup(svo_ba* ba) {
   ba->arena_dirty = true;
   ba->host_points_valid = false;
   ba->upload_pending = false;
-  ba->lm_penalty = 64;
+  ba->ov.lm_penalty = 64;
   ++ba->fallbacks;
   ba->lm_yielded = false; ba->lm_resumes_now = 0;  // (a continuation that gave up: the solve starts again from its image)
 }
@@ -4518,9 +4382,9 @@ static void ba_after_giveup(svo_ba* ba) {
 // wants another path): back to "loaded, not uploaded" — the image was only read — and whoever solves it starts from the beginning.
 static void ba_drop_yield(svo_ba* ba) {
   if (!ba->lm_yielded) return;
-  const int penalty = ba->lm_penalty; const long fallbacks = ba->fallbacks;
+  const int penalty = ba->ov.lm_penalty; const long fallbacks = ba->fallbacks;
   ba_after_giveup(ba);
-  ba->lm_penalty = penalty; ba->fallbacks = fallbacks;
+  ba->ov.lm_penalty = penalty; ba->fallbacks = fallbacks;
 }
 
 // The join of a caller that owns no schedule (a lone pipeline, svo_ba_solve_problem(s)): a solve that stepped aside is launched again,
@@ -4547,7 +4411,7 @@ static int ba_lm(svo_ba* ba, svo_ba_summary* sum) {
   if (ba_device_lm_launch(&ba, 1, ba->lm_yielded ? ba->lm_stream : ba->stream, ba->lm_yielded, nullptr) == 1) {  // the whole solve is one launch (or, where it yields, a few): nothing for the host to do until the completion word
     const int rcd = ba_device_lm_join(ba, sum);
     d.flag = nullptr;
-    if (rcd == SVO_OK) { if (ba->lm_penalty > 0) --ba->lm_penalty; return rcd; }
+    if (rcd == SVO_OK) { if (ba->ov.lm_penalty > 0) --ba->ov.lm_penalty; return rcd; }
     if (rcd != SVO_BA_REFUSED) {
     ba_after_giveup(ba);  // the problem is still loaded (pinned image untouched): solve it again below, never lose the keyframe
     fell_back = 1;
@@ -4614,7 +4478,7 @@ extern "C" int svo_ba_solve_problems(svo_ba** bas, int n, svo_ba_summary* summar
     int rc;
     if ((mask >> i) & 1ull) {
       rc = ba_device_lm_join(ba, sum); ba->d.flag = nullptr;
-      if (rc == SVO_OK) { if (ba->lm_penalty > 0) --ba->lm_penalty; }
+      if (rc == SVO_OK) { if (ba->ov.lm_penalty > 0) --ba->ov.lm_penalty; }
       else if (rc == SVO_BA_REFUSED) rc = ba_lm(ba, sum);
       else {  // gave up: the problem is still loaded — again, compact form or host-driven (see svo_ba_solve_finish)
         ba_after_giveup(ba);
@@ -4793,7 +4657,7 @@ int svo_ba_solve_finish(svo_ba* ba, svo_ba_summary* summary) {
   bool on_device_ok = on_device;
   if (ba->lm_inflight) {
     rc = ba_device_lm_join(ba, summary); ba->d.flag = nullptr;
-    if (rc == SVO_OK) { if (ba->lm_penalty > 0) --ba->lm_penalty; }
+    if (rc == SVO_OK) { if (ba->ov.lm_penalty > 0) --ba->ov.lm_penalty; }
     else if (rc == SVO_BA_REFUSED) { rc = ba_lm(ba, summary); on_device_ok = false; }
     else {  // gave up: never lose the keyframe — the problem is still loaded, solve it again (compact form, else host-driven)
       ba_after_giveup(ba);

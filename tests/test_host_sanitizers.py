@@ -1,7 +1,8 @@
 """AddressSanitizer + UndefinedBehaviorSanitizer over the GPU-free host code of the product (the step control
 host/lm.cpp, the dense Cholesky, the KITTI-layout decoders, the track rasteriser, the synthetic renderer, and the three
 GPU-free pieces of the bundle adjuster: the sliding-window graph host/ba_graph.h, the problem layout host/ba_layout.h, the
-admission ledger host/ba_admission.h, and the argument rules, sizes and launch geometry of the dense keyframe chain
+admission ledger host/ba_admission.h, the launch planning of its device-resident solve host/ba_plan.h with the kernels' LDS sizes
+csrc/lm_lds.h (tests/sanitize/ba_plan_test.cpp), and the argument rules, sizes and launch geometry of the dense keyframe chain
 host/dense_args.h), on the CPU: GPU sanitizers are not available on the target pool, and these are the
 pieces that parse files and index host arrays.  Every program is stand-alone (its own main); nothing is loaded into Python."""
 import os
@@ -99,7 +100,7 @@ def _run_sanitized(tmp_path, name, ok, *args):
     exe = str(tmp_path / name)
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
            "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "stereo_vo_amd", "host"),
-           os.path.join(ROOT, "tests", "sanitize", name + ".cpp"), "-o", exe, "-lpthread"]
+           "-I", os.path.join(ROOT, "stereo_vo_amd", "csrc"), os.path.join(ROOT, "tests", "sanitize", name + ".cpp"), "-o", exe, "-lpthread"]
     subprocess.run(cmd, check=True, timeout=300)
     r = subprocess.run([exe] + list(args), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
@@ -135,3 +136,14 @@ def test_dense_args_rules_sizes_and_launch_geometry_at_their_boundaries(tmp_path
     message; chunk, seam and path-grid counts against brute-force counts; the SGM workspace's regions aligned and disjoint, up to
     2^30 pixels; the keyframe clouds' resolved parameters, buffer sizes and sub-batch split."""
     _run_sanitized(tmp_path, "dense_args_test", "dense args ok")
+
+
+def test_ba_plan_sizes_forms_budget_and_raised_k_match_a_restatement(tmp_path):
+    """The launch planning of the device-resident window solve (host/ba_plan.h, csrc/lm_lds.h), walked on the CPU under ASan + UBSan
+    against restatements written from the rules: the LDS sizes of the wide and the compact form (monotone in k and in the waves, the
+    union, the tail, n = 36 pinned), form / k / eligibility for every C up to 300 with every boundary at its limit and one beyond, the
+    compact form's waves against a linear search and the shape of a mixed launch, budget and cost, the raise of k against a fake
+    occupancy and a fake ledger (nothing admissible skipped, nothing offered behind the occupancy drop, no offer that saves no
+    workgroup, an adjuster's own k never raised), and every knob parsed from unset, empty, in-range, out-of-range and non-numeric
+    strings."""
+    _run_sanitized(tmp_path, "ba_plan_test", "ba plan ok")
