@@ -107,6 +107,8 @@ def test_hip_stereo_odd_sizes(ctx, shape, nd, blk):
 
 @pytest.mark.gpu
 def test_hip_triangulate_dedup_bit_exact(ctx):
+    """One random case against the oracle.  The inputs built for every decision and launch-shape edge, against an independent
+    restatement, are in tests/test_geom_paths.py."""
     rng = np.random.default_rng(11)
     n = 3000
     xy = rng.uniform(0, 1241, (n, 2)).astype(np.float32)
