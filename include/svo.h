@@ -101,7 +101,8 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * svo_voxel_map_carve_dev: the counts' memset and the launch), "voxel_copy" (one svo_voxel_map_copy_live_dev), "voxel_render" (one
  * svo_voxel_map_render_dev: the two memsets and both launches), "voxel_remove" (one svo_voxel_map_remove_dev: the counts' memset and
  * the launch), "voxel_move" (one svo_voxel_map_move_dev: the counts' memset, the removal and the insert; the launches inside it
- * are not counted as "voxel_remove" or "voxel_insert");
+ * are not counted as "voxel_remove" or "voxel_insert"), "voxel_grid" (one svo_voxel_map_grid_dev: the memsets of the workspace
+ * and the counts and both launches);
  * NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
@@ -626,6 +627,100 @@ int svo_voxel_ledger_remove(svo_voxel_ledger* ledger, int64_t id, uint64_t* coun
 int svo_voxel_ledger_ids(svo_voxel_ledger* ledger, int64_t* ids, int capacity, int* n);
 /* What is held under id: the recorded pose7 (7 doubles), the record count and the DEVICE pointer of the copy; each may be NULL. */
 int svo_voxel_ledger_get(svo_voxel_ledger* ledger, int64_t id, double* pose7, int* n, const svo_cloud_point** points);
+
+/* Voxel map grid: the ground plan of the map, an axis-aligned na x nb grid over two of the map's axes.  Per cell: the highest and
+ * the lowest surface inside a height band, the mean intensity of the highest voxel, how many voxels and points fell into the cell,
+ * and a class (UNKNOWN, LEVEL, OBSTACLE).  One walk over the table bins every qualifying voxel by its KEY, in integers only; a second
+ * launch turns the cells into the outputs.  The grid is tested with ==.
+ *   Axes.  up_axis (0..2) is the map axis that points up or down, up_sign (+1 / -1) says which: a world frame that is the first
+ *      camera's frame has y down, i.e. up_axis 1, up_sign -1.  The grid's axes are the other two in cyclic order, a = (up_axis+1) % 3,
+ *      b = (up_axis+2) % 3: for the camera convention z forward and x right.  Cell (ia, ib) is element ia*nb + ib of every output.
+ *   Host-side conversion, once per call, with vs = (double)voxel_size, stated f64 operations:
+ *      ka0 = floor(origin_a / vs), kb0 = floor(origin_b / vs), each clamped to +-2^21;
+ *      hlo = floor(up_lo / vs * 65536.0), hhi = floor(up_hi / vs * 65536.0) (divide, then multiply), each clamped to +-2^38, as int64;
+ *      step = floor(obstacle_step / vs * 65536.0), clamped to 0..2^38.
+ *   Per slot, integers only:
+ *   1. A slot qualifies iff key != EMPTY and count = ci >> 40 >= min_count (>= 1).  Carved slots have count 0 and never qualify;
+ *      nothing divides by 0.
+ *   2. g = k_up * 65536 + s_up div count: k_up the signed key index of the up axis (its 21 key bits minus 2^20), s_up that axis's
+ *      sum word, div the exact integer floor division.  The quotient is at most 65535 because every fraction is, so g is the
+ *      voxel's mean height in 65536ths of a voxel.  hgt = up_sign * g, |hgt| < 2^37.
+ *   3. In the band iff hlo <= hgt && hgt <= hhi.
+ *   4. ia = floordiv(k_a - ka0, cell_voxels), ib = floordiv(k_b - kb0, cell_voxels): the FLOOR, not truncation (the voxel at
+ *      k_a - ka0 = -1 is outside, not in cell 0).  Binned iff 0 <= ia < na && 0 <= ib < nb; cell = ia*nb + ib.
+ *   5. Four u64 words per cell, in the caller's workspace at 4*cell .. 4*cell + 3:
+ *        top  = max(top, (uint64)(hgt + 2^37) << 8 | isum div count)      (isum: the low 40 bits of ci)
+ *        bot  = max(bot, (uint64)(2^37 - hgt))
+ *        nvox += 1
+ *        npts += count
+ *      by relaxed device-scope 64-bit atomics whose value is not read back.  max and + commute: the grid depends on no thread
+ *      order and on no slot placement.  Among voxels of equal height the larger mean intensity wins the cell.  Both max words are
+ *      never 0 for a binned voxel.
+ *   6. Resolve, a second launch on the same stream, per cell.  nvox == 0: cls = 0 (SVO_VOXEL_GRID_UNKNOWN), top = -infinity,
+ *      bottom = +infinity, intensity = 0, n_voxels = 0, n_points = 0.  Otherwise htop = (top >> 8) - 2^37, hbot = 2^37 - bot,
+ *      cls = htop - hbot > step ? 2 (SVO_VOXEL_GRID_OBSTACLE) : 1 (SVO_VOXEL_GRID_LEVEL),
+ *      top = (float)((double)htop / 65536.0 * vs) and bottom likewise from hbot (heights in map units along UP, whatever up_sign),
+ *      intensity = top word & 255, n_voxels = nvox (u32: a table has at most 2^28 slots), n_points = npts (u64, nothing saturates).
+ *   7. counts = {n_qualifying, n_in_band, n_binned, n_cells, n_obstacle}: 5 u64 on the device, or NULL.  n_cells: cells with
+ *      nvox > 0; n_obstacle: cells of class 2; the resolve counts these two.  One relaxed atomicAdd per workgroup and non-zero
+ *      counter.
+ *   8. SVO_ERR_INVALID with the argument named, and nothing launched, for: a null map, params, workspace, out or out->cls; up_axis
+ *      outside 0..2; up_sign other than +1 and -1; an origin that is not finite; cell_voxels outside 1..1024; na or nb outside
+ *      1..8192 or na*nb > 2^24; a NaN up_lo or up_hi (infinities are allowed) or up_lo > up_hi; obstacle_step negative or NaN;
+ *      min_count < 1; a workspace or counts that is not 8-byte aligned; top, bottom or n_voxels not 4-byte, n_points not 8-byte
+ *      aligned.
+ * workspace: svo_voxel_grid_workspace_bytes(na, nb) = 32*na*nb bytes of device memory, 8-byte aligned; its contents before the
+ * call are meaningless (it is zeroed on the stream before the first launch), afterwards it holds the four words of every cell.
+ * A table that only inserts ever wrote holds quotients <= 65535 (heights) and <= 255 (intensities).  The removal's KNOWN PROPERTY
+ * (item 6 of "Voxel map removal") can leave larger ones; both divisions are exact for every sum below 2^40 and count below 2^24,
+ * and the words are formed as written above in 64-bit arithmetic.
+ * KNOWN PROPERTIES.  The grid is aligned with the map's axes and is not rotated: a first camera that was pitched gives a tilted
+ * "up".  A cell's class is only the span between its highest and lowest voxel inside the band: a slope steeper than
+ * obstacle_step per cell is an obstacle, an overhang above the band is not seen.
+ * The defaults are NOT tuned on real imagery: the camera convention (up_axis 1, up_sign -1), cells of 0.5 map units (cell_voxels =
+ * floor(0.5 / vs + 0.5) clamped to 1..1024, 5 at the default voxel size), 256 x 256 cells starting at a = 0 and centred on b = 0
+ * (origin_a = 0, origin_b = -128 * cell_voxels * vs), the band -3 .. +2.5, obstacle_step 0.3, min_count 1.
+ * The pipeline never builds a grid by itself; call it after the ledger's updates and the carve. */
+#define SVO_VOXEL_GRID_UNKNOWN 0
+#define SVO_VOXEL_GRID_LEVEL 1
+#define SVO_VOXEL_GRID_OBSTACLE 2
+typedef struct svo_voxel_grid_params {
+  int up_axis;              /* 0..2 */
+  int up_sign;              /* +1 or -1 */
+  double origin_a, origin_b; /* finite, map units: the corner of cell (0, 0) */
+  int cell_voxels;          /* 1..1024: voxels per cell edge */
+  int na, nb;               /* each 1..8192, na*nb <= 2^24 */
+  double up_lo, up_hi;      /* the band of heights along UP in map units; not NaN, up_lo <= up_hi, infinities allowed */
+  double obstacle_step;     /* >= 0, not NaN: a cell whose span exceeds it is an obstacle */
+  int min_count;            /* >= 1 */
+} svo_voxel_grid_params;
+typedef struct svo_voxel_grid_out { /* na*nb elements each; every pointer but cls may be NULL */
+  uint8_t* cls;
+  float* top;
+  float* bottom;
+  uint8_t* intensity;
+  uint32_t* n_voxels;
+  uint64_t* n_points;
+} svo_voxel_grid_out;
+/* The defaults above for a map of this voxel size.  Pure; SVO_ERR_INVALID for null params or a voxel_size that is not finite and > 0. */
+int svo_voxel_grid_default_params(float voxel_size, svo_voxel_grid_params* params);
+/* 32*na*nb; 0 for na or nb < 1.  Pure. */
+size_t svo_voxel_grid_workspace_bytes(int na, int nb);
+/* Item 4 for a position (a, b) in map units along the grid's axes, so that a caller finds the vehicle's cell by the grid's own rule:
+ * k = floor(a / vs) clamped to +-2^21, *ia = floordiv(k - ka0, cell_voxels), likewise *ib (either may be NULL).  Returns 1 when
+ * the position is inside the grid, 0 when it is not (ia, ib are written all the same), SVO_ERR_INVALID for null or refused params,
+ * a voxel_size that is not finite and > 0, or a NaN position.  Pure. */
+int svo_voxel_grid_cell_of(const svo_voxel_grid_params* params, float voxel_size, double a, double b, int* ia, int* ib);
+/* DEVICE pointers, asynchronous on svo_stream(ctx): the memsets of the workspace and of the counts, then two launches. */
+int svo_voxel_map_grid_dev(svo_voxel_map* map, const svo_voxel_grid_params* params, void* workspace, const svo_voxel_grid_out* out,
+                           uint64_t* counts);
+/* HOST outputs, synchronous: the workspace and the device outputs are allocated and freed by the call.  out: host pointers (no
+ * alignment asked), cls required; counts: 5 u64 on the host or NULL. */
+int svo_voxel_map_grid(svo_voxel_map* map, const svo_voxel_grid_params* params, const svo_voxel_grid_out* out, uint64_t* counts);
+/* Measurement aid: how the walk issues the two max of item 5.  precheck != 0: a relaxed device-scope load of the word skips the atomic
+ * where the word already holds at least the value (words only grow within the launch, so a stale load costs a needless atomic, never
+ * a wrong skip).  It cannot change a bit of the outputs or of the workspace.  DESIGN 7j gives the figures and the default. */
+int svo_voxel_grid_set_mode(svo_voxel_map* map, int precheck);
 
 /* ------------------------------------------------------------------- a8 --
  * ImageProcessor::triangulate_stereo's reprojection loop

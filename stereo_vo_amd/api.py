@@ -247,6 +247,52 @@ def _render_params(params, min_count, max_radius):
     return _params(voxel_render_default_params, params, min_count=min_count, max_radius=max_radius)
 
 
+class VoxelGridParams(C.Structure):
+    """svo_voxel_grid_params: up_axis (0..2), up_sign (+1 / -1), the corner of cell (0, 0) in map units, voxels per cell edge
+    (1..1024), na x nb cells (each 1..8192, na*nb <= 2^24), the height band, the span beyond which a cell is an obstacle, min_count."""
+    _fields_ = [("up_axis", C.c_int), ("up_sign", C.c_int), ("origin_a", C.c_double), ("origin_b", C.c_double), ("cell_voxels", C.c_int),
+                ("na", C.c_int), ("nb", C.c_int), ("up_lo", C.c_double), ("up_hi", C.c_double), ("obstacle_step", C.c_double),
+                ("min_count", C.c_int)]
+
+
+class VoxelGridOut(C.Structure):
+    """svo_voxel_grid_out: na*nb elements each; every pointer but cls may be None."""
+    _fields_ = [("cls", C.c_void_p), ("top", C.c_void_p), ("bottom", C.c_void_p), ("intensity", C.c_void_p), ("n_voxels", C.c_void_p),
+                ("n_points", C.c_void_p)]
+
+
+VOXEL_GRID_UNKNOWN, VOXEL_GRID_LEVEL, VOXEL_GRID_OBSTACLE = 0, 1, 2
+GRID_PRECHECK_DEFAULT = False  # svo_voxel_grid_set_mode's state of a new map
+GRID_COUNTS = ("n_qualifying", "n_in_band", "n_binned", "n_cells", "n_obstacle")
+
+
+def voxel_grid_default_params(voxel_size):
+    """svo_voxel_grid_default_params: the camera convention (y down), 0.5-unit cells, 256 x 256 of them starting at a = 0 and centred
+    on b = 0, the band -3 .. 2.5, obstacle_step 0.3, min_count 1 (not tuned on real imagery)."""
+    p = VoxelGridParams()
+    if lib().svo_voxel_grid_default_params(C.c_float(voxel_size), C.byref(p)) != 0:
+        raise SvoError("svo_voxel_grid_default_params: voxel_size must be finite and > 0")
+    return p
+
+
+def voxel_grid_workspace_bytes(na, nb):
+    """svo_voxel_grid_workspace_bytes: 32 * na * nb (no GPU involved); 0 for na or nb < 1."""
+    return int(lib().svo_voxel_grid_workspace_bytes(int(na), int(nb)))
+
+
+def voxel_grid_cell_of(params, voxel_size, a, b):
+    """svo_voxel_grid_cell_of: (inside, ia, ib) of the position (a, b) in map units along the grid's axes, by the grid's own rule."""
+    ia, ib = C.c_int(0), C.c_int(0)
+    rc = lib().svo_voxel_grid_cell_of(C.byref(params), C.c_float(voxel_size), C.c_double(a), C.c_double(b), C.byref(ia), C.byref(ib))
+    if rc < 0:
+        raise SvoError("svo_voxel_grid_cell_of: refused parameters, voxel_size or a NaN position")
+    return bool(rc), ia.value, ib.value
+
+
+def _grid_params(voxel_size, params, overrides):
+    return _params(lambda: voxel_grid_default_params(voxel_size), params, **overrides)
+
+
 SPECKLE_TILE = (64, 16)  # SVO_SPECKLE_TILE_W, SVO_SPECKLE_TILE_H
 
 
@@ -436,6 +482,8 @@ SYMBOLS = [
     "svo_pipeline_copy_keyframe_disparity", "svo_pipeline_group_copy_keyframe_disparity",
     "svo_voxel_render_default_params", "svo_voxel_render_workspace_bytes", "svo_voxel_map_render_dev", "svo_voxel_map_render_pose7_dev",
     "svo_voxel_map_render", "svo_voxel_render_set_mode",
+    "svo_voxel_grid_default_params", "svo_voxel_grid_workspace_bytes", "svo_voxel_grid_cell_of", "svo_voxel_map_grid_dev", "svo_voxel_map_grid",
+    "svo_voxel_grid_set_mode",
     "svo_voxel_map_remove_dev", "svo_voxel_map_remove_pose7_dev", "svo_voxel_map_remove_sync", "svo_voxel_map_move_dev", "svo_voxel_map_move_pose7_dev",
     "svo_voxel_ledger_bytes", "svo_voxel_ledger_create", "svo_voxel_ledger_destroy", "svo_voxel_ledger_insert_pose7_dev",
     "svo_voxel_ledger_update_pose7", "svo_voxel_ledger_retire", "svo_voxel_ledger_remove", "svo_voxel_ledger_ids", "svo_voxel_ledger_get",
@@ -547,6 +595,16 @@ def lib():
         L.svo_voxel_render_set_mode.argtypes = [vp, ci, ci]
         for f in ("svo_voxel_render_default_params", "svo_voxel_map_render_dev", "svo_voxel_map_render_pose7_dev", "svo_voxel_map_render",
                   "svo_voxel_render_set_mode"):
+            getattr(L, f).restype = ci
+        # the grid
+        L.svo_voxel_grid_default_params.argtypes = [C.c_float, vp]
+        L.svo_voxel_grid_workspace_bytes.argtypes = [ci, ci]
+        L.svo_voxel_grid_workspace_bytes.restype = sz
+        L.svo_voxel_grid_cell_of.argtypes = [vp, C.c_float, C.c_double, C.c_double, vp, vp]
+        L.svo_voxel_map_grid_dev.argtypes = [vp, vp, vp, vp, vp]
+        L.svo_voxel_map_grid.argtypes = [vp, vp, vp, vp]
+        L.svo_voxel_grid_set_mode.argtypes = [vp, ci]
+        for f in ("svo_voxel_grid_default_params", "svo_voxel_grid_cell_of", "svo_voxel_map_grid_dev", "svo_voxel_map_grid", "svo_voxel_grid_set_mode"):
             getattr(L, f).restype = ci
         # removal, move and the keyframe ledger
         i64 = C.c_int64
@@ -1054,6 +1112,36 @@ class VoxelMap:
     def render_set_mode(self, cooperative=True, precheck=False):
         """svo_voxel_render_set_mode (measurement aid): how the splat launch draws; no bit of a render depends on it."""
         self.ctx._chk(self.L.svo_voxel_render_set_mode(self.h, int(bool(cooperative)), int(bool(precheck))), "svo_voxel_render_set_mode")
+
+    def grid(self, params=None, workspace_ptr=None, cls_ptr=None, top_ptr=None, bottom_ptr=None, intensity_ptr=None, n_voxels_ptr=None,
+             n_points_ptr=None, counts_ptr=None, **overrides):
+        """svo_voxel_map_grid_dev: the map's ground plan, na x nb cells over two of its axes.  params (a VoxelGridParams; None: the
+        defaults for this map's voxel size) and / or its fields as keywords.  All pointers are the caller's device memory:
+        workspace_ptr voxel_grid_workspace_bytes(na, nb) bytes, cls_ptr na * nb uint8 (required), top_ptr / bottom_ptr float32,
+        intensity_ptr uint8, n_voxels_ptr uint32, n_points_ptr uint64 or None each, counts_ptr 5 uint64 GRID_COUNTS or None.
+        Asynchronous on the context's stream; returns {"cls", "top", "bottom", "intensity", "n_voxels", "n_points", "counts",
+        "workspace", "na", "nb"}: the pointers the outputs are behind once the stream reaches this point."""
+        prm = _grid_params(self.params.voxel_size, params, overrides)
+        out = VoxelGridOut(cls_ptr, top_ptr, bottom_ptr, intensity_ptr, n_voxels_ptr, n_points_ptr)
+        self.ctx._chk(self.L.svo_voxel_map_grid_dev(self.h, C.byref(prm), workspace_ptr, C.byref(out), counts_ptr), "svo_voxel_map_grid_dev")
+        return {"cls": cls_ptr, "top": top_ptr, "bottom": bottom_ptr, "intensity": intensity_ptr, "n_voxels": n_voxels_ptr,
+                "n_points": n_points_ptr, "counts": counts_ptr, "workspace": workspace_ptr, "na": prm.na, "nb": prm.nb}
+
+    def grid_host(self, params=None, **overrides):
+        """svo_voxel_map_grid: synchronous.  Returns (cls (na, nb) uint8 of VOXEL_GRID_UNKNOWN / LEVEL / OBSTACLE, top and bottom
+        (na, nb) float32 (-inf / +inf where unknown), intensity uint8, n_voxels uint32, n_points uint64, {GRID_COUNTS})."""
+        prm = _grid_params(self.params.voxel_size, params, overrides)
+        shape = (max(prm.na, 1), max(prm.nb, 1))
+        arrays = [np.empty(shape, t) for t in (np.uint8, np.float32, np.float32, np.uint8, np.uint32, np.uint64)]
+        out = VoxelGridOut(*(a.ctypes.data for a in arrays))
+        c = np.zeros(5, np.uint64)
+        self.ctx._chk(self.L.svo_voxel_map_grid(self.h, C.byref(prm), C.byref(out), _p(c)), "svo_voxel_map_grid")
+        return (*arrays, dict(zip(GRID_COUNTS, (int(v) for v in c))))
+
+    def grid_set_mode(self, precheck=None):
+        """svo_voxel_grid_set_mode (measurement aid): whether a load skips the walk's max atomics where it can; no bit of a grid depends
+        on it.  None: the library's default."""
+        self.ctx._chk(self.L.svo_voxel_grid_set_mode(self.h, int(GRID_PRECHECK_DEFAULT if precheck is None else bool(precheck))), "svo_voxel_grid_set_mode")
 
     def stats(self):
         """The four counters as a dict (synchronises)."""

@@ -38,6 +38,16 @@
 //   voxel_resolve_kernel : the workspace -> the CV_16S map and the u8 image, four pixels per thread (16-byte load, 8-byte and 4-byte
 //                          stores where the pointers allow it, else and in the tail pixel by pixel); counts the covered pixels.
 //
+//   voxel_grid_kernel    : the ground plan.  The carve's tiling; keys first, ci where occupied, the up axis's sum word
+//                          where the slot qualifies (24 B per qualifying slot), integers and f32 only: a qualifying voxel inside the
+//                          height band is binned by its key into a cell of the caller's workspace by two 64-bit atomic max and two
+//                          64-bit atomic adds whose values are not read back.  The lanes of a wavefront address unrelated cells;
+//                          nothing is merged inside the wavefront (no such form was built).  Optionally a relaxed load skips a max
+//                          atomic where the word already holds at least the value (svo_voxel_grid_set_mode; DESIGN §7j has the
+//                          figures and the default); it cannot change a bit.
+//   voxel_grid_resolve_kernel : the cells -> class, top, bottom, intensity and the two tallies, one cell per thread; counts the
+//                          occupied cells and the obstacles.
+//
 // Nothing passes between workgroups except order-independent relaxed device-scope atomics (docs/HISTORY.md, "No cache maintenance
 // inside kernels"): no fence, no acquire / release, no waiting.  In a launch that CLAIMS slots (insert, copy) the CAS's RETURN value
 // decides a probe, never a plain load; a launch that claims nothing (extraction, carve, splat, removal) reads keys an earlier launch
@@ -154,6 +164,26 @@ struct VoxelResolveArgs {
   int vec;         // pix 16-byte, disp 8-byte and inten 4-byte aligned: the vector form
   u64* counts;
 };
+
+struct VoxelGridArgs {
+  const u64 *keys, *ci, *sup;  // sup: the up axis's sum words, chosen by the host among sx / sy / sz
+  size_t cap;
+  u64* cells;  // 4 words per cell {top, bot, nvox, npts}, zeroed on the stream before the launch
+  int shift_up, shift_a, shift_b;  // 21 * axis: where each axis's index sits in a key
+  int up_sign, ka0, kb0, cell_voxels, na, nb;
+  unsigned min_count;
+  long long hlo, hhi;
+  u64* counts;  // {n_qualifying, n_in_band, n_binned, n_cells, n_obstacle}, zeroed on the stream before the launch; or null
+};
+
+struct VoxelGridResolveArgs {
+  const u64* cells;
+  size_t n;  // na * nb
+  long long step;
+  float voxel_size;
+  svo_voxel_grid_out o;
+  u64* counts;
+};
 }  // namespace
 
 struct svo_voxel_map {
@@ -164,6 +194,7 @@ struct svo_voxel_map {
   VoxelTable t{};
   int* d_counts = nullptr;
   int render_coop = 1, render_pre = 0;  // svo_voxel_render_set_mode; the defaults are the measured choice
+  int grid_pre = 0;                     // svo_voxel_grid_set_mode; likewise
 };
 
 // The counts of a launch.  vx_wave_sum: per-thread tallies -> their sums over the wavefront, in every lane.  vx_tally: a wavefront's
@@ -625,6 +656,87 @@ __global__ __launch_bounds__(VX_T) void voxel_resolve_kernel(VoxelResolveArgs a)
   vx_tally(n, a.counts + 3);  // n_pixels
 }
 
+// The signed index of one axis in a key.
+__device__ __forceinline__ int vx_key_index(u64 key, int shift) { return (int)((key >> shift) & 0x1FFFFFull) - (1 << 20); }
+
+// One of a cell's two max words.  PRE: a relaxed device-scope load skips the atomic where the word already holds at least the value.
+// Words only grow within the launch and the memset precedes it on the stream, so a stale load costs a needless atomic, never a
+// wrong skip: no bit of the grid depends on PRE (svo_voxel_grid_set_mode).
+template <bool PRE>
+__device__ __forceinline__ void vx_grid_max(u64* p, u64 v) {
+  if (PRE && __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= v) return;
+  __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <bool PRE>
+__global__ __launch_bounds__(VX_T) void voxel_grid_kernel(VoxelGridArgs a) {
+  const size_t first = vx_walk_first();
+  unsigned n_qual = 0, n_band = 0, n_bin = 0;
+#pragma unroll
+  for (int j = 0; j < VX_ITEMS; ++j) {
+    const size_t s = first + (size_t)j * VX_T;
+    if (s >= a.cap) continue;
+    const u64 key = a.keys[s];
+    if (key == VX_EMPTY) continue;
+    const u64 ci = a.ci[s];
+    const unsigned count = (unsigned)(ci >> 40);
+    if (count < a.min_count) continue;  // min_count >= 1: a carved slot stops here, nothing divides by 0
+    ++n_qual;
+    const long long g = (long long)vx_key_index(key, a.shift_up) * 65536ll + (long long)voxel_div40(a.sup[s], count);
+    const long long hgt = a.up_sign < 0 ? -g : g;
+    if (hgt < a.hlo || hgt > a.hhi) continue;
+    ++n_band;
+    const int ia = voxel_floordiv(vx_key_index(key, a.shift_a) - a.ka0, a.cell_voxels);
+    const int ib = voxel_floordiv(vx_key_index(key, a.shift_b) - a.kb0, a.cell_voxels);
+    if (ia < 0 || ia >= a.na || ib < 0 || ib >= a.nb) continue;
+    ++n_bin;
+    u64* cell = a.cells + 4 * ((size_t)ia * (size_t)a.nb + (size_t)ib);  // inside the workspace by the test above
+    const u64 top = ((u64)(hgt + (1ll << 37)) << 8) | voxel_div40(ci & ((1ull << 40) - 1ull), count);
+    vx_grid_max<PRE>(&cell[0], top);
+    vx_grid_max<PRE>(&cell[1], (u64)((1ll << 37) - hgt));
+    __hip_atomic_fetch_add(&cell[2], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(&cell[3], (u64)count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (!a.counts) return;  // uniform over the launch
+  unsigned n[3] = {n_qual, n_band, n_bin};
+  vx_wave_sum(n);
+  vx_tally(n, a.counts);
+}
+
+__global__ __launch_bounds__(VX_T) void voxel_grid_resolve_kernel(VoxelGridResolveArgs a) {
+  const size_t i = (size_t)blockIdx.x * VX_T + (size_t)threadIdx.x;
+  unsigned n_cells = 0, n_obstacle = 0;
+  if (i < a.n) {
+    const u64* cell = a.cells + 4 * i;
+    const u64 nvox = cell[2];
+    uint8_t cls = SVO_VOXEL_GRID_UNKNOWN, inten = 0;
+    float top = -__builtin_inff(), bottom = __builtin_inff();
+    u64 npts = 0;
+    if (nvox) {
+      const u64 t = cell[0];
+      const long long htop = (long long)(t >> 8) - (1ll << 37), hbot = (1ll << 37) - (long long)cell[1];
+      const double vs = (double)a.voxel_size;
+      cls = htop - hbot > a.step ? SVO_VOXEL_GRID_OBSTACLE : SVO_VOXEL_GRID_LEVEL;
+      top = (float)((double)htop / 65536.0 * vs);
+      bottom = (float)((double)hbot / 65536.0 * vs);
+      inten = (uint8_t)(t & 255ull);
+      npts = cell[3];
+      n_cells = 1;
+      n_obstacle = cls == SVO_VOXEL_GRID_OBSTACLE ? 1u : 0u;
+    }
+    a.o.cls[i] = cls;
+    if (a.o.top) a.o.top[i] = top;
+    if (a.o.bottom) a.o.bottom[i] = bottom;
+    if (a.o.intensity) a.o.intensity[i] = inten;
+    if (a.o.n_voxels) a.o.n_voxels[i] = (uint32_t)nvox;
+    if (a.o.n_points) a.o.n_points[i] = npts;
+  }
+  if (!a.counts) return;  // uniform over the launch
+  unsigned n[2] = {n_cells, n_obstacle};
+  vx_wave_sum(n);
+  vx_tally(n, a.counts + 3);  // n_cells, n_obstacle
+}
+
 // ----------------------------------------------------------------------------- host side
 // A refusal of host/voxel_args.h goes into the context: `call` is one of its checks with `&err` as its last argument.
 #define VOXEL_CHECK(ctx, call) do { const char* err = nullptr; if (call) { (ctx)->err = err; return SVO_ERR_INVALID; } } while (0)
@@ -984,6 +1096,101 @@ extern "C" int svo_voxel_map_render(svo_voxel_map* m, int width, int height, con
       });
   if (rc) return rc;
   if (counts) for (int i = 0; i < 4; ++i) counts[i] = c[i];
+  return SVO_OK;
+}
+
+// ----------------------------------------------------------------------------- the grid
+extern "C" int svo_voxel_grid_default_params(float voxel_size, svo_voxel_grid_params* params) { return voxel_grid_default_params(voxel_size, params); }
+
+extern "C" size_t svo_voxel_grid_workspace_bytes(int na, int nb) { return voxel_grid_workspace_bytes(na, nb); }
+
+extern "C" int svo_voxel_grid_cell_of(const svo_voxel_grid_params* params, float voxel_size, double a, double b, int* ia, int* ib) {
+  return voxel_grid_cell_of(params, voxel_size, a, b, ia, ib);
+}
+
+extern "C" int svo_voxel_grid_set_mode(svo_voxel_map* m, int precheck) {
+  if (!m) return SVO_ERR_INVALID;
+  m->grid_pre = precheck != 0;
+  return SVO_OK;
+}
+
+// The walk's two forms, [pre-check] (svo_voxel_grid_set_mode).
+static void (*const voxel_grid_form[2])(VoxelGridArgs) = {voxel_grid_kernel<false>, voxel_grid_kernel<true>};
+
+extern "C" int svo_voxel_map_grid_dev(svo_voxel_map* m, const svo_voxel_grid_params* prm, void* workspace, const svo_voxel_grid_out* out,
+                                      uint64_t* counts) {
+  if (!m) return SVO_ERR_INVALID;
+  svo_ctx* ctx = m->ctx;
+  svo_use_device(ctx);
+  VOXEL_CHECK(ctx, voxel_grid_check(prm, workspace, out, counts, &err));
+  VoxelGridKeys k;
+  voxel_grid_keys(prm, m->prm.voxel_size, &k);
+  const u64* const sums[3] = {m->t.sx, m->t.sy, m->t.sz};
+  VoxelGridArgs a{};
+  a.keys = m->t.keys; a.ci = m->t.ci; a.sup = sums[prm->up_axis];
+  a.cap = m->cap;
+  a.cells = static_cast<u64*>(workspace);
+  a.shift_up = 21 * prm->up_axis; a.shift_a = 21 * ((prm->up_axis + 1) % 3); a.shift_b = 21 * ((prm->up_axis + 2) % 3);
+  a.up_sign = prm->up_sign; a.ka0 = k.ka0; a.kb0 = k.kb0; a.cell_voxels = prm->cell_voxels; a.na = prm->na; a.nb = prm->nb;
+  a.min_count = (unsigned)prm->min_count;
+  a.hlo = k.hlo; a.hhi = k.hhi;
+  a.counts = reinterpret_cast<u64*>(counts);
+  VoxelGridResolveArgs b{};
+  b.cells = a.cells;
+  b.n = (size_t)prm->na * (size_t)prm->nb;
+  b.step = k.step;
+  b.voxel_size = m->prm.voxel_size;
+  b.o = *out;
+  b.counts = a.counts;
+  SvoProfScope prof(ctx, SVO_PROF_VOXEL_GRID);
+  SVO_HIP_CHECK(ctx, hipMemsetAsync(workspace, 0, voxel_grid_workspace_bytes(prm->na, prm->nb), ctx->stream));
+  if (counts) SVO_HIP_CHECK(ctx, hipMemsetAsync(counts, 0, 5 * sizeof(u64), ctx->stream));
+  hipLaunchKernelGGL(voxel_grid_form[m->grid_pre], dim3((unsigned)voxel_walk_groups(m->cap)), dim3(VX_T), 0, ctx->stream, a);
+  SVO_HIP_CHECK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(voxel_grid_resolve_kernel, dim3((unsigned)voxel_grid_resolve_groups(b.n)), dim3(VX_T), 0, ctx->stream, b);
+  SVO_HIP_CHECK(ctx, hipGetLastError());
+  return SVO_OK;
+}
+
+extern "C" int svo_voxel_map_grid(svo_voxel_map* m, const svo_voxel_grid_params* prm, const svo_voxel_grid_out* out, uint64_t* counts) {
+  if (!m) return SVO_ERR_INVALID;
+  svo_ctx* ctx = m->ctx;
+  svo_use_device(ctx);
+  VOXEL_CHECK(ctx, voxel_grid_params_check(prm, &err));
+  VOXEL_CHECK(ctx, voxel_grid_out_check(out, false, &err));
+  const size_t n = (size_t)prm->na * (size_t)prm->nb, n16 = (n + 15) & ~(size_t)15;  // every part 16-byte aligned
+  unsigned char* d = nullptr;  // 5 counts (6 words) | cells | n_points | top | bottom | n_voxels | cls | intensity
+  SVO_HIP_CHECK(ctx, hipMalloc((void**)&d, 6 * sizeof(u64) + 54 * n16));
+  VoxelTemp hold{d};
+  unsigned char* d_cells = d + 6 * sizeof(u64);
+  svo_voxel_grid_out o{};
+  o.n_points = reinterpret_cast<uint64_t*>(d_cells + 32 * n16);
+  o.top = reinterpret_cast<float*>(d_cells + 40 * n16);
+  o.bottom = reinterpret_cast<float*>(d_cells + 44 * n16);
+  o.n_voxels = reinterpret_cast<uint32_t*>(d_cells + 48 * n16);
+  o.cls = d_cells + 52 * n16;
+  o.intensity = d_cells + 53 * n16;
+  svo_voxel_grid_out asked = o;  // what the caller did not ask for is not written
+  if (!out->top) asked.top = nullptr;
+  if (!out->bottom) asked.bottom = nullptr;
+  if (!out->intensity) asked.intensity = nullptr;
+  if (!out->n_voxels) asked.n_voxels = nullptr;
+  if (!out->n_points) asked.n_points = nullptr;
+  u64 c[5] = {0, 0, 0, 0, 0};
+  const int rc = voxel_sync(
+      ctx, "voxel_map_grid", hipSuccess, [&] { return svo_voxel_map_grid_dev(m, prm, d_cells, &asked, reinterpret_cast<uint64_t*>(d)); },
+      [&] {
+        hipError_t e = hipMemcpyAsync(out->cls, o.cls, n, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && out->top) e = hipMemcpyAsync(out->top, o.top, 4 * n, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && out->bottom) e = hipMemcpyAsync(out->bottom, o.bottom, 4 * n, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && out->intensity) e = hipMemcpyAsync(out->intensity, o.intensity, n, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && out->n_voxels) e = hipMemcpyAsync(out->n_voxels, o.n_voxels, 4 * n, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && out->n_points) e = hipMemcpyAsync(out->n_points, o.n_points, 8 * n, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, ctx->stream);
+        return e;
+      });
+  if (rc) return rc;
+  if (counts) for (int i = 0; i < 5; ++i) counts[i] = c[i];
   return SVO_OK;
 }
 

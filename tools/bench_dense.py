@@ -38,6 +38,11 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      beside one more svo_voxel_map_insert_dev of the same cloud in the same run and the time hbm_copy needs for its 16 bytes per
      record; and the 96-lane load with clouds at step 4 with every lane's ledger holding four keyframes and moving all of them after
      each call, beside clouds alone (--ledger-only runs just these two).
+ 11. grid: one svo_voxel_map_grid_dev of each filled map of section 7 (before section 8 carves it) at the defaults for its voxel size
+     (0.5 m cells, 256 x 256 of them, the band -3 .. 2.5), the origin shifted so that the last cloud's pose is at the start of the a
+     axis and the middle of the b axis ("voxel_grid" bracket: two memsets and both launches, mean of 5), with the five counts, the
+     binned voxels per occupied cell, and the time hbm_copy needs for 16 bytes per slot + 8 per qualifying slot + 64 per cell + the
+     26 per cell of the outputs, and the same grid in both modes of the walk (svo_voxel_grid_set_mode); its yardsticks are the carve with every voxel protected and the render of the same run and map.
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -264,7 +269,8 @@ def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy):
                         "extract_ms": ms / k, "extract_n_total": int(c2.cpu()[0]), "table_bytes_bound_ms": 1e3 * 40 * vm.capacity / copy,
                         "extract_share_of_bound": (1e3 * 40 * vm.capacity / copy) / (ms / k)})
             out[-1].update(remove_and_move(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, copy))
-            out[-1].update(render_view(S, torch, ctx, cam, vm, np.asarray(m12[batch - 1]), warmup, copy))  # before the carve changes the map
+            out[-1].update(grid_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # before the carve changes the map, as the render
+            out[-1].update(render_view(S, torch, ctx, cam, vm, np.asarray(m12[batch - 1]), warmup, copy))
             out[-1].update(carve_and_copy(S, torch, ctx, cam, dm, vm, np.asarray(m12[batch - 1]), warmup, copy))
             vm.close()
     return out
@@ -307,6 +313,49 @@ def remove_and_move(torch, ctx, vm, cloud, n, angle, forward, warmup, copy):
     out["remove_move_bound_ms"] = 1e3 * 16 * n / copy
     out["remove_move_points"] = n
     return out
+
+
+def grid_view(S, torch, ctx, vm, c2w, warmup, copy):
+    """Section 11 for one filled map: its ground plan around the last cloud's pose, at the defaults."""
+    prm = S.api.voxel_grid_default_params(vm.params.voxel_size)
+    x, z = float(c2w.reshape(3, 4)[0, 3]), float(c2w.reshape(3, 4)[2, 3])
+    prm.origin_a, prm.origin_b = prm.origin_a + z, prm.origin_b + x  # a = z forward, b = x right
+    n = prm.na * prm.nb
+    ws = torch.empty(4 * n, dtype=torch.int64, device="cuda")
+    cls, inten = (torch.empty(n, dtype=torch.uint8, device="cuda") for _ in range(2))
+    top, bottom = (torch.empty(n, dtype=torch.float32, device="cuda") for _ in range(2))
+    nvox = torch.empty(n, dtype=torch.int32, device="cuda")
+    npts, cnt = torch.empty(n, dtype=torch.int64, device="cuda"), torch.zeros(5, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    kw = dict(workspace_ptr=ws.data_ptr(), cls_ptr=cls.data_ptr(), top_ptr=top.data_ptr(), bottom_ptr=bottom.data_ptr(), intensity_ptr=inten.data_ptr(),
+              n_voxels_ptr=nvox.data_ptr(), n_points_ptr=npts.data_ptr(), counts_ptr=cnt.data_ptr())
+
+    def timed(pre):
+        vm.grid_set_mode(pre)
+        for _ in range(warmup):
+            vm.grid(prm, **kw)
+        ctx.profile_select("voxel_grid")
+        for _ in range(5):
+            vm.grid(prm, **kw)
+        ms, k = ctx.profile_read()
+        ctx.profile_select("")
+        vm.grid_set_mode()  # back to the default
+        return ms / k, tuple(t.cpu().numpy().tobytes() for t in (ws, cls, top, bottom, inten, nvox, npts, cnt))
+
+    modes = {}
+    for _ in range(2):  # alternating
+        for name, pre in (("no pre-check", False), ("pre-check", True)):
+            got = timed(pre)
+            modes.setdefault(name, []).append(got[0])
+            assert got[1] == modes.setdefault("bytes", got[1]), "a mode of the walk changed the grid"
+    del modes["bytes"]
+    ms, k = timed(None)[0], 1
+    counts = [int(v) for v in cnt.cpu()]
+    c = cls.cpu().numpy()
+    bound = 1e3 * (16 * vm.capacity + 8 * counts[0] + (64 + 26) * n) / copy
+    return {"grid_ms": ms / k, "grid_counts": counts, "grid_cells": [prm.na, prm.nb], "grid_cell_voxels": prm.cell_voxels,
+            "grid_classes": [int((c == v).sum()) for v in (0, 1, 2)], "grid_binned_per_cell": counts[2] / max(counts[3], 1),
+            "grid_bound_ms": bound, "grid_share_of_bound": bound / (ms / k), "grid_modes_ms": modes}
 
 
 def render_view(S, torch, ctx, cam, vm, c2w, warmup, copy):
@@ -623,6 +672,13 @@ def main():
                         f"({1e3 * c['render_r0_bound_ms']:.1f} us)\n"
                         f"  the default render by drawing mode of the splat launch (same image in all four, us): "
                         f"{ {k: round(1e3 * v, 1) for k, v in c['render_modes_ms'].items()} }\n"
+                        f"  grid of {c['grid_cells'][0]} x {c['grid_cells'][1]} cells of {c['grid_cell_voxels']} voxels around the last cloud's pose (two memsets + walk + "
+                        f"resolve, mean of 5): {1e3 * c['grid_ms']:.1f} us, counts {c['grid_counts']} (qualifying, in band, binned = 4 atomic requests each, cells, "
+                        f"obstacles), classes {c['grid_classes']} (unknown, level, obstacle), {c['grid_binned_per_cell']:.1f} binned voxels per occupied cell; "
+                        f"16 B per slot + 8 B per qualifying slot + 90 B per cell at hbm_copy {1e3 * c['grid_bound_ms']:.1f} us -> {100 * c['grid_share_of_bound']:.1f} % "
+                        f"of that bound; {c['grid_ms'] / c['carve_dry_ms']:.2f} x the carve with every voxel protected, {c['grid_ms'] / c['render_ms']:.2f} x the render\n"
+                        f"  the grid by mode of the walk (same bytes in both, two alternating blocks of 5, us): "
+                        f"{ {k: [round(1e3 * x, 1) for x in v] for k, v in c['grid_modes_ms'].items()} }; the figure above is the default mode's\n"
                         f"  removal of the last inserted cloud ({c['remove_move_points']} points, mean of 5): {1e3 * c['remove_ms']:.1f} us, counts {c['remove_counts']} "
                         f"(removed, rejected, missing, short); move to a pose 1 cm and 0.1 degrees away (removal + insert): {1e3 * c['move_ms']:.1f} us, counts "
                         f"{c['move_counts']}; the same cloud inserted once more, same run: {1e3 * c['insert_ms']:.1f} us -> removal / insert "
