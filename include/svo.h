@@ -102,7 +102,7 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * svo_voxel_map_render_dev: the two memsets and both launches), "voxel_remove" (one svo_voxel_map_remove_dev: the counts' memset and
  * the launch), "voxel_move" (one svo_voxel_map_move_dev: the counts' memset, the removal and the insert; the launches inside it
  * are not counted as "voxel_remove" or "voxel_insert"), "voxel_grid" (one svo_voxel_map_grid_dev: the memsets of the workspace
- * and the counts and both launches);
+ * and the counts and both launches), "grid_clearance" (one svo_grid_clearance_dev: the counts' memset and both launches);
  * NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
@@ -721,6 +721,66 @@ int svo_voxel_map_grid(svo_voxel_map* map, const svo_voxel_grid_params* params, 
  * where the word already holds at least the value (words only grow within the launch, so a stale load costs a needless atomic, never
  * a wrong skip).  It cannot change a bit of the outputs or of the workspace.  DESIGN 7j gives the figures and the default. */
 int svo_voxel_grid_set_mode(svo_voxel_map* map, int precheck);
+
+/* Ground plan clearance: per cell of a u8 class grid the exact squared distance, in cells, to the nearest SOURCE cell, which cell
+ * that is, the distance in map units and a robot-radius inflation: what a planner asks a ground plan first.  It works on any
+ * na x nb byte grid on the device, cell = ia*nb + ib (the layout of svo_voxel_map_grid*'s cls), is stated in integers, depends
+ * on no thread order and is tested with ==.  Two launches: a row pass writes, per cell, the signed offset to the nearest source of
+ * its own row into the caller's workspace; a column pass combines the rows.  No voxel map is involved.
+ *   1. A cell is a SOURCE iff cls < 32 and bit cls of source_mask is set.  Values >= 32 are never sources.
+ *   2. dist2[ia, ib] (u32) is the minimum over all source cells (ja, jb) of (ia-ja)^2 + (ib-jb)^2, provided that minimum is
+ *      <= max_dist^2; otherwise it is SVO_GRID_CLEARANCE_NONE = 0xFFFFFFFF.  A source has dist2 = 0.
+ *   3. nearest[ia, ib] (u32) is the SMALLEST cell index ja*nb + jb among the sources that attain that minimum, and NONE where dist2
+ *      is NONE.  A source names itself.
+ *   4. clearance[cell] (f32) = (float)(sqrt((double)dist2) * cell_size): a correctly rounded f64 square root, one f64 product, one
+ *      rounding to f32; +infinity where dist2 is NONE.
+ *   5. blocked[cell] (u8) is 2 for a source, 1 for a non-source with dist2 <= R2, otherwise 0, where rc = inflate_radius / cell_size
+ *      and R2 = (u64)floor(rc * rc) clamped to max_dist^2 (f64, computed once on the host).  inflate_radius 0 blocks sources only.
+ *   6. counts = {n_sources, n_reached, n_unreached, n_blocked}: 4 u64 on the device, or NULL.  n_reached: non-sources with
+ *      dist2 != NONE; n_unreached: cells with dist2 == NONE; n_blocked: cells of value 1 (counted whether or not blocked is asked
+ *      for).  The three first sum to na*nb.  Zeroed on the stream before the first launch; one relaxed atomicAdd per workgroup and
+ *      non-zero counter.
+ *   7. dist2 is required, every other output may be NULL and is then not written.  workspace: svo_grid_clearance_workspace_bytes(na,
+ *      nb) = 4*na*nb bytes of device memory, 4-byte aligned; its contents before the call are meaningless, afterwards it holds the
+ *      row pass's int32 offsets.  cls is only read; it must not overlap the workspace or an output.
+ *   8. SVO_ERR_INVALID with the argument named, and nothing launched, for: a null ctx, cls, params, workspace, out or out->dist2;
+ *      na or nb outside 1..8192 or na*nb > 2^24; source_mask 0; max_dist outside 1..8191; a cell_size that is not finite and > 0; an
+ *      inflate_radius that is not finite and >= 0; a workspace, dist2, nearest or clearance that is not 4-byte aligned, counts not
+ *      8-byte aligned.  The context stays usable.
+ * max_dist is part of the contract in the way SVO_VOXEL_MAX_PROBES is: it bounds what a cell far from every source costs (2 *
+ * max_dist + 1 cells of its row and as many rows), and cells farther than that from every source are NONE, not "far".
+ * EXACTNESS.  A source at distance <= max_dist lies inside the +-max_dist square the two passes cover, everything outside is
+ * farther.  The sources that attain a cell's minimum and have the smallest row ja are, in that row, the nearest to column ib, so the
+ * row pass's choice (the nearer of ib-g and ib+g, the left one at equal g) is among them and is the one with the smallest index.
+ * The defaults are NOT tuned on real data: the grid's na and nb, cell_size = cell_voxels * (double)voxel_size, source_mask =
+ * 1 << SVO_VOXEL_GRID_OBSTACLE, max_dist 64 cells, inflate_radius 0.
+ * The pipeline never computes a clearance by itself; call it after the grid it reads. */
+#define SVO_GRID_CLEARANCE_NONE 0xFFFFFFFFu
+typedef struct svo_grid_clearance_params {
+  int na, nb;             /* each 1..8192, na*nb <= 2^24 */
+  uint32_t source_mask;   /* != 0: bit c set makes class c (0..31) a source */
+  int max_dist;           /* 1..8191, in cells */
+  double cell_size;       /* finite, > 0: a cell's edge in map units */
+  double inflate_radius;  /* finite, >= 0, in map units */
+} svo_grid_clearance_params;
+typedef struct svo_grid_clearance_out { /* na*nb elements each; every pointer but dist2 may be NULL */
+  uint32_t* dist2;
+  uint32_t* nearest;
+  float* clearance;
+  uint8_t* blocked;
+} svo_grid_clearance_out;
+/* The defaults above for a grid of svo_voxel_map_grid* over a map of this voxel size.  Pure; SVO_ERR_INVALID for a null pointer, a
+ * voxel_size that is not finite and > 0, or a grid whose na, nb or cell_voxels svo_voxel_map_grid_dev would refuse. */
+int svo_grid_clearance_default_params(const svo_voxel_grid_params* grid, float voxel_size, svo_grid_clearance_params* out);
+/* 4*na*nb; 0 for na or nb < 1.  Pure. */
+size_t svo_grid_clearance_workspace_bytes(int na, int nb);
+/* DEVICE pointers, asynchronous on svo_stream(ctx): the counts' memset, then two launches. */
+int svo_grid_clearance_dev(svo_ctx* ctx, const uint8_t* cls, const svo_grid_clearance_params* params, void* workspace,
+                           const svo_grid_clearance_out* out, uint64_t* counts);
+/* HOST cls and outputs, synchronous: the device copies and the workspace are allocated and freed by the call.  out: host pointers
+ * (no alignment asked), dist2 required; counts: 4 u64 on the host or NULL. */
+int svo_grid_clearance(svo_ctx* ctx, const uint8_t* cls, const svo_grid_clearance_params* params, const svo_grid_clearance_out* out,
+                       uint64_t* counts);
 
 /* ------------------------------------------------------------------- a8 --
  * ImageProcessor::triangulate_stereo's reprojection loop

@@ -293,6 +293,42 @@ def _grid_params(voxel_size, params, overrides):
     return _params(lambda: voxel_grid_default_params(voxel_size), params, **overrides)
 
 
+class GridClearanceParams(C.Structure):
+    """svo_grid_clearance_params: na x nb cells (each 1..8192, na*nb <= 2^24), the classes that are sources as a bit mask (!= 0),
+    max_dist in cells (1..8191), a cell's edge and the inflation radius in map units."""
+    _fields_ = [("na", C.c_int), ("nb", C.c_int), ("source_mask", C.c_uint32), ("max_dist", C.c_int), ("cell_size", C.c_double),
+                ("inflate_radius", C.c_double)]
+
+
+class GridClearanceOut(C.Structure):
+    """svo_grid_clearance_out: na*nb elements each; every pointer but dist2 may be None."""
+    _fields_ = [("dist2", C.c_void_p), ("nearest", C.c_void_p), ("clearance", C.c_void_p), ("blocked", C.c_void_p)]
+
+
+GRID_CLEARANCE_NONE = 0xFFFFFFFF  # SVO_GRID_CLEARANCE_NONE
+GRID_CLEARANCE_COUNTS = ("n_sources", "n_reached", "n_unreached", "n_blocked")
+
+
+def grid_clearance_default_params(grid, voxel_size):
+    """svo_grid_clearance_default_params for a VoxelGridParams and its map's voxel size: the grid's na x nb, cell_size = cell_voxels *
+    voxel_size, OBSTACLE cells as the sources, max_dist 64 cells, inflate_radius 0 (not tuned on real data)."""
+    p = GridClearanceParams()
+    if lib().svo_grid_clearance_default_params(C.byref(grid), C.c_float(voxel_size), C.byref(p)) != 0:
+        raise SvoError("svo_grid_clearance_default_params: voxel_size must be finite and > 0, the grid's na, nb and cell_voxels in range")
+    return p
+
+
+def grid_clearance_workspace_bytes(na, nb):
+    """svo_grid_clearance_workspace_bytes: 4 * na * nb (no GPU involved); 0 for na or nb < 1."""
+    return int(lib().svo_grid_clearance_workspace_bytes(int(na), int(nb)))
+
+
+def _clearance_params(params, overrides):
+    """params and / or its fields as keywords; without params the mask, max_dist and inflate_radius of the defaults, and na, nb and
+    cell_size from the keywords (the library refuses what is left at 0)."""
+    return _params(lambda: GridClearanceParams(0, 0, 1 << VOXEL_GRID_OBSTACLE, 64, 0.0, 0.0), params, **overrides)
+
+
 SPECKLE_TILE = (64, 16)  # SVO_SPECKLE_TILE_W, SVO_SPECKLE_TILE_H
 
 
@@ -484,6 +520,7 @@ SYMBOLS = [
     "svo_voxel_map_render", "svo_voxel_render_set_mode",
     "svo_voxel_grid_default_params", "svo_voxel_grid_workspace_bytes", "svo_voxel_grid_cell_of", "svo_voxel_map_grid_dev", "svo_voxel_map_grid",
     "svo_voxel_grid_set_mode",
+    "svo_grid_clearance_default_params", "svo_grid_clearance_workspace_bytes", "svo_grid_clearance_dev", "svo_grid_clearance",
     "svo_voxel_map_remove_dev", "svo_voxel_map_remove_pose7_dev", "svo_voxel_map_remove_sync", "svo_voxel_map_move_dev", "svo_voxel_map_move_pose7_dev",
     "svo_voxel_ledger_bytes", "svo_voxel_ledger_create", "svo_voxel_ledger_destroy", "svo_voxel_ledger_insert_pose7_dev",
     "svo_voxel_ledger_update_pose7", "svo_voxel_ledger_retire", "svo_voxel_ledger_remove", "svo_voxel_ledger_ids", "svo_voxel_ledger_get",
@@ -605,6 +642,14 @@ def lib():
         L.svo_voxel_map_grid.argtypes = [vp, vp, vp, vp]
         L.svo_voxel_grid_set_mode.argtypes = [vp, ci]
         for f in ("svo_voxel_grid_default_params", "svo_voxel_grid_cell_of", "svo_voxel_map_grid_dev", "svo_voxel_map_grid", "svo_voxel_grid_set_mode"):
+            getattr(L, f).restype = ci
+        # the ground plan clearance
+        L.svo_grid_clearance_default_params.argtypes = [vp, C.c_float, vp]
+        L.svo_grid_clearance_workspace_bytes.argtypes = [ci, ci]
+        L.svo_grid_clearance_workspace_bytes.restype = sz
+        L.svo_grid_clearance_dev.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.svo_grid_clearance.argtypes = [vp, vp, vp, vp, vp]
+        for f in ("svo_grid_clearance_default_params", "svo_grid_clearance_dev", "svo_grid_clearance"):
             getattr(L, f).restype = ci
         # removal, move and the keyframe ledger
         i64 = C.c_int64
@@ -903,6 +948,39 @@ class Context:
         self._chk(self.L.svo_stereo_sgm_batch_dev(self.h, left_ptr, right_ptr, batch, width, height, row_stride, image_stride, ndisp, block,
                                                   _ref(params), workspace_ptr, workspace_bytes, disp16_ptr, cost16_ptr),
                   "svo_stereo_sgm_batch_dev")
+
+    # ---- ground plan clearance
+    def grid_clearance(self, cls_ptr, params=None, workspace_ptr=None, dist2_ptr=None, nearest_ptr=None, clearance_ptr=None, blocked_ptr=None,
+                       counts_ptr=None, **overrides):
+        """svo_grid_clearance_dev: per cell of the na x nb uint8 class grid behind cls_ptr the squared distance in cells to the nearest
+        source cell, that cell's index, the distance in map units and the inflation.  params (a GridClearanceParams) and / or its
+        fields as keywords.  All pointers are the caller's device memory: workspace_ptr grid_clearance_workspace_bytes(na, nb) bytes,
+        dist2_ptr na * nb uint32 (required), nearest_ptr uint32, clearance_ptr float32, blocked_ptr uint8 or None each, counts_ptr 4
+        uint64 GRID_CLEARANCE_COUNTS or None.  Asynchronous on the context's stream; returns {"dist2", "nearest", "clearance",
+        "blocked", "counts", "workspace", "na", "nb"}: the pointers the outputs are behind once the stream reaches this point."""
+        prm = _clearance_params(params, overrides)
+        out = GridClearanceOut(dist2_ptr, nearest_ptr, clearance_ptr, blocked_ptr)
+        self._chk(self.L.svo_grid_clearance_dev(self.h, cls_ptr, C.byref(prm), workspace_ptr, C.byref(out), counts_ptr), "svo_grid_clearance_dev")
+        return {"dist2": dist2_ptr, "nearest": nearest_ptr, "clearance": clearance_ptr, "blocked": blocked_ptr, "counts": counts_ptr,
+                "workspace": workspace_ptr, "na": prm.na, "nb": prm.nb}
+
+    def grid_clearance_host(self, cls, params=None, **overrides):
+        """svo_grid_clearance: synchronous.  cls: an (na, nb) uint8 array (na and nb are taken from it unless given).  Returns (dist2
+        and nearest (na, nb) uint32 with GRID_CLEARANCE_NONE where no source is within max_dist, clearance float32 (+inf there),
+        blocked uint8 (2 a source, 1 inside the inflation, 0 free), {GRID_CLEARANCE_COUNTS})."""
+        cls = np.ascontiguousarray(cls, np.uint8)
+        if cls.ndim != 2:
+            raise ValueError("grid_clearance_host: cls must be an (na, nb) array")
+        if params is None:
+            overrides = {"na": cls.shape[0], "nb": cls.shape[1], **overrides}
+        prm = _clearance_params(params, overrides)
+        if (prm.na, prm.nb) != cls.shape:
+            raise ValueError(f"grid_clearance_host: cls is {cls.shape}, the parameters say {(prm.na, prm.nb)}")
+        arrays = [np.empty(cls.shape, t) for t in (np.uint32, np.uint32, np.float32, np.uint8)]
+        out = GridClearanceOut(*(a.ctypes.data for a in arrays))
+        c = np.zeros(4, np.uint64)
+        self._chk(self.L.svo_grid_clearance(self.h, _p(cls), C.byref(prm), C.byref(out), _p(c)), "svo_grid_clearance")
+        return (*arrays, dict(zip(GRID_CLEARANCE_COUNTS, (int(v) for v in c))))
 
     # ---- a8
     def triangulate(self, xy, disp, pose16, focal, cx, cy, baseline):

@@ -43,6 +43,12 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      axis and the middle of the b axis ("voxel_grid" bracket: two memsets and both launches, mean of 5), with the five counts, the
      binned voxels per occupied cell, and the time hbm_copy needs for 16 bytes per slot + 8 per qualifying slot + 64 per cell + the
      26 per cell of the outputs, and the same grid in both modes of the walk (svo_voxel_grid_set_mode); its yardsticks are the carve with every voxel protected and the render of the same run and map.
+ 12. clearance: one svo_grid_clearance_dev (all four outputs and the counts; "grid_clearance" bracket: the counts' memset and both
+     launches, mean of 5) of section 11's grid of each filled map at the defaults (OBSTACLE cells are the sources, max_dist 64) and
+     with UNKNOWN cells as sources too, and of a synthetic 2048 x 2048 grid at source densities 0 (every cell searches its whole
+     window), 0.001 and 0.1 with max_dist 64 and at 0.001 with max_dist 512; each beside the time hbm_copy needs for 22 bytes per
+     cell (cls read, the offsets written and read, 13 bytes of outputs) and, for the 256 x 256 grids, the loop steps of both passes
+     summed over the cells, counted on the host from cls.
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -202,6 +208,8 @@ def standalone(S, torch, batch, warmup, reps):
                   "bytes_per_s": nbytes / per, "share_of_copy_rate": nbytes / per / copy,
                   "valid_per_pair_sgm": float((dm2 != -16).sum().item()) / batch, "valid_per_pair_bm": float((dm != -16).sum().item()) / batch}
     out["voxel"] = voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy)
+    out["clearance_synthetic"] = [clearance_case(S, torch, ctx, clearance_random(torch, 2048, 2048, density), 4, md, 0.5, warmup, copy, density=density)
+                                  for density, md in ((0.0, 64), (0.001, 64), (0.1, 64), (0.001, 512))]
     ctx.close()
     return out
 
@@ -270,9 +278,11 @@ def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy):
                         "extract_share_of_bound": (1e3 * 40 * vm.capacity / copy) / (ms / k)})
             out[-1].update(remove_and_move(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, copy))
             out[-1].update(grid_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # before the carve changes the map, as the render
+            out[-1].update(clearance_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # of the same grid, before the carve too
             out[-1].update(render_view(S, torch, ctx, cam, vm, np.asarray(m12[batch - 1]), warmup, copy))
             out[-1].update(carve_and_copy(S, torch, ctx, cam, dm, vm, np.asarray(m12[batch - 1]), warmup, copy))
             vm.close()
+            print(f"bench_dense: voxel map at cloud step {step}, voxel {vs} m done", file=sys.stderr, flush=True)
     return out
 
 
@@ -356,6 +366,86 @@ def grid_view(S, torch, ctx, vm, c2w, warmup, copy):
     return {"grid_ms": ms / k, "grid_counts": counts, "grid_cells": [prm.na, prm.nb], "grid_cell_voxels": prm.cell_voxels,
             "grid_classes": [int((c == v).sum()) for v in (0, 1, 2)], "grid_binned_per_cell": counts[2] / max(counts[3], 1),
             "grid_bound_ms": bound, "grid_share_of_bound": bound / (ms / k), "grid_modes_ms": modes}
+
+
+def clearance_steps(cls, mask, max_dist):
+    """The loop steps of the two passes summed over the cells, as the contract's suggested search takes them (one step looks at
+    up to two cells): the row pass left before right until a source or the row's end, the column pass outward until g * g > best."""
+    na, nb = cls.shape
+    c = cls.astype(np.int64)
+    src = (c < 32) & (((np.int64(mask) >> np.minimum(c, 31)) & 1) == 1)
+    none = np.int64(1) << 40
+    off = np.full((na, nb), none)
+    ib = np.arange(nb)[None, :]
+    for g in range(min(max_dist, nb - 1) + 1):
+        left = np.zeros((na, nb), bool)
+        left[:, g:] = src[:, :nb - g] if g else src
+        right = np.zeros((na, nb), bool)
+        right[:, :nb - g] = src[:, g:] if g else src
+        off = np.where((off == none) & left, -g, np.where((off == none) & ~left & right, g, off))
+    row_reach = np.minimum(max_dist, np.maximum(ib, nb - 1 - ib))
+    row_steps = np.where(off == none, row_reach + 1, np.abs(off) + 1)
+    best = np.full((na, nb), none)
+    for g in range(min(max_dist, na - 1) + 1):
+        for shifted in ((off[:na - g], slice(g, na)), (off[g:], slice(0, na - g))):
+            o, rows = shifted
+            best[rows] = np.minimum(best[rows], np.where(o == none, none, g * g + o * o))
+    ia = np.arange(na)[:, None]
+    col_reach = np.minimum(max_dist, np.maximum(ia, na - 1 - ia))
+    col_steps = np.minimum(col_reach, np.floor(np.sqrt(np.minimum(best, 1 << 30).astype(np.float64))).astype(np.int64)) + 1
+    return int(row_steps.sum()), int(col_steps.sum())
+
+
+def clearance_random(torch, na, nb, density, seed=12):
+    g = torch.Generator(device="cuda")
+    g.manual_seed(seed)
+    return (torch.rand((na, nb), generator=g, device="cuda") < density).to(torch.uint8) * 2  # OBSTACLE with this probability, else UNKNOWN
+
+
+def clearance_case(S, torch, ctx, cls, mask, max_dist, cell_size, warmup, copy, steps=False, density=None):
+    """Section 12 for one (na, nb) uint8 device grid."""
+    na, nb = cls.shape
+    n = na * nb
+    prm = S.api.GridClearanceParams(na, nb, mask, max_dist, cell_size, 2.0 * cell_size)
+    ws, d2, near = (torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(3))
+    clr = torch.empty(n, dtype=torch.float32, device="cuda")
+    blk = torch.empty(n, dtype=torch.uint8, device="cuda")
+    cnt = torch.zeros(4, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    kw = dict(workspace_ptr=ws.data_ptr(), dist2_ptr=d2.data_ptr(), nearest_ptr=near.data_ptr(), clearance_ptr=clr.data_ptr(),
+              blocked_ptr=blk.data_ptr(), counts_ptr=cnt.data_ptr())
+    for _ in range(warmup):
+        ctx.grid_clearance(cls.data_ptr(), prm, **kw)
+    ctx.profile_select("grid_clearance")
+    for _ in range(5):
+        ctx.grid_clearance(cls.data_ptr(), prm, **kw)
+    ms, k = ctx.profile_read()
+    ctx.profile_select("")
+    bound = 1e3 * 22 * n / copy
+    out = {"cells": [na, nb], "source_mask": mask, "max_dist": max_dist, "ms": ms / k, "counts": [int(v) for v in cnt.cpu()],
+           "bound_ms": bound, "share_of_bound": bound / (ms / k)}
+    if density is not None:
+        out["density"] = density
+    if steps:
+        out["steps"] = clearance_steps(cls.cpu().numpy(), mask, max_dist)
+    return out
+
+
+def clearance_view(S, torch, ctx, vm, c2w, warmup, copy):
+    """Section 12 for one filled map: the clearance of section 11's grid, with OBSTACLE cells as the sources and with UNKNOWN too."""
+    gp = S.api.voxel_grid_default_params(vm.params.voxel_size)
+    x, z = float(c2w.reshape(3, 4)[0, 3]), float(c2w.reshape(3, 4)[2, 3])
+    gp.origin_a, gp.origin_b = gp.origin_a + z, gp.origin_b + x
+    n = gp.na * gp.nb
+    ws = torch.empty(4 * n, dtype=torch.int64, device="cuda")
+    cls = torch.empty(n, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    vm.grid(gp, workspace_ptr=ws.data_ptr(), cls_ptr=cls.data_ptr())
+    ctx.sync()
+    cp = S.api.grid_clearance_default_params(gp, vm.params.voxel_size)
+    grid = cls.reshape(gp.na, gp.nb)
+    return {"clearance": [clearance_case(S, torch, ctx, grid, mask, cp.max_dist, cp.cell_size, warmup, copy, steps=True)
+                          for mask in (cp.source_mask, cp.source_mask | 1 << S.api.VOXEL_GRID_UNKNOWN)]}
 
 
 def render_view(S, torch, ctx, cam, vm, c2w, warmup, copy):
@@ -679,11 +769,20 @@ def main():
                         f"of that bound; {c['grid_ms'] / c['carve_dry_ms']:.2f} x the carve with every voxel protected, {c['grid_ms'] / c['render_ms']:.2f} x the render\n"
                         f"  the grid by mode of the walk (same bytes in both, two alternating blocks of 5, us): "
                         f"{ {k: [round(1e3 * x, 1) for x in v] for k, v in c['grid_modes_ms'].items()} }; the figure above is the default mode's\n"
+                        + "".join(
+                            f"  clearance of that grid, sources = classes of mask {k['source_mask']:#x}, max_dist {k['max_dist']} (counts' memset + row pass + column pass, all four "
+                            f"outputs, mean of 5): {1e3 * k['ms']:.1f} us, counts {k['counts']} (sources, reached, unreached, blocked at a radius of 2 cells); loop steps "
+                            f"summed over the cells {k['steps'][0]} (row pass) + {k['steps'][1]} (column pass); 22 B per cell at hbm_copy {1e3 * k['bound_ms']:.2f} us -> "
+                            f"{100 * k['share_of_bound']:.1f} % of that bound\n" for k in c['clearance']) +
                         f"  removal of the last inserted cloud ({c['remove_move_points']} points, mean of 5): {1e3 * c['remove_ms']:.1f} us, counts {c['remove_counts']} "
                         f"(removed, rejected, missing, short); move to a pose 1 cm and 0.1 degrees away (removal + insert): {1e3 * c['move_ms']:.1f} us, counts "
                         f"{c['move_counts']}; the same cloud inserted once more, same run: {1e3 * c['insert_ms']:.1f} us -> removal / insert "
                         f"{c['remove_ms'] / c['insert_ms']:.2f}, move / insert {c['move_ms'] / c['insert_ms']:.2f}; 16 B per record at hbm_copy "
                         f"{1e3 * c['remove_move_bound_ms']:.2f} us\n")
+            for k in s["clearance_synthetic"]:
+                f.write(f"clearance of a synthetic {k['cells'][0]} x {k['cells'][1]} grid, source density {k['density']}, max_dist {k['max_dist']} (all four outputs, mean of 5): "
+                        f"{1e3 * k['ms']:.1f} us, counts {k['counts']} (sources, reached, unreached, blocked); 22 B per cell at hbm_copy {1e3 * k['bound_ms']:.1f} us -> "
+                        f"{100 * k['share_of_bound']:.1f} % of that bound\n")
             if g and "ratio_ledger_to_clouds" in g:
                 f.write(f"{g['lanes']} lanes in {g['groups']} groups, {g['frames_per_step_per_lane']}-frame steps, {g['rounds']} alternating rounds of {g['steps']} steps, clouds at "
                         f"step {g['cloud_step']}, every lane's ledger holding {g['ledger_held_per_lane']} keyframes and moving all of them (1 cm, 0.1 degrees) after each call: "
