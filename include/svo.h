@@ -102,8 +102,8 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * svo_voxel_map_render_dev: the two memsets and both launches), "voxel_remove" (one svo_voxel_map_remove_dev: the counts' memset and
  * the launch), "voxel_move" (one svo_voxel_map_move_dev: the counts' memset, the removal and the insert; the launches inside it
  * are not counted as "voxel_remove" or "voxel_insert"), "voxel_grid" (one svo_voxel_map_grid_dev: the memsets of the workspace
- * and the counts and both launches), "grid_clearance" (one svo_grid_clearance_dev: the counts' memset and both launches);
- * NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
+ * and the counts and both launches), "grid_clearance" (one svo_grid_clearance_dev: the counts' memset and both launches),
+ * "grid_route" (one svo_grid_route_dev: its memsets and every launch); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
 /* Measurement aid: the card's own ceilings for the roofline objects (SURVEY 8d asks for a measured FP64 figure).
@@ -781,6 +781,85 @@ int svo_grid_clearance_dev(svo_ctx* ctx, const uint8_t* cls, const svo_grid_clea
  * (no alignment asked), dist2 required; counts: 4 u64 on the host or NULL. */
 int svo_grid_clearance(svo_ctx* ctx, const uint8_t* cls, const svo_grid_clearance_params* params, const svo_grid_clearance_out* out,
                        uint64_t* counts);
+
+/* Ground plan route: from every cell of a byte grid the cost of the cheapest way to a goal cell that stays off the impassable cells
+ * and pays for coming near an obstacle, the first move of that way, and the cells of the way from given start cells: what a planner
+ * asks a ground plan second.  Integers only; a converged result is the unique fixed point of the relaxation (positive integer
+ * weights), depends on no thread order and is tested with ==.  cell = ia*nb + ib, as in the grid and the clearance.
+ * INPUTS (device memory for the _dev entry): blocked, na*nb u8, required: a cell is passable iff its byte is 0 (the clearance's
+ * blocked fits as it is); dist2, na*nb u32 or NULL (the clearance's dist2, 0xFFFFFFFF included); goals, n_goals (1..65536) u32 cell
+ * indices; starts, n_starts (0..4096) u32 cell indices, NULL with n_starts == 0.
+ *   1. pen[v] = near_weight * (near_r2 - dist2[v]) where dist2 is given and dist2[v] < near_r2, else 0 (NONE is far, a NULL dist2 is
+ *      far everywhere).
+ *   2. The eight neighbours are coded k = 0..7 in raster order of (dia, dib): (-1,-1) (-1,0) (-1,+1) (0,-1) (0,+1) (+1,-1) (+1,0)
+ *      (+1,+1).  A move from v to u is allowed iff both cells are inside the grid and passable and, for a diagonal, both cells it
+ *      passes between, (ia+dia, ib) and (ia, ib+dib), are passable (no corner cutting).  It costs w * (16 + pen[u]), w = 5 along an
+ *      axis and 7 on a diagonal: the 5-7 chamfer with the penalty of the cell entered.  One step costs less than 2^23.
+ *   3. A goal index >= na*nb or on an impassable cell is ignored; the others have cost 0.
+ *   4. cost[v] (u32, required) is the cheapest sum of move costs from v to any used goal if that sum is <= max_cost, else
+ *      SVO_GRID_ROUTE_NONE = 0xFFFFFFFF; impassable cells are NONE.  Every prefix of a route within the cap is within the cap, so the
+ *      capped field is the true one truncated; candidates never exceed 0x7F000000 + 2^23, so u32 arithmetic does not wrap.
+ *   5. next[v] (u8, optional) is 8 at a used goal, otherwise the smallest k whose move is allowed and has cost[u_k] + step ==
+ *      cost[v], and 255 where cost is NONE.  Following next strictly lowers cost, so it ends at a goal.
+ *   6. Paths (optional, all three or none): path n_starts x max_path u32, path_len n_starts u32, path_status n_starts u8.  Row i holds
+ *      the cells from starts[i] along next to the goal, both ends included; path_len[i] is the full number of cells, only the first
+ *      max_path are written and row entries past the written ones are not touched.  Status SVO_GRID_ROUTE_OK, _TRUNCATED (len >
+ *      max_path), _UNREACHED (cost NONE; len 0), _OUT_OF_GRID (len 0) or _NOT_CONVERGED (len 0).
+ *   7. counts: 8 u64 on the device, or NULL: {n_goals_used, n_reached, n_unreached, n_impassable, converged, rounds_run, 0, 0}.  They
+ *      are zeroed on the stream and every add is a relaxed one behind everything queued before the call.  n_reached counts passable
+ *      cells with a cost, goals included; n_reached + n_unreached + n_impassable = na*nb; n_goals_used counts list entries, so a
+ *      duplicate counts twice.
+ *   8. The call enqueues max_rounds relaxation rounds.  converged is 1 iff the last round that ran changed nothing.  If it is 0,
+ *      cost holds upper bounds whose bits may depend on timing, next and path are not written, every path_len is 0 and every status
+ *      _NOT_CONVERGED, and the three cell counts stay 0.  rounds_run (the last round of this call in which a tile had work) is
+ *      reported but may depend on how workgroups interleave.  A call with resume = 1, the same blocked, dist2, goals and params and
+ *      the same workspace and cost buffers untouched since, continues where the earlier call stopped; repeating such calls reaches
+ *      converged = 1 and the unique field.
+ *   9. workspace: svo_grid_route_workspace_bytes(na, nb) bytes of device memory, 8-byte aligned, contents meaningless on entry
+ *      unless resume.  blocked, dist2, goals and starts are only read and must not overlap an output.
+ *  10. SVO_ERR_INVALID with the argument named, nothing launched and the context still usable, for: a null ctx, blocked, params,
+ *      goals, workspace, out or cost; every range of the fields below (max_path only when n_starts > 0); n_goals outside 1..65536,
+ *      n_starts outside 0..4096; starts NULL with n_starts > 0; any of path, path_len, path_status NULL while another is not, or
+ *      non-NULL with n_starts == 0; cost, dist2, goals, starts, path or path_len off 4 bytes; workspace or counts off 8 bytes.
+ * UNIQUENESS.  With positive integer step costs the equations cost[goal] = 0, cost[v] = min over allowed moves of cost[u] + step have
+ * one solution, the shortest-route cost; relaxation only lowers a word towards it and never below, in whatever order cells are
+ * relaxed.  That is what lets the tiled parallel form be compared with == against Dijkstra.
+ * The defaults are NOT tuned on real data: the clearance's na and nb, near_r2 0, near_weight 0, max_cost 0x7F000000, max_rounds 64,
+ * max_path 4096, resume 0.  64 rounds cover ground plans; a maze takes resume.
+ * The pipeline never computes a route by itself; call it after the clearance it reads. */
+#define SVO_GRID_ROUTE_NONE 0xFFFFFFFFu
+#define SVO_GRID_ROUTE_MAX_COST 0x7F000000u
+enum { SVO_GRID_ROUTE_OK = 0, SVO_GRID_ROUTE_TRUNCATED = 1, SVO_GRID_ROUTE_UNREACHED = 2, SVO_GRID_ROUTE_OUT_OF_GRID = 3,
+       SVO_GRID_ROUTE_NOT_CONVERGED = 4 };
+typedef struct svo_grid_route_params {
+  int na, nb;           /* each 1..8192, na*nb <= 2^24 */
+  uint32_t near_r2;     /* 0..2^26: squared radius, in cells, inside which the penalty applies */
+  uint32_t near_weight; /* near_weight * near_r2 <= 2^20: penalty per unit of near_r2 - dist2 */
+  uint32_t max_cost;    /* 1..0x7F000000: cap on a cell's cost */
+  int max_rounds;       /* 1..4096: relaxation rounds this call enqueues */
+  int max_path;         /* 1..2^20, read only when n_starts > 0: cells written per path */
+  int resume;           /* 0 or 1: continue an earlier call's field */
+} svo_grid_route_params;
+typedef struct svo_grid_route_out { /* every pointer but cost may be NULL; path, path_len and path_status only together */
+  uint32_t* cost;       /* na*nb */
+  uint8_t* next;        /* na*nb */
+  uint32_t* path;       /* n_starts * max_path */
+  uint32_t* path_len;   /* n_starts */
+  uint8_t* path_status; /* n_starts */
+} svo_grid_route_out;
+/* The defaults above for the grid of a clearance.  Pure; SVO_ERR_INVALID for a null pointer or an na, nb the clearance refuses. */
+int svo_grid_route_default_params(const svo_grid_clearance_params* clearance, svo_grid_route_params* out);
+/* Bytes of the workspace: a header, two activity words per tile and one byte per cell; 0 for na or nb < 1.  Pure. */
+size_t svo_grid_route_workspace_bytes(int na, int nb);
+/* DEVICE pointers, asynchronous on svo_stream(ctx).  Everything it enqueues is one "grid_route" profile bracket. */
+int svo_grid_route_dev(svo_ctx* ctx, const uint8_t* blocked, const uint32_t* dist2, const svo_grid_route_params* params,
+                       const uint32_t* goals, int n_goals, const uint32_t* starts, int n_starts, void* workspace,
+                       const svo_grid_route_out* out, uint64_t* counts);
+/* HOST arrays and outputs (no alignment asked), synchronous: one device allocation for the call, freed after the stream is drained.
+ * counts: 8 u64 on the host or NULL.  resume = 1 is refused: the workspace does not outlive the call. */
+int svo_grid_route(svo_ctx* ctx, const uint8_t* blocked, const uint32_t* dist2, const svo_grid_route_params* params,
+                   const uint32_t* goals, int n_goals, const uint32_t* starts, int n_starts, const svo_grid_route_out* out,
+                   uint64_t* counts);
 
 /* ------------------------------------------------------------------- a8 --
  * ImageProcessor::triangulate_stereo's reprojection loop

@@ -329,6 +329,46 @@ def _clearance_params(params, overrides):
     return _params(lambda: GridClearanceParams(0, 0, 1 << VOXEL_GRID_OBSTACLE, 64, 0.0, 0.0), params, **overrides)
 
 
+class GridRouteParams(C.Structure):
+    """svo_grid_route_params: na x nb cells (each 1..8192, na*nb <= 2^24), the penalty's squared radius in cells and its weight
+    (near_weight * near_r2 <= 2^20), the cap on a cell's cost (1..0x7F000000), the rounds one call enqueues (1..4096), the cells
+    written per path (1..2^20, read only with starts) and resume (0 or 1)."""
+    _fields_ = [("na", C.c_int), ("nb", C.c_int), ("near_r2", C.c_uint32), ("near_weight", C.c_uint32), ("max_cost", C.c_uint32),
+                ("max_rounds", C.c_int), ("max_path", C.c_int), ("resume", C.c_int)]
+
+
+class GridRouteOut(C.Structure):
+    """svo_grid_route_out: cost and next na*nb elements, path n_starts x max_path, path_len and path_status n_starts; every pointer
+    but cost may be None, the three of the paths only together."""
+    _fields_ = [("cost", C.c_void_p), ("next", C.c_void_p), ("path", C.c_void_p), ("path_len", C.c_void_p), ("path_status", C.c_void_p)]
+
+
+GRID_ROUTE_NONE = 0xFFFFFFFF  # SVO_GRID_ROUTE_NONE
+GRID_ROUTE_MAX_COST = 0x7F000000  # SVO_GRID_ROUTE_MAX_COST
+GRID_ROUTE_COUNTS = ("n_goals_used", "n_reached", "n_unreached", "n_impassable", "converged", "rounds_run")
+GRID_ROUTE_OK, GRID_ROUTE_TRUNCATED, GRID_ROUTE_UNREACHED, GRID_ROUTE_OUT_OF_GRID, GRID_ROUTE_NOT_CONVERGED = range(5)
+
+
+def grid_route_default_params(clearance):
+    """svo_grid_route_default_params for a GridClearanceParams: its na x nb, no penalty, max_cost 0x7F000000, 64 rounds, paths of up
+    to 4096 cells, no resume (not tuned on real data)."""
+    p = GridRouteParams()
+    if lib().svo_grid_route_default_params(C.byref(clearance), C.byref(p)) != 0:
+        raise SvoError("svo_grid_route_default_params: the clearance's na and nb must be in range")
+    return p
+
+
+def grid_route_workspace_bytes(na, nb):
+    """svo_grid_route_workspace_bytes (no GPU involved); 0 for na or nb < 1."""
+    return int(lib().svo_grid_route_workspace_bytes(int(na), int(nb)))
+
+
+def _route_params(params, overrides):
+    """params and / or its fields as keywords; without params the defaults' penalty, cap, rounds and path length, and na and nb from
+    the keywords (the library refuses what is left at 0)."""
+    return _params(lambda: GridRouteParams(0, 0, 0, 0, GRID_ROUTE_MAX_COST, 64, 4096, 0), params, **overrides)
+
+
 SPECKLE_TILE = (64, 16)  # SVO_SPECKLE_TILE_W, SVO_SPECKLE_TILE_H
 
 
@@ -521,6 +561,7 @@ SYMBOLS = [
     "svo_voxel_grid_default_params", "svo_voxel_grid_workspace_bytes", "svo_voxel_grid_cell_of", "svo_voxel_map_grid_dev", "svo_voxel_map_grid",
     "svo_voxel_grid_set_mode",
     "svo_grid_clearance_default_params", "svo_grid_clearance_workspace_bytes", "svo_grid_clearance_dev", "svo_grid_clearance",
+    "svo_grid_route_default_params", "svo_grid_route_workspace_bytes", "svo_grid_route_dev", "svo_grid_route",
     "svo_voxel_map_remove_dev", "svo_voxel_map_remove_pose7_dev", "svo_voxel_map_remove_sync", "svo_voxel_map_move_dev", "svo_voxel_map_move_pose7_dev",
     "svo_voxel_ledger_bytes", "svo_voxel_ledger_create", "svo_voxel_ledger_destroy", "svo_voxel_ledger_insert_pose7_dev",
     "svo_voxel_ledger_update_pose7", "svo_voxel_ledger_retire", "svo_voxel_ledger_remove", "svo_voxel_ledger_ids", "svo_voxel_ledger_get",
@@ -650,6 +691,14 @@ def lib():
         L.svo_grid_clearance_dev.argtypes = [vp, vp, vp, vp, vp, vp]
         L.svo_grid_clearance.argtypes = [vp, vp, vp, vp, vp]
         for f in ("svo_grid_clearance_default_params", "svo_grid_clearance_dev", "svo_grid_clearance"):
+            getattr(L, f).restype = ci
+        # the ground plan route
+        L.svo_grid_route_default_params.argtypes = [vp, vp]
+        L.svo_grid_route_workspace_bytes.argtypes = [ci, ci]
+        L.svo_grid_route_workspace_bytes.restype = sz
+        L.svo_grid_route_dev.argtypes = [vp, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp]
+        L.svo_grid_route.argtypes = [vp, vp, vp, vp, vp, ci, vp, ci, vp, vp]
+        for f in ("svo_grid_route_default_params", "svo_grid_route_dev", "svo_grid_route"):
             getattr(L, f).restype = ci
         # removal, move and the keyframe ledger
         i64 = C.c_int64
@@ -981,6 +1030,55 @@ class Context:
         c = np.zeros(4, np.uint64)
         self._chk(self.L.svo_grid_clearance(self.h, _p(cls), C.byref(prm), C.byref(out), _p(c)), "svo_grid_clearance")
         return (*arrays, dict(zip(GRID_CLEARANCE_COUNTS, (int(v) for v in c))))
+
+    # ---- ground plan route
+    def grid_route(self, blocked_ptr, params, goals_ptr, n_goals, workspace_ptr=None, cost_ptr=None, dist2_ptr=None, next_ptr=None,
+                   starts_ptr=None, n_starts=0, path_ptr=None, path_len_ptr=None, path_status_ptr=None, counts_ptr=None, **overrides):
+        """svo_grid_route_dev: the cost-to-go field to the goal cells over the na x nb uint8 grid behind blocked_ptr (passable iff 0),
+        the first move per cell and the paths from the start cells.  params (a GridRouteParams) and / or its fields as keywords.  All
+        pointers are the caller's device memory: workspace_ptr grid_route_workspace_bytes(na, nb) bytes, cost_ptr na * nb uint32
+        (required), dist2_ptr na * nb uint32, next_ptr na * nb uint8, goals_ptr n_goals and starts_ptr n_starts uint32 cell indices,
+        path_ptr n_starts x max_path uint32, path_len_ptr uint32 and path_status_ptr uint8 per start (the three together or None),
+        counts_ptr 8 uint64 (GRID_ROUTE_COUNTS and two zeros) or None.  Asynchronous on the context's stream; returns the pointers
+        the outputs are behind once the stream reaches this point, with "workspace", "na", "nb"."""
+        prm = _route_params(params, overrides)
+        out = GridRouteOut(cost_ptr, next_ptr, path_ptr, path_len_ptr, path_status_ptr)
+        self._chk(self.L.svo_grid_route_dev(self.h, blocked_ptr, dist2_ptr, C.byref(prm), goals_ptr, int(n_goals), starts_ptr, int(n_starts),
+                                            workspace_ptr, C.byref(out), counts_ptr), "svo_grid_route_dev")
+        return {"cost": cost_ptr, "next": next_ptr, "path": path_ptr, "path_len": path_len_ptr, "path_status": path_status_ptr,
+                "counts": counts_ptr, "workspace": workspace_ptr, "na": prm.na, "nb": prm.nb}
+
+    def grid_route_host(self, blocked, goals, dist2=None, starts=None, params=None, **overrides):
+        """svo_grid_route: synchronous.  blocked: an (na, nb) uint8 array (na and nb are taken from it unless given); goals, starts:
+        cell indices; dist2: (na, nb) uint32 or None.  Returns {"cost" (na, nb) uint32 with GRID_ROUTE_NONE, "next" (na, nb) uint8,
+        "counts" {GRID_ROUTE_COUNTS}} and, with starts, "path" (n_starts, max_path) uint32 (GRID_ROUTE_NONE where nothing was
+        written), "path_len" uint32 and "path_status" uint8 per start."""
+        blocked = np.ascontiguousarray(blocked, np.uint8)
+        if blocked.ndim != 2:
+            raise ValueError("grid_route_host: blocked must be an (na, nb) array")
+        if params is None:
+            overrides = {"na": blocked.shape[0], "nb": blocked.shape[1], **overrides}
+        prm = _route_params(params, overrides)
+        if (prm.na, prm.nb) != blocked.shape:
+            raise ValueError(f"grid_route_host: blocked is {blocked.shape}, the parameters say {(prm.na, prm.nb)}")
+        if dist2 is not None:
+            dist2 = np.ascontiguousarray(dist2, np.uint32)
+            if dist2.shape != blocked.shape:
+                raise ValueError("grid_route_host: dist2 must have the shape of blocked")
+        goals = np.ascontiguousarray(goals, np.uint32).ravel()
+        starts = None if starts is None else np.ascontiguousarray(starts, np.uint32).ravel()
+        ns = 0 if starts is None else len(starts)
+        res = {"cost": np.empty(blocked.shape, np.uint32), "next": np.full(blocked.shape, 255, np.uint8)}
+        if ns:
+            if not 1 <= prm.max_path <= 1 << 20:
+                raise SvoError("svo_grid_route: grid_route: max_path outside 1..2^20")
+            res.update(path=np.full((ns, prm.max_path), GRID_ROUTE_NONE, np.uint32), path_len=np.zeros(ns, np.uint32), path_status=np.zeros(ns, np.uint8))
+        out = GridRouteOut(*(res[k].ctypes.data if k in res else None for k in ("cost", "next", "path", "path_len", "path_status")))
+        c = np.zeros(8, np.uint64)
+        self._chk(self.L.svo_grid_route(self.h, _p(blocked), _p(dist2), C.byref(prm), _p(goals), len(goals), _p(starts) if ns else None, ns,
+                                        C.byref(out), _p(c)), "svo_grid_route")
+        res["counts"] = dict(zip(GRID_ROUTE_COUNTS, (int(v) for v in c)))
+        return res
 
     # ---- a8
     def triangulate(self, xy, disp, pose16, focal, cx, cy, baseline):

@@ -30,7 +30,8 @@ extern "C" int svo_profile_select(svo_ctx* ctx, const char* kernel) {
   static const char* names[] = {"", "corner_response", "corner_nms", "corner_select", "pyr_down", "lk_fb", "stereo_at",
                                 "triangulate", "pnp_hypotheses", "pnp_refine", "ba_linearize", "ba_backsub", "ba_step", "rectify_remap",
                                 "stereo_bm", "stereo_dense_batch", "cloud", "speckle", "lr_check", "stereo_sgm", "voxel_insert", "voxel_extract",
-                                "voxel_carve", "voxel_copy", "voxel_render", "voxel_remove", "voxel_move", "voxel_grid", "grid_clearance"};
+                                "voxel_carve", "voxel_copy", "voxel_render", "voxel_remove", "voxel_move", "voxel_grid", "grid_clearance",
+                                "grid_route"};
   int tag = 0;
   if (kernel && kernel[0]) {
     tag = -1;

@@ -49,6 +49,14 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      window), 0.001 and 0.1 with max_dist 64 and at 0.001 with max_dist 512; each beside the time hbm_copy needs for 22 bytes per
      cell (cls read, the offsets written and read, 13 bytes of outputs) and, for the 256 x 256 grids, the loop steps of both passes
      summed over the cells, counted on the host from cls.
+ 13. route: one svo_grid_route_dev ("grid_route" bracket: its memsets and every launch, mean of 5; cost, next, four paths of up to 4096
+     cells and the counts) over the clearance (inflate_radius two cells) of section 11's grid of each filled map, near_r2 64,
+     near_weight 4, the goal at the grid's centre cell, the starts at its four corners, at the default 64 rounds (raised fourfold
+     until the call converges); and of a synthetic 2048 x 2048 grid at blocked densities 0, 0.1 and 0.3 (goal and starts kept passable) without dist2.  Per case the
+     time, rounds_run, the counts and the longest path; the cost of an enqueued round that finds nothing to do (the same case at
+     max_rounds = rounds_run and at 64 more, the difference per launch); the path launch alone (the call with the starts minus the
+     call without, per step of the longest path); and, as context, the device-to-host copies of blocked and dist2 plus this tool's
+     host Dijkstra in Python (256 x 256 only): the detour the entry replaces.
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -210,6 +218,8 @@ def standalone(S, torch, batch, warmup, reps):
     out["voxel"] = voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy)
     out["clearance_synthetic"] = [clearance_case(S, torch, ctx, clearance_random(torch, 2048, 2048, density), 4, md, 0.5, warmup, copy, density=density)
                                   for density, md in ((0.0, 64), (0.001, 64), (0.1, 64), (0.001, 512))]
+    out["route_synthetic"] = [route_case(S, torch, ctx, route_random(torch, 2048, 2048, density), None, 0, 0, warmup, copy, density=density)
+                              for density in (0.0, 0.1, 0.3)]
     ctx.close()
     return out
 
@@ -279,6 +289,7 @@ def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy):
             out[-1].update(remove_and_move(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, copy))
             out[-1].update(grid_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # before the carve changes the map, as the render
             out[-1].update(clearance_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # of the same grid, before the carve too
+            out[-1].update(route_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # over that grid's clearance
             out[-1].update(render_view(S, torch, ctx, cam, vm, np.asarray(m12[batch - 1]), warmup, copy))
             out[-1].update(carve_and_copy(S, torch, ctx, cam, dm, vm, np.asarray(m12[batch - 1]), warmup, copy))
             vm.close()
@@ -446,6 +457,139 @@ def clearance_view(S, torch, ctx, vm, c2w, warmup, copy):
     grid = cls.reshape(gp.na, gp.nb)
     return {"clearance": [clearance_case(S, torch, ctx, grid, mask, cp.max_dist, cp.cell_size, warmup, copy, steps=True)
                           for mask in (cp.source_mask, cp.source_mask | 1 << S.api.VOXEL_GRID_UNKNOWN)]}
+
+
+def route_host_dijkstra(blocked, dist2, near_r2, near_weight, goal):
+    """This tool's host Dijkstra over host copies (Python, a heap): the cost field only.  Returns the number of reached cells."""
+    import heapq
+    na, nb = blocked.shape
+    B = (blocked.ravel() != 0).tolist()
+    pen = np.zeros(na * nb, np.int64) if dist2 is None else np.where(dist2.ravel() < near_r2, near_weight * (near_r2 - dist2.ravel().astype(np.int64)), 0)
+    unit = (16 + pen).tolist()
+    cost = [-1] * (na * nb)
+    if B[goal]:
+        return 0
+    heap, reached = [(0, goal)], 0
+    best = {goal: 0}
+    while heap:
+        c, u = heapq.heappop(heap)
+        if cost[u] >= 0:
+            continue
+        cost[u] = c
+        reached += 1
+        ua, ub = divmod(u, nb)
+        for da in (-1, 0, 1):
+            va = ua + da
+            if va < 0 or va >= na:
+                continue
+            for db in (-1, 0, 1):
+                vb = ub + db
+                if (da == 0 and db == 0) or vb < 0 or vb >= nb:
+                    continue
+                v = va * nb + vb
+                if B[v] or cost[v] >= 0 or (da and db and (B[va * nb + ub] or B[ua * nb + vb])):
+                    continue
+                c2 = c + (7 if da and db else 5) * unit[u]
+                if c2 < best.get(v, 1 << 62):
+                    best[v] = c2
+                    heapq.heappush(heap, (c2, v))
+    return reached
+
+
+def route_random(torch, na, nb, density, seed=13):
+    """A seeded grid, impassable with this probability, with the goal (the centre cell) and the starts (the corners) passable."""
+    g = torch.Generator(device="cuda")
+    g.manual_seed(seed)
+    b = (torch.rand((na, nb), generator=g, device="cuda") < density).to(torch.uint8)
+    b[na // 2, nb // 2] = 0
+    b[0, 0] = b[0, nb - 1] = b[na - 1, 0] = b[na - 1, nb - 1] = 0
+    return b
+
+
+def route_case(S, torch, ctx, blocked, dist2, near_r2, near_weight, warmup, copy, host_detour=False, density=None):
+    """Section 13 for one (na, nb) uint8 device grid (passable iff 0) and its uint32 device dist2 (or None)."""
+    api = S.api
+    na, nb = blocked.shape
+    n = na * nb
+    goal = (na // 2) * nb + nb // 2
+    h_starts = np.array([0, nb - 1, (na - 1) * nb, n - 1], np.uint32)
+    max_path = 4096
+    goals = torch.tensor([goal], dtype=torch.int32, device="cuda")
+    starts = torch.from_numpy(h_starts.view(np.int32)).cuda()
+    ws = torch.empty(api.grid_route_workspace_bytes(na, nb) // 8, dtype=torch.int64, device="cuda")
+    cost = torch.empty(n, dtype=torch.int32, device="cuda")
+    nxt = torch.empty(n, dtype=torch.uint8, device="cuda")
+    path = torch.empty(len(h_starts) * max_path, dtype=torch.int32, device="cuda")
+    plen = torch.zeros(len(h_starts), dtype=torch.int32, device="cuda")
+    status = torch.zeros(len(h_starts), dtype=torch.uint8, device="cuda")
+    cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+
+    def call(max_rounds, paths=True):
+        prm = api.GridRouteParams(na, nb, near_r2, near_weight, api.GRID_ROUTE_MAX_COST, max_rounds, max_path, 0)
+        kw = dict(starts_ptr=starts.data_ptr(), n_starts=len(h_starts), path_ptr=path.data_ptr(), path_len_ptr=plen.data_ptr(),
+                  path_status_ptr=status.data_ptr()) if paths else {}
+        ctx.grid_route(blocked.data_ptr(), prm, goals.data_ptr(), 1, workspace_ptr=ws.data_ptr(), cost_ptr=cost.data_ptr(),
+                       dist2_ptr=None if dist2 is None else dist2.data_ptr(), next_ptr=nxt.data_ptr(), counts_ptr=cnt.data_ptr(), **kw)
+
+    def timed(max_rounds, paths=True):
+        for _ in range(warmup):
+            call(max_rounds, paths)
+        ctx.profile_select("grid_route")
+        for _ in range(5):
+            call(max_rounds, paths)
+        ms, k = ctx.profile_read()
+        ctx.profile_select("")
+        return ms / k, [int(v) for v in cnt.cpu()]
+
+    rounds = 64  # the default; a call that does not converge is repeated from the start with four times as many
+    while True:
+        ms, counts = timed(rounds)
+        if counts[4] == 1 or rounds == 4096:
+            break
+        rounds *= 4
+    needed = max(counts[5], 1)
+    ms_needed, c_needed = timed(needed)
+    ms_more, c_more = timed(min(needed + 64, 4096))
+    ms_nopath, _ = timed(needed, paths=False)
+    lens = [int(v) for v in plen.cpu().numpy().view(np.uint32)]
+    out = {"cells": [na, nb], "near_r2": near_r2, "near_weight": near_weight, "with_dist2": dist2 is not None, "max_rounds": rounds, "ms": ms,
+           "counts": counts[:6], "rounds_run": counts[5], "path_lens": lens, "path_status": [int(v) for v in status.cpu()],
+           "ms_at_rounds_run": ms_needed, "converged_at_rounds_run": c_needed[4], "ms_at_64_more": ms_more,
+           "idle_round_us": 1e3 * (ms_more - ms_needed) / max(min(needed + 64, 4096) - needed, 1),
+           "path_launch_us": 1e3 * (ms_needed - ms_nopath), "path_us_per_step": 1e3 * (ms_needed - ms_nopath) / max(max(lens), 1),
+           "bound_ms": 1e3 * (n * (1 + 4 + 1 + (4 if dist2 is not None else 0)) + 4 * n) / copy}  # blocked, cost written, next, dist2 read once; NONE memset
+    if density is not None:
+        out["density"] = density
+    t0 = time.perf_counter()
+    h_b = blocked.cpu().numpy()
+    h_d = None if dist2 is None else dist2.cpu().numpy().view(np.uint32).reshape(na, nb)
+    out["d2h_copies_ms"] = 1e3 * (time.perf_counter() - t0)
+    if host_detour:
+        t0 = time.perf_counter()
+        reached = route_host_dijkstra(h_b, h_d, near_r2, near_weight, goal)
+        out["host_dijkstra_ms"] = 1e3 * (time.perf_counter() - t0)
+        assert reached == counts[1], (reached, counts)
+    return out
+
+
+def route_view(S, torch, ctx, vm, c2w, warmup, copy):
+    """Section 13 for one filled map: the route over the clearance (inflation two cells) of section 11's grid."""
+    gp = S.api.voxel_grid_default_params(vm.params.voxel_size)
+    x, z = float(c2w.reshape(3, 4)[0, 3]), float(c2w.reshape(3, 4)[2, 3])
+    gp.origin_a, gp.origin_b = gp.origin_a + z, gp.origin_b + x
+    n = gp.na * gp.nb
+    ws = torch.empty(4 * n, dtype=torch.int64, device="cuda")
+    cls = torch.empty(n, dtype=torch.uint8, device="cuda")
+    offsets, d2 = (torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(2))
+    blk = torch.empty(n, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    vm.grid(gp, workspace_ptr=ws.data_ptr(), cls_ptr=cls.data_ptr())
+    cp = S.api.grid_clearance_default_params(gp, vm.params.voxel_size)
+    cp.inflate_radius = 2.0 * cp.cell_size
+    ctx.grid_clearance(cls.data_ptr(), cp, workspace_ptr=offsets.data_ptr(), dist2_ptr=d2.data_ptr(), blocked_ptr=blk.data_ptr())
+    ctx.sync()
+    return {"route": route_case(S, torch, ctx, blk.reshape(gp.na, gp.nb), d2, 64, 4, warmup, copy, host_detour=True)}
 
 
 def render_view(S, torch, ctx, cam, vm, c2w, warmup, copy):
@@ -774,6 +918,15 @@ def main():
                             f"outputs, mean of 5): {1e3 * k['ms']:.1f} us, counts {k['counts']} (sources, reached, unreached, blocked at a radius of 2 cells); loop steps "
                             f"summed over the cells {k['steps'][0]} (row pass) + {k['steps'][1]} (column pass); 22 B per cell at hbm_copy {1e3 * k['bound_ms']:.2f} us -> "
                             f"{100 * k['share_of_bound']:.1f} % of that bound\n" for k in c['clearance']) +
+                        "".join(
+                            f"  route over that grid's clearance at an inflation of two cells, near_r2 {k['near_r2']}, near_weight {k['near_weight']}, goal at the centre cell, starts at the "
+                            f"corners (memsets + goals + rounds + verdict + finish + paths, mean of 5): "
+                            f"{1e3 * k['ms']:.1f} us at max_rounds {k['max_rounds']}, rounds_run {k['rounds_run']}, counts {k['counts'][:5]} (goals used, reached, unreached, impassable, "
+                            f"converged), path lengths {k['path_lens']} with status {k['path_status']}; at max_rounds = rounds_run {1e3 * k['ms_at_rounds_run']:.1f} us (converged "
+                            f"{k['converged_at_rounds_run']}), with 64 more {1e3 * k['ms_at_64_more']:.1f} us -> {k['idle_round_us']:.2f} us per round that finds nothing to do; the path "
+                            f"launch {k['path_launch_us']:.1f} us = {k['path_us_per_step']:.3f} us per step of the longest path; one pass over the arrays at hbm_copy "
+                            f"{1e3 * k['bound_ms']:.2f} us; device-to-host copies of blocked and dist2 {1e3 * k['d2h_copies_ms']:.0f} us"
+                            f" and this tool's Python Dijkstra on the host {k['host_dijkstra_ms']:.0f} ms\n" for k in [c['route']]) +
                         f"  removal of the last inserted cloud ({c['remove_move_points']} points, mean of 5): {1e3 * c['remove_ms']:.1f} us, counts {c['remove_counts']} "
                         f"(removed, rejected, missing, short); move to a pose 1 cm and 0.1 degrees away (removal + insert): {1e3 * c['move_ms']:.1f} us, counts "
                         f"{c['move_counts']}; the same cloud inserted once more, same run: {1e3 * c['insert_ms']:.1f} us -> removal / insert "
@@ -783,6 +936,14 @@ def main():
                 f.write(f"clearance of a synthetic {k['cells'][0]} x {k['cells'][1]} grid, source density {k['density']}, max_dist {k['max_dist']} (all four outputs, mean of 5): "
                         f"{1e3 * k['ms']:.1f} us, counts {k['counts']} (sources, reached, unreached, blocked); 22 B per cell at hbm_copy {1e3 * k['bound_ms']:.1f} us -> "
                         f"{100 * k['share_of_bound']:.1f} % of that bound\n")
+            for k in s["route_synthetic"]:
+                f.write(f"route over a synthetic {k['cells'][0]} x {k['cells'][1]} grid, blocked density {k['density']}, no dist2, goal at the centre cell, starts at the corners (mean of 5): "
+                        f"{1e3 * k['ms']:.1f} us at max_rounds {k['max_rounds']}, rounds_run {k['rounds_run']}, counts {k['counts'][:5]} (goals used, reached, unreached, impassable, "
+                        f"converged), path lengths {k['path_lens']} with status {k['path_status']}; at max_rounds = rounds_run {1e3 * k['ms_at_rounds_run']:.1f} us (converged "
+                        f"{k['converged_at_rounds_run']}), with 64 more {1e3 * k['ms_at_64_more']:.1f} us -> {k['idle_round_us']:.2f} us per round that finds nothing to do; the path "
+                        f"launch {k['path_launch_us']:.1f} us = {k['path_us_per_step']:.3f} us per step of the longest path; one pass over the arrays at hbm_copy "
+                        f"{1e3 * k['bound_ms']:.2f} us; device-to-host copies of blocked and dist2 {1e3 * k['d2h_copies_ms']:.0f} us"
+                        f"\n")
             if g and "ratio_ledger_to_clouds" in g:
                 f.write(f"{g['lanes']} lanes in {g['groups']} groups, {g['frames_per_step_per_lane']}-frame steps, {g['rounds']} alternating rounds of {g['steps']} steps, clouds at "
                         f"step {g['cloud_step']}, every lane's ledger holding {g['ledger_held_per_lane']} keyframes and moving all of them (1 cm, 0.1 degrees) after each call: "
