@@ -3,7 +3,7 @@ host/lm.cpp, the dense Cholesky, the KITTI-layout decoders, the track rasteriser
 GPU-free pieces of the bundle adjuster: the sliding-window graph host/ba_graph.h, the problem layout host/ba_layout.h, the
 admission ledger host/ba_admission.h, the launch planning of its device-resident solve host/ba_plan.h with the kernels' LDS sizes
 csrc/lm_lds.h (tests/sanitize/ba_plan_test.cpp), and the argument rules, sizes and launch geometry of the dense keyframe chain
-host/dense_args.h), on the CPU: GPU sanitizers are not available on the target pool, and these are the
+host/dense_args.h), and the pose conversions host/det_trig.h at their branches (tests/sanitize/det_trig_test.cpp), on the CPU: GPU sanitizers are not available on the target pool, and these are the
 pieces that parse files and index host arrays.  Every program is stand-alone (its own main); nothing is loaded into Python."""
 import os
 import struct
@@ -105,6 +105,7 @@ def _run_sanitized(tmp_path, name, ok, *args):
     r = subprocess.run([exe] + list(args), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     assert ok in r.stdout
+    return r.stdout
 
 
 def test_ba_graph_ids_truncation_window_gather_and_write_back(tmp_path):
@@ -147,3 +148,76 @@ def test_ba_plan_sizes_forms_budget_and_raised_k_match_a_restatement(tmp_path):
     workgroup, an adjuster's own k never raised), and every knob parsed from unset, empty, in-range, out-of-range and non-numeric
     strings."""
     _run_sanitized(tmp_path, "ba_plan_test", "ba plan ok")
+
+
+def _det_trig_inputs():
+    """rvecs (n, 3) f64 and matrices (m, 9) f32 at every branch of host/det_trig.h."""
+    F, eps = np.float32, np.float32(2.0 ** -52)                         # cv::Rodrigues' small-angle threshold DBL_EPSILON is a float, too
+    axes = [np.array(a, float) for a in ((1, 0, 0), (0, 1, 0), (0, 0, 1), (-1, 0, 0), (0, 0, -1), (0.48, -0.6, 0.64), (0.6, 0.64, 0.48), (-0.64, 0.48, 0.6))]
+    mags = [0.0, float(np.nextafter(eps, F(0))), float(eps), float(np.nextafter(eps, F(1))), 1e-20, 1e-300,
+            float(np.nextafter(1e-12, 0)), 1e-12, float(np.nextafter(1e-12, 1)), 1e-7, 0.3, 0.5, float(np.nextafter(0.5, 1)), 1.0,
+            np.pi - 1e-3, np.pi - 1e-7, float(np.nextafter(F(np.pi), F(0))), np.pi, float(F(np.pi)), np.pi + 1e-7, np.pi + 1e-3, 4.0, 6.0]
+    mags += list(np.deg2rad(np.arange(118.0, 181.0, 1.0)))             # 120 ... 180 degrees: the trace turns negative on the way
+    rv = np.array([a * m for a in axes for m in mags])
+    mats = []
+    rng = np.random.default_rng(7)
+    vals = (-1.0, -0.75, -0.5, -0.25, 0.0, 0.25, 0.5, 0.75, 1.0)
+    for a in vals:
+        for b in vals:
+            for c in vals:
+                big = max(a, b, c)
+                if a + b + c > 0.5 or 1.0 + 2.0 * big - (a + b + c) <= 0:    # a few with a positive trace; the root stays real
+                    continue
+                m = rng.uniform(-1, 1, (3, 3))
+                m[0, 0], m[1, 1], m[2, 2] = a, b, c
+                mats.append(m.ravel())
+    return rv, np.array(mats, F)
+
+
+def test_pose_conversions_at_their_branches_match_the_restatements(tmp_path):
+    """host/det_trig.h: svo_det_rodrigues_f, svo_det_quat_from_R, svo_det_quat_from_rvec and svo_det_rvec_from_quat, compiled for the
+    host under ASan + UBSan and run on rvecs of length 0, either side of 2^-52 and of 1e-12, near pi and from 118 to 180 degrees about
+    x, y, z and skew axes, and on matrices with a positive, a zero and a negative trace, each diagonal entry largest, with ties on the
+    diagonal.  Every result equals, bit for bit, the restatements in tests/pipeline_ref.py (cv::Rodrigues, Eigen::Quaternionf(Matrix3f))
+    and tests/pnp_ref.py (rvec <-> quaternion); the restatement's counters show that all four quaternion branches and the small-angle
+    branches ran."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pipeline_ref as PR
+    import pnp_ref
+    rv, mats = _det_trig_inputs()
+    path = tmp_path / "det_trig_inputs.bin"
+    path.write_bytes(np.array([len(rv), len(mats)], "<i4").tobytes() + rv.astype("<f8").tobytes() + mats.astype("<f4").tobytes())
+    lines = _run_sanitized(tmp_path, "det_trig_test", "det trig ok", str(path)).splitlines()
+    assert len(lines) == len(rv) + len(mats) + 1
+
+    def f32(words):
+        return np.array([int(w, 16) for w in words], np.uint32)
+
+    def f64(words):
+        return np.array([int(w, 16) for w in words], np.uint64)
+    rec = dict.fromkeys(PR.COUNTERS, 0)
+    flips = {"quat_flip": 0}
+    tie01 = tie2 = small_q = small_v = 0
+    for r, line in zip(rv, lines):
+        w = line.split()
+        assert w[0] == "v" and len(w) == 1 + 9 + 4 + 4 + 3 + 3
+        R = PR.rodrigues_f(r.astype(np.float32), rec)
+        q = pnp_ref.quat_from_rvec([float(v) for v in r])
+        small_q += np.linalg.norm(r) < 1e-12
+        small_v += np.linalg.norm(q[1:]) < 1e-12
+        want = [R.view(np.uint32).ravel(), PR.quat_from_R(R, rec).view(np.uint32), np.array(q).view(np.uint64),
+                np.array(pnp_ref.rvec_from_quat(q, flips)).view(np.uint64), np.array(pnp_ref.rvec_from_quat([-v for v in q], flips)).view(np.uint64)]
+        got = [f32(w[1:10]), f32(w[10:14]), f64(w[14:18]), f64(w[18:21]), f64(w[21:24])]
+        for k, (a, b) in enumerate(zip(got, want)):
+            assert np.array_equal(a, b), (r.tolist(), k, a, b)
+    for m, line in zip(mats, lines[len(rv):]):
+        w = line.split()
+        assert w[0] == "m" and len(w) == 5
+        assert np.array_equal(f32(w[1:]), PR.quat_from_R(m.reshape(3, 3), rec).view(np.uint32)), m.tolist()
+        if m[0] + m[4] + m[8] <= 0:
+            tie01 += m[4] == m[0]
+            tie2 += m[8] == max(m[0], m[4])
+    assert min(rec[k] for k in ("quat_trace_pos", "quat_x", "quat_y", "quat_z", "rodrigues_small")) > 0, rec
+    assert flips["quat_flip"] > 0 and tie01 > 0 and tie2 > 0 and small_q > 0 and small_v > 0
+    assert any(m[0] + m[4] + m[8] == 0 for m in mats)
