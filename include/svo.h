@@ -103,7 +103,8 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * the launch), "voxel_move" (one svo_voxel_map_move_dev: the counts' memset, the removal and the insert; the launches inside it
  * are not counted as "voxel_remove" or "voxel_insert"), "voxel_grid" (one svo_voxel_map_grid_dev: the memsets of the workspace
  * and the counts and both launches), "grid_clearance" (one svo_grid_clearance_dev: the counts' memset and both launches),
- * "grid_route" (one svo_grid_route_dev: its memsets and every launch); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
+ * "grid_route" (one svo_grid_route_dev: its memsets and every launch), "grid_frontier" (one svo_grid_frontiers_dev: the counts'
+ * memset and every launch); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
 /* Measurement aid: the card's own ceilings for the roofline objects (SURVEY 8d asks for a measured FP64 figure).
@@ -860,6 +861,81 @@ int svo_grid_route_dev(svo_ctx* ctx, const uint8_t* blocked, const uint32_t* dis
 int svo_grid_route(svo_ctx* ctx, const uint8_t* blocked, const uint32_t* dist2, const svo_grid_route_params* params,
                    const uint32_t* goals, int n_goals, const uint32_t* starts, int n_starts, const svo_grid_route_out* out,
                    uint64_t* counts);
+
+/* Ground plan frontiers: the passable cells of known ground that touch ground nobody has seen yet, grouped into connected pieces,
+ * each with its size, bounds, a representative cell and its cheapest cell: where a vehicle that builds its own map goes next, and
+ * what the route takes as its goals.  Integers only, no dependence on thread order, tested with ==.  cell = ia*nb + ib, as in the
+ * grid, the clearance and the route.
+ * INPUTS (device memory for the _dev entry): cls, na*nb u8, required (svo_voxel_map_grid*'s cls or any other class grid); blocked,
+ * na*nb u8 or NULL (the clearance's blocked); cost, na*nb u32 or NULL (a route's cost field, for instance one whose only goal is the
+ * vehicle's cell).
+ *   1. A cell is FREE iff cls < 32, bit cls of free_mask is set, and blocked is NULL or blocked[cell] == 0.  A cell is UNKNOWN iff
+ *      cls < 32 and bit cls of unknown_mask is set.  Values >= 32 are neither.
+ *   2. A cell is a FRONTIER CELL iff it is FREE and at least one of its four edge neighbours inside the grid is UNKNOWN.  The outside
+ *      of the grid is not unknown; a diagonal neighbour does not count.
+ *   3. A frontier is an 8-connected component of frontier cells.
+ *   4. Per frontier: size, the number of cells; first_cell, the smallest cell index; sum_a, sum_b, the sums of ia and of ib (at most
+ *      2^37); min_a, max_a, min_b, max_b, the bounds.
+ *   5. rep_cell: with (ca, cb) = (sum_a / size, sum_b / size), integer division, the member cell with the smallest (ia-ca)^2 +
+ *      (ib-cb)^2, ties to the smallest index.  It is always a member, so it is FREE; the centroid itself need not be one.
+ *   6. best_cell, best_cost: the member cell with the smallest cost among the members whose cost != 0xFFFFFFFF, ties to the smallest
+ *      index, and its cost.  Both are 0xFFFFFFFF when cost is NULL or no member has a cost.
+ *   7. A frontier is KEPT iff size >= min_size.  Kept frontiers are ranked by ascending first_cell.  Record i describes rank i for i <
+ *      min(n_kept, max_frontiers); records past that are not touched.
+ *   8. goal_cells[i] is rep_cell of rank i for i < min(n_kept, max_frontiers); all other entries up to max_frontiers are written as
+ *      0xFFFFFFFF, which svo_grid_route_dev ignores by its rule 3: the array goes into the route as it is, with n_goals =
+ *      max_frontiers and no count read back.
+ *   9. label[cell] is the rank of its frontier for a cell of a kept frontier, also where the rank is >= max_frontiers, and
+ *      0xFFFFFFFF for every other cell.
+ *  10. counts: 8 u64 on the device, or NULL: {n_free, n_unknown, n_frontier_cells, n_frontiers, n_kept, n_written, n_kept_cells, 0}.
+ *      Zeroed on the stream; relaxed adds only.  n_written = min(n_kept, max_frontiers).
+ *  11. workspace: svo_grid_frontier_workspace_bytes(na, nb, max_frontiers) bytes of device memory, 8-byte aligned, contents
+ *      meaningless on entry.  The function is pure, computes in size_t and returns 0 for a refused shape; the size is
+ *        256 + 64 * max_frontiers + round8(4 * ceil(na*nb / 256)) + round8(12 * na*nb),   round8(x) = x rounded up to 8,
+ *      which is at most 16 * na*nb + 64 * max_frontiers + 4096.
+ *  12. SVO_ERR_INVALID with the argument named, nothing launched and the context still usable, looked for in this order: a null
+ *      ctx; a null cls, params, workspace, out; na, nb outside 1..8192, na*nb > 2^24; free_mask 0; unknown_mask 0; min_size
+ *      outside 1..2^24; max_frontiers outside 1..65536; masks that share a bit; frontiers, goal_cells and label all NULL; cost,
+ *      label, goal_cells off 4 bytes; frontiers, workspace, counts off 8 bytes.  cls, blocked and cost are only read; they must not
+ *      overlap an output or the workspace.
+ * The defaults are NOT tuned on real data: the clearance's na and nb, free_mask = 1 << SVO_VOXEL_GRID_LEVEL, unknown_mask =
+ * 1 << SVO_VOXEL_GRID_UNKNOWN, min_size 3, max_frontiers 1024.
+ * The pipeline never calls the entry by itself; call it after the clearance (and, for best_cell, the route) it reads, before the
+ * route that takes goal_cells. */
+#define SVO_GRID_FRONTIER_NONE 0xFFFFFFFFu
+typedef struct svo_grid_frontier_params {
+  int na, nb;             /* each 1..8192, na*nb <= 2^24 */
+  uint32_t free_mask;     /* != 0: bit c set makes class c (0..31) FREE */
+  uint32_t unknown_mask;  /* != 0, no bit in common with free_mask */
+  uint32_t min_size;      /* 1..2^24: smallest frontier kept, in cells */
+  int max_frontiers;      /* 1..65536: records written; the route's n_goals limit */
+} svo_grid_frontier_params;
+typedef struct svo_grid_frontier {        /* 48 bytes, 8-byte aligned */
+  uint32_t first_cell, size, rep_cell, best_cell, best_cost;
+  uint16_t min_a, max_a, min_b, max_b;
+  uint32_t reserved;                      /* 0 */
+  uint64_t sum_a, sum_b;
+} svo_grid_frontier;
+typedef struct svo_grid_frontier_out {    /* each may be NULL, but not all three */
+  svo_grid_frontier* frontiers;           /* max_frontiers records */
+  uint32_t* goal_cells;                   /* max_frontiers */
+  uint32_t* label;                        /* na*nb */
+} svo_grid_frontier_out;
+/* The defaults above for the grid of a clearance.  Pure; SVO_ERR_INVALID for a null pointer or an na, nb the clearance refuses. */
+int svo_grid_frontier_default_params(const svo_grid_clearance_params* clearance, svo_grid_frontier_params* out);
+/* Item 11's size; 0 for a shape or a max_frontiers that item 12 refuses.  Pure. */
+size_t svo_grid_frontier_workspace_bytes(int na, int nb, int max_frontiers);
+/* DEVICE pointers, asynchronous on svo_stream(ctx).  Everything it enqueues is one "grid_frontier" profile bracket. */
+int svo_grid_frontiers_dev(svo_ctx* ctx, const uint8_t* cls, const uint8_t* blocked, const uint32_t* cost,
+                           const svo_grid_frontier_params* params, void* workspace, const svo_grid_frontier_out* out, uint64_t* counts);
+/* HOST arrays and outputs (no alignment asked), synchronous: one device allocation for the call, freed after the stream is drained
+ * whatever failed.  The caller's frontiers are copied up first, so that the records item 7 leaves untouched come back as they were.
+ * counts: 8 u64 on the host or NULL. */
+int svo_grid_frontiers(svo_ctx* ctx, const uint8_t* cls, const uint8_t* blocked, const uint32_t* cost,
+                       const svo_grid_frontier_params* params, const svo_grid_frontier_out* out, uint64_t* counts);
+/* Measurement aid: combine != 0 (the state of a new context) lets runs of equal rank along a wavefront add into a frontier's
+ * statistics once; 0 makes every cell issue its own atomics.  It cannot change a bit of an output.  DESIGN 7m gives the figures. */
+int svo_grid_frontier_set_mode(svo_ctx* ctx, int combine);
 
 /* ------------------------------------------------------------------- a8 --
  * ImageProcessor::triangulate_stereo's reprojection loop

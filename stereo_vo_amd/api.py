@@ -369,6 +369,49 @@ def _route_params(params, overrides):
     return _params(lambda: GridRouteParams(0, 0, 0, 0, GRID_ROUTE_MAX_COST, 64, 4096, 0), params, **overrides)
 
 
+class GridFrontierParams(C.Structure):
+    """svo_grid_frontier_params: na x nb cells (each 1..8192, na*nb <= 2^24), the classes that are FREE and those that are UNKNOWN as
+    bit masks (each != 0, no common bit), the smallest frontier kept in cells (1..2^24) and the records written (1..65536)."""
+    _fields_ = [("na", C.c_int), ("nb", C.c_int), ("free_mask", C.c_uint32), ("unknown_mask", C.c_uint32), ("min_size", C.c_uint32),
+                ("max_frontiers", C.c_int)]
+
+
+class GridFrontierOut(C.Structure):
+    """svo_grid_frontier_out: frontiers max_frontiers records of GRID_FRONTIER_DTYPE, goal_cells max_frontiers uint32, label na*nb
+    uint32; each may be None, but not all three."""
+    _fields_ = [("frontiers", C.c_void_p), ("goal_cells", C.c_void_p), ("label", C.c_void_p)]
+
+
+GRID_FRONTIER_NONE = 0xFFFFFFFF  # SVO_GRID_FRONTIER_NONE
+GRID_FRONTIER_COUNTS = ("n_free", "n_unknown", "n_frontier_cells", "n_frontiers", "n_kept", "n_written", "n_kept_cells")
+GRID_FRONTIER_COMBINE_DEFAULT = True  # svo_grid_frontier_set_mode's state of a new context
+# svo_grid_frontier: 48 bytes
+GRID_FRONTIER_DTYPE = np.dtype([("first_cell", "<u4"), ("size", "<u4"), ("rep_cell", "<u4"), ("best_cell", "<u4"), ("best_cost", "<u4"),
+                                ("min_a", "<u2"), ("max_a", "<u2"), ("min_b", "<u2"), ("max_b", "<u2"), ("reserved", "<u4"),
+                                ("sum_a", "<u8"), ("sum_b", "<u8")])
+assert GRID_FRONTIER_DTYPE.itemsize == 48
+
+
+def grid_frontier_default_params(clearance):
+    """svo_grid_frontier_default_params for a GridClearanceParams: its na x nb, LEVEL cells free, UNKNOWN cells unknown, min_size 3,
+    max_frontiers 1024 (not tuned on real data)."""
+    p = GridFrontierParams()
+    if lib().svo_grid_frontier_default_params(C.byref(clearance), C.byref(p)) != 0:
+        raise SvoError("svo_grid_frontier_default_params: the clearance's na and nb must be in range")
+    return p
+
+
+def grid_frontier_workspace_bytes(na, nb, max_frontiers):
+    """svo_grid_frontier_workspace_bytes (no GPU involved); 0 for a refused shape or max_frontiers."""
+    return int(lib().svo_grid_frontier_workspace_bytes(int(na), int(nb), int(max_frontiers)))
+
+
+def _frontier_params(params, overrides):
+    """params and / or its fields as keywords; without params the defaults' masks, min_size and max_frontiers, and na and nb from the
+    keywords (the library refuses what is left at 0)."""
+    return _params(lambda: GridFrontierParams(0, 0, 1 << VOXEL_GRID_LEVEL, 1 << VOXEL_GRID_UNKNOWN, 3, 1024), params, **overrides)
+
+
 SPECKLE_TILE = (64, 16)  # SVO_SPECKLE_TILE_W, SVO_SPECKLE_TILE_H
 
 
@@ -562,6 +605,8 @@ SYMBOLS = [
     "svo_voxel_grid_set_mode",
     "svo_grid_clearance_default_params", "svo_grid_clearance_workspace_bytes", "svo_grid_clearance_dev", "svo_grid_clearance",
     "svo_grid_route_default_params", "svo_grid_route_workspace_bytes", "svo_grid_route_dev", "svo_grid_route",
+    "svo_grid_frontier_default_params", "svo_grid_frontier_workspace_bytes", "svo_grid_frontiers_dev", "svo_grid_frontiers",
+    "svo_grid_frontier_set_mode",
     "svo_voxel_map_remove_dev", "svo_voxel_map_remove_pose7_dev", "svo_voxel_map_remove_sync", "svo_voxel_map_move_dev", "svo_voxel_map_move_pose7_dev",
     "svo_voxel_ledger_bytes", "svo_voxel_ledger_create", "svo_voxel_ledger_destroy", "svo_voxel_ledger_insert_pose7_dev",
     "svo_voxel_ledger_update_pose7", "svo_voxel_ledger_retire", "svo_voxel_ledger_remove", "svo_voxel_ledger_ids", "svo_voxel_ledger_get",
@@ -699,6 +744,15 @@ def lib():
         L.svo_grid_route_dev.argtypes = [vp, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp]
         L.svo_grid_route.argtypes = [vp, vp, vp, vp, vp, ci, vp, ci, vp, vp]
         for f in ("svo_grid_route_default_params", "svo_grid_route_dev", "svo_grid_route"):
+            getattr(L, f).restype = ci
+        # the ground plan frontiers
+        L.svo_grid_frontier_default_params.argtypes = [vp, vp]
+        L.svo_grid_frontier_workspace_bytes.argtypes = [ci, ci, ci]
+        L.svo_grid_frontier_workspace_bytes.restype = sz
+        L.svo_grid_frontiers_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+        L.svo_grid_frontiers.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.svo_grid_frontier_set_mode.argtypes = [vp, ci]
+        for f in ("svo_grid_frontier_default_params", "svo_grid_frontiers_dev", "svo_grid_frontiers", "svo_grid_frontier_set_mode"):
             getattr(L, f).restype = ci
         # removal, move and the keyframe ledger
         i64 = C.c_int64
@@ -1079,6 +1133,62 @@ class Context:
                                         C.byref(out), _p(c)), "svo_grid_route")
         res["counts"] = dict(zip(GRID_ROUTE_COUNTS, (int(v) for v in c)))
         return res
+
+    # ---- ground plan frontiers
+    def grid_frontiers(self, cls_ptr, params=None, blocked_ptr=None, cost_ptr=None, workspace_ptr=None, frontiers_ptr=None, goal_cells_ptr=None,
+                       label_ptr=None, counts_ptr=None, **overrides):
+        """svo_grid_frontiers_dev: the frontiers of the na x nb uint8 class grid behind cls_ptr: FREE cells (off the cells blocked_ptr
+        marks) with an UNKNOWN edge neighbour, in 8-connected pieces.  params (a GridFrontierParams) and / or its fields as keywords.
+        All pointers are the caller's device memory: blocked_ptr na * nb uint8 or None, cost_ptr na * nb uint32 (a route's cost) or
+        None, workspace_ptr grid_frontier_workspace_bytes(na, nb, max_frontiers) bytes, frontiers_ptr max_frontiers records of
+        GRID_FRONTIER_DTYPE, goal_cells_ptr max_frontiers uint32 (fits grid_route's goals_ptr with n_goals = max_frontiers), label_ptr
+        na * nb uint32 (at least one of the three), counts_ptr 8 uint64 (GRID_FRONTIER_COUNTS and a zero) or None.  Asynchronous on
+        the context's stream; returns the pointers the outputs are behind once the stream reaches this point, with "workspace", "na",
+        "nb", "max_frontiers"."""
+        prm = _frontier_params(params, overrides)
+        out = GridFrontierOut(frontiers_ptr, goal_cells_ptr, label_ptr)
+        self._chk(self.L.svo_grid_frontiers_dev(self.h, cls_ptr, blocked_ptr, cost_ptr, C.byref(prm), workspace_ptr, C.byref(out), counts_ptr),
+                  "svo_grid_frontiers_dev")
+        return {"frontiers": frontiers_ptr, "goal_cells": goal_cells_ptr, "label": label_ptr, "counts": counts_ptr, "workspace": workspace_ptr,
+                "na": prm.na, "nb": prm.nb, "max_frontiers": prm.max_frontiers}
+
+    def grid_frontiers_host(self, cls, blocked=None, cost=None, params=None, **overrides):
+        """svo_grid_frontiers: synchronous.  cls: an (na, nb) uint8 array (na and nb are taken from it unless given); blocked: (na, nb)
+        uint8 or None; cost: (na, nb) uint32 or None.  Returns {"frontiers": the n_written records as a structured array of
+        GRID_FRONTIER_DTYPE, "goal_cells" (max_frontiers,) uint32 padded with GRID_FRONTIER_NONE, "label" (na, nb) uint32, "counts"
+        {GRID_FRONTIER_COUNTS}}."""
+        cls = np.ascontiguousarray(cls, np.uint8)
+        if cls.ndim != 2:
+            raise ValueError("grid_frontiers_host: cls must be an (na, nb) array")
+        if params is None:
+            overrides = {"na": cls.shape[0], "nb": cls.shape[1], **overrides}
+        prm = _frontier_params(params, overrides)
+        if (prm.na, prm.nb) != cls.shape:
+            raise ValueError(f"grid_frontiers_host: cls is {cls.shape}, the parameters say {(prm.na, prm.nb)}")
+        if blocked is not None:
+            blocked = np.ascontiguousarray(blocked, np.uint8)
+            if blocked.shape != cls.shape:
+                raise ValueError("grid_frontiers_host: blocked must have the shape of cls")
+        if cost is not None:
+            cost = np.ascontiguousarray(cost, np.uint32)
+            if cost.shape != cls.shape:
+                raise ValueError("grid_frontiers_host: cost must have the shape of cls")
+        if not 1 <= prm.max_frontiers <= 65536:
+            raise SvoError("svo_grid_frontiers: grid_frontier: max_frontiers outside 1..65536")
+        rec = np.zeros(prm.max_frontiers, GRID_FRONTIER_DTYPE)
+        goal = np.empty(prm.max_frontiers, np.uint32)
+        label = np.empty(cls.shape, np.uint32)
+        out = GridFrontierOut(rec.ctypes.data, goal.ctypes.data, label.ctypes.data)
+        c = np.zeros(8, np.uint64)
+        self._chk(self.L.svo_grid_frontiers(self.h, _p(cls), _p(blocked), _p(cost), C.byref(prm), C.byref(out), _p(c)), "svo_grid_frontiers")
+        counts = dict(zip(GRID_FRONTIER_COUNTS, (int(v) for v in c)))
+        return {"frontiers": rec[:counts["n_written"]].copy(), "goal_cells": goal, "label": label, "counts": counts}
+
+    def grid_frontier_set_mode(self, combine=None):
+        """svo_grid_frontier_set_mode (measurement aid): whether runs of equal rank along a wavefront are combined before the
+        per-frontier atomics; no bit of a result depends on it.  None: the default."""
+        self._chk(self.L.svo_grid_frontier_set_mode(self.h, int(GRID_FRONTIER_COMBINE_DEFAULT if combine is None else bool(combine))),
+                  "svo_grid_frontier_set_mode")
 
     # ---- a8
     def triangulate(self, xy, disp, pose16, focal, cx, cy, baseline):

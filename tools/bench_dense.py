@@ -57,6 +57,13 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      max_rounds = rounds_run and at 64 more, the difference per launch); the path launch alone (the call with the starts minus the
      call without, per step of the longest path); and, as context, the device-to-host copies of blocked and dist2 plus this tool's
      host Dijkstra in Python (256 x 256 only): the detour the entry replaces.
+ 14. frontiers: one svo_grid_frontiers_dev ("grid_frontier" bracket: the counts' memset and every launch, mean of 5; records, goal_cells,
+     label and the counts at the defaults: min_size 3, max_frontiers 1024) of section 11's grid of each filled map off section 12's
+     clearance at an inflation of two cells, with the cost of a route from the grid's centre cell; of seeded 2048 x 2048 grids at
+     (unknown, obstacle) densities (0.05, 0.05), (0.3, 0.1) and (0.6, 0.2); and of a 2048 x 2048 serpentine, one frontier of about two
+     million cells.  Per case the time, the counts, the time without the combining of runs along a wavefront
+     (svo_grid_frontier_set_mode; the same bytes), the time hbm_copy needs for cls, blocked and 8 bytes of labels per cell and, as
+     context, the device-to-host copies of the inputs plus the restatement's numpy route on the host (256 x 256 only).
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -220,6 +227,9 @@ def standalone(S, torch, batch, warmup, reps):
                                   for density, md in ((0.0, 64), (0.001, 64), (0.1, 64), (0.001, 512))]
     out["route_synthetic"] = [route_case(S, torch, ctx, route_random(torch, 2048, 2048, density), None, 0, 0, warmup, copy, density=density)
                               for density in (0.0, 0.1, 0.3)]
+    out["frontier_synthetic"] = [frontier_case(S, torch, ctx, *frontier_random(torch, 2048, 2048, pu, po), warmup, copy, densities=[pu, po])
+                                 for pu, po in ((0.05, 0.05), (0.3, 0.1), (0.6, 0.2))]
+    out["frontier_synthetic"].append(frontier_case(S, torch, ctx, *frontier_serpentine(torch, 2048), warmup, copy, densities="serpentine"))
     ctx.close()
     return out
 
@@ -290,6 +300,7 @@ def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy):
             out[-1].update(grid_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # before the carve changes the map, as the render
             out[-1].update(clearance_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # of the same grid, before the carve too
             out[-1].update(route_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # over that grid's clearance
+            out[-1].update(frontier_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # of that grid, off that clearance
             out[-1].update(render_view(S, torch, ctx, cam, vm, np.asarray(m12[batch - 1]), warmup, copy))
             out[-1].update(carve_and_copy(S, torch, ctx, cam, dm, vm, np.asarray(m12[batch - 1]), warmup, copy))
             vm.close()
@@ -590,6 +601,109 @@ def route_view(S, torch, ctx, vm, c2w, warmup, copy):
     ctx.grid_clearance(cls.data_ptr(), cp, workspace_ptr=offsets.data_ptr(), dist2_ptr=d2.data_ptr(), blocked_ptr=blk.data_ptr())
     ctx.sync()
     return {"route": route_case(S, torch, ctx, blk.reshape(gp.na, gp.nb), d2, 64, 4, warmup, copy, host_detour=True)}
+
+
+def frontier_random(torch, na, nb, p_unknown, p_obstacle, seed=14):
+    """Seeded device arrays: cls drawn per cell, blocked 2 on OBSTACLE cells, cost below 2^20 with a quarter NONE."""
+    g = torch.Generator(device="cuda")
+    g.manual_seed(seed)
+    u = torch.rand((na, nb), generator=g, device="cuda")
+    cls = torch.where(u < p_unknown, 0, torch.where(u < p_unknown + p_obstacle, 2, 1)).to(torch.uint8)
+    blocked = ((cls == 2) * 2).to(torch.uint8)
+    cost = torch.randint(0, 1 << 20, (na, nb), generator=g, device="cuda", dtype=torch.int32)
+    cost[torch.rand((na, nb), generator=g, device="cuda") < 0.25] = -1
+    return cls, blocked, cost
+
+
+def frontier_serpentine(torch, n):
+    """Even rows LEVEL, odd rows UNKNOWN but for one LEVEL connector at alternating ends: one frontier of about n * n / 2 cells."""
+    cls = torch.ones((n, n), dtype=torch.uint8, device="cuda")
+    cls[1::2] = 0
+    cls[1::4, n - 1] = 1
+    cls[3::4, 0] = 1
+    return cls, None, None
+
+
+def frontier_case(S, torch, ctx, cls, blocked, cost, warmup, copy, host_detour=False, **tags):
+    """Section 14 for one (na, nb) uint8 device class grid, its uint8 device blocked and uint32 device cost (or None each)."""
+    api = S.api
+    na, nb = cls.shape
+    n = na * nb
+    prm = api.grid_frontier_default_params(api.GridClearanceParams(na, nb, 4, 64, 0.5, 0.0))
+    mf = prm.max_frontiers
+    ws = torch.empty(api.grid_frontier_workspace_bytes(na, nb, mf) // 8, dtype=torch.int64, device="cuda")
+    rec = torch.empty(6 * mf, dtype=torch.int64, device="cuda")
+    goal = torch.empty(mf, dtype=torch.int32, device="cuda")
+    label = torch.empty(n, dtype=torch.int32, device="cuda")
+    cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+
+    def call():
+        ctx.grid_frontiers(cls.data_ptr(), prm, blocked_ptr=None if blocked is None else blocked.data_ptr(),
+                           cost_ptr=None if cost is None else cost.data_ptr(), workspace_ptr=ws.data_ptr(), frontiers_ptr=rec.data_ptr(),
+                           goal_cells_ptr=goal.data_ptr(), label_ptr=label.data_ptr(), counts_ptr=cnt.data_ptr())
+
+    def timed(combine):
+        ctx.grid_frontier_set_mode(combine)
+        for _ in range(warmup):
+            call()
+        ctx.profile_select("grid_frontier")
+        for _ in range(5):
+            call()
+        ms, k = ctx.profile_read()
+        ctx.profile_select("")
+        ctx.grid_frontier_set_mode(None)
+        return ms / k, [int(v) for v in cnt.cpu()], (rec.cpu().numpy().tobytes(), goal.cpu().numpy().tobytes(), label.cpu().numpy().tobytes())
+
+    ms, counts, bytes_on = timed(True)
+    ms_plain, counts_plain, bytes_off = timed(False)
+    assert counts == counts_plain and bytes_on[1:] == bytes_off[1:] and bytes_on[0][:48 * counts[5]] == bytes_off[0][:48 * counts[5]]
+    largest = int(np.frombuffer(bytes_on[0][:48 * counts[5]], api.GRID_FRONTIER_DTYPE)["size"].max()) if counts[5] else 0
+    out = {"cells": [na, nb], "with_blocked": blocked is not None, "with_cost": cost is not None, "min_size": prm.min_size, "max_frontiers": mf, "ms": ms,
+           "ms_without_combining": ms_plain, "counts": counts[:7], "largest_written": largest,
+           "bound_ms": 1e3 * n * (1 + (1 if blocked is not None else 0) + 8) / copy, **tags}  # cls, blocked, 8 B of labels per cell
+    t0 = time.perf_counter()
+    h_cls = cls.cpu().numpy()
+    h_blk = None if blocked is None else blocked.cpu().numpy()
+    h_cost = None if cost is None else cost.cpu().numpy().view(np.uint32).reshape(na, nb)
+    out["d2h_copies_ms"] = 1e3 * (time.perf_counter() - t0)
+    if host_detour:
+        import grid_frontier_ref as F
+        t0 = time.perf_counter()
+        want = F.frontiers_np(h_cls, h_blk, h_cost, F.Params(na, nb, prm.free_mask, prm.unknown_mask, prm.min_size, mf))
+        out["host_numpy_ms"] = 1e3 * (time.perf_counter() - t0)
+        assert list(want.counts) == counts[:7], (want.counts, counts)
+    return out
+
+
+def frontier_view(S, torch, ctx, vm, c2w, warmup, copy):
+    """Section 14 for one filled map: the frontiers of section 11's grid off section 12's clearance (inflation two cells), with the
+    cost of a route from the grid's centre cell."""
+    api = S.api
+    gp = api.voxel_grid_default_params(vm.params.voxel_size)
+    x, z = float(c2w.reshape(3, 4)[0, 3]), float(c2w.reshape(3, 4)[2, 3])
+    gp.origin_a, gp.origin_b = gp.origin_a + z, gp.origin_b + x
+    na, nb = gp.na, gp.nb
+    n = na * nb
+    ws = torch.empty(4 * n, dtype=torch.int64, device="cuda")
+    cls = torch.empty(n, dtype=torch.uint8, device="cuda")
+    offsets, d2, cost = (torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(3))
+    blk = torch.empty(n, dtype=torch.uint8, device="cuda")
+    goals = torch.tensor([(na // 2) * nb + nb // 2], dtype=torch.int32, device="cuda")
+    rws = torch.empty(api.grid_route_workspace_bytes(na, nb) // 8, dtype=torch.int64, device="cuda")
+    cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    vm.grid(gp, workspace_ptr=ws.data_ptr(), cls_ptr=cls.data_ptr())
+    cp = api.grid_clearance_default_params(gp, vm.params.voxel_size)
+    cp.inflate_radius = 2.0 * cp.cell_size
+    ctx.grid_clearance(cls.data_ptr(), cp, workspace_ptr=offsets.data_ptr(), dist2_ptr=d2.data_ptr(), blocked_ptr=blk.data_ptr())
+    rp = api.grid_route_default_params(cp)
+    rp.max_rounds = 1024
+    ctx.grid_route(blk.data_ptr(), rp, goals.data_ptr(), 1, workspace_ptr=rws.data_ptr(), cost_ptr=cost.data_ptr(), counts_ptr=cnt.data_ptr())
+    ctx.sync()
+    out = frontier_case(S, torch, ctx, cls.reshape(na, nb), blk.reshape(na, nb), cost.reshape(na, nb), warmup, copy, host_detour=True)
+    out["route_counts"] = [int(v) for v in cnt.cpu()[:6]]
+    return {"frontier": out}
 
 
 def render_view(S, torch, ctx, cam, vm, c2w, warmup, copy):
@@ -927,6 +1041,13 @@ def main():
                             f"launch {k['path_launch_us']:.1f} us = {k['path_us_per_step']:.3f} us per step of the longest path; one pass over the arrays at hbm_copy "
                             f"{1e3 * k['bound_ms']:.2f} us; device-to-host copies of blocked and dist2 {1e3 * k['d2h_copies_ms']:.0f} us"
                             f" and this tool's Python Dijkstra on the host {k['host_dijkstra_ms']:.0f} ms\n" for k in [c['route']]) +
+                        "".join(
+                            f"  frontiers of that grid off that clearance, cost from a route out of the centre cell (route counts {k['route_counts']}), min_size {k['min_size']}, "
+                            f"max_frontiers {k['max_frontiers']} (counts' memset + ten launches, mean of 5): {1e3 * k['ms']:.1f} us, without the combining of runs "
+                            f"{1e3 * k['ms_without_combining']:.1f} us, counts {k['counts']} (free, unknown, frontier cells, frontiers, kept, written, kept cells), largest "
+                            f"written {k['largest_written']} cells; cls + blocked + 8 B of labels per cell at hbm_copy {1e3 * k['bound_ms']:.2f} us; device-to-host copies of "
+                            f"cls, blocked and cost {1e3 * k['d2h_copies_ms']:.0f} us and the restatement's numpy route on the host {k['host_numpy_ms']:.0f} ms\n"
+                            for k in [c['frontier']]) +
                         f"  removal of the last inserted cloud ({c['remove_move_points']} points, mean of 5): {1e3 * c['remove_ms']:.1f} us, counts {c['remove_counts']} "
                         f"(removed, rejected, missing, short); move to a pose 1 cm and 0.1 degrees away (removal + insert): {1e3 * c['move_ms']:.1f} us, counts "
                         f"{c['move_counts']}; the same cloud inserted once more, same run: {1e3 * c['insert_ms']:.1f} us -> removal / insert "
@@ -944,6 +1065,11 @@ def main():
                         f"launch {k['path_launch_us']:.1f} us = {k['path_us_per_step']:.3f} us per step of the longest path; one pass over the arrays at hbm_copy "
                         f"{1e3 * k['bound_ms']:.2f} us; device-to-host copies of blocked and dist2 {1e3 * k['d2h_copies_ms']:.0f} us"
                         f"\n")
+            for k in s["frontier_synthetic"]:
+                f.write(f"frontiers of a synthetic {k['cells'][0]} x {k['cells'][1]} grid, (unknown, obstacle) densities {k['densities']}, min_size {k['min_size']}, max_frontiers "
+                        f"{k['max_frontiers']} (mean of 5): {1e3 * k['ms']:.1f} us, without the combining of runs {1e3 * k['ms_without_combining']:.1f} us, counts {k['counts']} "
+                        f"(free, unknown, frontier cells, frontiers, kept, written, kept cells), largest written {k['largest_written']} cells; cls + blocked + 8 B of labels "
+                        f"per cell at hbm_copy {1e3 * k['bound_ms']:.2f} us; device-to-host copies of the inputs {1e3 * k['d2h_copies_ms']:.0f} us\n")
             if g and "ratio_ledger_to_clouds" in g:
                 f.write(f"{g['lanes']} lanes in {g['groups']} groups, {g['frames_per_step_per_lane']}-frame steps, {g['rounds']} alternating rounds of {g['steps']} steps, clouds at "
                         f"step {g['cloud_step']}, every lane's ledger holding {g['ledger_held_per_lane']} keyframes and moving all of them (1 cm, 0.1 degrees) after each call: "
