@@ -104,7 +104,7 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * are not counted as "voxel_remove" or "voxel_insert"), "voxel_grid" (one svo_voxel_map_grid_dev: the memsets of the workspace
  * and the counts and both launches), "grid_clearance" (one svo_grid_clearance_dev: the counts' memset and both launches),
  * "grid_route" (one svo_grid_route_dev: its memsets and every launch), "grid_frontier" (one svo_grid_frontiers_dev: the counts'
- * memset and every launch); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
+ * memset and every launch), "grid_view" (one svo_grid_view_dev: its two memsets and both launches); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
 /* Measurement aid: the card's own ceilings for the roofline objects (SURVEY 8d asks for a measured FP64 figure).
@@ -936,6 +936,92 @@ int svo_grid_frontiers(svo_ctx* ctx, const uint8_t* cls, const uint8_t* blocked,
 /* Measurement aid: combine != 0 (the state of a new context) lets runs of equal rank along a wavefront add into a frontier's
  * statistics once; 0 makes every cell issue its own atomics.  It cannot change a bit of an output.  DESIGN 7m gives the figures. */
 int svo_grid_frontier_set_mode(svo_ctx* ctx, int combine);
+
+/* Ground plan view: standing on each of a list of candidate cells, how much ground would be seen, how much of it is ground nobody
+ * has seen yet, and what that is worth against the cost of getting there; the candidates ranked and the best one named: which of the
+ * frontiers' goal_cells a vehicle that explores should drive to.  Integers only, no dependence on thread order, tested with ==.
+ * cell = ia*nb + ib, as in the grid, the clearance, the route and the frontiers.
+ * INPUTS (device memory for the _dev entry): cls, na*nb u8, required (svo_voxel_map_grid*'s cls or any other class grid); views,
+ * n_views (1..4096) u32 cell indices (the frontiers' goal_cells fit as they are, padding included); cost, na*nb u32 or NULL (a
+ * route's cost field, for instance the one whose only goal is the vehicle's cell).
+ *   1. A cell is OPAQUE iff cls < 32 and bit cls of opaque_mask is set.  It is GAIN iff cls < 32 and bit cls of gain_mask is set.
+ *      Values >= 32 are neither.  The masks may share a bit: with the UNKNOWN bit in both, a line ends at the first unknown cell and
+ *      only the first layer of unknown ground counts (the conservative gain); with it in gain_mask only, unknown ground is looked
+ *      through (the optimistic gain).
+ *   2. View i is USED iff views[i] < na*nb and that cell is not OPAQUE.  Every other entry is IGNORED: 0xFFFFFFFF padding, an index
+ *      outside the grid, a view standing in a wall.  Duplicates are each used.
+ *   3. The line from V = (va, vb) to T = (ta, tb): da = ta - va, db = tb - vb, n = max(|da|, |db|), and for i = 0..n
+ *        L_i = (va + sgn(da) * floor((2*i*|da| + n) / (2n)), vb + sgn(db) * floor((2*i*|db| + n) / (2n))).
+ *      L_0 = V, L_n = T; the major coordinate moves one cell per step; a tie of the minor coordinate rounds away from V.  The rule
+ *      commutes with the grid's eight symmetries; it is not symmetric in V and T.  Every L_i lies in the bounding box of V and T.
+ *   4. T is VISIBLE from V iff T is inside the grid, da^2 + db^2 <= max_range^2, no L_i with 1 <= i <= n-1 is OPAQUE, and for every
+ *      step L_(i-1) -> L_i, 1 <= i <= n, that changes both coordinates, not both cells it passes between, (a_i, b_(i-1)) and
+ *      (a_(i-1), b_i), are OPAQUE (no sight through a closed corner: the route's no-corner-cutting rule for light).  T itself may be
+ *      OPAQUE: one sees the face of a wall.  V is visible from itself.  Visibility is defined per target by its own line; "visible
+ *      iff the predecessor is visible" is a different function.
+ *   5. Record i (svo_grid_view_rec), for a used view: cell; n_visible; n_gain, the visible GAIN cells; n_opaque, the visible OPAQUE
+ *      cells; cost = cost[cell], or 0xFFFFFFFF when cost is NULL; score; reserved = 0.  For an ignored view: cell = 0xFFFFFFFF, the
+ *      three tallies 0, cost = 0xFFFFFFFF, score = 0.  All n_views records are written.
+ *   6. score of a used view: 0 when cost is given and cost[cell] == 0xFFFFFFFF (unreachable).  Otherwise with g = gain_weight *
+ *      n_gain in u64 (below 2^34) and c = cost[cell] / cost_div, or 0 when cost is NULL: score = g > c ? min(g - c, 0xFFFFFFFE) : 0.
+ *   7. order[r] (u32, n_views entries) is the view index of rank r: descending score, ties to the smaller index.  Ignored views are
+ *      ranked too, with score 0.
+ *   8. best (4 u32) is {cell, index, score, n_gain} of order[0] when its score is > 0, else {0xFFFFFFFF, 0xFFFFFFFF, 0, 0}.  Its
+ *      first word goes into svo_grid_route_dev as goals with n_goals = 1; the route ignores 0xFFFFFFFF by its rule 3.
+ *   9. seen[cell] (u32, na*nb, optional) is the smallest index of a used view from which the cell is visible, 0xFFFFFFFF for a cell
+ *      that no used view sees.
+ *  10. counts: 8 u64 on the device, or NULL: {n_used, n_ignored, n_in_range, n_visible, n_gain, n_covered, n_gain_covered, 0}.
+ *      Zeroed on the stream; relaxed adds only.  n_in_range counts the targets inside the grid and the range summed over the used
+ *      views, V included; n_visible and n_gain are the records' sums; n_covered counts the cells seen by at least one used view and
+ *      n_gain_covered the GAIN cells among them, whether or not seen is asked for (the workspace holds the array then).
+ *  11. workspace: svo_grid_view_workspace_bytes(na, nb, n_views) bytes of device memory, 8-byte aligned, contents meaningless on
+ *      entry: a header, 16 bytes per view and one u32 per cell.  The function is pure, computes in size_t and returns 0 for a
+ *      refused shape; the size is
+ *        256 + 16 * n_views + round8(4 * na*nb),   round8(x) = x rounded up to 8.
+ *  12. SVO_ERR_INVALID with the argument named, nothing launched and the context still usable, looked for in this order: a null
+ *      ctx; a null cls, params, views, workspace, out; na, nb outside 1..8192, na*nb > 2^24; opaque_mask 0; gain_mask 0; max_range
+ *      outside 1..255; gain_weight outside 1..65536; cost_div outside 1..2^31; n_views outside 1..4096; records, order, best and
+ *      seen all NULL; views, cost, order, best, seen off 4 bytes; records, workspace, counts off 8 bytes.  cls, views and cost are
+ *      only read; they must not overlap an output or the workspace.
+ * The defaults are NOT tuned on real data: the clearance's na and nb, opaque_mask = 1 << SVO_VOXEL_GRID_OBSTACLE, gain_mask =
+ * 1 << SVO_VOXEL_GRID_UNKNOWN, max_range = min(the clearance's max_dist, 255), gain_weight 16, cost_div 1.
+ * The pipeline never calls the entry by itself; call it after the frontiers whose goal_cells it reads and the route whose cost it
+ * reads, before the route that takes best. */
+#define SVO_GRID_VIEW_NONE 0xFFFFFFFFu
+#define SVO_GRID_VIEW_MAX_VIEWS 4096
+typedef struct svo_grid_view_params {
+  int na, nb;             /* each 1..8192, na*nb <= 2^24 */
+  uint32_t opaque_mask;   /* != 0: bit c set makes class c (0..31) OPAQUE */
+  uint32_t gain_mask;     /* != 0: bit c set makes class c (0..31) GAIN; may share bits with opaque_mask */
+  int max_range;          /* 1..255, in cells */
+  uint32_t gain_weight;   /* 1..65536: score per visible GAIN cell */
+  uint32_t cost_div;      /* 1..2^31: the cost is divided by it before it is taken off */
+} svo_grid_view_params;
+typedef struct svo_grid_view_rec {        /* 32 bytes, 8-byte aligned */
+  uint32_t cell, n_visible, n_gain, n_opaque, cost, score;
+  uint32_t reserved[2];                   /* 0 */
+} svo_grid_view_rec;
+typedef struct svo_grid_view_out {        /* each may be NULL, but not all four */
+  svo_grid_view_rec* records;             /* n_views records */
+  uint32_t* order;                        /* n_views */
+  uint32_t* best;                         /* 4 */
+  uint32_t* seen;                         /* na*nb */
+} svo_grid_view_out;
+/* The defaults above for the grid of a clearance.  Pure; SVO_ERR_INVALID for a null pointer or an na, nb the clearance refuses. */
+int svo_grid_view_default_params(const svo_grid_clearance_params* clearance, svo_grid_view_params* out);
+/* Item 11's size; 0 for a shape or an n_views that item 12 refuses.  Pure. */
+size_t svo_grid_view_workspace_bytes(int na, int nb, int n_views);
+/* DEVICE pointers, asynchronous on svo_stream(ctx).  Everything it enqueues is one "grid_view" profile bracket. */
+int svo_grid_view_dev(svo_ctx* ctx, const uint8_t* cls, const uint32_t* views, int n_views, const uint32_t* cost,
+                      const svo_grid_view_params* params, void* workspace, const svo_grid_view_out* out, uint64_t* counts);
+/* HOST arrays and outputs (no alignment asked), synchronous: one device allocation for the call, freed after the stream is drained
+ * whatever failed.  counts: 8 u64 on the host or NULL. */
+int svo_grid_view(svo_ctx* ctx, const uint8_t* cls, const uint32_t* views, int n_views, const uint32_t* cost,
+                  const svo_grid_view_params* params, const svo_grid_view_out* out, uint64_t* counts);
+/* Measurement aid: staged != 0 (the state of a new context) lets a view's workgroup walk its lines over two bit planes of the
+ * window staged in LDS; 0 makes every step of a line read cls from global memory.  It cannot change a bit of an output.  DESIGN 7n
+ * gives the figures. */
+int svo_grid_view_set_mode(svo_ctx* ctx, int staged);
 
 /* ------------------------------------------------------------------- a8 --
  * ImageProcessor::triangulate_stereo's reprojection loop

@@ -412,6 +412,51 @@ def _frontier_params(params, overrides):
     return _params(lambda: GridFrontierParams(0, 0, 1 << VOXEL_GRID_LEVEL, 1 << VOXEL_GRID_UNKNOWN, 3, 1024), params, **overrides)
 
 
+class GridViewParams(C.Structure):
+    """svo_grid_view_params: na x nb cells (each 1..8192, na*nb <= 2^24), the classes that are OPAQUE and those that are GAIN as bit
+    masks (each != 0; they may share bits), the range in cells (1..255), the score per visible GAIN cell (1..65536) and what the cost
+    is divided by before it is taken off (1..2^31)."""
+    _fields_ = [("na", C.c_int), ("nb", C.c_int), ("opaque_mask", C.c_uint32), ("gain_mask", C.c_uint32), ("max_range", C.c_int),
+                ("gain_weight", C.c_uint32), ("cost_div", C.c_uint32)]
+
+
+class GridViewOut(C.Structure):
+    """svo_grid_view_out: records n_views records of GRID_VIEW_DTYPE, order n_views uint32, best 4 uint32, seen na*nb uint32; each may
+    be None, but not all four."""
+    _fields_ = [("records", C.c_void_p), ("order", C.c_void_p), ("best", C.c_void_p), ("seen", C.c_void_p)]
+
+
+GRID_VIEW_NONE = 0xFFFFFFFF  # SVO_GRID_VIEW_NONE
+GRID_VIEW_MAX_VIEWS = 4096  # SVO_GRID_VIEW_MAX_VIEWS
+GRID_VIEW_COUNTS = ("n_used", "n_ignored", "n_in_range", "n_visible", "n_gain", "n_covered", "n_gain_covered")
+GRID_VIEW_BEST = ("cell", "index", "score", "n_gain")
+GRID_VIEW_STAGED_DEFAULT = True  # svo_grid_view_set_mode's state of a new context
+# svo_grid_view_rec: 32 bytes
+GRID_VIEW_DTYPE = np.dtype([("cell", "<u4"), ("n_visible", "<u4"), ("n_gain", "<u4"), ("n_opaque", "<u4"), ("cost", "<u4"), ("score", "<u4"),
+                            ("reserved", "<u4", (2,))])
+assert GRID_VIEW_DTYPE.itemsize == 32
+
+
+def grid_view_default_params(clearance):
+    """svo_grid_view_default_params for a GridClearanceParams: its na x nb, OBSTACLE cells opaque, UNKNOWN cells the gain, max_range
+    min(its max_dist, 255), gain_weight 16, cost_div 1 (not tuned on real data)."""
+    p = GridViewParams()
+    if lib().svo_grid_view_default_params(C.byref(clearance), C.byref(p)) != 0:
+        raise SvoError("svo_grid_view_default_params: the clearance's na and nb must be in range")
+    return p
+
+
+def grid_view_workspace_bytes(na, nb, n_views):
+    """svo_grid_view_workspace_bytes (no GPU involved); 0 for a refused shape or n_views."""
+    return int(lib().svo_grid_view_workspace_bytes(int(na), int(nb), int(n_views)))
+
+
+def _view_params(params, overrides):
+    """params and / or its fields as keywords; without params the defaults' masks, range 64, weight and divisor, and na and nb from the
+    keywords (the library refuses what is left at 0)."""
+    return _params(lambda: GridViewParams(0, 0, 1 << VOXEL_GRID_OBSTACLE, 1 << VOXEL_GRID_UNKNOWN, 64, 16, 1), params, **overrides)
+
+
 SPECKLE_TILE = (64, 16)  # SVO_SPECKLE_TILE_W, SVO_SPECKLE_TILE_H
 
 
@@ -607,6 +652,7 @@ SYMBOLS = [
     "svo_grid_route_default_params", "svo_grid_route_workspace_bytes", "svo_grid_route_dev", "svo_grid_route",
     "svo_grid_frontier_default_params", "svo_grid_frontier_workspace_bytes", "svo_grid_frontiers_dev", "svo_grid_frontiers",
     "svo_grid_frontier_set_mode",
+    "svo_grid_view_default_params", "svo_grid_view_workspace_bytes", "svo_grid_view_dev", "svo_grid_view", "svo_grid_view_set_mode",
     "svo_voxel_map_remove_dev", "svo_voxel_map_remove_pose7_dev", "svo_voxel_map_remove_sync", "svo_voxel_map_move_dev", "svo_voxel_map_move_pose7_dev",
     "svo_voxel_ledger_bytes", "svo_voxel_ledger_create", "svo_voxel_ledger_destroy", "svo_voxel_ledger_insert_pose7_dev",
     "svo_voxel_ledger_update_pose7", "svo_voxel_ledger_retire", "svo_voxel_ledger_remove", "svo_voxel_ledger_ids", "svo_voxel_ledger_get",
@@ -753,6 +799,15 @@ def lib():
         L.svo_grid_frontiers.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.svo_grid_frontier_set_mode.argtypes = [vp, ci]
         for f in ("svo_grid_frontier_default_params", "svo_grid_frontiers_dev", "svo_grid_frontiers", "svo_grid_frontier_set_mode"):
+            getattr(L, f).restype = ci
+        # the ground plan view
+        L.svo_grid_view_default_params.argtypes = [vp, vp]
+        L.svo_grid_view_workspace_bytes.argtypes = [ci, ci, ci]
+        L.svo_grid_view_workspace_bytes.restype = sz
+        L.svo_grid_view_dev.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp]
+        L.svo_grid_view.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp]
+        L.svo_grid_view_set_mode.argtypes = [vp, ci]
+        for f in ("svo_grid_view_default_params", "svo_grid_view_dev", "svo_grid_view", "svo_grid_view_set_mode"):
             getattr(L, f).restype = ci
         # removal, move and the keyframe ledger
         i64 = C.c_int64
@@ -1189,6 +1244,57 @@ class Context:
         per-frontier atomics; no bit of a result depends on it.  None: the default."""
         self._chk(self.L.svo_grid_frontier_set_mode(self.h, int(GRID_FRONTIER_COMBINE_DEFAULT if combine is None else bool(combine))),
                   "svo_grid_frontier_set_mode")
+
+    # ---- ground plan view
+    def grid_view(self, cls_ptr, views_ptr, n_views, params=None, cost_ptr=None, workspace_ptr=None, records_ptr=None, order_ptr=None,
+                  best_ptr=None, seen_ptr=None, counts_ptr=None, **overrides):
+        """svo_grid_view_dev: what each of the n_views uint32 cells behind views_ptr (the frontiers' goal_cells fit as they are) would
+        see of the na x nb uint8 class grid behind cls_ptr, scored against the uint32 cost field behind cost_ptr (a route's cost) where
+        given, ranked, and the best one named.  All device pointers: cost_ptr na * nb uint32 or None, workspace_ptr
+        grid_view_workspace_bytes(na, nb, n_views) bytes, records_ptr n_views records of GRID_VIEW_DTYPE, order_ptr n_views uint32,
+        best_ptr 4 uint32 (GRID_VIEW_BEST; its first word fits grid_route's goals_ptr with n_goals = 1), seen_ptr na * nb uint32 (at
+        least one of the four), counts_ptr 8 uint64 (GRID_VIEW_COUNTS and a zero) or None.  Asynchronous on the context's stream.
+        Returns the pointers and "na", "nb", "n_views"."""
+        prm = _view_params(params, overrides)
+        out = GridViewOut(records_ptr, order_ptr, best_ptr, seen_ptr)
+        self._chk(self.L.svo_grid_view_dev(self.h, cls_ptr, views_ptr, int(n_views), cost_ptr, C.byref(prm), workspace_ptr, C.byref(out), counts_ptr),
+                  "svo_grid_view_dev")
+        return {"records": records_ptr, "order": order_ptr, "best": best_ptr, "seen": seen_ptr, "counts": counts_ptr, "workspace": workspace_ptr,
+                "na": prm.na, "nb": prm.nb, "n_views": int(n_views)}
+
+    def grid_view_host(self, cls, views, cost=None, params=None, **overrides):
+        """svo_grid_view: synchronous.  cls: an (na, nb) uint8 array (na and nb are taken from it unless given); views: 1..4096 uint32
+        cell indices; cost: (na, nb) uint32 or None.  Returns {"records": a structured array of GRID_VIEW_DTYPE, one per view, "order"
+        (n_views,) uint32, "best" {GRID_VIEW_BEST}, "seen" (na, nb) uint32, "counts" {GRID_VIEW_COUNTS}}."""
+        cls = np.ascontiguousarray(cls, np.uint8)
+        if cls.ndim != 2:
+            raise ValueError("grid_view_host: cls must be an (na, nb) array")
+        if params is None:
+            overrides = {"na": cls.shape[0], "nb": cls.shape[1], **overrides}
+        prm = _view_params(params, overrides)
+        if (prm.na, prm.nb) != cls.shape:
+            raise ValueError(f"grid_view_host: cls is {cls.shape}, the parameters say {(prm.na, prm.nb)}")
+        views = np.ascontiguousarray(views, np.uint32).ravel()
+        if cost is not None:
+            cost = np.ascontiguousarray(cost, np.uint32)
+            if cost.shape != cls.shape:
+                raise ValueError("grid_view_host: cost must have the shape of cls")
+        if not 1 <= len(views) <= GRID_VIEW_MAX_VIEWS:
+            raise SvoError("svo_grid_view: grid_view: n_views outside 1..4096")
+        rec = np.zeros(len(views), GRID_VIEW_DTYPE)
+        order = np.empty(len(views), np.uint32)
+        best = np.empty(4, np.uint32)
+        seen = np.empty(cls.shape, np.uint32)
+        out = GridViewOut(rec.ctypes.data, order.ctypes.data, best.ctypes.data, seen.ctypes.data)
+        c = np.zeros(8, np.uint64)
+        self._chk(self.L.svo_grid_view(self.h, _p(cls), _p(views), len(views), _p(cost), C.byref(prm), C.byref(out), _p(c)), "svo_grid_view")
+        return {"records": rec, "order": order, "best": dict(zip(GRID_VIEW_BEST, (int(v) for v in best))), "seen": seen,
+                "counts": dict(zip(GRID_VIEW_COUNTS, (int(v) for v in c)))}
+
+    def grid_view_set_mode(self, staged=None):
+        """svo_grid_view_set_mode (measurement aid): whether a view's lines are walked over bit planes of its window staged in LDS or
+        over cls in global memory; no bit of a result depends on it.  None: the default."""
+        self._chk(self.L.svo_grid_view_set_mode(self.h, int(GRID_VIEW_STAGED_DEFAULT if staged is None else bool(staged))), "svo_grid_view_set_mode")
 
     # ---- a8
     def triangulate(self, xy, disp, pose16, focal, cx, cy, baseline):

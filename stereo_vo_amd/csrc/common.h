@@ -67,6 +67,7 @@ struct svo_ctx {
   int dense_cost_lds_granted = 0;
   int sgm_lds_granted = 0;             // sgm_volume_kernel (sgm.hip), likewise
   int frontier_combine = 1;            // svo_grid_frontier_set_mode (frontier.hip): a measurement aid, no bit of a result depends on it
+  int view_staged = 1;                 // svo_grid_view_set_mode (view.hip), likewise
   // completion words (see SvoPublish)
   int word_seq = 0;
   unsigned arrive_total = 0;
@@ -154,7 +155,7 @@ enum SvoProfTag { SVO_PROF_NONE = 0, SVO_PROF_CORNER_RESPONSE, SVO_PROF_CORNER_N
                   SVO_PROF_STEREO_BM, SVO_PROF_STEREO_DENSE_BATCH, SVO_PROF_CLOUD, SVO_PROF_SPECKLE, SVO_PROF_LR_CHECK,
                   SVO_PROF_STEREO_SGM, SVO_PROF_VOXEL_INSERT, SVO_PROF_VOXEL_EXTRACT,
                   SVO_PROF_VOXEL_CARVE, SVO_PROF_VOXEL_COPY, SVO_PROF_VOXEL_RENDER, SVO_PROF_VOXEL_REMOVE, SVO_PROF_VOXEL_MOVE,
-                  SVO_PROF_VOXEL_GRID, SVO_PROF_GRID_CLEARANCE, SVO_PROF_GRID_ROUTE, SVO_PROF_GRID_FRONTIER };
+                  SVO_PROF_VOXEL_GRID, SVO_PROF_GRID_CLEARANCE, SVO_PROF_GRID_ROUTE, SVO_PROF_GRID_FRONTIER, SVO_PROF_GRID_VIEW };
 
 // RAII event pair around one launch of the selected kernel (no-op for every other kernel).
 struct SvoProfScope {

@@ -64,6 +64,13 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      million cells.  Per case the time, the counts, the time without the combining of runs along a wavefront
      (svo_grid_frontier_set_mode; the same bytes), the time hbm_copy needs for cls, blocked and 8 bytes of labels per cell and, as
      context, the device-to-host copies of the inputs plus the restatement's numpy route on the host (256 x 256 only).
+ 15. view: one svo_grid_view_dev ("grid_view" bracket: two memsets and both launches, mean of 5; records, order, best, seen and the
+     counts at the defaults) over section 14's goal_cells (all 1024 entries) and cost field of section 11's grid of each filled map,
+     and over a seeded 2048 x 2048 grid with 1024 and 4096 views at max_range 64 and 255.  Per case the time staged in LDS and the
+     time with every step reading cls (svo_grid_view_set_mode; the same bytes), the counts, the steps walked per target in range
+     from the restatement's counter (the synthetic cases: over the first 8 views), the time hbm_copy needs for the windows once per
+     used view, the records and seen and, as context, the device-to-host copies of the inputs plus the restatement's numpy route on
+     the host (256 x 256 only): the detour the entry replaces.
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -230,6 +237,7 @@ def standalone(S, torch, batch, warmup, reps):
     out["frontier_synthetic"] = [frontier_case(S, torch, ctx, *frontier_random(torch, 2048, 2048, pu, po), warmup, copy, densities=[pu, po])
                                  for pu, po in ((0.05, 0.05), (0.3, 0.1), (0.6, 0.2))]
     out["frontier_synthetic"].append(frontier_case(S, torch, ctx, *frontier_serpentine(torch, 2048), warmup, copy, densities="serpentine"))
+    out["view_synthetic"] = view_synthetic(S, torch, ctx, warmup, copy)
     ctx.close()
     return out
 
@@ -703,7 +711,85 @@ def frontier_view(S, torch, ctx, vm, c2w, warmup, copy):
     ctx.sync()
     out = frontier_case(S, torch, ctx, cls.reshape(na, nb), blk.reshape(na, nb), cost.reshape(na, nb), warmup, copy, host_detour=True)
     out["route_counts"] = [int(v) for v in cnt.cpu()[:6]]
-    return {"frontier": out}
+    # section 15: the view over that call's goal_cells (all max_frontiers entries, padding included) and that route's cost
+    fp = api.grid_frontier_default_params(cp)
+    fws = torch.empty(api.grid_frontier_workspace_bytes(na, nb, fp.max_frontiers) // 8, dtype=torch.int64, device="cuda")
+    goal = torch.empty(fp.max_frontiers, dtype=torch.int32, device="cuda")
+    ctx.grid_frontiers(cls.data_ptr(), fp, blocked_ptr=blk.data_ptr(), cost_ptr=cost.data_ptr(), workspace_ptr=fws.data_ptr(), goal_cells_ptr=goal.data_ptr())
+    ctx.sync()
+    view = view_case(S, torch, ctx, cls.reshape(na, nb), goal, cost.reshape(na, nb), cp.max_dist, warmup, copy, host_detour=True)
+    return {"frontier": out, "view": view}
+
+
+def view_case(S, torch, ctx, cls, views, cost, max_range, warmup, copy, host_detour=False, sample=8, **tags):
+    """Section 15 for one (na, nb) uint8 device class grid, a device list of uint32 view cells and a uint32 device cost (or None)."""
+    import grid_view_ref as V
+    api = S.api
+    na, nb = cls.shape
+    n, nv = na * nb, views.numel()
+    prm = api.grid_view_default_params(api.GridClearanceParams(na, nb, 4, max_range, 0.5, 0.0))
+    ws = torch.empty(api.grid_view_workspace_bytes(na, nb, nv) // 8, dtype=torch.int64, device="cuda")
+    rec = torch.empty(4 * nv, dtype=torch.int64, device="cuda")
+    order = torch.empty(nv, dtype=torch.int32, device="cuda")
+    best = torch.empty(4, dtype=torch.int32, device="cuda")
+    seen = torch.empty(n, dtype=torch.int32, device="cuda")
+    cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+
+    def call():
+        ctx.grid_view(cls.data_ptr(), views.data_ptr(), nv, prm, cost_ptr=None if cost is None else cost.data_ptr(), workspace_ptr=ws.data_ptr(),
+                      records_ptr=rec.data_ptr(), order_ptr=order.data_ptr(), best_ptr=best.data_ptr(), seen_ptr=seen.data_ptr(), counts_ptr=cnt.data_ptr())
+
+    def timed(staged):
+        ctx.grid_view_set_mode(staged)
+        for _ in range(warmup):
+            call()
+        ctx.profile_select("grid_view")
+        for _ in range(5):
+            call()
+        ms, k = ctx.profile_read()
+        ctx.profile_select("")
+        ctx.grid_view_set_mode(None)
+        return ms / k, [int(v) for v in cnt.cpu()], tuple(t.cpu().numpy().tobytes() for t in (rec, order, best, seen))
+
+    ms, counts, bytes_on = timed(True)
+    ms_plain, counts_plain, bytes_off = timed(False)
+    assert counts == counts_plain and bytes_on == bytes_off
+    side = 2 * prm.max_range + 1
+    out = {"cells": [na, nb], "n_views": nv, "max_range": prm.max_range, "with_cost": cost is not None, "ms": ms, "ms_unstaged": ms_plain,
+           "staged_to_unstaged": ms / ms_plain, "counts": counts[:7], "best": [int(v) for v in best.cpu().numpy().view(np.uint32)],
+           "bound_ms": 1e3 * (counts[0] * side * side + 32 * nv + 4 * n) / copy, **tags}  # the windows once per used view, the records, seen
+    t0 = time.perf_counter()
+    h_cls, h_views = cls.cpu().numpy(), views.cpu().numpy().view(np.uint32)
+    h_cost = None if cost is None else cost.cpu().numpy().view(np.uint32).reshape(na, nb)
+    out["d2h_copies_ms"] = 1e3 * (time.perf_counter() - t0)
+    vp = V.Params(na, nb, prm.opaque_mask, prm.gain_mask, prm.max_range, prm.gain_weight, prm.cost_div)
+    stats = {}
+    if host_detour:
+        t0 = time.perf_counter()
+        want = V.views_np(h_cls, h_views, h_cost, vp, stats=stats)
+        out["host_numpy_ms"] = 1e3 * (time.perf_counter() - t0)
+        assert list(want.counts) == counts[:7], (want.counts, counts)
+        out["device_to_detour"] = ms / (out["d2h_copies_ms"] + out["host_numpy_ms"])
+    else:  # the restatement over the first views only: the steps walked per target
+        V.views_np(h_cls, h_views[:sample], h_cost, vp, stats=stats)
+        out["steps_sampled_views"] = min(sample, nv)
+    out["steps_per_target"] = stats["steps"] / max(stats["targets"], 1)
+    return out
+
+
+def view_synthetic(S, torch, ctx, warmup, copy):
+    """Section 15's ranges: one seeded 2048 x 2048 grid, 1024 and 4096 views drawn among its LEVEL cells, max_range 64 and 255."""
+    cls, _, cost = frontier_random(torch, 2048, 2048, 0.3, 0.1, seed=15)
+    g = torch.Generator(device="cuda")
+    g.manual_seed(15)
+    level = torch.nonzero(cls.reshape(-1) == 1).reshape(-1)
+    out = []
+    for nv in (1024, 4096):
+        views = level[torch.randint(0, level.numel(), (nv,), generator=g, device="cuda")].to(torch.int32)
+        for max_range in (64, 255):
+            out.append(view_case(S, torch, ctx, cls, views, cost, max_range, warmup, copy, densities=[0.3, 0.1]))
+    return out
 
 
 def render_view(S, torch, ctx, cam, vm, c2w, warmup, copy):
@@ -934,6 +1020,19 @@ def grouped(S, torch, lanes, n_groups, frames, warmup, steps, rounds, step_px, l
             **{k: v for k, v in ledger.items() if "ledger" in k}}
 
 
+def view_line(k):
+    """Section 15's line of the text report for one view_case."""
+    line = (f"{k['n_views']} views, max_range {k['max_range']} (two memsets + cast + rank, mean of 5): {1e3 * k['ms']:.1f} us staged in LDS, "
+            f"{1e3 * k['ms_unstaged']:.1f} us with every step reading cls (the same bytes): staged / unstaged {k['staged_to_unstaged']:.3f}; counts {k['counts']} "
+            f"(used, ignored, in range, visible, gain, covered, gain covered), best {k['best']} (cell, index, score, gain), "
+            f"{k['steps_per_target']:.2f} steps walked per target in range (restatement")
+    line += f", the first {k['steps_sampled_views']} views)" if "steps_sampled_views" in k else ")"
+    line += f"; the windows once per used view + records + seen at hbm_copy {1e3 * k['bound_ms']:.2f} us; device-to-host copies of cls, views and cost {1e3 * k['d2h_copies_ms']:.0f} us"
+    if "host_numpy_ms" in k:
+        line += f" and the restatement's numpy route on the host {k['host_numpy_ms']:.0f} ms: device / detour {k['device_to_detour']:.5f}"
+    return line + "\n"
+
+
 def api_sub():
     from stereo_vo_amd import api
     return api.SGM_KEYFRAME_SUB_BATCH
@@ -1048,6 +1147,7 @@ def main():
                             f"written {k['largest_written']} cells; cls + blocked + 8 B of labels per cell at hbm_copy {1e3 * k['bound_ms']:.2f} us; device-to-host copies of "
                             f"cls, blocked and cost {1e3 * k['d2h_copies_ms']:.0f} us and the restatement's numpy route on the host {k['host_numpy_ms']:.0f} ms\n"
                             for k in [c['frontier']]) +
+                        "  view over those frontiers' goal_cells and that route's cost: " + view_line(c['view']) +
                         f"  removal of the last inserted cloud ({c['remove_move_points']} points, mean of 5): {1e3 * c['remove_ms']:.1f} us, counts {c['remove_counts']} "
                         f"(removed, rejected, missing, short); move to a pose 1 cm and 0.1 degrees away (removal + insert): {1e3 * c['move_ms']:.1f} us, counts "
                         f"{c['move_counts']}; the same cloud inserted once more, same run: {1e3 * c['insert_ms']:.1f} us -> removal / insert "
@@ -1070,6 +1170,8 @@ def main():
                         f"{k['max_frontiers']} (mean of 5): {1e3 * k['ms']:.1f} us, without the combining of runs {1e3 * k['ms_without_combining']:.1f} us, counts {k['counts']} "
                         f"(free, unknown, frontier cells, frontiers, kept, written, kept cells), largest written {k['largest_written']} cells; cls + blocked + 8 B of labels "
                         f"per cell at hbm_copy {1e3 * k['bound_ms']:.2f} us; device-to-host copies of the inputs {1e3 * k['d2h_copies_ms']:.0f} us\n")
+            for k in s["view_synthetic"]:
+                f.write(f"view over a synthetic {k['cells'][0]} x {k['cells'][1]} grid, (unknown, obstacle) densities {k['densities']}: " + view_line(k))
             if g and "ratio_ledger_to_clouds" in g:
                 f.write(f"{g['lanes']} lanes in {g['groups']} groups, {g['frames_per_step_per_lane']}-frame steps, {g['rounds']} alternating rounds of {g['steps']} steps, clouds at "
                         f"step {g['cloud_step']}, every lane's ledger holding {g['ledger_held_per_lane']} keyframes and moving all of them (1 cm, 0.1 degrees) after each call: "
