@@ -104,7 +104,8 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * are not counted as "voxel_remove" or "voxel_insert"), "voxel_grid" (one svo_voxel_map_grid_dev: the memsets of the workspace
  * and the counts and both launches), "grid_clearance" (one svo_grid_clearance_dev: the counts' memset and both launches),
  * "grid_route" (one svo_grid_route_dev: its memsets and every launch), "grid_frontier" (one svo_grid_frontiers_dev: the counts'
- * memset and every launch), "grid_view" (one svo_grid_view_dev: its two memsets and both launches); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
+ * memset and every launch), "grid_view" (one svo_grid_view_dev: its two memsets and both launches), "grid_surface" (one svo_grid_surface_dev: the
+ * counts' memset and the launch); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
 /* Measurement aid: the card's own ceilings for the roofline objects (SURVEY 8d asks for a measured FP64 figure).
@@ -677,7 +678,8 @@ int svo_voxel_ledger_get(svo_voxel_ledger* ledger, int64_t id, double* pose7, in
  * and the words are formed as written above in 64-bit arithmetic.
  * KNOWN PROPERTIES.  The grid is aligned with the map's axes and is not rotated: a first camera that was pitched gives a tilted
  * "up".  A cell's class is only the span between its highest and lowest voxel inside the band: a slope steeper than
- * obstacle_step per cell is an obstacle, an overhang above the band is not seen.
+ * obstacle_step per cell is an obstacle, an overhang above the band is not seen.  What lies BETWEEN cells (a kerb on a cell
+ * boundary, a long gentle slope, a cell alone in unknown ground) is "Ground plan surface"'s, below.
  * The defaults are NOT tuned on real imagery: the camera convention (up_axis 1, up_sign -1), cells of 0.5 map units (cell_voxels =
  * floor(0.5 / vs + 0.5) clamped to 1..1024, 5 at the default voxel size), 256 x 256 cells starting at a = 0 and centred on b = 0
  * (origin_a = 0, origin_b = -128 * cell_voxels * vs), the band -3 .. +2.5, obstacle_step 0.3, min_count 1.
@@ -722,6 +724,81 @@ int svo_voxel_map_grid(svo_voxel_map* map, const svo_voxel_grid_params* params, 
  * where the word already holds at least the value (words only grow within the launch, so a stale load costs a needless atomic, never
  * a wrong skip).  It cannot change a bit of the outputs or of the workspace.  DESIGN 7j gives the figures and the default. */
 int svo_voxel_grid_set_mode(svo_voxel_map* map, int precheck);
+
+/* Ground plan surface: what the grid's class cannot say because it looks at one cell alone (its KNOWN PROPERTIES above).  From the
+ * grid's cls and top, per cell: the largest height step to an edge neighbour, the relief (highest minus lowest top) under a
+ * vehicle's footprint, how much of the footprint is known ground, and a refined class grid with three new values that every later
+ * step can select by its 32-bit mask.  One launch, no workspace; it depends on no thread order and is tested with ==, floats by
+ * bit pattern.  cell = ia*nb + ib, as in the grid.  No voxel map is involved.
+ *   1. GROUND.  A cell is GROUND iff cls < 32, bit cls of ground_mask is set and top is finite.  A cell whose class bit is set but
+ *      whose top is a NaN or infinite is NONFINITE: it gives no height and no support anywhere, and its own cls_out is
+ *      SVO_GRID_SURFACE_UNSUPPORTED.
+ *   2. Footprint.  rc = footprint_radius / cell_size and r2 = (u64)floor(rc * rc), f64 operations done once on the host; the call is
+ *      refused when rc * rc >= 226.  The footprint of a cell is the set of offsets (da, db) with da^2 + db^2 <= r2, at most 15 cells
+ *      each way; D(r2) is their number (svo_grid_surface_footprint_cells).  Offsets outside the grid hold nothing.
+ *   3. Step.  For a GROUND cell dstep = the maximum of |(double)top - (double)top_n| over its four EDGE neighbours that are inside
+ *      the grid and GROUND, one f64 subtraction each; 0 when there is none.  step = (float)dstep; -1.0f for a cell that is not
+ *      GROUND.  Diagonal neighbours do not count: the route never cuts a corner.
+ *   4. Relief.  For a GROUND cell drelief = (double)hi - (double)lo, hi and lo the largest and smallest top among the GROUND cells of
+ *      its footprint (the cell itself is one); where hi == lo it is +0.0, so that -0.0f and +0.0f are one height.  relief =
+ *      (float)drelief; -1.0f for a cell that is not GROUND.
+ *   5. Support.  support (u16) = the number of GROUND cells in the footprint, written for every cell.
+ *   6. Class.  A cell that is neither GROUND nor NONFINITE keeps its class, values >= 32 included.  A GROUND cell takes the first of
+ *        (a) dstep > max_step                           -> SVO_GRID_SURFACE_STEP (3)
+ *        (b) drelief > max_relief                       -> SVO_GRID_SURFACE_ROUGH (4)
+ *        (c) support * 256 < min_support_256 * D (u32)  -> SVO_GRID_SURFACE_UNSUPPORTED (5)
+ *      and otherwise keeps its class.  Both comparisons are strict and are made on the f64 values, before the rounding to f32.
+ *      +infinity switches (a) or (b) off, min_support_256 = 0 switches (c) off.
+ *   7. counts = {n_ground, n_step, n_rough, n_unsupported, n_nonfinite, n_kept}: 6 u64 on the device, or NULL.  n_unsupported leaves
+ *      out the NONFINITE cells; n_kept: the GROUND cells that keep their class; n_step + n_rough + n_unsupported + n_kept =
+ *      n_ground.  Zeroed on the stream before the launch; one relaxed atomicAdd per workgroup and non-zero counter, counted whether
+ *      or not the per-cell outputs are asked for.
+ *   8. cls_out is required; step, relief and support may be NULL and are then not written.  cls_out MUST NOT be cls (and no output
+ *      may overlap cls or top): neighbouring cells read cls while this one is written.
+ *   9. SVO_ERR_INVALID with the argument named, nothing launched and the context usable, for: a null ctx, cls, top, params, out or
+ *      cls_out; cls_out == cls; na or nb outside 1..8192 or na*nb > 2^24; ground_mask 0; a cell_size that is not finite and > 0; a
+ *      max_step or max_relief that is negative or a NaN; a footprint_radius that is not finite and >= 0, or with rc * rc >= 226;
+ *      min_support_256 outside 0..256; a top, step or relief that is not 4-byte aligned, a support not 2-byte, counts not 8-byte
+ *      aligned.
+ * Both cells of a step are STEP: the entry marks cells, not edges, and the route blocks both.
+ * How to use it: put cls_out where cls went, and SVO_GRID_SURFACE_SOURCES into the clearance's source_mask.  The frontiers' free
+ * mask stays LEVEL (a STEP cell is no frontier) and the view's opaque mask stays OBSTACLE (a kerb does not block sight).
+ * The defaults are NOT tuned on real data: the grid's na and nb, cell_size = cell_voxels * (double)voxel_size, ground_mask =
+ * 1 << SVO_VOXEL_GRID_LEVEL, max_step = obstacle_step, footprint_radius = 1.5 * cell_size (r2 = 2), max_relief = 2 * obstacle_step,
+ * min_support_256 = 0.
+ * The pipeline never calls it by itself; call it between the grid and the clearance. */
+#define SVO_GRID_SURFACE_STEP 3
+#define SVO_GRID_SURFACE_ROUGH 4
+#define SVO_GRID_SURFACE_UNSUPPORTED 5
+/* OBSTACLE, STEP, ROUGH and UNSUPPORTED: the clearance's source_mask over cls_out */
+#define SVO_GRID_SURFACE_SOURCES ((1u << 2) | (1u << 3) | (1u << 4) | (1u << 5))
+typedef struct svo_grid_surface_params {
+  int na, nb;               /* each 1..8192, na*nb <= 2^24 */
+  uint32_t ground_mask;     /* != 0: bit c set makes class c (0..31) ground */
+  double cell_size;         /* finite, > 0: a cell's edge in map units */
+  double max_step;          /* >= 0, not NaN; +infinity: no STEP */
+  double footprint_radius;  /* finite, >= 0, in map units; (footprint_radius / cell_size)^2 < 226 */
+  double max_relief;        /* >= 0, not NaN; +infinity: no ROUGH */
+  int min_support_256;      /* 0..256: the share of the footprint that must be ground, in 256ths; 0: no UNSUPPORTED among GROUND cells */
+} svo_grid_surface_params;
+typedef struct svo_grid_surface_out { /* na*nb elements each; every pointer but cls_out may be NULL */
+  uint8_t* cls_out;         /* must not be cls */
+  float* step;
+  float* relief;
+  uint16_t* support;
+} svo_grid_surface_out;
+/* The defaults above for a grid of svo_voxel_map_grid* over a map of this voxel size.  Pure; SVO_ERR_INVALID for a null pointer, a
+ * voxel_size that is not finite and > 0, or a grid whose na, nb, cell_voxels or obstacle_step svo_voxel_map_grid_dev would refuse. */
+int svo_grid_surface_default_params(const svo_voxel_grid_params* grid, float voxel_size, svo_grid_surface_params* out);
+/* D(r2) of rule 2: 1, 5, 9, 13, 25, 81, 709 for r2 = 0, 1, 2, 4, 8, 25, 225; 0 for r2 > 225, which no accepted call has.  Pure. */
+uint32_t svo_grid_surface_footprint_cells(uint32_t r2);
+/* DEVICE pointers, asynchronous on svo_stream(ctx).  The counts' memset and the launch are one "grid_surface" profile bracket. */
+int svo_grid_surface_dev(svo_ctx* ctx, const uint8_t* cls, const float* top, const svo_grid_surface_params* params,
+                         const svo_grid_surface_out* out, uint64_t* counts);
+/* HOST cls, top and outputs, synchronous: the device copies are allocated and freed by the call.  out: host pointers (no alignment
+ * asked), cls_out required; counts: 6 u64 on the host or NULL. */
+int svo_grid_surface(svo_ctx* ctx, const uint8_t* cls, const float* top, const svo_grid_surface_params* params,
+                     const svo_grid_surface_out* out, uint64_t* counts);
 
 /* Ground plan clearance: per cell of a u8 class grid the exact squared distance, in cells, to the nearest SOURCE cell, which cell
  * that is, the distance in map units and a robot-radius inflation: what a planner asks a ground plan first.  It works on any

@@ -329,6 +329,40 @@ def _clearance_params(params, overrides):
     return _params(lambda: GridClearanceParams(0, 0, 1 << VOXEL_GRID_OBSTACLE, 64, 0.0, 0.0), params, **overrides)
 
 
+class GridSurfaceParams(C.Structure):
+    """svo_grid_surface_params: na x nb cells (each 1..8192, na*nb <= 2^24), the classes that are ground as a bit mask (!= 0), a cell's
+    edge in map units, the largest step between edge neighbours (+inf: no rule), the footprint's radius in map units
+    ((footprint_radius / cell_size)^2 < 226), the largest relief under it (+inf: no rule) and the least share of it that must be
+    ground, in 256ths (0..256, 0: no rule)."""
+    _fields_ = [("na", C.c_int), ("nb", C.c_int), ("ground_mask", C.c_uint32), ("cell_size", C.c_double), ("max_step", C.c_double),
+                ("footprint_radius", C.c_double), ("max_relief", C.c_double), ("min_support_256", C.c_int)]
+
+
+class GridSurfaceOut(C.Structure):
+    """svo_grid_surface_out: na*nb elements each; every pointer but cls_out may be None; cls_out must not be cls."""
+    _fields_ = [("cls_out", C.c_void_p), ("step", C.c_void_p), ("relief", C.c_void_p), ("support", C.c_void_p)]
+
+
+GRID_SURFACE_STEP, GRID_SURFACE_ROUGH, GRID_SURFACE_UNSUPPORTED = 3, 4, 5
+GRID_SURFACE_SOURCES = 1 << 2 | 1 << 3 | 1 << 4 | 1 << 5  # SVO_GRID_SURFACE_SOURCES: the clearance's source_mask over cls_out
+GRID_SURFACE_COUNTS = ("n_ground", "n_step", "n_rough", "n_unsupported", "n_nonfinite", "n_kept")
+
+
+def grid_surface_default_params(grid, voxel_size):
+    """svo_grid_surface_default_params for a VoxelGridParams and its map's voxel size: the grid's na x nb, cell_size = cell_voxels *
+    voxel_size, LEVEL cells as the ground, max_step = obstacle_step, a footprint of 1.5 cells, max_relief = 2 * obstacle_step,
+    min_support_256 0 (not tuned on real data)."""
+    p = GridSurfaceParams()
+    if lib().svo_grid_surface_default_params(C.byref(grid), C.c_float(voxel_size), C.byref(p)) != 0:
+        raise SvoError("svo_grid_surface_default_params: voxel_size must be finite and > 0, the grid's na, nb, cell_voxels and obstacle_step in range")
+    return p
+
+
+def grid_surface_footprint_cells(r2):
+    """svo_grid_surface_footprint_cells: the number of offsets (da, db) with da^2 + db^2 <= r2 (no GPU involved); 0 for r2 > 225."""
+    return int(lib().svo_grid_surface_footprint_cells(int(r2)))
+
+
 class GridRouteParams(C.Structure):
     """svo_grid_route_params: na x nb cells (each 1..8192, na*nb <= 2^24), the penalty's squared radius in cells and its weight
     (near_weight * near_r2 <= 2^20), the cap on a cell's cost (1..0x7F000000), the rounds one call enqueues (1..4096), the cells
@@ -648,6 +682,7 @@ SYMBOLS = [
     "svo_voxel_map_render", "svo_voxel_render_set_mode",
     "svo_voxel_grid_default_params", "svo_voxel_grid_workspace_bytes", "svo_voxel_grid_cell_of", "svo_voxel_map_grid_dev", "svo_voxel_map_grid",
     "svo_voxel_grid_set_mode",
+    "svo_grid_surface_default_params", "svo_grid_surface_footprint_cells", "svo_grid_surface_dev", "svo_grid_surface",
     "svo_grid_clearance_default_params", "svo_grid_clearance_workspace_bytes", "svo_grid_clearance_dev", "svo_grid_clearance",
     "svo_grid_route_default_params", "svo_grid_route_workspace_bytes", "svo_grid_route_dev", "svo_grid_route",
     "svo_grid_frontier_default_params", "svo_grid_frontier_workspace_bytes", "svo_grid_frontiers_dev", "svo_grid_frontiers",
@@ -774,6 +809,14 @@ def lib():
         L.svo_voxel_map_grid.argtypes = [vp, vp, vp, vp]
         L.svo_voxel_grid_set_mode.argtypes = [vp, ci]
         for f in ("svo_voxel_grid_default_params", "svo_voxel_grid_cell_of", "svo_voxel_map_grid_dev", "svo_voxel_map_grid", "svo_voxel_grid_set_mode"):
+            getattr(L, f).restype = ci
+        # the ground plan surface
+        L.svo_grid_surface_default_params.argtypes = [vp, C.c_float, vp]
+        L.svo_grid_surface_footprint_cells.argtypes = [C.c_uint32]
+        L.svo_grid_surface_footprint_cells.restype = C.c_uint32
+        L.svo_grid_surface_dev.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.svo_grid_surface.argtypes = [vp, vp, vp, vp, vp, vp]
+        for f in ("svo_grid_surface_default_params", "svo_grid_surface_dev", "svo_grid_surface"):
             getattr(L, f).restype = ci
         # the ground plan clearance
         L.svo_grid_clearance_default_params.argtypes = [vp, C.c_float, vp]
@@ -1106,6 +1149,37 @@ class Context:
         self._chk(self.L.svo_stereo_sgm_batch_dev(self.h, left_ptr, right_ptr, batch, width, height, row_stride, image_stride, ndisp, block,
                                                   _ref(params), workspace_ptr, workspace_bytes, disp16_ptr, cost16_ptr),
                   "svo_stereo_sgm_batch_dev")
+
+    # ---- ground plan surface
+    def grid_surface(self, cls_ptr, top_ptr, params, cls_out_ptr=None, step_ptr=None, relief_ptr=None, support_ptr=None, counts_ptr=None,
+                     **overrides):
+        """svo_grid_surface_dev: per cell of the na x nb grid behind cls_ptr (uint8) and top_ptr (float32, the grid's top) the largest
+        height step to an edge neighbour, the relief and the support under the footprint, and the refined class grid (STEP 3, ROUGH 4,
+        UNSUPPORTED 5).  params (a GridSurfaceParams) and / or its fields as keywords.  All pointers are the caller's device memory:
+        cls_out_ptr na * nb uint8 (required, not cls_ptr), step_ptr and relief_ptr float32, support_ptr uint16 or None each,
+        counts_ptr 6 uint64 GRID_SURFACE_COUNTS or None.  Asynchronous on the context's stream; returns {"cls_out", "step", "relief",
+        "support", "counts", "na", "nb"}: the pointers the outputs are behind once the stream reaches this point."""
+        prm = _params(GridSurfaceParams, params, **overrides)
+        out = GridSurfaceOut(cls_out_ptr, step_ptr, relief_ptr, support_ptr)
+        self._chk(self.L.svo_grid_surface_dev(self.h, cls_ptr, top_ptr, C.byref(prm), C.byref(out), counts_ptr), "svo_grid_surface_dev")
+        return {"cls_out": cls_out_ptr, "step": step_ptr, "relief": relief_ptr, "support": support_ptr, "counts": counts_ptr,
+                "na": prm.na, "nb": prm.nb}
+
+    def grid_surface_host(self, cls, top, params, **overrides):
+        """svo_grid_surface: synchronous.  cls: an (na, nb) uint8 array, top: float32 of the same shape.  Returns (cls_out (na, nb)
+        uint8, step and relief float32 (-1 where the cell is not ground), support uint16, {GRID_SURFACE_COUNTS})."""
+        cls = np.ascontiguousarray(cls, np.uint8)
+        top = np.ascontiguousarray(top, np.float32)
+        if cls.ndim != 2 or top.shape != cls.shape:
+            raise ValueError("grid_surface_host: cls and top must be (na, nb) arrays of one shape")
+        prm = _params(GridSurfaceParams, params, **overrides)
+        if (prm.na, prm.nb) != cls.shape:
+            raise ValueError(f"grid_surface_host: cls is {cls.shape}, the parameters say {(prm.na, prm.nb)}")
+        arrays = [np.empty(cls.shape, t) for t in (np.uint8, np.float32, np.float32, np.uint16)]
+        out = GridSurfaceOut(*(a.ctypes.data for a in arrays))
+        c = np.zeros(6, np.uint64)
+        self._chk(self.L.svo_grid_surface(self.h, _p(cls), _p(top), C.byref(prm), C.byref(out), _p(c)), "svo_grid_surface")
+        return (*arrays, dict(zip(GRID_SURFACE_COUNTS, (int(v) for v in c))))
 
     # ---- ground plan clearance
     def grid_clearance(self, cls_ptr, params=None, workspace_ptr=None, dist2_ptr=None, nearest_ptr=None, clearance_ptr=None, blocked_ptr=None,

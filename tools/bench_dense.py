@@ -71,6 +71,13 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      from the restatement's counter (the synthetic cases: over the first 8 views), the time hbm_copy needs for the windows once per
      used view, the records and seen and, as context, the device-to-host copies of the inputs plus the restatement's numpy route on
      the host (256 x 256 only): the detour the entry replaces.
+ 16. surface: one svo_grid_surface_dev ("grid_surface" bracket: the counts' memset and the launch, mean of 5; cls_out, step, relief,
+     support and the counts) of section 11's grid of each filled map at the defaults (r2 = 2), and of seeded 2048 x 2048 and
+     8192 x 2048 grids at r2 = 0, 2, 25 and 225 (max_step 0.3, max_relief 0.6, min_support_256 200).  Per case the time, the counts,
+     the time hbm_copy needs for 5 bytes read and 11 written per cell, the time per cell and footprint cell and, as context, the
+     device-to-host copies of cls and top plus the restatement's numpy route on the host (the ground plans, and 2048 x 2048 up to
+     r2 = 25): the detour the entry replaces.  --surface-only runs just the seeded grids (a library built with another tile shape,
+     -DSVO_EXP_SURFACE_TILE_A / _B, is measured with it).
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -238,6 +245,7 @@ def standalone(S, torch, batch, warmup, reps):
                                  for pu, po in ((0.05, 0.05), (0.3, 0.1), (0.6, 0.2))]
     out["frontier_synthetic"].append(frontier_case(S, torch, ctx, *frontier_serpentine(torch, 2048), warmup, copy, densities="serpentine"))
     out["view_synthetic"] = view_synthetic(S, torch, ctx, warmup, copy)
+    out["surface_synthetic"] = surface_synthetic(S, torch, ctx, warmup, copy)
     ctx.close()
     return out
 
@@ -309,6 +317,7 @@ def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy):
             out[-1].update(clearance_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # of the same grid, before the carve too
             out[-1].update(route_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # over that grid's clearance
             out[-1].update(frontier_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # of that grid, off that clearance
+            out[-1].update(surface_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # of that grid's cls and top
             out[-1].update(render_view(S, torch, ctx, cam, vm, np.asarray(m12[batch - 1]), warmup, copy))
             out[-1].update(carve_and_copy(S, torch, ctx, cam, dm, vm, np.asarray(m12[batch - 1]), warmup, copy))
             vm.close()
@@ -792,6 +801,119 @@ def view_synthetic(S, torch, ctx, warmup, copy):
     return out
 
 
+def surface_case(S, torch, ctx, cls, top, prm, warmup, copy, host_detour=False, **tags):
+    """Section 16 for one (na, nb) device class grid (uint8) and its tops (float32) under a GridSurfaceParams: all four outputs and the
+    counts."""
+    import grid_surface_ref as G
+    api = S.api
+    na, nb = cls.shape
+    n = na * nb
+    cls_out = torch.empty(n, dtype=torch.uint8, device="cuda")
+    step, relief = (torch.empty(n, dtype=torch.float32, device="cuda") for _ in range(2))
+    support = torch.empty(n, dtype=torch.int16, device="cuda")
+    cnt = torch.zeros(6, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+
+    def call():
+        ctx.grid_surface(cls.data_ptr(), top.data_ptr(), prm, cls_out_ptr=cls_out.data_ptr(), step_ptr=step.data_ptr(), relief_ptr=relief.data_ptr(),
+                         support_ptr=support.data_ptr(), counts_ptr=cnt.data_ptr())
+
+    for _ in range(warmup):
+        call()
+    ctx.profile_select("grid_surface")
+    for _ in range(5):
+        call()
+    ms, k = ctx.profile_read()
+    ctx.profile_select("")
+    ms /= k
+    counts = [int(v) for v in cnt.cpu()]
+    rp = G.Params(*(getattr(prm, f) for f, _ in prm._fields_))
+    r2 = G.r2_of(rp)
+    bound = 1e3 * (5 + 11) * n / copy  # cls and top read once; cls_out, step, relief and support written
+    out = {"cells": [na, nb], "r2": r2, "footprint_cells": api.grid_surface_footprint_cells(r2), "ms": ms, "counts": counts, "bound_ms": bound,
+           "share_of_bound": bound / ms, "ps_per_cell_and_footprint_cell": 1e9 * ms / n / api.grid_surface_footprint_cells(r2), **tags}
+    if host_detour:
+        t0 = time.perf_counter()
+        h_cls, h_top = cls.cpu().numpy(), top.cpu().numpy()
+        out["d2h_copies_ms"] = 1e3 * (time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        want = G.surface_np(h_cls, h_top, rp)
+        out["host_numpy_ms"] = 1e3 * (time.perf_counter() - t0)
+        assert list(want.counts) == counts, (want.counts, counts)
+        assert np.array_equal(want.cls_out.ravel(), cls_out.cpu().numpy())
+        out["device_to_detour"] = ms / (out["d2h_copies_ms"] + out["host_numpy_ms"])
+    return out
+
+
+def surface_view(S, torch, ctx, vm, c2w, warmup, copy):
+    """Section 16 for one filled map: the surface of section 11's grid at the defaults."""
+    api = S.api
+    gp = api.voxel_grid_default_params(vm.params.voxel_size)
+    x, z = float(c2w.reshape(3, 4)[0, 3]), float(c2w.reshape(3, 4)[2, 3])
+    gp.origin_a, gp.origin_b = gp.origin_a + z, gp.origin_b + x
+    na, nb = gp.na, gp.nb
+    ws = torch.empty(4 * na * nb, dtype=torch.int64, device="cuda")
+    cls = torch.empty(na * nb, dtype=torch.uint8, device="cuda")
+    top = torch.empty(na * nb, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    vm.grid(gp, workspace_ptr=ws.data_ptr(), cls_ptr=cls.data_ptr(), top_ptr=top.data_ptr())
+    ctx.sync()
+    prm = api.grid_surface_default_params(gp, vm.params.voxel_size)
+    return {"surface": surface_case(S, torch, ctx, cls.reshape(na, nb), top.reshape(na, nb), prm, warmup, copy, host_detour=True)}
+
+
+def surface_random(torch, na, nb, seed=16):
+    """A seeded class grid and its tops on the device: three low-frequency waves and two cliffs (tests/grid_surface_ref.py's field, made
+    here because that one is numpy's), 6 % UNKNOWN (top -inf), 6 % OBSTACLE, 2 % of a class >= 32, 2 % LEVEL with a NaN top."""
+    g = torch.Generator(device="cuda")
+    g.manual_seed(seed)
+    rnd = np.random.default_rng(seed)
+    ia = torch.arange(na, dtype=torch.float32, device="cuda")[:, None]
+    ib = torch.arange(nb, dtype=torch.float32, device="cuda")[None, :]
+    top = torch.zeros((na, nb), dtype=torch.float32, device="cuda")
+    for _ in range(3):
+        fa, fb, ph = rnd.uniform(-0.12, 0.12), rnd.uniform(-0.12, 0.12), rnd.uniform(0, 2 * np.pi)
+        top += 0.25 * torch.sin(fa * ia + fb * ib + ph)
+    for height in (0.45, 1.0):
+        ca, cb, th = rnd.uniform(0, na), rnd.uniform(0, nb), rnd.uniform(0, np.pi)
+        top += height * (((ia - ca) * np.cos(th) + (ib - cb) * np.sin(th)) > 0)
+    u = torch.rand((na, nb), generator=g, device="cuda")
+    cls = torch.ones((na, nb), dtype=torch.uint8, device="cuda")
+    cls[u < 0.06] = 0
+    top[u < 0.06] = float("-inf")
+    cls[(u >= 0.06) & (u < 0.12)] = 2
+    cls[(u >= 0.12) & (u < 0.14)] = 77
+    top[(u >= 0.14) & (u < 0.16)] = float("nan")
+    torch.cuda.synchronize()
+    return cls.contiguous(), top.contiguous()
+
+
+def surface_synthetic(S, torch, ctx, warmup, copy):
+    """Section 16's footprints: seeded 2048 x 2048 and 8192 x 2048 grids at r2 = 0, 2, 25 and 225; max_step 0.3, max_relief 0.6,
+    min_support_256 200.  The host detour is taken on the smaller grid up to r2 = 25 (the restatement makes one pass per footprint
+    cell: 709 passes over 4 or 16 million cells were not waited for)."""
+    import grid_surface_ref as G
+    out = []
+    for na, nb in ((2048, 2048), (8192, 2048)):
+        cls, top = surface_random(torch, na, nb)
+        for r2 in (0, 2, 25, 225):
+            prm = S.api.GridSurfaceParams(na, nb, 1 << 1, 0.5, 0.3, G.radius_for(r2), 0.6, 200)
+            out.append(surface_case(S, torch, ctx, cls, top, prm, warmup, copy, host_detour=na == 2048 and r2 <= 25))
+        del cls, top
+    return out
+
+
+def surface_line(k):
+    """Section 16's line of the text report for one surface_case."""
+    line = (f"r2 {k['r2']} (D = {k['footprint_cells']}; the counts' memset + one launch, all four outputs, mean of 5): {1e3 * k['ms']:.1f} us, counts {k['counts']} "
+            f"(ground, step, rough, unsupported, nonfinite, kept); 5 B read + 11 B written per cell at hbm_copy {1e3 * k['bound_ms']:.2f} us -> "
+            f"{100 * k['share_of_bound']:.1f} % of that bound; {k['ps_per_cell_and_footprint_cell']:.2f} ps per cell and footprint cell")
+    if "host_numpy_ms" in k:
+        line += (f"; device-to-host copies of cls and top {1e3 * k['d2h_copies_ms']:.0f} us and the restatement's numpy route on the host {k['host_numpy_ms']:.0f} ms: "
+                 f"device / detour {k['device_to_detour']:.6f}")
+    return line + "\n"
+
+
 def render_view(S, torch, ctx, cam, vm, c2w, warmup, copy):
     """Section 9 for one filled map: what it shows a camera at the last cloud's pose."""
     w2c = np.linalg.inv(np.vstack([c2w.reshape(3, 4), [0, 0, 0, 1]]))[:3].reshape(12)
@@ -1051,12 +1173,24 @@ def main():
     ap.add_argument("--cloud-step", type=int, default=4)
     ap.add_argument("--skip-groups", action="store_true")
     ap.add_argument("--ledger-only", action="store_true", help="of the 96-lane loads only clouds alone and clouds with the ledger loop")
+    ap.add_argument("--surface-only", action="store_true", help="section 16's seeded grids alone")
     ap.add_argument("--out", help="write the text report here as well")
     a = ap.parse_args()
     import torch
     import stereo_vo_amd as S
     if not torch.cuda.is_available():
         sys.exit("bench_dense: needs the GPU (nothing is measured without it)")
+    if a.surface_only:
+        ctx = S.Context(W, H, max_batch=1, max_corners=64, max_candidates=1 << 12, max_features=64)
+        copy = ctx.measure_peak("hbm_copy")
+        res = {"hbm_copy_bytes_per_s": copy, "surface_synthetic": surface_synthetic(S, torch, ctx, 3, copy)}
+        ctx.close()
+        print(json.dumps(res))
+        if a.out:
+            with open(a.out, "w") as f:
+                for k in res["surface_synthetic"]:
+                    f.write(f"surface of a synthetic {k['cells'][0]} x {k['cells'][1]} grid: " + surface_line(k))
+        return
     res = {"standalone": standalone(S, torch, a.batch, 3, a.reps)}
     print("bench_dense: standalone sections done", file=sys.stderr, flush=True)
     if not a.skip_groups:
@@ -1148,6 +1282,7 @@ def main():
                             f"cls, blocked and cost {1e3 * k['d2h_copies_ms']:.0f} us and the restatement's numpy route on the host {k['host_numpy_ms']:.0f} ms\n"
                             for k in [c['frontier']]) +
                         "  view over those frontiers' goal_cells and that route's cost: " + view_line(c['view']) +
+                        "  surface of that grid's cls and top at the defaults: " + surface_line(c['surface']) +
                         f"  removal of the last inserted cloud ({c['remove_move_points']} points, mean of 5): {1e3 * c['remove_ms']:.1f} us, counts {c['remove_counts']} "
                         f"(removed, rejected, missing, short); move to a pose 1 cm and 0.1 degrees away (removal + insert): {1e3 * c['move_ms']:.1f} us, counts "
                         f"{c['move_counts']}; the same cloud inserted once more, same run: {1e3 * c['insert_ms']:.1f} us -> removal / insert "
@@ -1172,6 +1307,8 @@ def main():
                         f"per cell at hbm_copy {1e3 * k['bound_ms']:.2f} us; device-to-host copies of the inputs {1e3 * k['d2h_copies_ms']:.0f} us\n")
             for k in s["view_synthetic"]:
                 f.write(f"view over a synthetic {k['cells'][0]} x {k['cells'][1]} grid, (unknown, obstacle) densities {k['densities']}: " + view_line(k))
+            for k in s["surface_synthetic"]:
+                f.write(f"surface of a synthetic {k['cells'][0]} x {k['cells'][1]} grid: " + surface_line(k))
             if g and "ratio_ledger_to_clouds" in g:
                 f.write(f"{g['lanes']} lanes in {g['groups']} groups, {g['frames_per_step_per_lane']}-frame steps, {g['rounds']} alternating rounds of {g['steps']} steps, clouds at "
                         f"step {g['cloud_step']}, every lane's ledger holding {g['ledger_held_per_lane']} keyframes and moving all of them (1 cm, 0.1 degrees) after each call: "
