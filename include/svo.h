@@ -105,7 +105,7 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * and the counts and both launches), "grid_clearance" (one svo_grid_clearance_dev: the counts' memset and both launches),
  * "grid_route" (one svo_grid_route_dev: its memsets and every launch), "grid_frontier" (one svo_grid_frontiers_dev: the counts'
  * memset and every launch), "grid_view" (one svo_grid_view_dev: its two memsets and both launches), "grid_surface" (one svo_grid_surface_dev: the
- * counts' memset and the launch); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
+ * counts' memset and the launch), "grid_waypoints" (one svo_grid_waypoints_dev: the counts' memset and the launch); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
 /* Measurement aid: the card's own ceilings for the roofline objects (SURVEY 8d asks for a measured FP64 figure).
@@ -1099,6 +1099,84 @@ int svo_grid_view(svo_ctx* ctx, const uint8_t* cls, const uint32_t* views, int n
  * window staged in LDS; 0 makes every step of a line read cls from global memory.  It cannot change a bit of an output.  DESIGN 7n
  * gives the figures. */
 int svo_grid_view_set_mode(svo_ctx* ctx, int staged);
+
+/* Ground plan waypoints: from a route's paths, one entry per cell of a 5-7 chamfer staircase, the few cells between which a vehicle
+ * may drive in straight lines: what a planner hands to a controller.  Integers apart from one optional length, no dependence on thread
+ * order, tested with ==.  cell = ia*nb + ib, as in the grid, the clearance, the route, the frontiers and the view.
+ * INPUTS (device memory for the _dev entry): blocked, na*nb u8, required: passable iff 0 (the clearance's blocked as it is); dist2,
+ * na*nb u32 or NULL (the clearance's dist2); path, n_paths x path_stride u32 (the route's path; path_stride is the route's max_path);
+ * path_len, n_paths u32; path_status, n_paths u8 or NULL (NULL: every path counts as OK); n_paths 1..4096.
+ *   1. A cell is SOLID iff blocked[v] != 0, or dist2 is given and dist2[v] < min_dist2.  0xFFFFFFFF is far; min_dist2 = 0 switches
+ *      the second clause off.
+ *   2. m = min(path_len[p], path_stride) cells of path p are available.  Path p is USED iff path_status is NULL or its status is
+ *      SVO_GRID_ROUTE_OK or _TRUNCATED, and m >= 1, and every one of its first m entries is < na*nb.  Otherwise it is SKIPPED:
+ *      way_len = 0, length = 0.0, its rows of way and way_index are not touched, and its status is SVO_GRID_WAY_BAD_CELL where the
+ *      reason is an entry outside the grid (a status the route would refuse comes first, then m = 0, then the entries) and
+ *      SVO_GRID_WAY_SKIPPED otherwise.  Adjacency of consecutive entries is not checked: any list of in-grid cells is accepted.
+ *   3. The line from V = (va, vb) to T = (ta, tb): da = ta - va, db = tb - vb, n = max(|da|, |db|), and for i = 0..n
+ *        L_i = (va + sgn(da) * floor((2*i*|da| + n) / (2n)), vb + sgn(db) * floor((2*i*|db| + n) / (2n))).
+ *      L_0 = V, L_n = T; the major coordinate moves one cell per step; a tie of the minor coordinate rounds away from V.  The rule
+ *      commutes with the grid's eight symmetries; it is not symmetric in V and T.  Every L_i lies in the bounding box of V and T.
+ *      (The view's rule 3, word for word.)  V is the waypoint already chosen, T the candidate.
+ *   4. CLEAR(V, T) holds iff n <= max_look, neither V nor T is SOLID, no L_i with 1 <= i <= n-1 is SOLID, and for every step L_(i-1)
+ *      -> L_i, 1 <= i <= n, that changes both coordinates, NEITHER of the two cells it passes between, (a_i, b_(i-1)) and (a_(i-1),
+ *      b_i), is SOLID.  The last clause is the route's rule 2; the view's rule 4 stops only at a corner closed on both sides.  For
+ *      n = 1 CLEAR is exactly the route's allowed move; for n = 0 it holds iff V is not SOLID.
+ *   5. The waypoints are path indices k_0 < k_1 < ... < k_(w-1) with k_0 = 0.  While k_t < m-1: k_(t+1) is the LARGEST j with
+ *      k_t + 1 < j <= min(k_t + max_look, m-1) and CLEAR(path[k_t], path[j]); if there is none, k_(t+1) = k_t + 1, and that step is
+ *      FORCED iff CLEAR(path[k_t], path[k_t + 1]) is false.  k_(w-1) = m-1, and m = 1 gives w = 1.  CLEAR is decided per candidate by
+ *      its own line: "the largest clear j" is a different function from "the last j before the first failure".  For a path the route
+ *      made from the same blocked, with min_dist2 = 0, no step is FORCED (rule 4 at n = 1).
+ *   6. OUTPUTS (svo_grid_waypoint_out).  way, n_paths x max_way u32: way[p][t] = path[p][k_t] for t < max_way; later entries are not
+ *      touched.  way_index, the same shape: k_t.  way_len, n_paths u32: w, the full number.  way_status, n_paths u8: for a used path
+ *      a sum of SVO_GRID_WAY_PATH_TRUNCATED = 1 (path_len > path_stride, so the last waypoint is not the goal) and SVO_GRID_WAY_FULL
+ *      = 2 (w > max_way), so 0 is OK; SVO_GRID_WAY_SKIPPED = 4 and SVO_GRID_WAY_BAD_CELL = 5 for a skipped one.  length, n_paths f64:
+ *      s = 0.0; for t = 1..w-1 in order s = s + sqrt((double)(da^2 + db^2)) between k_(t-1) and k_t, a correctly rounded f64 square
+ *      root as in the clearance's rule 4; length = s * cell_size, one product.  All w segments count, those past max_way too.
+ *   7. counts: 8 u64 on the device, or NULL: {n_used, n_skipped, n_cells_in, n_waypoints, n_forced, n_full, max_d2, 0}.  Zeroed on
+ *      the stream; relaxed adds, a relaxed max for max_d2.  n_skipped includes the paths refused for a bad cell; n_cells_in is the sum
+ *      of m over used paths; n_waypoints the sum of w; n_forced the number of FORCED steps; n_full the number of paths with _FULL;
+ *      max_d2 the largest da^2 + db^2 of any segment.
+ *   8. SVO_ERR_INVALID with the argument named, nothing launched and the context still usable, looked for in this order: a null
+ *      ctx; a null blocked, params, path, path_len, out; na, nb outside 1..8192, na*nb > 2^24; path_stride outside 1..2^20; max_look
+ *      outside 1..255; min_dist2 > 2^26; max_way outside 1..2^20; a cell_size that is not finite and > 0; n_paths outside 1..4096;
+ *      one of way and way_len NULL and the other not, every output NULL; dist2, path, path_len, way, way_index, way_len off 4 bytes;
+ *      length, counts off 8 bytes.  The inputs are only read; they must not overlap an output.
+ *   9. No workspace: a path's workgroup keeps what it needs in registers and LDS.
+ * The defaults are NOT tuned on real data: the route's na and nb, path_stride = the route's max_path, max_look 64, min_dist2 0, max_way
+ * 256, the clearance's cell_size.
+ * The pipeline never calls the entry by itself; call it after the route whose paths it reads. */
+#define SVO_GRID_WAY_MAX_PATHS 4096
+enum { SVO_GRID_WAY_OK = 0, SVO_GRID_WAY_PATH_TRUNCATED = 1, SVO_GRID_WAY_FULL = 2, SVO_GRID_WAY_SKIPPED = 4, SVO_GRID_WAY_BAD_CELL = 5 };
+typedef struct svo_grid_waypoint_params {
+  int na, nb;          /* each 1..8192, na*nb <= 2^24 */
+  int path_stride;     /* 1..2^20: entries between two rows of path; the route's max_path */
+  int max_look;        /* 1..255: the longest segment in cells (Chebyshev) and in path entries */
+  uint32_t min_dist2;  /* 0..2^26: with dist2, cells nearer than this to an obstacle are SOLID */
+  int max_way;         /* 1..2^20: waypoints written per path */
+  double cell_size;    /* finite, > 0: a cell's edge in map units, for length */
+} svo_grid_waypoint_params;
+typedef struct svo_grid_waypoint_out { /* each may be NULL, but not all; way and way_len only together */
+  uint32_t* way;        /* n_paths * max_way */
+  uint32_t* way_index;  /* n_paths * max_way */
+  uint32_t* way_len;    /* n_paths */
+  uint8_t* way_status;  /* n_paths */
+  double* length;       /* n_paths */
+} svo_grid_waypoint_out;
+/* The defaults above for a route and the clearance it read.  Pure; SVO_ERR_INVALID for a null pointer, an na, nb or max_path the
+ * route refuses or a cell_size the clearance refuses. */
+int svo_grid_waypoints_default_params(const svo_grid_route_params* route, const svo_grid_clearance_params* clearance,
+                                      svo_grid_waypoint_params* out);
+/* DEVICE pointers, asynchronous on svo_stream(ctx): the counts' memset and one launch, one "grid_waypoints" profile bracket. */
+int svo_grid_waypoints_dev(svo_ctx* ctx, const uint8_t* blocked, const uint32_t* dist2, const uint32_t* path, const uint32_t* path_len,
+                           const uint8_t* path_status, int n_paths, const svo_grid_waypoint_params* params,
+                           const svo_grid_waypoint_out* out, uint64_t* counts);
+/* HOST arrays and outputs (no alignment asked), synchronous: one device allocation for the call, freed after the stream is drained
+ * whatever failed.  The caller's way and way_index are copied up first, so that what rules 2 and 6 leave untouched comes back as it
+ * was.  counts: 8 u64 on the host or NULL. */
+int svo_grid_waypoints(svo_ctx* ctx, const uint8_t* blocked, const uint32_t* dist2, const uint32_t* path, const uint32_t* path_len,
+                       const uint8_t* path_status, int n_paths, const svo_grid_waypoint_params* params,
+                       const svo_grid_waypoint_out* out, uint64_t* counts);
 
 /* ------------------------------------------------------------------- a8 --
  * ImageProcessor::triangulate_stereo's reprojection loop

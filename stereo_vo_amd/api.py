@@ -491,6 +491,35 @@ def _view_params(params, overrides):
     return _params(lambda: GridViewParams(0, 0, 1 << VOXEL_GRID_OBSTACLE, 1 << VOXEL_GRID_UNKNOWN, 64, 16, 1), params, **overrides)
 
 
+class GridWaypointParams(C.Structure):
+    """svo_grid_waypoint_params: na x nb cells (each 1..8192, na*nb <= 2^24), the entries between two rows of path (the route's
+    max_path, 1..2^20), the longest segment in cells and in path entries (1..255), the squared distance in cells below which a cell
+    with a dist2 is SOLID (0..2^26; 0: none), the waypoints written per path (1..2^20) and a cell's edge in map units (finite, > 0)."""
+    _fields_ = [("na", C.c_int), ("nb", C.c_int), ("path_stride", C.c_int), ("max_look", C.c_int), ("min_dist2", C.c_uint32),
+                ("max_way", C.c_int), ("cell_size", C.c_double)]
+
+
+class GridWaypointOut(C.Structure):
+    """svo_grid_waypoint_out: way and way_index n_paths * max_way uint32, way_len n_paths uint32, way_status n_paths uint8, length
+    n_paths float64; each may be None, but not all, and way and way_len only together."""
+    _fields_ = [("way", C.c_void_p), ("way_index", C.c_void_p), ("way_len", C.c_void_p), ("way_status", C.c_void_p), ("length", C.c_void_p)]
+
+
+GRID_WAY_NONE = 0xFFFFFFFF  # what grid_waypoints_host fills way and way_index with before the call
+GRID_WAY_MAX_PATHS = 4096  # SVO_GRID_WAY_MAX_PATHS
+GRID_WAY_OK, GRID_WAY_PATH_TRUNCATED, GRID_WAY_FULL, GRID_WAY_SKIPPED, GRID_WAY_BAD_CELL = 0, 1, 2, 4, 5  # SVO_GRID_WAY_*
+GRID_WAY_COUNTS = ("n_used", "n_skipped", "n_cells_in", "n_waypoints", "n_forced", "n_full", "max_d2")
+
+
+def grid_waypoints_default_params(route_params, clearance_params):
+    """svo_grid_waypoints_default_params for a GridRouteParams and the GridClearanceParams it read: the route's na x nb, path_stride
+    = its max_path, max_look 64, min_dist2 0, max_way 256, the clearance's cell_size (not tuned on real data)."""
+    p = GridWaypointParams()
+    if lib().svo_grid_waypoints_default_params(C.byref(route_params), C.byref(clearance_params), C.byref(p)) != 0:
+        raise SvoError("svo_grid_waypoints_default_params: the route's na, nb and max_path and the clearance's cell_size must be in range")
+    return p
+
+
 SPECKLE_TILE = (64, 16)  # SVO_SPECKLE_TILE_W, SVO_SPECKLE_TILE_H
 
 
@@ -688,6 +717,7 @@ SYMBOLS = [
     "svo_grid_frontier_default_params", "svo_grid_frontier_workspace_bytes", "svo_grid_frontiers_dev", "svo_grid_frontiers",
     "svo_grid_frontier_set_mode",
     "svo_grid_view_default_params", "svo_grid_view_workspace_bytes", "svo_grid_view_dev", "svo_grid_view", "svo_grid_view_set_mode",
+    "svo_grid_waypoints_default_params", "svo_grid_waypoints_dev", "svo_grid_waypoints",
     "svo_voxel_map_remove_dev", "svo_voxel_map_remove_pose7_dev", "svo_voxel_map_remove_sync", "svo_voxel_map_move_dev", "svo_voxel_map_move_pose7_dev",
     "svo_voxel_ledger_bytes", "svo_voxel_ledger_create", "svo_voxel_ledger_destroy", "svo_voxel_ledger_insert_pose7_dev",
     "svo_voxel_ledger_update_pose7", "svo_voxel_ledger_retire", "svo_voxel_ledger_remove", "svo_voxel_ledger_ids", "svo_voxel_ledger_get",
@@ -850,6 +880,11 @@ def lib():
         L.svo_grid_view_dev.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp]
         L.svo_grid_view.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp]
         L.svo_grid_view_set_mode.argtypes = [vp, ci]
+        L.svo_grid_waypoints_default_params.argtypes = [vp, vp, vp]
+        L.svo_grid_waypoints_dev.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]
+        L.svo_grid_waypoints.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]
+        for f in ("svo_grid_waypoints_default_params", "svo_grid_waypoints_dev", "svo_grid_waypoints"):
+            getattr(L, f).restype = ci
         for f in ("svo_grid_view_default_params", "svo_grid_view_dev", "svo_grid_view", "svo_grid_view_set_mode"):
             getattr(L, f).restype = ci
         # removal, move and the keyframe ledger
@@ -1369,6 +1404,56 @@ class Context:
         """svo_grid_view_set_mode (measurement aid): whether a view's lines are walked over bit planes of its window staged in LDS or
         over cls in global memory; no bit of a result depends on it.  None: the default."""
         self._chk(self.L.svo_grid_view_set_mode(self.h, int(GRID_VIEW_STAGED_DEFAULT if staged is None else bool(staged))), "svo_grid_view_set_mode")
+
+    # ---- ground plan waypoints
+    def grid_waypoints(self, blocked_ptr, path_ptr, path_len_ptr, n_paths, params, dist2_ptr=None, path_status_ptr=None, way_ptr=None,
+                       way_index_ptr=None, way_len_ptr=None, way_status_ptr=None, length_ptr=None, counts_ptr=None):
+        """svo_grid_waypoints_dev: per path of a route (path_ptr n_paths * path_stride uint32, path_len_ptr n_paths uint32,
+        path_status_ptr n_paths uint8 or None: grid_route's outputs as they are) the few cells between which a vehicle may drive in
+        straight lines over the na x nb uint8 grid behind blocked_ptr (passable iff 0; dist2_ptr na * nb uint32 or None).  params: a
+        GridWaypointParams.  All device pointers: way_ptr and way_index_ptr n_paths * max_way uint32, way_len_ptr n_paths uint32,
+        way_status_ptr n_paths uint8, length_ptr n_paths float64 (at least one; way and way_len together), counts_ptr 8 uint64
+        (GRID_WAY_COUNTS and a zero) or None.  Asynchronous on the context's stream.  Returns the pointers and "n_paths", "max_way"."""
+        out = GridWaypointOut(way_ptr, way_index_ptr, way_len_ptr, way_status_ptr, length_ptr)
+        self._chk(self.L.svo_grid_waypoints_dev(self.h, blocked_ptr, dist2_ptr, path_ptr, path_len_ptr, path_status_ptr, int(n_paths), C.byref(params),
+                                                C.byref(out), counts_ptr), "svo_grid_waypoints_dev")
+        return {"way": way_ptr, "way_index": way_index_ptr, "way_len": way_len_ptr, "way_status": way_status_ptr, "length": length_ptr,
+                "counts": counts_ptr, "n_paths": int(n_paths), "max_way": params.max_way}
+
+    def grid_waypoints_host(self, blocked, path, path_len, params, dist2=None, path_status=None):
+        """svo_grid_waypoints: synchronous.  blocked: an (na, nb) uint8 array; path: (n_paths, path_stride) uint32; path_len: (n_paths,)
+        uint32; dist2: (na, nb) uint32 or None; path_status: (n_paths,) uint8 or None.  Returns {"way" and "way_index" (n_paths,
+        max_way) uint32 with GRID_WAY_NONE where nothing was written, "way_len" (n_paths,) uint32, "way_status" (n_paths,) uint8,
+        "length" (n_paths,) float64, "counts" {GRID_WAY_COUNTS}}."""
+        blocked = np.ascontiguousarray(blocked, np.uint8)
+        if blocked.shape != (params.na, params.nb):
+            raise ValueError(f"grid_waypoints_host: blocked is {blocked.shape}, the parameters say {(params.na, params.nb)}")
+        path = np.ascontiguousarray(path, np.uint32)
+        path_len = np.ascontiguousarray(path_len, np.uint32).ravel()
+        n_paths = len(path_len)
+        if path.ndim != 2 or path.shape != (n_paths, params.path_stride):
+            raise ValueError(f"grid_waypoints_host: path is {path.shape}, path_len and the parameters say {(n_paths, params.path_stride)}")
+        if dist2 is not None:
+            dist2 = np.ascontiguousarray(dist2, np.uint32)
+            if dist2.shape != blocked.shape:
+                raise ValueError("grid_waypoints_host: dist2 must have the shape of blocked")
+        if path_status is not None:
+            path_status = np.ascontiguousarray(path_status, np.uint8).ravel()
+            if len(path_status) != n_paths:
+                raise ValueError("grid_waypoints_host: path_status must have one entry per path")
+        if not 1 <= n_paths <= GRID_WAY_MAX_PATHS:
+            raise SvoError("svo_grid_waypoints: grid_waypoints: n_paths outside 1..4096")
+        if not 1 <= params.max_way <= 1 << 20:
+            raise SvoError("svo_grid_waypoints: grid_waypoints: max_way outside 1..2^20")
+        way = np.full((n_paths, params.max_way), GRID_WAY_NONE, np.uint32)
+        index = np.full((n_paths, params.max_way), GRID_WAY_NONE, np.uint32)
+        wlen, status, length = np.empty(n_paths, np.uint32), np.empty(n_paths, np.uint8), np.empty(n_paths, np.float64)
+        out = GridWaypointOut(way.ctypes.data, index.ctypes.data, wlen.ctypes.data, status.ctypes.data, length.ctypes.data)
+        c = np.zeros(8, np.uint64)
+        self._chk(self.L.svo_grid_waypoints(self.h, _p(blocked), _p(dist2), _p(path), _p(path_len), _p(path_status), n_paths, C.byref(params),
+                                            C.byref(out), _p(c)), "svo_grid_waypoints")
+        return {"way": way, "way_index": index, "way_len": wlen, "way_status": status, "length": length,
+                "counts": dict(zip(GRID_WAY_COUNTS, (int(v) for v in c)))}
 
     # ---- a8
     def triangulate(self, xy, disp, pose16, focal, cx, cy, baseline):

@@ -78,6 +78,11 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      device-to-host copies of cls and top plus the restatement's numpy route on the host (the ground plans, and 2048 x 2048 up to
      r2 = 25): the detour the entry replaces.  --surface-only runs just the seeded grids (a library built with another tile shape,
      -DSVO_EXP_SURFACE_TILE_A / _B, is measured with it).
+ 17. waypoints: one svo_grid_waypoints_dev ("grid_waypoints" bracket: the counts' memset and the launch, mean of 5; all five outputs
+     and the counts) over the paths of a route to the centre cell: on section 12's clearance (inflation two cells) of section 11's
+     grid of each filled map from one start, the corner with the longest path, and on a seeded 2048 x 2048 grid (blocked density
+     0.1) from one start (a corner) and from 4,096 seeded starts; max_look 16, 64 and 255.  Per case the counts and, as context for one path up to max_look 64, the device-to-host copies of path, path_len and blocked plus the
+     restatement's Python walk on the host: the detour the entry replaces.  --waypoints-only runs just the seeded grid.
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -246,6 +251,7 @@ def standalone(S, torch, batch, warmup, reps):
     out["frontier_synthetic"].append(frontier_case(S, torch, ctx, *frontier_serpentine(torch, 2048), warmup, copy, densities="serpentine"))
     out["view_synthetic"] = view_synthetic(S, torch, ctx, warmup, copy)
     out["surface_synthetic"] = surface_synthetic(S, torch, ctx, warmup, copy)
+    out["waypoint_synthetic"] = waypoint_synthetic(S, torch, ctx, warmup)
     ctx.close()
     return out
 
@@ -318,6 +324,7 @@ def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy):
             out[-1].update(route_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # over that grid's clearance
             out[-1].update(frontier_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # of that grid, off that clearance
             out[-1].update(surface_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # of that grid's cls and top
+            out[-1].update(waypoint_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # of a route over that grid's clearance
             out[-1].update(render_view(S, torch, ctx, cam, vm, np.asarray(m12[batch - 1]), warmup, copy))
             out[-1].update(carve_and_copy(S, torch, ctx, cam, dm, vm, np.asarray(m12[batch - 1]), warmup, copy))
             vm.close()
@@ -914,6 +921,123 @@ def surface_line(k):
     return line + "\n"
 
 
+WAYPOINT_LOOKS = (16, 64, 255)
+
+
+def waypoint_case(S, torch, ctx, blocked, starts, warmup, one_path=False, host_detour=False, **tags):
+    """Section 17 for one (na, nb) uint8 device grid (passable iff 0): the route from `starts` to the centre cell, then the waypoints of
+    its paths at each max_look.  one_path: of the starts only the one with the longest complete path is used."""
+    import grid_waypoints_ref as G
+    api = S.api
+    na, nb = blocked.shape
+    n = na * nb
+    ns, max_path, max_way = len(starts), 4096, 256
+    goals = torch.tensor([(na // 2) * nb + nb // 2], dtype=torch.int32, device="cuda")
+    d_starts = torch.from_numpy(np.asarray(starts, np.uint32).view(np.int32)).cuda()
+    ws = torch.empty(api.grid_route_workspace_bytes(na, nb) // 8, dtype=torch.int64, device="cuda")
+    cost = torch.empty(n, dtype=torch.int32, device="cuda")
+    path = torch.empty(ns * max_path, dtype=torch.int32, device="cuda")
+    plen = torch.zeros(ns, dtype=torch.int32, device="cuda")
+    status = torch.zeros(ns, dtype=torch.uint8, device="cuda")
+    rcnt = torch.zeros(8, dtype=torch.int64, device="cuda")
+    rounds = 64
+    while True:  # a call that does not converge is repeated from the start with four times as many rounds
+        ctx.grid_route(blocked.data_ptr(), api.GridRouteParams(na, nb, 0, 0, api.GRID_ROUTE_MAX_COST, rounds, max_path, 0), goals.data_ptr(), 1,
+                       workspace_ptr=ws.data_ptr(), cost_ptr=cost.data_ptr(), starts_ptr=d_starts.data_ptr(), n_starts=ns, path_ptr=path.data_ptr(),
+                       path_len_ptr=plen.data_ptr(), path_status_ptr=status.data_ptr(), counts_ptr=rcnt.data_ptr())
+        ctx.sync()
+        if int(rcnt.cpu()[4]) == 1 or rounds == 4096:
+            break
+        rounds *= 4
+    lens, stat = plen.cpu().numpy().view(np.uint32), status.cpu().numpy()
+    row, n_paths = 0, ns
+    if one_path:
+        ok = np.flatnonzero(stat == 0)
+        if len(ok) == 0:
+            return {"cells": [na, nb], "no_path": True, "path_status": stat.tolist(), **tags}
+        row, n_paths = int(ok[np.argmax(lens[ok])]), 1
+    way, index = (torch.empty(n_paths * max_way, dtype=torch.int32, device="cuda") for _ in range(2))
+    wlen = torch.zeros(n_paths, dtype=torch.int32, device="cuda")
+    wstat = torch.zeros(n_paths, dtype=torch.uint8, device="cuda")
+    length = torch.zeros(n_paths, dtype=torch.float64, device="cuda")
+    cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    out = {"cells": [na, nb], "n_paths": n_paths, "path_cells": int(lens[row]) if one_path else int(lens.sum()), "route_rounds": rounds, "looks": [], **tags}
+    for look in WAYPOINT_LOOKS:
+        prm = api.GridWaypointParams(na, nb, max_path, look, 0, max_way, 0.5)
+
+        def call():
+            ctx.grid_waypoints(blocked.data_ptr(), path.data_ptr() + 4 * row * max_path, plen.data_ptr() + 4 * row, n_paths, prm,
+                               path_status_ptr=status.data_ptr() + row, way_ptr=way.data_ptr(), way_index_ptr=index.data_ptr(), way_len_ptr=wlen.data_ptr(),
+                               way_status_ptr=wstat.data_ptr(), length_ptr=length.data_ptr(), counts_ptr=cnt.data_ptr())
+
+        for _ in range(warmup):
+            call()
+        ctx.profile_select("grid_waypoints")
+        for _ in range(5):
+            call()
+        ms, calls = ctx.profile_read()
+        ctx.profile_select("")
+        k = {"max_look": look, "us": 1e3 * ms / calls}
+        k["counts"] = [int(v) for v in cnt.cpu()[:7]]
+        if host_detour and look <= 64:
+            t0 = time.perf_counter()
+            h_path = path.cpu().numpy().view(np.uint32).reshape(ns, max_path)[row:row + n_paths]
+            h_len, h_stat, h_b = lens[row:row + n_paths].copy(), status.cpu().numpy()[row:row + n_paths], blocked.cpu().numpy()
+            k["d2h_copies_ms"] = 1e3 * (time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            want = G.waypoints_py(h_b, None, h_path, h_len, h_stat, G.Params(na, nb, max_path, look, 0, max_way, 0.5))
+            k["host_python_ms"] = 1e3 * (time.perf_counter() - t0)
+            assert list(want.counts) == k["counts"], (want.counts, k["counts"])
+            assert np.array_equal(want.way_len, wlen.cpu().numpy().view(np.uint32)) and want.length.tobytes() == length.cpu().numpy().tobytes()
+        out["looks"].append(k)
+    return out
+
+
+def waypoint_view(S, torch, ctx, vm, c2w, warmup, copy):
+    """Section 17 for one filled map: the waypoints of the route over the clearance (inflation two cells) of section 11's grid."""
+    gp = S.api.voxel_grid_default_params(vm.params.voxel_size)
+    x, z = float(c2w.reshape(3, 4)[0, 3]), float(c2w.reshape(3, 4)[2, 3])
+    gp.origin_a, gp.origin_b = gp.origin_a + z, gp.origin_b + x
+    n = gp.na * gp.nb
+    ws = torch.empty(4 * n, dtype=torch.int64, device="cuda")
+    cls = torch.empty(n, dtype=torch.uint8, device="cuda")
+    offsets, d2 = (torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(2))
+    blk = torch.empty(n, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    vm.grid(gp, workspace_ptr=ws.data_ptr(), cls_ptr=cls.data_ptr())
+    cp = S.api.grid_clearance_default_params(gp, vm.params.voxel_size)
+    cp.inflate_radius = 2.0 * cp.cell_size
+    ctx.grid_clearance(cls.data_ptr(), cp, workspace_ptr=offsets.data_ptr(), dist2_ptr=d2.data_ptr(), blocked_ptr=blk.data_ptr())
+    ctx.sync()
+    corners = [0, gp.nb - 1, (gp.na - 1) * gp.nb, n - 1]
+    return {"waypoints": waypoint_case(S, torch, ctx, blk.reshape(gp.na, gp.nb), corners, warmup, one_path=True, host_detour=True)}
+
+
+def waypoint_synthetic(S, torch, ctx, warmup):
+    """Section 17's seeded grid: 2048 x 2048, blocked density 0.1, from one corner and from 4,096 seeded starts."""
+    na = nb = 2048
+    blocked = route_random(torch, na, nb, 0.1, seed=17)
+    starts = np.random.default_rng(17).integers(0, na * nb, 4096)
+    return [waypoint_case(S, torch, ctx, blocked, [0, nb - 1, (na - 1) * nb, na * nb - 1], warmup, one_path=True, host_detour=True, density=0.1),
+            waypoint_case(S, torch, ctx, blocked, starts, warmup, density=0.1)]
+
+
+def waypoint_line(k):
+    """Section 17's lines of the text report for one waypoint_case."""
+    if k.get("no_path"):
+        return f"no corner has a path to the centre cell (status {k['path_status']})\n"
+    line = f"{k['n_paths']} path(s) of {k['path_cells']} cells in all (the counts' memset + one launch, all five outputs, mean of 5):\n"
+    for q in k["looks"]:
+        line += (f"    max_look {q['max_look']}: {q['us']:.1f} us"
+                 f"; counts {q['counts']} (used, skipped, cells in, waypoints, forced, full, max_d2)")
+        if "host_python_ms" in q:
+            line += (f"; device-to-host copies of path, path_len, path_status and blocked {1e3 * q['d2h_copies_ms']:.0f} us and the restatement's Python walk "
+                     f"on the host {q['host_python_ms']:.0f} ms")
+        line += "\n"
+    return line
+
+
 def render_view(S, torch, ctx, cam, vm, c2w, warmup, copy):
     """Section 9 for one filled map: what it shows a camera at the last cloud's pose."""
     w2c = np.linalg.inv(np.vstack([c2w.reshape(3, 4), [0, 0, 0, 1]]))[:3].reshape(12)
@@ -1174,6 +1298,7 @@ def main():
     ap.add_argument("--skip-groups", action="store_true")
     ap.add_argument("--ledger-only", action="store_true", help="of the 96-lane loads only clouds alone and clouds with the ledger loop")
     ap.add_argument("--surface-only", action="store_true", help="section 16's seeded grids alone")
+    ap.add_argument("--waypoints-only", action="store_true", help="section 17's seeded grid alone")
     ap.add_argument("--out", help="write the text report here as well")
     a = ap.parse_args()
     import torch
@@ -1190,6 +1315,16 @@ def main():
             with open(a.out, "w") as f:
                 for k in res["surface_synthetic"]:
                     f.write(f"surface of a synthetic {k['cells'][0]} x {k['cells'][1]} grid: " + surface_line(k))
+        return
+    if a.waypoints_only:
+        ctx = S.Context(W, H, max_batch=1, max_corners=64, max_candidates=1 << 12, max_features=64)
+        res = {"waypoint_synthetic": waypoint_synthetic(S, torch, ctx, 3)}
+        ctx.close()
+        print(json.dumps(res))
+        if a.out:
+            with open(a.out, "w") as f:
+                for k in res["waypoint_synthetic"]:
+                    f.write(f"waypoints over a synthetic {k['cells'][0]} x {k['cells'][1]} grid, blocked density {k['density']}: " + waypoint_line(k))
         return
     res = {"standalone": standalone(S, torch, a.batch, 3, a.reps)}
     print("bench_dense: standalone sections done", file=sys.stderr, flush=True)
@@ -1283,6 +1418,7 @@ def main():
                             for k in [c['frontier']]) +
                         "  view over those frontiers' goal_cells and that route's cost: " + view_line(c['view']) +
                         "  surface of that grid's cls and top at the defaults: " + surface_line(c['surface']) +
+                        "  waypoints of the route from a corner to the centre cell over that clearance: " + waypoint_line(c['waypoints']) +
                         f"  removal of the last inserted cloud ({c['remove_move_points']} points, mean of 5): {1e3 * c['remove_ms']:.1f} us, counts {c['remove_counts']} "
                         f"(removed, rejected, missing, short); move to a pose 1 cm and 0.1 degrees away (removal + insert): {1e3 * c['move_ms']:.1f} us, counts "
                         f"{c['move_counts']}; the same cloud inserted once more, same run: {1e3 * c['insert_ms']:.1f} us -> removal / insert "
@@ -1309,6 +1445,8 @@ def main():
                 f.write(f"view over a synthetic {k['cells'][0]} x {k['cells'][1]} grid, (unknown, obstacle) densities {k['densities']}: " + view_line(k))
             for k in s["surface_synthetic"]:
                 f.write(f"surface of a synthetic {k['cells'][0]} x {k['cells'][1]} grid: " + surface_line(k))
+            for k in s["waypoint_synthetic"]:
+                f.write(f"waypoints over a synthetic {k['cells'][0]} x {k['cells'][1]} grid, blocked density {k['density']}: " + waypoint_line(k))
             if g and "ratio_ledger_to_clouds" in g:
                 f.write(f"{g['lanes']} lanes in {g['groups']} groups, {g['frames_per_step_per_lane']}-frame steps, {g['rounds']} alternating rounds of {g['steps']} steps, clouds at "
                         f"step {g['cloud_step']}, every lane's ledger holding {g['ledger_held_per_lane']} keyframes and moving all of them (1 cm, 0.1 degrees) after each call: "
