@@ -105,7 +105,9 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * and the counts and both launches), "grid_clearance" (one svo_grid_clearance_dev: the counts' memset and both launches),
  * "grid_route" (one svo_grid_route_dev: its memsets and every launch), "grid_frontier" (one svo_grid_frontiers_dev: the counts'
  * memset and every launch), "grid_view" (one svo_grid_view_dev: its two memsets and both launches), "grid_surface" (one svo_grid_surface_dev: the
- * counts' memset and the launch), "grid_waypoints" (one svo_grid_waypoints_dev: the counts' memset and the launch); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
+ * counts' memset and the launch), "grid_waypoints" (one svo_grid_waypoints_dev: the counts' memset and the launch),
+ * "voxel_align" (one svo_voxel_map_align_sums_dev: the sums' memset and the launch; svo_voxel_map_align is one bracket per
+ * iteration); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
 /* Measurement aid: the card's own ceilings for the roofline objects (SURVEY 8d asks for a measured FP64 figure).
@@ -629,6 +631,108 @@ int svo_voxel_ledger_remove(svo_voxel_ledger* ledger, int64_t id, uint64_t* coun
 int svo_voxel_ledger_ids(svo_voxel_ledger* ledger, int64_t* ids, int capacity, int* n);
 /* What is held under id: the recorded pose7 (7 doubles), the record count and the DEVICE pointer of the copy; each may be NULL. */
 int svo_voxel_ledger_get(svo_voxel_ledger* ledger, int64_t id, double* pose7, int* n, const svo_cloud_point** points);
+
+/* Voxel map align: the map is asked where a new cloud fits (scan-to-map refinement of a keyframe's pose BEFORE its cloud is
+ * inserted).  One launch matches every record of the cloud with the nearest voxel mean around it and reduces the normal equations
+ * of a point-to-point pose increment to 21 integers; a small host loop solves the 6 x 6 system and repeats.  Every step is an
+ * integer operation or an f64 operation in the written order, without contraction.  Inputs of both entries: the map, n records at
+ * a DEVICE pointer (4-byte aligned, as for the insert), a camera->world transform m (12 HOST doubles by value, the insert's
+ * matrix) and svo_voxel_align_params.  Per record p = {x, y, z, tag}:
+ *   1. Rejected (n_rejected) iff item 1 of the voxel map rejects it (!(z > 0.0f), or max_depth > 0 && z > max_depth), or any of
+ *      |x|, |y|, |z| fails < 1024.0f (f32; a NaN fails), or, with w_r and q_r exactly as item 2 of the voxel map, any q_r fails
+ *      q_r >= -1048575.0 && q_r < 1048575.0: one voxel inside the key range, so every neighbour has a key.
+ *   2. Candidates.  k_r = floor(q_r); the candidates are the voxels k + (i, j, l) with |i|, |j|, |l| <= reach (reach 0 or 1: 1 or
+ *      27 voxels), each with the voxel map's key of its indices.  Each is looked up by item 2 of "Voxel map removal": home slot,
+ *      linear probing, a plain load decides; keys[h] == key is found, EMPTY is absent, and after SVO_VOXEL_MAX_PROBES foreign
+ *      slots the key is absent.  A found slot QUALIFIES iff count = ci >> 40 >= min_count (>= 1): carved slots never qualify.
+ *      Nothing is ever claimed or written to the table: its bytes and the map's counters are the same afterwards.
+ *   3. Nearest candidate.  A qualifying candidate k' has the mean mu_r = ((double)k'_r + (double)s_r / ((double)count * 65536.0))
+ *      * (double)voxel_size (the render's rule 2).  e_r = w_r - mu_r; d2 = e_0*e_0 + e_1*e_1 + e_2*e_2, summed left to right.  The
+ *      MATCH is the qualifying candidate with the smallest d2, and among equal d2 the one with the smallest key (as u64).  No
+ *      qualifying candidate: n_unmatched.  d2 > (double)max_dist * (double)max_dist: n_far (equality still matches).
+ *   4. A match's contribution.  Residual in the camera frame: c_r = m[0][r]*e_0 + m[1][r]*e_1 + m[2][r]*e_2, left to right;
+ *      P = ((double)x, (double)y, (double)z).  The model is c(xi) ~ c + v + omega x P for a pose increment xi = (v, omega) applied
+ *      on the camera side, m' = m [I + [omega]x | v].  Its normal equations need 17 sums; every non-count term is quantised PER
+ *      RECORD by Q_S(t) = (int64)floor(t*S + 0.5) (multiply, add, floor, convert) and the terms are added as 64-bit integers:
+ *        word 0      N, the number of matches
+ *        words 1-3   Q_16(P_0), Q_16(P_1), Q_16(P_2)                                             S = 2^16
+ *        words 4-9   Q_16(P_0*P_0), Q_16(P_0*P_1), Q_16(P_0*P_2), Q_16(P_1*P_1), Q_16(P_1*P_2), Q_16(P_2*P_2)   S = 2^16
+ *        words 10-12 Q_28(c_0), Q_28(c_1), Q_28(c_2)                                             S = 2^28
+ *        words 13-15 Q_28(P_1*c_2 - P_2*c_1), Q_28(P_2*c_0 - P_0*c_2), Q_28(P_0*c_1 - P_1*c_0)   (product, product, difference)
+ *        word 16     Q_28(c_0*c_0 + c_1*c_1 + c_2*c_2), left to right: the cost
+ *      Integer sums commute: the words and the counts depend on no thread order and on no slot placement.
+ *   5. Bounds.  n <= 2^20; max_dist finite and in (0, 8]; |P_i| < 1024 by rule 1; the 3 x 3 part of m is a rotation (the CALLER's
+ *      bound, not checked: with another matrix the words of rule 4 are not defined; nothing faults).  Then |c| = |e| <= 8 and
+ *      |P| < 1774, so the largest term is |P x c| * 2^28 < 2^14 * 2^28 and no word exceeds 2^20 * 2^42 = 2^62 < 2^63 (the
+ *      others: P_i P_j * 2^16 < 2^36, cost * 2^28 <= 2^34, P_i * 2^16 < 2^26, each times 2^20).
+ *   6. sums: 32 int64 on the device, 8-byte aligned.  Words 0-16 as above; words 17-20 = {n_matched, n_rejected, n_unmatched,
+ *      n_far}, whose sum is n (word 0 == word 17); words 21-31 are zero.  sums is zeroed on the stream before the launch; one
+ *      relaxed atomicAdd per workgroup and non-zero word.
+ * The host loop (svo_voxel_map_align; every step is +, -, *, / or sqrt on doubles in the written order, so a restatement in
+ * another language gives the same bits).  pose7 is in the project's convention, X_cam = R(q) X_world + t:
+ *   a. In.  s = sqrt(qw*qw + qx*qx + qy*qy + qz*qz); the camera->world quaternion is u = (qw/s, -qx/s, -qy/s, -qz/s); with
+ *      R = R(u) by the rule of svo_pose7_to_cam_to_world (row-major R[3r + c]) the camera->world translation is
+ *      T_r = -(R[3r]*t_0 + R[3r+1]*t_1 + R[3r+2]*t_2).
+ *   b. Per iteration: R = R(u) by that rule, m[r][c] = R[3r + c], m[r][3] = T_r; one svo_voxel_map_align_sums_dev under m and a
+ *      copy of the 32 words to the host.  n_matched < min_matches ends with SVO_VOXEL_ALIGN_TOO_FEW.
+ *   c. H (symmetric 6 x 6, rows and columns 0-2 for v, 3-5 for omega) and g from the integers, each word converted to double and
+ *      divided by its S (N by none): with A_i = word(1+i)/2^16, B = words 4-9 /2^16, H_vv = N I; H_v,omega = -[A]x, that is
+ *      H[0][4] = A_2, H[0][5] = -A_1, H[1][3] = -A_2, H[1][5] = A_0, H[2][3] = A_1, H[2][4] = -A_0; H_omega,omega = (B_00 + B_11 +
+ *      B_22) I - B, written H[3][3] = B_11 + B_22, H[4][4] = B_00 + B_22, H[5][5] = B_00 + B_11, off-diagonal H[3+i][3+j] = -B_ij;
+ *      g = (words 10-12, words 13-15) / 2^28.
+ *   d. Solve H xi = -g by an unpivoted Cholesky factorisation H = L L^T: for j = 0..5: d = H[j][j]; for k = 0..j-1: d = d -
+ *      L[j][k]*L[j][k]; a pivot d that fails d > 0 && d <= DBL_MAX ends with SVO_VOXEL_ALIGN_DEGENERATE; L[j][j] = sqrt(d); for
+ *      i = j+1..5: s = H[i][j]; for k = 0..j-1: s = s - L[i][k]*L[j][k]; L[i][j] = s / L[j][j].  Forward, i = 0..5: s = -g_i; for
+ *      k = 0..i-1: s = s - L[i][k]*y_k; y_i = s / L[i][i].  Backward, i = 5..0: s = y_i; for k = i+1..5: s = s - L[k][i]*xi_k;
+ *      xi_i = s / L[i][i].
+ *   e. Update, with R still the matrix of step b: T_r = T_r + (R[3r]*v_0 + R[3r+1]*v_1 + R[3r+2]*v_2); b_i = omega_i / 2;
+ *      u' = u (x) (1, b): w = u_0 - u_1*b_0 - u_2*b_1 - u_3*b_2; x = u_1 + u_0*b_0 + u_2*b_2 - u_3*b_1; y = u_2 + u_0*b_1 - u_1*b_2 +
+ *      u_3*b_0; z = u_3 + u_0*b_2 + u_1*b_1 - u_2*b_0, each left to right; a = (w, x, y, z) / sqrt(w*w + x*x + y*y + z*z); then one first-order
+ *      correction of the norm: h = (1 - (a_0*a_0 + a_1*a_1 + a_2*a_2 + a_3*a_3)) / 2, u_i = a_i + a_i*h.
+ *   f. Stop SVO_VOXEL_ALIGN_CONVERGED when v_0*v_0 + v_1*v_1 + v_2*v_2 < (double)eps_t*(double)eps_t and the same of omega <
+ *      (double)eps_r*(double)eps_r (both strict); else SVO_VOXEL_ALIGN_MAX_ITERS after max_iters iterations.
+ *   g. Out.  No step taken: pose7_out = pose7_in, bit for bit.  Otherwise q = (u_0, -u_1, -u_2, -u_3) and, with R = R(u),
+ *      t_r = -(R[r]*T_0 + R[3 + r]*T_1 + R[6 + r]*T_2).  pose7_out is written for every status.
+ * Refusals: SVO_ERR_INVALID with the argument named, nothing launched, outputs untouched, in this order: a null map; n < 0;
+ * n > 2^20; a null matrix or pose7 (pose7_in, then pose7_out, then result for the loop); null params; min_count < 1; reach outside
+ * 0..1; max_dist not finite or outside (0, 8]; max_iters < 1; min_matches < 6; eps_t, then eps_r, not finite or negative; null
+ * sums; sums not 8-byte aligned; and with n > 0 null points, then points not 4-byte aligned.
+ * Order of use: align a keyframe's cloud BEFORE inserting it (a map that already holds the cloud pulls it to where it is), then
+ * insert it (or svo_voxel_ledger_insert_pose7_dev) under the refined pose.  The pipeline never aligns by itself.
+ * Synchronisation as for the voxel map: relaxed device-scope atomics only, no fence, everything on svo_stream(ctx). */
+typedef struct svo_voxel_align_params {
+  int min_count;   /* >= 1: voxels with fewer points are no candidates */
+  int reach;       /* 0 or 1: the record's own voxel, or the 27 around it */
+  float max_dist;  /* finite, in (0, 8]: matches farther than this (map units) are n_far */
+  int max_iters;   /* >= 1 */
+  int min_matches; /* >= 6 */
+  float eps_t;     /* finite, >= 0: the stop rule's bound on |v| (map units) */
+  float eps_r;     /* finite, >= 0: the stop rule's bound on |omega| (radians) */
+} svo_voxel_align_params;
+enum { SVO_VOXEL_ALIGN_CONVERGED = 0, SVO_VOXEL_ALIGN_MAX_ITERS = 1, SVO_VOXEL_ALIGN_TOO_FEW = 2, SVO_VOXEL_ALIGN_DEGENERATE = 3 };
+#define SVO_VOXEL_ALIGN_WORDS 32
+#define SVO_VOXEL_ALIGN_MAX_POINTS (1 << 20)
+typedef struct svo_voxel_align_result {
+  int status;          /* SVO_VOXEL_ALIGN_* */
+  int iterations;      /* launches of the sums */
+  int64_t first_matched, last_matched; /* n_matched of the first and of the last iteration */
+  int64_t first_cost, last_cost;       /* word 16 of the first and of the last iteration */
+  double xi[6];        /* the last increment (v, omega); zeros if no step was taken */
+} svo_voxel_align_result;
+/* min_count 1, reach 1, max_dist = 2 * voxel_size (at most 8), max_iters 10, min_matches 64, eps_t = voxel_size / 100, eps_r = 1e-5.
+ * NOT tuned on real imagery.  Pure; SVO_ERR_INVALID for null params or a voxel_size that is not finite and > 0. */
+int svo_voxel_align_default_params(float voxel_size, svo_voxel_align_params* params);
+/* Asynchronous on svo_stream(ctx): one memset of sums and one launch, one "voxel_align" profile bracket.  n == 0 zeroes sums and
+ * launches nothing more (points may then be NULL). */
+int svo_voxel_map_align_sums_dev(svo_voxel_map* map, const svo_cloud_point* points, int n, const double* c2w12,
+                                 const svo_voxel_align_params* params, int64_t* sums);
+/* svo_pose7_to_cam_to_world, then svo_voxel_map_align_sums_dev. */
+int svo_voxel_map_align_sums_pose7_dev(svo_voxel_map* map, const svo_cloud_point* points, int n, const double* pose7,
+                                       const svo_voxel_align_params* params, int64_t* sums);
+/* The host loop above, synchronous: DEVICE points; pose7_in, pose7_out (7 doubles each, may be the same array) and result on the
+ * HOST.  The sums live in the context's scratch: nothing is allocated. */
+int svo_voxel_map_align(svo_voxel_map* map, const svo_cloud_point* points, int n, const double* pose7_in,
+                        const svo_voxel_align_params* params, double* pose7_out, svo_voxel_align_result* result);
 
 /* Voxel map grid: the ground plan of the map, an axis-aligned na x nb grid over two of the map's axes.  Per cell: the highest and
  * the lowest surface inside a height band, the mean intensity of the highest voxel, how many voxels and points fell into the cell,

@@ -9,4 +9,5 @@ from .api import (SvoError, lib, lib_path, Context, Limits, SynthParams, synth_r
                   CameraInfo, BAOptions, BASummary, PipelineParams, FrameResult, BA, Pipeline, PipelineGroup,
                   pipeline_default_params, synth_default, image_read_gray, kitti_read_poses, ate_rmse, kitti_run, lm_solve, LmStats,
                   RectifyEye, rectify_eye, rectify_eye_from_camera_info, rectify_build_map, VoxelMap, VoxelMapParams,
-                  VoxelCarveParams, VoxelRenderParams, VoxelLedger, VoxelLedgerParams, VoxelGridParams, GridClearanceParams, GridRouteParams)
+                  VoxelCarveParams, VoxelRenderParams, VoxelLedger, VoxelLedgerParams, VoxelGridParams, GridClearanceParams, GridRouteParams,
+                  VoxelAlignParams)

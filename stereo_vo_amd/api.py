@@ -247,6 +247,34 @@ def _render_params(params, min_count, max_radius):
     return _params(voxel_render_default_params, params, min_count=min_count, max_radius=max_radius)
 
 
+class VoxelAlignParams(C.Structure):
+    """svo_voxel_align_params: min_count (>= 1), reach (0 or 1), max_dist (finite, in (0, 8]), max_iters (>= 1), min_matches (>= 6),
+    eps_t and eps_r (finite, >= 0)."""
+    _fields_ = [("min_count", C.c_int), ("reach", C.c_int), ("max_dist", C.c_float), ("max_iters", C.c_int), ("min_matches", C.c_int),
+                ("eps_t", C.c_float), ("eps_r", C.c_float)]
+
+
+class VoxelAlignResult(C.Structure):
+    """svo_voxel_align_result."""
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("first_matched", C.c_int64), ("last_matched", C.c_int64),
+                ("first_cost", C.c_int64), ("last_cost", C.c_int64), ("xi", C.c_double * 6)]
+
+
+VOXEL_ALIGN_WORDS = 32  # SVO_VOXEL_ALIGN_WORDS: int64 words of `sums`
+VOXEL_ALIGN_MAX_POINTS = 1 << 20
+VOXEL_ALIGN_STATUS = ("CONVERGED", "MAX_ITERS", "TOO_FEW", "DEGENERATE")  # SVO_VOXEL_ALIGN_*, by value
+ALIGN_COUNTS = ("n_matched", "n_rejected", "n_unmatched", "n_far")  # words 17..20 of the sums
+
+
+def voxel_align_default_params(voxel_size):
+    """svo_voxel_align_default_params: min_count 1, reach 1, max_dist 2 * voxel_size (at most 8), max_iters 10, min_matches 64,
+    eps_t voxel_size / 100, eps_r 1e-5 (not tuned on real imagery)."""
+    p = VoxelAlignParams()
+    if lib().svo_voxel_align_default_params(C.c_float(voxel_size), C.byref(p)) != 0:
+        raise SvoError("svo_voxel_align_default_params: voxel_size must be finite and > 0")
+    return p
+
+
 class VoxelGridParams(C.Structure):
     """svo_voxel_grid_params: up_axis (0..2), up_sign (+1 / -1), the corner of cell (0, 0) in map units, voxels per cell edge
     (1..1024), na x nb cells (each 1..8192, na*nb <= 2^24), the height band, the span beyond which a cell is an obstacle, min_count."""
@@ -721,6 +749,7 @@ SYMBOLS = [
     "svo_voxel_map_remove_dev", "svo_voxel_map_remove_pose7_dev", "svo_voxel_map_remove_sync", "svo_voxel_map_move_dev", "svo_voxel_map_move_pose7_dev",
     "svo_voxel_ledger_bytes", "svo_voxel_ledger_create", "svo_voxel_ledger_destroy", "svo_voxel_ledger_insert_pose7_dev",
     "svo_voxel_ledger_update_pose7", "svo_voxel_ledger_retire", "svo_voxel_ledger_remove", "svo_voxel_ledger_ids", "svo_voxel_ledger_get",
+    "svo_voxel_align_default_params", "svo_voxel_map_align_sums_dev", "svo_voxel_map_align_sums_pose7_dev", "svo_voxel_map_align",
 ]
 
 
@@ -907,6 +936,13 @@ def lib():
         for f in ("svo_voxel_map_remove_dev", "svo_voxel_map_remove_pose7_dev", "svo_voxel_map_remove_sync", "svo_voxel_map_move_dev", "svo_voxel_map_move_pose7_dev",
                   "svo_voxel_ledger_bytes", "svo_voxel_ledger_create", "svo_voxel_ledger_insert_pose7_dev", "svo_voxel_ledger_update_pose7",
                   "svo_voxel_ledger_retire", "svo_voxel_ledger_remove", "svo_voxel_ledger_ids", "svo_voxel_ledger_get"):
+            getattr(L, f).restype = ci
+        # the align
+        L.svo_voxel_align_default_params.argtypes = [C.c_float, vp]
+        L.svo_voxel_map_align_sums_dev.argtypes = [vp, vp, ci, vp, vp, vp]
+        L.svo_voxel_map_align_sums_pose7_dev.argtypes = [vp, vp, ci, vp, vp, vp]
+        L.svo_voxel_map_align.argtypes = [vp, vp, ci, vp, vp, vp, vp]
+        for f in ("svo_voxel_align_default_params", "svo_voxel_map_align_sums_dev", "svo_voxel_map_align_sums_pose7_dev", "svo_voxel_map_align"):
             getattr(L, f).restype = ci
         _LIB = L
     return _LIB
@@ -1601,6 +1637,27 @@ class VoxelMap:
         else:
             a, b = _f64(from_pose7).reshape(7), _f64(to_pose7).reshape(7)
             self.ctx._chk(self.L.svo_voxel_map_move_pose7_dev(self.h, dev_ptr, int(n), _p(a), _p(b), counts_ptr), "svo_voxel_map_move_pose7_dev")
+
+    def align_sums(self, points_ptr, n, c2w12=None, pose7=None, params=None, sums_ptr=None, **overrides):
+        """svo_voxel_map_align_sums_dev / _pose7_dev: the n records at the device pointer matched against the map under c2w12 (3 x 4
+        camera->world) or pose7, exactly one of them; the normal equations of the pose increment and the four counts go to the 32
+        int64 at the device pointer sums_ptr (include/svo.h, "Voxel map align").  params: a VoxelAlignParams (None: the defaults for
+        this map's voxel size) and / or its fields as keywords.  Nothing in the map changes.  Asynchronous on the context's stream."""
+        prm = _params(lambda: voxel_align_default_params(self.params.voxel_size), params, **overrides)
+        self._by_pose("align_sums", "c2w12", c2w12, pose7, "align_sums", (points_ptr, int(n)), (C.byref(prm), sums_ptr))
+
+    def align(self, points_ptr, n, pose7, params=None, **overrides):
+        """svo_voxel_map_align: the pose7 of the cloud at the device pointer refined against the map by the host-driven loop;
+        synchronous.  Align a keyframe's cloud BEFORE inserting it, then insert it under the result.  Returns (pose7_out as 7
+        float64, {"status" (one of VOXEL_ALIGN_STATUS), "iterations", "first_matched", "last_matched", "first_cost", "last_cost",
+        "xi" (6 float64)})."""
+        prm = _params(lambda: voxel_align_default_params(self.params.voxel_size), params, **overrides)
+        q = _f64(pose7).reshape(7)
+        out, res = np.empty(7, np.float64), VoxelAlignResult()
+        self.ctx._chk(self.L.svo_voxel_map_align(self.h, points_ptr, int(n), _p(q), C.byref(prm), _p(out), C.byref(res)), "svo_voxel_map_align")
+        return out, {"status": VOXEL_ALIGN_STATUS[res.status], "iterations": res.iterations, "first_matched": int(res.first_matched),
+                     "last_matched": int(res.last_matched), "first_cost": int(res.first_cost), "last_cost": int(res.last_cost),
+                     "xi": np.array(list(res.xi), np.float64)}
 
     def insert_keyframe_clouds(self, table, poses7):
         """The list Pipeline.keyframe_clouds() / PipelineGroup.keyframe_clouds() returns, one pose7 per entry: every entry's device

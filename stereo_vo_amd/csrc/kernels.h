@@ -133,5 +133,13 @@ int svo_kfc_table(SvoKfClouds* k, int* n, const svo_keyframe_cloud** table);
 int svo_kfc_copy(SvoKfClouds* k, int i, svo_cloud_point* host, int capacity);
 int svo_kfc_disparity(SvoKfClouds* k, int i, const int16_t** dev);  // entry i's map as its cloud was formed from it
 int svo_kfc_copy_disparity(SvoKfClouds* k, int i, int16_t* host);   // the same, W * H values to the host, synchronous
+// What csrc/voxel_align.hip reads a voxel map through (csrc/voxel.hip owns the map): the table's five arrays, read only.
+struct SvoVoxelView {
+  svo_ctx* ctx;
+  const unsigned long long *keys, *ci, *sx, *sy, *sz;
+  unsigned long long mask;  // cap - 1
+  float voxel_size, max_depth;
+};
+SvoVoxelView svo_voxel_map_view(const svo_voxel_map* m);  // m is not null
 const char* svo_rectify_error_text();  // of the calling thread's last context-free rectification call ("" if none failed)
 #endif

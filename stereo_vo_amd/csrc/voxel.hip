@@ -834,6 +834,10 @@ extern "C" int svo_voxel_map_clear(svo_voxel_map* m) {
   return voxel_clear(m);
 }
 
+SvoVoxelView svo_voxel_map_view(const svo_voxel_map* m) {  // kernels.h: for csrc/voxel_align.hip
+  return SvoVoxelView{m->ctx, m->t.keys, m->t.ci, m->t.sx, m->t.sy, m->t.sz, m->t.mask, m->prm.voxel_size, m->prm.max_depth};
+}
+
 static int voxel_insert_launch(svo_voxel_map* m, const svo_cloud_point* points, int n, const double* m12) {
   svo_ctx* ctx = m->ctx;
   VoxelInsertArgs a{};

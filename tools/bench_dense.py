@@ -83,6 +83,12 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      grid of each filled map from one start, the corner with the longest path, and on a seeded 2048 x 2048 grid (blocked density
      0.1) from one start (a corner) and from 4,096 seeded starts; max_look 16, 64 and 255.  Per case the counts and, as context for one path up to max_look 64, the device-to-host copies of path, path_len and blocked plus the
      restatement's Python walk on the host: the detour the entry replaces.  --waypoints-only runs just the seeded grid.
+ 18. align: on each filled map of section 7 (before sections 8 and 9), one svo_voxel_map_align_sums_dev of the batch's last cloud
+     under its own pose ("voxel_align" bracket: the sums' memset and the launch, mean of 5 after the warm-up) at reach 0 and 1, with
+     the four counts, beside section 10's insert of the same cloud in the same run (one probe per record against 27 look-ups); and
+     svo_voxel_map_align of that cloud from its pose displaced by half a voxel and 0.01 rad at the defaults: wall clock (mean of 5),
+     the iterations taken, the status, and the share of the wall clock that is not inside the "voxel_align" brackets of one more run
+     (the 256-byte copies, the waits and the host solves).
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -319,6 +325,7 @@ def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy):
                         "extract_ms": ms / k, "extract_n_total": int(c2.cpu()[0]), "table_bytes_bound_ms": 1e3 * 40 * vm.capacity / copy,
                         "extract_share_of_bound": (1e3 * 40 * vm.capacity / copy) / (ms / k)})
             out[-1].update(remove_and_move(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, copy))
+            out[-1].update(align_view(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup))
             out[-1].update(grid_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # before the carve changes the map, as the render
             out[-1].update(clearance_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # of the same grid, before the carve too
             out[-1].update(route_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # over that grid's clearance
@@ -369,6 +376,67 @@ def remove_and_move(torch, ctx, vm, cloud, n, angle, forward, warmup, copy):
     out["remove_move_bound_ms"] = 1e3 * 16 * n / copy
     out["remove_move_points"] = n
     return out
+
+
+def align_view(torch, ctx, vm, cloud, n, angle, forward, warmup):
+    """Section 18 for one filled map: the sums of the last inserted cloud under its own pose at reach 0 and 1, and the loop from the
+    pose displaced by half a voxel and 0.01 rad.  Nothing in the map changes."""
+    import voxel_ref as V
+    here = V.rot_y(angle, (0.0, 0.0, forward))
+    vs = float(vm.params.voxel_size)
+    sums = torch.zeros(32, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    p, out = cloud.data_ptr(), {"points": n}
+    for reach in (0, 1):
+        for _ in range(warmup):
+            vm.align_sums(p, n, c2w12=here, sums_ptr=sums.data_ptr(), reach=reach)
+        ctx.profile_select("voxel_align")
+        for _ in range(5):
+            vm.align_sums(p, n, c2w12=here, sums_ptr=sums.data_ptr(), reach=reach)
+        ms, k = ctx.profile_read()
+        ctx.profile_select("")
+        assert k == 5, k
+        out[f"sums_reach{reach}_ms"] = ms / k
+        out[f"sums_reach{reach}_counts"] = [int(v) for v in sums.cpu()[17:21]]
+    # the cloud's pose7 (X_cam = R(q) X_world + t) from its camera->world rot_y(angle), shift (0, 0, forward), then displaced
+    c, sn = np.cos(angle / 2), np.sin(angle / 2)
+    R = np.asarray(here).reshape(3, 4)[:, :3]
+    pose = np.concatenate([[c, 0.0, -sn, 0.0], -R.T @ np.array([0.0, 0.0, forward])])
+    from stereo_vo_amd import api
+    assert np.allclose(api.pose7_to_cam_to_world(pose).reshape(12), here, rtol=0, atol=1e-12)
+    import voxel_align_ref as A  # the tests' maker of a displaced pose: the shift in the world frame, the turn on the camera side
+    start = np.array(A.displaced(pose, [0.5 * vs * c for c in (0.6, -0.5, 0.62)], [0.01 * c for c in (0.5, 0.7, -0.5)]))
+    for _ in range(warmup):
+        vm.align(p, n, start)
+    t0 = time.perf_counter()
+    for _ in range(5):
+        pose_out, res = vm.align(p, n, start)
+    out["loop_wall_ms"] = 1e3 * (time.perf_counter() - t0) / 5
+    ctx.profile_select("voxel_align")
+    t0 = time.perf_counter()
+    vm.align(p, n, start)
+    wall = 1e3 * (time.perf_counter() - t0)
+    ms, k = ctx.profile_read()
+    ctx.profile_select("")
+    assert k == res["iterations"], (k, res)
+    out.update({"loop_iterations": res["iterations"], "loop_status": res["status"], "loop_first_matched": res["first_matched"],
+                "loop_last_matched": res["last_matched"], "loop_first_cost": res["first_cost"], "loop_last_cost": res["last_cost"],
+                "loop_brackets_ms": ms, "loop_profiled_wall_ms": wall, "loop_share_outside_brackets": 1.0 - ms / wall,
+                "loop_start_shift": float(0.5 * vs * np.linalg.norm([0.6, -0.5, 0.62])),
+                "loop_shift_left": float(np.linalg.norm(api.pose7_to_cam_to_world(pose_out)[:, 3] - np.array([0.0, 0.0, forward])))})
+    return {"align": out}
+
+
+def align_line(k, insert_ms):
+    """Section 18's lines of the text report for one align_view."""
+    return (f"sums of the last inserted cloud ({k['points']} points) under its own pose (memset + one launch, mean of 5): reach 0 "
+            f"{1e3 * k['sums_reach0_ms']:.1f} us, counts {k['sums_reach0_counts']}; reach 1 {1e3 * k['sums_reach1_ms']:.1f} us, counts {k['sums_reach1_counts']} "
+            f"(matched, rejected, unmatched, far); the same run's insert of the same cloud {1e3 * insert_ms:.1f} us -> reach 0 / insert "
+            f"{k['sums_reach0_ms'] / insert_ms:.2f}, reach 1 / insert {k['sums_reach1_ms'] / insert_ms:.2f}\n"
+            f"  align from that pose displaced by half a voxel ({k['loop_start_shift']:.4f}) and 0.01 rad, defaults: {k['loop_wall_ms']:.3f} ms wall clock (mean of 5), "
+            f"{k['loop_iterations']} iterations, status {k['loop_status']}, matched {k['loop_first_matched']} -> {k['loop_last_matched']}, cost word "
+            f"{k['loop_first_cost']} -> {k['loop_last_cost']}, shift left {k['loop_shift_left']:.4f}; one more run with the brackets on: {k['loop_profiled_wall_ms']:.3f} ms, "
+            f"of which {k['loop_brackets_ms']:.3f} ms inside the brackets -> {100 * k['loop_share_outside_brackets']:.1f} % is the 256-byte copies, the waits and the host solves\n")
 
 
 def grid_view(S, torch, ctx, vm, c2w, warmup, copy):
@@ -1423,7 +1491,8 @@ def main():
                         f"(removed, rejected, missing, short); move to a pose 1 cm and 0.1 degrees away (removal + insert): {1e3 * c['move_ms']:.1f} us, counts "
                         f"{c['move_counts']}; the same cloud inserted once more, same run: {1e3 * c['insert_ms']:.1f} us -> removal / insert "
                         f"{c['remove_ms'] / c['insert_ms']:.2f}, move / insert {c['move_ms'] / c['insert_ms']:.2f}; 16 B per record at hbm_copy "
-                        f"{1e3 * c['remove_move_bound_ms']:.2f} us\n")
+                        f"{1e3 * c['remove_move_bound_ms']:.2f} us\n"
+                        "  align: " + align_line(c['align'], c['insert_ms']))
             for k in s["clearance_synthetic"]:
                 f.write(f"clearance of a synthetic {k['cells'][0]} x {k['cells'][1]} grid, source density {k['density']}, max_dist {k['max_dist']} (all four outputs, mean of 5): "
                         f"{1e3 * k['ms']:.1f} us, counts {k['counts']} (sources, reached, unreached, blocked); 22 B per cell at hbm_copy {1e3 * k['bound_ms']:.1f} us -> "
