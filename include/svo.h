@@ -734,6 +734,115 @@ int svo_voxel_map_align_sums_pose7_dev(svo_voxel_map* map, const svo_cloud_point
 int svo_voxel_map_align(svo_voxel_map* map, const svo_cloud_point* points, int n, const double* pose7_in,
                         const svo_voxel_align_params* params, double* pose7_out, svo_voxel_align_result* result);
 
+/* Voxel map normals: one launch gives every voxel a surface normal and a curvature from the means of the 27 voxels around it, into
+ * a side array of the CALLER's with one 16-byte record per slot, indexed by slot.  Slots never move and keys stay, so an index stays
+ * valid across later inserts; only the values go stale, and the caller runs the launch again after inserts, removals or a carve.
+ * Every record of the array is written by every call; no byte of the table and no map counter changes.  Every step is an integer
+ * operation or an f64 operation in the written order, without contraction.  Per slot:
+ *   1. Centre.  A slot is a centre iff its key is not EMPTY and count = ci >> 40 >= min_count (>= 1).  Any other slot gets the
+ *      record {0, 0, 0, -1.0f}.
+ *   2. Candidates.  With k the centre's indices, the 27 voxels k + (i, j, l), |i|, |j|, |l| <= 1, candidate c = (i + 1) + 3 (j + 1) +
+ *      9 (l + 1) (the align's order; c = 13 is the centre).  A candidate one of whose indices leaves [-2^20, 2^20) has no key and is
+ *      absent: the centre, unlike an align record, may sit at the edge of the key range.  Each other candidate is looked up by item
+ *      2 of "Voxel map removal": home slot, linear probing, a plain load decides, absent after SVO_VOXEL_MAX_PROBES foreign slots;
+ *      nothing is claimed.  A found candidate TAKES PART iff its count >= min_count; the centre always takes part.
+ *   3. Integer moments.  Per participant and axis r, with o = (i, j, l) its offset and (s_0, s_1, s_2) = (sx, sy, sz) of its slot:
+ *      g_r = o_r * 65536 + s_r div count (exact floor division; the mean in 65536ths of a voxel relative to the centre's voxel,
+ *      -65536 <= g_r < 131072).  N = the number of participants; S1_r = sum g_r; S2_rs = sum g_r * g_s (r <= s); C_rs = N * S2_rs -
+ *      S1_r * S1_s in int64 (each product is below 2^44).  Every voxel counts once, not once per point.  C is the covariance of the
+ *      means scaled by 65536^2 N^2; it depends on no slot placement and on no thread order.
+ *   4. Eigenvectors.  a = (double)C (symmetric, a_rs = a_sr), V = I (3 x 3).  Exactly 4 sweeps over (p, q) = (0, 1), (0, 2), (1, 2),
+ *      with r the third index.  Per pair: skipped iff a_pq == 0.0; else
+ *        th = (a_qq - a_pp) / (2.0 * a_pq);  t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
+ *        c = 1.0 / sqrt(t * t + 1.0);  s = t * c;
+ *        x = t * a_pq;  a_pp = a_pp - x;  a_qq = a_qq + x;  a_pq = 0.0;
+ *        y = a_rp, z = a_rq:  a_rp = c * y - s * z;  a_rq = s * y + c * z;
+ *        for k = 0, 1, 2: y = V[k][p], z = V[k][q]:  V[k][p] = c * y - s * z;  V[k][q] = s * y + c * z.
+ *      Only + - * / and sqrt; a th * th that overflows gives t = 0 by IEEE rules (th is never a NaN: a_pq != 0 and finite).
+ *   5. Validity.  lambda_i = a_ii.  lo = the lowest index with the smallest lambda; mid = of the other two indices the one with
+ *      the smaller lambda (the lower index if equal).  tr = lambda_0 + lambda_1 + lambda_2, left to right.  Tested in this order,
+ *      the first failing test counts: N >= min_neighbours (else n_few; 3 <= min_neighbours <= 27); lambda_mid > 0.0 (else
+ *      n_collinear: the means lie on a line or in a point); max(lambda_lo, 0.0) <= (double)max_curvature * tr (else n_curved).
+ *      An invalid centre gets {0, 0, 0, -1.0f}.
+ *   6. Output of a valid centre.  n = column lo of V; with m the lowest index of the largest fabs(n_i), n is negated iff n_m < 0.0;
+ *      then each component is converted to f32.  curvature = (float)(max(lambda_lo, 0.0) / tr), in [0, 1/3].  A valid normal is
+ *      never all zero: the zero vector is what "no normal" means to every reader.
+ *   7. counts: 8 u64 on the device, 8-byte aligned, or NULL: {n_centres, n_valid, n_few, n_collinear, n_curved, 0, 0, 0} with
+ *      n_centres = n_valid + n_few + n_collinear + n_curved.  Zeroed on the stream before the launch; combined per wavefront, then
+ *      one relaxed atomicAdd per workgroup and non-zero word.
+ * Refusals: SVO_ERR_INVALID with the argument named, nothing launched, outputs untouched, in this order: a null map; null params;
+ * min_count < 1; min_neighbours outside 3..27; max_curvature not finite or outside (0, 1]; null normals; normals not 16-byte
+ * aligned; counts not 8-byte aligned.
+ * Order of use: after the last insert / update / carve and before whoever reads the normals.
+ * Synchronisation as for the voxel map: relaxed device-scope atomics only (the counts), no fence, everything on svo_stream(ctx). */
+typedef struct svo_voxel_normal { float nx, ny, nz, curvature; } svo_voxel_normal; /* 16 bytes; {0, 0, 0, -1}: no normal */
+typedef struct svo_voxel_normals_params {
+  int min_count;       /* >= 1: voxels with fewer points are neither centres nor neighbours */
+  int min_neighbours;  /* 3..27: participants (the centre included) a normal needs */
+  float max_curvature; /* finite, in (0, 1]: lambda_lo / trace above this is no surface; 1 refuses nothing */
+} svo_voxel_normals_params;
+#define SVO_VOXEL_NORMALS_COUNTS 8
+/* min_count 1, min_neighbours 5, max_curvature 1.0f.  NOT tuned on real imagery.  Pure; SVO_ERR_INVALID for null params. */
+int svo_voxel_normals_default_params(svo_voxel_normals_params* params);
+/* Bytes of the side array: 16 << capacity_log2.  Pure; SVO_ERR_INVALID and *bytes = 0 for parameters svo_voxel_map_create refuses. */
+int svo_voxel_map_normals_bytes(const svo_voxel_map_params* params, size_t* bytes);
+/* Asynchronous on svo_stream(ctx): the counts' memset (if any) and one launch, one "voxel_normals" profile bracket.  normals: DEVICE,
+ * svo_voxel_map_normals_bytes bytes. */
+int svo_voxel_map_normals_dev(svo_voxel_map* map, const svo_voxel_normals_params* params, svo_voxel_normal* normals, uint64_t* counts);
+/* svo_voxel_map_normals_dev into device memory of its own, copied to the HOST; synchronous; allocates and frees.  host_normals:
+ * one record per slot (any alignment); host_counts: 8 words, or NULL. */
+int svo_voxel_map_normals(svo_voxel_map* map, const svo_voxel_normals_params* params, svo_voxel_normal* host_normals,
+                          uint64_t* host_counts);
+
+/* Voxel map align, plane form: the align with the distance ALONG THE MATCHED VOXEL'S NORMAL as its residual.  A point-to-mean
+ * residual holds a cloud along a plane only as well as the two samplings agree; this one lets it slide.  `normals` is the DEVICE
+ * array svo_voxel_map_normals_dev wrote for this map (one record per slot; stale values are the caller's affair).
+ * svo_voxel_align_params and svo_voxel_align_result are the align's.  Rules 1-3 of "Voxel map align" hold word for word (rejection,
+ * candidates, the nearest qualifying mean, ties, n_far): the match is chosen BEFORE its normal is looked at.
+ *   4'. A match's contribution.  With s the matched slot: nn = ((double)normals[s].nx, (double).ny, (double).nz).  If all three
+ *      are zero the record is counted in n_no_normal and contributes nothing.  Otherwise, with e_r = w_r - mu_r (world frame) and
+ *      P as in rule 4:
+ *        r   = nn_0*e_0 + nn_1*e_1 + nn_2*e_2, left to right;
+ *        a_c = m[0][c]*nn_0 + m[1][c]*nn_1 + m[2][c]*nn_2, left to right: the normal in the camera frame;
+ *        b   = P x a: b_0 = P_1*a_2 - P_2*a_1, b_1 = P_2*a_0 - P_0*a_2, b_2 = P_0*a_1 - P_1*a_0 (product, product, difference).
+ *      The model is r(xi) ~ r + a.v + b.omega for the same camera-side increment, so the Jacobian row is j = (a_0, a_1, a_2, b_0,
+ *      b_1, b_2).  Every term is quantised per record by Q_S and added as a 64-bit integer:
+ *        word 0       N, the contributing matches
+ *        words 1-21   Q_S(j_i * j_k), i <= k, row-major over the upper triangle (word 1 + 6 i - i (i - 1) / 2 + (k - i));
+ *                     S = 2^40 for i, k < 3; 2^30 for i < 3 <= k; 2^20 for i, k >= 3
+ *        words 22-24  Q_36(a_i * r)
+ *        words 25-27  Q_28(b_i * r)
+ *        word 28      Q_28(r * r): the cost
+ *        words 29-33  n_matched (= word 0), n_rejected, n_unmatched, n_far, n_no_normal; their sum is n
+ *        words 34-39  zero
+ *   5'. Bounds.  n <= 2^20; |P| < 1774; |nn| <= 1.0001 (the CALLER's bound, as the rotation is; the normals launch meets it);
+ *      |e| <= 8.  Then a_i a_k <= 1.0003 and S = 2^40 gives less than 2^41; |a_i b_k| < 2^11 and S = 2^30 gives less than 2^41;
+ *      |b_i b_k| < 2^22 and S = 2^20 gives less than 2^42; |a_i r| < 2^4 and S = 2^36 gives less than 2^40; |b_i r| < 2^14 and
+ *      S = 2^28 gives less than 2^42; r*r <= 65 and S = 2^28 gives less than 2^35.  Every term times its S stays below 2^43 and no
+ *      word exceeds 2^63.
+ *   6'. sums: SVO_VOXEL_ALIGN_PLANE_WORDS int64 on the device, 8-byte aligned, zeroed on the stream before the launch; one relaxed
+ *      atomicAdd per workgroup and non-zero word.
+ * The host loop (svo_voxel_map_align_plane): steps a, b, d, e, f and g of the align's loop as they are, over these sums.  Step c':
+ * H[i][k] = H[k][i] = (double)word(i, k) / S(i, k); g_i = (double)word(22 + i) / 2^36 for i < 3 and (double)word(22 + i) / 2^28 for
+ * i >= 3.  SVO_VOXEL_ALIGN_TOO_FEW tests word 29; first_cost and last_cost are word 28, first_matched and last_matched word 29.  A
+ * scene that does not hold all six freedoms (one plane; two planes leave the shift along their common line free only up to what
+ * the match distance adds) ends SVO_VOXEL_ALIGN_DEGENERATE when a pivot fails, and is otherwise NOT held along its free directions:
+ * the residual sees no motion inside a plane.
+ * Refusals: the align's list in the align's order, with "null normals, then normals not 16-byte aligned" directly after the null map.
+ * Order of use: svo_voxel_map_normals_dev after the map's last change, then this, then the cloud's own insert. */
+#define SVO_VOXEL_ALIGN_PLANE_WORDS 40
+/* Asynchronous on svo_stream(ctx): one memset of sums and one launch, one "voxel_align_plane" profile bracket.  n == 0 zeroes sums
+ * and launches nothing more. */
+int svo_voxel_map_align_plane_sums_dev(svo_voxel_map* map, const svo_voxel_normal* normals, const svo_cloud_point* points, int n,
+                                       const double* c2w12, const svo_voxel_align_params* params, int64_t* sums);
+/* svo_pose7_to_cam_to_world, then svo_voxel_map_align_plane_sums_dev. */
+int svo_voxel_map_align_plane_sums_pose7_dev(svo_voxel_map* map, const svo_voxel_normal* normals, const svo_cloud_point* points, int n,
+                                             const double* pose7, const svo_voxel_align_params* params, int64_t* sums);
+/* The host loop, synchronous; the 40 words live in the context's scratch: nothing is allocated. */
+int svo_voxel_map_align_plane(svo_voxel_map* map, const svo_voxel_normal* normals, const svo_cloud_point* points, int n,
+                              const double* pose7_in, const svo_voxel_align_params* params, double* pose7_out,
+                              svo_voxel_align_result* result);
+
 /* Voxel map grid: the ground plan of the map, an axis-aligned na x nb grid over two of the map's axes.  Per cell: the highest and
  * the lowest surface inside a height band, the mean intensity of the highest voxel, how many voxels and points fell into the cell,
  * and a class (UNKNOWN, LEVEL, OBSTACLE).  One walk over the table bins every qualifying voxel by its KEY, in integers only; a second

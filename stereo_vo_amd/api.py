@@ -266,6 +266,13 @@ VOXEL_ALIGN_STATUS = ("CONVERGED", "MAX_ITERS", "TOO_FEW", "DEGENERATE")  # SVO_
 ALIGN_COUNTS = ("n_matched", "n_rejected", "n_unmatched", "n_far")  # words 17..20 of the sums
 
 
+def _align_result(res):
+    """A VoxelAlignResult as the dict VoxelMap.align and .align_plane return."""
+    return {"status": VOXEL_ALIGN_STATUS[res.status], "iterations": res.iterations, "first_matched": int(res.first_matched),
+            "last_matched": int(res.last_matched), "first_cost": int(res.first_cost), "last_cost": int(res.last_cost),
+            "xi": np.array(list(res.xi), np.float64)}
+
+
 def voxel_align_default_params(voxel_size):
     """svo_voxel_align_default_params: min_count 1, reach 1, max_dist 2 * voxel_size (at most 8), max_iters 10, min_matches 64,
     eps_t voxel_size / 100, eps_r 1e-5 (not tuned on real imagery)."""
@@ -273,6 +280,34 @@ def voxel_align_default_params(voxel_size):
     if lib().svo_voxel_align_default_params(C.c_float(voxel_size), C.byref(p)) != 0:
         raise SvoError("svo_voxel_align_default_params: voxel_size must be finite and > 0")
     return p
+
+
+class VoxelNormalsParams(C.Structure):
+    """svo_voxel_normals_params: min_count (>= 1), min_neighbours (3..27), max_curvature (finite, in (0, 1])."""
+    _fields_ = [("min_count", C.c_int), ("min_neighbours", C.c_int), ("max_curvature", C.c_float)]
+
+
+VoxelNormal = np.dtype([("nx", np.float32), ("ny", np.float32), ("nz", np.float32), ("curvature", np.float32)])  # svo_voxel_normal
+NORMALS_COUNTS = ("n_centres", "n_valid", "n_few", "n_collinear", "n_curved")  # words 0..4 of the 8 counts; the rest stay zero
+VOXEL_NORMALS_COUNTS = 8  # SVO_VOXEL_NORMALS_COUNTS: uint64 words of `counts`
+VOXEL_ALIGN_PLANE_WORDS = 40  # SVO_VOXEL_ALIGN_PLANE_WORDS: int64 words of the plane form's `sums`
+ALIGN_PLANE_COUNTS = ("n_matched", "n_rejected", "n_unmatched", "n_far", "n_no_normal")  # words 29..33 of the plane form's sums
+
+
+def voxel_normals_default_params():
+    """svo_voxel_normals_default_params: min_count 1, min_neighbours 5, max_curvature 1.0 (not tuned on real imagery)."""
+    p = VoxelNormalsParams()
+    if lib().svo_voxel_normals_default_params(C.byref(p)) != 0:
+        raise SvoError("svo_voxel_normals_default_params failed")
+    return p
+
+
+def voxel_map_normals_bytes(params):
+    """svo_voxel_map_normals_bytes: bytes of a map's side array of normals, 16 per slot (no GPU involved); params: a VoxelMapParams."""
+    n = C.c_size_t(0)
+    if lib().svo_voxel_map_normals_bytes(C.byref(params), C.byref(n)) != 0:
+        raise SvoError("svo_voxel_map_normals_bytes: voxel_size must be finite and > 0, capacity_log2 in 8..28")
+    return int(n.value)
 
 
 class VoxelGridParams(C.Structure):
@@ -750,6 +785,8 @@ SYMBOLS = [
     "svo_voxel_ledger_bytes", "svo_voxel_ledger_create", "svo_voxel_ledger_destroy", "svo_voxel_ledger_insert_pose7_dev",
     "svo_voxel_ledger_update_pose7", "svo_voxel_ledger_retire", "svo_voxel_ledger_remove", "svo_voxel_ledger_ids", "svo_voxel_ledger_get",
     "svo_voxel_align_default_params", "svo_voxel_map_align_sums_dev", "svo_voxel_map_align_sums_pose7_dev", "svo_voxel_map_align",
+    "svo_voxel_normals_default_params", "svo_voxel_map_normals_bytes", "svo_voxel_map_normals_dev", "svo_voxel_map_normals",
+    "svo_voxel_map_align_plane_sums_dev", "svo_voxel_map_align_plane_sums_pose7_dev", "svo_voxel_map_align_plane",
 ]
 
 
@@ -943,6 +980,17 @@ def lib():
         L.svo_voxel_map_align_sums_pose7_dev.argtypes = [vp, vp, ci, vp, vp, vp]
         L.svo_voxel_map_align.argtypes = [vp, vp, ci, vp, vp, vp, vp]
         for f in ("svo_voxel_align_default_params", "svo_voxel_map_align_sums_dev", "svo_voxel_map_align_sums_pose7_dev", "svo_voxel_map_align"):
+            getattr(L, f).restype = ci
+        # the normals and the plane form of the align
+        L.svo_voxel_normals_default_params.argtypes = [vp]
+        L.svo_voxel_map_normals_bytes.argtypes = [vp, vp]
+        L.svo_voxel_map_normals_dev.argtypes = [vp, vp, vp, vp]
+        L.svo_voxel_map_normals.argtypes = [vp, vp, vp, vp]
+        L.svo_voxel_map_align_plane_sums_dev.argtypes = [vp, vp, vp, ci, vp, vp, vp]
+        L.svo_voxel_map_align_plane_sums_pose7_dev.argtypes = [vp, vp, vp, ci, vp, vp, vp]
+        L.svo_voxel_map_align_plane.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp]
+        for f in ("svo_voxel_normals_default_params", "svo_voxel_map_normals_bytes", "svo_voxel_map_normals_dev", "svo_voxel_map_normals",
+                  "svo_voxel_map_align_plane_sums_dev", "svo_voxel_map_align_plane_sums_pose7_dev", "svo_voxel_map_align_plane"):
             getattr(L, f).restype = ci
         _LIB = L
     return _LIB
@@ -1655,9 +1703,41 @@ class VoxelMap:
         q = _f64(pose7).reshape(7)
         out, res = np.empty(7, np.float64), VoxelAlignResult()
         self.ctx._chk(self.L.svo_voxel_map_align(self.h, points_ptr, int(n), _p(q), C.byref(prm), _p(out), C.byref(res)), "svo_voxel_map_align")
-        return out, {"status": VOXEL_ALIGN_STATUS[res.status], "iterations": res.iterations, "first_matched": int(res.first_matched),
-                     "last_matched": int(res.last_matched), "first_cost": int(res.first_cost), "last_cost": int(res.last_cost),
-                     "xi": np.array(list(res.xi), np.float64)}
+        return out, _align_result(res)
+
+    def normals(self, normals_ptr, params=None, counts_ptr=None, **overrides):
+        """svo_voxel_map_normals_dev: a normal and a curvature per slot from the means of the 27 voxels around it, into the
+        voxel_map_normals_bytes(self.params) bytes at the device pointer normals_ptr (16-byte aligned, one VoxelNormal per slot,
+        indexed by slot; {0, 0, 0, -1}: no normal).  counts_ptr: 8 uint64 on the device (NORMALS_COUNTS, then zeros), or None.
+        params: a VoxelNormalsParams and / or its fields as keywords.  Nothing in the map changes; run it again after inserts,
+        removals or a carve.  Asynchronous on the context's stream."""
+        prm = _params(voxel_normals_default_params, params, **overrides)
+        self.ctx._chk(self.L.svo_voxel_map_normals_dev(self.h, C.byref(prm), normals_ptr, counts_ptr), "svo_voxel_map_normals_dev")
+
+    def normals_host(self, params=None, **overrides):
+        """svo_voxel_map_normals: normals() into memory of its own, synchronous.  Returns (a VoxelNormal array with one record per
+        slot, {"n_centres", "n_valid", "n_few", "n_collinear", "n_curved"})."""
+        prm = _params(voxel_normals_default_params, params, **overrides)
+        out, c = np.empty(self.capacity, VoxelNormal), np.zeros(VOXEL_NORMALS_COUNTS, np.uint64)
+        self.ctx._chk(self.L.svo_voxel_map_normals(self.h, C.byref(prm), _p(out), _p(c)), "svo_voxel_map_normals")
+        return out, dict(zip(NORMALS_COUNTS, (int(v) for v in c)))
+
+    def align_plane_sums(self, normals_ptr, points_ptr, n, c2w12=None, pose7=None, params=None, sums_ptr=None, **overrides):
+        """svo_voxel_map_align_plane_sums_dev / _pose7_dev: align_sums' matching, then the normal equations of the point-to-plane
+        increment along the matched voxel's normal (normals_ptr: what normals() wrote) and the five counts, into the 40 int64 at
+        the device pointer sums_ptr (include/svo.h, "Voxel map align, plane form").  Asynchronous on the context's stream."""
+        prm = _params(lambda: voxel_align_default_params(self.params.voxel_size), params, **overrides)
+        self._by_pose("align_plane_sums", "c2w12", c2w12, pose7, "align_plane_sums", (normals_ptr, points_ptr, int(n)), (C.byref(prm), sums_ptr))
+
+    def align_plane(self, normals_ptr, points_ptr, n, pose7, params=None, **overrides):
+        """svo_voxel_map_align_plane: align() with the point-to-plane residual; synchronous.  Run normals() after the map's last
+        change and before this.  Returns (pose7_out, the result dict of align(): the costs are word 28, the matches word 29)."""
+        prm = _params(lambda: voxel_align_default_params(self.params.voxel_size), params, **overrides)
+        q = _f64(pose7).reshape(7)
+        out, res = np.empty(7, np.float64), VoxelAlignResult()
+        self.ctx._chk(self.L.svo_voxel_map_align_plane(self.h, normals_ptr, points_ptr, int(n), _p(q), C.byref(prm), _p(out), C.byref(res)),
+                      "svo_voxel_map_align_plane")
+        return out, _align_result(res)
 
     def insert_keyframe_clouds(self, table, poses7):
         """The list Pipeline.keyframe_clouds() / PipelineGroup.keyframe_clouds() returns, one pose7 per entry: every entry's device

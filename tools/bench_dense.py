@@ -88,7 +88,12 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      the four counts, beside section 10's insert of the same cloud in the same run (one probe per record against 27 look-ups); and
      svo_voxel_map_align of that cloud from its pose displaced by half a voxel and 0.01 rad at the defaults: wall clock (mean of 5),
      the iterations taken, the status, and the share of the wall clock that is not inside the "voxel_align" brackets of one more run
-     (the 256-byte copies, the waits and the host solves).
+ 19. normals and the plane form of the align: on the same maps and clouds, in the same run as section 18, one
+     svo_voxel_map_normals_dev at the defaults ("voxel_normals" bracket: the counts' memset and the launch, mean of 5 after the warm-up)
+     beside the map's load factor and live voxel count; svo_voxel_map_align_plane_sums_dev at reach 0 and 1 ("voxel_align_plane"
+     bracket) with its five counts, beside section 18's point sums and section 10's insert of the same cloud; and
+     svo_voxel_map_align_plane from section 18's displaced pose: wall clock (mean of 5), iterations, status, beside section 18's
+     svo_voxel_map_align.  --align-only runs section 7's fill and sections 10, 18 and 19 alone.
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -262,7 +267,7 @@ def standalone(S, torch, batch, warmup, reps):
     return out
 
 
-def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy):
+def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy, only_align=False):
     """Section 7: the batch's clouds into one map.  Cloud i goes in under a small rotation and 0.8 m of forward motion per frame
     (the synthetic stream's step), so consecutive clouds see almost the same surfaces, as consecutive keyframes do."""
     import voxel_ref as V
@@ -326,6 +331,10 @@ def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy):
                         "extract_share_of_bound": (1e3 * 40 * vm.capacity / copy) / (ms / k)})
             out[-1].update(remove_and_move(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, copy))
             out[-1].update(align_view(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup))
+            out[-1].update(normals_view(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, out[-1]["align"]))
+            if only_align:
+                vm.close()
+                continue
             out[-1].update(grid_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # before the carve changes the map, as the render
             out[-1].update(clearance_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # of the same grid, before the carve too
             out[-1].update(route_view(S, torch, ctx, vm, np.asarray(m12[batch - 1]), warmup, copy))  # over that grid's clearance
@@ -422,7 +431,7 @@ def align_view(torch, ctx, vm, cloud, n, angle, forward, warmup):
     out.update({"loop_iterations": res["iterations"], "loop_status": res["status"], "loop_first_matched": res["first_matched"],
                 "loop_last_matched": res["last_matched"], "loop_first_cost": res["first_cost"], "loop_last_cost": res["last_cost"],
                 "loop_brackets_ms": ms, "loop_profiled_wall_ms": wall, "loop_share_outside_brackets": 1.0 - ms / wall,
-                "loop_start_shift": float(0.5 * vs * np.linalg.norm([0.6, -0.5, 0.62])),
+                "loop_start_shift": float(0.5 * vs * np.linalg.norm([0.6, -0.5, 0.62])), "loop_start_pose7": [float(v) for v in start],
                 "loop_shift_left": float(np.linalg.norm(api.pose7_to_cam_to_world(pose_out)[:, 3] - np.array([0.0, 0.0, forward])))})
     return {"align": out}
 
@@ -437,6 +446,67 @@ def align_line(k, insert_ms):
             f"{k['loop_iterations']} iterations, status {k['loop_status']}, matched {k['loop_first_matched']} -> {k['loop_last_matched']}, cost word "
             f"{k['loop_first_cost']} -> {k['loop_last_cost']}, shift left {k['loop_shift_left']:.4f}; one more run with the brackets on: {k['loop_profiled_wall_ms']:.3f} ms, "
             f"of which {k['loop_brackets_ms']:.3f} ms inside the brackets -> {100 * k['loop_share_outside_brackets']:.1f} % is the 256-byte copies, the waits and the host solves\n")
+
+
+def normals_view(torch, ctx, vm, cloud, n, angle, forward, warmup, align):
+    """Section 19 for one filled map: the normals launch at the defaults, the plane sums of the last inserted cloud under its own pose
+    at reach 0 and 1, and the plane loop from section 18's displaced pose (`align`: section 18's figures of this map).  Nothing in
+    the map changes."""
+    import voxel_ref as V
+    from stereo_vo_amd import api
+    here = V.rot_y(angle, (0.0, 0.0, forward))
+    nbuf = torch.empty(vm.capacity * 4, dtype=torch.float32, device="cuda")
+    cnt = torch.zeros(api.VOXEL_NORMALS_COUNTS, dtype=torch.int64, device="cuda")
+    sums = torch.zeros(api.VOXEL_ALIGN_PLANE_WORDS, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    p, out = cloud.data_ptr(), {"points": n, "capacity": vm.capacity}
+    for _ in range(warmup):
+        vm.normals(nbuf.data_ptr(), counts_ptr=cnt.data_ptr())
+    ctx.profile_select("voxel_normals")
+    for _ in range(5):
+        vm.normals(nbuf.data_ptr(), counts_ptr=cnt.data_ptr())
+    ms, k = ctx.profile_read()
+    ctx.profile_select("")
+    assert k == 5, k
+    out["normals_ms"] = ms / k
+    out["normals_counts"] = [int(v) for v in cnt.cpu()[:5]]
+    out["load"] = vm.stats()["n_voxels"] / vm.capacity
+    for reach in (0, 1):
+        for _ in range(warmup):
+            vm.align_plane_sums(nbuf.data_ptr(), p, n, c2w12=here, sums_ptr=sums.data_ptr(), reach=reach)
+        ctx.profile_select("voxel_align_plane")
+        for _ in range(5):
+            vm.align_plane_sums(nbuf.data_ptr(), p, n, c2w12=here, sums_ptr=sums.data_ptr(), reach=reach)
+        ms, k = ctx.profile_read()
+        ctx.profile_select("")
+        assert k == 5, k
+        out[f"sums_reach{reach}_ms"] = ms / k
+        out[f"sums_reach{reach}_counts"] = [int(v) for v in sums.cpu()[29:34]]
+    start = np.array(align["loop_start_pose7"])
+    for _ in range(warmup):
+        vm.align_plane(nbuf.data_ptr(), p, n, start)
+    t0 = time.perf_counter()
+    for _ in range(5):
+        pose_out, res = vm.align_plane(nbuf.data_ptr(), p, n, start)
+    out["loop_wall_ms"] = 1e3 * (time.perf_counter() - t0) / 5
+    out.update({"loop_iterations": res["iterations"], "loop_status": res["status"], "loop_first_matched": res["first_matched"],
+                "loop_last_matched": res["last_matched"], "loop_first_cost": res["first_cost"], "loop_last_cost": res["last_cost"],
+                "loop_shift_left": float(np.linalg.norm(api.pose7_to_cam_to_world(pose_out)[:, 3] - np.array([0.0, 0.0, forward])))})
+    return {"normals": out}
+
+
+def normals_line(k, a, insert_ms):
+    """Section 19's lines of the text report for one normals_view beside its align_view `a`."""
+    c = k['normals_counts']
+    return (f"one launch over 2^{k['capacity'].bit_length() - 1} slots at load {k['load']:.3f} (counts' memset + launch, mean of 5): {1e3 * k['normals_ms']:.1f} us, counts {c} "
+            f"(centres, valid, few, collinear, curved) -> {1e6 * k['normals_ms'] / max(c[0], 1):.2f} ns per live voxel\n"
+            f"  plane sums of the last inserted cloud ({k['points']} points) under its own pose (memset + one launch, mean of 5): reach 0 "
+            f"{1e3 * k['sums_reach0_ms']:.1f} us, counts {k['sums_reach0_counts']}; reach 1 {1e3 * k['sums_reach1_ms']:.1f} us, counts {k['sums_reach1_counts']} "
+            f"(matched, rejected, unmatched, far, no normal); plane / point sums {k['sums_reach0_ms'] / a['sums_reach0_ms']:.2f} at reach 0, "
+            f"{k['sums_reach1_ms'] / a['sums_reach1_ms']:.2f} at reach 1; plane / insert {k['sums_reach0_ms'] / insert_ms:.2f} and {k['sums_reach1_ms'] / insert_ms:.2f}\n"
+            f"  plane align from section 18's displaced pose, defaults: {k['loop_wall_ms']:.3f} ms wall clock (mean of 5), {k['loop_iterations']} iterations, status "
+            f"{k['loop_status']}, matched {k['loop_first_matched']} -> {k['loop_last_matched']}, cost word {k['loop_first_cost']} -> {k['loop_last_cost']}, shift left "
+            f"{k['loop_shift_left']:.4f}; the point form from the same pose {a['loop_wall_ms']:.3f} ms, {a['loop_iterations']} iterations, shift left {a['loop_shift_left']:.4f}\n")
 
 
 def grid_view(S, torch, ctx, vm, c2w, warmup, copy):
@@ -1367,6 +1437,7 @@ def main():
     ap.add_argument("--ledger-only", action="store_true", help="of the 96-lane loads only clouds alone and clouds with the ledger loop")
     ap.add_argument("--surface-only", action="store_true", help="section 16's seeded grids alone")
     ap.add_argument("--waypoints-only", action="store_true", help="section 17's seeded grid alone")
+    ap.add_argument("--align-only", action="store_true", help="section 7's fill and sections 10, 18 and 19 alone")
     ap.add_argument("--out", help="write the text report here as well")
     a = ap.parse_args()
     import torch
@@ -1393,6 +1464,28 @@ def main():
             with open(a.out, "w") as f:
                 for k in res["waypoint_synthetic"]:
                     f.write(f"waypoints over a synthetic {k['cells'][0]} x {k['cells'][1]} grid, blocked density {k['density']}: " + waypoint_line(k))
+        return
+    if a.align_only:
+        ctx = S.Context(W, H, max_batch=a.batch, max_corners=64, max_candidates=1 << 12, max_features=64)
+        p = S.synth_default(W, H)
+        cam = S.CameraInfo(p.focal, p.cx, p.cy, 0, 0, 0, 0, p.baseline)
+        pairs = [S.synth_render(p, i) for i in range(a.batch)]
+        dl = torch.from_numpy(np.stack([x[0] for x in pairs])).cuda()
+        dr = torch.from_numpy(np.stack([x[1] for x in pairs])).cuda()
+        dm = torch.empty((a.batch, H, W), dtype=torch.int16, device="cuda")
+        torch.cuda.synchronize()
+        copy = ctx.measure_peak("hbm_copy")
+        ctx.stereo_bm_batch(dl.data_ptr(), dr.data_ptr(), a.batch, W, H, W, W * H, dm.data_ptr(), NDISP, BLOCK)
+        ctx.sync()
+        res = {"hbm_copy_bytes_per_s": copy, "voxel": voxel(S, torch, ctx, cam, dm, dl, a.batch, 3, copy, only_align=True)}
+        ctx.close()
+        print(json.dumps(res))
+        if a.out:
+            with open(a.out, "w") as f:
+                for c in res["voxel"]:
+                    f.write(f"voxel map, clouds at step {c['cloud_step']} ({c['points_per_cloud']:.0f} points per cloud), voxel {c['voxel_size']} m, 2^{c['capacity_log2']} slots, "
+                            f"{c['stats_after_fresh']['n_voxels']} voxels, load {c['load']:.3f}:\n  align: " + align_line(c['align'], c['insert_ms']) +
+                            "  normals: " + normals_line(c['normals'], c['align'], c['insert_ms']))
         return
     res = {"standalone": standalone(S, torch, a.batch, 3, a.reps)}
     print("bench_dense: standalone sections done", file=sys.stderr, flush=True)
@@ -1492,7 +1585,8 @@ def main():
                         f"{c['move_counts']}; the same cloud inserted once more, same run: {1e3 * c['insert_ms']:.1f} us -> removal / insert "
                         f"{c['remove_ms'] / c['insert_ms']:.2f}, move / insert {c['move_ms'] / c['insert_ms']:.2f}; 16 B per record at hbm_copy "
                         f"{1e3 * c['remove_move_bound_ms']:.2f} us\n"
-                        "  align: " + align_line(c['align'], c['insert_ms']))
+                        "  align: " + align_line(c['align'], c['insert_ms']) +
+                        "  normals: " + normals_line(c['normals'], c['align'], c['insert_ms']))
             for k in s["clearance_synthetic"]:
                 f.write(f"clearance of a synthetic {k['cells'][0]} x {k['cells'][1]} grid, source density {k['density']}, max_dist {k['max_dist']} (all four outputs, mean of 5): "
                         f"{1e3 * k['ms']:.1f} us, counts {k['counts']} (sources, reached, unreached, blocked); 22 B per cell at hbm_copy {1e3 * k['bound_ms']:.1f} us -> "
