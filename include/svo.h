@@ -107,7 +107,10 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * memset and every launch), "grid_view" (one svo_grid_view_dev: its two memsets and both launches), "grid_surface" (one svo_grid_surface_dev: the
  * counts' memset and the launch), "grid_waypoints" (one svo_grid_waypoints_dev: the counts' memset and the launch),
  * "voxel_align" (one svo_voxel_map_align_sums_dev: the sums' memset and the launch; svo_voxel_map_align is one bracket per
- * iteration); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
+ * iteration), "voxel_normals" (one svo_voxel_map_normals_dev), "voxel_align_plane" (one svo_voxel_map_align_plane_sums_dev),
+ * "voxel_occupancy" (one svo_voxel_map_occupancy_dev: its two memsets and the launch), "voxel_locate" (one
+ * svo_voxel_map_locate_scores_dev: its memsets, the score launches and the best launch; the occupancy launch and the
+ * refinements inside svo_voxel_map_locate count under their own tags); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
 /* Measurement aid: the card's own ceilings for the roofline objects (SURVEY 8d asks for a measured FP64 figure).
@@ -842,6 +845,123 @@ int svo_voxel_map_align_plane_sums_pose7_dev(svo_voxel_map* map, const svo_voxel
 int svo_voxel_map_align_plane(svo_voxel_map* map, const svo_voxel_normal* normals, const svo_cloud_point* points, int n,
                               const double* pose7_in, const svo_voxel_align_params* params, double* pose7_out,
                               svo_voxel_align_result* result);
+
+/* Voxel map locate: the coarse stage in front of the align.  The align's basin is one voxel wide; this searches a box
+ * of whole-voxel shifts and a fan of turns about one world axis for the pose under which most records of a cloud land in live
+ * voxels, and hands the peak to the align.  Three parts: a dense bit volume of the map, the scores, and a host loop.  Integer work
+ * throughout: a restatement in another language gives the same words.
+ *
+ * Occupancy volume (svo_voxel_map_occupancy_dev; also of use alone, for 3D collision tests).  Inputs: min_count >= 1; origin[3],
+ * int32 voxel indices, each in [-2^20, 2^20); dims[3] = (d0, d1, d2), each in 1..2048, d0 a multiple of 64, d0*d1*d2 <= 2^30;
+ * bits, DEVICE, 8-byte aligned, d0*d1*d2/8 bytes (svo_voxel_occupancy_bytes); counts, 2 DEVICE u32, 4-byte aligned.
+ *   The voxel with indices i has j_r = i_r - origin_r and is INSIDE iff 0 <= j_r < d_r for all r.  Its bit number is
+ *   B = j_0 + d0*(j_1 + d1*j_2), in the little-endian u64 word B >> 6 at bit B & 63.  The bit is 1 iff a slot holds that key and
+ *   ci >> 40 >= min_count; carved slots are 0.  counts = {n_inside, n_outside} over the qualifying slots.  One memset of the volume
+ *   and one of the counts, then one walk over the table with one thread per slot: a load decides, nothing is claimed, the bits are
+ *   set by relaxed atomicOr and the counts added by relaxed atomicAdd (one per workgroup and non-zero count).  No byte of the table
+ *   and no map counter changes.  Profile tag "voxel_occupancy".
+ *   Refusals, in this order: a null map; min_count < 1; null origin; an origin_r outside [-2^20, 2^20); null dims; a d_r outside
+ *   1..2048; d0 not a multiple of 64; d0*d1*d2 > 2^30; null bits; bits not 8-byte aligned; null counts; counts not 4-byte aligned.
+ *
+ * Scores (svo_voxel_map_locate_scores_dev).  Inputs: the map (read for voxel_size and max_depth ONLY: the table is not touched);
+ * bits, origin, dims as above; n <= 2^20 records at a DEVICE pointer; K camera->world matrices, 1 <= K <= 63, as K*12 HOST doubles
+ * (they travel as kernel arguments, at most 32 candidates per launch: K > 32 takes two score launches); box[3] = (r0, r1, r2), each
+ * in 0..16, S_r = 2 r_r + 1; hits, DEVICE u32, K*S0*S1*S2 words, 4-byte aligned; best, K DEVICE svo_voxel_locate_best, 8-byte
+ * aligned.  Per candidate k and record:
+ *   1. Rejected (n_rejected[k] = n - n_used[k]) iff item 1 of the voxel map rejects it, or any of |x|, |y|, |z| fails < 1024.0f, or,
+ *      with w_r and q_r exactly as item 2 of the voxel map under m_k, any q_r fails q_r >= -1048560.0 && q_r < 1048560.0: sixteen
+ *      voxels inside the key range, whatever the box.
+ *   2. j_r = floor(q_r) - origin_r.  A record that is not rejected counts in n_used[k], and in n_inside[k] iff j is inside.
+ *   3. For every shift s with |s_r| <= r_r, c = j + s.  The record is a HIT iff c is inside the volume and its bit is 1; a c outside
+ *      is never a hit.  hits[k*S0*S1*S2 + (s_2 + r2)*S1*S0 + (s_1 + r1)*S0 + (s_0 + r0)] is the number of hits: records count with
+ *      multiplicity, at most 2^20.  Shift s means the cloud moved by s * voxel_size in the world.
+ *   4. best[k] = {hits_max, s0, s1, s2, n_used, n_inside, index, 0}: hits_max the largest score of k, index the SMALLEST linear
+ *      index inside k's block that holds it, s that index's shift.  All scores zero: index 0.
+ *   hits and best are written in full by every call; n == 0 zeroes hits and writes the all-zero best with shift (-r0, -r1, -r2).
+ *   Integer sums commute: nothing depends on thread order.  Relaxed device-scope atomics only, no fence, no waiting on another
+ *   workgroup.  Profile tag "voxel_locate": one bracket over the memsets, the score launches and the best launch.
+ *   Refusals, in this order: a null map; n < 0; n > 2^20; null mats; K outside 1..63; null box; a box_r outside 0..16; the origin
+ *   and dims refusals above; null bits; bits not 8-byte aligned; null hits; hits not 4-byte aligned; null best; best not 8-byte
+ *   aligned; and with n > 0 null points, then points not 4-byte aligned.
+ *
+ * The host loop (svo_voxel_map_locate; host/voxel_locate.h; only + - * / and sqrt on doubles in the written order, and NO
+ * trigonometric function):
+ *   a. In.  u, T from pose7_in by the align's step a.
+ *   b. Candidates.  K = 2 n_turn + 1; candidate k has j = k - n_turn and b = ((double)j * (double)turn_step) / 2.  a = (1, b e_axis)
+ *      / sqrt(1 + b*b), that is a_0 = 1 / nrm, a_axis = b / nrm, the other two 0.  u_k = a (x) u, the turn on the WORLD side, about
+ *      the world axis through the camera centre: w = a_0*u_0 - a_1*u_1 - a_2*u_2 - a_3*u_3; x = a_0*u_1 + a_1*u_0 + a_2*u_3 - a_3*u_2;
+ *      y = a_0*u_2 - a_1*u_3 + a_2*u_0 + a_3*u_1; z = a_0*u_3 + a_1*u_2 - a_2*u_1 + a_3*u_0, each left to right; then the align's
+ *      normalisation with its first-order correction (step e).  m_k = [R(u_k) | T].  The angle of candidate k is 2 atan(b), NOT
+ *      j * turn_step: the two differ by a factor 1 - b*b/3 + ..., 0.1 % at the default fan's end.
+ *   c. Volume.  origin_r = (int)floor(T_r / (double)voxel_size) - d_r / 2 (integer division).  Refused with SVO_ERR_INVALID if a
+ *      floor is not within +-2^21 or an origin_r or origin_r + d_r leaves [-2^20, 2^20].  The volume, the counts, the scores and
+ *      the bests live in the CALLER's workspace (DEVICE, 256-byte aligned, svo_voxel_locate_workspace_bytes): nothing is allocated.
+ *   d. One occupancy launch, one scores call, one copy of K*32 bytes to the host.
+ *   e. Rank by descending hits_max, ties by ascending k; candidates with hits_max < min_hits are dropped.  None left:
+ *      SVO_VOXEL_LOCATE_NO_CANDIDATE, pose7_out = pose7_in bit for bit (k = -1, rank = -1, coarse_pose7 = pose7_in, the rest 0).
+ *   f. Each of the first n_refine ranked candidates: (u_k, T_r + (double)s_r * (double)voxel_size) through the align's step g to a
+ *      pose7 (its coarse pose), then svo_voxel_map_align_plane if normals were given, else svo_voxel_map_align, with align_params.
+ *   g. Eligible: refinements that ended CONVERGED or MAX_ITERS.  The largest last_matched wins, ties by the smallest last_cost, then
+ *      by the earlier rank: SVO_VOXEL_LOCATE_FOUND, pose7_out the refined pose.  None eligible: SVO_VOXEL_LOCATE_UNREFINED, pose7_out
+ *      the coarse pose of rank 0 and the result that of rank 0.
+ *   Refusals, in this order: a null map; n < 0; n > 2^20; null pose7_in; null pose7_out; null result; null params; min_count < 1;
+ *   up_axis outside 0..2; n_turn outside 0..31; turn_step not finite or outside (0, 0.25]; a box_r outside 0..16; the dims
+ *   refusals of the occupancy; n_refine outside 1..63; min_hits < 1; the align's params refusals; null workspace; workspace not
+ *   256-byte aligned; normals not 16-byte aligned; with n > 0 null points, then points not 4-byte aligned; then step c's.
+ * The defaults are NOT tuned on real imagery.  Order of use: normals if wanted, then locate, then the cloud's own insert: locate
+ * BEFORE inserting the cloud, as for the align.  The pipeline never locates by itself. */
+typedef struct svo_voxel_locate_best {
+  uint32_t hits_max;
+  int32_t s0, s1, s2;
+  uint32_t n_used, n_inside, index, zero;
+} svo_voxel_locate_best; /* 32 bytes */
+typedef struct svo_voxel_locate_params {
+  int min_count;   /* >= 1: of the occupancy volume */
+  int up_axis;     /* 0..2: the world axis the candidates turn about */
+  int n_turn;      /* 0..31: K = 2 n_turn + 1 candidates */
+  float turn_step; /* finite, in (0, 0.25]: b = j * turn_step / 2, the angle is 2 atan(b) */
+  int box[3];      /* each 0..16: whole-voxel shifts |s_r| <= box_r */
+  int dims[3];     /* the volume around the prior: each 1..2048, dims[0] a multiple of 64, product <= 2^30 */
+  int n_refine;    /* 1..63: ranked candidates handed to the align */
+  int min_hits;    /* >= 1: candidates whose peak is below this are dropped */
+} svo_voxel_locate_params;
+enum { SVO_VOXEL_LOCATE_FOUND = 0, SVO_VOXEL_LOCATE_UNREFINED = 1, SVO_VOXEL_LOCATE_NO_CANDIDATE = 2 };
+#define SVO_VOXEL_LOCATE_MAX_K 63
+#define SVO_VOXEL_LOCATE_MAX_BOX 16
+typedef struct svo_voxel_locate_result {
+  int status;        /* SVO_VOXEL_LOCATE_* */
+  int k;             /* the chosen candidate */
+  int shift[3];      /* its peak's shift, in voxels */
+  uint32_t hits;     /* its peak */
+  int rank;          /* its place in step e's order */
+  int n_refined;     /* refinements run */
+  double coarse_pose7[7];
+  svo_voxel_align_result align; /* the chosen refinement's */
+} svo_voxel_locate_result;
+/* Bytes of a volume: d0*d1*d2/8.  Pure; SVO_ERR_INVALID and *bytes = 0 for dims the occupancy refuses. */
+int svo_voxel_occupancy_bytes(const int* dims3, size_t* bytes);
+/* Asynchronous on svo_stream(ctx): two memsets and one launch, one "voxel_occupancy" profile bracket. */
+int svo_voxel_map_occupancy_dev(svo_voxel_map* map, int min_count, const int* origin3, const int* dims3, uint64_t* bits, uint32_t* counts);
+/* svo_voxel_map_occupancy_dev into device memory of its own, copied to the HOST; synchronous; allocates and frees.  host_bits:
+ * svo_voxel_occupancy_bytes bytes (any alignment); host_counts: 2 words, or NULL. */
+int svo_voxel_map_occupancy(svo_voxel_map* map, int min_count, const int* origin3, const int* dims3, uint64_t* host_bits,
+                            uint32_t* host_counts);
+/* Asynchronous on svo_stream(ctx); one "voxel_locate" profile bracket. */
+int svo_voxel_map_locate_scores_dev(svo_voxel_map* map, const uint64_t* bits, const int* origin3, const int* dims3,
+                                    const svo_cloud_point* points, int n, const double* mats, int K, const int* box3, uint32_t* hits,
+                                    svo_voxel_locate_best* best);
+/* min_count 1, up_axis 1, n_turn 4, turn_step 0.04, box (8, 4, 8), dims (512, 128, 512) (4 MB), n_refine 3, min_hits 64.  NOT
+ * tuned on real imagery.  Pure; SVO_ERR_INVALID for null params or a voxel_size that is not finite and > 0 (the voxel size is taken
+ * for the day the defaults depend on it; today they do not). */
+int svo_voxel_locate_default_params(float voxel_size, svo_voxel_locate_params* params);
+/* Bytes of the loop's workspace: the volume, the counts, K*S0*S1*S2 scores and K bests, each part rounded up to 256 bytes.  Pure;
+ * SVO_ERR_INVALID and *bytes = 0 for params the loop refuses. */
+int svo_voxel_locate_workspace_bytes(const svo_voxel_locate_params* params, size_t* bytes);
+/* The host loop above, synchronous.  normals: the DEVICE array of svo_voxel_map_normals_dev (plane form of the refinement), or NULL
+ * (point form).  pose7_in, pose7_out (may be the same array) and result on the HOST. */
+int svo_voxel_map_locate(svo_voxel_map* map, const svo_voxel_normal* normals, const svo_cloud_point* points, int n,
+                         const double* pose7_in, const svo_voxel_locate_params* params, const svo_voxel_align_params* align_params,
+                         void* workspace, double* pose7_out, svo_voxel_locate_result* result);
 
 /* Voxel map grid: the ground plan of the map, an axis-aligned na x nb grid over two of the map's axes.  Per cell: the highest and
  * the lowest surface inside a height band, the mean intensity of the highest voxel, how many voxels and points fell into the cell,

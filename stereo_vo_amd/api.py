@@ -310,6 +310,58 @@ def voxel_map_normals_bytes(params):
     return int(n.value)
 
 
+class VoxelLocateParams(C.Structure):
+    """svo_voxel_locate_params: min_count (>= 1), up_axis (0..2), n_turn (0..31), turn_step (finite, in (0, 0.25]), box[3] (each
+    0..16), dims[3] (each 1..2048, dims[0] a multiple of 64, product <= 2^30), n_refine (1..63), min_hits (>= 1)."""
+    _fields_ = [("min_count", C.c_int), ("up_axis", C.c_int), ("n_turn", C.c_int), ("turn_step", C.c_float), ("box", C.c_int * 3),
+                ("dims", C.c_int * 3), ("n_refine", C.c_int), ("min_hits", C.c_int)]
+
+
+class VoxelLocateResult(C.Structure):
+    """svo_voxel_locate_result."""
+    _fields_ = [("status", C.c_int), ("k", C.c_int), ("shift", C.c_int * 3), ("hits", C.c_uint32), ("rank", C.c_int), ("n_refined", C.c_int),
+                ("coarse_pose7", C.c_double * 7), ("align", VoxelAlignResult)]
+
+
+VoxelLocateBest = np.dtype([("hits_max", np.uint32), ("s0", np.int32), ("s1", np.int32), ("s2", np.int32), ("n_used", np.uint32),
+                            ("n_inside", np.uint32), ("index", np.uint32), ("zero", np.uint32)])  # svo_voxel_locate_best, 32 bytes
+VOXEL_LOCATE_STATUS = ("FOUND", "UNREFINED", "NO_CANDIDATE")  # SVO_VOXEL_LOCATE_*, by value
+VOXEL_LOCATE_CHUNK = 1024  # records per workgroup of the score launch (host/voxel_locate.h): the tests straddle it
+OCCUPANCY_COUNTS = ("n_inside", "n_outside")
+
+
+def _int3(v):
+    a = np.ascontiguousarray(v, dtype=np.int32)
+    if a.shape != (3,):
+        raise ValueError("three integers wanted")
+    return a
+
+
+def voxel_locate_default_params(voxel_size):
+    """svo_voxel_locate_default_params: min_count 1, up_axis 1, n_turn 4, turn_step 0.04, box (8, 4, 8), dims (512, 128, 512),
+    n_refine 3, min_hits 64 (not tuned on real imagery)."""
+    p = VoxelLocateParams()
+    if lib().svo_voxel_locate_default_params(C.c_float(voxel_size), C.byref(p)) != 0:
+        raise SvoError("svo_voxel_locate_default_params: voxel_size must be finite and > 0")
+    return p
+
+
+def voxel_locate_workspace_bytes(params):
+    """svo_voxel_locate_workspace_bytes: bytes of the workspace VoxelMap.locate wants (no GPU involved); params: a VoxelLocateParams."""
+    n = C.c_size_t(0)
+    if lib().svo_voxel_locate_workspace_bytes(C.byref(params), C.byref(n)) != 0:
+        raise SvoError("svo_voxel_locate_workspace_bytes: parameters svo_voxel_map_locate refuses")
+    return int(n.value)
+
+
+def voxel_occupancy_bytes(dims):
+    """svo_voxel_occupancy_bytes: bytes of an occupancy volume of dims = (d0, d1, d2) voxels, one bit each (no GPU involved)."""
+    n = C.c_size_t(0)
+    if lib().svo_voxel_occupancy_bytes(_p(_int3(dims)), C.byref(n)) != 0:
+        raise SvoError("svo_voxel_occupancy_bytes: each dimension in 1..2048, dims[0] a multiple of 64, the product at most 2^30")
+    return int(n.value)
+
+
 class VoxelGridParams(C.Structure):
     """svo_voxel_grid_params: up_axis (0..2), up_sign (+1 / -1), the corner of cell (0, 0) in map units, voxels per cell edge
     (1..1024), na x nb cells (each 1..8192, na*nb <= 2^24), the height band, the span beyond which a cell is an obstacle, min_count."""
@@ -787,6 +839,8 @@ SYMBOLS = [
     "svo_voxel_align_default_params", "svo_voxel_map_align_sums_dev", "svo_voxel_map_align_sums_pose7_dev", "svo_voxel_map_align",
     "svo_voxel_normals_default_params", "svo_voxel_map_normals_bytes", "svo_voxel_map_normals_dev", "svo_voxel_map_normals",
     "svo_voxel_map_align_plane_sums_dev", "svo_voxel_map_align_plane_sums_pose7_dev", "svo_voxel_map_align_plane",
+    "svo_voxel_occupancy_bytes", "svo_voxel_map_occupancy_dev", "svo_voxel_map_occupancy", "svo_voxel_map_locate_scores_dev",
+    "svo_voxel_locate_default_params", "svo_voxel_locate_workspace_bytes", "svo_voxel_map_locate",
 ]
 
 
@@ -991,6 +1045,17 @@ def lib():
         L.svo_voxel_map_align_plane.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp]
         for f in ("svo_voxel_normals_default_params", "svo_voxel_map_normals_bytes", "svo_voxel_map_normals_dev", "svo_voxel_map_normals",
                   "svo_voxel_map_align_plane_sums_dev", "svo_voxel_map_align_plane_sums_pose7_dev", "svo_voxel_map_align_plane"):
+            getattr(L, f).restype = ci
+        # the occupancy volume and the locate
+        L.svo_voxel_occupancy_bytes.argtypes = [vp, vp]
+        L.svo_voxel_map_occupancy_dev.argtypes = [vp, ci, vp, vp, vp, vp]
+        L.svo_voxel_map_occupancy.argtypes = [vp, ci, vp, vp, vp, vp]
+        L.svo_voxel_map_locate_scores_dev.argtypes = [vp, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp]
+        L.svo_voxel_locate_default_params.argtypes = [C.c_float, vp]
+        L.svo_voxel_locate_workspace_bytes.argtypes = [vp, vp]
+        L.svo_voxel_map_locate.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+        for f in ("svo_voxel_occupancy_bytes", "svo_voxel_map_occupancy_dev", "svo_voxel_map_occupancy", "svo_voxel_map_locate_scores_dev",
+                  "svo_voxel_locate_default_params", "svo_voxel_locate_workspace_bytes", "svo_voxel_map_locate"):
             getattr(L, f).restype = ci
         _LIB = L
     return _LIB
@@ -1738,6 +1803,48 @@ class VoxelMap:
         self.ctx._chk(self.L.svo_voxel_map_align_plane(self.h, normals_ptr, points_ptr, int(n), _p(q), C.byref(prm), _p(out), C.byref(res)),
                       "svo_voxel_map_align_plane")
         return out, _align_result(res)
+
+    def occupancy(self, bits_ptr, origin, dims, min_count=1, counts_ptr=None):
+        """svo_voxel_map_occupancy_dev: the dense bit volume of the map's voxels with at least min_count points, dims = (d0, d1, d2)
+        voxels from the voxel indices origin, into the voxel_occupancy_bytes(dims) bytes at the device pointer bits_ptr (8-byte
+        aligned): voxel i is bit j_0 + d0 (j_1 + d1 j_2), j = i - origin, of little-endian u64 words.  counts_ptr: 2 uint32 on the
+        device (OCCUPANCY_COUNTS).  Nothing in the map changes.  Asynchronous on the context's stream."""
+        self.ctx._chk(self.L.svo_voxel_map_occupancy_dev(self.h, int(min_count), _p(_int3(origin)), _p(_int3(dims)), bits_ptr, counts_ptr),
+                      "svo_voxel_map_occupancy_dev")
+
+    def occupancy_host(self, origin, dims, min_count=1):
+        """svo_voxel_map_occupancy: occupancy() into memory of its own, synchronous.  Returns (the volume's uint64 words,
+        {"n_inside", "n_outside"})."""
+        bits, c = np.empty(voxel_occupancy_bytes(dims) // 8, np.uint64), np.zeros(2, np.uint32)
+        self.ctx._chk(self.L.svo_voxel_map_occupancy(self.h, int(min_count), _p(_int3(origin)), _p(_int3(dims)), _p(bits), _p(c)), "svo_voxel_map_occupancy")
+        return bits, dict(zip(OCCUPANCY_COUNTS, (int(v) for v in c)))
+
+    def locate_scores(self, bits_ptr, origin, dims, points_ptr, n, mats, box, hits_ptr=None, best_ptr=None):
+        """svo_voxel_map_locate_scores_dev: for each of the K camera->world matrices mats (K x 12 doubles, K <= 63) and every
+        whole-voxel shift |s_r| <= box_r (<= 16), how many of the n records land in a set bit of the volume occupancy() wrote:
+        K * S0 * S1 * S2 uint32 at the device pointer hits_ptr and K VoxelLocateBest records at best_ptr (include/svo.h, "Voxel map
+        locate").  Asynchronous on the context's stream."""
+        m = _f64(mats).reshape(-1, 12)
+        self.ctx._chk(self.L.svo_voxel_map_locate_scores_dev(self.h, bits_ptr, _p(_int3(origin)), _p(_int3(dims)), points_ptr, int(n), _p(m), len(m),
+                                                             _p(_int3(box)), hits_ptr, best_ptr), "svo_voxel_map_locate_scores_dev")
+
+    def locate(self, points_ptr, n, pose7, params=None, align_params=None, normals_ptr=None, workspace_ptr=None, **overrides):
+        """svo_voxel_map_locate: search a box of whole-voxel shifts and a fan of turns about one world axis for the cloud's pose, then
+        refine the best candidates with align() (align_plane() if normals_ptr is given); synchronous.  workspace_ptr: a device
+        pointer, 256-byte aligned, voxel_locate_workspace_bytes(params) bytes.  params: a VoxelLocateParams and / or its fields as
+        keywords; align_params: a VoxelAlignParams (default: voxel_align_default_params).  Locate BEFORE inserting the cloud.
+        Returns (pose7_out, {"status", "k", "shift", "hits", "rank", "n_refined", "coarse_pose7", "align"})."""
+        threes = {k: overrides.pop(k) for k in ("box", "dims") if overrides.get(k) is not None}
+        prm = _params(lambda: voxel_locate_default_params(self.params.voxel_size), params, **overrides)
+        for k, v in threes.items():
+            setattr(prm, k, (C.c_int * 3)(*(int(x) for x in v)))
+        ap = _params(lambda: voxel_align_default_params(self.params.voxel_size), align_params)
+        q = _f64(pose7).reshape(7)
+        out, res = np.empty(7, np.float64), VoxelLocateResult()
+        self.ctx._chk(self.L.svo_voxel_map_locate(self.h, normals_ptr, points_ptr, int(n), _p(q), C.byref(prm), C.byref(ap), workspace_ptr, _p(out),
+                                                  C.byref(res)), "svo_voxel_map_locate")
+        return out, {"status": VOXEL_LOCATE_STATUS[res.status], "k": res.k, "shift": tuple(res.shift), "hits": int(res.hits), "rank": res.rank,
+                     "n_refined": res.n_refined, "coarse_pose7": np.array(list(res.coarse_pose7), np.float64), "align": _align_result(res.align)}
 
     def insert_keyframe_clouds(self, table, poses7):
         """The list Pipeline.keyframe_clouds() / PipelineGroup.keyframe_clouds() returns, one pose7 per entry: every entry's device

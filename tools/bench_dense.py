@@ -94,6 +94,14 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      bracket) with its five counts, beside section 18's point sums and section 10's insert of the same cloud; and
      svo_voxel_map_align_plane from section 18's displaced pose: wall clock (mean of 5), iterations, status, beside section 18's
      svo_voxel_map_align.  --align-only runs section 7's fill and sections 10, 18 and 19 alone.
+ 20. locate: on the same maps and clouds, in the same run as sections 7, 18 and 19, one svo_voxel_map_occupancy_dev at the default
+     dims around the last cloud's pose ("voxel_occupancy" bracket, mean of 5) beside section 7's extraction walk of the same table;
+     one svo_voxel_map_locate_scores_dev of the last inserted cloud over the nine default candidates at box (8, 4, 8) and at
+     (16, 4, 16) ("voxel_locate" bracket, mean of 5), as us and as occupancy tests per second (n * K * |box| per call), beside
+     section 18's reach-1 sums of the same cloud as look-ups per second (27 n per call); and svo_voxel_map_locate (point and plane
+     form) from the cloud's pose moved by (5.3, -1.7, 4.2) voxels and turned by 0.11 rad about the world's y: wall clock (mean of 5),
+     status, chosen candidate and the shift left.  A library built with -DSVO_EXP_LOCATE_BASELINE (SVO_EXTRA_HIPFLAGS) runs the same
+     section with the baseline form of the score kernel.  --align-only runs this section too.
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -332,6 +340,7 @@ def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy, only_align=False):
             out[-1].update(remove_and_move(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, copy))
             out[-1].update(align_view(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup))
             out[-1].update(normals_view(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, out[-1]["align"]))
+            out[-1].update(locate_view(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, out[-1]["align"], out[-1]["extract_ms"]))
             if only_align:
                 vm.close()
                 continue
@@ -493,6 +502,91 @@ def normals_view(torch, ctx, vm, cloud, n, angle, forward, warmup, align):
                 "loop_last_matched": res["last_matched"], "loop_first_cost": res["first_cost"], "loop_last_cost": res["last_cost"],
                 "loop_shift_left": float(np.linalg.norm(api.pose7_to_cam_to_world(pose_out)[:, 3] - np.array([0.0, 0.0, forward])))})
     return {"normals": out}
+
+
+def locate_view(torch, ctx, vm, cloud, n, angle, forward, warmup, align, extract_ms):
+    """Section 20 for one filled map (`align`: section 18's figures of this map).  Nothing in the map changes."""
+    import voxel_locate_ref as L
+    import voxel_ref as V
+    from stereo_vo_amd import api
+    vs = float(vm.params.voxel_size)
+    c, sn = np.cos(angle / 2), np.sin(angle / 2)
+    R = np.asarray(V.rot_y(angle, (0.0, 0.0, forward))).reshape(3, 4)[:, :3]
+    pose = np.concatenate([[c, 0.0, -sn, 0.0], -R.T @ np.array([0.0, 0.0, forward])])
+    prm = api.voxel_locate_default_params(vs)
+    ref = L.default_params()
+    T, _, mats = L.candidates(pose, ref)
+    origin = L.origin_of(T, vs, ref.dims)
+    ws = torch.empty(api.voxel_locate_workspace_bytes(prm) + 256, dtype=torch.uint8, device="cuda")
+    bits = torch.empty(api.voxel_occupancy_bytes(ref.dims) // 8, dtype=torch.int64, device="cuda")
+    cnt = torch.zeros(2, dtype=torch.int32, device="cuda")
+    best = torch.zeros(9 * 8, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    p, out = cloud.data_ptr(), {"points": n, "capacity": vm.capacity, "extract_ms": extract_ms, "dims": list(ref.dims), "K": len(mats)}
+    for _ in range(warmup):
+        vm.occupancy(bits.data_ptr(), origin, ref.dims, counts_ptr=cnt.data_ptr())
+    ctx.profile_select("voxel_occupancy")
+    for _ in range(5):
+        vm.occupancy(bits.data_ptr(), origin, ref.dims, counts_ptr=cnt.data_ptr())
+    ms, k = ctx.profile_read()
+    ctx.profile_select("")
+    assert k == 5, k
+    out["occupancy_ms"] = ms / k
+    out["occupancy_counts"] = [int(v) for v in cnt.cpu()]
+    for box in ((8, 4, 8), (16, 4, 16)):
+        shifts = (2 * box[0] + 1) * (2 * box[1] + 1) * (2 * box[2] + 1)
+        hits = torch.zeros(len(mats) * shifts, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        call = lambda: vm.locate_scores(bits.data_ptr(), origin, ref.dims, p, n, np.array(mats), box, hits_ptr=hits.data_ptr(), best_ptr=best.data_ptr())
+        for _ in range(warmup):
+            call()
+        ctx.profile_select("voxel_locate")
+        for _ in range(5):
+            call()
+        ms, k = ctx.profile_read()
+        ctx.profile_select("")
+        assert k == 5, k
+        b = best.cpu().numpy().view(L.BEST)
+        tag = "x".join(str(v) for v in box)
+        out[f"scores_{tag}_ms"] = ms / k
+        out[f"scores_{tag}_tests_per_s"] = n * len(mats) * shifts / (1e-3 * ms / k)
+        out[f"scores_{tag}_best"] = [int(b["hits_max"][4]), int(b["s0"][4]), int(b["s1"][4]), int(b["s2"][4]), int(b["n_used"][4]), int(b["n_inside"][4])]
+    out["align_lookups_per_s"] = 27 * n / (1e-3 * align["sums_reach1_ms"])
+    start = np.array(L.start_pose(pose, [5.3 * vs, -1.7 * vs, 4.2 * vs], 0.11))
+    wptr = (ws.data_ptr() + 255) & ~255
+    nbuf = torch.empty(vm.capacity * 4, dtype=torch.float32, device="cuda")
+    vm.normals(nbuf.data_ptr())
+    ctx.sync()
+    for name, nptr in (("point", None), ("plane", nbuf.data_ptr())):
+        for _ in range(warmup):
+            vm.locate(p, n, start, normals_ptr=nptr, workspace_ptr=wptr)
+        t0 = time.perf_counter()
+        for _ in range(5):
+            pose_out, res = vm.locate(p, n, start, normals_ptr=nptr, workspace_ptr=wptr)
+        out[f"locate_{name}_wall_ms"] = 1e3 * (time.perf_counter() - t0) / 5
+        out[f"locate_{name}"] = {"status": res["status"], "k": res["k"], "shift": list(res["shift"]), "hits": res["hits"], "rank": res["rank"],
+                                 "align_status": res["align"]["status"], "align_iterations": res["align"]["iterations"],
+                                 "shift_left": float(np.linalg.norm(api.pose7_to_cam_to_world(pose_out)[:, 3] - np.array([0.0, 0.0, forward])))}
+    out["locate_start_shift"] = float(vs * np.linalg.norm([5.3, -1.7, 4.2]))
+    return {"locate": out}
+
+
+def locate_line(k, a):
+    """Section 20's lines of the text report for one locate_view beside its align_view `a`."""
+    s = ""
+    for tag in ("8x4x8", "16x4x16"):
+        s += (f"; box {tag.replace('x', ', ')}: {1e3 * k['scores_' + tag + '_ms']:.1f} us, {k['scores_' + tag + '_tests_per_s'] / 1e9:.1f} G tests/s, "
+              f"identity candidate {k['scores_' + tag + '_best']}")
+    out = (f"occupancy of 2^{k['capacity'].bit_length() - 1} slots into {k['dims']} (two memsets + launch, mean of 5): {1e3 * k['occupancy_ms']:.1f} us, counts "
+           f"{k['occupancy_counts']} (inside, outside); the same run's extraction walk {1e3 * k['extract_ms']:.1f} us -> {k['occupancy_ms'] / k['extract_ms']:.2f}\n"
+           f"  scores of the last inserted cloud ({k['points']} points), {k['K']} candidates (memsets + score launch + best launch, mean of 5; hits_max, shift, n_used, "
+           f"n_inside){s}; the same run's reach-1 align sums {1e3 * a['sums_reach1_ms']:.1f} us = {k['align_lookups_per_s'] / 1e9:.2f} G look-ups/s\n")
+    for name in ("point", "plane"):
+        r = k["locate_" + name]
+        out += (f"  locate ({name} form) from that pose moved by {k['locate_start_shift']:.3f} and 0.11 rad, defaults: {k['locate_' + name + '_wall_ms']:.3f} ms wall clock (mean of 5), "
+                f"{r['status']}, candidate {r['k']} shift {r['shift']} hits {r['hits']} rank {r['rank']}, refinement {r['align_status']} after {r['align_iterations']} iterations, "
+                f"shift left {r['shift_left']:.4f}\n")
+    return out
 
 
 def normals_line(k, a, insert_ms):
@@ -1437,7 +1531,7 @@ def main():
     ap.add_argument("--ledger-only", action="store_true", help="of the 96-lane loads only clouds alone and clouds with the ledger loop")
     ap.add_argument("--surface-only", action="store_true", help="section 16's seeded grids alone")
     ap.add_argument("--waypoints-only", action="store_true", help="section 17's seeded grid alone")
-    ap.add_argument("--align-only", action="store_true", help="section 7's fill and sections 10, 18 and 19 alone")
+    ap.add_argument("--align-only", action="store_true", help="section 7's fill and sections 10, 18, 19 and 20 alone")
     ap.add_argument("--out", help="write the text report here as well")
     a = ap.parse_args()
     import torch
@@ -1485,7 +1579,7 @@ def main():
                 for c in res["voxel"]:
                     f.write(f"voxel map, clouds at step {c['cloud_step']} ({c['points_per_cloud']:.0f} points per cloud), voxel {c['voxel_size']} m, 2^{c['capacity_log2']} slots, "
                             f"{c['stats_after_fresh']['n_voxels']} voxels, load {c['load']:.3f}:\n  align: " + align_line(c['align'], c['insert_ms']) +
-                            "  normals: " + normals_line(c['normals'], c['align'], c['insert_ms']))
+                            "  normals: " + normals_line(c['normals'], c['align'], c['insert_ms']) + "  locate: " + locate_line(c['locate'], c['align']))
         return
     res = {"standalone": standalone(S, torch, a.batch, 3, a.reps)}
     print("bench_dense: standalone sections done", file=sys.stderr, flush=True)
@@ -1586,7 +1680,7 @@ def main():
                         f"{c['remove_ms'] / c['insert_ms']:.2f}, move / insert {c['move_ms'] / c['insert_ms']:.2f}; 16 B per record at hbm_copy "
                         f"{1e3 * c['remove_move_bound_ms']:.2f} us\n"
                         "  align: " + align_line(c['align'], c['insert_ms']) +
-                        "  normals: " + normals_line(c['normals'], c['align'], c['insert_ms']))
+                        "  normals: " + normals_line(c['normals'], c['align'], c['insert_ms']) + "  locate: " + locate_line(c['locate'], c['align']))
             for k in s["clearance_synthetic"]:
                 f.write(f"clearance of a synthetic {k['cells'][0]} x {k['cells'][1]} grid, source density {k['density']}, max_dist {k['max_dist']} (all four outputs, mean of 5): "
                         f"{1e3 * k['ms']:.1f} us, counts {k['counts']} (sources, reached, unreached, blocked); 22 B per cell at hbm_copy {1e3 * k['bound_ms']:.1f} us -> "
