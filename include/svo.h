@@ -110,7 +110,8 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * iteration), "voxel_normals" (one svo_voxel_map_normals_dev), "voxel_align_plane" (one svo_voxel_map_align_plane_sums_dev),
  * "voxel_occupancy" (one svo_voxel_map_occupancy_dev: its two memsets and the launch), "voxel_locate" (one
  * svo_voxel_map_locate_scores_dev: its memsets, the score launches and the best launch; the occupancy launch and the
- * refinements inside svo_voxel_map_locate count under their own tags); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
+ * refinements inside svo_voxel_map_locate count under their own tags), "voxel_coarse" (one svo_voxel_occupancy_coarse_dev: its memset
+ * and the launch), "voxel_rays" (one svo_voxel_occupancy_rays_dev or _raycast_dev: the counts' memset and the launch); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
 /* Measurement aid: the card's own ceilings for the roofline objects (SURVEY 8d asks for a measured FP64 figure).
@@ -962,6 +963,135 @@ int svo_voxel_locate_workspace_bytes(const svo_voxel_locate_params* params, size
 int svo_voxel_map_locate(svo_voxel_map* map, const svo_voxel_normal* normals, const svo_cloud_point* points, int n,
                          const double* pose7_in, const svo_voxel_locate_params* params, const svo_voxel_align_params* align_params,
                          void* workspace, double* pose7_out, svo_voxel_locate_result* result);
+
+/* Voxel map sight lines: what a straight line through the occupancy volume meets first.  A ray walk through the dense
+ * bit volume of svo_voxel_map_occupancy_dev: a hole-free depth view in the dense track's CV_16S format, visibility and
+ * segment-collision queries for arbitrary rays, and the 3D sight lines a view planner needs.  Integer work apart from a few
+ * ordered f64 operations per ray (no contraction); a restatement in another language gives the same bytes.
+ * Inputs bits, origin3, dims3 are exactly those of svo_voxel_map_occupancy_dev, with the same refusals in the same order.  The map
+ * argument is read for voxel_size and the stream ONLY.  The table is not touched.
+ *
+ * 1. Coarse volume (svo_voxel_occupancy_coarse_dev).  cd_r = (d_r + 7) >> 3.  Coarse bit Bc = b0 + cd0*(b1 + cd1*b2) lives in
+ *    little-endian u64 words, (cd0*cd1*cd2 + 63) >> 6 of them.  A coarse bit is 1 iff any fine bit with j_r >> 3 == b_r is 1.  Bits
+ *    past the last block are 0.  svo_voxel_occupancy_coarse_bytes(dims3, &bytes) is pure.  The entry issues one memset and one
+ *    launch, under profile tag "voxel_coarse".  coarse is a DEVICE pointer, 8-byte aligned.  Refusals, in this order: a null map;
+ *    the dims refusals of the occupancy; null bits; bits not 8-byte aligned; null coarse; coarse not 8-byte aligned.
+ *
+ * 2. A ray is the 32-byte record svo_voxel_ray {float ox, oy, oz, max_range, dx, dy, dz; uint32_t tag}.  Rays are 16-byte aligned,
+ *    in world metres.  d may have any length.  tag is carried and never read.  Set-up is in doubles, each f32 widened first, in
+ *    the written order:
+ *      REJECTED iff any of the seven floats is not finite, or max_range < 0, or m = max(|dx|, |dy|, |dz|) == 0.
+ *      REJECTED also iff any q_r = o_r / (double)voxel_size fails q_r >= -1048560.0 && q_r < 1048560.0.
+ *      p_r = (int64)floor(q_r * 256.0) - 256*origin_r.  This is the position in 1/256 voxel, relative to the volume.
+ *      D_r = (int)floor((d_r / m) * 16384.0 + 0.5).  The largest component is exactly +-16384.
+ *      S = D_0^2 + D_1^2 + D_2^2.
+ *      R = (max_range / (double)voxel_size) * 256.0.
+ *      L_r = (int64)min(floor((R * (double)|D_r|) / sqrt((double)S)), 2^40), the min taken in f64.
+ *
+ * 3. The walk.  The rule is stated for one ray.  Every implementation must return exactly these values.
+ *    Start: c_r = p_r >> 8 (arithmetic shift) and f_r = p_r & 255.  OUTSIDE iff some c_r is not in [0, d_r).  There is no walk and
+ *    no entry into the volume from outside: the volume is meant to be centred on the viewer.  Step count k = 0.  A visited cell is
+ *    TESTED iff k >= min_step (min_step in 0..255).  It is a HIT iff tested and its bit is 1.  The start cell is visited at k = 0
+ *    (HIT there: axis = 3, n = 0).
+ *    Per-axis state: n_r = 256 - f_r if D_r > 0, f_r if D_r < 0.  w_r is the product of max(|D_s|, 1) over the other two axes.
+ *    X_r = n_r*w_r, or 2^62 if D_r == 0.
+ *    Repeat:
+ *      1. a = the axis with the smallest X, ties to the smallest axis number.
+ *      2. If n_a > L_a: RANGE.  Stop.
+ *      3. c_a += sign(D_a).  If that leaves [0, d_a): LEFT.  Stop.
+ *      4. k += 1.  Visit the cell.  HIT: stop.
+ *      5. n_a += 256, X_a += 256*w_a.
+ *    Bounds and loop length: X < 2^48, so every compare is a 64-bit integer compare and every update an add.  The loop makes at
+ *    most d0 + d1 + d2 steps by construction.  The kernel also carries that number as an explicit iteration cap, so that no input
+ *    can make a wavefront spin.
+ *
+ * 4. Result is the 16-byte record svo_voxel_ray_hit {uint32_t cell, steps; float dist; uint32_t status}.  status = code | axis << 8.
+ *    Codes: HIT 0, LEFT 1, RANGE 2, OUTSIDE 3, REJECTED 4.  axis is the a of the last crossing considered, or 3 where there was
+ *    none.  cell is the bit number B of the last cell visited.  It is 0xFFFFFFFF for OUTSIDE and REJECTED.  steps = k.
+ *    dist = (float)((((double)n_a * sqrt((double)S)) / (double)|D_a|) / 256.0 * (double)voxel_size), with the n_a of that last
+ *    crossing.  It is 0.0f where there was none.
+ *
+ * 5. Counts.  counts = 6 DEVICE u64 (or NULL): {n_hit, n_left, n_range, n_outside, n_rejected, n_steps = sum of steps}.  They are
+ *    zeroed on the stream.  One relaxed atomicAdd is issued per workgroup and non-zero counter.  There is no fence and no waiting
+ *    on another workgroup.
+ *
+ * 6. svo_voxel_occupancy_rays_dev(map, bits, coarse_or_NULL, origin3, dims3, rays, n, min_step, hits, counts).  n <= 2^20.  hits
+ *    holds n records, 16-byte aligned.  Every record is written by every call.  n == 0 launches nothing but the counts' memset.
+ *    coarse == NULL selects the plain walk.  A given coarse selects the block-skipping walk: while the current cell's coarse bit
+ *    is 0, all crossings up to the one that leaves the cell's 8-block (or the volume through it) are made at once, if none of
+ *    them breaks n <= L (host/voxel_rays.h).  The two walks give the same bytes.  coarse is trusted to be item 1's
+ *    output for these bits.  Profile tag "voxel_rays".
+ *    Refusals, in this order, each with nothing launched: null map; n < 0; n > 2^20; min_step outside 0..255; the origin and dims
+ *    refusals of the occupancy; null bits, then bits misaligned; coarse misaligned; null hits, then hits misaligned; counts not
+ *    8-byte aligned; with n > 0: null rays, then rays misaligned.
+ *
+ * 7. svo_voxel_occupancy_rays is the synchronous host form: HOST rays in, HOST hits and counts out (counts may be NULL; no
+ *    alignment is asked of the host arrays).  It allocates and frees its own device copies of rays, hits and counts.  bits and
+ *    coarse stay DEVICE pointers.
+ *
+ * 8. Camera form (svo_voxel_occupancy_raycast_dev, _raycast_pose7_dev).  Inputs are width, height, cam (focal, cx, cy, baseline
+ *    read), c2w12 (CAMERA->WORLD, 12 HOST doubles by value; the pose7 form goes through svo_pose7_to_cam_to_world), and
+ *    svo_voxel_raycast_params {float max_range; int min_step;}.  The defaults are 30.0 and 1.  There is one ray per pixel (x, y):
+ *      v0 = ((double)x - cx) / focal, v1 = ((double)y - cy) / focal.
+ *      d_r = m[r][0]*v0 + m[r][1]*v1 + m[r][2], left to right.  o_r = m[r][3].
+ *      Item 2's set-up is applied to these doubles (nothing is narrowed to f32), then item 3's walk.
+ *    The output is disp16, a tight CV_16S map in sixteenths.  A HIT with k >= 1 gives
+ *      z = ((double)n_a * (double)voxel_size * 64.0) / ((double)|D_a| * m).
+ *    This is the depth along the optical axis of the point where the ray enters the hit voxel.
+ *      d16 = floor((focal*baseline) / z * 16.0 + 0.5).  It is kept iff 1.0 <= d16 && d16 <= 32767.0, compared in f64.
+ *    Every other pixel is FILTERED (-16).  cell is a tight u32 per pixel, or NULL.  It is 0xFFFFFFFF where disp16 is FILTERED.
+ *    counts is as in item 5 plus a seventh word, n_pixels, the kept pixels.  A wavefront takes an 8 x 8 pixel tile.
+ *    Refusals, in this order: null map; null cam; null c2w12 (pose7 form: null pose7); null params; max_range not finite or < 0;
+ *    min_step outside 0..255; width or height < 1 or beyond the context's limits; focal or baseline not finite or <= 0; then
+ *    item 6's refusals for the volume (origin, dims, bits, coarse); null disp16; disp16 not 2-byte aligned; cell not 4-byte
+ *    aligned; counts not 8-byte aligned.
+ *
+ * 9. Host convenience svo_voxel_map_raycast.  It takes map, min_count, dims3, width, height, cam, c2w12, params, and HOST outputs.
+ *    The volume's origin comes from the camera centre (m[r][3]) by the locate's step c.  The call then runs occupancy, coarse and
+ *    raycast, and copies out.  It is synchronous, and allocates and frees.  Refusals: null map; min_count < 1; item 8's for cam, c2w12, params, width and height; the dims refusals; null disp16;
+ *    then step c's.
+ * The defaults are NOT tuned on real imagery.  Order of use: occupancy after the map's last insert / update / carve, then coarse,
+ * then rays.  The pipeline never casts rays by itself. */
+typedef struct svo_voxel_ray {
+  float ox, oy, oz, max_range;
+  float dx, dy, dz;
+  uint32_t tag;
+} svo_voxel_ray; /* 32 bytes */
+typedef struct svo_voxel_ray_hit {
+  uint32_t cell, steps;
+  float dist;
+  uint32_t status;
+} svo_voxel_ray_hit; /* 16 bytes */
+enum { SVO_VOXEL_RAY_HIT = 0, SVO_VOXEL_RAY_LEFT = 1, SVO_VOXEL_RAY_RANGE = 2, SVO_VOXEL_RAY_OUTSIDE = 3, SVO_VOXEL_RAY_REJECTED = 4 };
+typedef struct svo_voxel_raycast_params {
+  float max_range; /* finite, >= 0: metres along the ray */
+  int min_step;    /* 0..255: cells visited before this step are not tested (1: the viewer's own cell is skipped) */
+} svo_voxel_raycast_params;
+/* max_range 30.0, min_step 1.  NOT tuned on real imagery.  Pure. */
+int svo_voxel_raycast_default_params(svo_voxel_raycast_params* params);
+/* Bytes of a coarse volume.  Pure; SVO_ERR_INVALID and *bytes = 0 for dims the occupancy refuses. */
+int svo_voxel_occupancy_coarse_bytes(const int* dims3, size_t* bytes);
+/* Asynchronous on svo_stream(ctx): one memset and one launch, one "voxel_coarse" profile bracket. */
+int svo_voxel_occupancy_coarse_dev(svo_voxel_map* map, const uint64_t* bits, const int* dims3, uint64_t* coarse);
+/* Asynchronous on svo_stream(ctx): the counts' memset and one launch, one "voxel_rays" profile bracket. */
+int svo_voxel_occupancy_rays_dev(svo_voxel_map* map, const uint64_t* bits, const uint64_t* coarse, const int* origin3, const int* dims3,
+                                 const svo_voxel_ray* rays, int n, int min_step, svo_voxel_ray_hit* hits, uint64_t* counts);
+/* Item 7: HOST rays, hits and counts (6 words, or NULL); bits and coarse on the DEVICE.  Synchronous; allocates and frees. */
+int svo_voxel_occupancy_rays(svo_voxel_map* map, const uint64_t* bits, const uint64_t* coarse, const int* origin3, const int* dims3,
+                             const svo_voxel_ray* host_rays, int n, int min_step, svo_voxel_ray_hit* host_hits, uint64_t* host_counts);
+/* Item 8.  DEVICE pointers; cell and counts (7 words) may be NULL.  Asynchronous; one "voxel_rays" profile bracket. */
+int svo_voxel_occupancy_raycast_dev(svo_voxel_map* map, const uint64_t* bits, const uint64_t* coarse, const int* origin3, const int* dims3,
+                                    int width, int height, const svo_camera_info* cam, const double* c2w12,
+                                    const svo_voxel_raycast_params* params, int16_t* disp16, uint32_t* cell, uint64_t* counts);
+/* svo_pose7_to_cam_to_world, then svo_voxel_occupancy_raycast_dev. */
+int svo_voxel_occupancy_raycast_pose7_dev(svo_voxel_map* map, const uint64_t* bits, const uint64_t* coarse, const int* origin3,
+                                          const int* dims3, int width, int height, const svo_camera_info* cam, const double* pose7,
+                                          const svo_voxel_raycast_params* params, int16_t* disp16, uint32_t* cell, uint64_t* counts);
+/* Item 9.  HOST outputs: disp16 width*height int16; cell width*height u32 or NULL; counts 7 u64 or NULL; origin3_out: the volume's
+ * origin, 3 ints, or NULL. */
+int svo_voxel_map_raycast(svo_voxel_map* map, int min_count, const int* dims3, int width, int height, const svo_camera_info* cam,
+                          const double* c2w12, const svo_voxel_raycast_params* params, int16_t* disp16, uint32_t* cell, uint64_t* counts,
+                          int* origin3_out);
 
 /* Voxel map grid: the ground plan of the map, an axis-aligned na x nb grid over two of the map's axes.  Per cell: the highest and
  * the lowest surface inside a height band, the mean intensity of the highest voxel, how many voxels and points fell into the cell,

@@ -362,6 +362,38 @@ def voxel_occupancy_bytes(dims):
     return int(n.value)
 
 
+class VoxelRaycastParams(C.Structure):
+    """svo_voxel_raycast_params: max_range (finite, >= 0, metres along the ray), min_step (0..255: cells visited before this step are
+    not tested)."""
+    _fields_ = [("max_range", C.c_float), ("min_step", C.c_int)]
+
+
+VoxelRay = np.dtype([("ox", np.float32), ("oy", np.float32), ("oz", np.float32), ("max_range", np.float32), ("dx", np.float32),
+                     ("dy", np.float32), ("dz", np.float32), ("tag", np.uint32)])  # svo_voxel_ray, 32 bytes
+VoxelRayHit = np.dtype([("cell", np.uint32), ("steps", np.uint32), ("dist", np.float32), ("status", np.uint32)])  # svo_voxel_ray_hit, 16 bytes
+VOXEL_RAY_STATUS = ("HIT", "LEFT", "RANGE", "OUTSIDE", "REJECTED")  # SVO_VOXEL_RAY_*, by value: status & 255; status >> 8 is the axis
+RAYS_COUNTS = ("n_hit", "n_left", "n_range", "n_outside", "n_rejected", "n_steps")
+RAYCAST_COUNTS = RAYS_COUNTS + ("n_pixels",)
+VOXEL_RAYS_MAX = 1 << 20
+
+
+def voxel_raycast_default_params():
+    """svo_voxel_raycast_default_params: max_range 30.0, min_step 1 (not tuned on real imagery)."""
+    p = VoxelRaycastParams()
+    if lib().svo_voxel_raycast_default_params(C.byref(p)) != 0:
+        raise SvoError("svo_voxel_raycast_default_params failed")
+    return p
+
+
+def voxel_occupancy_coarse_bytes(dims):
+    """svo_voxel_occupancy_coarse_bytes: bytes of the coarse volume of an occupancy volume of dims voxels, one bit per 8 x 8 x 8 block
+    (no GPU involved)."""
+    n = C.c_size_t(0)
+    if lib().svo_voxel_occupancy_coarse_bytes(_p(_int3(dims)), C.byref(n)) != 0:
+        raise SvoError("svo_voxel_occupancy_coarse_bytes: each dimension in 1..2048, dims[0] a multiple of 64, the product at most 2^30")
+    return int(n.value)
+
+
 class VoxelGridParams(C.Structure):
     """svo_voxel_grid_params: up_axis (0..2), up_sign (+1 / -1), the corner of cell (0, 0) in map units, voxels per cell edge
     (1..1024), na x nb cells (each 1..8192, na*nb <= 2^24), the height band, the span beyond which a cell is an obstacle, min_count."""
@@ -841,6 +873,8 @@ SYMBOLS = [
     "svo_voxel_map_align_plane_sums_dev", "svo_voxel_map_align_plane_sums_pose7_dev", "svo_voxel_map_align_plane",
     "svo_voxel_occupancy_bytes", "svo_voxel_map_occupancy_dev", "svo_voxel_map_occupancy", "svo_voxel_map_locate_scores_dev",
     "svo_voxel_locate_default_params", "svo_voxel_locate_workspace_bytes", "svo_voxel_map_locate",
+    "svo_voxel_raycast_default_params", "svo_voxel_occupancy_coarse_bytes", "svo_voxel_occupancy_coarse_dev", "svo_voxel_occupancy_rays_dev",
+    "svo_voxel_occupancy_rays", "svo_voxel_occupancy_raycast_dev", "svo_voxel_occupancy_raycast_pose7_dev", "svo_voxel_map_raycast",
 ]
 
 
@@ -1056,6 +1090,18 @@ def lib():
         L.svo_voxel_map_locate.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
         for f in ("svo_voxel_occupancy_bytes", "svo_voxel_map_occupancy_dev", "svo_voxel_map_occupancy", "svo_voxel_map_locate_scores_dev",
                   "svo_voxel_locate_default_params", "svo_voxel_locate_workspace_bytes", "svo_voxel_map_locate"):
+            getattr(L, f).restype = ci
+        # the sight lines
+        L.svo_voxel_raycast_default_params.argtypes = [vp]
+        L.svo_voxel_occupancy_coarse_bytes.argtypes = [vp, vp]
+        L.svo_voxel_occupancy_coarse_dev.argtypes = [vp, vp, vp, vp]
+        L.svo_voxel_occupancy_rays_dev.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp]
+        L.svo_voxel_occupancy_rays.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp]
+        L.svo_voxel_occupancy_raycast_dev.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp]
+        L.svo_voxel_occupancy_raycast_pose7_dev.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp]
+        L.svo_voxel_map_raycast.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+        for f in ("svo_voxel_raycast_default_params", "svo_voxel_occupancy_coarse_bytes", "svo_voxel_occupancy_coarse_dev", "svo_voxel_occupancy_rays_dev",
+                  "svo_voxel_occupancy_rays", "svo_voxel_occupancy_raycast_dev", "svo_voxel_occupancy_raycast_pose7_dev", "svo_voxel_map_raycast"):
             getattr(L, f).restype = ci
         _LIB = L
     return _LIB
@@ -1845,6 +1891,59 @@ class VoxelMap:
                                                   C.byref(res)), "svo_voxel_map_locate")
         return out, {"status": VOXEL_LOCATE_STATUS[res.status], "k": res.k, "shift": tuple(res.shift), "hits": int(res.hits), "rank": res.rank,
                      "n_refined": res.n_refined, "coarse_pose7": np.array(list(res.coarse_pose7), np.float64), "align": _align_result(res.align)}
+
+    def occupancy_coarse(self, bits_ptr, dims, coarse_ptr):
+        """svo_voxel_occupancy_coarse_dev: one bit per 8 x 8 x 8 block of the volume occupancy() wrote at bits_ptr, set iff any of the
+        block's voxels is, into the voxel_occupancy_coarse_bytes(dims) bytes at the device pointer coarse_ptr (8-byte aligned).  Run
+        it after occupancy() and before rays() / raycast() with coarse_ptr.  Asynchronous on the context's stream."""
+        self.ctx._chk(self.L.svo_voxel_occupancy_coarse_dev(self.h, bits_ptr, _p(_int3(dims)), coarse_ptr), "svo_voxel_occupancy_coarse_dev")
+
+    def rays(self, bits_ptr, origin, dims, rays_ptr, n, hits_ptr=None, coarse_ptr=None, min_step=1, counts_ptr=None):
+        """svo_voxel_occupancy_rays_dev: what each of the n VoxelRay records at the device pointer rays_ptr (16-byte aligned, world
+        metres) meets first in the volume occupancy() wrote: n VoxelRayHit records at hits_ptr (16-byte aligned) and 6 uint64
+        RAYS_COUNTS at counts_ptr (or None).  coarse_ptr: what occupancy_coarse() wrote (the block-skipping walk), or None (the
+        plain walk); the same bytes either way (include/svo.h, "Voxel map sight lines").  Asynchronous on the context's stream."""
+        self.ctx._chk(self.L.svo_voxel_occupancy_rays_dev(self.h, bits_ptr, coarse_ptr, _p(_int3(origin)), _p(_int3(dims)), rays_ptr, int(n), int(min_step),
+                                                          hits_ptr, counts_ptr), "svo_voxel_occupancy_rays_dev")
+
+    def rays_host(self, bits_ptr, origin, dims, rays, coarse_ptr=None, min_step=1):
+        """svo_voxel_occupancy_rays: rays() for a host array of VoxelRay records, synchronous; bits_ptr and coarse_ptr stay device
+        pointers.  Returns (a VoxelRayHit array, {"n_hit", "n_left", "n_range", "n_outside", "n_rejected", "n_steps"})."""
+        r = np.ascontiguousarray(rays, dtype=VoxelRay)
+        out, c = np.empty(max(len(r), 1), VoxelRayHit), np.zeros(6, np.uint64)
+        self.ctx._chk(self.L.svo_voxel_occupancy_rays(self.h, bits_ptr, coarse_ptr, _p(_int3(origin)), _p(_int3(dims)), _p(r) if len(r) else None, len(r),
+                                                      int(min_step), _p(out), _p(c)), "svo_voxel_occupancy_rays")
+        return out[:len(r)], dict(zip(RAYS_COUNTS, (int(v) for v in c)))
+
+    def raycast(self, bits_ptr, origin, dims, width, height, cam, c2w12=None, pose7=None, params=None, coarse_ptr=None, disp_ptr=None,
+                cell_ptr=None, counts_ptr=None, **overrides):
+        """svo_voxel_occupancy_raycast_dev / _pose7_dev: one ray per pixel of `cam` at the pose, exactly one of c2w12 (3 x 4
+        camera->world) and pose7, walked through the volume at bits_ptr: a tight CV_16S disparity map in sixteenths at disp_ptr
+        (FILTERED = -16 where the ray meets nothing), the hit voxel's bit number per pixel at cell_ptr (uint32, or None) and 7
+        uint64 RAYCAST_COUNTS at counts_ptr (or None).  params: a VoxelRaycastParams and / or its fields as keywords; coarse_ptr as
+        in rays().  A view without the splat render's holes, in the format carve() takes.  Asynchronous on the context's stream."""
+        if (c2w12 is None) == (pose7 is None):
+            raise ValueError("VoxelMap.raycast: give exactly one of c2w12 and pose7")
+        prm = _params(voxel_raycast_default_params, params, **overrides)
+        fn, a = ("svo_voxel_occupancy_raycast_dev", _f64(c2w12).reshape(12)) if pose7 is None else ("svo_voxel_occupancy_raycast_pose7_dev", _f64(pose7).reshape(7))
+        self.ctx._chk(getattr(self.L, fn)(self.h, bits_ptr, coarse_ptr, _p(_int3(origin)), _p(_int3(dims)), int(width), int(height), C.byref(cam), _p(a),
+                                          C.byref(prm), disp_ptr, cell_ptr, counts_ptr), fn)
+
+    def raycast_host(self, width, height, cam, c2w12=None, pose7=None, dims=(512, 128, 512), min_count=1, params=None, **overrides):
+        """svo_voxel_map_raycast: the occupancy volume of dims voxels around the camera centre, its coarse volume and raycast() in one
+        synchronous call that allocates and frees.  Returns (disp16 (height, width) int16, cell (height, width) uint32,
+        {RAYCAST_COUNTS..., "origin": the volume's origin})."""
+        if (c2w12 is None) == (pose7 is None):
+            raise ValueError("VoxelMap.raycast_host: give exactly one of c2w12 and pose7")
+        prm = _params(voxel_raycast_default_params, params, **overrides)
+        m = _f64(pose7_to_cam_to_world(pose7) if c2w12 is None else c2w12).reshape(12)
+        d = np.empty((max(int(height), 1), max(int(width), 1)), np.int16)
+        cell, c, o = np.empty(d.shape, np.uint32), np.zeros(7, np.uint64), np.zeros(3, np.int32)
+        self.ctx._chk(self.L.svo_voxel_map_raycast(self.h, int(min_count), _p(_int3(dims)), int(width), int(height), C.byref(cam), _p(m), C.byref(prm), _p(d),
+                                                   _p(cell), _p(c), _p(o)), "svo_voxel_map_raycast")
+        counts = dict(zip(RAYCAST_COUNTS, (int(v) for v in c)))
+        counts["origin"] = tuple(int(v) for v in o)
+        return d, cell, counts
 
     def insert_keyframe_clouds(self, table, poses7):
         """The list Pipeline.keyframe_clouds() / PipelineGroup.keyframe_clouds() returns, one pose7 per entry: every entry's device

@@ -102,6 +102,14 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      form) from the cloud's pose moved by (5.3, -1.7, 4.2) voxels and turned by 0.11 rad about the world's y: wall clock (mean of 5),
      status, chosen candidate and the shift left.  A library built with -DSVO_EXP_LOCATE_BASELINE (SVO_EXTRA_HIPFLAGS) runs the same
      section with the baseline form of the score kernel.  --align-only runs this section too.
+ 21. sight lines: on the same maps, in the same run as section 20 and from the same volume (the default dims around the last cloud's
+     pose), one svo_voxel_occupancy_coarse_dev ("voxel_coarse" bracket: the memset and the launch, mean of 5); the camera form at
+     the image size from the map's own pose and 262,144 random rays (range 30 m, directions normal) from the volume's centre
+     ("voxel_rays" bracket: the counts' memset and the launch, mean of 5), each with the plain and with the block-skipping walk,
+     whose outputs are compared byte for byte; steps per ray from the counts, and the share of the visited cells the skipping
+     walk jumps from the restatement over the first 4,096 of the random rays (the two walks' counts are equal by contract, so
+     they cannot say); beside them, for context only, the same run's splat render at the defaults and section 20's occupancy.
+     --align-only runs this section too.
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -341,6 +349,7 @@ def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy, only_align=False):
             out[-1].update(align_view(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup))
             out[-1].update(normals_view(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, out[-1]["align"]))
             out[-1].update(locate_view(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, out[-1]["align"], out[-1]["extract_ms"]))
+            out[-1].update(rays_view(torch, ctx, cam, vm, 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, out[-1]["locate"]))
             if only_align:
                 vm.close()
                 continue
@@ -569,6 +578,91 @@ def locate_view(torch, ctx, vm, cloud, n, angle, forward, warmup, align, extract
                                  "shift_left": float(np.linalg.norm(api.pose7_to_cam_to_world(pose_out)[:, 3] - np.array([0.0, 0.0, forward])))}
     out["locate_start_shift"] = float(vs * np.linalg.norm([5.3, -1.7, 4.2]))
     return {"locate": out}
+
+
+def rays_view(torch, ctx, cam, vm, angle, forward, warmup, locate):
+    """Section 21 for one filled map (`locate`: section 20's figures of this map).  Nothing in the map changes."""
+    import voxel_locate_ref as L
+    import voxel_rays_ref as RR
+    import voxel_ref as V
+    from stereo_vo_amd import api
+    vs = float(vm.params.voxel_size)
+    c2w = np.asarray(V.rot_y(angle, (0.0, 0.0, forward)), np.float64).reshape(12)
+    dims = L.default_params().dims
+    origin = RR.origin_of((c2w[3], c2w[7], c2w[11]), vs, dims)
+    bits = torch.empty(api.voxel_occupancy_bytes(dims) // 8, dtype=torch.int64, device="cuda")
+    coarse = torch.empty(api.voxel_occupancy_coarse_bytes(dims) // 8, dtype=torch.int64, device="cuda")
+    occ = torch.zeros(2, dtype=torch.int32, device="cuda")
+    cnt = torch.zeros(7, dtype=torch.int64, device="cuda")
+    disp, cell = torch.empty(W * H, dtype=torch.int16, device="cuda"), torch.empty(W * H, dtype=torch.int32, device="cuda")
+    n = 1 << 18
+    rng = np.random.default_rng(21)
+    rays = np.zeros(n, api.VoxelRay)
+    centre = [(origin[r] + dims[r] / 2 + 0.37) * vs for r in range(3)]
+    rays["ox"], rays["oy"], rays["oz"], rays["max_range"] = centre[0], centre[1], centre[2], 30.0
+    d = rng.normal(size=(n, 3)).astype(np.float32)
+    rays["dx"], rays["dy"], rays["dz"] = d[:, 0], d[:, 1], d[:, 2]
+    drays = torch.from_numpy(rays.view(np.int32).reshape(-1, 8)).cuda()
+    hits = torch.empty((n, 4), dtype=torch.int32, device="cuda")
+    vm.occupancy(bits.data_ptr(), origin, dims, counts_ptr=occ.data_ptr())
+    torch.cuda.synchronize()
+
+    def timed(tag, call):
+        for _ in range(warmup):
+            call()
+        ctx.profile_select(tag)
+        for _ in range(5):
+            call()
+        ms, k = ctx.profile_read()
+        ctx.profile_select("")
+        assert k == 5, k
+        return ms / k
+
+    out = {"dims": list(dims), "occupancy_ms": locate["occupancy_ms"], "occupancy_counts": [int(v) for v in occ.cpu()], "rays": n, "image": [W, H]}
+    out["coarse_ms"] = timed("voxel_coarse", lambda: vm.occupancy_coarse(bits.data_ptr(), dims, coarse.data_ptr()))
+    words, cw = bits.cpu().numpy().view(np.uint64), coarse.cpu().numpy().view(np.uint64)
+    out["coarse_blocks_set"] = int(np.unpackbits(cw.view(np.uint8)).sum())
+    out["coarse_blocks"] = int(np.prod(RR.coarse_dims(dims)))
+    seen = {}
+    for name, cp in (("plain", None), ("skip", coarse.data_ptr())):
+        out[f"raycast_{name}_ms"] = timed("voxel_rays", lambda: vm.raycast(bits.data_ptr(), origin, dims, W, H, cam, c2w12=c2w, coarse_ptr=cp, disp_ptr=disp.data_ptr(),
+                                                                        cell_ptr=cell.data_ptr(), counts_ptr=cnt.data_ptr()))
+        out["raycast_counts"] = [int(v) for v in cnt.cpu()]
+        view = (disp.cpu().numpy().tobytes(), cell.cpu().numpy().tobytes(), out["raycast_counts"])
+        out[f"rays_{name}_ms"] = timed("voxel_rays", lambda: vm.rays(bits.data_ptr(), origin, dims, drays.data_ptr(), n, hits_ptr=hits.data_ptr(), coarse_ptr=cp,
+                                                                  counts_ptr=cnt.data_ptr()))
+        out["rays_counts"] = [int(v) for v in cnt.cpu()[:6]]
+        seen[name] = (view, hits.cpu().numpy().tobytes(), out["rays_counts"])
+    assert seen["plain"] == seen["skip"], "the two walks differ"
+    out["raycast_steps_per_ray"] = out["raycast_counts"][5] / (W * H)
+    out["rays_steps_per_ray"] = out["rays_counts"][5] / n
+    vol = RR.Volume(words, dims, cw)
+    steps = jumped = jumps = 0
+    for ray in rays[:4096]:
+        s = RR.setup_a(*RR.widen(ray), vs, origin)
+        if s is not None:
+            e, j, k = RR.walk_skip(s, vol, 1)
+            steps, jumped, jumps = steps + e[3], jumped + j, jumps + k
+    out.update({"sample_steps": steps, "sample_jumped": jumped, "sample_jumps": jumps})
+    ws = torch.empty(W * H, dtype=torch.int32, device="cuda")
+    gg = torch.empty(W * H, dtype=torch.uint8, device="cuda")
+    w2c = np.linalg.inv(np.vstack([c2w.reshape(3, 4), [0, 0, 0, 1]]))[:3].reshape(12)
+    torch.cuda.synchronize()
+    out["render_ms"] = timed("voxel_render", lambda: vm.render(W, H, cam, w2c12=w2c, workspace_ptr=ws.data_ptr(), disp_ptr=disp.data_ptr(), intensity_ptr=gg.data_ptr()))
+    return {"rays": out}
+
+
+def rays_line(k):
+    """Section 21's lines of the text report for one rays_view."""
+    return (f"coarse volume of {k['dims']} (memset + launch, mean of 5): {1e3 * k['coarse_ms']:.1f} us, {k['coarse_blocks_set']} of {k['coarse_blocks']} blocks set; "
+            f"the same run's occupancy {1e3 * k['occupancy_ms']:.1f} us (counts {k['occupancy_counts']}) and splat render at the defaults {1e3 * k['render_ms']:.1f} us\n"
+            f"  camera form {k['image'][0]} x {k['image'][1]} from the map's own pose (counts' memset + launch, mean of 5): plain walk {1e3 * k['raycast_plain_ms']:.1f} us, "
+            f"block-skipping walk {1e3 * k['raycast_skip_ms']:.1f} us -> skip / plain {k['raycast_skip_ms'] / k['raycast_plain_ms']:.3f}; counts {k['raycast_counts']} "
+            f"(hit, left, range, outside, rejected, steps, pixels), {k['raycast_steps_per_ray']:.1f} steps per ray\n"
+            f"  {k['rays']} random rays from the volume's centre, range 30 m: plain {1e3 * k['rays_plain_ms']:.1f} us, block-skipping {1e3 * k['rays_skip_ms']:.1f} us -> skip / plain "
+            f"{k['rays_skip_ms'] / k['rays_plain_ms']:.3f}; counts {k['rays_counts']}, {k['rays_steps_per_ray']:.1f} steps per ray; of the first 4,096 rays' "
+            f"{k['sample_steps']} visited cells the skipping walk jumps {k['sample_jumped']} ({100.0 * k['sample_jumped'] / max(k['sample_steps'], 1):.1f} %) in {k['sample_jumps']} jumps "
+            f"(restatement); the outputs of the two walks are equal in every byte\n")
 
 
 def locate_line(k, a):
@@ -1531,7 +1625,7 @@ def main():
     ap.add_argument("--ledger-only", action="store_true", help="of the 96-lane loads only clouds alone and clouds with the ledger loop")
     ap.add_argument("--surface-only", action="store_true", help="section 16's seeded grids alone")
     ap.add_argument("--waypoints-only", action="store_true", help="section 17's seeded grid alone")
-    ap.add_argument("--align-only", action="store_true", help="section 7's fill and sections 10, 18, 19 and 20 alone")
+    ap.add_argument("--align-only", action="store_true", help="section 7's fill and sections 10, 18, 19, 20 and 21 alone")
     ap.add_argument("--out", help="write the text report here as well")
     a = ap.parse_args()
     import torch
@@ -1579,7 +1673,7 @@ def main():
                 for c in res["voxel"]:
                     f.write(f"voxel map, clouds at step {c['cloud_step']} ({c['points_per_cloud']:.0f} points per cloud), voxel {c['voxel_size']} m, 2^{c['capacity_log2']} slots, "
                             f"{c['stats_after_fresh']['n_voxels']} voxels, load {c['load']:.3f}:\n  align: " + align_line(c['align'], c['insert_ms']) +
-                            "  normals: " + normals_line(c['normals'], c['align'], c['insert_ms']) + "  locate: " + locate_line(c['locate'], c['align']))
+                            "  normals: " + normals_line(c['normals'], c['align'], c['insert_ms']) + "  locate: " + locate_line(c['locate'], c['align']) + "  sight lines: " + rays_line(c['rays']))
         return
     res = {"standalone": standalone(S, torch, a.batch, 3, a.reps)}
     print("bench_dense: standalone sections done", file=sys.stderr, flush=True)
@@ -1680,7 +1774,7 @@ def main():
                         f"{c['remove_ms'] / c['insert_ms']:.2f}, move / insert {c['move_ms'] / c['insert_ms']:.2f}; 16 B per record at hbm_copy "
                         f"{1e3 * c['remove_move_bound_ms']:.2f} us\n"
                         "  align: " + align_line(c['align'], c['insert_ms']) +
-                        "  normals: " + normals_line(c['normals'], c['align'], c['insert_ms']) + "  locate: " + locate_line(c['locate'], c['align']))
+                        "  normals: " + normals_line(c['normals'], c['align'], c['insert_ms']) + "  locate: " + locate_line(c['locate'], c['align']) + "  sight lines: " + rays_line(c['rays']))
             for k in s["clearance_synthetic"]:
                 f.write(f"clearance of a synthetic {k['cells'][0]} x {k['cells'][1]} grid, source density {k['density']}, max_dist {k['max_dist']} (all four outputs, mean of 5): "
                         f"{1e3 * k['ms']:.1f} us, counts {k['counts']} (sources, reached, unreached, blocked); 22 B per cell at hbm_copy {1e3 * k['bound_ms']:.1f} us -> "
