@@ -111,7 +111,9 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * "voxel_occupancy" (one svo_voxel_map_occupancy_dev: its two memsets and the launch), "voxel_locate" (one
  * svo_voxel_map_locate_scores_dev: its memsets, the score launches and the best launch; the occupancy launch and the
  * refinements inside svo_voxel_map_locate count under their own tags), "voxel_coarse" (one svo_voxel_occupancy_coarse_dev: its memset
- * and the launch), "voxel_rays" (one svo_voxel_occupancy_rays_dev or _raycast_dev: the counts' memset and the launch); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
+ * and the launch), "voxel_rays" (one svo_voxel_occupancy_rays_dev or _raycast_dev: the counts' memset and the launch),
+ * "voxel_distance" (one svo_voxel_occupancy_distance_dev: the counts' memset and its three launches), "voxel_distance_query" (one
+ * svo_voxel_distance_query_dev: the counts' memset and the launch); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
 /* Measurement aid: the card's own ceilings for the roofline objects (SURVEY 8d asks for a measured FP64 figure).
@@ -1092,6 +1094,96 @@ int svo_voxel_occupancy_raycast_pose7_dev(svo_voxel_map* map, const uint64_t* bi
 int svo_voxel_map_raycast(svo_voxel_map* map, int min_count, const int* dims3, int width, int height, const svo_camera_info* cam,
                           const double* c2w12, const svo_voxel_raycast_params* params, int16_t* disp16, uint32_t* cell, uint64_t* counts,
                           int* origin3_out);
+
+/* Voxel map distance field: how far every voxel of the occupancy volume is from the nearest occupied one.  The exact
+ * squared Euclidean distance in voxels, the nearest occupied cell, the distance in map units, the volume inflated by a radius (in
+ * the occupancy's own bit format, so that svo_voxel_occupancy_rays_dev over it is a swept-sphere test) and a per-point query.
+ * Integers only but for rule 5 and a sphere's set-up; nothing depends on thread order; a restatement in another language gives
+ * the same bytes.  Inputs bits, dims3 and (the query, the host call) origin3 are exactly those of svo_voxel_map_occupancy_dev, with
+ * the same refusals in the same order.  Bit number B = j0 + d0*(j1 + d1*j2).  The map argument is read for voxel_size and the stream
+ * ONLY.  The table is not touched.
+ *   svo_voxel_distance_params {int max_dist; float inflate_radius;}: max_dist in voxels, 1..254; inflate_radius in map units, finite
+ *   and >= 0.  The defaults are 32 and 0, NOT tuned on real data.
+ * 1. A cell is a source iff its bit is 1.  Cells outside the volume are never sources.  Axis 0 does not run on from the end of one
+ *    row into the next row.
+ * 2. dist2[B] (u16, required) is the minimum over sources s of sum_r (j_r - s_r)^2 if that is <= max_dist^2, else NONE16 = 0xFFFF.
+ *    A source has 0.  254^2 = 64,516 fits.
+ * 3. nearest[B] (u32, optional) is the smallest bit number among the sources that attain the minimum, 0xFFFFFFFF where dist2 is
+ *    NONE16.
+ * 4. inflated (u64 words in the occupancy's layout, svo_voxel_occupancy_bytes of them, optional): bit B is 1 iff dist2[B] <= R2, with
+ *    rc = (double)inflate_radius / (double)voxel_size and R2 = floor(rc*rc) clamped to max_dist^2, computed once on the host (an
+ *    overflowing quotient or square takes the clamp).  Sources are therefore always set.  Every word is written by every call: no
+ *    memset is needed.
+ * 5. clearance[B] (f32, optional) = (float)(sqrt((double)dist2) * (double)voxel_size), +infinity where dist2 is NONE16.
+ * 6. counts = 4 DEVICE u64 {n_sources, n_reached (0 < dist2 <= max_dist^2), n_unreached (NONE16), n_inflated (the set bits of rule
+ *    4's volume, sources included, counted whether or not inflated is given)}, or NULL.  Zeroed on the stream; one relaxed
+ *    atomicAdd per workgroup and non-zero counter.  No fence, no waiting on another workgroup.
+ * 7. The workspace is the caller's: svo_voxel_distance_workspace_bytes(dims3, want_nearest, &bytes) DEVICE bytes, 8-byte aligned, 3
+ *    per cell without nearest and 6 with it (want_nearest must be non-zero iff out->nearest is given).  Its contents are free on
+ *    entry and meaningless afterwards.
+ * 8. svo_voxel_occupancy_distance_dev refuses, in this order, each with SVO_ERR_INVALID, the argument named and nothing launched:
+ *    null map; null params; max_dist outside 1..254; inflate_radius not finite or negative; the dims refusals of the occupancy;
+ *    null bits, then bits misaligned; null workspace, then workspace not 8-byte aligned; null out; null dist2; dist2 not 2-byte
+ *    aligned; nearest, then clearance not 4-byte aligned; inflated not 8-byte aligned; counts not 8-byte aligned.
+ * 9. Query (svo_voxel_distance_query_dev).  A sphere is the 16-byte record svo_voxel_sphere {float x, y, z, radius} in world metres,
+ *    a result the 16-byte record svo_voxel_sphere_hit {uint32_t cell, dist2; float clearance; uint32_t code}.  In doubles, each f32
+ *    widened first: q_r = x_r / (double)voxel_size.  REJECTED (3) unless radius >= 0 and finite and every q_r >= -1048560.0 &&
+ *    q_r < 1048560.0 (a NaN and the infinities fail).  j_r = (int)floor(q_r) - origin_r.  OUTSIDE (2) iff some j_r is not in [0, d_r).
+ *    For both, cell and dist2 are 0xFFFFFFFF and clearance is +infinity.  Otherwise cell = B, dist2 is dist2[B] widened (NONE16
+ *    becomes 0xFFFFFFFF), clearance follows rule 5, and the code is COLLIDES (1) iff (double)dist2 <= floor(rc*rc) with
+ *    rc = (double)radius / (double)voxel_size, per sphere and without a clamp, else FREE (0).  A cell beyond max_dist therefore
+ *    collides only with a radius of 65,536 voxels or more.  This is cell centre to cell centre; a caller who wants a
+ *    conservative test adds sqrt(3) * voxel_size to the radius.  counts = 6 DEVICE u64 {n, n_free, n_collides, n_outside,
+ *    n_rejected, n_beyond (inside the volume, dist2 NONE16)}, or NULL.  n <= 2^20; n == 0 launches nothing but the counts' memset.
+ *    Profile tag "voxel_distance_query".  Refusals, in this order: null map; n < 0; n > 2^20; the origin and dims refusals of the
+ *    occupancy; null dist2, then dist2 not 2-byte aligned; null hits, then hits not 16-byte aligned; counts not 8-byte aligned; with
+ *    n > 0: null spheres, then spheres not 16-byte aligned.
+ * 10. svo_voxel_distance_query is the synchronous host form: HOST spheres in, HOST hits and counts out (counts may be NULL; no
+ *    alignment is asked of the host arrays); dist2 stays a DEVICE pointer.  It allocates and frees.
+ * 11. svo_voxel_map_distance runs svo_voxel_map_occupancy_dev and the distance field into device memory of its own and copies the
+ *    asked outputs to the HOST; synchronous; allocates and frees.  Refusals: null map; min_count < 1; the params refusals of rule 8;
+ *    the origin and dims refusals; null out; null dist2.
+ * Order of use: occupancy after the map's last insert / update / carve, then distance, then queries, or rays over inflated.  The
+ * pipeline never calls any of this by itself. */
+typedef struct svo_voxel_distance_params {
+  int max_dist;         /* 1..254 voxels: farther sources are not looked for */
+  float inflate_radius; /* finite, >= 0, map units: rule 4 */
+} svo_voxel_distance_params;
+typedef struct svo_voxel_distance_out {
+  uint16_t* dist2;    /* required */
+  uint32_t* nearest;  /* or NULL */
+  float* clearance;   /* or NULL */
+  uint64_t* inflated; /* or NULL */
+} svo_voxel_distance_out;
+typedef struct svo_voxel_sphere {
+  float x, y, z, radius;
+} svo_voxel_sphere; /* 16 bytes */
+typedef struct svo_voxel_sphere_hit {
+  uint32_t cell, dist2;
+  float clearance;
+  uint32_t code;
+} svo_voxel_sphere_hit; /* 16 bytes */
+enum { SVO_VOXEL_SPHERE_FREE = 0, SVO_VOXEL_SPHERE_COLLIDES = 1, SVO_VOXEL_SPHERE_OUTSIDE = 2, SVO_VOXEL_SPHERE_REJECTED = 3 };
+/* max_dist 32, inflate_radius 0.  NOT tuned on real data.  Pure; SVO_ERR_INVALID for null out or a voxel_size that is not finite and
+ * > 0 (the voxel size is taken for the day the defaults depend on it; today they do not). */
+int svo_voxel_distance_default_params(float voxel_size, svo_voxel_distance_params* out);
+/* Rule 7.  Pure; SVO_ERR_INVALID and *bytes = 0 for dims the occupancy refuses. */
+int svo_voxel_distance_workspace_bytes(const int* dims3, int want_nearest, size_t* bytes);
+/* Bytes of dist2: 2 per cell.  Pure; SVO_ERR_INVALID and *bytes = 0 for dims the occupancy refuses. */
+int svo_voxel_distance_bytes(const int* dims3, size_t* bytes);
+/* Asynchronous on svo_stream(ctx): the counts' memset and three launches, one "voxel_distance" profile bracket.  DEVICE pointers. */
+int svo_voxel_occupancy_distance_dev(svo_voxel_map* map, const uint64_t* bits, const int* dims3, const svo_voxel_distance_params* params,
+                                     void* workspace, const svo_voxel_distance_out* out, uint64_t* counts);
+/* Rule 9.  DEVICE pointers.  Asynchronous; one "voxel_distance_query" profile bracket. */
+int svo_voxel_distance_query_dev(svo_voxel_map* map, const uint16_t* dist2, const int* origin3, const int* dims3,
+                                 const svo_voxel_sphere* spheres, int n, svo_voxel_sphere_hit* hits, uint64_t* counts);
+/* Rule 10: HOST spheres, hits and counts (6 words, or NULL); dist2 on the DEVICE.  Synchronous; allocates and frees. */
+int svo_voxel_distance_query(svo_voxel_map* map, const uint16_t* dist2, const int* origin3, const int* dims3,
+                             const svo_voxel_sphere* host_spheres, int n, svo_voxel_sphere_hit* host_hits, uint64_t* host_counts);
+/* Rule 11.  host_out: HOST arrays (dist2 required, any alignment; inflated holds svo_voxel_occupancy_bytes bytes); host_counts: 4
+ * u64, or NULL. */
+int svo_voxel_map_distance(svo_voxel_map* map, int min_count, const int* origin3, const int* dims3,
+                           const svo_voxel_distance_params* params, const svo_voxel_distance_out* host_out, uint64_t* host_counts);
 
 /* Voxel map grid: the ground plan of the map, an axis-aligned na x nb grid over two of the map's axes.  Per cell: the highest and
  * the lowest surface inside a height band, the mean intensity of the highest voxel, how many voxels and points fell into the cell,

@@ -394,6 +394,52 @@ def voxel_occupancy_coarse_bytes(dims):
     return int(n.value)
 
 
+class VoxelDistanceParams(C.Structure):
+    """svo_voxel_distance_params: max_dist (1..254 voxels: farther sources are not looked for), inflate_radius (finite, >= 0, map
+    units: the radius of the inflated volume)."""
+    _fields_ = [("max_dist", C.c_int), ("inflate_radius", C.c_float)]
+
+
+class VoxelDistanceOut(C.Structure):
+    """svo_voxel_distance_out: dist2 (uint16 per cell, required), nearest (uint32 per cell), clearance (float32 per cell), inflated
+    (uint64 words of the occupancy's layout); the last three may be None."""
+    _fields_ = [("dist2", C.c_void_p), ("nearest", C.c_void_p), ("clearance", C.c_void_p), ("inflated", C.c_void_p)]
+
+
+VoxelSphere = np.dtype([("x", np.float32), ("y", np.float32), ("z", np.float32), ("radius", np.float32)])  # svo_voxel_sphere, 16 bytes
+VoxelSphereHit = np.dtype([("cell", np.uint32), ("dist2", np.uint32), ("clearance", np.float32), ("code", np.uint32)])  # svo_voxel_sphere_hit, 16 bytes
+VOXEL_SPHERE_CODE = ("FREE", "COLLIDES", "OUTSIDE", "REJECTED")  # SVO_VOXEL_SPHERE_*, by value
+DISTANCE_COUNTS = ("n_sources", "n_reached", "n_unreached", "n_inflated")
+DISTANCE_QUERY_COUNTS = ("n", "n_free", "n_collides", "n_outside", "n_rejected", "n_beyond")
+VOXEL_DISTANCE_NONE16 = 0xFFFF
+VOXEL_DISTANCE_QUERY_MAX = 1 << 20
+
+
+def voxel_distance_default_params(voxel_size):
+    """svo_voxel_distance_default_params: max_dist 32 voxels, inflate_radius 0 (not tuned on real data)."""
+    p = VoxelDistanceParams()
+    if lib().svo_voxel_distance_default_params(C.c_float(voxel_size), C.byref(p)) != 0:
+        raise SvoError("svo_voxel_distance_default_params: voxel_size must be finite and > 0")
+    return p
+
+
+def voxel_distance_workspace_bytes(dims, want_nearest=False):
+    """svo_voxel_distance_workspace_bytes: bytes of the workspace VoxelMap.distance wants for a volume of dims voxels, 3 per cell, or 6
+    when nearest is asked for (no GPU involved)."""
+    n = C.c_size_t(0)
+    if lib().svo_voxel_distance_workspace_bytes(_p(_int3(dims)), int(bool(want_nearest)), C.byref(n)) != 0:
+        raise SvoError("svo_voxel_distance_workspace_bytes: each dimension in 1..2048, dims[0] a multiple of 64, the product at most 2^30")
+    return int(n.value)
+
+
+def voxel_distance_bytes(dims):
+    """svo_voxel_distance_bytes: bytes of the dist2 output for a volume of dims voxels, 2 per cell (no GPU involved)."""
+    n = C.c_size_t(0)
+    if lib().svo_voxel_distance_bytes(_p(_int3(dims)), C.byref(n)) != 0:
+        raise SvoError("svo_voxel_distance_bytes: each dimension in 1..2048, dims[0] a multiple of 64, the product at most 2^30")
+    return int(n.value)
+
+
 class VoxelGridParams(C.Structure):
     """svo_voxel_grid_params: up_axis (0..2), up_sign (+1 / -1), the corner of cell (0, 0) in map units, voxels per cell edge
     (1..1024), na x nb cells (each 1..8192, na*nb <= 2^24), the height band, the span beyond which a cell is an obstacle, min_count."""
@@ -875,6 +921,8 @@ SYMBOLS = [
     "svo_voxel_locate_default_params", "svo_voxel_locate_workspace_bytes", "svo_voxel_map_locate",
     "svo_voxel_raycast_default_params", "svo_voxel_occupancy_coarse_bytes", "svo_voxel_occupancy_coarse_dev", "svo_voxel_occupancy_rays_dev",
     "svo_voxel_occupancy_rays", "svo_voxel_occupancy_raycast_dev", "svo_voxel_occupancy_raycast_pose7_dev", "svo_voxel_map_raycast",
+    "svo_voxel_distance_default_params", "svo_voxel_distance_workspace_bytes", "svo_voxel_distance_bytes", "svo_voxel_occupancy_distance_dev",
+    "svo_voxel_distance_query_dev", "svo_voxel_distance_query", "svo_voxel_map_distance",
 ]
 
 
@@ -1102,6 +1150,17 @@ def lib():
         L.svo_voxel_map_raycast.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]
         for f in ("svo_voxel_raycast_default_params", "svo_voxel_occupancy_coarse_bytes", "svo_voxel_occupancy_coarse_dev", "svo_voxel_occupancy_rays_dev",
                   "svo_voxel_occupancy_rays", "svo_voxel_occupancy_raycast_dev", "svo_voxel_occupancy_raycast_pose7_dev", "svo_voxel_map_raycast"):
+            getattr(L, f).restype = ci
+        # the distance field
+        L.svo_voxel_distance_default_params.argtypes = [C.c_float, vp]
+        L.svo_voxel_distance_workspace_bytes.argtypes = [vp, ci, vp]
+        L.svo_voxel_distance_bytes.argtypes = [vp, vp]
+        L.svo_voxel_occupancy_distance_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.svo_voxel_distance_query_dev.argtypes = [vp, vp, vp, vp, vp, ci, vp, vp]
+        L.svo_voxel_distance_query.argtypes = [vp, vp, vp, vp, vp, ci, vp, vp]
+        L.svo_voxel_map_distance.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+        for f in ("svo_voxel_distance_default_params", "svo_voxel_distance_workspace_bytes", "svo_voxel_distance_bytes", "svo_voxel_occupancy_distance_dev",
+                  "svo_voxel_distance_query_dev", "svo_voxel_distance_query", "svo_voxel_map_distance"):
             getattr(L, f).restype = ci
         _LIB = L
     return _LIB
@@ -1944,6 +2003,60 @@ class VoxelMap:
         counts = dict(zip(RAYCAST_COUNTS, (int(v) for v in c)))
         counts["origin"] = tuple(int(v) for v in o)
         return d, cell, counts
+
+    def _distance_params(self, params, overrides):
+        return _params(lambda: voxel_distance_default_params(self.params.voxel_size), params, **overrides)
+
+    def distance(self, bits_ptr, dims, params=None, workspace_ptr=None, dist2_ptr=None, nearest_ptr=None, clearance_ptr=None, inflated_ptr=None,
+                 counts_ptr=None, **overrides):
+        """svo_voxel_occupancy_distance_dev: per cell of the volume occupancy() wrote at bits_ptr the exact squared distance in voxels
+        to the nearest set bit, capped at max_dist (uint16 at dist2_ptr, 0xFFFF beyond), and optionally that bit's number (uint32 at
+        nearest_ptr), the distance in map units (float32 at clearance_ptr), the volume inflated by inflate_radius in the occupancy's
+        bit format (inflated_ptr; rays() over it is a swept-sphere test) and 4 uint64 DISTANCE_COUNTS at counts_ptr.  workspace_ptr:
+        voxel_distance_workspace_bytes(dims, nearest_ptr is not None) device bytes, 8-byte aligned.  params: a VoxelDistanceParams and
+        / or its fields as keywords.  Run it after occupancy().  Asynchronous on the context's stream."""
+        prm = self._distance_params(params, overrides)
+        out = VoxelDistanceOut(dist2_ptr, nearest_ptr, clearance_ptr, inflated_ptr)
+        self.ctx._chk(self.L.svo_voxel_occupancy_distance_dev(self.h, bits_ptr, _p(_int3(dims)), C.byref(prm), workspace_ptr, C.byref(out), counts_ptr),
+                      "svo_voxel_occupancy_distance_dev")
+
+    def distance_host(self, origin, dims, min_count=1, params=None, nearest=True, clearance=True, inflated=True, **overrides):
+        """svo_voxel_map_distance: occupancy() and distance() into memory of its own, synchronous; allocates and frees.  Returns a
+        dict: "dist2" (d2, d1, d0) uint16, and where asked "nearest" uint32, "clearance" float32 of that shape and "inflated", the
+        volume's uint64 words; "counts": {DISTANCE_COUNTS...}."""
+        prm = self._distance_params(params, overrides)
+        d = _int3(dims)
+        shape = (max(int(d[2]), 1), max(int(d[1]), 1), max(int(d[0]), 1))
+        res = {"dist2": np.empty(shape, np.uint16)}
+        if nearest:
+            res["nearest"] = np.empty(shape, np.uint32)
+        if clearance:
+            res["clearance"] = np.empty(shape, np.float32)
+        if inflated:
+            res["inflated"] = np.empty(max(shape[0] * shape[1] * shape[2] // 64, 1), np.uint64)
+        out = VoxelDistanceOut(*(res[k].ctypes.data if k in res else None for k in ("dist2", "nearest", "clearance", "inflated")))
+        c = np.zeros(4, np.uint64)
+        self.ctx._chk(self.L.svo_voxel_map_distance(self.h, int(min_count), _p(_int3(origin)), _p(d), C.byref(prm), C.byref(out), _p(c)), "svo_voxel_map_distance")
+        res["counts"] = dict(zip(DISTANCE_COUNTS, (int(v) for v in c)))
+        return res
+
+    def distance_query(self, dist2_ptr, origin, dims, spheres_ptr, n, hits_ptr=None, counts_ptr=None):
+        """svo_voxel_distance_query_dev: for each of the n VoxelSphere records at the device pointer spheres_ptr (16-byte aligned, world
+        metres) the cell of its centre, that cell's dist2 and clearance in the field distance() wrote at dist2_ptr, and whether a
+        sphere of its radius collides (cell centre to cell centre; add sqrt(3) * voxel_size to the radius for a conservative test):
+        n VoxelSphereHit records at hits_ptr (16-byte aligned) and 6 uint64 DISTANCE_QUERY_COUNTS at counts_ptr (or None).
+        Asynchronous on the context's stream."""
+        self.ctx._chk(self.L.svo_voxel_distance_query_dev(self.h, dist2_ptr, _p(_int3(origin)), _p(_int3(dims)), spheres_ptr, int(n), hits_ptr, counts_ptr),
+                      "svo_voxel_distance_query_dev")
+
+    def distance_query_host(self, dist2_ptr, origin, dims, spheres):
+        """svo_voxel_distance_query: distance_query() for a host array of VoxelSphere records, synchronous; dist2_ptr stays a device
+        pointer.  Returns (a VoxelSphereHit array, {DISTANCE_QUERY_COUNTS...})."""
+        s = np.ascontiguousarray(spheres, dtype=VoxelSphere)
+        out, c = np.empty(max(len(s), 1), VoxelSphereHit), np.zeros(6, np.uint64)
+        self.ctx._chk(self.L.svo_voxel_distance_query(self.h, dist2_ptr, _p(_int3(origin)), _p(_int3(dims)), _p(s) if len(s) else None, len(s), _p(out), _p(c)),
+                      "svo_voxel_distance_query")
+        return out[:len(s)], dict(zip(DISTANCE_QUERY_COUNTS, (int(v) for v in c)))
 
     def insert_keyframe_clouds(self, table, poses7):
         """The list Pipeline.keyframe_clouds() / PipelineGroup.keyframe_clouds() returns, one pose7 per entry: every entry's device

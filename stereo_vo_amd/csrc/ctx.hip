@@ -32,7 +32,8 @@ extern "C" int svo_profile_select(svo_ctx* ctx, const char* kernel) {
                                 "stereo_bm", "stereo_dense_batch", "cloud", "speckle", "lr_check", "stereo_sgm", "voxel_insert", "voxel_extract",
                                 "voxel_carve", "voxel_copy", "voxel_render", "voxel_remove", "voxel_move", "voxel_grid", "grid_clearance",
                                 "grid_route", "grid_frontier", "grid_view", "grid_surface", "grid_waypoints", "voxel_align",
-                                "voxel_normals", "voxel_align_plane", "voxel_occupancy", "voxel_locate", "voxel_coarse", "voxel_rays"};
+                                "voxel_normals", "voxel_align_plane", "voxel_occupancy", "voxel_locate", "voxel_coarse", "voxel_rays",
+                                "voxel_distance", "voxel_distance_query"};
   int tag = 0;
   if (kernel && kernel[0]) {
     tag = -1;

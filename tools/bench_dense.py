@@ -110,6 +110,13 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      walk jumps from the restatement over the first 4,096 of the random rays (the two walks' counts are equal by contract, so
      they cannot say); beside them, for context only, the same run's splat render at the defaults and section 20's occupancy.
      --align-only runs this section too.
+ 22. distance field: on the same maps, in the same run as sections 20 and 21 and over the same volume, svo_voxel_occupancy_distance_dev
+     ("voxel_distance" bracket: the counts' memset and the three launches, mean of 5) at max_dist 8, 32 and 128 with dist2 alone and
+     with all four outputs (inflate_radius 3 voxels), and svo_voxel_distance_query_dev of 262,144 random spheres in and around the
+     volume ("voxel_distance_query" bracket, mean of 5).  Beside each: section 20's occupancy launch, the time hbm_copy needs for the
+     bytes the workspace layout moves per cell (8.125 for dist2 alone, 22.25 for all four outputs) and the steps per cell, counted
+     on the host by the search's stop rule: the words each wavefront reads from the volume's words (axis 0), and the outward steps
+     from the downloaded partial and final squares (axes 1 and 2).  --align-only runs this section too.
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -350,6 +357,7 @@ def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy, only_align=False):
             out[-1].update(normals_view(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, out[-1]["align"]))
             out[-1].update(locate_view(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, out[-1]["align"], out[-1]["extract_ms"]))
             out[-1].update(rays_view(torch, ctx, cam, vm, 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, out[-1]["locate"]))
+            out[-1].update(distance_view(torch, ctx, vm, 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, out[-1]["locate"], copy))
             if only_align:
                 vm.close()
                 continue
@@ -650,6 +658,106 @@ def rays_view(torch, ctx, cam, vm, angle, forward, warmup, locate):
     torch.cuda.synchronize()
     out["render_ms"] = timed("voxel_render", lambda: vm.render(W, H, cam, w2c12=w2c, workspace_ptr=ws.data_ptr(), disp_ptr=disp.data_ptr(), intensity_ptr=gg.data_ptr()))
     return {"rays": out}
+
+
+def distance_steps(words, dims, max_dist, mid, dist2):
+    """Section 22's steps per cell of the three passes, by the search's stop rule: words read per cell's wavefront along axis 0
+    (its own, then each side up to the first non-zero word, ceil(max_dist / 64) words or the row's end), and the outward steps along
+    axes 1 and 2, a batch of four at a time while g <= reach and g * g <= the pass's result (mid: the axis-1 pass's u16 squares,
+    dist2: the final ones; 0xFFFF: nothing found, the search runs to its reach)."""
+    d0, d1, d2 = dims
+    wpr, K = d0 // 64, (max_dist + 63) // 64
+    nz = (np.asarray(words).reshape(-1, wpr) != 0)
+    x = np.arange(wpr)[None, :]
+    last = np.maximum.accumulate(np.where(nz, x, -1), axis=1)
+    prev = np.concatenate([np.full((len(nz), 1), -1), last[:, :-1]], axis=1)          # the nearest non-zero word to the left, or -1
+    nxt_ = np.minimum.accumulate(np.where(nz, x, 2 * wpr)[:, ::-1], axis=1)[:, ::-1]
+    nxt = np.concatenate([nxt_[:, 1:], np.full((len(nz), 1), 2 * wpr)], axis=1)      # to the right, or beyond the row
+    left = np.minimum(np.minimum(K, x), np.where(prev >= 0, x - prev, K))
+    right = np.minimum(np.minimum(K, wpr - 1 - x), np.where(nxt < wpr, nxt - x, K))
+    row_words = float((1 + left + right).mean())
+    out = [row_words]
+    for arr, ax, L in ((mid, 1, d1), (dist2, 0, d2)):
+        a = np.asarray(arr).reshape(d2, d1, d0)
+        pos = np.arange(L).reshape((-1, 1, 1) if ax == 0 else (1, -1, 1))
+        reach = np.minimum(max_dist, np.maximum(pos, L - 1 - pos))
+        root = np.where(a == 0xFFFF, 255, np.floor(np.sqrt(a.astype(np.float64))).astype(np.int64))
+        out.append(float((4 * (np.minimum(reach, root) // 4 + 1)).mean()))
+    return out
+
+
+def distance_view(torch, ctx, vm, angle, forward, warmup, locate, copy):
+    """Section 22 for one filled map (`locate`: section 20's figures of this map).  Nothing in the map changes."""
+    import voxel_locate_ref as L
+    import voxel_rays_ref as RR
+    import voxel_ref as V
+    from stereo_vo_amd import api
+    vs = float(vm.params.voxel_size)
+    c2w = np.asarray(V.rot_y(angle, (0.0, 0.0, forward)), np.float64).reshape(12)
+    dims = tuple(L.default_params().dims)
+    origin = RR.origin_of((c2w[3], c2w[7], c2w[11]), vs, dims)
+    cells = dims[0] * dims[1] * dims[2]
+    bits = torch.empty(cells // 64, dtype=torch.int64, device="cuda")
+    occ = torch.zeros(2, dtype=torch.int32, device="cuda")
+    ws = torch.empty(api.voxel_distance_workspace_bytes(dims, True) // 8, dtype=torch.int64, device="cuda")
+    d2 = torch.empty(cells, dtype=torch.int16, device="cuda")
+    near, clr = torch.empty(cells, dtype=torch.int32, device="cuda"), torch.empty(cells, dtype=torch.float32, device="cuda")
+    infl = torch.empty(cells // 64, dtype=torch.int64, device="cuda")
+    cnt = torch.zeros(6, dtype=torch.int64, device="cuda")
+    n = 1 << 18
+    rng = np.random.default_rng(22)
+    sph = np.zeros(n, api.VoxelSphere)
+    for r, k in enumerate(("x", "y", "z")):
+        sph[k] = ((origin[r] + rng.uniform(-0.05 * dims[r], 1.05 * dims[r], n)) * vs).astype(np.float32)
+    sph["radius"] = rng.uniform(0.0, 1.0, n).astype(np.float32)
+    dsph = torch.from_numpy(sph.view(np.int32).reshape(-1, 4)).cuda()
+    hits = torch.empty((n, 4), dtype=torch.int32, device="cuda")
+    vm.occupancy(bits.data_ptr(), origin, dims, counts_ptr=occ.data_ptr())
+    torch.cuda.synchronize()
+    words = bits.cpu().numpy().view(np.uint64)
+
+    def timed(tag, call):
+        for _ in range(warmup):
+            call()
+        ctx.profile_select(tag)
+        for _ in range(5):
+            call()
+        ms, k = ctx.profile_read()
+        ctx.profile_select("")
+        assert k == 5, k
+        return ms / k
+
+    out = {"dims": list(dims), "occupancy_ms": locate["occupancy_ms"], "occupancy_counts": [int(v) for v in occ.cpu()], "spheres": n,
+           "bound_dist2_ms": 1e3 * 8.125 * cells / copy, "bound_all_ms": 1e3 * 22.25 * cells / copy, "runs": []}
+    for md in (8, 32, 128):
+        k = {"max_dist": md}
+        k["dist2_ms"] = timed("voxel_distance", lambda: vm.distance(bits.data_ptr(), dims, workspace_ptr=ws.data_ptr(), dist2_ptr=d2.data_ptr(), counts_ptr=cnt.data_ptr(),
+                                                                     max_dist=md, inflate_radius=3.0 * vs))
+        k["counts"] = [int(v) for v in cnt.cpu()[:4]]
+        plain = d2.cpu().numpy().view(np.uint16)
+        mid = ws.cpu().numpy().view(np.uint16)[cells // 2:cells // 2 + cells]  # the axis-1 pass's squares: behind the u8 part
+        k["steps"] = distance_steps(words, dims, md, mid, plain)
+        k["all_ms"] = timed("voxel_distance", lambda: vm.distance(bits.data_ptr(), dims, workspace_ptr=ws.data_ptr(), dist2_ptr=d2.data_ptr(), nearest_ptr=near.data_ptr(),
+                                                                   clearance_ptr=clr.data_ptr(), inflated_ptr=infl.data_ptr(), counts_ptr=cnt.data_ptr(), max_dist=md,
+                                                                   inflate_radius=3.0 * vs))
+        assert k["counts"] == [int(v) for v in cnt.cpu()[:4]] and np.array_equal(plain, d2.cpu().numpy().view(np.uint16)), "the two forms differ"
+        k["query_ms"] = timed("voxel_distance_query", lambda: vm.distance_query(d2.data_ptr(), origin, dims, dsph.data_ptr(), n, hits_ptr=hits.data_ptr(),
+                                                                                 counts_ptr=cnt.data_ptr()))
+        k["query_counts"] = [int(v) for v in cnt.cpu()]
+        out["runs"].append(k)
+    return {"distance": out}
+
+
+def distance_line(k):
+    """Section 22's lines of the text report for one distance_view."""
+    s = (f"distance field of {k['dims']} (counts' memset + three launches, mean of 5); the same run's occupancy {1e3 * k['occupancy_ms']:.1f} us "
+         f"(counts {k['occupancy_counts']}); 8.125 B per cell at hbm_copy {1e3 * k['bound_dist2_ms']:.1f} us, 22.25 B per cell {1e3 * k['bound_all_ms']:.1f} us\n")
+    for r in k["runs"]:
+        s += (f"  max_dist {r['max_dist']}: dist2 alone {1e3 * r['dist2_ms']:.1f} us ({r['dist2_ms'] / k['bound_dist2_ms']:.1f} x its byte bound), all four outputs "
+              f"{1e3 * r['all_ms']:.1f} us ({r['all_ms'] / k['bound_all_ms']:.1f} x); counts {r['counts']} (sources, reached, unreached, inflated); per cell "
+              f"{r['steps'][0]:.2f} words along axis 0, {r['steps'][1]:.1f} + {r['steps'][2]:.1f} steps along axes 1 and 2; query of {k['spheres']} spheres "
+              f"{1e3 * r['query_ms']:.1f} us, counts {r['query_counts']} (n, free, collides, outside, rejected, beyond)\n")
+    return s
 
 
 def rays_line(k):
@@ -1625,7 +1733,7 @@ def main():
     ap.add_argument("--ledger-only", action="store_true", help="of the 96-lane loads only clouds alone and clouds with the ledger loop")
     ap.add_argument("--surface-only", action="store_true", help="section 16's seeded grids alone")
     ap.add_argument("--waypoints-only", action="store_true", help="section 17's seeded grid alone")
-    ap.add_argument("--align-only", action="store_true", help="section 7's fill and sections 10, 18, 19, 20 and 21 alone")
+    ap.add_argument("--align-only", action="store_true", help="section 7's fill and sections 10, 18, 19, 20, 21 and 22 alone")
     ap.add_argument("--out", help="write the text report here as well")
     a = ap.parse_args()
     import torch
@@ -1673,7 +1781,8 @@ def main():
                 for c in res["voxel"]:
                     f.write(f"voxel map, clouds at step {c['cloud_step']} ({c['points_per_cloud']:.0f} points per cloud), voxel {c['voxel_size']} m, 2^{c['capacity_log2']} slots, "
                             f"{c['stats_after_fresh']['n_voxels']} voxels, load {c['load']:.3f}:\n  align: " + align_line(c['align'], c['insert_ms']) +
-                            "  normals: " + normals_line(c['normals'], c['align'], c['insert_ms']) + "  locate: " + locate_line(c['locate'], c['align']) + "  sight lines: " + rays_line(c['rays']))
+                            "  normals: " + normals_line(c['normals'], c['align'], c['insert_ms']) + "  locate: " + locate_line(c['locate'], c['align']) + "  sight lines: " + rays_line(c['rays']) +
+                            "  " + distance_line(c['distance']))
         return
     res = {"standalone": standalone(S, torch, a.batch, 3, a.reps)}
     print("bench_dense: standalone sections done", file=sys.stderr, flush=True)
@@ -1774,7 +1883,8 @@ def main():
                         f"{c['remove_ms'] / c['insert_ms']:.2f}, move / insert {c['move_ms'] / c['insert_ms']:.2f}; 16 B per record at hbm_copy "
                         f"{1e3 * c['remove_move_bound_ms']:.2f} us\n"
                         "  align: " + align_line(c['align'], c['insert_ms']) +
-                        "  normals: " + normals_line(c['normals'], c['align'], c['insert_ms']) + "  locate: " + locate_line(c['locate'], c['align']) + "  sight lines: " + rays_line(c['rays']))
+                        "  normals: " + normals_line(c['normals'], c['align'], c['insert_ms']) + "  locate: " + locate_line(c['locate'], c['align']) + "  sight lines: " + rays_line(c['rays']) +
+                        "  " + distance_line(c['distance']))
             for k in s["clearance_synthetic"]:
                 f.write(f"clearance of a synthetic {k['cells'][0]} x {k['cells'][1]} grid, source density {k['density']}, max_dist {k['max_dist']} (all four outputs, mean of 5): "
                         f"{1e3 * k['ms']:.1f} us, counts {k['counts']} (sources, reached, unreached, blocked); 22 B per cell at hbm_copy {1e3 * k['bound_ms']:.1f} us -> "
