@@ -113,7 +113,8 @@ int svo_reference_constants(svo_reference_constants_t* out);
  * refinements inside svo_voxel_map_locate count under their own tags), "voxel_coarse" (one svo_voxel_occupancy_coarse_dev: its memset
  * and the launch), "voxel_rays" (one svo_voxel_occupancy_rays_dev or _raycast_dev: the counts' memset and the launch),
  * "voxel_distance" (one svo_voxel_occupancy_distance_dev: the counts' memset and its three launches), "voxel_distance_query" (one
- * svo_voxel_distance_query_dev: the counts' memset and the launch); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
+ * svo_voxel_distance_query_dev: the counts' memset and the launch), "voxel_route" (one svo_voxel_occupancy_route_dev: its memsets and
+ * every launch); NULL/"" disables.  svo_profile_read synchronises the stream and returns the summed duration and the
  * launch count since the last svo_profile_select. */
 int svo_profile_select(svo_ctx* ctx, const char* kernel);
 /* Measurement aid: the card's own ceilings for the roofline objects (SURVEY 8d asks for a measured FP64 figure).
@@ -1184,6 +1185,101 @@ int svo_voxel_distance_query(svo_voxel_map* map, const uint16_t* dist2, const in
  * u64, or NULL. */
 int svo_voxel_map_distance(svo_voxel_map* map, int min_count, const int* origin3, const int* dims3,
                            const svo_voxel_distance_params* params, const svo_voxel_distance_out* host_out, uint64_t* host_counts);
+
+/* Voxel map route: from every cell of the occupancy volume the cost of the cheapest way through free space to a goal cell, the first
+ * move of that way, and the cells of the way from given start cells: what a planner asks a volumetric map second, and
+ * what anything that leaves the ground plane - a drone, an arm, a vehicle on a ramp under a bridge - cannot ask the ground plan.  The
+ * ground plan route lifted to 26 neighbours.  Integers only; a converged result is the unique fixed point of the relaxation,
+ * depends on no thread order and is tested with ==.  The map argument is read for the stream ONLY.  The table is not touched.
+ * INPUTS (device memory for the _dev entry): closed, u64 words in the occupancy's layout (svo_voxel_occupancy_bytes of them),
+ * required: cell B = j0 + d0*(j1 + d1*j2) is passable iff bit B is 0 (the distance field's inflated fits as it is, and so do the
+ * occupancy bits themselves); dims3, with the occupancy's checks, messages and order; dist2, u16 per cell or NULL (the distance
+ * field's array, 0xFFFF meaning far); goals, n_goals (1..65536) u32 cell numbers; starts, n_starts (0..4096) u32 cell numbers, NULL
+ * iff n_starts == 0.
+ *   1. pen[v] = near_weight * (near_r2 - dist2[v]) where dist2 is given and dist2[v] < near_r2, else 0 (0xFFFF is far, a NULL dist2
+ *      is far everywhere).
+ *   2. The 26 neighbours are coded k = 9*(dj2+1) + 3*(dj1+1) + (dj0+1), 0..26 without 13.  A move from v to u is allowed iff both
+ *      cells are inside the volume and passable and every other cell of the box spanned by v and u is passable: 2 cells for an
+ *      edge move (two coordinates change), 6 for a vertex move (three change) - the ground plan route's no-corner-cutting rule in
+ *      3D.  Axis 0 never runs on from the end of one row into the next.  The move costs w * (16 + pen[u]), w = 5 / 7 / 9 for 1 / 2
+ *      / 3 changed coordinates: the penalty of the cell entered.  One step stays below 2^24.  With these weights a one-layer
+ *      volume (d2 = 1) has exactly the ground plan route's 5-7 field.
+ *   3. A goal >= d0*d1*d2 or on a closed cell is ignored; the others have cost 0.
+ *   4. cost[B] (u32, required) is the cheapest sum of move costs from B to any used goal if that sum is <= max_cost, else
+ *      SVO_VOXEL_ROUTE_NONE = 0xFFFFFFFF; closed cells are NONE.  Every prefix of a route within the cap is within the cap, so the
+ *      capped field is the true one truncated; candidates never exceed 0x7F000000 + 2^24, so u32 arithmetic does not wrap.
+ *   5. next[B] (u8, optional) is 13 at a used goal, otherwise the smallest k whose move is allowed and has cost[u_k] + step ==
+ *      cost[B], and 255 where cost is NONE.  Following next strictly lowers cost, so it ends at a goal.
+ *   6. Paths (optional, all three or none): path n_starts x max_path u32, path_len n_starts u32, path_status n_starts u8.  Row i holds
+ *      the cells from starts[i] along next to the goal, both ends included; path_len[i] is the full number of cells, only the first
+ *      max_path are written and row entries past the written ones are not touched.  Status SVO_VOXEL_ROUTE_OK, _TRUNCATED (len >
+ *      max_path), _UNREACHED (cost NONE; len 0), _OUT_OF_VOLUME (len 0) or _NOT_CONVERGED (len 0).
+ *   7. counts: 8 u64 on the device, or NULL: {n_goals_used, n_reached, n_unreached, n_closed, converged, rounds_run, 0, 0}.  They
+ *      are zeroed on the stream.  n_reached counts passable cells with a cost, goals included; n_reached + n_unreached + n_closed
+ *      = d0*d1*d2; n_goals_used counts list entries, so a duplicate counts twice.
+ *   8. The call enqueues max_rounds relaxation rounds.  converged is 1 iff a further round would have nothing to do.  If it is 0,
+ *      cost holds upper bounds whose bits may depend on timing, next and path are not written, every path_len is 0 and every status
+ *      _NOT_CONVERGED, and the three cell counts stay 0.  rounds_run (the last round of this call in which a tile had work) is
+ *      reported but may depend on how workgroups interleave.  A call with resume = 1, the same closed, dims3, dist2, goals and
+ *      params and the same workspace and cost buffers untouched since, continues where the earlier call stopped; repeating such
+ *      calls reaches converged = 1 and the unique field.
+ *   9. workspace: svo_voxel_route_workspace_bytes(dims3, &bytes) bytes of device memory, 8-byte aligned, contents free on entry
+ *      unless resume: a header, two activity words per tile and one direction byte per cell.  closed, dist2, goals and starts are
+ *      only read and must not overlap an output.
+ *  10. svo_voxel_occupancy_route_dev refuses, in this order, each with SVO_ERR_INVALID, the argument named, nothing launched and the
+ *      context still usable: null map; null params; near_r2 > 254^2; near_weight * near_r2 > 2^20; max_cost outside 1..0x7F000000;
+ *      max_rounds outside 1..4096; max_path outside 1..2^20 (only when n_starts > 0); resume not 0 or 1; the dims refusals of the
+ *      occupancy; null closed, then closed not 8-byte aligned; null goals; n_goals outside 1..65536; n_starts outside 0..4096;
+ *      starts NULL with n_starts > 0, then non-NULL with n_starts == 0; null workspace; null out; null cost; any of path, path_len,
+ *      path_status NULL while another is not, then non-NULL with n_starts == 0; cost, goals, starts, path, path_len off 4 bytes;
+ *      dist2 off 2 bytes; workspace, then counts off 8 bytes.
+ * UNIQUENESS.  With positive integer step costs the equations cost[goal] = 0, cost[v] = min over allowed moves of cost[u] + step have
+ * one solution, the shortest-route cost; relaxation only lowers a word towards it and never below, in whatever order cells are
+ * relaxed.  That is what lets the tiled parallel form be compared with == against Dijkstra.
+ * The defaults are NOT tuned on real data: near_r2 0, near_weight 0, max_cost 0x7F000000, max_rounds 32, max_path 4096, resume 0.
+ * 32 rounds cover random clutter and open space in a volume of 128 x 32 x 128 (the CPU trial of DESIGN 7v); a larger volume, a goal
+ * far from the volume's centre or a maze of slabs takes more rounds or resume.
+ * Order of use: occupancy, then distance (for inflated and dist2), then the route.  The pipeline never computes a route by itself
+ * (INTEGRATION 4a). */
+#define SVO_VOXEL_ROUTE_NONE 0xFFFFFFFFu
+#define SVO_VOXEL_ROUTE_MAX_COST 0x7F000000u
+enum { SVO_VOXEL_ROUTE_OK = 0, SVO_VOXEL_ROUTE_TRUNCATED = 1, SVO_VOXEL_ROUTE_UNREACHED = 2, SVO_VOXEL_ROUTE_OUT_OF_VOLUME = 3,
+       SVO_VOXEL_ROUTE_NOT_CONVERGED = 4 };
+typedef struct svo_voxel_route_params {
+  uint32_t near_r2;     /* 0..254^2: squared radius, in voxels, inside which the penalty applies */
+  uint32_t near_weight; /* near_weight * near_r2 <= 2^20: penalty per unit of near_r2 - dist2 */
+  uint32_t max_cost;    /* 1..0x7F000000: cap on a cell's cost */
+  int max_rounds;       /* 1..4096: relaxation rounds this call enqueues */
+  int max_path;         /* 1..2^20, read only when n_starts > 0: cells written per path */
+  int resume;           /* 0 or 1: continue an earlier call's field */
+} svo_voxel_route_params;
+typedef struct svo_voxel_route_out { /* every pointer but cost may be NULL; path, path_len and path_status only together */
+  uint32_t* cost;       /* d0*d1*d2 */
+  uint8_t* next;        /* d0*d1*d2 */
+  uint32_t* path;       /* n_starts * max_path */
+  uint32_t* path_len;   /* n_starts */
+  uint8_t* path_status; /* n_starts */
+} svo_voxel_route_out;
+/* The defaults above.  Pure; SVO_ERR_INVALID for null out or a voxel_size that is not finite and > 0 (the voxel size is taken for
+ * the day the defaults depend on it; today they do not). */
+int svo_voxel_route_default_params(float voxel_size, svo_voxel_route_params* out);
+/* Rule 9.  Pure; SVO_ERR_INVALID and *bytes = 0 for dims the occupancy refuses. */
+int svo_voxel_route_workspace_bytes(const int* dims3, size_t* bytes);
+/* The cell number B of the world position xyz3 (three floats, map units) in the volume of origin3 and dims3, by exactly the distance
+ * field's rule 9: what goals and starts are formed with.  Pure; SVO_ERR_INVALID for a null pointer, a voxel_size that is not finite
+ * and > 0, an origin or dims the occupancy refuses, and a rejected or outside position. */
+int svo_voxel_occupancy_cell_of(float voxel_size, const int* origin3, const int* dims3, const float* xyz3, uint32_t* cell);
+/* DEVICE pointers, asynchronous on the map's stream.  Everything it enqueues is one "voxel_route" profile bracket. */
+int svo_voxel_occupancy_route_dev(svo_voxel_map* map, const uint64_t* closed, const int* dims3, const uint16_t* dist2,
+                                  const svo_voxel_route_params* params, const uint32_t* goals, int n_goals, const uint32_t* starts,
+                                  int n_starts, void* workspace, const svo_voxel_route_out* out, uint64_t* counts);
+/* closed and dist2 stay DEVICE pointers; goals, starts, the outputs and counts (8 u64 or NULL) are HOST arrays of any alignment.
+ * Synchronous: one device allocation for the call, freed after the stream is drained whatever failed.  The refusals of rule 10
+ * without the workspace's and the host arrays' alignments; resume = 1 is refused after the params' ranges: the workspace does not
+ * outlive the call. */
+int svo_voxel_occupancy_route(svo_voxel_map* map, const uint64_t* closed, const int* dims3, const uint16_t* dist2,
+                              const svo_voxel_route_params* params, const uint32_t* goals, int n_goals, const uint32_t* starts,
+                              int n_starts, const svo_voxel_route_out* out, uint64_t* counts);
 
 /* Voxel map grid: the ground plan of the map, an axis-aligned na x nb grid over two of the map's axes.  Per cell: the highest and
  * the lowest surface inside a height band, the mean intensity of the highest voxel, how many voxels and points fell into the cell,

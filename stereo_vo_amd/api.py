@@ -440,6 +440,58 @@ def voxel_distance_bytes(dims):
     return int(n.value)
 
 
+class VoxelRouteParams(C.Structure):
+    """svo_voxel_route_params: the penalty's squared radius in voxels (0..254^2) and its weight (near_weight * near_r2 <= 2^20), the
+    cap on a cell's cost (1..0x7F000000), the relaxation rounds one call enqueues (1..4096), the cells written per path (1..2^20,
+    read only with starts) and resume (0 or 1)."""
+    _fields_ = [("near_r2", C.c_uint32), ("near_weight", C.c_uint32), ("max_cost", C.c_uint32), ("max_rounds", C.c_int), ("max_path", C.c_int),
+                ("resume", C.c_int)]
+
+
+class VoxelRouteOut(C.Structure):
+    """svo_voxel_route_out: cost and next d0*d1*d2 elements, path n_starts x max_path, path_len and path_status n_starts; every pointer
+    but cost may be None, the three path pointers only together."""
+    _fields_ = [("cost", C.c_void_p), ("next", C.c_void_p), ("path", C.c_void_p), ("path_len", C.c_void_p), ("path_status", C.c_void_p)]
+
+
+VOXEL_ROUTE_NONE = 0xFFFFFFFF  # SVO_VOXEL_ROUTE_NONE
+VOXEL_ROUTE_MAX_COST = 0x7F000000  # SVO_VOXEL_ROUTE_MAX_COST
+VOXEL_ROUTE_COUNTS = ("n_goals_used", "n_reached", "n_unreached", "n_closed", "converged", "rounds_run")
+VOXEL_ROUTE_OK, VOXEL_ROUTE_TRUNCATED, VOXEL_ROUTE_UNREACHED, VOXEL_ROUTE_OUT_OF_VOLUME, VOXEL_ROUTE_NOT_CONVERGED = range(5)
+VOXEL_ROUTE_SELF = 13  # next at a used goal
+
+
+def voxel_route_default_params(voxel_size):
+    """svo_voxel_route_default_params: no penalty, max_cost 0x7F000000, 32 rounds, paths of up to 4096 cells, resume 0 (not tuned on
+    real data)."""
+    p = VoxelRouteParams()
+    if lib().svo_voxel_route_default_params(C.c_float(voxel_size), C.byref(p)) != 0:
+        raise SvoError("svo_voxel_route_default_params: voxel_size must be finite and > 0")
+    return p
+
+
+def voxel_route_workspace_bytes(dims):
+    """svo_voxel_route_workspace_bytes: bytes of the workspace VoxelMap.route wants for a volume of dims voxels: a header, two words
+    per tile and a byte per cell (no GPU involved)."""
+    n = C.c_size_t(0)
+    if lib().svo_voxel_route_workspace_bytes(_p(_int3(dims)), C.byref(n)) != 0:
+        raise SvoError("svo_voxel_route_workspace_bytes: each dimension in 1..2048, dims[0] a multiple of 64, the product at most 2^30")
+    return int(n.value)
+
+
+def voxel_occupancy_cell_of(voxel_size, origin, dims, xyz):
+    """svo_voxel_occupancy_cell_of: the cell number j0 + d0 * (j1 + d1 * j2) of the world position xyz (three float32, map units) in the
+    volume of origin and dims, by the distance query's rule; what route() takes as goals and starts.  Raises SvoError for a position
+    outside the volume or the key range and for refused arguments (no GPU involved)."""
+    x = np.ascontiguousarray(xyz, np.float32).ravel()
+    if x.size != 3:
+        raise ValueError("voxel_occupancy_cell_of: xyz must hold three values")
+    cell = C.c_uint32(0)
+    if lib().svo_voxel_occupancy_cell_of(C.c_float(voxel_size), _p(_int3(origin)), _p(_int3(dims)), _p(x), C.byref(cell)) != 0:
+        raise SvoError("svo_voxel_occupancy_cell_of: the position is outside the volume or the key range, or an argument is refused")
+    return int(cell.value)
+
+
 class VoxelGridParams(C.Structure):
     """svo_voxel_grid_params: up_axis (0..2), up_sign (+1 / -1), the corner of cell (0, 0) in map units, voxels per cell edge
     (1..1024), na x nb cells (each 1..8192, na*nb <= 2^24), the height band, the span beyond which a cell is an obstacle, min_count."""
@@ -923,6 +975,8 @@ SYMBOLS = [
     "svo_voxel_occupancy_rays", "svo_voxel_occupancy_raycast_dev", "svo_voxel_occupancy_raycast_pose7_dev", "svo_voxel_map_raycast",
     "svo_voxel_distance_default_params", "svo_voxel_distance_workspace_bytes", "svo_voxel_distance_bytes", "svo_voxel_occupancy_distance_dev",
     "svo_voxel_distance_query_dev", "svo_voxel_distance_query", "svo_voxel_map_distance",
+    "svo_voxel_route_default_params", "svo_voxel_route_workspace_bytes", "svo_voxel_occupancy_cell_of", "svo_voxel_occupancy_route_dev",
+    "svo_voxel_occupancy_route",
 ]
 
 
@@ -1161,6 +1215,15 @@ def lib():
         L.svo_voxel_map_distance.argtypes = [vp, ci, vp, vp, vp, vp, vp]
         for f in ("svo_voxel_distance_default_params", "svo_voxel_distance_workspace_bytes", "svo_voxel_distance_bytes", "svo_voxel_occupancy_distance_dev",
                   "svo_voxel_distance_query_dev", "svo_voxel_distance_query", "svo_voxel_map_distance"):
+            getattr(L, f).restype = ci
+        # the route through the volume
+        L.svo_voxel_route_default_params.argtypes = [C.c_float, vp]
+        L.svo_voxel_route_workspace_bytes.argtypes = [vp, vp]
+        L.svo_voxel_occupancy_cell_of.argtypes = [C.c_float, vp, vp, vp, vp]
+        L.svo_voxel_occupancy_route_dev.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp]
+        L.svo_voxel_occupancy_route.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, ci, vp, vp]
+        for f in ("svo_voxel_route_default_params", "svo_voxel_route_workspace_bytes", "svo_voxel_occupancy_cell_of", "svo_voxel_occupancy_route_dev",
+                  "svo_voxel_occupancy_route"):
             getattr(L, f).restype = ci
         _LIB = L
     return _LIB
@@ -2057,6 +2120,47 @@ class VoxelMap:
         self.ctx._chk(self.L.svo_voxel_distance_query(self.h, dist2_ptr, _p(_int3(origin)), _p(_int3(dims)), _p(s) if len(s) else None, len(s), _p(out), _p(c)),
                       "svo_voxel_distance_query")
         return out[:len(s)], dict(zip(DISTANCE_QUERY_COUNTS, (int(v) for v in c)))
+
+    def _route_params(self, params, overrides):
+        return _params(lambda: voxel_route_default_params(self.params.voxel_size), params, **overrides)
+
+    def route(self, closed_ptr, dims, goals_ptr, n_goals, params=None, dist2_ptr=None, starts_ptr=None, n_starts=0, workspace_ptr=None, cost_ptr=None,
+              next_ptr=None, path_ptr=None, path_len_ptr=None, path_status_ptr=None, counts_ptr=None, **overrides):
+        """svo_voxel_occupancy_route_dev: the cost-to-go field to the goal cells through the free space of the bit volume behind
+        closed_ptr (the occupancy's layout, a cell passable iff its bit is 0: distance()'s inflated or occupancy()'s bits), the first
+        move per cell (26 neighbours) and the paths from the start cells.  params (a VoxelRouteParams) and / or its fields as keywords.
+        All pointers are the caller's device memory: dist2_ptr distance()'s uint16 field or None, goals_ptr n_goals and starts_ptr
+        n_starts uint32 cell numbers (voxel_occupancy_cell_of), workspace_ptr voxel_route_workspace_bytes(dims) bytes, cost_ptr one
+        uint32 per cell (required), next_ptr one uint8 per cell, path_ptr n_starts x max_path uint32, path_len_ptr uint32 and
+        path_status_ptr uint8 per start (the three together or None), counts_ptr 8 uint64 (VOXEL_ROUTE_COUNTS and two zeros) or None.
+        Asynchronous on the context's stream."""
+        prm = self._route_params(params, overrides)
+        out = VoxelRouteOut(cost_ptr, next_ptr, path_ptr, path_len_ptr, path_status_ptr)
+        self.ctx._chk(self.L.svo_voxel_occupancy_route_dev(self.h, closed_ptr, _p(_int3(dims)), dist2_ptr, C.byref(prm), goals_ptr, int(n_goals), starts_ptr,
+                                                           int(n_starts), workspace_ptr, C.byref(out), counts_ptr), "svo_voxel_occupancy_route_dev")
+
+    def route_host(self, closed_ptr, dims, goals, starts=None, dist2_ptr=None, params=None, **overrides):
+        """svo_voxel_occupancy_route: route() with host goals and starts and host results, synchronous; closed_ptr and dist2_ptr stay
+        device pointers.  Returns {"cost" (d2, d1, d0) uint32 with VOXEL_ROUTE_NONE, "next" (d2, d1, d0) uint8, "counts"
+        {VOXEL_ROUTE_COUNTS}} and, with starts, "path" (n_starts, max_path) uint32 (VOXEL_ROUTE_NONE where nothing was written),
+        "path_len" uint32 and "path_status" uint8 per start."""
+        prm = self._route_params(params, overrides)
+        d = _int3(dims)
+        shape = (max(int(d[2]), 1), max(int(d[1]), 1), max(int(d[0]), 1))
+        goals = np.ascontiguousarray(goals, np.uint32).ravel()
+        starts = None if starts is None else np.ascontiguousarray(starts, np.uint32).ravel()
+        ns = 0 if starts is None else len(starts)
+        res = {"cost": np.empty(shape, np.uint32), "next": np.full(shape, 255, np.uint8)}
+        if ns:
+            if not 1 <= prm.max_path <= 1 << 20:
+                raise SvoError("svo_voxel_occupancy_route: voxel_route: max_path outside 1..2^20")
+            res.update(path=np.full((ns, prm.max_path), VOXEL_ROUTE_NONE, np.uint32), path_len=np.zeros(ns, np.uint32), path_status=np.zeros(ns, np.uint8))
+        out = VoxelRouteOut(*(res[k].ctypes.data if k in res else None for k in ("cost", "next", "path", "path_len", "path_status")))
+        c = np.zeros(8, np.uint64)
+        self.ctx._chk(self.L.svo_voxel_occupancy_route(self.h, closed_ptr, _p(d), dist2_ptr, C.byref(prm), _p(goals) if len(goals) else None, len(goals),
+                                                       _p(starts) if ns else None, ns, C.byref(out), _p(c)), "svo_voxel_occupancy_route")
+        res["counts"] = dict(zip(VOXEL_ROUTE_COUNTS, (int(v) for v in c)))
+        return res
 
     def insert_keyframe_clouds(self, table, poses7):
         """The list Pipeline.keyframe_clouds() / PipelineGroup.keyframe_clouds() returns, one pose7 per entry: every entry's device

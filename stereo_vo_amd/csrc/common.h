@@ -158,7 +158,8 @@ enum SvoProfTag { SVO_PROF_NONE = 0, SVO_PROF_CORNER_RESPONSE, SVO_PROF_CORNER_N
                   SVO_PROF_VOXEL_GRID, SVO_PROF_GRID_CLEARANCE, SVO_PROF_GRID_ROUTE, SVO_PROF_GRID_FRONTIER, SVO_PROF_GRID_VIEW,
                   SVO_PROF_GRID_SURFACE, SVO_PROF_GRID_WAYPOINTS, SVO_PROF_VOXEL_ALIGN, SVO_PROF_VOXEL_NORMALS,
                   SVO_PROF_VOXEL_ALIGN_PLANE, SVO_PROF_VOXEL_OCCUPANCY, SVO_PROF_VOXEL_LOCATE,
-                  SVO_PROF_VOXEL_COARSE, SVO_PROF_VOXEL_RAYS, SVO_PROF_VOXEL_DISTANCE, SVO_PROF_VOXEL_DISTANCE_QUERY };
+                  SVO_PROF_VOXEL_COARSE, SVO_PROF_VOXEL_RAYS, SVO_PROF_VOXEL_DISTANCE, SVO_PROF_VOXEL_DISTANCE_QUERY,
+                  SVO_PROF_VOXEL_ROUTE };
 
 // RAII event pair around one launch of the selected kernel (no-op for every other kernel).
 struct SvoProfScope {

@@ -33,7 +33,7 @@ extern "C" int svo_profile_select(svo_ctx* ctx, const char* kernel) {
                                 "voxel_carve", "voxel_copy", "voxel_render", "voxel_remove", "voxel_move", "voxel_grid", "grid_clearance",
                                 "grid_route", "grid_frontier", "grid_view", "grid_surface", "grid_waypoints", "voxel_align",
                                 "voxel_normals", "voxel_align_plane", "voxel_occupancy", "voxel_locate", "voxel_coarse", "voxel_rays",
-                                "voxel_distance", "voxel_distance_query"};
+                                "voxel_distance", "voxel_distance_query", "voxel_route"};
   int tag = 0;
   if (kernel && kernel[0]) {
     tag = -1;

@@ -233,7 +233,24 @@ VOXEL_HD inline float voxel_distance_clearance(uint32_t d2, float voxel_size) {
   return d2 == VOXEL_DISTANCE_NONE ? __builtin_inff() : (float)(sqrt((double)d2) * (double)voxel_size);
 }
 
-// ----------------------------------------------------------------------------- a sphere's record
+// ----------------------------------------------------------------------------- a position's cell, a sphere's record
+// Rule 9's cell of the world position xyz: VOXEL_SPHERE_REJECTED, VOXEL_SPHERE_OUTSIDE, or VOXEL_SPHERE_FREE with *cell = B.
+VOXEL_HD inline int voxel_distance_cell_of(const float* xyz, float voxel_size, const int* origin, const int* dims, size_t* cell) {
+  const double vs = (double)voxel_size;
+  double q[3];
+  for (int r = 0; r < 3; ++r) {
+    q[r] = (double)xyz[r] / vs;
+    if (!(q[r] >= -VOXEL_LOCATE_LIMIT && q[r] < VOXEL_LOCATE_LIMIT)) return VOXEL_SPHERE_REJECTED;  // NaN and the infinities fail too
+  }
+  int j[3];
+  for (int r = 0; r < 3; ++r) {
+    j[r] = (int)floor(q[r]) - origin[r];
+    if (j[r] < 0 || j[r] >= dims[r]) return VOXEL_SPHERE_OUTSIDE;
+  }
+  *cell = (size_t)j[0] + (size_t)dims[0] * ((size_t)j[1] + (size_t)dims[1] * (size_t)j[2]);
+  return VOXEL_SPHERE_FREE;
+}
+
 // s: {x, y, z, radius}.  *beyond: the centre's cell is inside the volume and its dist2 is NONE16.
 VOXEL_HD inline svo_voxel_sphere_hit voxel_distance_query_one(const float* s, float voxel_size, const int* origin, const int* dims, const uint16_t* dist2,
                                                               bool* beyond) {
@@ -242,18 +259,9 @@ VOXEL_HD inline svo_voxel_sphere_hit voxel_distance_query_one(const float* s, fl
   *beyond = false;
   const double vs = (double)voxel_size, rad = (double)s[3];
   if (!(rad >= 0.0 && rad <= DBL_MAX)) return h;  // a NaN fails
-  double q[3];
-  for (int r = 0; r < 3; ++r) {
-    q[r] = (double)s[r] / vs;
-    if (!(q[r] >= -VOXEL_LOCATE_LIMIT && q[r] < VOXEL_LOCATE_LIMIT)) return h;  // NaN and the infinities fail too
-  }
-  h.code = VOXEL_SPHERE_OUTSIDE;
-  int j[3];
-  for (int r = 0; r < 3; ++r) {
-    j[r] = (int)floor(q[r]) - origin[r];
-    if (j[r] < 0 || j[r] >= dims[r]) return h;
-  }
-  const size_t B = (size_t)j[0] + (size_t)dims[0] * ((size_t)j[1] + (size_t)dims[1] * (size_t)j[2]);
+  size_t B = 0;
+  h.code = (uint32_t)voxel_distance_cell_of(s, voxel_size, origin, dims, &B);
+  if (h.code != VOXEL_SPHERE_FREE) return h;
   const uint16_t d = dist2[B];
   *beyond = d == VOXEL_DISTANCE_NONE16;
   h.cell = (uint32_t)B;

@@ -117,6 +117,15 @@ One process, one GPU, HIP events (svo_profile_select) around the launches:
      bytes the workspace layout moves per cell (8.125 for dist2 alone, 22.25 for all four outputs) and the steps per cell, counted
      on the host by the search's stop rule: the words each wavefront reads from the volume's words (axis 0), and the outward steps
      from the downloaded partial and final squares (axes 1 and 2).  --align-only runs this section too.
+ 23. route through the volume: on the same maps and over the same volume, svo_voxel_occupancy_route_dev ("voxel_route" bracket: its
+     memsets and every launch, mean of 5) over the distance field's `inflated` at inflate_radius 0 (the occupancy itself) and 0.3 m
+     (max_dist 8), without dist2 and with it (near_r2 16, near_weight 4), the goal at the free cell nearest the volume's centre: the
+     rounds a call of 1,024 needs (rounds_run), cost alone at rounds_run + 1 and the time per round, the same with 64 more rounds
+     (what an enqueued round with no active tile costs), at the default max_rounds, and with next and 64 paths from random free cells;
+     beside each the time hbm_copy (measured in the same run) needs for one pass over the arrays (12.125 B per cell for cost alone,
+     + 2 with dist2; 18.25 with next, + 4 with dist2).  The tile shape is the library's: a library built with
+     -DSVO_EXP_VOXEL_ROUTE_CUBE (SVO_EXTRA_HIPFLAGS) runs the same section with 8 x 8 x 8 tiles.  --align-only runs this section too;
+     --route-only runs section 7's fill and this section alone.
 Prints one JSON line; --out also writes the text report.  Needs the GPU: there is no fallback."""
 import argparse
 import json
@@ -290,7 +299,7 @@ def standalone(S, torch, batch, warmup, reps):
     return out
 
 
-def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy, only_align=False):
+def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy, only_align=False, only_route=False):
     """Section 7: the batch's clouds into one map.  Cloud i goes in under a small rotation and 0.8 m of forward motion per frame
     (the synthetic stream's step), so consecutive clouds see almost the same surfaces, as consecutive keyframes do."""
     import voxel_ref as V
@@ -352,12 +361,17 @@ def voxel(S, torch, ctx, cam, dm, dl, batch, warmup, copy, only_align=False):
                         "stats_after_fresh": stats[vs], "load": stats[vs]["n_voxels"] / vm.capacity,
                         "extract_ms": ms / k, "extract_n_total": int(c2.cpu()[0]), "table_bytes_bound_ms": 1e3 * 40 * vm.capacity / copy,
                         "extract_share_of_bound": (1e3 * 40 * vm.capacity / copy) / (ms / k)})
+            if only_route:
+                out[-1].update(voxel_route_view(torch, ctx, vm, 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, copy))
+                vm.close()
+                continue
             out[-1].update(remove_and_move(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, copy))
             out[-1].update(align_view(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup))
             out[-1].update(normals_view(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, out[-1]["align"]))
             out[-1].update(locate_view(torch, ctx, vm, pts[batch - 1], n[batch - 1], 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, out[-1]["align"], out[-1]["extract_ms"]))
             out[-1].update(rays_view(torch, ctx, cam, vm, 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, out[-1]["locate"]))
             out[-1].update(distance_view(torch, ctx, vm, 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, out[-1]["locate"], copy))
+            out[-1].update(voxel_route_view(torch, ctx, vm, 0.004 * (batch - 1), 0.8 * (batch - 1), warmup, copy))
             if only_align:
                 vm.close()
                 continue
@@ -757,6 +771,107 @@ def distance_line(k):
               f"{1e3 * r['all_ms']:.1f} us ({r['all_ms'] / k['bound_all_ms']:.1f} x); counts {r['counts']} (sources, reached, unreached, inflated); per cell "
               f"{r['steps'][0]:.2f} words along axis 0, {r['steps'][1]:.1f} + {r['steps'][2]:.1f} steps along axes 1 and 2; query of {k['spheres']} spheres "
               f"{1e3 * r['query_ms']:.1f} us, counts {r['query_counts']} (n, free, collides, outside, rejected, beyond)\n")
+    return s
+
+
+def voxel_route_view(torch, ctx, vm, angle, forward, warmup, copy):
+    """Section 23 for one filled map.  Nothing in the map changes."""
+    import voxel_locate_ref as L
+    import voxel_rays_ref as RR
+    import voxel_ref as V
+    import voxel_route_ref as VR
+    from stereo_vo_amd import api
+    vs = float(vm.params.voxel_size)
+    c2w = np.asarray(V.rot_y(angle, (0.0, 0.0, forward)), np.float64).reshape(12)
+    dims = tuple(L.default_params().dims)
+    origin = RR.origin_of((c2w[3], c2w[7], c2w[11]), vs, dims)
+    cells = dims[0] * dims[1] * dims[2]
+    bits = torch.empty(cells // 64, dtype=torch.int64, device="cuda")
+    occ = torch.zeros(2, dtype=torch.int32, device="cuda")
+    dws = torch.empty(api.voxel_distance_workspace_bytes(dims, False) // 8, dtype=torch.int64, device="cuda")
+    d2 = torch.empty(cells, dtype=torch.int16, device="cuda")
+    infl = torch.empty(cells // 64, dtype=torch.int64, device="cuda")
+    ws = torch.empty(api.voxel_route_workspace_bytes(dims) // 8, dtype=torch.int64, device="cuda")
+    cost = torch.empty(cells, dtype=torch.int32, device="cuda")
+    nxt = torch.empty(cells, dtype=torch.uint8, device="cuda")
+    n_starts, max_path = 64, 4096
+    path = torch.empty(n_starts * max_path, dtype=torch.int32, device="cuda")
+    plen = torch.empty(n_starts, dtype=torch.int32, device="cuda")
+    pst = torch.empty(n_starts, dtype=torch.uint8, device="cuda")
+    cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
+    vm.occupancy(bits.data_ptr(), origin, dims, counts_ptr=occ.data_ptr())
+    out = {"dims": list(dims), "tile": None, "occupancy_counts": None, "hbm_copy_bytes_per_s": copy, "runs": []}
+    tiles = (api.voxel_route_workspace_bytes(dims) - 64 - cells) // 8
+    out["tiles"] = int(tiles)
+    out["tile"] = "8 x 8 x 8" if api.voxel_route_workspace_bytes((64, 8, 4)) == 64 + 8 * 8 + 2048 else "16 x 8 x 4"  # 8 tiles or 4: the library's shape
+    for radius in (0.0, 0.3):
+        vm.distance(bits.data_ptr(), dims, workspace_ptr=dws.data_ptr(), dist2_ptr=d2.data_ptr(), inflated_ptr=infl.data_ptr(), max_dist=8, inflate_radius=radius)
+        torch.cuda.synchronize()
+        out["occupancy_counts"] = [int(v) for v in occ.cpu()]
+        closed = VR.unpack(infl.cpu().numpy().view(np.uint64), dims)
+        free = np.flatnonzero(~closed.ravel())
+        centre = dims[0] // 2 + dims[0] * (dims[1] // 2 + dims[1] * (dims[2] // 2))
+        goal = int(free[np.argmin(np.abs(free - centre))])  # the camera's cell, or the free cell whose number is nearest to it
+        rng = np.random.default_rng(23)
+        goals = torch.from_numpy(np.array([goal], np.uint32).view(np.int32)).cuda()
+        starts = torch.from_numpy(free[rng.integers(0, len(free), n_starts)].astype(np.uint32).view(np.int32)).cuda()
+
+        def call(max_rounds, with_d2, paths):
+            vm.route(infl.data_ptr(), dims, goals.data_ptr(), 1, dist2_ptr=d2.data_ptr() if with_d2 else None, starts_ptr=starts.data_ptr() if paths else None,
+                     n_starts=n_starts if paths else 0, workspace_ptr=ws.data_ptr(), cost_ptr=cost.data_ptr(), next_ptr=nxt.data_ptr() if paths else None,
+                     path_ptr=path.data_ptr() if paths else None, path_len_ptr=plen.data_ptr() if paths else None, path_status_ptr=pst.data_ptr() if paths else None,
+                     counts_ptr=cnt.data_ptr(), near_r2=16 if with_d2 else 0, near_weight=4 if with_d2 else 0, max_rounds=max_rounds, max_path=max_path)
+
+        def timed(max_rounds, with_d2, paths):
+            for _ in range(warmup):
+                call(max_rounds, with_d2, paths)
+            ctx.profile_select("voxel_route")
+            for _ in range(5):
+                call(max_rounds, with_d2, paths)
+            ms, k = ctx.profile_read()
+            ctx.profile_select("")
+            assert k == 5, k
+            return ms / k
+
+        for with_d2 in (False, True):
+            k = {"inflate_radius": radius, "closed": int(closed.sum()), "with_dist2": with_d2}
+            call(1024, with_d2, False)
+            ctx.sync()
+            c = [int(v) for v in cnt.cpu()]
+            k["counts"], k["rounds_run"] = c[:5], c[5]
+            need = min(c[5] + 1, 4096)  # one more round finds nothing to do
+            k["cost_ms"] = timed(need, with_d2, False)
+            ctx.sync()
+            k["converged_at_need"] = int(cnt.cpu()[4])
+            k["cost_ms_64_more"] = timed(need + 64, with_d2, False)
+            k["empty_round_us"] = 1e3 * (k["cost_ms_64_more"] - k["cost_ms"]) / 64
+            k["ms_per_round"] = k["cost_ms"] / max(c[5], 1)
+            k["default_ms"] = timed(api.voxel_route_default_params(vs).max_rounds, with_d2, False)
+            ctx.sync()
+            k["converged_at_default"] = int(cnt.cpu()[4])
+            k["paths_ms"] = timed(need, with_d2, True)
+            ctx.sync()
+            lens = plen.cpu().numpy().view(np.uint32)
+            k["longest_path"], k["path_status"] = int(lens.max()), np.bincount(pst.cpu().numpy(), minlength=5).tolist()
+            # one pass over the arrays: cost 4 B by the memset, 4 read and 4 written by the tiles, closed 1/8 (+ dist2 2); with next and
+            # paths the finish launch reads cost 4 + closed 1/8 (+ dist2 2) and writes next and the workspace's byte
+            k["bound_cost_ms"] = 1e3 * (12.125 + (2 if with_d2 else 0)) * cells / copy
+            k["bound_paths_ms"] = 1e3 * (12.125 + 6.125 + (4 if with_d2 else 0)) * cells / copy
+            out["runs"].append(k)
+    return {"voxel_route": out}
+
+
+def voxel_route_line(k):
+    """Section 23's lines of the text report for one voxel_route_view."""
+    s = (f"route through {k['dims']}, tile {k['tile']} ({k['tiles']} workgroups per round), goal at the free cell nearest the centre, 64 random free starts, max_dist 8 "
+         f"(one \"voxel_route\" bracket, mean of 5); occupancy counts {k['occupancy_counts']}; hbm_copy {k['hbm_copy_bytes_per_s'] / 1e12:.3f} TB/s in this run\n")
+    for r in k["runs"]:
+        s += (f"  inflate_radius {r['inflate_radius']} m ({r['closed']} closed cells), {'with' if r['with_dist2'] else 'without'} dist2: counts {r['counts']} (goals used, reached, "
+              f"unreached, closed, converged at 1,024 rounds), rounds_run {r['rounds_run']}; cost alone at rounds_run + 1: {r['cost_ms']:.3f} ms (converged "
+              f"{r['converged_at_need']}) = {1e3 * r['ms_per_round']:.1f} us per round; with 64 more rounds {r['cost_ms_64_more']:.3f} ms -> {r['empty_round_us']:.2f} us per "
+              f"round that finds nothing to do; at the default max_rounds {r['default_ms']:.3f} ms (converged {r['converged_at_default']}); with next and 64 paths "
+              f"{r['paths_ms']:.3f} ms, longest path {r['longest_path']} cells, statuses {r['path_status']}; one pass over the arrays at hbm_copy "
+              f"{1e3 * r['bound_cost_ms']:.0f} us (cost alone) / {1e3 * r['bound_paths_ms']:.0f} us (with next)\n")
     return s
 
 
@@ -1733,7 +1848,8 @@ def main():
     ap.add_argument("--ledger-only", action="store_true", help="of the 96-lane loads only clouds alone and clouds with the ledger loop")
     ap.add_argument("--surface-only", action="store_true", help="section 16's seeded grids alone")
     ap.add_argument("--waypoints-only", action="store_true", help="section 17's seeded grid alone")
-    ap.add_argument("--align-only", action="store_true", help="section 7's fill and sections 10, 18, 19, 20, 21 and 22 alone")
+    ap.add_argument("--align-only", action="store_true", help="section 7's fill and sections 10, 18, 19, 20, 21, 22 and 23 alone")
+    ap.add_argument("--route-only", action="store_true", help="section 7's fill and section 23 alone")
     ap.add_argument("--out", help="write the text report here as well")
     a = ap.parse_args()
     import torch
@@ -1761,6 +1877,27 @@ def main():
                 for k in res["waypoint_synthetic"]:
                     f.write(f"waypoints over a synthetic {k['cells'][0]} x {k['cells'][1]} grid, blocked density {k['density']}: " + waypoint_line(k))
         return
+    if a.route_only:
+        ctx = S.Context(W, H, max_batch=a.batch, max_corners=64, max_candidates=1 << 12, max_features=64)
+        p = S.synth_default(W, H)
+        cam = S.CameraInfo(p.focal, p.cx, p.cy, 0, 0, 0, 0, p.baseline)
+        pairs = [S.synth_render(p, i) for i in range(a.batch)]
+        dl = torch.from_numpy(np.stack([x[0] for x in pairs])).cuda()
+        dr = torch.from_numpy(np.stack([x[1] for x in pairs])).cuda()
+        dm = torch.empty((a.batch, H, W), dtype=torch.int16, device="cuda")
+        torch.cuda.synchronize()
+        copy = ctx.measure_peak("hbm_copy")
+        ctx.stereo_bm_batch(dl.data_ptr(), dr.data_ptr(), a.batch, W, H, W, W * H, dm.data_ptr(), NDISP, BLOCK)
+        ctx.sync()
+        res = {"hbm_copy_bytes_per_s": copy, "voxel": voxel(S, torch, ctx, cam, dm, dl, a.batch, 3, copy, only_route=True)}
+        ctx.close()
+        print(json.dumps(res))
+        if a.out:
+            with open(a.out, "w") as f:
+                for c in res["voxel"]:
+                    f.write(f"voxel map, clouds at step {c['cloud_step']} ({c['points_per_cloud']:.0f} points per cloud), voxel {c['voxel_size']} m, 2^{c['capacity_log2']} slots, "
+                            f"{c['stats_after_fresh']['n_voxels']} voxels, load {c['load']:.3f}:\n  " + voxel_route_line(c['voxel_route']))
+        return
     if a.align_only:
         ctx = S.Context(W, H, max_batch=a.batch, max_corners=64, max_candidates=1 << 12, max_features=64)
         p = S.synth_default(W, H)
@@ -1782,7 +1919,7 @@ def main():
                     f.write(f"voxel map, clouds at step {c['cloud_step']} ({c['points_per_cloud']:.0f} points per cloud), voxel {c['voxel_size']} m, 2^{c['capacity_log2']} slots, "
                             f"{c['stats_after_fresh']['n_voxels']} voxels, load {c['load']:.3f}:\n  align: " + align_line(c['align'], c['insert_ms']) +
                             "  normals: " + normals_line(c['normals'], c['align'], c['insert_ms']) + "  locate: " + locate_line(c['locate'], c['align']) + "  sight lines: " + rays_line(c['rays']) +
-                            "  " + distance_line(c['distance']))
+                            "  " + distance_line(c['distance']) + "  " + voxel_route_line(c['voxel_route']))
         return
     res = {"standalone": standalone(S, torch, a.batch, 3, a.reps)}
     print("bench_dense: standalone sections done", file=sys.stderr, flush=True)
@@ -1884,7 +2021,7 @@ def main():
                         f"{1e3 * c['remove_move_bound_ms']:.2f} us\n"
                         "  align: " + align_line(c['align'], c['insert_ms']) +
                         "  normals: " + normals_line(c['normals'], c['align'], c['insert_ms']) + "  locate: " + locate_line(c['locate'], c['align']) + "  sight lines: " + rays_line(c['rays']) +
-                        "  " + distance_line(c['distance']))
+                        "  " + distance_line(c['distance']) + "  " + voxel_route_line(c['voxel_route']))
             for k in s["clearance_synthetic"]:
                 f.write(f"clearance of a synthetic {k['cells'][0]} x {k['cells'][1]} grid, source density {k['density']}, max_dist {k['max_dist']} (all four outputs, mean of 5): "
                         f"{1e3 * k['ms']:.1f} us, counts {k['counts']} (sources, reached, unreached, blocked); 22 B per cell at hbm_copy {1e3 * k['bound_ms']:.1f} us -> "
