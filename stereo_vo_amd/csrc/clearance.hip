@@ -145,9 +145,6 @@ __global__ __launch_bounds__(CL_T) void clearance_column_kernel(ClearanceColumnA
 }
 
 // ----------------------------------------------------------------------------- host side
-// A refusal of host/clearance_args.h goes into the context: `call` is one of its checks with `&err` as its last argument.
-#define CLEARANCE_CHECK(ctx, call) do { const char* err = nullptr; if (call) { (ctx)->err = err; return SVO_ERR_INVALID; } } while (0)
-
 extern "C" int svo_grid_clearance_default_params(const svo_voxel_grid_params* grid, float voxel_size, svo_grid_clearance_params* out) {
   return clearance_default_params(grid, voxel_size, out);
 }
@@ -158,7 +155,7 @@ extern "C" int svo_grid_clearance_dev(svo_ctx* ctx, const uint8_t* cls, const sv
                                       const svo_grid_clearance_out* out, uint64_t* counts) {
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
-  CLEARANCE_CHECK(ctx, clearance_check(cls, prm, workspace, out, counts, &err));
+  SVO_ARGS_CHECK(ctx, clearance_check(cls, prm, workspace, out, counts, &err));
   ClearanceRowArgs a{};
   a.cls = cls; a.offsets = static_cast<int32_t*>(workspace);
   a.n = (size_t)prm->na * (size_t)prm->nb;
@@ -185,39 +182,33 @@ extern "C" int svo_grid_clearance(svo_ctx* ctx, const uint8_t* cls, const svo_gr
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
   SVO_REQUIRE(ctx, cls, "grid_clearance: null cls");
-  CLEARANCE_CHECK(ctx, clearance_params_check(prm, &err));
-  CLEARANCE_CHECK(ctx, clearance_out_check(out, false, &err));
-  const size_t n = (size_t)prm->na * (size_t)prm->nb, n16 = (n + 15) & ~(size_t)15;  // every part 16-byte aligned
-  struct Temp { void* p; ~Temp() { if (p) (void)hipFree(p); } } hold{nullptr};
-  SVO_HIP_CHECK(ctx, hipMalloc(&hold.p, 4 * sizeof(u64) + 18 * n16));  // 4 counts | offsets | dist2 | nearest | clearance | blocked | cls
-  unsigned char* const d = static_cast<unsigned char*>(hold.p);
-  unsigned char* const d_ws = d + 4 * sizeof(u64);
+  SVO_ARGS_CHECK(ctx, clearance_params_check(prm, &err));
+  SVO_ARGS_CHECK(ctx, clearance_out_check(out, false, &err));
+  const size_t n = (size_t)prm->na * (size_t)prm->nb;
+  SvoParts parts;
+  const size_t o_counts = parts.add(4 * sizeof(u64)), o_ws = parts.add(clearance_workspace_bytes(prm->na, prm->nb)), o_dist2 = parts.add(4 * n),
+               o_nearest = parts.add(4 * n), o_clearance = parts.add(4 * n), o_blocked = parts.add(n), o_cls = parts.add(n);
+  SvoTemp d;
+  SVO_HIP_CHECK(ctx, hipMalloc(&d.p, parts.total()));
   svo_grid_clearance_out o{};
-  o.dist2 = reinterpret_cast<uint32_t*>(d_ws + 4 * n16);
-  o.nearest = reinterpret_cast<uint32_t*>(d_ws + 8 * n16);
-  o.clearance = reinterpret_cast<float*>(d_ws + 12 * n16);
-  o.blocked = d_ws + 16 * n16;
-  uint8_t* const d_cls = d_ws + 17 * n16;
-  svo_grid_clearance_out asked = o;  // what the caller did not ask for is not written
-  if (!out->nearest) asked.nearest = nullptr;
-  if (!out->clearance) asked.clearance = nullptr;
-  if (!out->blocked) asked.blocked = nullptr;
+  o.dist2 = d.at<uint32_t>(o_dist2);
+  o.nearest = out->nearest ? d.at<uint32_t>(o_nearest) : nullptr;  // what the caller did not ask for is not written
+  o.clearance = out->clearance ? d.at<float>(o_clearance) : nullptr;
+  o.blocked = out->blocked ? d.at(o_blocked) : nullptr;
   u64 c[4] = {0, 0, 0, 0};
   hipStream_t st = ctx->stream;
-  // The stream is drained before the temporary buffer goes away, whatever failed; the _dev entry's refusal is reported first.
-  hipError_t e = hipMemcpyAsync(d_cls, cls, n, hipMemcpyHostToDevice, st);
-  const int rc = e == hipSuccess ? svo_grid_clearance_dev(ctx, d_cls, prm, d_ws, &asked, reinterpret_cast<uint64_t*>(d)) : SVO_OK;
-  if (e == hipSuccess && !rc) {
-    e = hipMemcpyAsync(out->dist2, o.dist2, 4 * n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out->nearest) e = hipMemcpyAsync(out->nearest, o.nearest, 4 * n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out->clearance) e = hipMemcpyAsync(out->clearance, o.clearance, 4 * n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out->blocked) e = hipMemcpyAsync(out->blocked, o.blocked, n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, st);
-  }
-  const hipError_t e2 = hipStreamSynchronize(st);
+  const int rc = svo_host_call(
+      ctx, "grid_clearance", hipMemcpyAsync(d.at(o_cls), cls, n, hipMemcpyHostToDevice, st),
+      [&] { return svo_grid_clearance_dev(ctx, d.at(o_cls), prm, d.at(o_ws), &o, d.at<uint64_t>(o_counts)); },
+      [&] {
+        hipError_t e = hipMemcpyAsync(out->dist2, o.dist2, 4 * n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out->nearest) e = hipMemcpyAsync(out->nearest, o.nearest, 4 * n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out->clearance) e = hipMemcpyAsync(out->clearance, o.clearance, 4 * n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out->blocked) e = hipMemcpyAsync(out->blocked, o.blocked, n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(c, d.at(o_counts), sizeof(c), hipMemcpyDeviceToHost, st);
+        return e;
+      });
   if (rc) return rc;
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) { ctx->err = std::string("grid_clearance: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
   if (counts) for (int k = 0; k < 4; ++k) counts[k] = c[k];
   return SVO_OK;
 }

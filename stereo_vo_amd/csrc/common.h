@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "host_call.h"
 #include "svo.h"
 
 // Last-error text of a context.  The caller thread and the asynchronous bundle-adjustment worker may both report
@@ -213,6 +214,26 @@ struct SvoScratch {
     return p;
   }
 };
+
+// The one temporary device allocation of a synchronous entry, freed when the entry returns; at<T>(off) is a part of it (SvoParts).
+struct SvoTemp {
+  void* p = nullptr;
+  ~SvoTemp() { if (p) (void)hipFree(p); }
+  template <typename T = unsigned char>
+  T* at(size_t off) const { return reinterpret_cast<T*>(static_cast<unsigned char*>(p) + off); }
+};
+
+// What every synchronous entry does around its _dev entry (svo_host_sequence, host/host_call.h): `e_up` is what the copies up left,
+// `dev` runs the _dev entry, `back` queues the copies back to the host; the stream is drained before the caller's SvoTemp goes away,
+// whatever failed; the _dev entry's refusal is reported first (its message stands), a HIP error second, as "`what`: its text".
+template <typename Dev, typename Back>
+inline int svo_host_call(svo_ctx* ctx, const char* what, hipError_t e_up, Dev dev, Back back) {
+  hipError_t e = hipSuccess;
+  const int rc = svo_host_sequence(e_up, dev, back, [&] { return hipStreamSynchronize(ctx->stream); }, &e);
+  if (rc) return rc;
+  if (e != hipSuccess) { ctx->err = std::string(what) + ": " + hipGetErrorString(e); return SVO_ERR_HIP; }
+  return SVO_OK;
+}
 
 #ifdef __HIPCC__
 __device__ __forceinline__ int reflect101(int i, int n) {

@@ -308,7 +308,7 @@ static int stereo_bm_batch(svo_ctx* ctx, const uint8_t* left, const uint8_t* rig
   if (rc) return rc;
   SVO_REQUIRE(ctx, disp16, t.null_disp);
   if (t.null_cost) SVO_REQUIRE(ctx, cost16, t.null_cost);
-  DENSE_CHECK(ctx, dense_batch_check(batch, ctx->lim.max_batch, width, height, row_stride, image_stride, t, &err));
+  SVO_ARGS_CHECK(ctx, dense_batch_check(batch, ctx->lim.max_batch, width, height, row_stride, image_stride, t, &err));
   SvoDensePairs src{left, right, image_stride, nullptr};
   return svo_k_stereo_dense_batch(ctx, src, batch, width, height, row_stride, num_disparities, block_size, disp16, cost16);
 }
@@ -332,7 +332,7 @@ extern "C" int svo_disparity_cloud_batch_dev(svo_ctx* ctx, const int16_t* disp16
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
   SVO_REQUIRE(ctx, disp16 && left && points && counts, "disparity_cloud: null buffer");
-  DENSE_CHECK(ctx, cloud_check(width, height, row_stride, cam, params, ctx->lim.max_width, ctx->lim.max_height, &err));
+  SVO_ARGS_CHECK(ctx, cloud_check(width, height, row_stride, cam, params, ctx->lim.max_width, ctx->lim.max_height, &err));
   SVO_REQUIRE(ctx, batch >= 1 && batch <= ctx->lim.max_batch, "disparity_cloud: batch outside 1..max_batch");
   // per-chunk counts for the largest call this context takes, once
   const size_t need = (size_t)ctx->lim.max_batch * (size_t)cloud_chunks(ctx->lim.max_width, ctx->lim.max_height, 1);
@@ -350,7 +350,7 @@ extern "C" int svo_stereo_cloud(svo_ctx* ctx, const uint8_t* left, const uint8_t
   int rc = svo_stereo_check(ctx, left, right, width, height, row_stride, num_disparities, block_size);
   if (rc) return rc;
   SVO_REQUIRE(ctx, points && n_total && n_stored, "stereo_cloud: null output");
-  DENSE_CHECK(ctx, cloud_check(width, height, row_stride, cam, params, ctx->lim.max_width, ctx->lim.max_height, &err));
+  SVO_ARGS_CHECK(ctx, cloud_check(width, height, row_stride, cam, params, ctx->lim.max_width, ctx->lim.max_height, &err));
   SvoScratch s(ctx);
   const size_t px = (size_t)width * height;
   uint8_t* dL = s.take<uint8_t>(px);

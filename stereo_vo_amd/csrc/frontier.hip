@@ -401,9 +401,6 @@ __global__ __launch_bounds__(FR_T) void frontier_write_kernel(FrontierArgs a) {
 }
 
 // ----------------------------------------------------------------------------- host side
-// A refusal of host/frontier_args.h goes into the context: `call` is one of its checks with `&err` as its last argument.
-#define FRONTIER_CHECK(ctx, call) do { const char* err = nullptr; if (call) { (ctx)->err = err; return SVO_ERR_INVALID; } } while (0)
-
 extern "C" int svo_grid_frontier_default_params(const svo_grid_clearance_params* clearance, svo_grid_frontier_params* out) {
   return frontier_default_params(clearance, out);
 }
@@ -421,7 +418,7 @@ extern "C" int svo_grid_frontiers_dev(svo_ctx* ctx, const uint8_t* cls, const ui
                                       uint64_t* counts) {
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
-  FRONTIER_CHECK(ctx, frontier_check(cls, cost, prm, workspace, out, counts, true, &err));
+  SVO_ARGS_CHECK(ctx, frontier_check(cls, cost, prm, workspace, out, counts, true, &err));
   const int na = prm->na, nb = prm->nb, mf = prm->max_frontiers;
   unsigned char* const ws = static_cast<unsigned char*>(workspace);
   FrontierArgs a{};
@@ -463,42 +460,40 @@ extern "C" int svo_grid_frontiers(svo_ctx* ctx, const uint8_t* cls, const uint8_
                                   const svo_grid_frontier_params* prm, const svo_grid_frontier_out* out, uint64_t* counts) {
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
-  FRONTIER_CHECK(ctx, frontier_check(cls, cost, prm, nullptr, out, counts, false, &err));
-  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };  // every part 16-byte aligned
-  const size_t n = (size_t)prm->na * (size_t)prm->nb, mf = (size_t)prm->max_frontiers;
-  const size_t b_ws = up16(frontier_workspace_bytes(prm->na, prm->nb, prm->max_frontiers)), b_rec = mf * sizeof(svo_grid_frontier);
-  // 8 counts | workspace | frontiers | cost | label | goal_cells | cls | blocked
-  const size_t o_ws = 8 * sizeof(u64), o_rec = o_ws + b_ws, o_cost = o_rec + up16(b_rec), o_label = o_cost + up16(4 * n),
-               o_goal = o_label + up16(4 * n), o_cls = o_goal + up16(4 * mf), o_blocked = o_cls + up16(n), total = o_blocked + up16(n);
-  struct Temp { void* p; ~Temp() { if (p) (void)hipFree(p); } } hold{nullptr};
-  SVO_HIP_CHECK(ctx, hipMalloc(&hold.p, total));
-  unsigned char* const d = static_cast<unsigned char*>(hold.p);
+  SVO_ARGS_CHECK(ctx, frontier_check(cls, cost, prm, nullptr, out, counts, false, &err));
+  const size_t n = (size_t)prm->na * (size_t)prm->nb, mf = (size_t)prm->max_frontiers, b_rec = mf * sizeof(svo_grid_frontier);
+  SvoParts parts;
+  const size_t o_counts = parts.add(8 * sizeof(u64)), o_ws = parts.add(frontier_workspace_bytes(prm->na, prm->nb, prm->max_frontiers)),
+               o_rec = parts.add(b_rec), o_cost = parts.add(4 * n), o_label = parts.add(4 * n), o_goal = parts.add(4 * mf), o_cls = parts.add(n),
+               o_blocked = parts.add(n);
+  SvoTemp d;
+  SVO_HIP_CHECK(ctx, hipMalloc(&d.p, parts.total()));
   svo_grid_frontier_out o{};
-  o.frontiers = out->frontiers ? reinterpret_cast<svo_grid_frontier*>(d + o_rec) : nullptr;  // what the caller did not ask for is not written
-  o.goal_cells = out->goal_cells ? reinterpret_cast<uint32_t*>(d + o_goal) : nullptr;
-  o.label = out->label ? reinterpret_cast<uint32_t*>(d + o_label) : nullptr;
+  o.frontiers = out->frontiers ? d.at<svo_grid_frontier>(o_rec) : nullptr;  // what the caller did not ask for is not written
+  o.goal_cells = out->goal_cells ? d.at<uint32_t>(o_goal) : nullptr;
+  o.label = out->label ? d.at<uint32_t>(o_label) : nullptr;
   u64 c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   hipStream_t st = ctx->stream;
-  // The stream is drained before the temporary buffer goes away, whatever failed.  The caller's frontiers go up first, so that the
-  // records the contract leaves untouched come back as they were.
-  hipError_t e = hipMemcpyAsync(d + o_cls, cls, n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && blocked) e = hipMemcpyAsync(d + o_blocked, blocked, n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && cost) e = hipMemcpyAsync(d + o_cost, cost, 4 * n, hipMemcpyHostToDevice, st);
+  // The caller's frontiers go up first, so that the records the contract leaves untouched come back as they were.
+  hipError_t e = hipMemcpyAsync(d.at(o_cls), cls, n, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && blocked) e = hipMemcpyAsync(d.at(o_blocked), blocked, n, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && cost) e = hipMemcpyAsync(d.at(o_cost), cost, 4 * n, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && out->frontiers) e = hipMemcpyAsync(o.frontiers, out->frontiers, b_rec, hipMemcpyHostToDevice, st);
-  const int rc = e == hipSuccess ? svo_grid_frontiers_dev(ctx, d + o_cls, blocked ? d + o_blocked : nullptr,
-                                                          cost ? reinterpret_cast<const uint32_t*>(d + o_cost) : nullptr, prm, d + o_ws, &o,
-                                                          reinterpret_cast<uint64_t*>(d))
-                                 : SVO_OK;
-  if (e == hipSuccess && !rc) {
-    if (out->frontiers) e = hipMemcpyAsync(out->frontiers, o.frontiers, b_rec, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out->goal_cells) e = hipMemcpyAsync(out->goal_cells, o.goal_cells, 4 * mf, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out->label) e = hipMemcpyAsync(out->label, o.label, 4 * n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, st);
-  }
-  const hipError_t e2 = hipStreamSynchronize(st);
+  const int rc = svo_host_call(
+      ctx, "grid_frontier", e,
+      [&] {
+        return svo_grid_frontiers_dev(ctx, d.at(o_cls), blocked ? d.at(o_blocked) : nullptr, cost ? d.at<uint32_t>(o_cost) : nullptr, prm, d.at(o_ws),
+                                      &o, d.at<uint64_t>(o_counts));
+      },
+      [&] {
+        hipError_t e = hipSuccess;
+        if (out->frontiers) e = hipMemcpyAsync(out->frontiers, o.frontiers, b_rec, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out->goal_cells) e = hipMemcpyAsync(out->goal_cells, o.goal_cells, 4 * mf, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out->label) e = hipMemcpyAsync(out->label, o.label, 4 * n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(c, d.at(o_counts), sizeof(c), hipMemcpyDeviceToHost, st);
+        return e;
+      });
   if (rc) return rc;
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) { ctx->err = std::string("grid_frontier: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
   if (counts) for (int k = 0; k < 8; ++k) counts[k] = c[k];
   return SVO_OK;
 }

@@ -96,7 +96,7 @@ extern "C" int svo_disparity_lr_check_batch_dev(svo_ctx* ctx, int16_t* disp16, c
   svo_use_device(ctx);
   SVO_REQUIRE(ctx, disp16, "lr_check: null disp16");
   SVO_REQUIRE(ctx, cost16, "lr_check: null cost16");
-  DENSE_CHECK(ctx, lr_check_check(width, height, batch, params, &err));
+  SVO_ARGS_CHECK(ctx, lr_check_check(width, height, batch, params, &err));
   return svo_k_lr_check(ctx, disp16, cost16, batch, width, height, params, n_removed);
 }
 
@@ -106,7 +106,7 @@ extern "C" int svo_disparity_lr_check(svo_ctx* ctx, int16_t* disp16, const uint1
   svo_use_device(ctx);
   SVO_REQUIRE(ctx, disp16, "lr_check: null disp16");
   SVO_REQUIRE(ctx, cost16, "lr_check: null cost16");
-  DENSE_CHECK(ctx, lr_check_check(width, height, 1, params, &err));
+  SVO_ARGS_CHECK(ctx, lr_check_check(width, height, 1, params, &err));
   SvoScratch s(ctx);
   const size_t px = (size_t)width * (size_t)height;
   int16_t* dD = s.take<int16_t>(px);

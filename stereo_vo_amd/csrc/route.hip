@@ -300,9 +300,6 @@ __global__ __launch_bounds__(RT_T) void route_path_kernel(RoutePathArgs a) {
 }
 
 // ----------------------------------------------------------------------------- host side
-// A refusal of host/route_args.h goes into the context: `call` is one of its checks with `&err` as its last argument.
-#define ROUTE_CHECK(ctx, call) do { const char* err = nullptr; if (call) { (ctx)->err = err; return SVO_ERR_INVALID; } } while (0)
-
 extern "C" int svo_grid_route_default_params(const svo_grid_clearance_params* clearance, svo_grid_route_params* out) {
   return route_default_params(clearance, out);
 }
@@ -314,7 +311,7 @@ extern "C" int svo_grid_route_dev(svo_ctx* ctx, const uint8_t* blocked, const ui
                                   const svo_grid_route_out* out, uint64_t* counts) {
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
-  ROUTE_CHECK(ctx, route_check(blocked, dist2, prm, goals, n_goals, starts, n_starts, workspace, out, counts, &err));
+  SVO_ARGS_CHECK(ctx, route_check(blocked, dist2, prm, goals, n_goals, starts, n_starts, workspace, out, counts, &err));
   const int na = prm->na, nb = prm->nb;
   unsigned char* const ws = static_cast<unsigned char*>(workspace);
   RouteGrid g{};
@@ -368,52 +365,48 @@ extern "C" int svo_grid_route(svo_ctx* ctx, const uint8_t* blocked, const uint32
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
   SVO_REQUIRE(ctx, blocked, "grid_route: null blocked");
-  ROUTE_CHECK(ctx, route_params_check(prm, n_starts, &err));
+  SVO_ARGS_CHECK(ctx, route_params_check(prm, n_starts, &err));
   SVO_REQUIRE(ctx, prm->resume == 0, "grid_route: resume needs the _dev entry, whose workspace outlives the call");
-  ROUTE_CHECK(ctx, route_lists_check(goals, n_goals, starts, n_starts, &err));
-  ROUTE_CHECK(ctx, route_out_check(out, n_starts, false, &err));
-  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };  // every part 16-byte aligned
+  SVO_ARGS_CHECK(ctx, route_lists_check(goals, n_goals, starts, n_starts, &err));
+  SVO_ARGS_CHECK(ctx, route_out_check(out, n_starts, false, &err));
   const size_t n = (size_t)prm->na * (size_t)prm->nb, ns = (size_t)n_starts, ng = (size_t)n_goals;
   const bool paths = ns > 0 && out->path;
-  const size_t b_ws = up16(route_workspace_bytes(prm->na, prm->nb)), b_path = paths ? up16(4 * ns * (size_t)prm->max_path) : 0;
-  // 8 counts | workspace | cost | dist2 | goals | starts | path_len | path | next | blocked | path_status
-  const size_t o_ws = 8 * sizeof(u64), o_cost = o_ws + b_ws, o_d2 = o_cost + up16(4 * n), o_goals = o_d2 + up16(4 * n), o_starts = o_goals + up16(4 * ng),
-               o_len = o_starts + up16(4 * ns), o_path = o_len + up16(4 * ns), o_next = o_path + b_path, o_blocked = o_next + up16(n),
-               o_status = o_blocked + up16(n), total = o_status + up16(ns);
-  struct Temp { void* p; ~Temp() { if (p) (void)hipFree(p); } } hold{nullptr};
-  SVO_HIP_CHECK(ctx, hipMalloc(&hold.p, total));
-  unsigned char* const d = static_cast<unsigned char*>(hold.p);
+  const size_t b_path = paths ? 4 * ns * (size_t)prm->max_path : 0;
+  SvoParts parts;
+  const size_t o_counts = parts.add(8 * sizeof(u64)), o_ws = parts.add(route_workspace_bytes(prm->na, prm->nb)), o_cost = parts.add(4 * n),
+               o_d2 = parts.add(4 * n), o_goals = parts.add(4 * ng), o_starts = parts.add(4 * ns), o_len = parts.add(4 * ns),
+               o_path = parts.add(b_path), o_next = parts.add(n), o_blocked = parts.add(n), o_status = parts.add(ns);
+  SvoTemp d;
+  SVO_HIP_CHECK(ctx, hipMalloc(&d.p, parts.total()));
   svo_grid_route_out o{};
-  o.cost = reinterpret_cast<uint32_t*>(d + o_cost);
-  o.next = out->next ? d + o_next : nullptr;  // what the caller did not ask for is not written
-  if (paths) { o.path = reinterpret_cast<uint32_t*>(d + o_path); o.path_len = reinterpret_cast<uint32_t*>(d + o_len); o.path_status = d + o_status; }
+  o.cost = d.at<uint32_t>(o_cost);
+  o.next = out->next ? d.at(o_next) : nullptr;  // what the caller did not ask for is not written
+  if (paths) { o.path = d.at<uint32_t>(o_path); o.path_len = d.at<uint32_t>(o_len); o.path_status = d.at(o_status); }
   u64 c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   hipStream_t st = ctx->stream;
-  // The stream is drained before the temporary buffer goes away, whatever failed; the _dev entry's refusal is reported first.  The
-  // caller's next and path go up first, so that what the contract leaves untouched comes back as it was.
-  hipError_t e = hipMemcpyAsync(d + o_blocked, blocked, n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && dist2) e = hipMemcpyAsync(d + o_d2, dist2, 4 * n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d + o_goals, goals, 4 * ng, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && ns) e = hipMemcpyAsync(d + o_starts, starts, 4 * ns, hipMemcpyHostToDevice, st);
+  // The caller's next and path go up first, so that what the contract leaves untouched comes back as it was.
+  hipError_t e = hipMemcpyAsync(d.at(o_blocked), blocked, n, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && dist2) e = hipMemcpyAsync(d.at(o_d2), dist2, 4 * n, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d.at(o_goals), goals, 4 * ng, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && ns) e = hipMemcpyAsync(d.at(o_starts), starts, 4 * ns, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && out->next) e = hipMemcpyAsync(o.next, out->next, n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && paths) e = hipMemcpyAsync(o.path, out->path, 4 * ns * (size_t)prm->max_path, hipMemcpyHostToDevice, st);
-  const int rc = e == hipSuccess ? svo_grid_route_dev(ctx, d + o_blocked, dist2 ? reinterpret_cast<const uint32_t*>(d + o_d2) : nullptr, prm,
-                                                      reinterpret_cast<const uint32_t*>(d + o_goals), n_goals,
-                                                      ns ? reinterpret_cast<const uint32_t*>(d + o_starts) : nullptr, n_starts, d + o_ws, &o,
-                                                      reinterpret_cast<uint64_t*>(d))
-                                 : SVO_OK;
-  if (e == hipSuccess && !rc) {
-    e = hipMemcpyAsync(out->cost, o.cost, 4 * n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out->next) e = hipMemcpyAsync(out->next, o.next, n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && paths) e = hipMemcpyAsync(out->path, o.path, 4 * ns * (size_t)prm->max_path, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && paths) e = hipMemcpyAsync(out->path_len, o.path_len, 4 * ns, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && paths) e = hipMemcpyAsync(out->path_status, o.path_status, ns, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, st);
-  }
-  const hipError_t e2 = hipStreamSynchronize(st);
+  if (e == hipSuccess && paths) e = hipMemcpyAsync(o.path, out->path, b_path, hipMemcpyHostToDevice, st);
+  const int rc = svo_host_call(
+      ctx, "grid_route", e,
+      [&] {
+        return svo_grid_route_dev(ctx, d.at(o_blocked), dist2 ? d.at<uint32_t>(o_d2) : nullptr, prm, d.at<uint32_t>(o_goals), n_goals,
+                                  ns ? d.at<uint32_t>(o_starts) : nullptr, n_starts, d.at(o_ws), &o, d.at<uint64_t>(o_counts));
+      },
+      [&] {
+        hipError_t e = hipMemcpyAsync(out->cost, o.cost, 4 * n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out->next) e = hipMemcpyAsync(out->next, o.next, n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && paths) e = hipMemcpyAsync(out->path, o.path, b_path, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && paths) e = hipMemcpyAsync(out->path_len, o.path_len, 4 * ns, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && paths) e = hipMemcpyAsync(out->path_status, o.path_status, ns, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(c, d.at(o_counts), sizeof(c), hipMemcpyDeviceToHost, st);
+        return e;
+      });
   if (rc) return rc;
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) { ctx->err = std::string("grid_route: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
   if (counts) for (int k = 0; k < 8; ++k) counts[k] = c[k];
   return SVO_OK;
 }

@@ -280,8 +280,8 @@ extern "C" int svo_stereo_sgm_batch_dev(svo_ctx* ctx, const uint8_t* left, const
   if (rc) return rc;
   SVO_REQUIRE(ctx, disp16, STEREO_SGM_BATCH_TEXTS.null_disp);
   SVO_REQUIRE(ctx, workspace, "stereo_sgm: null workspace");
-  DENSE_CHECK(ctx, dense_batch_check(batch, ctx->lim.max_batch, width, height, row_stride, image_stride, STEREO_SGM_BATCH_TEXTS, &err));
-  DENSE_CHECK(ctx, sgm_check(width, height, num_disparities, block_size, batch, params, &err));
+  SVO_ARGS_CHECK(ctx, dense_batch_check(batch, ctx->lim.max_batch, width, height, row_stride, image_stride, STEREO_SGM_BATCH_TEXTS, &err));
+  SVO_ARGS_CHECK(ctx, sgm_check(width, height, num_disparities, block_size, batch, params, &err));
   SVO_REQUIRE(ctx, workspace_bytes >= sgm_workspace_bytes(width, height, num_disparities, block_size, batch),
               "stereo_sgm: workspace_bytes is less than svo_sgm_workspace_bytes for this call");
   SvoDensePairs src{left, right, image_stride, nullptr};
@@ -293,28 +293,26 @@ extern "C" int svo_stereo_sgm(svo_ctx* ctx, const uint8_t* left, const uint8_t* 
   int rc = svo_stereo_check(ctx, left, right, width, height, row_stride, num_disparities, block_size);
   if (rc) return rc;
   SVO_REQUIRE(ctx, disp16, STEREO_SGM_BATCH_TEXTS.null_disp);
-  DENSE_CHECK(ctx, sgm_check(width, height, num_disparities, block_size, 1, params, &err));
+  SVO_ARGS_CHECK(ctx, sgm_check(width, height, num_disparities, block_size, 1, params, &err));
   // the volume of one pair is far larger than the context's scratch: one allocation for this call, freed before it returns
   const size_t px = (size_t)width * (size_t)height;
   const SgmOneShot o = sgm_one_shot(sgm_workspace_bytes(width, height, num_disparities, block_size, 1), px);
-  uint8_t* d = nullptr;
-  SVO_HIP_CHECK(ctx, hipMalloc((void**)&d, o.total));
+  SvoTemp d;
+  SVO_HIP_CHECK(ctx, hipMalloc(&d.p, o.total));
   hipStream_t st = ctx->stream;
-  int16_t* dD = reinterpret_cast<int16_t*>(d + o.disp);
-  uint16_t* dC = reinterpret_cast<uint16_t*>(d + o.cost);
-  hipError_t e = hipMemcpy2DAsync(d + o.left, width, left, row_stride, width, height, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpy2DAsync(d + o.right, width, right, row_stride, width, height, hipMemcpyHostToDevice, st);
-  rc = SVO_OK;
-  if (e == hipSuccess) {
-    SvoDensePairs src{d + o.left, d + o.right, px, nullptr};
-    rc = svo_k_stereo_sgm(ctx, src, 1, width, height, width, num_disparities, block_size, params, d, dD, cost16 ? dC : nullptr);
-  }
-  if (e == hipSuccess && rc == SVO_OK) e = hipMemcpyAsync(disp16, dD, px * sizeof(int16_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && rc == SVO_OK && cost16) e = hipMemcpyAsync(cost16, dC, px * sizeof(uint16_t), hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  (void)hipFree(d);
-  if (rc) return rc;
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) { ctx->err = std::string("stereo_sgm: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
-  return SVO_OK;
+  int16_t* dD = d.at<int16_t>(o.disp);
+  uint16_t* dC = d.at<uint16_t>(o.cost);
+  hipError_t e = hipMemcpy2DAsync(d.at(o.left), width, left, row_stride, width, height, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(d.at(o.right), width, right, row_stride, width, height, hipMemcpyHostToDevice, st);
+  return svo_host_call(
+      ctx, "stereo_sgm", e,
+      [&] {
+        SvoDensePairs src{d.at(o.left), d.at(o.right), px, nullptr};
+        return svo_k_stereo_sgm(ctx, src, 1, width, height, width, num_disparities, block_size, params, d.p, dD, cost16 ? dC : nullptr);
+      },
+      [&] {
+        hipError_t e = hipMemcpyAsync(disp16, dD, px * sizeof(int16_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && cost16) e = hipMemcpyAsync(cost16, dC, px * sizeof(uint16_t), hipMemcpyDeviceToHost, st);
+        return e;
+      });
 }

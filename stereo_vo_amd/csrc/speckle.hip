@@ -199,7 +199,7 @@ extern "C" int svo_disparity_speckle_filter_batch_dev(svo_ctx* ctx, int16_t* dis
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
   SVO_REQUIRE(ctx, disp16, "speckle_filter: null disp16");
-  DENSE_CHECK(ctx, speckle_check(width, height, batch, params, &err));
+  SVO_ARGS_CHECK(ctx, speckle_check(width, height, batch, params, &err));
   if (params->max_size == 0) return SVO_OK;
   SVO_REQUIRE(ctx, workspace && ((uintptr_t)workspace & 3) == 0, "speckle_filter: workspace is null or not 4-byte aligned");
   SVO_REQUIRE(ctx, workspace_bytes >= svo_speckle_workspace_bytes(width, height, batch),
@@ -212,7 +212,7 @@ extern "C" int svo_disparity_speckle_filter(svo_ctx* ctx, int16_t* disp16, int w
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
   SVO_REQUIRE(ctx, disp16, "speckle_filter: null disp16");
-  DENSE_CHECK(ctx, speckle_check(width, height, 1, params, &err));
+  SVO_ARGS_CHECK(ctx, speckle_check(width, height, 1, params, &err));
   if (n_removed) *n_removed = 0;
   if (params->max_size == 0) return SVO_OK;
   SvoScratch s(ctx);

@@ -390,7 +390,7 @@ __global__ __launch_bounds__(256) void stereo_dense_kernel(const uint8_t* __rest
 int svo_stereo_check(svo_ctx* ctx, const void* l, const void* r, int W, int H, int stride, int ndisp, int block) {
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
-  DENSE_CHECK(ctx, stereo_shape_check(l, r, W, H, stride, ndisp, block, ctx->lim.max_width, ctx->lim.max_height, &err));
+  SVO_ARGS_CHECK(ctx, stereo_shape_check(l, r, W, H, stride, ndisp, block, ctx->lim.max_width, ctx->lim.max_height, &err));
   return SVO_OK;
 }
 

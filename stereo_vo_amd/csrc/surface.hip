@@ -141,9 +141,6 @@ __global__ __launch_bounds__(SF_T) void surface_kernel(SurfaceArgs a) {
 }
 
 // ----------------------------------------------------------------------------- host side
-// A refusal of host/surface_args.h goes into the context: `call` is one of its checks with `&err` as its last argument.
-#define SURFACE_CHECK(ctx, call) do { const char* err = nullptr; if (call) { (ctx)->err = err; return SVO_ERR_INVALID; } } while (0)
-
 extern "C" int svo_grid_surface_default_params(const svo_voxel_grid_params* grid, float voxel_size, svo_grid_surface_params* out) {
   return surface_default_params(grid, voxel_size, out);
 }
@@ -154,7 +151,7 @@ extern "C" int svo_grid_surface_dev(svo_ctx* ctx, const uint8_t* cls, const floa
                                     const svo_grid_surface_out* out, uint64_t* counts) {
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
-  SURFACE_CHECK(ctx, surface_check(cls, top, prm, out, counts, true, &err));
+  SVO_ARGS_CHECK(ctx, surface_check(cls, top, prm, out, counts, true, &err));
   const SurfaceFootprint f = surface_footprint(surface_r2(prm));
   SurfaceArgs a{};
   a.cls = cls; a.top = top; a.o = *out;
@@ -177,39 +174,33 @@ extern "C" int svo_grid_surface(svo_ctx* ctx, const uint8_t* cls, const float* t
                                 const svo_grid_surface_out* out, uint64_t* counts) {
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
-  SURFACE_CHECK(ctx, surface_check(cls, top, prm, out, counts, false, &err));
-  const size_t n = (size_t)prm->na * (size_t)prm->nb, n16 = (n + 15) & ~(size_t)15;  // every part 16-byte aligned
-  struct Temp { void* p; ~Temp() { if (p) (void)hipFree(p); } } hold{nullptr};
-  SVO_HIP_CHECK(ctx, hipMalloc(&hold.p, 64 + 16 * n16));  // 6 counts | top | step | relief | support | cls | cls_out
-  unsigned char* const d = static_cast<unsigned char*>(hold.p);
-  float* const d_top = reinterpret_cast<float*>(d + 64);
-  uint8_t* const d_cls = d + 64 + 14 * n16;
+  SVO_ARGS_CHECK(ctx, surface_check(cls, top, prm, out, counts, false, &err));
+  const size_t n = (size_t)prm->na * (size_t)prm->nb;
+  SvoParts parts;
+  const size_t o_counts = parts.add(6 * sizeof(u64)), o_top = parts.add(4 * n), o_step = parts.add(4 * n), o_relief = parts.add(4 * n),
+               o_support = parts.add(2 * n), o_cls = parts.add(n), o_cls_out = parts.add(n);
+  SvoTemp d;
+  SVO_HIP_CHECK(ctx, hipMalloc(&d.p, parts.total()));
   svo_grid_surface_out o{};
-  o.cls_out = d + 64 + 15 * n16;
-  o.step = reinterpret_cast<float*>(d + 64 + 4 * n16);
-  o.relief = reinterpret_cast<float*>(d + 64 + 8 * n16);
-  o.support = reinterpret_cast<uint16_t*>(d + 64 + 12 * n16);
-  svo_grid_surface_out asked = o;  // what the caller did not ask for is not written
-  if (!out->step) asked.step = nullptr;
-  if (!out->relief) asked.relief = nullptr;
-  if (!out->support) asked.support = nullptr;
+  o.cls_out = d.at(o_cls_out);
+  o.step = out->step ? d.at<float>(o_step) : nullptr;  // what the caller did not ask for is not written
+  o.relief = out->relief ? d.at<float>(o_relief) : nullptr;
+  o.support = out->support ? d.at<uint16_t>(o_support) : nullptr;
   u64 c[6] = {0, 0, 0, 0, 0, 0};
   hipStream_t st = ctx->stream;
-  // The stream is drained before the temporary buffer goes away, whatever failed; the _dev entry's refusal is reported first.
-  hipError_t e = hipMemcpyAsync(d_cls, cls, n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_top, top, 4 * n, hipMemcpyHostToDevice, st);
-  const int rc = e == hipSuccess ? svo_grid_surface_dev(ctx, d_cls, d_top, prm, &asked, reinterpret_cast<uint64_t*>(d)) : SVO_OK;
-  if (e == hipSuccess && !rc) {
-    e = hipMemcpyAsync(out->cls_out, o.cls_out, n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out->step) e = hipMemcpyAsync(out->step, o.step, 4 * n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out->relief) e = hipMemcpyAsync(out->relief, o.relief, 4 * n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out->support) e = hipMemcpyAsync(out->support, o.support, 2 * n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, st);
-  }
-  const hipError_t e2 = hipStreamSynchronize(st);
+  hipError_t e = hipMemcpyAsync(d.at(o_cls), cls, n, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d.at(o_top), top, 4 * n, hipMemcpyHostToDevice, st);
+  const int rc = svo_host_call(
+      ctx, "grid_surface", e, [&] { return svo_grid_surface_dev(ctx, d.at(o_cls), d.at<float>(o_top), prm, &o, d.at<uint64_t>(o_counts)); },
+      [&] {
+        hipError_t e = hipMemcpyAsync(out->cls_out, o.cls_out, n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out->step) e = hipMemcpyAsync(out->step, o.step, 4 * n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out->relief) e = hipMemcpyAsync(out->relief, o.relief, 4 * n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out->support) e = hipMemcpyAsync(out->support, o.support, 2 * n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(c, d.at(o_counts), sizeof(c), hipMemcpyDeviceToHost, st);
+        return e;
+      });
   if (rc) return rc;
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) { ctx->err = std::string("grid_surface: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
   if (counts) for (int k = 0; k < 6; ++k) counts[k] = c[k];
   return SVO_OK;
 }

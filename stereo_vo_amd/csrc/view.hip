@@ -213,9 +213,6 @@ __global__ __launch_bounds__(VW_T) void view_rank_kernel(ViewArgs a) {
 }
 
 // ----------------------------------------------------------------------------- host side
-// A refusal of host/view_args.h goes into the context: `call` is one of its checks with `&err` as its last argument.
-#define VIEW_CHECK(ctx, call) do { const char* err = nullptr; if (call) { (ctx)->err = err; return SVO_ERR_INVALID; } } while (0)
-
 extern "C" int svo_grid_view_default_params(const svo_grid_clearance_params* clearance, svo_grid_view_params* out) {
   return view_default_params(clearance, out);
 }
@@ -232,7 +229,7 @@ extern "C" int svo_grid_view_dev(svo_ctx* ctx, const uint8_t* cls, const uint32_
                                  const svo_grid_view_params* prm, void* workspace, const svo_grid_view_out* out, uint64_t* counts) {
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
-  VIEW_CHECK(ctx, view_check(cls, views, n_views, cost, prm, workspace, out, counts, true, &err));
+  SVO_ARGS_CHECK(ctx, view_check(cls, views, n_views, cost, prm, workspace, out, counts, true, &err));
   const int na = prm->na, nb = prm->nb, range = prm->max_range;
   unsigned char* const ws = static_cast<unsigned char*>(workspace);
   ViewArgs a{};
@@ -266,42 +263,40 @@ extern "C" int svo_grid_view(svo_ctx* ctx, const uint8_t* cls, const uint32_t* v
                              const svo_grid_view_params* prm, const svo_grid_view_out* out, uint64_t* counts) {
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
-  VIEW_CHECK(ctx, view_check(cls, views, n_views, cost, prm, nullptr, out, counts, false, &err));
-  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };  // every part 16-byte aligned
-  const size_t n = (size_t)prm->na * (size_t)prm->nb, nv = (size_t)n_views;
-  const size_t b_ws = up16(view_workspace_bytes(prm->na, prm->nb, n_views)), b_rec = nv * sizeof(svo_grid_view_rec);
-  // 8 counts | workspace | records | order | best | seen | views | cost | cls
-  const size_t o_ws = 8 * sizeof(u64), o_rec = o_ws + b_ws, o_order = o_rec + up16(b_rec), o_best = o_order + up16(4 * nv), o_seen = o_best + 16,
-               o_views = o_seen + up16(4 * n), o_cost = o_views + up16(4 * nv), o_cls = o_cost + up16(4 * n), total = o_cls + up16(n);
-  struct Temp { void* p; ~Temp() { if (p) (void)hipFree(p); } } hold{nullptr};
-  SVO_HIP_CHECK(ctx, hipMalloc(&hold.p, total));
-  unsigned char* const d = static_cast<unsigned char*>(hold.p);
+  SVO_ARGS_CHECK(ctx, view_check(cls, views, n_views, cost, prm, nullptr, out, counts, false, &err));
+  const size_t n = (size_t)prm->na * (size_t)prm->nb, nv = (size_t)n_views, b_rec = nv * sizeof(svo_grid_view_rec);
+  SvoParts parts;
+  const size_t o_counts = parts.add(8 * sizeof(u64)), o_ws = parts.add(view_workspace_bytes(prm->na, prm->nb, n_views)), o_rec = parts.add(b_rec),
+               o_order = parts.add(4 * nv), o_best = parts.add(16), o_seen = parts.add(4 * n), o_views = parts.add(4 * nv), o_cost = parts.add(4 * n),
+               o_cls = parts.add(n);
+  SvoTemp d;
+  SVO_HIP_CHECK(ctx, hipMalloc(&d.p, parts.total()));
   svo_grid_view_out o{};
-  o.records = out->records ? reinterpret_cast<svo_grid_view_rec*>(d + o_rec) : nullptr;  // what the caller did not ask for is not written
-  o.order = out->order ? reinterpret_cast<uint32_t*>(d + o_order) : nullptr;
-  o.best = out->best ? reinterpret_cast<uint32_t*>(d + o_best) : nullptr;
-  o.seen = out->seen ? reinterpret_cast<uint32_t*>(d + o_seen) : nullptr;
+  o.records = out->records ? d.at<svo_grid_view_rec>(o_rec) : nullptr;  // what the caller did not ask for is not written
+  o.order = out->order ? d.at<uint32_t>(o_order) : nullptr;
+  o.best = out->best ? d.at<uint32_t>(o_best) : nullptr;
+  o.seen = out->seen ? d.at<uint32_t>(o_seen) : nullptr;
   u64 c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   hipStream_t st = ctx->stream;
-  // The stream is drained before the temporary buffer goes away, whatever failed.
-  hipError_t e = hipMemcpyAsync(d + o_cls, cls, n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d + o_views, views, 4 * nv, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && cost) e = hipMemcpyAsync(d + o_cost, cost, 4 * n, hipMemcpyHostToDevice, st);
-  const int rc = e == hipSuccess ? svo_grid_view_dev(ctx, d + o_cls, reinterpret_cast<const uint32_t*>(d + o_views), n_views,
-                                                     cost ? reinterpret_cast<const uint32_t*>(d + o_cost) : nullptr, prm, d + o_ws, &o,
-                                                     counts ? reinterpret_cast<uint64_t*>(d) : nullptr)
-                                 : SVO_OK;
-  if (e == hipSuccess && !rc) {
-    if (out->records) e = hipMemcpyAsync(out->records, o.records, b_rec, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out->order) e = hipMemcpyAsync(out->order, o.order, 4 * nv, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out->best) e = hipMemcpyAsync(out->best, o.best, 16, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out->seen) e = hipMemcpyAsync(out->seen, o.seen, 4 * n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && counts) e = hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, st);
-  }
-  const hipError_t e2 = hipStreamSynchronize(st);
+  hipError_t e = hipMemcpyAsync(d.at(o_cls), cls, n, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d.at(o_views), views, 4 * nv, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && cost) e = hipMemcpyAsync(d.at(o_cost), cost, 4 * n, hipMemcpyHostToDevice, st);
+  const int rc = svo_host_call(
+      ctx, "grid_view", e,
+      [&] {
+        return svo_grid_view_dev(ctx, d.at(o_cls), d.at<uint32_t>(o_views), n_views, cost ? d.at<uint32_t>(o_cost) : nullptr, prm, d.at(o_ws), &o,
+                                 counts ? d.at<uint64_t>(o_counts) : nullptr);
+      },
+      [&] {
+        hipError_t e = hipSuccess;
+        if (out->records) e = hipMemcpyAsync(out->records, o.records, b_rec, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out->order) e = hipMemcpyAsync(out->order, o.order, 4 * nv, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out->best) e = hipMemcpyAsync(out->best, o.best, 16, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out->seen) e = hipMemcpyAsync(out->seen, o.seen, 4 * n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && counts) e = hipMemcpyAsync(c, d.at(o_counts), sizeof(c), hipMemcpyDeviceToHost, st);
+        return e;
+      });
   if (rc) return rc;
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) { ctx->err = std::string("grid_view: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
   if (counts) for (int k = 0; k < 8; ++k) counts[k] = c[k];
   return SVO_OK;
 }

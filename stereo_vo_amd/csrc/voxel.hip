@@ -738,26 +738,6 @@ __global__ __launch_bounds__(VX_T) void voxel_grid_resolve_kernel(VoxelGridResol
 }
 
 // ----------------------------------------------------------------------------- host side
-// A refusal of host/voxel_args.h goes into the context: `call` is one of its checks with `&err` as its last argument.
-#define VOXEL_CHECK(ctx, call) do { const char* err = nullptr; if (call) { (ctx)->err = err; return SVO_ERR_INVALID; } } while (0)
-
-// A temporary device allocation of a synchronous entry, freed when the entry returns.
-struct VoxelTemp { void* p; ~VoxelTemp() { if (p) (void)hipFree(p); } };
-
-// What every synchronous entry does around its _dev entry: `dev` runs it (unless the copy in before it failed), `back` queues
-// the copies back to the host; the stream is drained before the caller's temporary buffer goes away, whatever failed; the _dev
-// entry's refusal is reported first (its message stands), a HIP error second.
-template <typename Dev, typename Back>
-static int voxel_sync(svo_ctx* ctx, const char* what, hipError_t e, Dev dev, Back back) {
-  const int rc = e == hipSuccess ? dev() : SVO_OK;
-  if (e == hipSuccess && !rc) e = back();
-  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-  if (rc) return rc;
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) { ctx->err = std::string(what) + ": " + hipGetErrorString(e); return SVO_ERR_HIP; }
-  return SVO_OK;
-}
-
 // The head of every pose7 entry: null refused under the entry's own name, then the matrix its matrix form takes.
 static int voxel_pose7(svo_voxel_map* m, const double* pose7, void (*to_matrix)(const double*, double*), double* m12, const char* null_text) {
   if (!m) return SVO_ERR_INVALID;
@@ -798,7 +778,7 @@ extern "C" int svo_voxel_map_create(svo_ctx* ctx, const svo_voxel_map_params* pa
   svo_use_device(ctx);
   SVO_REQUIRE(ctx, out, "voxel_map_create: null out");
   *out = nullptr;
-  VOXEL_CHECK(ctx, voxel_params_check(params, &err));
+  SVO_ARGS_CHECK(ctx, voxel_params_check(params, &err));
   svo_voxel_map* m = new svo_voxel_map();
   m->ctx = ctx;
   m->prm = *params;
@@ -853,7 +833,7 @@ extern "C" int svo_voxel_map_insert_dev(svo_voxel_map* m, const svo_cloud_point*
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = m->ctx;
   svo_use_device(ctx);
-  VOXEL_CHECK(ctx, voxel_cloud_check(points, n, m12, VOXEL_INSERT_TEXTS, &err));
+  SVO_ARGS_CHECK(ctx, voxel_cloud_check(points, n, m12, VOXEL_INSERT_TEXTS, &err));
   if (n == 0) return SVO_OK;
   SvoProfScope prof(ctx, SVO_PROF_VOXEL_INSERT);
   return voxel_insert_launch(m, points, n, m12);
@@ -906,11 +886,11 @@ extern "C" int svo_voxel_map_extract(svo_voxel_map* m, int min_count, svo_cloud_
   SVO_REQUIRE(ctx, points || capacity == 0, "voxel_map_extract: null points");
   SVO_REQUIRE(ctx, n_total && n_stored, "voxel_map_extract: null n_total or n_stored");
   const size_t room = (size_t)capacity < m->cap ? (size_t)capacity : m->cap;  // no more than cap voxels exist
-  svo_cloud_point* d = nullptr;
-  if (room) SVO_HIP_CHECK(ctx, hipMalloc((void**)&d, room * sizeof(svo_cloud_point)));
-  VoxelTemp hold{d};
+  SvoTemp hold;
+  if (room) SVO_HIP_CHECK(ctx, hipMalloc(&hold.p, room * sizeof(svo_cloud_point)));
+  svo_cloud_point* const d = hold.at<svo_cloud_point>(0);
   int c[2] = {0, 0};
-  const int rc = voxel_sync(
+  const int rc = svo_host_call(
       ctx, "voxel_map_extract", hipSuccess, [&] { return svo_voxel_map_extract_dev(m, min_count, d, (int)room, m->d_counts); },
       [&] {  // the counts first: they say how many points there are to copy
         hipError_t e = hipMemcpyAsync(c, m->d_counts, sizeof(c), hipMemcpyDeviceToHost, ctx->stream);
@@ -946,7 +926,7 @@ extern "C" int svo_voxel_map_carve_dev(svo_voxel_map* m, const int16_t* disp16, 
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = m->ctx;
   svo_use_device(ctx);
-  VOXEL_CHECK(ctx, voxel_carve_check(disp16, width, height, cam, w2c12, prm, ctx->lim.max_width, ctx->lim.max_height, &err));
+  SVO_ARGS_CHECK(ctx, voxel_carve_check(disp16, width, height, cam, w2c12, prm, ctx->lim.max_width, ctx->lim.max_height, &err));
   VoxelCarveArgs a{};
   a.t = m->t;
   a.disp = disp16; a.width = width; a.height = height;
@@ -974,14 +954,16 @@ extern "C" int svo_voxel_map_carve(svo_voxel_map* m, const int16_t* disp16, int 
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = m->ctx;
   svo_use_device(ctx);
-  VOXEL_CHECK(ctx, voxel_carve_check(disp16, width, height, cam, w2c12, prm, ctx->lim.max_width, ctx->lim.max_height, &err));
+  SVO_ARGS_CHECK(ctx, voxel_carve_check(disp16, width, height, cam, w2c12, prm, ctx->lim.max_width, ctx->lim.max_height, &err));
   const size_t bytes = sizeof(int16_t) * (size_t)width * (size_t)height;
-  u64* d = nullptr;  // 3 counts | the map
-  SVO_HIP_CHECK(ctx, hipMalloc((void**)&d, 4 * sizeof(u64) + bytes));
-  VoxelTemp hold{d};
-  int16_t* d_disp = reinterpret_cast<int16_t*>(d + 4);
+  SvoParts parts;
+  const size_t o_counts = parts.add(3 * sizeof(u64)), o_disp = parts.add(bytes);
+  SvoTemp hold;
+  SVO_HIP_CHECK(ctx, hipMalloc(&hold.p, parts.total()));
+  u64* const d = hold.at<u64>(o_counts);
+  int16_t* const d_disp = hold.at<int16_t>(o_disp);
   u64 c[3] = {0, 0, 0};
-  const int rc = voxel_sync(
+  const int rc = svo_host_call(
       ctx, "voxel_map_carve", hipMemcpyAsync(d_disp, disp16, bytes, hipMemcpyHostToDevice, ctx->stream),
       [&] { return svo_voxel_map_carve_dev(m, d_disp, width, height, cam, w2c12, prm, reinterpret_cast<uint64_t*>(d)); },
       [&] { return hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, ctx->stream); });
@@ -1002,7 +984,7 @@ extern "C" int svo_voxel_map_copy_live_dev(svo_voxel_map* src, svo_voxel_map* ds
   a.src = src->t; a.dst = dst->t;
   a.min_count = (unsigned)min_count;
   if (box6) {
-    VOXEL_CHECK(ctx, voxel_box_keys(box6, src->prm.voxel_size, a.klo, a.khi, &err));
+    SVO_ARGS_CHECK(ctx, voxel_box_keys(box6, src->prm.voxel_size, a.klo, a.khi, &err));
     a.boxed = 1;
   }
   SvoProfScope prof(ctx, SVO_PROF_VOXEL_COPY);
@@ -1038,7 +1020,7 @@ extern "C" int svo_voxel_map_render_dev(svo_voxel_map* m, int width, int height,
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = m->ctx;
   svo_use_device(ctx);
-  VOXEL_CHECK(ctx, voxel_render_check(width, height, cam, w2c12, prm, ctx->lim.max_width, ctx->lim.max_height, &err));
+  SVO_ARGS_CHECK(ctx, voxel_render_check(width, height, cam, w2c12, prm, ctx->lim.max_width, ctx->lim.max_height, &err));
   SVO_REQUIRE(ctx, workspace, "voxel_map_render: null workspace");
   SVO_REQUIRE(ctx, ((uintptr_t)workspace & 3u) == 0, "voxel_map_render: workspace must be 4-byte aligned");
   SVO_REQUIRE(ctx, disp16, "voxel_map_render: null disp16");
@@ -1079,17 +1061,20 @@ extern "C" int svo_voxel_map_render(svo_voxel_map* m, int width, int height, con
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = m->ctx;
   svo_use_device(ctx);
-  VOXEL_CHECK(ctx, voxel_render_check(width, height, cam, w2c12, prm, ctx->lim.max_width, ctx->lim.max_height, &err));
+  SVO_ARGS_CHECK(ctx, voxel_render_check(width, height, cam, w2c12, prm, ctx->lim.max_width, ctx->lim.max_height, &err));
   SVO_REQUIRE(ctx, disp16, "voxel_map_render: null disp16");
-  const size_t n = (size_t)width * (size_t)height, n16 = (n + 15) & ~(size_t)15;  // every part 16-byte aligned
-  unsigned char* d = nullptr;                                                      // 4 counts | pix | disp16 | intensity
-  SVO_HIP_CHECK(ctx, hipMalloc((void**)&d, 4 * sizeof(u64) + 7 * n16));
-  VoxelTemp hold{d};
-  unsigned char* d_pix = d + 4 * sizeof(u64);
-  int16_t* d_disp = reinterpret_cast<int16_t*>(d_pix + 4 * n16);
-  uint8_t* d_int = d_pix + 6 * n16;
+  const size_t n = (size_t)width * (size_t)height;
+  SvoParts parts;
+  const size_t o_counts = parts.add(4 * sizeof(u64)), o_pix = parts.add(svo_voxel_render_workspace_bytes(width, height)), o_disp = parts.add(2 * n),
+               o_int = parts.add(n);
+  SvoTemp hold;
+  SVO_HIP_CHECK(ctx, hipMalloc(&hold.p, parts.total()));
+  u64* const d = hold.at<u64>(o_counts);
+  unsigned char* const d_pix = hold.at(o_pix);
+  int16_t* const d_disp = hold.at<int16_t>(o_disp);
+  uint8_t* const d_int = hold.at(o_int);
   u64 c[4] = {0, 0, 0, 0};
-  const int rc = voxel_sync(
+  const int rc = svo_host_call(
       ctx, "voxel_map_render", hipSuccess,
       [&] { return svo_voxel_map_render_dev(m, width, height, cam, w2c12, prm, d_pix, d_disp, intensity ? d_int : nullptr, reinterpret_cast<uint64_t*>(d)); },
       [&] {
@@ -1126,7 +1111,7 @@ extern "C" int svo_voxel_map_grid_dev(svo_voxel_map* m, const svo_voxel_grid_par
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = m->ctx;
   svo_use_device(ctx);
-  VOXEL_CHECK(ctx, voxel_grid_check(prm, workspace, out, counts, &err));
+  SVO_ARGS_CHECK(ctx, voxel_grid_check(prm, workspace, out, counts, &err));
   VoxelGridKeys k;
   voxel_grid_keys(prm, m->prm.voxel_size, &k);
   const u64* const sums[3] = {m->t.sx, m->t.sy, m->t.sz};
@@ -1160,20 +1145,23 @@ extern "C" int svo_voxel_map_grid(svo_voxel_map* m, const svo_voxel_grid_params*
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = m->ctx;
   svo_use_device(ctx);
-  VOXEL_CHECK(ctx, voxel_grid_params_check(prm, &err));
-  VOXEL_CHECK(ctx, voxel_grid_out_check(out, false, &err));
-  const size_t n = (size_t)prm->na * (size_t)prm->nb, n16 = (n + 15) & ~(size_t)15;  // every part 16-byte aligned
-  unsigned char* d = nullptr;  // 5 counts (6 words) | cells | n_points | top | bottom | n_voxels | cls | intensity
-  SVO_HIP_CHECK(ctx, hipMalloc((void**)&d, 6 * sizeof(u64) + 54 * n16));
-  VoxelTemp hold{d};
-  unsigned char* d_cells = d + 6 * sizeof(u64);
+  SVO_ARGS_CHECK(ctx, voxel_grid_params_check(prm, &err));
+  SVO_ARGS_CHECK(ctx, voxel_grid_out_check(out, false, &err));
+  const size_t n = (size_t)prm->na * (size_t)prm->nb;
+  SvoParts parts;
+  const size_t o_counts = parts.add(5 * sizeof(u64)), o_cells = parts.add(voxel_grid_workspace_bytes(prm->na, prm->nb)), o_points = parts.add(8 * n),
+               o_top = parts.add(4 * n), o_bottom = parts.add(4 * n), o_voxels = parts.add(4 * n), o_cls = parts.add(n), o_int = parts.add(n);
+  SvoTemp hold;
+  SVO_HIP_CHECK(ctx, hipMalloc(&hold.p, parts.total()));
+  u64* const d = hold.at<u64>(o_counts);
+  unsigned char* const d_cells = hold.at(o_cells);
   svo_voxel_grid_out o{};
-  o.n_points = reinterpret_cast<uint64_t*>(d_cells + 32 * n16);
-  o.top = reinterpret_cast<float*>(d_cells + 40 * n16);
-  o.bottom = reinterpret_cast<float*>(d_cells + 44 * n16);
-  o.n_voxels = reinterpret_cast<uint32_t*>(d_cells + 48 * n16);
-  o.cls = d_cells + 52 * n16;
-  o.intensity = d_cells + 53 * n16;
+  o.n_points = hold.at<uint64_t>(o_points);
+  o.top = hold.at<float>(o_top);
+  o.bottom = hold.at<float>(o_bottom);
+  o.n_voxels = hold.at<uint32_t>(o_voxels);
+  o.cls = hold.at(o_cls);
+  o.intensity = hold.at(o_int);
   svo_voxel_grid_out asked = o;  // what the caller did not ask for is not written
   if (!out->top) asked.top = nullptr;
   if (!out->bottom) asked.bottom = nullptr;
@@ -1181,7 +1169,7 @@ extern "C" int svo_voxel_map_grid(svo_voxel_map* m, const svo_voxel_grid_params*
   if (!out->n_voxels) asked.n_voxels = nullptr;
   if (!out->n_points) asked.n_points = nullptr;
   u64 c[5] = {0, 0, 0, 0, 0};
-  const int rc = voxel_sync(
+  const int rc = svo_host_call(
       ctx, "voxel_map_grid", hipSuccess, [&] { return svo_voxel_map_grid_dev(m, prm, d_cells, &asked, reinterpret_cast<uint64_t*>(d)); },
       [&] {
         hipError_t e = hipMemcpyAsync(out->cls, o.cls, n, hipMemcpyDeviceToHost, ctx->stream);
@@ -1216,8 +1204,8 @@ extern "C" int svo_voxel_map_remove_dev(svo_voxel_map* m, const svo_cloud_point*
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = m->ctx;
   svo_use_device(ctx);
-  VOXEL_CHECK(ctx, voxel_cloud_check(points, n, m12, VOXEL_REMOVE_TEXTS, &err));
-  VOXEL_CHECK(ctx, voxel_counts_check(counts, VOXEL_REMOVE_TEXTS, &err));
+  SVO_ARGS_CHECK(ctx, voxel_cloud_check(points, n, m12, VOXEL_REMOVE_TEXTS, &err));
+  SVO_ARGS_CHECK(ctx, voxel_counts_check(counts, VOXEL_REMOVE_TEXTS, &err));
   if (n == 0) return SVO_OK;
   SvoProfScope prof(ctx, SVO_PROF_VOXEL_REMOVE);
   return voxel_remove_launch(m, points, n, m12, counts);
@@ -1238,7 +1226,7 @@ extern "C" int svo_voxel_map_remove_sync(svo_voxel_map* m, const svo_cloud_point
   SvoScratch scratch(ctx);
   u64* d = scratch.take<u64>(4);  // the context's scratch: this call ends with the stream drained
   SVO_REQUIRE(ctx, d, "voxel_map_remove_sync: the context has no scratch");
-  const int rc = voxel_sync(
+  const int rc = svo_host_call(
       ctx, "voxel_map_remove_sync", hipSuccess, [&] { return svo_voxel_map_remove_dev(m, points, n, m12, reinterpret_cast<uint64_t*>(d)); },
       [&] { return n > 0 ? hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; });
   if (rc) return rc;
@@ -1251,9 +1239,9 @@ extern "C" int svo_voxel_map_move_dev(svo_voxel_map* m, const svo_cloud_point* p
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = m->ctx;
   svo_use_device(ctx);
-  VOXEL_CHECK(ctx, voxel_cloud_check(points, n, from_m12, VOXEL_MOVE_TEXTS, &err));
+  SVO_ARGS_CHECK(ctx, voxel_cloud_check(points, n, from_m12, VOXEL_MOVE_TEXTS, &err));
   SVO_REQUIRE(ctx, to_m12, "voxel_map_move: null to_m12");
-  VOXEL_CHECK(ctx, voxel_counts_check(counts, VOXEL_MOVE_TEXTS, &err));
+  SVO_ARGS_CHECK(ctx, voxel_counts_check(counts, VOXEL_MOVE_TEXTS, &err));
   if (n == 0) return SVO_OK;
   if (memcmp(from_m12, to_m12, 12 * sizeof(double)) == 0) return SVO_OK;  // the same bits: the cloud is where it belongs
   SvoProfScope prof(ctx, SVO_PROF_VOXEL_MOVE);

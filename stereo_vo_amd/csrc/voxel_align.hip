@@ -236,8 +236,6 @@ __global__ __launch_bounds__(VA_T) void voxel_align_kernel(VoxelAlignArgs a) {
 }  // namespace
 
 // ----------------------------------------------------------------------------- host side
-#define VOXEL_ALIGN_CHECK(ctx, call) do { const char* err = nullptr; if (call) { (ctx)->err = err; return SVO_ERR_INVALID; } } while (0)
-
 extern "C" int svo_voxel_align_default_params(float voxel_size, svo_voxel_align_params* params) { return voxel_align_default_params(voxel_size, params); }
 
 // The memset and the launch of checked arguments.
@@ -268,7 +266,7 @@ extern "C" int svo_voxel_map_align_sums_dev(svo_voxel_map* m, const svo_cloud_po
   if (!m) return SVO_ERR_INVALID;
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_use_device(t.ctx);
-  VOXEL_ALIGN_CHECK(t.ctx, voxel_align_sums_check(points, n, c2w12, prm, sums, &err));
+  SVO_ARGS_CHECK(t.ctx, voxel_align_sums_check(points, n, c2w12, prm, sums, &err));
   return voxel_align_launch(t, points, n, c2w12, prm, sums);
 }
 
@@ -276,7 +274,7 @@ extern "C" int svo_voxel_map_align_sums_pose7_dev(svo_voxel_map* m, const svo_cl
                                                   const svo_voxel_align_params* prm, int64_t* sums) {
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = svo_voxel_map_view(m).ctx;
-  VOXEL_ALIGN_CHECK(ctx, voxel_align_n_check(n, &err));
+  SVO_ARGS_CHECK(ctx, voxel_align_n_check(n, &err));
   SVO_REQUIRE(ctx, pose7, "voxel_map_align: null pose7");
   double m12[12];
   voxel_pose7_to_cam_to_world(pose7, m12);
@@ -289,20 +287,16 @@ extern "C" int svo_voxel_map_align(svo_voxel_map* m, const svo_cloud_point* poin
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_ctx* ctx = t.ctx;
   svo_use_device(ctx);
-  VOXEL_ALIGN_CHECK(ctx, voxel_align_loop_check(points, n, pose7_in, prm, pose7_out, result, &err));
+  SVO_ARGS_CHECK(ctx, voxel_align_loop_check(points, n, pose7_in, prm, pose7_out, result, &err));
   SvoScratch scratch(ctx);
   int64_t* d = scratch.take<int64_t>(VOXEL_ALIGN_WORDS);  // the context's scratch: every iteration ends with the stream drained
   SVO_REQUIRE(ctx, d, "voxel_map_align: the context has no scratch");
   return voxel_align_loop(
       pose7_in, prm,
       [&](const double* m12, int64_t* w) {
-        int rc = voxel_align_launch(t, points, n, m12, prm, d);
-        hipError_t e = rc ? hipSuccess : hipMemcpyAsync(w, d, VOXEL_ALIGN_WORDS * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
-        const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        if (rc) return rc;
-        if (e == hipSuccess) e = e2;
-        if (e != hipSuccess) { ctx->err = std::string("voxel_map_align: ") + hipGetErrorString(e); return (int)SVO_ERR_HIP; }
-        return (int)SVO_OK;
+        return svo_host_call(
+            ctx, "voxel_map_align", hipSuccess, [&] { return voxel_align_launch(t, points, n, m12, prm, d); },
+            [&] { return hipMemcpyAsync(w, d, VOXEL_ALIGN_WORDS * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream); });
       },
       pose7_out, result);
 }

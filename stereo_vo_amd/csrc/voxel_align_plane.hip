@@ -216,8 +216,6 @@ __global__ __launch_bounds__(VP_T) void voxel_align_plane_kernel(VoxelAlignPlane
 }  // namespace
 
 // ----------------------------------------------------------------------------- host side
-#define VOXEL_ALIGN_PLANE_CHECK(ctx, call) do { const char* err = nullptr; if (call) { (ctx)->err = err; return SVO_ERR_INVALID; } } while (0)
-
 // The memset and the launch of checked arguments.
 static int voxel_align_plane_launch(const SvoVoxelView& t, const svo_voxel_normal* normals, const svo_cloud_point* points, int n, const double* c2w12,
                                     const svo_voxel_align_params* prm, int64_t* sums) {
@@ -247,7 +245,7 @@ extern "C" int svo_voxel_map_align_plane_sums_dev(svo_voxel_map* m, const svo_vo
   if (!m) return SVO_ERR_INVALID;
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_use_device(t.ctx);
-  VOXEL_ALIGN_PLANE_CHECK(t.ctx, voxel_align_plane_sums_check(normals, points, n, c2w12, prm, sums, &err));
+  SVO_ARGS_CHECK(t.ctx, voxel_align_plane_sums_check(normals, points, n, c2w12, prm, sums, &err));
   return voxel_align_plane_launch(t, normals, points, n, c2w12, prm, sums);
 }
 
@@ -255,8 +253,8 @@ extern "C" int svo_voxel_map_align_plane_sums_pose7_dev(svo_voxel_map* m, const 
                                                         const double* pose7, const svo_voxel_align_params* prm, int64_t* sums) {
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = svo_voxel_map_view(m).ctx;
-  VOXEL_ALIGN_PLANE_CHECK(ctx, voxel_align_plane_normals_check(normals, &err));
-  VOXEL_ALIGN_PLANE_CHECK(ctx, voxel_align_n_check(n, &err));
+  SVO_ARGS_CHECK(ctx, voxel_align_plane_normals_check(normals, &err));
+  SVO_ARGS_CHECK(ctx, voxel_align_n_check(n, &err));
   SVO_REQUIRE(ctx, pose7, "voxel_map_align_plane: null pose7");
   double m12[12];
   voxel_pose7_to_cam_to_world(pose7, m12);
@@ -270,20 +268,16 @@ extern "C" int svo_voxel_map_align_plane(svo_voxel_map* m, const svo_voxel_norma
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_ctx* ctx = t.ctx;
   svo_use_device(ctx);
-  VOXEL_ALIGN_PLANE_CHECK(ctx, voxel_align_plane_loop_check(normals, points, n, pose7_in, prm, pose7_out, result, &err));
+  SVO_ARGS_CHECK(ctx, voxel_align_plane_loop_check(normals, points, n, pose7_in, prm, pose7_out, result, &err));
   SvoScratch scratch(ctx);
   int64_t* d = scratch.take<int64_t>(VOXEL_ALIGN_PLANE_WORDS);  // the context's scratch: every iteration ends with the stream drained
   SVO_REQUIRE(ctx, d, "voxel_map_align_plane: the context has no scratch");
   return voxel_align_plane_loop(
       pose7_in, prm,
       [&](const double* m12, int64_t* w) {
-        int rc = voxel_align_plane_launch(t, normals, points, n, m12, prm, d);
-        hipError_t e = rc ? hipSuccess : hipMemcpyAsync(w, d, VOXEL_ALIGN_PLANE_WORDS * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
-        const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        if (rc) return rc;
-        if (e == hipSuccess) e = e2;
-        if (e != hipSuccess) { ctx->err = std::string("voxel_map_align_plane: ") + hipGetErrorString(e); return (int)SVO_ERR_HIP; }
-        return (int)SVO_OK;
+        return svo_host_call(
+            ctx, "voxel_map_align_plane", hipSuccess, [&] { return voxel_align_plane_launch(t, normals, points, n, m12, prm, d); },
+            [&] { return hipMemcpyAsync(w, d, VOXEL_ALIGN_PLANE_WORDS * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream); });
       },
       pose7_out, result);
 }

@@ -149,8 +149,6 @@ void voxel_distance_launches(hipStream_t st, dim3 grid, const VoxelDistanceRowAr
 }  // namespace
 
 // ----------------------------------------------------------------------------- host side
-#define VOXEL_DISTANCE_CHECK(ctx, call) do { const char* err = nullptr; if (call) { (ctx)->err = err; return SVO_ERR_INVALID; } } while (0)
-
 extern "C" int svo_voxel_distance_default_params(float voxel_size, svo_voxel_distance_params* out) { return voxel_distance_default_params(voxel_size, out); }
 extern "C" int svo_voxel_distance_workspace_bytes(const int* dims3, int want_nearest, size_t* bytes) { return voxel_distance_workspace_bytes(dims3, want_nearest, bytes); }
 extern "C" int svo_voxel_distance_bytes(const int* dims3, size_t* bytes) { return voxel_distance_bytes(dims3, bytes); }
@@ -161,7 +159,7 @@ extern "C" int svo_voxel_occupancy_distance_dev(svo_voxel_map* m, const uint64_t
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_ctx* ctx = t.ctx;
   svo_use_device(ctx);
-  VOXEL_DISTANCE_CHECK(ctx, voxel_distance_check(bits, dims3, prm, workspace, out, counts, &err));
+  SVO_ARGS_CHECK(ctx, voxel_distance_check(bits, dims3, prm, workspace, out, counts, &err));
   const bool near = out->nearest != nullptr;
   const VoxelDistanceLayout lay = voxel_distance_layout(dims3, near);
   char* const ws = static_cast<char*>(workspace);
@@ -211,7 +209,7 @@ extern "C" int svo_voxel_distance_query_dev(svo_voxel_map* m, const uint16_t* di
   if (!m) return SVO_ERR_INVALID;
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_use_device(t.ctx);
-  VOXEL_DISTANCE_CHECK(t.ctx, voxel_distance_query_check(dist2, origin3, dims3, spheres, n, hits, counts, true, &err));
+  SVO_ARGS_CHECK(t.ctx, voxel_distance_query_check(dist2, origin3, dims3, spheres, n, hits, counts, true, &err));
   return voxel_distance_query_launch(t, dist2, origin3, dims3, spheres, n, hits, counts);
 }
 
@@ -221,22 +219,25 @@ extern "C" int svo_voxel_distance_query(svo_voxel_map* m, const uint16_t* dist2,
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_ctx* ctx = t.ctx;
   svo_use_device(ctx);
-  VOXEL_DISTANCE_CHECK(ctx, voxel_distance_query_check(dist2, origin3, dims3, host_spheres, n, host_hits, host_counts, false, &err));
-  const size_t cbytes = 256, sbytes = sizeof(svo_voxel_sphere) * (size_t)n, hbytes = sizeof(svo_voxel_sphere_hit) * (size_t)n;  // counts | spheres | hits
-  char* d = nullptr;
-  SVO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&d), cbytes + sbytes + hbytes));
-  svo_voxel_sphere* d_s = reinterpret_cast<svo_voxel_sphere*>(d + cbytes);
-  svo_voxel_sphere_hit* d_h = reinterpret_cast<svo_voxel_sphere_hit*>(d + cbytes + sbytes);
-  hipError_t e = n ? hipMemcpyAsync(d_s, host_spheres, sbytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
-  int rc = SVO_OK;
-  if (e == hipSuccess) rc = voxel_distance_query_launch(t, dist2, origin3, dims3, d_s, n, d_h, reinterpret_cast<uint64_t*>(d));
-  if (!rc && e == hipSuccess && n) e = hipMemcpyAsync(host_hits, d_h, hbytes, hipMemcpyDeviceToHost, ctx->stream);
-  if (!rc && e == hipSuccess && host_counts) e = hipMemcpyAsync(host_counts, d, VOXEL_DISTANCE_QUERY_COUNTS * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream);
-  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d);
+  SVO_ARGS_CHECK(ctx, voxel_distance_query_check(dist2, origin3, dims3, host_spheres, n, host_hits, host_counts, false, &err));
+  const size_t sbytes = sizeof(svo_voxel_sphere) * (size_t)n, hbytes = sizeof(svo_voxel_sphere_hit) * (size_t)n;
+  SvoParts parts;
+  const size_t o_counts = parts.add(VOXEL_DISTANCE_QUERY_COUNTS * sizeof(uint64_t)), o_s = parts.add(sbytes), o_h = parts.add(hbytes);
+  SvoTemp d;
+  SVO_HIP_CHECK(ctx, hipMalloc(&d.p, parts.total()));
+  uint64_t c[VOXEL_DISTANCE_QUERY_COUNTS] = {};
+  const int rc = svo_host_call(
+      ctx, "voxel_distance_query", n ? hipMemcpyAsync(d.at(o_s), host_spheres, sbytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess,
+      [&] {
+        return voxel_distance_query_launch(t, dist2, origin3, dims3, d.at<svo_voxel_sphere>(o_s), n, d.at<svo_voxel_sphere_hit>(o_h), d.at<uint64_t>(o_counts));
+      },
+      [&] {
+        hipError_t e = n ? hipMemcpyAsync(host_hits, d.at(o_h), hbytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+        if (e == hipSuccess && host_counts) e = hipMemcpyAsync(c, d.at(o_counts), sizeof(c), hipMemcpyDeviceToHost, ctx->stream);
+        return e;
+      });
   if (rc) return rc;
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) { ctx->err = std::string("voxel_distance_query: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
+  if (host_counts) memcpy(host_counts, c, sizeof(c));
   return SVO_OK;
 }
 
@@ -246,34 +247,36 @@ extern "C" int svo_voxel_map_distance(svo_voxel_map* m, int min_count, const int
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_ctx* ctx = t.ctx;
   svo_use_device(ctx);
-  VOXEL_DISTANCE_CHECK(ctx, voxel_map_distance_check(min_count, origin3, dims3, prm, host_out, &err));
-  const size_t n = voxel_distance_cells(dims3), bbytes = n / 8, r256 = 255;
+  SVO_ARGS_CHECK(ctx, voxel_map_distance_check(min_count, origin3, dims3, prm, host_out, &err));
+  const size_t n = voxel_distance_cells(dims3), bbytes = n / 8;
   const bool near = host_out->nearest != nullptr;
-  const size_t wbytes = voxel_distance_layout(dims3, near).total;
-  // counts (4 words, and the occupancy's two u32 behind them) | bits | inflated | workspace | dist2 | nearest | clearance
-  const size_t o_bits = 256, o_infl = o_bits + ((bbytes + r256) & ~r256), o_ws = o_infl + ((bbytes + r256) & ~r256), o_d2 = o_ws + ((wbytes + r256) & ~r256);
-  const size_t o_near = o_d2 + ((2 * n + r256) & ~r256), o_clr = o_near + (near ? 4 * n : 0), total = o_clr + (host_out->clearance ? 4 * n : 0);
-  char* d = nullptr;
-  SVO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&d), total));
-  uint64_t* d_counts = reinterpret_cast<uint64_t*>(d);
-  uint64_t* d_bits = reinterpret_cast<uint64_t*>(d + o_bits);
+  SvoParts parts;  // the occupancy's two u32 counts are asked for and dropped
+  const size_t o_counts = parts.add(VOXEL_DISTANCE_COUNTS * sizeof(uint64_t)), o_occ = parts.add(2 * sizeof(uint32_t)), o_bits = parts.add(bbytes),
+               o_infl = parts.add(host_out->inflated ? bbytes : 0), o_ws = parts.add(voxel_distance_layout(dims3, near).total), o_d2 = parts.add(2 * n),
+               o_near = parts.add(near ? 4 * n : 0), o_clr = parts.add(host_out->clearance ? 4 * n : 0);
+  SvoTemp d;
+  SVO_HIP_CHECK(ctx, hipMalloc(&d.p, parts.total()));
   svo_voxel_distance_out o{};
-  o.dist2 = reinterpret_cast<uint16_t*>(d + o_d2);
-  o.nearest = near ? reinterpret_cast<uint32_t*>(d + o_near) : nullptr;
-  o.clearance = host_out->clearance ? reinterpret_cast<float*>(d + o_clr) : nullptr;
-  o.inflated = host_out->inflated ? reinterpret_cast<uint64_t*>(d + o_infl) : nullptr;
-  int rc = svo_voxel_map_occupancy_dev(m, min_count, origin3, dims3, d_bits, reinterpret_cast<uint32_t*>(d_counts + 8));
-  if (!rc) rc = svo_voxel_occupancy_distance_dev(m, d_bits, dims3, prm, d + o_ws, &o, d_counts);
-  hipError_t e = hipSuccess;
-  if (!rc) e = hipMemcpyAsync(host_out->dist2, o.dist2, 2 * n, hipMemcpyDeviceToHost, ctx->stream);
-  if (!rc && e == hipSuccess && near) e = hipMemcpyAsync(host_out->nearest, o.nearest, 4 * n, hipMemcpyDeviceToHost, ctx->stream);
-  if (!rc && e == hipSuccess && o.clearance) e = hipMemcpyAsync(host_out->clearance, o.clearance, 4 * n, hipMemcpyDeviceToHost, ctx->stream);
-  if (!rc && e == hipSuccess && o.inflated) e = hipMemcpyAsync(host_out->inflated, o.inflated, bbytes, hipMemcpyDeviceToHost, ctx->stream);
-  if (!rc && e == hipSuccess && host_counts) e = hipMemcpyAsync(host_counts, d_counts, VOXEL_DISTANCE_COUNTS * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream);
-  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d);
+  o.dist2 = d.at<uint16_t>(o_d2);
+  o.nearest = near ? d.at<uint32_t>(o_near) : nullptr;  // what the caller did not ask for is not written
+  o.clearance = host_out->clearance ? d.at<float>(o_clr) : nullptr;
+  o.inflated = host_out->inflated ? d.at<uint64_t>(o_infl) : nullptr;
+  uint64_t c[VOXEL_DISTANCE_COUNTS] = {};
+  const int rc = svo_host_call(
+      ctx, "voxel_map_distance", hipSuccess,
+      [&] {
+        const int rc = svo_voxel_map_occupancy_dev(m, min_count, origin3, dims3, d.at<uint64_t>(o_bits), d.at<uint32_t>(o_occ));
+        return rc ? rc : svo_voxel_occupancy_distance_dev(m, d.at<uint64_t>(o_bits), dims3, prm, d.at(o_ws), &o, d.at<uint64_t>(o_counts));
+      },
+      [&] {
+        hipError_t e = hipMemcpyAsync(host_out->dist2, o.dist2, 2 * n, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && near) e = hipMemcpyAsync(host_out->nearest, o.nearest, 4 * n, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && o.clearance) e = hipMemcpyAsync(host_out->clearance, o.clearance, 4 * n, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && o.inflated) e = hipMemcpyAsync(host_out->inflated, o.inflated, bbytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && host_counts) e = hipMemcpyAsync(c, d.at(o_counts), sizeof(c), hipMemcpyDeviceToHost, ctx->stream);
+        return e;
+      });
   if (rc) return rc;
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) { ctx->err = std::string("voxel_map_distance: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
+  if (host_counts) memcpy(host_counts, c, sizeof(c));
   return SVO_OK;
 }

@@ -280,8 +280,6 @@ __global__ __launch_bounds__(VL_T) void voxel_locate_best_kernel(VoxelLocateBest
 }  // namespace
 
 // ----------------------------------------------------------------------------- host side
-#define VOXEL_LOCATE_CHECK(ctx, call) do { const char* err = nullptr; if (call) { (ctx)->err = err; return SVO_ERR_INVALID; } } while (0)
-
 extern "C" int svo_voxel_occupancy_bytes(const int* dims3, size_t* bytes) { return voxel_occupancy_bytes(dims3, bytes); }
 extern "C" int svo_voxel_locate_default_params(float voxel_size, svo_voxel_locate_params* params) { return voxel_locate_default_params(voxel_size, params); }
 extern "C" int svo_voxel_locate_workspace_bytes(const svo_voxel_locate_params* params, size_t* bytes) { return voxel_locate_workspace_bytes(params, bytes); }
@@ -308,7 +306,7 @@ extern "C" int svo_voxel_map_occupancy_dev(svo_voxel_map* m, int min_count, cons
   if (!m) return SVO_ERR_INVALID;
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_use_device(t.ctx);
-  VOXEL_LOCATE_CHECK(t.ctx, voxel_occupancy_check(min_count, origin3, dims3, bits, counts, true, &err));
+  SVO_ARGS_CHECK(t.ctx, voxel_occupancy_check(min_count, origin3, dims3, bits, counts, true, &err));
   return voxel_occupancy_launch(t, min_count, origin3, dims3, bits, counts);
 }
 
@@ -318,19 +316,23 @@ extern "C" int svo_voxel_map_occupancy(svo_voxel_map* m, int min_count, const in
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_ctx* ctx = t.ctx;
   svo_use_device(ctx);
-  VOXEL_LOCATE_CHECK(ctx, voxel_occupancy_check(min_count, origin3, dims3, host_bits, host_counts, false, &err));
-  const size_t bytes = 8 * voxel_occupancy_words(dims3), cbytes = 2 * sizeof(uint32_t);
-  char* d = nullptr;
-  SVO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&d), bytes + cbytes));  // the counts behind the volume: 8-byte aligned
-  int rc = voxel_occupancy_launch(t, min_count, origin3, dims3, reinterpret_cast<uint64_t*>(d), reinterpret_cast<uint32_t*>(d + bytes));
-  hipError_t e = hipSuccess;
-  if (!rc) e = hipMemcpyAsync(host_bits, d, bytes, hipMemcpyDeviceToHost, ctx->stream);
-  if (!rc && e == hipSuccess && host_counts) e = hipMemcpyAsync(host_counts, d + bytes, cbytes, hipMemcpyDeviceToHost, ctx->stream);
-  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d);
+  SVO_ARGS_CHECK(ctx, voxel_occupancy_check(min_count, origin3, dims3, host_bits, host_counts, false, &err));
+  const size_t bytes = 8 * voxel_occupancy_words(dims3);
+  SvoParts parts;
+  const size_t o_bits = parts.add(bytes), o_counts = parts.add(2 * sizeof(uint32_t));
+  SvoTemp d;
+  SVO_HIP_CHECK(ctx, hipMalloc(&d.p, parts.total()));
+  uint32_t c[2] = {0, 0};
+  const int rc = svo_host_call(
+      ctx, "voxel_map_occupancy", hipSuccess,
+      [&] { return voxel_occupancy_launch(t, min_count, origin3, dims3, d.at<uint64_t>(o_bits), d.at<uint32_t>(o_counts)); },
+      [&] {
+        hipError_t e = hipMemcpyAsync(host_bits, d.at(o_bits), bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && host_counts) e = hipMemcpyAsync(c, d.at(o_counts), sizeof(c), hipMemcpyDeviceToHost, ctx->stream);
+        return e;
+      });
   if (rc) return rc;
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) { ctx->err = std::string("voxel_map_occupancy: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
+  if (host_counts) memcpy(host_counts, c, sizeof(c));
   return SVO_OK;
 }
 
@@ -367,7 +369,7 @@ extern "C" int svo_voxel_map_locate_scores_dev(svo_voxel_map* m, const uint64_t*
   if (!m) return SVO_ERR_INVALID;
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_use_device(t.ctx);
-  VOXEL_LOCATE_CHECK(t.ctx, voxel_locate_scores_check(bits, origin3, dims3, points, n, mats, K, box3, hits, best, &err));
+  SVO_ARGS_CHECK(t.ctx, voxel_locate_scores_check(bits, origin3, dims3, points, n, mats, K, box3, hits, best, &err));
   return voxel_locate_launch(t, bits, origin3, dims3, points, n, mats, K, box3, hits, best);
 }
 
@@ -378,7 +380,7 @@ extern "C" int svo_voxel_map_locate(svo_voxel_map* m, const svo_voxel_normal* no
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_ctx* ctx = t.ctx;
   svo_use_device(ctx);
-  VOXEL_LOCATE_CHECK(ctx, voxel_locate_loop_check(normals, points, n, pose7_in, prm, aprm, workspace, pose7_out, result, &err));
+  SVO_ARGS_CHECK(ctx, voxel_locate_loop_check(normals, points, n, pose7_in, prm, aprm, workspace, pose7_out, result, &err));
   const VoxelLocateLayout l = voxel_locate_layout(prm);
   char* ws = static_cast<char*>(workspace);
   uint64_t* bits = reinterpret_cast<uint64_t*>(ws + l.bits);
@@ -388,14 +390,13 @@ extern "C" int svo_voxel_map_locate(svo_voxel_map* m, const svo_voxel_normal* no
   const int rc = voxel_locate_loop(
       pose7_in, prm, t.voxel_size,
       [&](const double* mats, int K, const int* origin, svo_voxel_locate_best* host_best) {
-        int rc = voxel_occupancy_launch(t, prm->min_count, origin, prm->dims, bits, counts);
-        if (!rc) rc = voxel_locate_launch(t, bits, origin, prm->dims, points, n, mats, K, prm->box, hits, best);
-        hipError_t e = rc ? hipSuccess : hipMemcpyAsync(host_best, best, sizeof(svo_voxel_locate_best) * (size_t)K, hipMemcpyDeviceToHost, ctx->stream);
-        const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        if (rc) return rc;
-        if (e == hipSuccess) e = e2;
-        if (e != hipSuccess) { ctx->err = std::string("voxel_map_locate: ") + hipGetErrorString(e); return (int)SVO_ERR_HIP; }
-        return (int)SVO_OK;
+        return svo_host_call(
+            ctx, "voxel_map_locate", hipSuccess,
+            [&] {
+              const int rc = voxel_occupancy_launch(t, prm->min_count, origin, prm->dims, bits, counts);
+              return rc ? rc : voxel_locate_launch(t, bits, origin, prm->dims, points, n, mats, K, prm->box, hits, best);
+            },
+            [&] { return hipMemcpyAsync(host_best, best, sizeof(svo_voxel_locate_best) * (size_t)K, hipMemcpyDeviceToHost, ctx->stream); });
       },
       [&](const double* pose7, double* out, svo_voxel_align_result* res) {
         return normals ? svo_voxel_map_align_plane(m, normals, points, n, pose7, aprm, out, res) : svo_voxel_map_align(m, points, n, pose7, aprm, out, res);

@@ -218,8 +218,6 @@ __global__ __launch_bounds__(VN_T) void voxel_normals_kernel(VoxelNormalsArgs a)
 }  // namespace
 
 // ----------------------------------------------------------------------------- host side
-#define VOXEL_NORMALS_CHECK(ctx, call) do { const char* err = nullptr; if (call) { (ctx)->err = err; return SVO_ERR_INVALID; } } while (0)
-
 extern "C" int svo_voxel_normals_default_params(svo_voxel_normals_params* params) { return voxel_normals_default_params(params); }
 extern "C" int svo_voxel_map_normals_bytes(const svo_voxel_map_params* params, size_t* bytes) { return voxel_normals_bytes(params, bytes); }
 
@@ -246,7 +244,7 @@ extern "C" int svo_voxel_map_normals_dev(svo_voxel_map* m, const svo_voxel_norma
   if (!m) return SVO_ERR_INVALID;
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_use_device(t.ctx);
-  VOXEL_NORMALS_CHECK(t.ctx, voxel_normals_check(prm, normals, counts, true, &err));
+  SVO_ARGS_CHECK(t.ctx, voxel_normals_check(prm, normals, counts, true, &err));
   return voxel_normals_launch(t, prm, normals, counts);
 }
 
@@ -255,18 +253,21 @@ extern "C" int svo_voxel_map_normals(svo_voxel_map* m, const svo_voxel_normals_p
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_ctx* ctx = t.ctx;
   svo_use_device(ctx);
-  VOXEL_NORMALS_CHECK(ctx, voxel_normals_check(prm, host_normals, host_counts, false, &err));
-  const size_t bytes = VOXEL_NORMAL_BYTES * ((size_t)t.mask + 1), cbytes = VOXEL_NORMALS_COUNTS * sizeof(uint64_t);
-  char* d = nullptr;
-  SVO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&d), bytes + cbytes));  // the counts behind the records: 16-byte aligned
-  int rc = voxel_normals_launch(t, prm, reinterpret_cast<svo_voxel_normal*>(d), reinterpret_cast<uint64_t*>(d + bytes));
-  hipError_t e = hipSuccess;
-  if (!rc) e = hipMemcpyAsync(host_normals, d, bytes, hipMemcpyDeviceToHost, ctx->stream);
-  if (!rc && e == hipSuccess && host_counts) e = hipMemcpyAsync(host_counts, d + bytes, cbytes, hipMemcpyDeviceToHost, ctx->stream);
-  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d);
+  SVO_ARGS_CHECK(ctx, voxel_normals_check(prm, host_normals, host_counts, false, &err));
+  const size_t bytes = VOXEL_NORMAL_BYTES * ((size_t)t.mask + 1);
+  SvoParts parts;
+  const size_t o_normals = parts.add(bytes), o_counts = parts.add(VOXEL_NORMALS_COUNTS * sizeof(uint64_t));
+  SvoTemp d;
+  SVO_HIP_CHECK(ctx, hipMalloc(&d.p, parts.total()));
+  uint64_t c[VOXEL_NORMALS_COUNTS] = {};
+  const int rc = svo_host_call(
+      ctx, "voxel_map_normals", hipSuccess, [&] { return voxel_normals_launch(t, prm, d.at<svo_voxel_normal>(o_normals), d.at<uint64_t>(o_counts)); },
+      [&] {
+        hipError_t e = hipMemcpyAsync(host_normals, d.at(o_normals), bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && host_counts) e = hipMemcpyAsync(c, d.at(o_counts), sizeof(c), hipMemcpyDeviceToHost, ctx->stream);
+        return e;
+      });
   if (rc) return rc;
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) { ctx->err = std::string("voxel_map_normals: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
+  if (host_counts) memcpy(host_counts, c, sizeof(c));
   return SVO_OK;
 }

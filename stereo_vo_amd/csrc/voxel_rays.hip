@@ -147,8 +147,6 @@ __global__ __launch_bounds__(VR_T) void voxel_raycast_kernel(VoxelRaycastArgs a)
 }  // namespace
 
 // ----------------------------------------------------------------------------- host side
-#define VOXEL_RAYS_CHECK(ctx, call) do { const char* err = nullptr; if (call) { (ctx)->err = err; return SVO_ERR_INVALID; } } while (0)
-
 extern "C" int svo_voxel_raycast_default_params(svo_voxel_raycast_params* params) { return voxel_raycast_default_params(params); }
 extern "C" int svo_voxel_occupancy_coarse_bytes(const int* dims3, size_t* bytes) { return voxel_coarse_bytes(dims3, bytes); }
 
@@ -156,7 +154,7 @@ extern "C" int svo_voxel_occupancy_coarse_dev(svo_voxel_map* m, const uint64_t* 
   if (!m) return SVO_ERR_INVALID;
   svo_ctx* ctx = svo_voxel_map_view(m).ctx;
   svo_use_device(ctx);
-  VOXEL_RAYS_CHECK(ctx, voxel_coarse_check(bits, dims3, coarse, &err));
+  SVO_ARGS_CHECK(ctx, voxel_coarse_check(bits, dims3, coarse, &err));
   SvoProfScope prof(ctx, SVO_PROF_VOXEL_COARSE);
   SVO_HIP_CHECK(ctx, hipMemsetAsync(coarse, 0, 8 * voxel_coarse_words(dims3), ctx->stream));
   VoxelCoarseArgs a{};
@@ -197,7 +195,7 @@ extern "C" int svo_voxel_occupancy_rays_dev(svo_voxel_map* m, const uint64_t* bi
   if (!m) return SVO_ERR_INVALID;
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_use_device(t.ctx);
-  VOXEL_RAYS_CHECK(t.ctx, voxel_rays_check(bits, coarse, origin3, dims3, rays, n, min_step, hits, counts, true, &err));
+  SVO_ARGS_CHECK(t.ctx, voxel_rays_check(bits, coarse, origin3, dims3, rays, n, min_step, hits, counts, true, &err));
   return voxel_rays_launch(t, bits, coarse, origin3, dims3, rays, n, min_step, hits, counts);
 }
 
@@ -207,22 +205,26 @@ extern "C" int svo_voxel_occupancy_rays(svo_voxel_map* m, const uint64_t* bits, 
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_ctx* ctx = t.ctx;
   svo_use_device(ctx);
-  VOXEL_RAYS_CHECK(ctx, voxel_rays_check(bits, coarse, origin3, dims3, host_rays, n, min_step, host_hits, host_counts, false, &err));
-  const size_t cbytes = 256, rbytes = sizeof(svo_voxel_ray) * (size_t)n, hbytes = sizeof(svo_voxel_ray_hit) * (size_t)n;  // counts | rays | hits
-  char* d = nullptr;
-  SVO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&d), cbytes + rbytes + hbytes));
-  svo_voxel_ray* d_rays = reinterpret_cast<svo_voxel_ray*>(d + cbytes);
-  svo_voxel_ray_hit* d_hits = reinterpret_cast<svo_voxel_ray_hit*>(d + cbytes + rbytes);
-  hipError_t e = n ? hipMemcpyAsync(d_rays, host_rays, rbytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
-  int rc = SVO_OK;
-  if (e == hipSuccess) rc = voxel_rays_launch(t, bits, coarse, origin3, dims3, d_rays, n, min_step, d_hits, reinterpret_cast<uint64_t*>(d));
-  if (!rc && e == hipSuccess && n) e = hipMemcpyAsync(host_hits, d_hits, hbytes, hipMemcpyDeviceToHost, ctx->stream);
-  if (!rc && e == hipSuccess && host_counts) e = hipMemcpyAsync(host_counts, d, VOXEL_RAYS_COUNTS * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream);
-  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d);
+  SVO_ARGS_CHECK(ctx, voxel_rays_check(bits, coarse, origin3, dims3, host_rays, n, min_step, host_hits, host_counts, false, &err));
+  const size_t rbytes = sizeof(svo_voxel_ray) * (size_t)n, hbytes = sizeof(svo_voxel_ray_hit) * (size_t)n;
+  SvoParts parts;
+  const size_t o_counts = parts.add(VOXEL_RAYS_COUNTS * sizeof(uint64_t)), o_rays = parts.add(rbytes), o_hits = parts.add(hbytes);
+  SvoTemp d;
+  SVO_HIP_CHECK(ctx, hipMalloc(&d.p, parts.total()));
+  uint64_t c[VOXEL_RAYS_COUNTS] = {};
+  const int rc = svo_host_call(
+      ctx, "voxel_occupancy_rays", n ? hipMemcpyAsync(d.at(o_rays), host_rays, rbytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess,
+      [&] {
+        return voxel_rays_launch(t, bits, coarse, origin3, dims3, d.at<svo_voxel_ray>(o_rays), n, min_step, d.at<svo_voxel_ray_hit>(o_hits),
+                                 d.at<uint64_t>(o_counts));
+      },
+      [&] {
+        hipError_t e = n ? hipMemcpyAsync(host_hits, d.at(o_hits), hbytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+        if (e == hipSuccess && host_counts) e = hipMemcpyAsync(c, d.at(o_counts), sizeof(c), hipMemcpyDeviceToHost, ctx->stream);
+        return e;
+      });
   if (rc) return rc;
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) { ctx->err = std::string("voxel_occupancy_rays: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
+  if (host_counts) memcpy(host_counts, c, sizeof(c));
   return SVO_OK;
 }
 
@@ -233,7 +235,7 @@ extern "C" int svo_voxel_occupancy_raycast_dev(svo_voxel_map* m, const uint64_t*
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_ctx* ctx = t.ctx;
   svo_use_device(ctx);
-  VOXEL_RAYS_CHECK(ctx, voxel_raycast_check(bits, coarse, origin3, dims3, width, height, cam, c2w12, prm, ctx->lim.max_width, ctx->lim.max_height, disp16,
+  SVO_ARGS_CHECK(ctx, voxel_raycast_check(bits, coarse, origin3, dims3, width, height, cam, c2w12, prm, ctx->lim.max_width, ctx->lim.max_height, disp16,
                                             cell, counts, &err));
   SvoProfScope prof(ctx, SVO_PROF_VOXEL_RAYS);
   if (counts) SVO_HIP_CHECK(ctx, hipMemsetAsync(counts, 0, VOXEL_RAYCAST_COUNTS * sizeof(uint64_t), ctx->stream));
@@ -274,32 +276,37 @@ extern "C" int svo_voxel_map_raycast(svo_voxel_map* m, int min_count, const int*
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_ctx* ctx = t.ctx;
   svo_use_device(ctx);
-  VOXEL_RAYS_CHECK(ctx, voxel_map_raycast_check(min_count, dims3, width, height, cam, c2w12, prm, ctx->lim.max_width, ctx->lim.max_height, disp16, &err));
+  SVO_ARGS_CHECK(ctx, voxel_map_raycast_check(min_count, dims3, width, height, cam, c2w12, prm, ctx->lim.max_width, ctx->lim.max_height, disp16, &err));
   const double T[3] = {c2w12[3], c2w12[7], c2w12[11]};
   int origin[3];
-  VOXEL_RAYS_CHECK(ctx, voxel_locate_origin(T, t.voxel_size, dims3, origin, &err));
+  SVO_ARGS_CHECK(ctx, voxel_locate_origin(T, t.voxel_size, dims3, origin, &err));
   if (origin3_out) memcpy(origin3_out, origin, sizeof(origin));
-  const size_t px = (size_t)width * (size_t)height, r256 = 255;
-  const size_t bbytes = 8 * voxel_occupancy_words(dims3), cbytes = (8 * voxel_coarse_words(dims3) + r256) & ~r256;
-  const size_t dbytes = (2 * px + r256) & ~r256, lbytes = 4 * px;  // volume | coarse | counts | disp16 | cell
-  char* d = nullptr;
-  SVO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&d), bbytes + cbytes + 256 + dbytes + lbytes));
-  uint64_t *d_bits = reinterpret_cast<uint64_t*>(d), *d_coarse = reinterpret_cast<uint64_t*>(d + bbytes);
-  uint64_t* d_counts = reinterpret_cast<uint64_t*>(d + bbytes + cbytes);  // seven words, and the occupancy's two u32 behind them
-  int16_t* d_disp = reinterpret_cast<int16_t*>(d + bbytes + cbytes + 256);
-  uint32_t* d_cell = reinterpret_cast<uint32_t*>(d + bbytes + cbytes + 256 + dbytes);
-  int rc = svo_voxel_map_occupancy_dev(m, min_count, origin, dims3, d_bits, reinterpret_cast<uint32_t*>(d_counts + 8));
-  if (!rc && VOXEL_RAYCAST_HOST_SKIPS) rc = svo_voxel_occupancy_coarse_dev(m, d_bits, dims3, d_coarse);
-  if (!rc) rc = svo_voxel_occupancy_raycast_dev(m, d_bits, VOXEL_RAYCAST_HOST_SKIPS ? d_coarse : nullptr, origin, dims3, width, height, cam, c2w12, prm, d_disp,
-                                                cell ? d_cell : nullptr, d_counts);
-  hipError_t e = hipSuccess;
-  if (!rc) e = hipMemcpyAsync(disp16, d_disp, 2 * px, hipMemcpyDeviceToHost, ctx->stream);
-  if (!rc && e == hipSuccess && cell) e = hipMemcpyAsync(cell, d_cell, 4 * px, hipMemcpyDeviceToHost, ctx->stream);
-  if (!rc && e == hipSuccess && counts) e = hipMemcpyAsync(counts, d_counts, VOXEL_RAYCAST_COUNTS * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream);
-  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d);
+  const size_t px = (size_t)width * (size_t)height;
+  SvoParts parts;  // the occupancy's two u32 counts are asked for and dropped
+  const size_t o_bits = parts.add(8 * voxel_occupancy_words(dims3)), o_coarse = parts.add(8 * voxel_coarse_words(dims3)),
+               o_counts = parts.add(VOXEL_RAYCAST_COUNTS * sizeof(uint64_t)), o_occ = parts.add(2 * sizeof(uint32_t)), o_disp = parts.add(2 * px),
+               o_cell = parts.add(4 * px);
+  SvoTemp d;
+  SVO_HIP_CHECK(ctx, hipMalloc(&d.p, parts.total()));
+  uint64_t* const d_bits = d.at<uint64_t>(o_bits);
+  uint64_t* const d_coarse = VOXEL_RAYCAST_HOST_SKIPS ? d.at<uint64_t>(o_coarse) : nullptr;
+  uint64_t c[VOXEL_RAYCAST_COUNTS] = {};
+  const int rc = svo_host_call(
+      ctx, "voxel_map_raycast", hipSuccess,
+      [&] {
+        int rc = svo_voxel_map_occupancy_dev(m, min_count, origin, dims3, d_bits, d.at<uint32_t>(o_occ));
+        if (!rc && d_coarse) rc = svo_voxel_occupancy_coarse_dev(m, d_bits, dims3, d_coarse);
+        if (!rc) rc = svo_voxel_occupancy_raycast_dev(m, d_bits, d_coarse, origin, dims3, width, height, cam, c2w12, prm, d.at<int16_t>(o_disp),
+                                                      cell ? d.at<uint32_t>(o_cell) : nullptr, d.at<uint64_t>(o_counts));
+        return rc;
+      },
+      [&] {
+        hipError_t e = hipMemcpyAsync(disp16, d.at(o_disp), 2 * px, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && cell) e = hipMemcpyAsync(cell, d.at(o_cell), 4 * px, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && counts) e = hipMemcpyAsync(c, d.at(o_counts), sizeof(c), hipMemcpyDeviceToHost, ctx->stream);
+        return e;
+      });
   if (rc) return rc;
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) { ctx->err = std::string("voxel_map_raycast: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
+  if (counts) memcpy(counts, c, sizeof(c));
   return SVO_OK;
 }

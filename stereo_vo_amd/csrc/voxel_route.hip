@@ -268,8 +268,6 @@ __global__ __launch_bounds__(VR_T) void voxel_route_path_kernel(VoxelRoutePathAr
 }
 
 // ----------------------------------------------------------------------------- host side
-#define VOXEL_ROUTE_CHECK(ctx, call) do { const char* err = nullptr; if (call) { (ctx)->err = err; return SVO_ERR_INVALID; } } while (0)
-
 extern "C" int svo_voxel_route_default_params(float voxel_size, svo_voxel_route_params* out) { return voxel_route_default_params(voxel_size, out); }
 extern "C" int svo_voxel_route_workspace_bytes(const int* dims3, size_t* bytes) { return voxel_route_workspace_bytes(dims3, bytes); }
 extern "C" int svo_voxel_occupancy_cell_of(float voxel_size, const int* origin3, const int* dims3, const float* xyz3, uint32_t* cell) {
@@ -283,7 +281,7 @@ extern "C" int svo_voxel_occupancy_route_dev(svo_voxel_map* m, const uint64_t* c
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_ctx* ctx = t.ctx;
   svo_use_device(ctx);
-  VOXEL_ROUTE_CHECK(ctx, voxel_route_check(closed, dims3, dist2, prm, goals, n_goals, starts, n_starts, workspace, out, counts, &err));
+  SVO_ARGS_CHECK(ctx, voxel_route_check(closed, dims3, dist2, prm, goals, n_goals, starts, n_starts, workspace, out, counts, &err));
   unsigned char* const ws = static_cast<unsigned char*>(workspace);
   const VoxelRouteTiles tiles = voxel_route_tiles(dims3);
   VoxelRouteGrid g{};
@@ -340,48 +338,45 @@ extern "C" int svo_voxel_occupancy_route(svo_voxel_map* m, const uint64_t* close
   const SvoVoxelView t = svo_voxel_map_view(m);
   svo_ctx* ctx = t.ctx;
   svo_use_device(ctx);
-  VOXEL_ROUTE_CHECK(ctx, voxel_route_host_check(closed, dims3, dist2, prm, goals, n_goals, starts, n_starts, out, &err));
-  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };  // every part 16-byte aligned
+  SVO_ARGS_CHECK(ctx, voxel_route_host_check(closed, dims3, dist2, prm, goals, n_goals, starts, n_starts, out, &err));
   size_t b_ws = 0;
   (void)voxel_route_workspace_bytes(dims3, &b_ws);
   const size_t n = voxel_distance_cells(dims3), ns = (size_t)n_starts, ng = (size_t)n_goals;
   const bool paths = ns > 0 && out->path;
-  const size_t b_path = paths ? up16(4 * ns * (size_t)prm->max_path) : 0;
-  // 8 counts | workspace | cost | goals | starts | path_len | path | next | path_status
-  const size_t o_ws = 8 * sizeof(u64), o_cost = o_ws + up16(b_ws), o_goals = o_cost + up16(4 * n), o_starts = o_goals + up16(4 * ng),
-               o_len = o_starts + up16(4 * ns), o_path = o_len + up16(4 * ns), o_next = o_path + b_path, o_status = o_next + (out->next ? up16(n) : 0),
-               total = o_status + up16(ns);
-  struct Temp { void* p; ~Temp() { if (p) (void)hipFree(p); } } hold{nullptr};
-  SVO_HIP_CHECK(ctx, hipMalloc(&hold.p, total));
-  unsigned char* const d = static_cast<unsigned char*>(hold.p);
+  const size_t b_path = paths ? 4 * ns * (size_t)prm->max_path : 0;
+  SvoParts parts;
+  const size_t o_counts = parts.add(8 * sizeof(u64)), o_ws = parts.add(b_ws), o_cost = parts.add(4 * n), o_goals = parts.add(4 * ng),
+               o_starts = parts.add(4 * ns), o_len = parts.add(4 * ns), o_path = parts.add(b_path), o_next = parts.add(out->next ? n : 0),
+               o_status = parts.add(ns);
+  SvoTemp d;
+  SVO_HIP_CHECK(ctx, hipMalloc(&d.p, parts.total()));
   svo_voxel_route_out o{};
-  o.cost = reinterpret_cast<uint32_t*>(d + o_cost);
-  o.next = out->next ? d + o_next : nullptr;  // what the caller did not ask for is not written
-  if (paths) { o.path = reinterpret_cast<uint32_t*>(d + o_path); o.path_len = reinterpret_cast<uint32_t*>(d + o_len); o.path_status = d + o_status; }
+  o.cost = d.at<uint32_t>(o_cost);
+  o.next = out->next ? d.at(o_next) : nullptr;  // what the caller did not ask for is not written
+  if (paths) { o.path = d.at<uint32_t>(o_path); o.path_len = d.at<uint32_t>(o_len); o.path_status = d.at(o_status); }
   u64 c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   hipStream_t st = ctx->stream;
-  // The stream is drained before the temporary buffer goes away, whatever failed; the _dev entry's refusal is reported first.  The
-  // caller's next and path go up first, so that what the contract leaves untouched comes back as it was.
-  hipError_t e = hipMemcpyAsync(d + o_goals, goals, 4 * ng, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && ns) e = hipMemcpyAsync(d + o_starts, starts, 4 * ns, hipMemcpyHostToDevice, st);
+  // The caller's next and path go up first, so that what the contract leaves untouched comes back as it was.
+  hipError_t e = hipMemcpyAsync(d.at(o_goals), goals, 4 * ng, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && ns) e = hipMemcpyAsync(d.at(o_starts), starts, 4 * ns, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && out->next) e = hipMemcpyAsync(o.next, out->next, n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && paths) e = hipMemcpyAsync(o.path, out->path, 4 * ns * (size_t)prm->max_path, hipMemcpyHostToDevice, st);
-  const int rc = e == hipSuccess ? svo_voxel_occupancy_route_dev(m, closed, dims3, dist2, prm, reinterpret_cast<const uint32_t*>(d + o_goals), n_goals,
-                                                                 ns ? reinterpret_cast<const uint32_t*>(d + o_starts) : nullptr, n_starts, d + o_ws, &o,
-                                                                 reinterpret_cast<uint64_t*>(d))
-                                 : SVO_OK;
-  if (e == hipSuccess && !rc) {
-    e = hipMemcpyAsync(out->cost, o.cost, 4 * n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out->next) e = hipMemcpyAsync(out->next, o.next, n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && paths) e = hipMemcpyAsync(out->path, o.path, 4 * ns * (size_t)prm->max_path, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && paths) e = hipMemcpyAsync(out->path_len, o.path_len, 4 * ns, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && paths) e = hipMemcpyAsync(out->path_status, o.path_status, ns, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, st);
-  }
-  const hipError_t e2 = hipStreamSynchronize(st);
+  if (e == hipSuccess && paths) e = hipMemcpyAsync(o.path, out->path, b_path, hipMemcpyHostToDevice, st);
+  const int rc = svo_host_call(
+      ctx, "voxel_route", e,
+      [&] {
+        return svo_voxel_occupancy_route_dev(m, closed, dims3, dist2, prm, d.at<uint32_t>(o_goals), n_goals, ns ? d.at<uint32_t>(o_starts) : nullptr,
+                                             n_starts, d.at(o_ws), &o, d.at<uint64_t>(o_counts));
+      },
+      [&] {
+        hipError_t e = hipMemcpyAsync(out->cost, o.cost, 4 * n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out->next) e = hipMemcpyAsync(out->next, o.next, n, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && paths) e = hipMemcpyAsync(out->path, o.path, b_path, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && paths) e = hipMemcpyAsync(out->path_len, o.path_len, 4 * ns, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && paths) e = hipMemcpyAsync(out->path_status, o.path_status, ns, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(c, d.at(o_counts), sizeof(c), hipMemcpyDeviceToHost, st);
+        return e;
+      });
   if (rc) return rc;
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) { ctx->err = std::string("voxel_route: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
   if (counts) for (int k = 0; k < 8; ++k) counts[k] = c[k];
   return SVO_OK;
 }

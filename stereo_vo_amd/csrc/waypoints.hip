@@ -125,9 +125,6 @@ __global__ __launch_bounds__(WY_T) void way_kernel(WayArgs a) {
 }
 
 // ----------------------------------------------------------------------------- host side
-// A refusal of host/waypoint_args.h goes into the context: `call` is one of its checks with `&err` as its last argument.
-#define WAY_CHECK(ctx, call) do { const char* err = nullptr; if (call) { (ctx)->err = err; return SVO_ERR_INVALID; } } while (0)
-
 extern "C" int svo_grid_waypoints_default_params(const svo_grid_route_params* route, const svo_grid_clearance_params* clearance,
                                                  svo_grid_waypoint_params* out) {
   return way_default_params(route, clearance, out);
@@ -138,7 +135,7 @@ extern "C" int svo_grid_waypoints_dev(svo_ctx* ctx, const uint8_t* blocked, cons
                                       const svo_grid_waypoint_params* prm, const svo_grid_waypoint_out* out, uint64_t* counts) {
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
-  WAY_CHECK(ctx, way_check(blocked, dist2, path, path_len, n_paths, prm, out, counts, true, &err));
+  SVO_ARGS_CHECK(ctx, way_check(blocked, dist2, path, path_len, n_paths, prm, out, counts, true, &err));
   WayArgs a{};
   a.blocked = blocked; a.dist2 = dist2; a.path = path; a.path_len = path_len; a.path_status = path_status;
   a.way = out->way; a.way_index = out->way_index; a.way_len = out->way_len; a.way_status = out->way_status; a.length = out->length;
@@ -161,50 +158,47 @@ extern "C" int svo_grid_waypoints(svo_ctx* ctx, const uint8_t* blocked, const ui
                                   const svo_grid_waypoint_out* out, uint64_t* counts) {
   if (!ctx) return SVO_ERR_INVALID;
   svo_use_device(ctx);
-  WAY_CHECK(ctx, way_check(blocked, dist2, path, path_len, n_paths, prm, out, counts, false, &err));
-  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };  // every part 16-byte aligned
+  SVO_ARGS_CHECK(ctx, way_check(blocked, dist2, path, path_len, n_paths, prm, out, counts, false, &err));
   const size_t n = (size_t)prm->na * (size_t)prm->nb, np = (size_t)n_paths;
   const size_t b_path = 4 * np * (size_t)prm->path_stride, b_way = 4 * np * (size_t)prm->max_way;
-  // 8 counts | length | way | way_index | way_len | way_status | path | path_len | path_status | dist2 | blocked
-  const size_t o_length = 8 * sizeof(u64), o_way = o_length + up16(8 * np), o_index = o_way + up16(b_way), o_len = o_index + up16(b_way),
-               o_status = o_len + up16(4 * np), o_path = o_status + up16(np), o_plen = o_path + up16(b_path), o_pst = o_plen + up16(4 * np),
-               o_dist2 = o_pst + up16(np), o_blocked = o_dist2 + up16(4 * n), total = o_blocked + up16(n);
-  struct Temp { void* p; ~Temp() { if (p) (void)hipFree(p); } } hold{nullptr};
-  SVO_HIP_CHECK(ctx, hipMalloc(&hold.p, total));
-  unsigned char* const d = static_cast<unsigned char*>(hold.p);
+  SvoParts parts;
+  const size_t o_counts = parts.add(8 * sizeof(u64)), o_length = parts.add(8 * np), o_way = parts.add(b_way), o_index = parts.add(b_way),
+               o_len = parts.add(4 * np), o_status = parts.add(np), o_path = parts.add(b_path), o_plen = parts.add(4 * np), o_pst = parts.add(np),
+               o_dist2 = parts.add(4 * n), o_blocked = parts.add(n);
+  SvoTemp d;
+  SVO_HIP_CHECK(ctx, hipMalloc(&d.p, parts.total()));
   svo_grid_waypoint_out o{};
-  o.way = out->way ? reinterpret_cast<uint32_t*>(d + o_way) : nullptr;  // what the caller did not ask for is not written
-  o.way_index = out->way_index ? reinterpret_cast<uint32_t*>(d + o_index) : nullptr;
-  o.way_len = out->way_len ? reinterpret_cast<uint32_t*>(d + o_len) : nullptr;
-  o.way_status = out->way_status ? d + o_status : nullptr;
-  o.length = out->length ? reinterpret_cast<double*>(d + o_length) : nullptr;
+  o.way = out->way ? d.at<uint32_t>(o_way) : nullptr;  // what the caller did not ask for is not written
+  o.way_index = out->way_index ? d.at<uint32_t>(o_index) : nullptr;
+  o.way_len = out->way_len ? d.at<uint32_t>(o_len) : nullptr;
+  o.way_status = out->way_status ? d.at(o_status) : nullptr;
+  o.length = out->length ? d.at<double>(o_length) : nullptr;
   u64 c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   hipStream_t st = ctx->stream;
-  // The stream is drained before the temporary buffer goes away, whatever failed.
-  hipError_t e = hipMemcpyAsync(d + o_blocked, blocked, n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && dist2) e = hipMemcpyAsync(d + o_dist2, dist2, 4 * n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d + o_path, path, b_path, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d + o_plen, path_len, 4 * np, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && path_status) e = hipMemcpyAsync(d + o_pst, path_status, np, hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(d.at(o_blocked), blocked, n, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && dist2) e = hipMemcpyAsync(d.at(o_dist2), dist2, 4 * n, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d.at(o_path), path, b_path, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d.at(o_plen), path_len, 4 * np, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && path_status) e = hipMemcpyAsync(d.at(o_pst), path_status, np, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && out->way) e = hipMemcpyAsync(o.way, out->way, b_way, hipMemcpyHostToDevice, st);  // the untouched entries come back
   if (e == hipSuccess && out->way_index) e = hipMemcpyAsync(o.way_index, out->way_index, b_way, hipMemcpyHostToDevice, st);
-  const int rc = e == hipSuccess ? svo_grid_waypoints_dev(ctx, d + o_blocked, dist2 ? reinterpret_cast<const uint32_t*>(d + o_dist2) : nullptr,
-                                                          reinterpret_cast<const uint32_t*>(d + o_path), reinterpret_cast<const uint32_t*>(d + o_plen),
-                                                          path_status ? d + o_pst : nullptr, n_paths, prm, &o,
-                                                          counts ? reinterpret_cast<uint64_t*>(d) : nullptr)
-                                 : SVO_OK;
-  if (e == hipSuccess && !rc) {
-    if (out->way) e = hipMemcpyAsync(out->way, o.way, b_way, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out->way_index) e = hipMemcpyAsync(out->way_index, o.way_index, b_way, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out->way_len) e = hipMemcpyAsync(out->way_len, o.way_len, 4 * np, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out->way_status) e = hipMemcpyAsync(out->way_status, o.way_status, np, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out->length) e = hipMemcpyAsync(out->length, o.length, 8 * np, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && counts) e = hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, st);
-  }
-  const hipError_t e2 = hipStreamSynchronize(st);
+  const int rc = svo_host_call(
+      ctx, "grid_waypoints", e,
+      [&] {
+        return svo_grid_waypoints_dev(ctx, d.at(o_blocked), dist2 ? d.at<uint32_t>(o_dist2) : nullptr, d.at<uint32_t>(o_path), d.at<uint32_t>(o_plen),
+                                      path_status ? d.at(o_pst) : nullptr, n_paths, prm, &o, counts ? d.at<uint64_t>(o_counts) : nullptr);
+      },
+      [&] {
+        hipError_t e = hipSuccess;
+        if (out->way) e = hipMemcpyAsync(out->way, o.way, b_way, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out->way_index) e = hipMemcpyAsync(out->way_index, o.way_index, b_way, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out->way_len) e = hipMemcpyAsync(out->way_len, o.way_len, 4 * np, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out->way_status) e = hipMemcpyAsync(out->way_status, o.way_status, np, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out->length) e = hipMemcpyAsync(out->length, o.length, 8 * np, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && counts) e = hipMemcpyAsync(c, d.at(o_counts), sizeof(c), hipMemcpyDeviceToHost, st);
+        return e;
+      });
   if (rc) return rc;
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) { ctx->err = std::string("grid_waypoints: ") + hipGetErrorString(e); return SVO_ERR_HIP; }
   if (counts) for (int k = 0; k < 8; ++k) counts[k] = c[k];
   return SVO_OK;
 }

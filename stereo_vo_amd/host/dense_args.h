@@ -1,18 +1,17 @@
 // The dense keyframe chain's host logic that needs no GPU (include/svo.h, "dense depth clouds" .. "semi-global matching"; DESIGN
 // §7b-§7e): the constants the host and the kernels share, the argument rules of the StereoBM, cloud, speckle, left-right and SGM
 // entries, their buffer sizes and launch geometry, and the sizes of a pipeline's keyframe clouds.  A refusal is SVO_ERR_INVALID
-// with *err set to the message; the .hip files and host/keyframe_clouds.cpp store it in the context (DENSE_CHECK) and keep no
+// with *err set to the message; the .hip files and host/keyframe_clouds.cpp store it in the context (SVO_ARGS_CHECK) and keep no
 // second copy of anything here.  tests/sanitize/dense_args_test.cpp walks every rule at its boundary on a CPU.
 #ifndef SVO_DENSE_ARGS_H_
 #define SVO_DENSE_ARGS_H_
 #include <stddef.h>
 #include <stdint.h>
 
+#include "host_call.h"
 #include "svo.h"
 
 #define DENSE_REFUSE(cond, msg) do { if (!(cond)) { *err = (msg); return SVO_ERR_INVALID; } } while (0)
-// How an entry stores a refusal in its context: `call` is one of the checks below with `&err` as its last argument.
-#define DENSE_CHECK(ctx, call) do { const char* err = nullptr; if (call) { (ctx)->err = err; return SVO_ERR_INVALID; } } while (0)
 
 inline int dense_div_up(int a, int b) { return (a + b - 1) / b; }
 
@@ -203,12 +202,14 @@ inline int sgm_path_groups(int dir, const SgmRect& r, int lps) { return dense_di
 // svo_stereo_sgm's single allocation: the workspace, then the two tight images, the map and the cost map of one pair of px pixels.
 struct SgmOneShot { size_t left, right, disp, cost, total; };
 inline SgmOneShot sgm_one_shot(size_t workspace_bytes, size_t px) {
+  SvoParts parts;
+  (void)parts.add(workspace_bytes);  // the workspace comes first, at 0
   SgmOneShot o;
-  o.left = workspace_bytes;
-  o.right = o.left + sgm_up(px);
-  o.disp = o.right + sgm_up(px);
-  o.cost = o.disp + sgm_up(2 * px);
-  o.total = o.cost + sgm_up(2 * px);
+  o.left = parts.add(px);
+  o.right = parts.add(px);
+  o.disp = parts.add(2 * px);
+  o.cost = parts.add(2 * px);
+  o.total = parts.total();
   return o;
 }
 

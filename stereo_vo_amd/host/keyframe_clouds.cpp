@@ -51,7 +51,7 @@ int svo_kfc_create(svo_ctx* ctx, const svo_cloud_params* params, int W, int H, i
   *out = nullptr;
   svo_use_device(ctx);
   svo_cloud_params prm;
-  DENSE_CHECK(ctx, kfc_resolve(params, W, H, max_kf, ctx->lim.max_batch, &prm, &max_kf, &err));
+  SVO_ARGS_CHECK(ctx, kfc_resolve(params, W, H, max_kf, ctx->lim.max_batch, &prm, &max_kf, &err));
   SvoKfClouds* k = new (std::nothrow) SvoKfClouds();
   if (!k) return SVO_ERR_HIP;
   k->ctx = ctx; k->prm = prm; k->W = W; k->H = H; k->max_kf = max_kf;
@@ -103,17 +103,17 @@ static int kfc_switch(SvoKfClouds* k, KfcStage<P>& s, const P* prm, size_t bytes
 }
 
 int svo_kfc_set_speckle(SvoKfClouds* k, const svo_speckle_params* prm) {
-  if (prm) DENSE_CHECK(k->ctx, speckle_check(k->W, k->H, k->max_kf, prm, &err));
+  if (prm) SVO_ARGS_CHECK(k->ctx, speckle_check(k->W, k->H, k->max_kf, prm, &err));
   return kfc_switch(k, k->speckle, prm, speckle_workspace_bytes(k->W, k->H, k->max_kf), "set_keyframe_speckle_filter: allocation failed: ");
 }
 
 int svo_kfc_set_lr_check(SvoKfClouds* k, const svo_lr_check_params* prm) {
-  if (prm) DENSE_CHECK(k->ctx, lr_check_check(k->W, k->H, k->max_kf, prm, &err));
+  if (prm) SVO_ARGS_CHECK(k->ctx, lr_check_check(k->W, k->H, k->max_kf, prm, &err));
   return kfc_switch(k, k->lr, prm, kfc_cost_bytes(k->W, k->H, k->max_kf), "set_keyframe_lr_check: allocation failed: ");
 }
 
 int svo_kfc_set_sgm(SvoKfClouds* k, const svo_sgm_params* prm) {
-  if (prm) DENSE_CHECK(k->ctx, sgm_check(k->W, k->H, KF_NDISP, KF_BLOCK, SVO_SGM_KEYFRAME_SUB_BATCH, prm, &err));
+  if (prm) SVO_ARGS_CHECK(k->ctx, sgm_check(k->W, k->H, KF_NDISP, KF_BLOCK, SVO_SGM_KEYFRAME_SUB_BATCH, prm, &err));
   return kfc_switch(k, k->sgm, prm, sgm_workspace_bytes(k->W, k->H, KF_NDISP, KF_BLOCK, SVO_SGM_KEYFRAME_SUB_BATCH),
                     "set_keyframe_sgm: allocation failed: ");
 }
@@ -144,7 +144,7 @@ int svo_kfc_run(SvoKfClouds* k, const svo_camera_info* cam, const SvoCloudPair* 
   }
   svo_cloud_params one{};
   one.step = 1; one.max_points = 1;
-  DENSE_CHECK(ctx, cloud_check(k->W, k->H, k->W, cam, &one, ctx->lim.max_width, ctx->lim.max_height, &err));
+  SVO_ARGS_CHECK(ctx, cloud_check(k->W, k->H, k->W, cam, &one, ctx->lim.max_width, ctx->lim.max_height, &err));
   int rc = SVO_OK;
   hipStream_t st = ctx->stream;
   SvoCloudPair* h_tab = static_cast<SvoCloudPair*>(k->h_pinned);

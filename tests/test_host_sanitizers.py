@@ -150,6 +150,15 @@ def test_ba_plan_sizes_forms_budget_and_raised_k_match_a_restatement(tmp_path):
     _run_sanitized(tmp_path, "ba_plan_test", "ba plan ok")
 
 
+def test_host_call_order_rule_and_parts_carver_match_a_restatement(tmp_path):
+    """What every synchronous entry shares (host/host_call.h), walked on the CPU under ASan + UBSan with a fake error type: all 16
+    combinations of {the copies up fail, the _dev entry refuses, the copies back fail, the drain fails} against a restatement of the
+    rule (which callables ran and in what order, the drain exactly once and last, the returned code, the reported error), a refusal's
+    way into the context, and the parts carver (offsets multiples of 256, parts disjoint and in order, empty parts take no room, the
+    total at least the parts' sum, sizes up to 2^40)."""
+    _run_sanitized(tmp_path, "host_call_test", "host call ok")
+
+
 def _det_trig_inputs():
     """rvecs (n, 3) f64 and matrices (m, 9) f32 at every branch of host/det_trig.h."""
     F, eps = np.float32, np.float32(2.0 ** -52)                         # cv::Rodrigues' small-angle threshold DBL_EPSILON is a float, too
